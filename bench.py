@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- MCMC proposal steps/s of the HIP likelihood inner loop on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          # N > 1: spawns its own N ranks (one per GPU)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]   # N > 1: spawns its own N ranks (one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Workload (BASELINE.json configs[2], the one the metric is quoted on): 1 000 synthetic events x 64 stations
@@ -18,11 +18,17 @@ the timed region starts; the region is bracketed by a barrier + device synchroni
 
 Besides the driver contract the JSON line carries
   roofline          the dominant kernel of the timed region (k_mcmc), HIP events on its stream; peak = 8 TB/s
+and, with --full only (each takes runs of its own after the timed region):
   roofline_batch64  the full-evaluation kernel on its own (64 stacked models per launch)            [N = 1]
   stages            the two stages of an iteration timed separately on the two-kernel path           [N = 1]
   cpu_baseline      the compiled reference (oracle/_ref; else the C restatement) timed on the host cores of
                     this box on a bounded sample of the same workload: all chains of the job spread over
-                    min(chains, cores) MPI ranks, plus the one-core figure
+                    min(chains, cores) MPI ranks, plus the one-core figure (not with --no-cpu-baseline)
+
+--dump-outputs DIR writes what the timed path left after its last step, the arrays a caller of ChainSet.run gets
+back, as DIR/<name>.npy (float64): every chain's model (hypo, t_corr, vs, a_corr, qs), temperature, log-likelihood
+and proposal / acceptance counters, chains in job order, and each rank's random-stream state.  The inputs are
+seeded, so two builds run with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -40,6 +46,7 @@ sys.path.insert(0, ROOT)
 N_EVENTS, N_STA, N_CHAINS, SEED = 1000, 64, 8, 1
 ITERS_PER_STEP = 65536     # 20 timed steps = 1.3 M iterations: several seconds of the persistent kernel (the driver's GPU sampler sees it)
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def algorithmic_bytes(E, S, w=8):
@@ -151,6 +158,36 @@ def cpu_baseline(params, data, total_chains, seconds_target=10.0):
 
 
 # ---------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ---------------------------------------------------------------------------------------------------
+def rank_outputs(src, n_chains):
+    """What the timed path hands a caller of one rank's chain set after its last step (ChainSet.state of every chain,
+    ChainSet.rng_state), in float64: the counters and the stream's 32-bit words are exact in it."""
+    import numpy as np
+
+    st = [src.state(c) for c in range(n_chains)]
+    out = {k: np.array([getattr(s, k) for s in st], dtype=np.float64)
+           for k in ("hypo", "t_corr", "vs", "a_corr", "qs", "temp", "log_likelihood", "n_propose", "n_accept")}
+    out["rng_state"] = np.array([src.rng_state()], dtype=np.float64)
+    return out
+
+
+def dump_outputs(directory, arrays, limit=DUMP_LIMIT_BYTES):
+    """DIR/<name>.npy per array; should the whole exceed `limit`, an array above its equal share of it is replaced by a
+    fixed, seeded sample of its elements (flattened, in index order)."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    share = (limit - 4096 * len(arrays)) // len(arrays)         # room for the .npy headers
+    too_big = sum(a.nbytes for a in arrays.values()) > limit - 4096 * len(arrays)
+    for name, a in arrays.items():
+        if too_big and a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+# ---------------------------------------------------------------------------------------------------
 # launcher: `python bench.py --gpus N` (N > 1) starts its own ranks -- the reference is launched as
 # `mpirun -np N` (README.md:62-66); here one rank per GPU under torch.distributed.run
 # ---------------------------------------------------------------------------------------------------
@@ -178,7 +215,12 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--iters-per-step", type=int, default=ITERS_PER_STEP,
                     help="main-loop iterations per bench step (default %(default)s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures that take runs of their own after the timed region: stages, roofline_batch64 "
+                         "and cpu_baseline (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the timed path's outputs after its last step as DIR/<name>.npy (see the module docstring)")
     ap.add_argument("--chains", type=int, default=N_CHAINS)
     ap.add_argument("--events", type=int, default=N_EVENTS)
     ap.add_argument("--stations", type=int, default=N_STA)
@@ -307,6 +349,16 @@ def main(argv=None):
         dt = max(rank_dts)
     done = eng.iterations_done if test_engine else cs.iterations_done
     assert done == n_warm + n_timed, (done, n_warm + n_timed)
+    if args.dump_outputs:
+        arrays = rank_outputs(eng if test_engine else cs, nc)
+        if dist is not None:
+            import numpy as np
+
+            parts = [None] * world
+            dist.all_gather_object(parts, arrays)
+            arrays = {k: np.concatenate([p[k] for p in parts]) for k in arrays}     # chains and streams in rank order
+        if rank == 0:
+            dump_outputs(args.dump_outputs, arrays)
 
     value = world * nc * n_timed / dt
     b_full, b_part = algorithmic_bytes(E, S, 4 if args.forward_precision == "fp32" else 8)
@@ -400,10 +452,10 @@ def main(argv=None):
                     "(SURVEY 8d) x the evaluations counted on the device in the timed region (rank 0's GPU), / the HIP-event "
                     "time of that region on the kernels' stream.  At a few chains per GPU an iteration is a dependent chain "
                     "of a few us whose data (observations, chain state) stays in L2 / Infinity Cache: the workload is bound by "
-                    "instruction issue and latency on the master's CU, not by HBM (DESIGN.md 5); see roofline_batch64 for the "
+                    "instruction issue and latency on the master's CU, not by HBM (DESIGN.md 5); see roofline_batch64 (--full) for the "
                     "full-evaluation kernel on its own",
         }
-    if rank == 0 and world == 1 and not args.force_lockstep and not test_engine:
+    if args.full and rank == 0 and world == 1 and not args.force_lockstep and not test_engine:
         # ---- the two stages timed separately (fallback two-kernel path, same arithmetic), HIP events per launch
         n_prof = 2000
         prof = cs.profile(n_prof)
@@ -446,7 +498,7 @@ def main(argv=None):
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0 and not args.no_cpu_baseline and not test_engine:
+    if args.full and rank == 0 and not args.no_cpu_baseline and not test_engine:
         try:
             out["cpu_baseline"] = cpu_baseline(params, data, world * nc)
         except Exception as exc:           # the baseline is a side figure: never lose the measurement over it

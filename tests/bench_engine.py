@@ -2,6 +2,7 @@
 by the CPU oracle's lock-step mode and exchanged over gloo, so that `python bench.py --gpus N` -- launcher,
 rendezvous, barrier/timing protocol, JSON contract -- can be exercised on a box without a GPU.  Test
 infrastructure only; bench.py marks such a line as a test double."""
+from hypotremormcmc_amd.chains import ChainState
 from oracle import oracle
 
 from tests.helpers import OracleRank
@@ -26,6 +27,14 @@ class _Engine:
 
     def sync(self):
         pass
+
+    def state(self, chain):
+        st = self.job.chain(self.rank, chain)
+        st["log_likelihood"] = st.pop("loglik")
+        return ChainState(**st)
+
+    def rng_state(self):
+        return self.job.rng_state(self.rank)
 
 
 def make(params, data, rank, world):

@@ -96,7 +96,12 @@ def test_unmodified_reference_driver_on_hip_forward_shim(tmp_path):
     params = dict(params, n_iter="4000", n_burn="2000")
     synth.write_dataset(str(tmp_path), data)
     synth.write_param_file(str(tmp_path / "run.in"), **params)
-    r = subprocess.run([mpiexec, "-np", "2", exe, "run.in"], cwd=tmp_path, timeout=900, capture_output=True, text=True)
+    # oracle/_ref is a build product that may reach this tree through a link, where its $ORIGIN run path no longer
+    # leads here: the shim's library is this tree's, named explicitly (mpiexec hands the environment to the ranks)
+    lib = os.path.join(ROOT, "hypotremormcmc_amd", "lib")
+    env = dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(p for p in (lib, os.environ.get("LD_LIBRARY_PATH")) if p))
+    r = subprocess.run([mpiexec, "-np", "2", exe, "run.in"], cwd=tmp_path, timeout=900, capture_output=True, text=True,
+                       env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     for rank in range(2):
         it, v = _records(tmp_path / ("likelihood%02d.out" % rank), 1)

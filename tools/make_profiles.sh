@@ -9,23 +9,23 @@ OUT=$ROOT/gpurun_out
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 rm -rf "$OUT/prof_${TAG}_stats" "$OUT/prof_${TAG}_fetch" "$OUT/prof_${TAG}_write"
-rocprofv3 --kernel-trace --stats -d "$OUT/prof_${TAG}_stats" -o st --output-format csv -- python3 "$ROOT/bench.py" --no-cpu-baseline \
+rocprofv3 --kernel-trace --stats -d "$OUT/prof_${TAG}_stats" -o st --output-format csv -- python3 "$ROOT/bench.py" --full --no-cpu-baseline \
     > "$OUT/${TAG}_bench_under_rocprof.json" 2> "$OUT/prof_${TAG}_stats.log"
 echo "stats pass done"
-rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/prof_${TAG}_fetch" -o pf --output-format csv -- python3 "$ROOT/bench.py" --steps 4 --warmup 1 --iters-per-step 1024 --no-cpu-baseline \
+rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/prof_${TAG}_fetch" -o pf --output-format csv -- python3 "$ROOT/bench.py" --full --steps 4 --warmup 1 --iters-per-step 1024 --no-cpu-baseline \
     > /dev/null 2> "$OUT/prof_${TAG}_fetch.log"
 echo "fetch pass done"
-rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/prof_${TAG}_write" -o pw --output-format csv -- python3 "$ROOT/bench.py" --steps 4 --warmup 1 --iters-per-step 1024 --no-cpu-baseline \
+rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/prof_${TAG}_write" -o pw --output-format csv -- python3 "$ROOT/bench.py" --full --steps 4 --warmup 1 --iters-per-step 1024 --no-cpu-baseline \
     > /dev/null 2> "$OUT/prof_${TAG}_write.log"
 echo "write pass done"
-python3 "$ROOT/bench.py" > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+python3 "$ROOT/bench.py" --full > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
 python3 - "$OUT" "$TAG" <<'PY'
 import csv, glob, os, sys, collections
 out, tag = sys.argv[1], sys.argv[2]
 st = glob.glob(os.path.join(out, f"prof_{tag}_stats", "**", "*kernel_stats.csv"), recursive=True)
 if st:
     open(os.path.join(out, f"{tag}_kernel_stats.csv"), "w").write(open(st[0]).read())
-lines = [f"# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) --kernel-trace -- python3 bench.py --steps 4 --warmup 1 --iters-per-step 1024 --no-cpu-baseline",
+lines = [f"# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) --kernel-trace -- python3 bench.py --full --steps 4 --warmup 1 --iters-per-step 1024 --no-cpu-baseline",
          "# per dispatch, KB as rocprofv3 reports them (raw; gfx950: FETCH_SIZE counts 64 B per 128-B request of wide coalesced reads)",
          "%-34s %-11s %7s %14s %12s %14s" % ("kernel", "counter", "count", "mean", "min", "max")]
 for sub, cname in (("fetch", "FETCH_SIZE"), ("write", "WRITE_SIZE")):
@@ -46,7 +46,7 @@ try:
     b = _j.load(open(os.path.join(out, f"{tag}_bench_under_rocprof.json")))["roofline"]
     dur = [(int(x["End_Timestamp"]) - int(x["Start_Timestamp"])) / 1e6 for x in csv.DictReader(open(tr[0])) if "k_mcmc" in x["Kernel_Name"]]
     open(os.path.join(out, f"{tag}_kernel_launches.txt"), "w").write(
-        "# k_mcmc launches of `rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline` (ms, in launch order)\n"
+        "# k_mcmc launches of `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline` (ms, in launch order)\n"
         "# the first launches are the untimed warm-up, the last %d the timed region\n" % b["launches"] +
         " ".join("%.3f" % x for x in dur) + "\n" +
         "timed launches, rocprofv3 trace: %.3f ms   bench.py (HIP events on the kernels' stream, same run): %.3f ms\n"
@@ -66,7 +66,7 @@ for sub, cname in (("fetch", "FETCH_SIZE"), ("write", "WRITE_SIZE")):
     tot[sub] = sum(v)
     nl = len(v)
 iters = 5 * 1024
-json.dump({"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace), python3 bench.py --steps 4 --warmup 1 --iters-per-step 1024 --no-cpu-baseline",
+json.dump({"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace), python3 bench.py --full --steps 4 --warmup 1 --iters-per-step 1024 --no-cpu-baseline",
            "kernel": "htm::k_mcmc (the launches of the run)", "iterations": iters, "launches": nl,
            "fetch_kb_raw_total": tot["fetch"], "write_kb_total": tot["write"],
            "fetch_bytes_per_iteration_raw": tot["fetch"] * 1024 / iters, "write_bytes_per_iteration": tot["write"] * 1024 / iters,

@@ -4,7 +4,7 @@
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$ROOT"
 row() {
-  timeout -k 10 120 python bench.py --no-cpu-baseline "$@" 2>/dev/null | python -c "
+  timeout -k 10 120 python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 r=d['roofline']; b=d.get('roofline_batch64',{})
