@@ -11,6 +11,9 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HTM_LIB") or os.path.join(_HERE, "lib", "libhtm_hip.so")   # HTM_LIB: A/B builds
 
+# most chains one rank holds: HTM_MAX_CHAINS of include/htm_hip.h (tests/test_wide_chains_limit.py keeps the two equal)
+HTM_MAX_CHAINS = 64
+
 dp = C.POINTER(C.c_double)
 ip = C.POINTER(C.c_int32)
 up = C.POINTER(C.c_uint32)

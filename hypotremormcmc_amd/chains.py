@@ -40,6 +40,8 @@ class ChainSet:
     def __init__(self, fwd: Forward, models, temps, rng_state, *, n_procs=1, rank=0, solve_vs=True,
                  solve_t_corr=True, solve_qs=True, solve_a_corr=True, n_burn=0, n_interval=1,
                  lik_capacity=0, sample_capacity=0):
+        if len(models) > _lib.HTM_MAX_CHAINS:
+            raise ValueError(f"{len(models)} chains on one rank: at most {_lib.HTM_MAX_CHAINS} (HTM_MAX_CHAINS)")
         self._lib = _lib.load()
         self.fwd = fwd
         self.n_chains = len(models)

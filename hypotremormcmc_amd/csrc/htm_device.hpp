@@ -21,6 +21,7 @@ constexpr double kPi2 = 6.283185307179586;       // 2.d0 * acos(-1.d0)   (mod_ra
 constexpr double kFreq = 5.0;                    // cls_forward.f90:190
 constexpr double kEps = 2.220446049250313e-16;   // epsilon(1.d0)
 constexpr int kMaxChains = 32;                   // chains per rank held by one k_step workgroup
+constexpr int kMaxWideChains = 64;               // ... by the wide instantiations of the barrier loop (33..64 chains: htm_step.hpp)
 
 // ---------------------------------------------------------------------------------------------------
 // wave-level fp64 sum over 64 lanes, DPP only (no LDS traffic, fixed order => deterministic)
@@ -664,7 +665,7 @@ struct FullEntry {
 };
 struct FullDesc {
     int n, pad0, pad1, pad2;      // number of entries; 0 = nothing pending
-    FullEntry e[kMaxChains];
+    FullEntry e[kMaxWideChains];
 };
 
 // Hand-shake words between the chain master (block 0) and the full-evaluation workers (blocks 1..W) of one

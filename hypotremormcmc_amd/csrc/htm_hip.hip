@@ -168,6 +168,7 @@ struct htm_chains {
     unsigned long long launch_seq = 0;         // k_mcmc launches of this chain set so far (the kernels' launch index)
     bool persist = true;                       // k_mcmc (master + resident full-evaluation workers) vs k_step + k_full
     bool flow = false;                         // single-rank loop on the free-running master (htm_flow.hpp) instead of step_body
+    bool wide = false;                         // more than kMaxChains chains: the loop with barriers at kMaxWideChains (k_mcmc_wide, k_step_wide)
     int worker_cap = 250;                      // most worker blocks a launch takes (HTM_WORKER_CAP)
     long blocks_fit = 0;                       // resident blocks of a k_mcmc launch on this device (htm_chains_share_gpu)
     bool flow_lock = false;                    // lock-step ranks (MODE_LOCKRUN) on the free-running master too
@@ -245,7 +246,22 @@ int launch_mcmc(htm_chains *hc, int mode, int target, const double *gathered)
         else HTM_LAUNCH_MCMC(0, false, K);                                                                 \
     } while (0)
     // one instantiation per main loop: the single-rank loop, one lock-step iteration per launch, persistent lock-step
-    if (mode == MODE_RUN && hc->pipe) {
+    if (hc->wide) {
+#define HTM_LAUNCH_WIDE(N, F, K) hipLaunchKernelGGL((k_mcmc_wide<N, F, K>), grid, block, hc->step_smem, h->stream, h->dev, hc->dev, mode, target, gathered, hc->ring_size, hc->wmax, seq)
+#define HTM_LAUNCH_WIDE_K(K)                                                                              \
+    do {                                                                                                   \
+        if (h->dev.fp32) { if (h->nch == 1) HTM_LAUNCH_WIDE(1, true, K); else HTM_LAUNCH_WIDE(2, true, K); } \
+        else if (h->nch == 1) HTM_LAUNCH_WIDE(1, false, K);                                                \
+        else if (h->nch == 2) HTM_LAUNCH_WIDE(2, false, K);                                                \
+        else HTM_LAUNCH_WIDE(0, false, K);                                                                 \
+    } while (0)
+        if (mode == MODE_RUN) HTM_LAUNCH_WIDE_K(0);
+        else if (mode == MODE_LOCKRUN) HTM_LAUNCH_WIDE_K(2);
+        else HTM_LAUNCH_WIDE_K(1);
+#undef HTM_LAUNCH_WIDE_K
+#undef HTM_LAUNCH_WIDE
+    }
+    else if (mode == MODE_RUN && hc->pipe) {
         // the pipelined master (htm_pipe.hpp): one or two stations per lane only
 #define HTM_LAUNCH_PIPE(N, F) hipLaunchKernelGGL((k_mcmc<N, F, 5>), grid, dim3(mcmc_threads<N, 5>()), hc->pipe_smem, h->stream, h->dev, hc->dev, mode, target, gathered, hc->pipe_ring, hc->wmax, seq)
         if (h->dev.fp32) { if (h->nch == 1) HTM_LAUNCH_PIPE(1, true); else HTM_LAUNCH_PIPE(2, true); }
@@ -283,6 +299,17 @@ int launch_step(htm_chains *hc, int mode, int target, const double *gathered)
     htm_forward *h = hc->fwd;
     hc->ctrl_fresh = false;
     dim3 grid(1), block(64 * hc->nw);
+    if (hc->wide) {
+        const size_t sm = hc->step_smem;
+        if (h->dev.fp32) {
+            if (h->nch == 1) hipLaunchKernelGGL((k_step_wide<1, true>), grid, block, sm, h->stream, h->dev, hc->dev_np, mode, target, gathered, hc->ring_size, hc->wmax);
+            else hipLaunchKernelGGL((k_step_wide<2, true>), grid, block, sm, h->stream, h->dev, hc->dev_np, mode, target, gathered, hc->ring_size, hc->wmax);
+        } else if (h->nch == 1) hipLaunchKernelGGL(k_step_wide<1>, grid, block, sm, h->stream, h->dev, hc->dev_np, mode, target, gathered, hc->ring_size, hc->wmax);
+        else if (h->nch == 2) hipLaunchKernelGGL(k_step_wide<2>, grid, block, sm, h->stream, h->dev, hc->dev_np, mode, target, gathered, hc->ring_size, hc->wmax);
+        else hipLaunchKernelGGL(k_step_wide<0>, grid, block, sm, h->stream, h->dev, hc->dev_np, mode, target, gathered, hc->ring_size, hc->wmax);
+        HIPCHK(hipGetLastError());
+        return HTM_OK;
+    }
     if (h->dev.fp32) {
         if (h->nch == 1) hipLaunchKernelGGL((k_step<1, true>), grid, block, hc->step_smem, h->stream, h->dev, hc->dev_np, mode, target, gathered, hc->ring_size, hc->wmax);
         else hipLaunchKernelGGL((k_step<2, true>), grid, block, hc->step_smem, h->stream, h->dev, hc->dev_np, mode, target, gathered, hc->ring_size, hc->wmax);
@@ -732,7 +759,8 @@ int htm_chains_create(htm_forward *h, const htm_chains_init *init, htm_chains **
     *out = nullptr;
     if (!h || !init) return fail(HTM_EINVAL, "NULL argument");
     const int nc = init->n_chains;
-    if (nc < 1 || nc > kMaxChains) return fail(HTM_EINVAL, "n_chains must be in 1..%d", kMaxChains);
+    static_assert(HTM_MAX_CHAINS == kMaxWideChains, "include/htm_hip.h and htm_device.hpp disagree on the chain limit");
+    if (nc < 1 || nc > HTM_MAX_CHAINS) return fail(HTM_EINVAL, "n_chains must be in 1..%d (HTM_MAX_CHAINS), got %d", HTM_MAX_CHAINS, nc);
     if (init->n_procs < 1 || init->rank < 0 || init->rank >= init->n_procs) return fail(HTM_EINVAL, "bad rank/n_procs");
     if (init->n_interval < 1) return fail(HTM_EINVAL, "n_interval must be >= 1");
     if (!init->temp) return fail(HTM_EINVAL, "temp is NULL");
@@ -742,6 +770,7 @@ int htm_chains_create(htm_forward *h, const htm_chains_init *init, htm_chains **
     HIPCHK(hipSetDevice(h->device));
     htm_chains *hc = new htm_chains();
     hc->fwd = h;
+    hc->wide = nc > kMaxChains;
     auto cleanup = [&](int code) { htm_chains_destroy(hc); return code; };
     int rc;
     ChainsDev &d = hc->dev;
@@ -821,7 +850,7 @@ int htm_chains_create(htm_forward *h, const htm_chains_init *init, htm_chains **
             return std::max(lo, std::min(hi, v));
         };
         d.slot_rep = env_int("HTM_SLOT_REPLICAS", 1, 1, kMaxSlotReplicas);
-        d.slot_stride = env_int("HTM_SLOT_STRIDE", 4096, kMaxChains * kGranPerSlot * 8, 1 << 22) / 8;     // bytes -> words
+        d.slot_stride = env_int("HTM_SLOT_STRIDE", 4096, std::max(nc, kMaxChains) * kGranPerSlot * 8, 1 << 22) / 8;     // bytes -> words
         d.pgran_stride = env_int("HTM_PGRAN_STRIDE", 16, 16, 4096) / 8;
         d.npoll = env_int("HTM_NPOLL", 1, 1, 3);
     }
@@ -928,7 +957,9 @@ int htm_chains_create(htm_forward *h, const htm_chains_init *init, htm_chains **
     // iterations ahead), else one -- and the mirror of (vs, t_corr, qs, a_corr) x all chains + their step sizes that
     // role P reads (without it no orders are sent ahead).  Per ring position: U, LOGU, pg, pr, plogr (5 doubles), dec,
     // sw (int4), hop (kHops ints).
-    const size_t lds_fixed = ((sizeof(FlowShared) + 15) & ~size_t(15)) + 3 * (size_t)h->S * sizeof(double) + kGathStage * sizeof(double);
+    // (the wide kernels' LDS layout is step_body's at kMaxWideChains; every narrow loop shares FlowShared's)
+    const size_t shared_bytes = hc->wide ? sizeof(StepSharedT<kMaxWideChains>) : sizeof(FlowShared);
+    const size_t lds_fixed = ((shared_bytes + 15) & ~size_t(15)) + 3 * (size_t)h->S * sizeof(double) + kGathStage * sizeof(double);
     const size_t lds_pos = 5 * sizeof(double) + 2 * sizeof(int4) + kHops * sizeof(int);
     const size_t mir = 2 * (size_t)nc + 2 * (size_t)nc * h->S;
     const size_t lds_cap = 156 * 1024;
@@ -965,10 +996,16 @@ int htm_chains_create(htm_forward *h, const htm_chains_init *init, htm_chains **
         mb_want = false;      // (the longer ring does not fit beside the mirror: one workgroup, the usual ring)
     }
     hc->step_smem = lds_fixed + (size_t)hc->ring_size * lds_pos + (1 + hc->dev.mirror_steps) * (size_t)hc->dev.mirror_n * sizeof(double);
+    if (hc->step_smem > lds_cap && hc->wide)
+        return cleanup(fail(HTM_EINVAL, "%d chains x %d stations: the loop with barriers needs %zu B of LDS, more than the %zu B budget", nc, h->S,
+                            hc->step_smem, lds_cap));
     if (hc->step_smem > lds_cap) return cleanup(fail(HTM_EINVAL, "n_chains / n_sta too large for k_step's LDS budget"));
     if (hc->step_smem > 48 * 1024) {
         const void *fn = h->dev.fp32 ? (h->nch == 1 ? (const void *)k_step<1, true> : (const void *)k_step<2, true>)
                          : h->nch == 1 ? (const void *)k_step<1> : h->nch == 2 ? (const void *)k_step<2> : (const void *)k_step<0>;
+        if (hc->wide)
+            fn = h->dev.fp32 ? (h->nch == 1 ? (const void *)k_step_wide<1, true> : (const void *)k_step_wide<2, true>)
+                 : h->nch == 1 ? (const void *)k_step_wide<1> : h->nch == 2 ? (const void *)k_step_wide<2> : (const void *)k_step_wide<0>;
         HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hc->step_smem));
     }
     if (hipEventCreateWithFlags(&hc->ev_wd, hipEventDisableTiming) != hipSuccess) return cleanup(fail(HTM_EHIP, "hipEventCreate failed"));
@@ -982,11 +1019,16 @@ int htm_chains_create(htm_forward *h, const htm_chains_init *init, htm_chains **
         // block carries the master's LDS size).  Workers take events round-robin, so fewer of them only take longer.
 #define HTM_MCMC_FN(K) (h->dev.fp32 ? (h->nch == 1 ? (const void *)k_mcmc<1, true, K> : (const void *)k_mcmc<2, true, K>)                  \
                         : h->nch == 1 ? (const void *)k_mcmc<1, false, K> : h->nch == 2 ? (const void *)k_mcmc<2, false, K> : (const void *)k_mcmc<0, false, K>)
-        std::vector<const void *> fns = {HTM_MCMC_FN(0), HTM_MCMC_FN(1), HTM_MCMC_FN(2), HTM_MCMC_FN(3), HTM_MCMC_FN(4)};
+#define HTM_MCMC_WIDE_FN(K) (h->dev.fp32 ? (h->nch == 1 ? (const void *)k_mcmc_wide<1, true, K> : (const void *)k_mcmc_wide<2, true, K>)                  \
+                             : h->nch == 1 ? (const void *)k_mcmc_wide<1, false, K> : h->nch == 2 ? (const void *)k_mcmc_wide<2, false, K> : (const void *)k_mcmc_wide<0, false, K>)
+        std::vector<const void *> fns;
+        if (hc->wide) fns = {HTM_MCMC_WIDE_FN(0), HTM_MCMC_WIDE_FN(1), HTM_MCMC_WIDE_FN(2)};
+        else fns = {HTM_MCMC_FN(0), HTM_MCMC_FN(1), HTM_MCMC_FN(2), HTM_MCMC_FN(3), HTM_MCMC_FN(4)};
+#undef HTM_MCMC_WIDE_FN
 #undef HTM_MCMC_FN
         // (several master workgroups, k_mcmc<.., 7>: one or two stations per lane)
-        if (h->nch == 1) fns.push_back(h->dev.fp32 ? (const void *)k_mcmc<1, true, 7> : (const void *)k_mcmc<1, false, 7>);
-        else if (h->nch == 2) fns.push_back(h->dev.fp32 ? (const void *)k_mcmc<2, true, 7> : (const void *)k_mcmc<2, false, 7>);
+        if (!hc->wide && h->nch == 1) fns.push_back(h->dev.fp32 ? (const void *)k_mcmc<1, true, 7> : (const void *)k_mcmc<1, false, 7>);
+        else if (!hc->wide && h->nch == 2) fns.push_back(h->dev.fp32 ? (const void *)k_mcmc<2, true, 7> : (const void *)k_mcmc<2, false, 7>);
         if (hc->step_smem > 48 * 1024)
             for (const void *g : fns) HIPCHK(hipFuncSetAttribute(g, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hc->step_smem));
         // the residency bound holds for whichever main loop gets launched: the smallest of the instantiations' occupancies
@@ -1017,7 +1059,8 @@ int htm_chains_create(htm_forward *h, const htm_chains_init *init, htm_chains **
         // debug switches.
         const char *e = getenv("HTM_FLOW");
         const int wd = 6 * nc + 16, c_max = 8 * ((nc - 1) / 8);
-        const bool window_ok = hc->persist && !(e && e[0] == '0') && d.dbg == 0 && hc->dev.mirror_n > 0 &&
+        // More than kMaxChains chains: the loop with barriers whatever HTM_FLOW / HTM_MB / HTM_PIPE say (hc->wide).
+        const bool window_ok = hc->persist && !hc->wide && !(e && e[0] == '0') && d.dbg == 0 && hc->dev.mirror_n > 0 &&
                                hc->ring_size >= 4 * wd + 32 + 2 * c_max + 16;
         hc->flow = window_ok && d.n_procs == 1;
         // More than eight chains on a rank: a master workgroup for every eight (k_mcmc<.., 7>, htm_flow.hpp MbShared) instead of
@@ -1051,7 +1094,7 @@ int htm_chains_create(htm_forward *h, const htm_chains_init *init, htm_chains **
             // (opt-in, HTM_PIPE=1 / HTM_PIPE_LOCK=1: on one CU it matches the free-running master -- 4.8 us per iteration at 1000 x 64 x 8,
             // +8 % at 16 chains, profiles/r04_pipe_*.txt -- and does not beat it; DESIGN.md 3.6 says what it is for)
             const char *epl = getenv("HTM_PIPE_LOCK");
-            const bool usable = hc->persist && d.dbg == 0 && (h->nch == 1 || h->nch == 2) && smem <= lds_cap &&
+            const bool usable = hc->persist && !hc->wide && d.dbg == 0 && (h->nch == 1 || h->nch == 2) && smem <= lds_cap &&
                                 hc->dev.mirror_n == (int)mirp;      // (the mirror is part of every loop's LDS layout: one size for all)
             hc->pipe = usable && d.n_procs == 1 && ep && ep[0] == '1';
             hc->pipe_lock = usable && epl && epl[0] == '1' &&

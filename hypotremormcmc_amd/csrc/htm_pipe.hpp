@@ -1228,4 +1228,23 @@ __global__ __launch_bounds__((mcmc_threads<NCH, MK>())) void k_mcmc(FwdDev f, Ch
     }
 }
 
+// k_mcmc for 33..64 chains: the loop with barriers only (MK 0 single rank, 1 one lock-step iteration per launch, 2 persistent
+// lock-step), its StepShared and the workers' order polls sized for kMaxWideChains.  The free-running, several-workgroup and
+// pipelined masters keep kMaxChains: their stream windows do not fit the LDS above ~35 chains.
+template <int NCH, bool F32, int MK>
+__global__ __launch_bounds__(512) void k_mcmc_wide(FwdDev f, ChainsDev cs, int mode, int target_arg,
+                                                    const double *gathered, int ring_size, int wmax,
+                                                    unsigned long long launch)
+{
+    static_assert(MK >= 0 && MK <= 2, "the wide kernels run the loop with barriers only");
+    const KArgLayout __attribute__((address_space(4))) &ka = *(const KArgLayout __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+    if (blockIdx.x == 0) {
+        step_body<NCH, true, F32, MK, kMaxWideChains>(ka.f, ka.cs, mode, target_arg, gathered, ring_size, wmax, launch);
+        __syncthreads();
+        if (threadIdx.x == 0) st_agent(&ka.cs.ps->quit, launch + 1ull);
+    } else {
+        worker_body<NCH, F32, 8, false, kMaxWideChains>(ka.f, ka.cs, launch, (int)blockIdx.x - 1);
+    }
+}
+
 }  // namespace htm

@@ -46,23 +46,25 @@ struct KArgLayout { FwdDev f; ChainsDev cs; };
 
 constexpr int kGathStage = 512;   // doubles of LDS for the gathered swap records (else they are read in place)
 
-struct StepShared {
-    Proposal prop[kMaxChains];
-    double temp[kMaxChains], L[kMaxChains];
-    double rtemp[kMaxChains];     // 1 / temperature (the Metropolis ratio multiplies by it), renewed wherever temp is written
-    int start[kMaxChains];        // stream position (relative) at which each chain step started
-    int start_fix[kMaxChains];    // corrected starts for a repeat pass (written by wave 0)
-    int cnt[kMaxChains];          // draws the step consumed (judge draw included iff prior_ok)
-    int slot_l[kMaxChains], slot_s[kMaxChains];
-    int redone[kMaxChains];       // the chain repeated its step in this iteration (undo + new commit: role P stays out)
+template <int CAP>
+struct StepSharedT {
+    static constexpr int kCap = CAP;
+    Proposal prop[CAP];
+    double temp[CAP], L[CAP];
+    double rtemp[CAP];     // 1 / temperature (the Metropolis ratio multiplies by it), renewed wherever temp is written
+    int start[CAP];        // stream position (relative) at which each chain step started
+    int start_fix[CAP];    // corrected starts for a repeat pass (written by wave 0)
+    int cnt[CAP];          // draws the step consumed (judge draw included iff prior_ok)
+    int slot_l[CAP], slot_s[CAP];
+    int redone[CAP];       // the chain repeated its step in this iteration (undo + new commit: role P stays out)
     // role P (k_mcmc): [iteration & 1][chain]: the chain's step of that iteration, starting at position pre_p, already
     // has its order out under pre_tag; pre_mode 1: sent one iteration ahead, 2: two iterations ahead (evaluated on
     // the state before the step in between; see chain_pass)
-    int pre_p[2][kMaxChains];
-    unsigned pre_tag[2][kMaxChains];
-    int pre_mode[2][kMaxChains];
-    int pre_pa[2][kMaxChains];   // two-ahead orders: where the step in between was expected to start
-    int np[kMaxChains * 7], na[kMaxChains * 7];   // proposal / acceptance counters of this launch
+    int pre_p[2][CAP];
+    unsigned pre_tag[2][CAP];
+    int pre_mode[2][CAP];
+    int pre_pa[2][CAP];   // two-ahead orders: where the step in between was expected to start
+    int np[CAP * 7], na[CAP * 7];   // proposal / acceptance counters of this launch
     int sw_do, sw_c1, sw_c2;      // swap decided between the barriers; applied by the waves owning the chains
     double sw_T1, sw_T2;          // new temperatures of chains sw_c1 / sw_c2
     long long origin;             // absolute stream position of relative position 0 (= spos at launch)
@@ -73,7 +75,7 @@ struct StepShared {
     int redo;                     // >= 0: chains >= redo repeat their pass; -1: validated; -2: aborted
     int catchup;                  // written between the barriers: the LDS window must be extended first
     int rolep_iter;               // role P has finished for this iteration (see step_body)
-    double xrec[4 + 2 * kMaxChains];   // MODE_LOCKRUN: this rank's swap record of the iteration (what goes to every rank's inbox)
+    double xrec[4 + 2 * CAP];   // MODE_LOCKRUN: this rank's swap record of the iteration (what goes to every rank's inbox)
     int xdone;                    // MODE_LOCKRUN: the swap of every iteration <= xdone has been applied (see exchange_finish)
     int xstop, xspec;             // decided by role V: this rank asks for a stop; the next iteration starts before the swap is known
     unsigned xctl;                // the control word this rank posted with its latest record (exchange_post; read back by exchange_finish)
@@ -83,6 +85,8 @@ struct StepShared {
     unsigned long long stamp_acc[96];   // diagnostic cycle accounting of this launch, flushed to ChainsDev::stamps at its end
 #endif
 };
+// the narrow loops (htm_flow.hpp, htm_pipe.hpp and step_body up to kMaxChains); step_body at kMaxWideChains: the wide kernels
+using StepShared = StepSharedT<kMaxChains>;
 
 struct Ring {                     // LDS window of the stream rings, index = relative position & mask
     double *U, *LOGU, *pg, *pr, *plogr;
@@ -110,7 +114,8 @@ struct PfRegs {
     int p;                        // relative position, -1: nothing to store
 };
 
-__device__ __forceinline__ void pf_load(PfRegs &r, CsRef cs_, const StepShared &sh, int p, int limit)
+template <int CAP>
+__device__ __forceinline__ void pf_load(PfRegs &r, CsRef cs_, const StepSharedT<CAP> &sh, int p, int limit)
 {
     CsRef cs = rebase(cs_);
     r.p = -1;
@@ -138,7 +143,8 @@ __device__ __forceinline__ void pf_store(const PfRegs &r, const Ring &rg)
 
 // every thread of the workgroup: extend the LDS window to cover relative positions < target
 // (kernel start; later only if a long select_pair redraw run ate the look-ahead)
-__device__ __forceinline__ void prefetch_all(CsRef cs_, StepShared &sh, const Ring &rg, int target)
+template <int CAP>
+__device__ __forceinline__ void prefetch_all(CsRef cs_, StepSharedT<CAP> &sh, const Ring &rg, int target)
 {
     CsRef cs = rebase(cs_);
     if (target > sh.avail) target = sh.avail;
@@ -272,7 +278,8 @@ __device__ __forceinline__ bool metropolis(double L_new, double L_cur, double T,
 // to wait for, and this step may overwrite that very element (role P ruled that out for the step it predicted only).
 // Workers waiting for a value that never shows serve no other order -- every chain would end up waiting for them -- and
 // role P's own stale checks run one iteration too late for that.  The slot holds one order: whatever is on the books goes.
-__device__ __forceinline__ void drop_disproved_orders(CsRef cs, StepShared &sh, int c, int p, int iter, int lane)
+template <int CAP>
+__device__ __forceinline__ void drop_disproved_orders(CsRef cs, StepSharedT<CAP> &sh, int c, int p, int iter, int lane)
 {
     if (__builtin_expect(cs.dbg & 1, 0)) return;     // HTM_DEBUG_NO_DROP=1 (tests: the workers' deferral alone must keep the job alive)
     const int book_a = sh.pre_p[iter & 1][c], book_b = sh.pre_p[(iter + 1) & 1][c];
@@ -296,8 +303,8 @@ __device__ __forceinline__ void drop_disproved_orders(CsRef cs, StepShared &sh, 
 // worker blocks from HERE, by the chain's own wave, as soon as the proposed value is known: the order goes out
 // while the other chain waves are still in their partial updates, so the workers' round trip is hidden behind
 // them.  The wave then collects the workers' partial sums, judges and commits like any other step.
-template <int NCH, bool PERSIST, bool F32, int MK>
-__device__ __forceinline__ int chain_pass(FwRef f_, CsRef cs_, StepShared &sh, const Ring &rg,
+template <int NCH, bool PERSIST, bool F32, int MK, int CAP>
+__device__ __forceinline__ int chain_pass(FwRef f_, CsRef cs_, StepSharedT<CAP> &sh, const Ring &rg,
                                           const double *s_sx, const double *s_sy, const double *s_sz, int c,
                                           int p, int iter, int lane, unsigned long long launch, bool wait_rolep, bool first_pass,
                                           int xwait, int base_used)
@@ -603,7 +610,8 @@ __device__ __forceinline__ int chain_pass(FwRef f_, CsRef cs_, StepShared &sh, c
 }
 
 // lane 0 of the owning wave: take back the speculative effects of chain c's step
-__device__ __forceinline__ void undo_chain(CsRef cs_, StepShared &sh, const Ring &rg, int c)
+template <int CAP>
+__device__ __forceinline__ void undo_chain(CsRef cs_, StepSharedT<CAP> &sh, const Ring &rg, int c)
 {
     CsRef cs = rebase(cs_);
     Proposal &pr = sh.prop[c];
@@ -625,8 +633,8 @@ struct Valid {
     unsigned long long bad, mf;
     int total, base;
 };
-template <bool PERSIST>
-__device__ __forceinline__ Valid validate(const StepShared &sh, int nc, int lane)
+template <bool PERSIST, int CAP>
+__device__ __forceinline__ Valid validate(const StepSharedT<CAP> &sh, int nc, int lane)
 {
     Valid v;
     const bool in = lane < nc;
@@ -640,7 +648,8 @@ __device__ __forceinline__ Valid validate(const StepShared &sh, int nc, int lane
 }
 
 // role R: record slots (hypo_tremor_mcmc.f90:270-280), step log, per-chain part of the swap record
-__device__ __forceinline__ void role_records(CsRef cs_, StepShared &sh, int iter, bool lockstep, int lane, double *rec)
+template <int CAP>
+__device__ __forceinline__ void role_records(CsRef cs_, StepSharedT<CAP> &sh, int iter, bool lockstep, int lane, double *rec)
 {
     CsRef cs = rebase(cs_);
     const int nc = cs.n_chains;
@@ -673,7 +682,8 @@ __device__ __forceinline__ void role_records(CsRef cs_, StepShared &sh, int iter
 
 // role W: the temperature swap of cls_parallel.f90:121-136 + :285-302 (single rank) or the header of this
 // rank's record (lock-step).  Uniform over the wave; lane 0 writes.
-__device__ __forceinline__ void role_swap(CsRef cs_, StepShared &sh, int iter, bool lockstep, int lane,
+template <int CAP>
+__device__ __forceinline__ void role_swap(CsRef cs_, StepSharedT<CAP> &sh, int iter, bool lockstep, int lane,
                                           int i1, int i2, double sr, double slr, double *rec)
 {
     CsRef cs = rebase(cs_);
@@ -692,7 +702,8 @@ __device__ __forceinline__ void role_swap(CsRef cs_, StepShared &sh, int iter, b
 
 // select_pair + the judge_swap draw starting at relative position `end` (uniform over the wave).
 // Returns false if the look-ahead window does not cover it (p < 1e-40).
-__device__ __forceinline__ bool swap_plan(CsRef cs_, const StepShared &sh, const Ring &rg, bool lockstep,
+template <int CAP>
+__device__ __forceinline__ bool swap_plan(CsRef cs_, const StepSharedT<CAP> &sh, const Ring &rg, bool lockstep,
                                           int end, int &pos_out, int &i1, int &i2, double &sr, double &slr)
 {
     CsRef cs = rebase(cs_);
@@ -748,7 +759,8 @@ struct PreOrder {            // per lane (<-> chain)
 // evaluated on the state that memory holds when the workers get to it, before or after the step in between commits;
 // the order names that step's element: the workers leave that event out of their sums and the chain's own wave adds it
 // (chain_pass), so the result does not depend on when the workers looked.
-__device__ __forceinline__ PreOrder role_prepublish_plan(CsRef cs_, StepShared &sh, const Ring &rg, int iter,
+template <int CAP>
+__device__ __forceinline__ PreOrder role_prepublish_plan(CsRef cs_, StepSharedT<CAP> &sh, const Ring &rg, int iter,
                                                          int pos, int lane, bool allow2, bool lockstep)
 {
     CsRef cs = rebase(cs_);
@@ -820,8 +832,11 @@ __device__ __forceinline__ PreOrder role_prepublish_plan(CsRef cs_, StepShared &
     if (mode == 2 && pr.accepted && cgoff + c * cgnx + pr.idx == o_hy + dA.y) mode = 0;
     po.job = mode != 0; po.c = c;
     // own tag space (chain_pass tags stay below 2^31); a step can get a two-ahead order AND, if that one turned out to
-    // be addressed to the wrong position, a one-ahead order: the two must not share a tag
-    po.tag = 0x80000000u | (mode == 2 ? 0x40000000u : 0u) | (((unsigned)(iter + mode) & 0x01ffffffu) << 5) | (unsigned)c;
+    // be addressed to the wrong position, a one-ahead order: the two must not share a tag.  The chain takes the low 5 bits
+    // (6 in the wide kernels: a chain >= 32 in 5 bits would give the orders of iterations 2k and 2k + 1 one tag, and the workers
+    // skip a tag they have served)
+    constexpr int kChainBits = CAP > 32 ? 6 : 5;
+    po.tag = 0x80000000u | (mode == 2 ? 0x40000000u : 0u) | (((unsigned)(iter + mode) & (0x3fffffffu >> kChainBits)) << kChainBits) | (unsigned)c;
     po.w1 = (unsigned)type | ((unsigned)idx << 3);
     po.x_hi = (unsigned)(xb >> 32); po.x_lo = (unsigned)xb;
     po.co = pr.accepted ? (unsigned)(cgoff + c * cgnx + pr.idx) : 0xffffffffu;
@@ -864,7 +879,8 @@ __device__ __forceinline__ void role_prepublish_send(CsRef cs_, const PreOrder &
 }
 
 // chain wave, after the second barrier: this iteration's swap (if it touches chain c) and its records
-__device__ __forceinline__ void post_chain(CsRef cs_, StepShared &sh, int c, int iter, int lane)
+template <int CAP>
+__device__ __forceinline__ void post_chain(CsRef cs_, StepSharedT<CAP> &sh, int c, int iter, int lane)
 {
     CsRef cs = rebase(cs_);
     const int sl = sh.slot_l[c], ss = sh.slot_s[c];
@@ -896,7 +912,8 @@ __device__ __forceinline__ void post_chain(CsRef cs_, StepShared &sh, int c, int
 
 // thread 0: temperature swap between chains of any two ranks from the all-gathered records
 // (cls_parallel.f90:118-213, :285-302).  Every rank evaluates the same decision from the same records.
-__device__ __forceinline__ void apply_swap(CsRef cs_, StepShared &sh, const double *gathered)
+template <int CAP>
+__device__ __forceinline__ void apply_swap(CsRef cs_, StepSharedT<CAP> &sh, const double *gathered)
 {
     CsRef cs = rebase(cs_);
     const int nc = cs.n_chains, RW = 4 + 2 * nc;
@@ -935,7 +952,8 @@ __device__ __forceinline__ void apply_swap(CsRef cs_, StepShared &sh, const doub
 constexpr int kXLoads = 8;        // granule loads per lane in flight while polling
 
 // every thread, after the roles of an iteration: does this rank ask everybody to stop after it?
-__device__ __forceinline__ bool want_stop_now(CsRef cs_, const StepShared &sh, int wmax)
+template <int CAP>
+__device__ __forceinline__ bool want_stop_now(CsRef cs_, const StepSharedT<CAP> &sh, int wmax)
 {
     CsRef cs = rebase(cs_);
     const int nc = cs.n_chains;
@@ -943,7 +961,8 @@ __device__ __forceinline__ bool want_stop_now(CsRef cs_, const StepShared &sh, i
 }
 
 // one wave: this rank's record of iteration `iter` into every rank's inbox
-__device__ __forceinline__ void exchange_post(CsRef cs_, StepShared &sh, int iter, int lane, bool want_stop)
+template <int CAP>
+__device__ __forceinline__ void exchange_post(CsRef cs_, StepSharedT<CAP> &sh, int iter, int lane, bool want_stop)
 {
     CsRef cs = rebase(cs_);
     const int nc = cs.n_chains, RW = 4 + 2 * nc, G = cs.xg, np = cs.n_procs, par = iter & 1;
@@ -968,7 +987,8 @@ __device__ __forceinline__ void exchange_post(CsRef cs_, StepShared &sh, int ite
 
 // the same wave, later: wait for the n_procs records of iteration `iter`, decide the swap, publish sh.xdone = iter.
 // Rows of 64 granules, row = (rank r, chunk k of its record); kXLoads rows in flight.
-__device__ __forceinline__ void exchange_finish(CsRef cs_, StepShared &sh, double *s_gath, int iter, int lane, bool publish = true)
+template <int CAP>
+__device__ __forceinline__ void exchange_finish(CsRef cs_, StepSharedT<CAP> &sh, double *s_gath, int iter, int lane, bool publish = true)
 {
     CsRef cs = rebase(cs_);
     const int nc = cs.n_chains, RW = 4 + 2 * nc, G = cs.xg, np = cs.n_procs, par = iter & 1;
@@ -1050,15 +1070,15 @@ __device__ __forceinline__ void exchange_finish(CsRef cs_, StepShared &sh, doubl
 // PERSIST = true: this is block 0 of a k_mcmc launch; full evaluations are handed to the worker blocks of the
 // same launch through PSync (no kernel exit).  PERSIST = false: the kernel exits at a hand-over and k_full runs
 // as its own launch (fallback path, also used for profiling the two stages separately).
-template <int NCH, bool PERSIST, bool F32, int MK>
+template <int NCH, bool PERSIST, bool F32, int MK, int CAP = kMaxChains>
 __device__ __forceinline__ void step_body(FwRef f_, CsRef cs_, int mode, int target_arg,
                                           const double *gathered, int ring_size, int wmax, unsigned long long launch)
 {
     CsRef cs = rebase(cs_);
     FwRef f = rebase(f_);
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    StepShared &sh = *reinterpret_cast<StepShared *>(smem);
-    char *carve = smem + ((sizeof(StepShared) + 15) & ~size_t(15));
+    StepSharedT<CAP> &sh = *reinterpret_cast<StepSharedT<CAP> *>(smem);
+    char *carve = smem + ((sizeof(StepSharedT<CAP>) + 15) & ~size_t(15));
     Ring rg;
     rg.mask = ring_size - 1;
     rg.U = reinterpret_cast<double *>(carve);          carve += sizeof(double) * ring_size;
@@ -1136,7 +1156,7 @@ __device__ __forceinline__ void step_body(FwRef f_, CsRef cs_, int mode, int tar
         sh.fill = 0; sh.base = 0; sh.redo = -1; sh.sw_do = 0; sh.catchup = 0; sh.rolep_iter = -1;
         sh.xdone = sh.c.iter_done; sh.xstop = 0; sh.xspec = 0; sh.xctl = 0u; sh.xctl_iter = -1;
     }
-    for (int c = tid; c < kMaxChains; c += blockDim.x) { sh.pre_p[0][c] = -1; sh.pre_p[1][c] = -1; sh.redone[c] = 0; }
+    for (int c = tid; c < CAP; c += blockDim.x) { sh.pre_p[0][c] = -1; sh.pre_p[1][c] = -1; sh.redone[c] = 0; }
     {
         if (do_apply && tid == 0 && sh.c.stage == ST_WAIT_SWAP && sh.c.err == 0) {
             apply_swap(cs, sh, staged ? s_gath : gathered);
@@ -1444,6 +1464,15 @@ __global__ __launch_bounds__(512) void k_step(FwdDev f, ChainsDev cs, int mode, 
     step_body<NCH, false, F32, -1>(ka.f, ka.cs, mode, target_arg, gathered, ring_size, wmax, 0ull);
 }
 
+// k_step for 33..64 chains (HTM_PERSIST=0): the same loop on the StepShared of kMaxWideChains; the narrow kernel keeps its LDS
+template <int NCH, bool F32 = false>
+__global__ __launch_bounds__(512) void k_step_wide(FwdDev f, ChainsDev cs, int mode, int target_arg,
+                                                    const double *gathered, int ring_size, int wmax)
+{
+    const KArgLayout __attribute__((address_space(4))) &ka = *(const KArgLayout __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+    step_body<NCH, false, F32, -1, kMaxWideChains>(ka.f, ka.cs, mode, target_arg, gathered, ring_size, wmax, 0ull);
+}
+
 // Worker block of a k_mcmc launch: waits for work orders of its own launch and evaluates its event tile of
 // every model in the order (same arithmetic as k_full: wave <-> event, lane <-> station).  Block w, wave v
 // take events (w*8 + v) + k * 8 * W.  The immutable inputs of its first event (observation rows, station
@@ -1454,7 +1483,7 @@ __global__ __launch_bounds__(512) void k_step(FwdDev f, ChainsDev cs, int mode, 
 // NWV = waves per worker block (8: the master's block shape).  PIPE: the launch's master is the pipelined one (htm_pipe.hpp), whose
 // orders name a second left-out event and want the left-out events' sums reported on their own -- compiled only into those
 // launches: in the workers' event loop it costs the others 13 % at 10 000 x 128 x 16 fp64 (profiles/r04_h_worker_pipe_ab.txt).
-template <int NCH, bool F32, int NWV = 8, bool PIPE = false>
+template <int NCH, bool F32, int NWV = 8, bool PIPE = false, int CAP = kMaxChains>
 __device__ __forceinline__ void worker_body(FwRef f_, CsRef cs_, unsigned long long launch, int w)
 {
     CsRef cs = rebase(cs_);
@@ -1484,7 +1513,7 @@ __device__ __forceinline__ void worker_body(FwRef f_, CsRef cs_, unsigned long l
 
     int *s_chain = reinterpret_cast<int *>(smem + 136);
     // wave 0: lane 8k + g holds granule g of chain (8 j + k)'s slot; lane 8k remembers the last tag served
-    constexpr int kGroups = (kMaxChains + 7) / 8;
+    constexpr int kGroups = (CAP + 7) / 8;
     unsigned last_tag[kGroups];
 #pragma unroll
     for (int j = 0; j < kGroups; ++j) last_tag[j] = 0;

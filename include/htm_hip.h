@@ -141,8 +141,12 @@ typedef struct {
     const int32_t *prior_type;   /* 0 Gaussian, 1 Rayleigh (src/cls_model.f90:9) */
 } htm_model_init;
 
+/* Most chains one rank holds (htm_chains_create refuses more).  Up to 32 a rank may run any of the main loops; 33..64 run
+ * the loop with barriers (htm_chains_master_stats reports it). */
+#define HTM_MAX_CHAINS 64
+
 typedef struct {
-    int            n_chains;      /* chains on this rank            (para%get_n_chains()) */
+    int            n_chains;      /* chains on this rank, 1..HTM_MAX_CHAINS (para%get_n_chains()) */
     int            n_procs;       /* ranks in the job               (mpi_comm_size)       */
     int            rank;          /* this rank                      (mpi_comm_rank)       */
     htm_model_init hypo, t_corr, vs, a_corr, qs;
