@@ -104,6 +104,10 @@ SIGNATURES = {
     "htm_chains_profile": (C.c_int, [vp, C.c_int, dp, C.POINTER(C.c_int), dp, C.POINTER(C.c_int),
                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "htm_select_regress": (C.c_int, [C.c_int, C.c_int, C.c_int, dp, dp, dp, C.c_double, dp, dp, dp, dp, dp]),
+    "htm_xcorr_dev": (C.c_int, [C.c_int, vp, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
+                                C.c_long, vp, vp]),
+    "htm_xcorr": (C.c_int, [C.c_int, dp, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp]),
+    "htm_measure_windows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp, dp, dp, dp, dp]),
     "htm_selftest": (C.c_int, [C.c_int]),
     "htm_selftest_math": (C.c_int, [C.c_int, C.c_int, dp, dp, C.c_int]),
     "htm_rng_jump": (C.c_int, [up, C.c_ulonglong, up]),

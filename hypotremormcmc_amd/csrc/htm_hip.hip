@@ -22,6 +22,7 @@
 #include "htm_kernels.hpp"
 #include "htm_pipe.hpp"
 #include "htm_select.hpp"
+#include "htm_xcorr.hpp"
 
 using namespace htm;
 
@@ -2305,6 +2306,88 @@ int htm_select_regress(int device, int n_sta, int n_win, const double *sta_x, co
     hipLaunchKernelGGL(k_regress, dim3((n_win + 3) / 4), dim3(256), 0, 0, n_sta, n_win, dx, dy, dz, z_guess, dt, dte, da, dae, dout);
     if (hipGetLastError() != hipSuccess) return done(fail(HTM_EHIP, "k_regress launch failed"));
     if (hipMemcpy(out, dout, 6 * (size_t)n_win * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return done(fail(HTM_EHIP, "download failed"));
+    return done(HTM_OK);
+}
+
+static int xcorr_check(long ld_env, long n_smp, int n_sta, int n, int n_step, int n_win, int pair0, int n_pairs, long ld_cc)
+{
+    if (n < 2 || n > kXcMaxN || n % 2) return fail(HTM_EINVAL, "window length n = %d: need an even n in 2..%d (the reference refuses odd n)", n, kXcMaxN);
+    if (n_sta < 2 || n_step < 1 || n_win < 1 || n_pairs < 1 || pair0 < 0)
+        return fail(HTM_EINVAL, "bad shape (n_sta %d, n_step %d, n_win %d, pair0 %d, n_pairs %d)", n_sta, n_step, n_win, pair0, n_pairs);
+    if ((long)pair0 + n_pairs > (long)n_sta * (n_sta - 1) / 2)
+        return fail(HTM_EINVAL, "pairs %d..%d outside the %d pairs of %d stations", pair0, pair0 + n_pairs - 1, n_sta * (n_sta - 1) / 2, n_sta);
+    if ((long)(n_win - 1) * n_step + n > n_smp || n_smp > ld_env)
+        return fail(HTM_EINVAL, "%d windows of %d samples every %d do not fit in %ld samples (row stride %ld)", n_win, n, n_step, n_smp, ld_env);
+    if (ld_cc < n_pairs) return fail(HTM_EINVAL, "ld_cc %ld < n_pairs %d", ld_cc, n_pairs);
+    if ((long)n_win * n_pairs > 0x7fffffffL) return fail(HTM_EINVAL, "n_win * n_pairs = %ld exceeds one launch", (long)n_win * n_pairs);
+    return HTM_OK;
+}
+
+int htm_xcorr_dev(int device, const double *d_env, long ld_env, long n_smp, int n_sta, int n, int n_step, int n_win, int pair0,
+                  int n_pairs, double *d_cc, long ld_cc, double *d_cc_max, void *hip_stream)
+{
+    if (!d_env || !d_cc || !d_cc_max) return fail(HTM_EINVAL, "NULL argument");
+    int rc = xcorr_check(ld_env, n_smp, n_sta, n, n_step, n_win, pair0, n_pairs, ld_cc);
+    if (rc) return rc;
+    if ((rc = use_device(device))) return rc;
+    const int threads = xc_threads(n);
+    hipLaunchKernelGGL(k_xcorr, dim3((unsigned)((long)n_win * n_pairs)), dim3(threads), 2 * (size_t)n * sizeof(double),
+                       static_cast<hipStream_t>(hip_stream), d_env, ld_env, n_sta, n, n_step, n_win, pair0, n_pairs, d_cc, ld_cc,
+                       d_cc_max);
+    HIPCHK(hipGetLastError());
+    return HTM_OK;
+}
+
+int htm_xcorr(int device, const double *env, long n_smp, int n_sta, int n, int n_step, int n_win, int pair0, int n_pairs,
+              double *cc, double *cc_max)
+{
+    if (!env || !cc || !cc_max) return fail(HTM_EINVAL, "NULL argument");
+    int rc = xcorr_check(n_smp, n_smp, n_sta, n, n_step, n_win, pair0, n_pairs, n_pairs);
+    if (rc) return rc;
+    if ((rc = use_device(device))) return rc;
+    std::vector<void *> pool;
+    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
+    double *de = nullptr, *dc = nullptr, *dm = nullptr;
+    const size_t n_cc = (size_t)n_win * n * n_pairs, n_m = (size_t)n_win * n_pairs;
+    if ((rc = dev_upload(pool, &de, env, (size_t)n_sta * n_smp)) || (rc = dev_alloc(pool, &dc, n_cc)) || (rc = dev_alloc(pool, &dm, n_m)))
+        return done(rc);
+    if ((rc = htm_xcorr_dev(device, de, n_smp, n_smp, n_sta, n, n_step, n_win, pair0, n_pairs, dc, n_pairs, dm, nullptr))) return done(rc);
+    if (hipMemcpy(cc, dc, n_cc * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(cc_max, dm, n_m * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        return done(fail(HTM_EHIP, "k_xcorr or its download failed"));
+    return done(HTM_OK);
+}
+
+int htm_measure_windows(int device, int n_sta, int n, double dt, int n_det, const double *x, double *t, double *t_stdv,
+                        double *amp, double *amp_stdv)
+{
+    if (!x || !t || !t_stdv || !amp || !amp_stdv) return fail(HTM_EINVAL, "NULL argument");
+    if (n_sta < 3 || n < 2 || n > kXcMaxN || n_det < 0 || !(dt > 0.0))
+        return fail(HTM_EINVAL, "need n_sta >= 3, n in 2..%d, n_det >= 0, dt > 0 (got %d, %d, %d, %g)", kXcMaxN, n_sta, n, n_det, dt);
+    if (n_det == 0) return HTM_OK;
+    int rc = use_device(device);
+    if (rc) return rc;
+    std::vector<void *> pool;
+    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
+    // windows in launches of at most ~256 MB of inputs and workspace (every window of a usual run in one launch)
+    const size_t per_win = ((size_t)n_sta * n + (size_t)n_sta * n_sta + 5 * (size_t)n_sta) * sizeof(double);
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_det, ((size_t)256 << 20) / per_win));
+    double *dx = nullptr, *dws = nullptr, *dout = nullptr;
+    if ((rc = dev_alloc(pool, &dx, (size_t)chunk * n_sta * n)) || (rc = dev_alloc(pool, &dws, (size_t)chunk * ((size_t)n_sta * n_sta + n_sta))) ||
+        (rc = dev_alloc(pool, &dout, 4 * (size_t)chunk * n_sta)))
+        return done(rc);
+    double *outs[4] = {t, t_stdv, amp, amp_stdv};
+    for (int w0 = 0; w0 < n_det; w0 += chunk) {
+        const int nw = std::min(chunk, n_det - w0);
+        const size_t ns = (size_t)nw * n_sta;
+        HIPCHK(hipMemcpy(dx, x + (size_t)w0 * n_sta * n, ns * n * sizeof(double), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_measure, dim3(nw), dim3(xc_threads(n)), 2 * (size_t)n * sizeof(double), 0, dx, n_sta, n, dt, nw, dws,
+                           dout, dout + (size_t)chunk * n_sta, dout + 2 * (size_t)chunk * n_sta, dout + 3 * (size_t)chunk * n_sta);
+        if (hipGetLastError() != hipSuccess) return done(fail(HTM_EHIP, "k_measure launch failed"));
+        for (int k = 0; k < 4; ++k)
+            if (hipMemcpy(outs[k] + (size_t)w0 * n_sta, dout + k * (size_t)chunk * n_sta, ns * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+                return done(fail(HTM_EHIP, "k_measure or its download failed"));
+    }
     return done(HTM_OK);
 }
 

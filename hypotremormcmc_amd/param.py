@@ -34,6 +34,10 @@ REQUIRED_MCMC = [
 
 # src/cls_param.f90:123-126
 REQUIRED_SELECT = ["n_procs", "station_file", "z_guess", "vs_min", "vs_max", "b_min", "b_max"]
+# src/cls_param.f90:117-122.  Step 3 also reads t_win_corr and t_step_corr (src/hypo_tremor_measure.f90:50-51) without
+# requiring them; hypotremormcmc_amd.measure checks them itself (require()).
+REQUIRED_CORRELATE = ["n_procs", "station_file", "t_win_corr", "t_step_corr"]
+REQUIRED_MEASURE = ["n_procs", "station_file", "alpha", "n_pair_thred"]
 
 
 class ParamError(SystemExit):
@@ -80,12 +84,19 @@ class Param:
                 if nv is None:
                     continue
                 self.set_value(*nv)
-        for key in {"mcmc": REQUIRED_MCMC, "select": REQUIRED_SELECT}.get(from_where, []):
+        for key in {"mcmc": REQUIRED_MCMC, "select": REQUIRED_SELECT, "correlate": REQUIRED_CORRELATE,
+                    "measure": REQUIRED_MEASURE}.get(from_where, []):
             if key not in self.given:
                 raise ParamError(f"ERROR: {key} is not given.")
         base = os.path.dirname(os.path.abspath(param_file))
         sf = self.values["station_file"]
         self.read_station_file(sf if os.path.isabs(sf) or os.path.exists(sf) else os.path.join(base, sf))
+
+    def require(self, *keys):
+        """a clear error for keys a program reads that its reference list does not require"""
+        for key in keys:
+            if key not in self.given:
+                raise ParamError(f"ERROR: {key} is not given.")
 
     def set_value(self, name: str, val: str):
         if name in STR_KEYS:

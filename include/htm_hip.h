@@ -322,6 +322,38 @@ int htm_select_regress(int device, int n_sta, int n_win, const double *sta_x, co
                        const double *sta_z, double z_guess, const double *t, const double *t_err,
                        const double *a, const double *a_err, double *out);
 
+/* ------------------------------------------------------------------------------------------------
+ * Step 2, `hypo_tremor_correlate`       reference: src/cls_correlator.f90:179-235, src/mod_signal_process.f90
+ * Windowed cross-correlations of station envelopes.  d_env: n_sta rows of n_smp amplitudes, row stride ld_env
+ * doubles.  Window w (0-based) of a station is samples w*n_step .. w*n_step+n-1; it is tapered (nleng = int(0.05 n)
+ * cosine samples at each end), demeaned and divided by its norm (:207-223; a window of zero energy gives an all-zero
+ * correlogram and cc_max = 0, where the reference reuses a stale buffer).  For the pairs pair0 .. pair0+n_pairs-1 of
+ * the station-file order (1,2), (1,3), ..., (2,3), ... (0-based index), every window and every lag:
+ *     d_cc[(w*n + j)*ld_cc + p] = sum_m r_i[m] * r_j[(m + k) mod n],  k = (j - n/2) mod n,
+ * i.e. row j holds lag j - n/2, negative lags first (:234-235), one column per pair -- the layout htm_quantiles_dev
+ * selects over with n_mod = n_win*n, ld = ld_cc.  d_cc_max[w*ld_cc + p] = max_j of that window.  n even in 2..4096
+ * (the reference refuses odd n, :179-182), (n_win-1)*n_step + n <= n_smp <= ld_env, ld_cc >= n_pairs; anything else
+ * is HTM_EINVAL.  Device pointers; asynchronous on `hip_stream` (NULL = the null stream). */
+int htm_xcorr_dev(int device, const double *d_env, long ld_env, long n_smp, int n_sta, int n, int n_step, int n_win,
+                  int pair0, int n_pairs, double *d_cc, long ld_cc, double *d_cc_max, void *hip_stream);
+/* the same with host pointers, for tests: env [n_sta][n_smp], cc [n_win*n][n_pairs], cc_max [n_win][n_pairs].
+ * Synchronous. */
+int htm_xcorr(int device, const double *env, long n_smp, int n_sta, int n, int n_step, int n_win, int pair0,
+              int n_pairs, double *cc, double *cc_max);
+
+/* ------------------------------------------------------------------------------------------------
+ * Step 3, `hypo_tremor_measure`                 reference: src/cls_measurer.f90:405-523
+ * Per detected window (one workgroup each): optimize_cc (:463-523) -- r = taper(x) / sum(x^2), for every pair
+ * i < j the first maximum of the circular correlation in natural order (Fortran maxloc), lag = idx*dt for
+ * idx < n/2 else (idx - n)*dt, t(i) = -sum_j lag(i,j) / n_sta and t_stdv(i) = sqrt(sum_{j!=i} (t(j) - t(i) -
+ * lag(i,j))^2 / (n_sta - 2)), both summed serially in j; a station of zero energy has lag 0 against every
+ * station (the reference divides 0 by 0).  Then optimize_amp (:405-459) -- each station shifted by nint(t/dt),
+ * rel(i,j) = log(sxy / sxx(i)), amp and amp_stdv as t and t_stdv; any sxy < 0 gives amp = amp_stdv = 0 for the
+ * whole window (:430-434).  x [n_det][n_sta][n] raw envelope windows; t, t_stdv, amp, amp_stdv [n_det][n_sta].
+ * n_sta >= 3, 2 <= n <= 4096, dt > 0.  Host pointers; synchronous. */
+int htm_measure_windows(int device, int n_sta, int n, double dt, int n_det, const double *x, double *t,
+                        double *t_stdv, double *amp, double *amp_stdv);
+
 int htm_selftest(int device);
 
 /* y[i] = fn(x[i]) for n host values, fn = the forward model's own fp64 routines: which = 0 the logarithm of the amplitude
