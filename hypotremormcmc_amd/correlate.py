@@ -102,12 +102,22 @@ def read_max_corr(path):
     return v[: v.size // 2 * 2].reshape(-1, 2)
 
 
+MAX_WORK_ITEMS = 2 ** 32 - 1    # one launch: the dispatch packet holds the grid in work-items as a uint32
+
+
+def xc_threads(n: int) -> int:
+    """work-items per (window, pair) workgroup of htm_xcorr_dev: n rounded up to whole waves, at most 1024"""
+    return min(1024, (n + 63) // 64 * 64)
+
+
 def batch_pairs(n_win: int, n: int, mb=None) -> int:
-    """pairs per batch whose correlograms (and cc_max) fit in HTM_XCORR_MB MiB, at least one"""
+    """pairs per batch whose correlograms (and cc_max) fit in HTM_XCORR_MB MiB, at least one, and whose launch of
+    n_win * pairs workgroups stays below 2^32 work-items (htm_xcorr_dev refuses a single pair beyond that)"""
     if mb is None:
         mb = float(os.environ.get("HTM_XCORR_MB", DEFAULT_XCORR_MB))
     per_pair = 8 * n_win * (n + 1)
-    return max(1, int(mb * (1 << 20)) // per_pair)
+    launch = MAX_WORK_ITEMS // (n_win * xc_threads(n))
+    return max(1, min(int(mb * (1 << 20)) // per_pair, launch))
 
 
 class Envelopes:

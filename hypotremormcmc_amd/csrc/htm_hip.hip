@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
+#include <climits>
 #include <cstring>
 #include <thread>
 #include <string>
@@ -2213,6 +2214,8 @@ int htm_quantiles_dev(int device, const double *d_samples, long n_mod, long n_pa
 {
     if (!d_samples || !d_out || !ranks_1based) return fail(HTM_EINVAL, "NULL argument");
     if (n_mod < 1 || n_par < 1 || ld < n_par) return fail(HTM_EINVAL, "bad shape (n_mod %ld, n_par %ld, ld %ld)", n_mod, n_par, ld);
+    // the select kernels count rows in int (LDS counters, the slab histogram's atomics) and take int ranks
+    if (n_mod > INT_MAX) return fail(HTM_EINVAL, "n_mod %ld exceeds %d rows per column", n_mod, INT_MAX);
     for (int r = 0; r < 3; ++r)
         if (ranks_1based[r] < 1 || ranks_1based[r] > n_mod)
             return fail(HTM_EINVAL, "rank %d outside 1..%ld (the reference would index outside its sorted column)", ranks_1based[r], n_mod);
@@ -2274,6 +2277,7 @@ int htm_quantiles(int device, const double *samples, long n_mod, long n_par, con
 {
     if (!samples || !out) return fail(HTM_EINVAL, "NULL argument");
     if (n_mod < 1 || n_par < 1) return fail(HTM_EINVAL, "bad shape");
+    if (n_mod > INT_MAX) return fail(HTM_EINVAL, "n_mod %ld exceeds %d rows per column", n_mod, INT_MAX);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
     HIPCHK(hipSetDevice(device));
@@ -2320,6 +2324,10 @@ static int xcorr_check(long ld_env, long n_smp, int n_sta, int n, int n_step, in
         return fail(HTM_EINVAL, "%d windows of %d samples every %d do not fit in %ld samples (row stride %ld)", n_win, n, n_step, n_smp, ld_env);
     if (ld_cc < n_pairs) return fail(HTM_EINVAL, "ld_cc %ld < n_pairs %d", ld_cc, n_pairs);
     if ((long)n_win * n_pairs > 0x7fffffffL) return fail(HTM_EINVAL, "n_win * n_pairs = %ld exceeds one launch", (long)n_win * n_pairs);
+    // the dispatch packet holds the grid in work-items as a uint32_t (hsa_kernel_dispatch_packet_t::grid_size_x)
+    if ((long)n_win * n_pairs * xc_threads(n) > 0xffffffffL)
+        return fail(HTM_EINVAL, "n_win * n_pairs * %d threads = %ld work-items exceed one launch (2^32 - 1)", xc_threads(n),
+                    (long)n_win * n_pairs * xc_threads(n));
     return HTM_OK;
 }
 
@@ -2369,9 +2377,13 @@ int htm_measure_windows(int device, int n_sta, int n, double dt, int n_det, cons
     if (rc) return rc;
     std::vector<void *> pool;
     auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
-    // windows in launches of at most ~256 MB of inputs and workspace (every window of a usual run in one launch)
+    // windows in launches of at most HTM_MEASURE_MB MiB of inputs and workspace (default 256: every window of a usual
+    // run in one launch; at least one window per launch)
     const size_t per_win = ((size_t)n_sta * n + (size_t)n_sta * n_sta + 5 * (size_t)n_sta) * sizeof(double);
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_det, ((size_t)256 << 20) / per_win));
+    const char *mb_env = getenv("HTM_MEASURE_MB");
+    const double mb = mb_env ? atof(mb_env) : 256.0;
+    const size_t budget = mb > 0.0 ? (size_t)std::min(mb * 1048576.0, 1e18) : 0;
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_det, budget / per_win));
     double *dx = nullptr, *dws = nullptr, *dout = nullptr;
     if ((rc = dev_alloc(pool, &dx, (size_t)chunk * n_sta * n)) || (rc = dev_alloc(pool, &dws, (size_t)chunk * ((size_t)n_sta * n_sta + n_sta))) ||
         (rc = dev_alloc(pool, &dout, 4 * (size_t)chunk * n_sta)))

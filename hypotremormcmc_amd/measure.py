@@ -38,6 +38,8 @@ from . import _lib, correlate as corr
 from ._lib import check, dp
 from .param import Param
 
+INT_MAX = 2 ** 31 - 1      # htm_quantiles_dev takes int ranks and counts rows in int
+
 
 def _p(a):
     return a.ctypes.data_as(dp)
@@ -66,6 +68,9 @@ def common_dt(stations, directory="."):
 def threshold_rank(n: int, n_win: int, alpha: float) -> int:
     """1-based rank of the threshold, int(n*n_win*alpha) (src/cls_measurer.f90:238)"""
     r = int(n * n_win * alpha)
+    if n * n_win > INT_MAX:
+        raise SystemExit(f"ERROR: {n * n_win} correlation values per pair (n = {n}, n_win = {n_win}) exceed the "
+                         f"threshold select's limit of {INT_MAX}; use fewer windows per run")
     if r < 1:
         raise SystemExit(f"ERROR: alpha = {alpha} gives threshold rank {r} of {n * n_win} correlation values; "
                          "the rank must be at least 1")
@@ -126,6 +131,8 @@ def _thresholds_dev(d_cc, n_mod, nb, rank, device):
     """rank-th smallest of each column of the device buffer [>= n_mod][nb]"""
     import torch
 
+    if not (1 <= rank <= n_mod <= INT_MAX):      # ctypes.c_int would wrap silently
+        raise ValueError(f"threshold rank {rank} of {n_mod} values: need 1 <= rank <= n_mod <= {INT_MAX}")
     out = torch.empty((nb, 3), dtype=torch.float64, device=d_cc.device)
     rk = (C.c_int * 3)(rank, rank, rank)
     with torch.cuda.device(d_cc.device):

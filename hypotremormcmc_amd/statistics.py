@@ -23,6 +23,8 @@ import numpy as np
 from . import _lib
 from .param import Param
 
+INT_MAX = 2 ** 31 - 1      # htm_quantiles takes int ranks and counts rows in int
+
 HYPO_HEADER = ("# window ID, x (50%), x (2.5%) x (97.5%), y (50%), y (2.5%), y (97.5%)"
                "z (50 %), z (2.5%), z (97.5%)")
 CORR_HEADER = ("# station name, t_corr (50%), t_corr (2.5%) t_corr (97.5%), a_corr (50%), a_corr (2.5%), "
@@ -48,6 +50,9 @@ def quantiles(samples: np.ndarray, n_mod: int | None = None, device: int = 0) ->
         x = x[:, None]
     n_rows, n_par = x.shape
     il, im, iu = ranks(n_rows if n_mod is None else n_mod)
+    for what, v in (("rows", n_rows), ("n_mod", n_mod or 0), ("rank", max(il, im, iu))):
+        if v > INT_MAX:        # ctypes.c_int would wrap silently; htm_quantiles counts rows in int
+            raise ValueError(f"{what} = {v} exceeds {INT_MAX}: htm_quantiles selects over at most {INT_MAX} rows")
     rk = (C.c_int * 3)(il, im, iu)
     out = np.empty((n_par, 3))
     lib = _lib.load()

@@ -304,7 +304,8 @@ int htm_chains_profile(htm_chains *hc, int n_iter, double *step_us, int *step_la
  * the elements il = int(0.025*n_mod), im = int(0.5*n_mod), iu = int(0.975*n_mod) (1-based, single-
  * precision products) of the sorted column.  htm_quantiles returns exactly those elements without sorting:
  * samples [n_mod][n_par] row-major (one recorded model per row), ranks_1based[3] = {il, im, iu} or any other
- * three ranks in 1..n_mod, out [n_par][3].  Host pointers; synchronous.  The _dev form takes device
+ * three ranks in 1..n_mod, out [n_par][3]; n_mod <= INT_MAX, else HTM_EINVAL before any device call.  Host
+ * pointers; synchronous.  The _dev form takes device
  * pointers (ld = row stride in doubles) and is asynchronous on `hip_stream` (NULL = the null stream). */
 int htm_quantiles(int device, const double *samples, long n_mod, long n_par, const int ranks_1based[3],
                   double *out);
@@ -332,8 +333,9 @@ int htm_select_regress(int device, int n_sta, int n_win, const double *sta_x, co
  *     d_cc[(w*n + j)*ld_cc + p] = sum_m r_i[m] * r_j[(m + k) mod n],  k = (j - n/2) mod n,
  * i.e. row j holds lag j - n/2, negative lags first (:234-235), one column per pair -- the layout htm_quantiles_dev
  * selects over with n_mod = n_win*n, ld = ld_cc.  d_cc_max[w*ld_cc + p] = max_j of that window.  n even in 2..4096
- * (the reference refuses odd n, :179-182), (n_win-1)*n_step + n <= n_smp <= ld_env, ld_cc >= n_pairs; anything else
- * is HTM_EINVAL.  Device pointers; asynchronous on `hip_stream` (NULL = the null stream). */
+ * (the reference refuses odd n, :179-182), (n_win-1)*n_step + n <= n_smp <= ld_env, ld_cc >= n_pairs, and one launch:
+ * n_win*n_pairs*min(1024, n rounded up to 64) work-items below 2^32; anything else is HTM_EINVAL, returned before
+ * any device call.  Device pointers; asynchronous on `hip_stream` (NULL = the null stream). */
 int htm_xcorr_dev(int device, const double *d_env, long ld_env, long n_smp, int n_sta, int n, int n_step, int n_win,
                   int pair0, int n_pairs, double *d_cc, long ld_cc, double *d_cc_max, void *hip_stream);
 /* the same with host pointers, for tests: env [n_sta][n_smp], cc [n_win*n][n_pairs], cc_max [n_win][n_pairs].
@@ -350,7 +352,9 @@ int htm_xcorr(int device, const double *env, long n_smp, int n_sta, int n, int n
  * station (the reference divides 0 by 0).  Then optimize_amp (:405-459) -- each station shifted by nint(t/dt),
  * rel(i,j) = log(sxy / sxx(i)), amp and amp_stdv as t and t_stdv; any sxy < 0 gives amp = amp_stdv = 0 for the
  * whole window (:430-434).  x [n_det][n_sta][n] raw envelope windows; t, t_stdv, amp, amp_stdv [n_det][n_sta].
- * n_sta >= 3, 2 <= n <= 4096, dt > 0.  Host pointers; synchronous. */
+ * n_sta >= 3, 2 <= n <= 4096, dt > 0.  The windows go in launches of at most HTM_MEASURE_MB MiB (environment,
+ * default 256) of inputs and workspace, at least one window each; the results do not depend on it.  Host
+ * pointers; synchronous. */
 int htm_measure_windows(int device, int n_sta, int n, double dt, int n_det, const double *x, double *t,
                         double *t_stdv, double *amp, double *amp_stdv);
 

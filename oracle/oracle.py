@@ -40,8 +40,8 @@ class OrcRng(C.Structure):
 
 def build(force: bool = False) -> str:
     so = os.path.join(_HERE, "liboracle.so")
-    src = os.path.join(_HERE, "htm_oracle.c")
-    if force or not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
+    srcs = [os.path.join(_HERE, f) for f in ("htm_oracle.c", "htm_oracle.h", "ref_dft.c")]
+    if force or not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in srcs):
         subprocess.check_call(["make", "-C", _HERE, "liboracle.so"], stdout=subprocess.DEVNULL)
     return so
 
@@ -88,8 +88,36 @@ def lib():
     L.orc_job_enable_steplog.argtypes = [vp, C.c_int]
     L.orc_job_steplog_n.argtypes = [vp]
     L.orc_job_get_steplog.argtypes = [vp, ip, dp]
+    # the FFT stand-in the compiled reference's steps 2 and 3 link instead of FFTW (ref_dft.c)
+    for n in ("fftw_plan_dft_r2c_1d", "fftw_plan_dft_c2r_1d"):
+        getattr(L, n).argtypes = [C.c_int, vp, vp, C.c_int]
+        getattr(L, n).restype = vp
+    for n in ("fftw_execute_dft_r2c", "fftw_execute_dft_c2r"):
+        getattr(L, n).argtypes = [vp, vp, vp]
+        getattr(L, n).restype = None
     _LIB = L
     return L
+
+
+def ref_dft_r2c(x):
+    """the stand-in's r2c of a real vector of n samples -> n // 2 + 1 complex bins"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    out = np.zeros(x.size // 2 + 1, dtype=np.complex128)
+    L = lib()
+    p = L.fftw_plan_dft_r2c_1d(x.size, x.ctypes.data, out.ctypes.data, 64)
+    L.fftw_execute_dft_r2c(p, x.ctypes.data, out.ctypes.data)
+    return out
+
+
+def ref_dft_c2r(c, n):
+    """the stand-in's unnormalised c2r of n // 2 + 1 complex bins -> n real samples"""
+    c = np.ascontiguousarray(c, dtype=np.complex128)
+    assert c.size == n // 2 + 1
+    out = np.zeros(n)
+    L = lib()
+    p = L.fftw_plan_dft_c2r_1d(n, c.ctypes.data, out.ctypes.data, 64)
+    L.fftw_execute_dft_c2r(p, c.ctypes.data, out.ctypes.data)
+    return out
 
 
 def _d(a):

@@ -19,6 +19,11 @@ Cases
   select, select_wide   step 4 (hypo_tremor_select): 60 windows x 12 stations under 2 ranks, 33 x 70 under 3 ranks
   c4     1000 ev x 64 stn, seed 1, 8 ranks x 8 chains = 64 tempered chains, temp_high = 200, 400 it (BASELINE
          configs[3], run under mpiexec -np 8); inputs as for c3.
+  xcorr_overlap, xcorr_gapped   steps 2 and 3 (hypo_tremor_correlate, hypo_tremor_measure) on seeded
+         synth.make_tremor_envelopes data, each under mpiexec -np 1 and -np 3 (the outputs must be identical).  These
+         two programs are linked with oracle/ref_dft.c in place of FFTW (oracle/Makefile): their values agree with
+         an FFTW build's to rounding only.  Inputs are regenerated from the stored generator arguments and checked
+         against a stored checksum.
 """
 from __future__ import annotations
 
@@ -243,11 +248,105 @@ def run_select_case(name, spec):
         shutil.rmtree(work, ignore_errors=True)
 
 
+CORRELATE_BIN = os.path.join(ROOT, "oracle", "_ref", "hypo_tremor_correlate_ref")
+MEASURE_BIN = os.path.join(ROOT, "oracle", "_ref", "hypo_tremor_measure_ref")
+XCORR_CASES = {
+    # overlapping windows (n_step = n / 2), noise, three bursts; the taper is active (nleng = 3)
+    "xcorr_overlap": dict(gen=dict(n_sta=5, n_win=40, n=64, n_step=32, burst_win=[5, 14, 27], delay=[0, 2, -1, 3, 1],
+                                   log_amp=[0.0, 0.3, -0.2, 0.1, -0.4], noise=0.3, width=3.0, burst_amp=10.0,
+                                   level=1.0, dt=1.0, seed=11),
+                          alpha=0.99, n_pair_thred=5),
+    # gapped windows (n_step > n), dt = 0.5; the delays have a mean of half a sample, so every t of a burst window
+    # falls on +-0.5 dt, +-1.5 dt, +-2.5 dt: step 3's nint(t / dt) rounds half away from zero
+    "xcorr_gapped": dict(gen=dict(n_sta=6, n_win=24, n=50, n_step=70, burst_win=[6, 17], delay=[0, 1, 2, 3, -2, -1],
+                                  log_amp=[0.0, -0.3, 0.2, 0.4, -0.1, 0.25], noise=0.1, width=2.5, burst_amp=10.0,
+                                  level=1.0, dt=0.5, seed=12),
+                         alpha=0.995, n_pair_thred=10),
+}
+
+
+def xcorr_envelopes(gen):
+    """the case's envelopes, regenerated from its generator arguments"""
+    return synth.make_tremor_envelopes(**gen)
+
+
+def xcorr_checksum(env) -> str:
+    return hashlib.sha256(np.ascontiguousarray(env.amps, dtype="<f8").tobytes()).hexdigest()
+
+
+def run_xcorr_once(work, env, spec, n_procs):
+    """reference steps 2 and 3 under mpiexec -np n_procs in a fresh directory -> {file name: bytes}"""
+    g = spec["gen"]
+    synth.write_envelopes(work, env, n_procs=n_procs, t_win_corr=repr(g["n"] * g["dt"]),
+                          t_step_corr=repr(g["n_step"] * g["dt"]), alpha=repr(spec["alpha"]),
+                          n_pair_thred=spec["n_pair_thred"])
+    for exe in (CORRELATE_BIN, MEASURE_BIN):
+        subprocess.check_call([MPIEXEC, "-np", str(n_procs), exe, "tremor.in"], cwd=work,
+                              stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    return {f: open(os.path.join(work, f), "rb").read() for f in sorted(os.listdir(work))
+            if f.endswith((".corr", ".max_corr")) or f in ("cc_thred.dat", "detected_win.dat") or f.startswith("opt_data.")}
+
+
+def run_xcorr_case(name, spec):
+    """Reference steps 2 and 3, unmodified but for the FFT stand-in.  Stored: cc [n_win][n_pair][n] (the .corr
+    values, the reference's lag order), cc_max [n_win][n_pair], the thresholds as the .corr element of rank
+    int(n*n_win*alpha) and as printed in cc_thred.dat, the detected window ids and times, and every detected window's
+    opt_data columns [n_det][n_sta][7] (x y z t t_stdv amp amp_stdv)."""
+    g = spec["gen"]
+    env = xcorr_envelopes(g)
+    S, n, n_win = g["n_sta"], g["n"], g["n_win"]
+    assert np.min(env.amps) > 0.0           # no zero-energy window: the reference's stale buffer depends on the ranks
+    outs = []
+    for n_procs in (1, 3):
+        work = tempfile.mkdtemp(prefix="htm_golden_xc_")
+        try:
+            outs.append(run_xcorr_once(work, env, spec, n_procs))
+        finally:
+            shutil.rmtree(work, ignore_errors=True)
+    assert outs[0] == outs[1], "reference steps 2 and 3 differ between 1 and 3 ranks"
+    files = outs[0]
+    stn = env.stations
+    prs = [(stn[i], stn[j]) for i in range(S - 1) for j in range(i + 1, S)]
+    cc = np.empty((n_win, len(prs), n))
+    cc_max = np.empty((n_win, len(prs)))
+    for p, (a, b) in enumerate(prs):
+        v = np.frombuffer(files[f"{a}.{b}.corr"], dtype="<f8").reshape(n_win, n, 3)
+        cc[:, p] = v[:, :, 2]
+        cc_max[:, p] = np.frombuffer(files[f"{a}.{b}.max_corr"], dtype="<f8").reshape(n_win, 2)[:, 1]
+    rank = int(n * n_win * spec["alpha"])
+    thred = np.array([np.sort(cc[:, p].ravel())[rank - 1] for p in range(len(prs))])
+    # list-directed output: whitespace-separated tokens, lines wrapped wherever the compiler likes
+    tok = files["cc_thred.dat"].decode().split()
+    assert tok[0::3] == [a for a, _ in prs] and tok[1::3] == [b for _, b in prs]
+    thred_text = np.array([float(t) for t in tok[2::3]])
+    assert np.all(np.abs(thred_text - thred) <= 4 * np.spacing(thred)), (thred_text - thred)
+    tok = files["detected_win.dat"].decode().split()
+    det = np.array([int(t) for t in tok[0::2]], dtype=np.int32)
+    det_time = np.array([float(t) for t in tok[1::2]])
+    assert set(g["burst_win"]) <= set(det.tolist()) and len(det) < n_win, det
+    opt = np.array([[float(t) for t in files["opt_data.%06d.dat" % w].decode().split()] for w in det]).reshape(-1, S, 7)
+    if name == "xcorr_gapped":
+        frac = np.abs(opt[:, :, 3] / g["dt"]) % 1.0
+        assert np.any(frac == 0.5), "no t on a half sample"
+    first = f"{prs[0][0]}.{prs[0][1]}"
+    fx = dict(cc=cc, cc_max=cc_max, thred=thred, thred_text=thred_text, thred_rank=np.array(rank), detected=det,
+              detected_time=det_time, opt=opt,
+              corr0_sha256=np.array(hashlib.sha256(files[first + ".corr"]).hexdigest()),
+              max_corr0_sha256=np.array(hashlib.sha256(files[first + ".max_corr"]).hexdigest()),
+              in_checksum=np.array(xcorr_checksum(env)),
+              in_gen_keys=np.array(list(g.keys())), in_gen_vals=np.array([repr(v) for v in g.values()]),
+              alpha=np.array(spec["alpha"]), n_pair_thred=np.array(spec["n_pair_thred"]))
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **fx)
+    print(name, "ok: detected", det.tolist(), "threshold rank", rank)
+
+
 if __name__ == "__main__":
-    if not (os.path.exists(REF_BIN) and os.path.exists(PROBE_BIN) and os.path.exists(STATS_BIN) and os.path.exists(SELECT_BIN)):
+    if not all(os.path.exists(b) for b in (REF_BIN, PROBE_BIN, STATS_BIN, SELECT_BIN, CORRELATE_BIN, MEASURE_BIN)):
         subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"])
-    for nm in (sys.argv[1:] or list(CASES) + list(SELECT_CASES)):
+    for nm in (sys.argv[1:] or list(CASES) + list(SELECT_CASES) + list(XCORR_CASES)):
         if nm in SELECT_CASES:
             run_select_case(nm, SELECT_CASES[nm])
+        elif nm in XCORR_CASES:
+            run_xcorr_case(nm, XCORR_CASES[nm])
         else:
             run_case(nm, CASES[nm])

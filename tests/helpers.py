@@ -59,3 +59,20 @@ class OracleRank:
             st = self.job.chain(self.rank, c)
             npr += st["n_propose"]; nac += st["n_accept"]
         return npr, nac
+
+
+XCORR_CASES = ["xcorr_overlap", "xcorr_gapped"]
+
+
+def load_xcorr_case(name):
+    """Returns (fixture npz, SynthEnvelopes inputs, generator arguments) of a steps-2/3 fixture: the envelopes come
+    from the seeded generator, checksum-verified against what the reference was run on."""
+    import ast
+    import hashlib
+
+    fx = np.load(os.path.join(GOLDEN, name + ".npz"))
+    gen = {k: ast.literal_eval(v) for k, v in zip(fx["in_gen_keys"].tolist(), fx["in_gen_vals"].tolist())}
+    env = synth.make_tremor_envelopes(**gen)
+    h = hashlib.sha256(np.ascontiguousarray(env.amps, dtype="<f8").tobytes()).hexdigest()
+    assert h == str(fx["in_checksum"]), "tremor envelope generator no longer reproduces the fixture inputs"
+    return fx, env, gen

@@ -1,7 +1,9 @@
 """Steps 2 and 3 on the GPU (`htm_xcorr`, `htm_measure_windows`, python -m hypotremormcmc_amd.correlate / .measure)
-against the numpy restatement of the reference in tests/xcorr_restatement.py, and on synthetic tremor with known
-delays and amplitudes."""
+against the compiled reference (tests/golden/xcorr_*.npz), against the numpy restatement of the reference in
+tests/xcorr_restatement.py and its long-double direct sums at edge shapes, and on synthetic tremor with known delays
+and amplitudes."""
 import ctypes as C
+import math
 import os
 import subprocess
 import sys
@@ -9,11 +11,11 @@ import sys
 import numpy as np
 import pytest
 
-from hypotremormcmc_amd import _lib, measure, synth
+from hypotremormcmc_amd import _lib, correlate as corr, measure, synth
 from hypotremormcmc_amd._lib import check, dp
 from hypotremormcmc_amd.select import read_detected_win
 
-from . import xcorr_restatement as rs
+from . import helpers, xcorr_restatement as rs
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 pytestmark = pytest.mark.gpu
@@ -211,3 +213,250 @@ def test_pipeline_end_to_end(tmp_path):
     for f in os.listdir(a):
         if f.endswith((".corr", ".max_corr")):
             assert open(a / f, "rb").read() == open(c / f, "rb").read(), f
+
+
+# ---- steps 2 and 3 against the compiled reference (tests/golden/xcorr_*.npz, make_golden.py) ---------------------------
+
+def _fixture_dir(tmp_path, case):
+    fx, env, g = helpers.load_xcorr_case(case)
+    synth.write_envelopes(str(tmp_path), env, t_win_corr=repr(g["n"] * g["dt"]), t_step_corr=repr(g["n_step"] * g["dt"]),
+                          alpha=repr(float(fx["alpha"])), n_pair_thred=int(fx["n_pair_thred"]))
+    return fx, env, g
+
+
+def _check_step3_files(d, fx, env, g):
+    S = g["n_sta"]
+    prs = corr.pairs(env.stations)
+    tok = open(d / "cc_thred.dat").read().split()
+    assert tok[0::3] == [a for a, _ in prs] and tok[1::3] == [b for _, b in prs]
+    np.testing.assert_allclose([float(v) for v in tok[2::3]], fx["thred"], rtol=0, atol=1e-12)
+    ids, times = read_detected_win(str(d / "detected_win.dat"))
+    assert ids == fx["detected"].tolist() and times == fx["detected_time"].tolist()
+    for k, w in enumerate(ids):
+        rows = np.array([float(v) for v in open(d / ("opt_data.%06d.dat" % w)).read().split()]).reshape(S, 7)
+        ref = fx["opt"][k]
+        assert np.array_equal(rows[:, :5], ref[:, :5]), w               # x y z, t, t_stdv
+        np.testing.assert_allclose(rows[:, 5:], ref[:, 5:], rtol=1e-10, atol=0)
+
+
+@pytest.mark.parametrize("case", helpers.XCORR_CASES)
+def test_programs_equal_compiled_reference(case, tmp_path, monkeypatch):
+    fx, env, g = _fixture_dir(tmp_path / "files", case)
+    _fixture_dir(tmp_path / "dev", case)
+    n, n_win = g["n"], g["n_win"]
+    monkeypatch.chdir(tmp_path / "files")
+    corr.main(["tremor.in"])
+    for p, (a, b) in enumerate(corr.pairs(env.stations)):
+        v = corr.read_corr(f"{a}.{b}.corr").reshape(n_win, n, 3)
+        np.testing.assert_allclose(v[:, :, 2], fx["cc"][:, p], rtol=0, atol=1e-12)
+        np.testing.assert_allclose(corr.read_max_corr(f"{a}.{b}.max_corr")[:, 1], fx["cc_max"][:, p], rtol=0, atol=1e-12)
+    measure.main(["tremor.in"])
+    _check_step3_files(tmp_path / "files", fx, env, g)
+    monkeypatch.chdir(tmp_path / "dev")
+    measure.main(["tremor.in", "--from-envelopes"])
+    _check_step3_files(tmp_path / "dev", fx, env, g)
+
+
+# ---- k_xcorr at the shapes and edges where it could go wrong, against a long-double direct sum -------------------------
+
+def _prep_exact(w):
+    """src/cls_correlator.f90:207-212 in long double (the taper factors in double, as the kernel takes them)"""
+    n = w.size
+    nleng = int(n * 0.05)
+    f = np.ones(n)
+    for q in range(nleng):
+        f[q] = f[n - 1 - q] = 0.5 * (1.0 - math.cos(q * math.pi / nleng))
+    x = np.asarray(w, dtype=np.longdouble) * np.asarray(f, dtype=np.longdouble)
+    x = x - np.sum(x) / n
+    return x / np.sqrt(np.sum(x * x))
+
+
+def _xcorr_exact(amps, n, n_step, n_win, prs):
+    """-> cc (n_win, len(prs), n) in the reference's lag order from long-double sums"""
+    out = np.empty((n_win, len(prs), n))
+    for w in range(n_win):
+        r = {s: _prep_exact(amps[s, w * n_step:w * n_step + n]) for s in {s for pr in prs for s in pr}}
+        for p, (i, j) in enumerate(prs):
+            out[w, p] = rs.reference_order(rs.circ_exact(r[i], r[j]))
+    return out
+
+
+def _envelopes(rng, n_sta, n_smp, n):
+    """positive envelopes: a level, noise, and a burst of n/8 samples somewhere in every row"""
+    m = np.arange(n_smp)
+    a = 1.0 + rng.random((n_sta, n_smp))
+    for s in range(n_sta):
+        c = rng.integers(0, n_smp)
+        a[s] += 8.0 * np.exp(-0.5 * ((m - c) / (n / 8.0 + 0.5)) ** 2)
+    return a
+
+
+def _bound(n):
+    return 2.0 * n * 2.0 ** -53
+
+
+XC_SIZES = [2, 20, 22, 62, 64, 66, 130, 1022, 1024, 1026, 2050, 3000, 4094]
+
+
+@pytest.mark.parametrize("k,n", list(enumerate(XC_SIZES)))
+def test_xcorr_shapes_against_exact_sums(k, n):
+    # n_step below, at and above n in turn; 3 stations up to 1026 samples, 2 above (one pair, n_sta = 2)
+    n_step = (n // 2 + 1, n, n + 3)[k % 3]
+    n_sta, n_win = (3, 3) if n <= 1026 else (2, 2)
+    rng = np.random.default_rng(100 + n)
+    amps = _envelopes(rng, n_sta, (n_win - 1) * n_step + n + 1, n)
+    cc, mx = xcorr(amps, n, n_step, n_win)
+    prs = [(i, j) for i in range(n_sta - 1) for j in range(i + 1, n_sta)]
+    ex = _xcorr_exact(amps, n, n_step, n_win, prs)
+    assert np.max(np.abs(cc - ex)) <= _bound(n), np.max(np.abs(cc - ex))
+    assert np.array_equal(mx, cc.max(axis=2))
+    assert np.max(np.abs(mx - ex.max(axis=2))) <= _bound(n)
+
+
+@pytest.mark.parametrize("n_sta,n,n_step,n_win,pair0,n_pairs,pad_env,pad_cc", [
+    (5, 300, 100, 4, 2, 6, 37, 5),            # a middle range of pairs
+    (100, 66, 70, 3, 4949, 1, 11, 3),         # the last pair of 100 stations
+    (2, 1026, 500, 2, 0, 1, 1, 7),            # two stations
+    (4, 3000, 3000, 2, 0, 6, 64, 2),          # several lags per thread
+])
+def test_xcorr_dev_strides_leave_padding_alone(n_sta, n, n_step, n_win, pair0, n_pairs, pad_env, pad_cc):
+    """htm_xcorr_dev on a torch buffer with row stride ld_env > n_smp and ld_cc > n_pairs: NaN in every padding element
+    of the input must not reach a result, and NaN in the padding columns of cc and cc_max must stay untouched."""
+    import torch
+
+    rng = np.random.default_rng(n_sta + n)
+    n_smp = (n_win - 1) * n_step + n
+    host = np.full((n_sta, n_smp + pad_env), np.nan)
+    host[:, :n_smp] = _envelopes(rng, n_sta, n_smp, n)
+    dev = torch.device("cuda", 0)
+    d_env = torch.from_numpy(host).to(dev)
+    ld_cc = n_pairs + pad_cc
+    d_cc = torch.full((n_win * n, ld_cc), float("nan"), dtype=torch.float64, device=dev)
+    d_mx = torch.full((n_win, ld_cc), float("nan"), dtype=torch.float64, device=dev)
+    check(_lib.load().htm_xcorr_dev(0, C.c_void_p(d_env.data_ptr()), n_smp + pad_env, n_smp, n_sta, n, n_step, n_win,
+                                    pair0, n_pairs, C.c_void_p(d_cc.data_ptr()), ld_cc, C.c_void_p(d_mx.data_ptr()), None))
+    torch.cuda.synchronize()
+    cc, mx = d_cc.cpu().numpy(), d_mx.cpu().numpy()
+    assert np.all(np.isnan(cc[:, n_pairs:])) and np.all(np.isnan(mx[:, n_pairs:]))
+    all_prs = [(i, j) for i in range(n_sta - 1) for j in range(i + 1, n_sta)]
+    ex = _xcorr_exact(host[:, :n_smp], n, n_step, n_win, all_prs[pair0:pair0 + n_pairs])
+    got = cc[:, :n_pairs].reshape(n_win, n, n_pairs).transpose(0, 2, 1)
+    assert np.max(np.abs(got - ex)) <= _bound(n)
+    assert np.array_equal(mx[:, :n_pairs], got.max(axis=2))
+
+
+def test_thresholds_of_correlograms_take_the_slab_path_exactly():
+    """k_xcorr output of 2000 windows x 60 pairs at n = 300 (n_mod * n_par = 36 M: the slab select) in a buffer of
+    row stride 64 > 60, through htm_quantiles_dev: every selected element equals np.sort's"""
+    import torch
+
+    n, n_step, n_win, n_sta, pair0, n_pairs, ld = 300, 150, 2000, 12, 3, 60, 64
+    rng = np.random.default_rng(77)
+    amps = _envelopes(rng, n_sta, (n_win - 1) * n_step + n, n)
+    env = corr.Envelopes(amps, device=0)
+    d_cc = torch.full((n_win * n, ld), float("nan"), dtype=torch.float64, device=env.dev)
+    d_mx = torch.full((n_win, ld), float("nan"), dtype=torch.float64, device=env.dev)
+    env.correlate(n, n_step, n_win, pair0, n_pairs, d_cc, d_mx)
+    n_mod = n * n_win
+    r = measure.threshold_rank(n, n_win, 0.995)
+    thr = measure._thresholds_dev(d_cc, n_mod, n_pairs, r, 0)
+    ranks = (1, r, n_mod)
+    out = torch.empty((n_pairs, 3), dtype=torch.float64, device=env.dev)
+    check(_lib.load().htm_quantiles_dev(0, C.c_void_p(d_cc.data_ptr()), n_mod, n_pairs, ld, (C.c_int * 3)(*ranks),
+                                        C.c_void_p(out.data_ptr()), None))
+    torch.cuda.synchronize()
+    srt = np.sort(d_cc.cpu().numpy()[:, :n_pairs], axis=0)
+    assert not np.any(np.isnan(srt))
+    assert np.array_equal(thr, srt[r - 1])
+    assert np.array_equal(out.cpu().numpy(), srt[[q - 1 for q in ranks]].T)
+    assert np.all(np.isnan(d_mx.cpu().numpy()[:, n_pairs:]))
+
+
+# ---- k_measure at the shapes and edges where it could go wrong ---------------------------------------------------------
+
+def _pulses(rng, n_det, n_sta, n, width=None):
+    m = np.arange(n)
+    x = 0.5 + 0.2 * rng.random((n_det, n_sta, n))
+    w = width or (n / 40 + 1)
+    for d in range(n_det):
+        for s in range(n_sta):
+            c = n / 2 + rng.integers(-n // 6, n // 6 + 1)
+            x[d, s] += 6.0 * np.exp(-0.5 * ((m - c) / w) ** 2)
+    return x
+
+
+def _measure_vs_exact(x, dt):
+    """measure_windows against the restatement with long-double direct correlations; near-tied pairs (top two within
+    1e-12) are counted, not compared.  NaN and inf results (zero-energy stations) must match in place."""
+    t, ts, a, asd = measure.measure_windows(x, dt)
+    n_pairs = n_tied = 0
+    S = x.shape[1]
+    for d in range(x.shape[0]):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rt, rts, ra, rasd, lag, gap = rs.measure(x[d], dt, circ=rs.circ_exact)
+        n_pairs += S * (S - 1) // 2
+        tied = int(np.count_nonzero(np.triu(gap < 1e-12, 1)))
+        n_tied += tied
+        if tied:
+            continue
+        assert np.array_equal(t[d], rt), d
+        assert np.array_equal(ts[d], rts), d
+        np.testing.assert_allclose(a[d], ra, rtol=1e-10, atol=1e-13, equal_nan=True)
+        np.testing.assert_allclose(asd[d], rasd, rtol=1e-10, atol=1e-13, equal_nan=True)
+    assert n_tied <= 1e-3 * n_pairs, (n_tied, n_pairs)
+    return t, ts, a, asd
+
+
+@pytest.mark.parametrize("n_sta,n", [(5, 301), (4, 1025), (5, 20), (5, 66), (4, 1026), (3, 3000), (3, 20), (130, 64)])
+def test_measure_shapes_against_exact_sums(n_sta, n):
+    # odd n; the taper inside one wave; several samples per thread; stations outnumbering the threads (130 > 64)
+    rng = np.random.default_rng(7 * n + n_sta)
+    x = _pulses(rng, 2 if n_sta < 100 else 1, n_sta, n)
+    _measure_vs_exact(x, 0.25)
+
+
+@pytest.mark.parametrize("n", [64, 300, 1026])
+def test_measure_maximum_at_half_window_and_shifts_off_both_ends(n):
+    """pair (0, 1) peaks at natural lag n/2 exactly, where the sign convention switches (lag -n/2 dt: idx < n/2 gives
+    idx dt, else (idx - n) dt); the large lags then shift stations by more than n/4 samples in both directions"""
+    m = np.arange(n)
+    pulse = lambda c: 0.05 + 10.0 * np.exp(-0.5 * ((m - c) / 2.0) ** 2)
+    q = n // 4
+    x = np.stack([pulse(q), pulse(q + n // 2), pulse(q + 1), pulse(q + n // 2 - 2), pulse(2 * q)])[None]
+    t, ts, a, asd = _measure_vs_exact(x, 0.5)
+    lag = rs.optimize_cc(x[0], 0.5, rs.circ_exact)[2]
+    assert lag[0, 1] == -(n // 2) * 0.5                  # the maximum at index n/2 exactly
+    it = [corr.nint(v / 0.5) for v in t[0]]
+    assert max(it) > n // 8 and min(it) < -n // 8        # samples pushed off both ends
+    assert np.all(np.isfinite(a))
+
+
+def test_measure_zero_energy_station_nan_and_inf_in_place():
+    rng = np.random.default_rng(31)
+    x = _pulses(rng, 3, 5, 300)
+    x[0, 0] = 0.0               # the first station: 0/0 in every rel(0, j)
+    x[1, 3] = 0.0               # a later one: log(0 / sxx(i)) = -inf
+    x[2, 4] = 0.0               # the last one
+    t, ts, a, asd = _measure_vs_exact(x, 1.0)
+    assert np.any(np.isnan(a)) and np.any(np.isinf(a[1:]) | np.isnan(a[1:]))
+
+
+def test_measure_windows_split_over_launches_same_bits(monkeypatch):
+    """HTM_MEASURE_MB: one window per launch, 7 per launch (7 + 7 + 6), all in one launch -- identical bits"""
+    rng = np.random.default_rng(41)
+    n_det, S, n = 20, 6, 300
+    x = _pulses(rng, n_det, S, n)
+    x[5, 2] = 0.0               # NaN / inf results travel through the chunk copies too
+    per_win = (S * n + S * S + 5 * S) * 8
+    runs = []
+    for mb in (None, 1e-9, 7.5 * per_win / 2 ** 20):
+        if mb is None:
+            monkeypatch.delenv("HTM_MEASURE_MB", raising=False)
+        else:
+            monkeypatch.setenv("HTM_MEASURE_MB", repr(mb))
+        runs.append(measure.measure_windows(x, 0.5))
+    for r in runs[1:]:
+        for u, v in zip(runs[0], r):
+            assert u.tobytes() == v.tobytes()
+    monkeypatch.delenv("HTM_MEASURE_MB", raising=False)
+    _measure_vs_exact(x[:5], 0.5)

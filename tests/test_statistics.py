@@ -44,6 +44,16 @@ def test_rank_rule_is_single_precision():
     assert st.expected_n_mod(20000, 10000, 2, 1, 100) == 200
 
 
+def test_quantiles_refuse_ranks_beyond_int_max():
+    """ctypes.c_int would wrap a rank silently (2^32 + 7 -> 7, a valid rank of another element): refused first"""
+    from hypotremormcmc_amd import statistics
+
+    with pytest.raises(ValueError, match="exceeds"):
+        statistics.quantiles(np.zeros((10, 2)), n_mod=2 ** 32 + 14, device=-1)
+    with pytest.raises(ValueError, match="exceeds"):
+        statistics.quantiles(np.zeros((10, 2)), n_mod=2 ** 31, device=-1)
+
+
 def test_remove_double_counts_rule():
     """two consecutive windows whose medians both lie inside the overlap of their 95 % boxes collapse into the
     first; a gap in the ids or a median outside the overlap keeps both (src/cls_statistics.f90:150-185)"""

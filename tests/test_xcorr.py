@@ -13,7 +13,7 @@ from hypotremormcmc_amd.obs_data import ObsData
 from hypotremormcmc_amd.param import Param, ParamError
 from hypotremormcmc_amd.select import read_detected_win
 
-from . import xcorr_restatement as rs
+from . import helpers, xcorr_restatement as rs
 
 
 def test_restatement_fft_equals_direct_sum():
@@ -149,3 +149,144 @@ def test_synthetic_envelopes_files(tmp_path):
     c = (3 - 1) * 50 + 50
     assert env.amps[1][c + 2] - 1.0 == pytest.approx(10.0 * math.exp(0.5))
     assert np.argmax(env.amps[3][c - 20:c + 20]) == 20 + 3
+
+
+# ---- pinned to the compiled reference (tests/golden/xcorr_*.npz, written by the unmodified steps 2 and 3 linked with
+# the FFT stand-in oracle/ref_dft.c; make_golden.py)
+
+@pytest.mark.parametrize("n", [1, 2, 3, 10, 31, 64, 300])
+def test_reference_fft_stand_in_equals_numpy(n):
+    from oracle import oracle
+
+    x = np.random.default_rng(n).standard_normal(n)
+    X = oracle.ref_dft_r2c(x)
+    np.testing.assert_allclose(X, np.fft.rfft(x), rtol=0, atol=1e-13 * max(1, n))
+    # c2r: unnormalised, the imaginary parts of bin 0 and (n even) bin n/2 ignored
+    c = np.fft.rfft(np.random.default_rng(n + 1).standard_normal(n))
+    c[0] += 5j
+    if n % 2 == 0:
+        c[-1] += 7j
+    y = oracle.ref_dft_c2r(c, n)
+    want = np.fft.irfft(np.where(np.arange(c.size) == 0, c.real, c) if n % 2 else
+                        np.where((np.arange(c.size) == 0) | (np.arange(c.size) == n // 2), c.real, c), n) * n
+    np.testing.assert_allclose(y, want, rtol=0, atol=1e-13 * max(1, n))
+    np.testing.assert_allclose(oracle.ref_dft_c2r(oracle.ref_dft_r2c(x), n), n * x, rtol=0, atol=1e-13 * n)
+
+
+@pytest.mark.parametrize("case", helpers.XCORR_CASES)
+def test_restatement_correlograms_equal_reference(case):
+    fx, env, g = helpers.load_xcorr_case(case)
+    n, n_step, n_win = g["n"], g["n_step"], g["n_win"]
+    cc, cc_max = rs.correlate(env.amps, n, n_step, n_win)
+    np.testing.assert_allclose(cc, fx["cc"], rtol=0, atol=1e-13)
+    np.testing.assert_allclose(cc_max, fx["cc_max"], rtol=0, atol=1e-13)
+    assert np.array_equal(fx["cc_max"], fx["cc"].max(axis=2))
+
+
+@pytest.mark.parametrize("case", helpers.XCORR_CASES)
+def test_threshold_rank_and_detection_equal_reference(case):
+    fx, env, g = helpers.load_xcorr_case(case)
+    n, n_win, alpha = g["n"], g["n_win"], float(fx["alpha"])
+    assert measure.threshold_rank(n, n_win, alpha) == int(fx["thred_rank"])
+    # the threshold is the element of that rank among the reference's own .corr values, as cc_thred.dat prints it
+    ref_cc = fx["cc"]
+    for p in range(ref_cc.shape[1]):
+        assert rs.threshold(ref_cc[:, p], alpha) == fx["thred"][p]
+        assert np.sort(ref_cc[:, p].ravel())[measure.threshold_rank(n, n_win, alpha) - 1] == fx["thred"][p]
+    assert np.all(np.abs(fx["thred_text"] - fx["thred"]) <= 2 * np.spacing(fx["thred"]))
+    # detection on the reference's own cc_max and thresholds, then on the restatement's
+    det = fx["detected"].tolist()
+    assert measure.detect(fx["cc_max"], fx["thred"], int(fx["n_pair_thred"])) == det
+    cc, cc_max = rs.correlate(env.amps, n, g["n_step"], n_win)
+    thr = [rs.threshold(cc[:, p], alpha) for p in range(cc.shape[1])]
+    np.testing.assert_allclose(thr, fx["thred"], rtol=0, atol=1e-13)
+    assert measure.detect(cc_max, thr, int(fx["n_pair_thred"])) == det
+    t_win, t_step = n * g["dt"], g["n_step"] * g["dt"]
+    assert [(w - 1) * t_step + 0.5 * t_win for w in det] == fx["detected_time"].tolist()
+
+
+@pytest.mark.parametrize("case", helpers.XCORR_CASES)
+def test_restatement_measurements_equal_reference(case):
+    fx, env, g = helpers.load_xcorr_case(case)
+    det = fx["detected"].tolist()
+    x = measure.gather_windows(list(env.amps), det, g["n"], g["n_step"])
+    S = g["n_sta"]
+    n_tied = 0
+    for d in range(len(det)):
+        rt, rts, ra, rasd, lag, gap = rs.measure(x[d], g["dt"])
+        if np.any(np.triu(gap < 1e-12, 1)):          # a near-tied pair may pick another lag: counted, not compared
+            n_tied += 1
+            continue
+        opt = fx["opt"][d]
+        assert np.array_equal(opt[:, 3], rt), d
+        assert np.array_equal(opt[:, 4], rts), d
+        np.testing.assert_allclose(opt[:, 5], ra, rtol=1e-12, atol=0)
+        np.testing.assert_allclose(opt[:, 6], rasd, rtol=1e-12, atol=0)
+    assert n_tied == 0
+    assert fx["opt"].shape == (len(det), S, 7)
+
+
+@pytest.mark.parametrize("case", helpers.XCORR_CASES)
+def test_corr_writers_reproduce_reference_files(case, tmp_path):
+    """the .corr / .max_corr streams of the first pair, written from the reference's own values, are its bytes"""
+    import hashlib
+
+    fx, env, g = helpers.load_xcorr_case(case)
+    n, dt = g["n"], g["dt"]
+    p, q = str(tmp_path / "a.corr"), str(tmp_path / "a.max_corr")
+    corr.write_corr(p, fx["cc"][:, 0], n, dt, g["n_step"] * dt, n * dt)
+    corr.write_max_corr(q, fx["cc_max"][:, 0], g["n_step"] * dt, n * dt)
+    assert hashlib.sha256(open(p, "rb").read()).hexdigest() == str(fx["corr0_sha256"])
+    assert hashlib.sha256(open(q, "rb").read()).hexdigest() == str(fx["max_corr0_sha256"])
+
+
+# ---- limits: ranks and launches that would wrap a 32-bit integer are refused, not wrapped
+
+def test_threshold_rank_refuses_more_values_than_int_max():
+    assert measure.threshold_rank(4096, 524287, 0.5) == 4096 * 524287 // 2          # 2^31 - 4096 values: fine
+    with pytest.raises(SystemExit, match="exceed"):
+        measure.threshold_rank(4096, 524288, 0.5)                                   # 2^31 values
+    with pytest.raises(SystemExit, match="exceed"):
+        measure.threshold_rank(4096, 60 * 24 * 366, 0.999)                          # a year of windows every 60 s
+    with pytest.raises(ValueError, match="rank"):
+        measure._thresholds_dev(None, 2 ** 32 + 7, 1, 2 ** 32 + 7, -1)
+
+
+def test_batch_pairs_stays_below_one_launch():
+    assert corr.xc_threads(2) == 64 and corr.xc_threads(66) == 128 and corr.xc_threads(4096) == 1024
+    for n_win, n, mb in ((4000, 300, 512), (100000, 4096, 1e9), (2 ** 21, 4096, 1e12), (10, 2, 1e12)):
+        b = corr.batch_pairs(n_win, n, mb)
+        assert b >= 1
+        assert b == 1 or n_win * b * corr.xc_threads(n) <= corr.MAX_WORK_ITEMS, (n_win, n, mb, b)
+    assert corr.batch_pairs(2 ** 20, 4096, 1e12) == 3 and corr.batch_pairs(4000, 300, 512) == 512 * 2 ** 20 // (8 * 4000 * 301)
+
+
+def test_c_abi_refuses_launches_and_selects_beyond_32_bits():
+    """The guards answer HTM_EINVAL before any device call (device -1: without them the call would fail in the device
+    selection, never in a launch with undersized buffers)."""
+    import ctypes as C
+
+    from hypotremormcmc_amd import _lib
+
+    lib = _lib.load()
+    buf = np.zeros(64)
+    p = C.c_void_p(buf.ctypes.data)
+    rk = (C.c_int * 3)(1, 2, 3)
+    assert lib.htm_quantiles_dev(-1, p, 2 ** 31, 1, 1, rk, p, None) == -1
+    assert b"n_mod" in lib.htm_last_error()
+    q = buf.ctypes.data_as(_lib.dp)
+    assert lib.htm_quantiles(-1, q, 2 ** 31, 1, rk, q) == -1
+    assert b"n_mod" in lib.htm_last_error()
+    # k_xcorr: 2^22 windows of 4096 samples (1024 work-items each) for one pair is 2^32 work-items: refused
+    n, n_win = 4096, 2 ** 22
+    n_smp = n_win - 1 + n
+    assert lib.htm_xcorr_dev(-1, p, n_smp, n_smp, 2, n, 1, n_win, 0, 1, p, 1, p, None) == -1
+    assert b"work-items" in lib.htm_last_error()
+    # one window fewer fits in a launch: past the guard, the call fails at device -1
+    lib.htm_xcorr_dev(-1, p, n_smp, n_smp, 2, n, 1, n_win - 1, 0, 1, p, 1, p, None)
+    assert b"work-items" not in lib.htm_last_error() and b"device" in lib.htm_last_error().lower()
+    # n = 66 runs 128 work-items per workgroup: 2^25 workgroups of it are 2^32
+    n, n_win = 66, 2 ** 24
+    n_smp = n_win - 1 + n
+    assert lib.htm_xcorr_dev(-1, p, n_smp, n_smp, 3, n, 1, n_win, 0, 2, p, 2, p, None) == -1
+    assert b"work-items" in lib.htm_last_error()

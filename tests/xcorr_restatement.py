@@ -40,6 +40,20 @@ def circ_direct(ri, rj):
     return np.array([sum(ri[m] * rj[(m + k) % n] for m in range(n)) for k in range(n)])
 
 
+def circ_exact(ri, rj):
+    """the same circular correlation summed in long double (each lag exact to a few units of 2^-64 relative to
+    sum |ri rj|), rounded once to float64"""
+    n = ri.size
+    a, b = np.asarray(ri, dtype=np.longdouble), np.asarray(rj, dtype=np.longdouble)
+    out = np.empty(n, dtype=np.longdouble)
+    step = max(1, (1 << 21) // n)
+    m = np.arange(n)
+    for k0 in range(0, n, step):
+        k = np.arange(k0, min(n, k0 + step))
+        out[k] = np.sum(a[None, :] * b[(m[None, :] + k[:, None]) % n], axis=1)
+    return out.astype(np.float64)
+
+
 def reference_order(c):
     """cc(1:n/2) = r2(n/2+1:n), cc(n/2+1:n) = r2(1:n/2) (src/cls_correlator.f90:234-235): lag j - n/2 at j"""
     n = c.size
@@ -64,9 +78,10 @@ def threshold(values, alpha):
     return v[int(v.size * alpha) - 1]
 
 
-def optimize_cc(x, dt):
+def optimize_cc(x, dt, circ=None):
     """src/cls_measurer.f90:463-523 for one window x (n_sta, n); -> t, t_stdv, lag matrix, and the relative gap of
-    each pair's two largest correlation values (near-ties can pick another lag under other rounding)"""
+    each pair's two largest correlation values (near-ties can pick another lag under other rounding).  circ: the
+    natural-order circular correlation (default the FFT form, c2r(conj(r2c(ri)) r2c(rj)) / n, times n)"""
     n_sta, n = x.shape
     r = []
     for i in range(n_sta):
@@ -76,12 +91,13 @@ def optimize_cc(x, dt):
     gap = np.full((n_sta, n_sta), np.inf)
     for i in range(n_sta - 1):
         for j in range(i + 1, n_sta):
-            c = circ_fft(r[i], r[j]) * n
+            c = circ_fft(r[i], r[j]) * n if circ is None else circ(r[i], r[j])
             il = int(np.argmax(c)) + 1                               # maxloc: first maximum, 1-based
             lag[i, j] = (il - 1) * dt if il <= n // 2 else (il - n - 1) * dt
             lag[j, i] = -lag[i, j]
             top = np.sort(c)[-2:]
-            gap[i, j] = abs(top[1] - top[0]) / max(abs(top[1]), 1e-300)
+            if np.any(c):           # all zeros (a zero-energy station): index 0 under any rounding, no near-tie
+                gap[i, j] = abs(top[1] - top[0]) / max(abs(top[1]), 1e-300)
     t = [0.0] * n_sta
     for i in range(n_sta):
         for j in range(n_sta):
@@ -135,8 +151,8 @@ def optimize_amp(x, t, dt):
     return np.array(amp), np.sqrt(np.array(sd) / (n_sta - 2))
 
 
-def measure(x, dt):
+def measure(x, dt, circ=None):
     """one window: t, t_stdv, amp, amp_stdv, lag matrix, top-two gaps"""
-    t, ts, lag, gap = optimize_cc(x, dt)
+    t, ts, lag, gap = optimize_cc(x, dt, circ)
     a, asd = optimize_amp(x, t, dt)
     return t, ts, a, asd, lag, gap
