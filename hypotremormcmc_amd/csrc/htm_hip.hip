@@ -2298,6 +2298,10 @@ int htm_select_regress(int device, int n_sta, int n_win, const double *sta_x, co
 {
     if (!sta_x || !sta_y || !sta_z || !t || !t_err || !a || !a_err || !out) return fail(HTM_EINVAL, "NULL argument");
     if (n_sta < 3 || n_win < 1) return fail(HTM_EINVAL, "need n_sta >= 3 and n_win >= 1 (got %d, %d)", n_sta, n_win);
+    // a wave per window, four per workgroup: the dispatch packet holds the grid in work-items as a uint32_t
+    if (256L * ((n_win + 3L) / 4) > 0xffffffffL)
+        return fail(HTM_EINVAL, "n_win = %d windows need %ld work-items: more than one launch holds (2^32 - 1)", n_win,
+                    256L * ((n_win + 3L) / 4));
     int rc = use_device(device);
     if (rc) return rc;
     std::vector<void *> pool;

@@ -217,19 +217,23 @@ __global__ __launch_bounds__(256) void k_regress(int S, int W, const double *sx,
     const int win = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (win >= W) return;
     const size_t base = (size_t)win * S;
-    // maxloc(a): the FIRST maximum (cls_selector.f90:99)
-    double best = -1.0e300;
-    int near = 0x7fffffff;
+    // maxloc(a) (cls_selector.f90:98) as the reference's compiler evaluates it: the first element that is
+    // not NaN is the candidate, -inf included; a later one replaces it only if strictly greater; a row of NaN gives
+    // station 0.  Each lane scans its stations in ascending order (near < 0: none yet), then the lanes combine with ties
+    // to the lower index: the lowest index of the largest value that is not NaN.  near is always a valid station.
+    double best = -INFINITY;
+    int near = -1;
     for (int j = lane; j < S; j += 64) {
         const double v = a[base + j];
-        if (v > best) { best = v; near = j; }
+        if (near < 0 ? !isnan(v) : v > best) { best = v; near = j; }
     }
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) {
         const double ov = __shfl_xor(best, m);
         const int oi = __shfl_xor(near, m);
-        if (ov > best || (ov == best && oi < near)) { best = ov; near = oi; }
+        if (oi >= 0 && (near < 0 || ov > best || (ov == best && oi < near))) { best = ov; near = oi; }
     }
+    if (near < 0) near = 0;
     const double nx = sx[near], ny = sy[near];
     double r[10];
 #pragma unroll

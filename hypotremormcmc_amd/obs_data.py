@@ -9,6 +9,17 @@ import os
 import numpy as np
 
 
+def maxloc(a):
+    """0-based Fortran `maxloc` of every row of `a` (last axis) as the reference's compiler evaluates it (DESIGN.md
+    §3.3): the first element that is not NaN is the candidate, -inf included; a later one replaces it only if strictly
+    greater.  That is the lowest index of the largest value that is not NaN; a row of NaN gives 0."""
+    a = np.asarray(a, dtype=np.float64)
+    nan = np.isnan(a)
+    v = np.where(nan, -np.inf, a)
+    hit = (v == v.max(axis=-1, keepdims=True)) & ~nan
+    return np.argmax(hit, axis=-1)      # the first hit; none (a row of NaN) -> 0
+
+
 class ObsData:
     def __init__(self, win_id, n_sta, sta_x, sta_y, verb=False, directory="."):
         self.win_id = [int(w) for w in win_id]
@@ -50,7 +61,7 @@ class ObsData:
                 self.t_obs[i, j], self.t_stdv[i, j], self.a_obs[i, j], self.a_stdv[i, j] = v[3], v[4], v[5], v[6]
 
     def make_initial_guess(self):
-        ista = np.argmax(self.a_obs, axis=1)  # first maximum, like maxloc
+        ista = maxloc(self.a_obs)
         return self.sta_x[ista].copy(), self.sta_y[ista].copy()
 
     def get_t_obs(self): return self.t_obs

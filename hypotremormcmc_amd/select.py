@@ -31,11 +31,17 @@ def regress(sta_x, sta_y, sta_z, z_guess, t, t_err, a, a_err, device=0):
     """rows {vs, b, t0, a0, cc_t, cc_a} per window; t, t_err, a, a_err of shape (n_win, n_sta)
     (src/cls_selector.f90:75-132)."""
     t = np.ascontiguousarray(t, dtype=np.float64)
+    if t.ndim != 2:
+        raise ValueError("t must have shape (n_win, n_sta)")
     n_win, n_sta = t.shape
     arrs = [np.ascontiguousarray(v, dtype=np.float64) for v in (sta_x, sta_y, sta_z, t, t_err, a, a_err)]
     for v in arrs[:3]:
         if v.size != n_sta:
             raise ValueError("station arrays must have n_sta entries")
+    # the C side reads n_win * n_sta doubles of each: a smaller array would be read past its end
+    for name, v in zip(("t_err", "a", "a_err"), arrs[4:]):
+        if v.shape != t.shape:
+            raise ValueError("%s has shape %s, t has %s" % (name, v.shape, t.shape))
     out = np.empty((n_win, 6))
     check(_lib.load().htm_select_regress(int(device), n_sta, n_win, _p(arrs[0]), _p(arrs[1]), _p(arrs[2]), float(z_guess),
                                          _p(arrs[3]), _p(arrs[4]), _p(arrs[5]), _p(arrs[6]), _p(out)))

@@ -318,7 +318,11 @@ int htm_quantiles_dev(int device, const double *d_samples, long n_mod, long n_pa
  * amplitudes are corrected for geometrical spreading (+ ln d), and arrival time and amplitude are regressed
  * against distance with weights 1/err^2.  t, t_err, a, a_err: (n_sta, n_win) column-major = the columns 4-7 of the
  * opt_data.NNNNNN.dat files; out[n_win][6] = {vs, b, t0, a0, cc_t, cc_a}: the columns of a regress.dat row after
- * the window id (src/hypo_tremor_select.f90:124-125).  Host pointers; synchronous. */
+ * the window id (src/hypo_tremor_select.f90:124-125).  The station of largest amplitude is Fortran maxloc(a) as the
+ * reference's compiler evaluates it: the first station whose a is not NaN is the candidate, -inf
+ * included; a later one replaces it only if its a is strictly greater, so ties go to the lower index; a window whose
+ * a are all NaN takes station 1.  NaN and inf inputs give NaN or inf outputs as the reference's arithmetic does.
+ * n_sta >= 3; n_win < 2^26 - 3 (a wave per window: 64 n_win work-items in one launch).  Host pointers; synchronous. */
 int htm_select_regress(int device, int n_sta, int n_win, const double *sta_x, const double *sta_y,
                        const double *sta_z, double z_guess, const double *t, const double *t_err,
                        const double *a, const double *a_err, double *out);

@@ -377,6 +377,16 @@ struct orc_job {
 
 static const double EPS = 2.220446049250313e-16; /* epsilon(1.d0) */
 
+/* Fortran maxloc(a(1:n)) as the reference's compiler evaluates it, 0-based: the first element that is
+ * not NaN is the candidate, -inf included; a later one replaces it only if strictly greater; a row of NaN gives 0. */
+static int orc_maxloc(int n, const double *a)
+{
+    int k = -1;
+    for (int j = 0; j < n; ++j)
+        if (k < 0 ? !isnan(a[j]) : a[j] > a[k]) k = j;
+    return k < 0 ? 0 : k;
+}
+
 orc_job *orc_job_create(const orc_params *p, int n_sta, int n_events, const double *sta_x,
                         const double *sta_y, const double *sta_z, const double *t_obs,
                         const double *t_stdv, const double *a_obs, const double *a_stdv)
@@ -393,13 +403,11 @@ orc_job *orc_job_create(const orc_params *p, int n_sta, int n_events, const doub
     job->p_qs = p->solve_qs ? 0.025 : 0.0;
     job->p_a_corr = p->solve_a_corr ? 0.025 : 0.0;
 
-    /* obs%make_initial_guess: src/cls_obs_data.f90:120-134 (maxloc = first maximum) */
+    /* obs%make_initial_guess: src/cls_obs_data.f90:120-134 (maxloc) */
     double *x_mu = (double *)malloc(n_events * sizeof(double));
     double *y_mu = (double *)malloc(n_events * sizeof(double));
     for (int i = 0; i < n_events; ++i) {
-        int ista = 0;
-        for (int j = 1; j < n_sta; ++j)
-            if (a_obs[(size_t)i * n_sta + j] > a_obs[(size_t)i * n_sta + ista]) ista = j;
+        const int ista = orc_maxloc(n_sta, a_obs + (size_t)i * n_sta);
         x_mu[i] = sta_x[ista];
         y_mu[i] = sta_y[ista];
     }
@@ -826,8 +834,7 @@ void orc_select_regress(int n_sta, int n_win, const double *sta_x, const double 
     for (int i = 0; i < n_win; ++i) {
         const double *ti = t + (size_t)i * n_sta, *te = t_err + (size_t)i * n_sta;
         const double *ai = a + (size_t)i * n_sta, *ae = a_err + (size_t)i * n_sta;
-        int near = 0;                                                         /* maxloc(a): first maximum, cls_selector.f90:99 */
-        for (int j = 1; j < n_sta; ++j) if (ai[j] > ai[near]) near = j;
+        const int near = orc_maxloc(n_sta, ai);                              /* maxloc(a), cls_selector.f90:98 */
         for (int j = 0; j < n_sta; ++j) {                                     /* :62-64: source at the nearest station's x, y and depth z_guess */
             const double dx = sta_x[j] - sta_x[near], dy = sta_y[j] - sta_y[near], dz = sta_z[j] - z_guess;
             d[j] = sqrt(dx * dx + dy * dy + dz * dz);

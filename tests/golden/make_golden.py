@@ -17,6 +17,10 @@ Cases
   c3     1000 ev x 64 stn, seed 1, 1 rank x 8 chains, 600 it: inputs are NOT stored (2 MB) -- the seeded
          generator reproduces them; a checksum of the inputs is stored instead.
   select, select_wide   step 4 (hypo_tremor_select): 60 windows x 12 stations under 2 ranks, 33 x 70 under 3 ranks
+  select_edges, select_min   step 4 on constructed windows (70 and 3 stations): rows of NaN, -inf, ties of the largest
+         amplitude, +-0, a station at depth z_guess, zero errors, +inf; each under mpiexec -np 1 and -np 3 (the outputs
+         must be identical).  The inputs are stored; so is each window's nearest station, recovered from the
+         reference's dist_plot.NNNNNN.dat.
   c4     1000 ev x 64 stn, seed 1, 8 ranks x 8 chains = 64 tempered chains, temp_high = 200, 400 it (BASELINE
          configs[3], run under mpiexec -np 8); inputs as for c3.
   xcorr_overlap, xcorr_gapped   steps 2 and 3 (hypo_tremor_correlate, hypo_tremor_measure) on seeded
@@ -248,6 +252,169 @@ def run_select_case(name, spec):
         shutil.rmtree(work, ignore_errors=True)
 
 
+EDGE_CASES = {
+    # step 4 on windows built for maxloc's edges and the NaN / inf paths; 70 stations: lanes 0-5 of a wave hold two each
+    "select_edges": dict(n_sta=70, seed=31, z_guess=1.25, z_station=17, vs_min=0.5, vs_max=50.0, b_min=-1.0, b_max=1.0),
+    # 3 stations, the fewest htm_select_regress takes
+    "select_min": dict(n_sta=3, seed=32, z_guess=0.75, z_station=2, vs_min=0.5, vs_max=50.0, b_min=-1.0, b_max=1.0),
+}
+
+
+def edge_rows(S, kz):
+    """[(label, nearest station as the reference's maxloc rule gives it, edit of one window's t, t_err, a, a_err)]"""
+    def top(*js):                       # the same maximum at every j of js
+        def f(t, te, a, ae):
+            m = a.max() + 0.5
+            a[list(js)] = m
+        return f
+
+    def fill(*pairs):                   # (index or slice, value) in order
+        def f(t, te, a, ae):
+            for ix, v in pairs:
+                a[ix] = v
+        return f
+
+    def both(f, g):
+        return lambda *x: (f(*x), g(*x))
+
+    def zero_amp(t, te, a, ae):
+        a[:] = 0.0
+        ae[:] = 0.0
+
+    def signed_zeros(j0, j1):
+        def f(t, te, a, ae):
+            a[:] = -(np.abs(a) + 0.1)
+            a[j0] = -0.0
+            a[j1] = 0.0
+        return f
+
+    def t_err_zero(j):
+        def f(t, te, a, ae):
+            te[j] = 0.0
+        return f
+
+    nan, inf = float("nan"), float("inf")
+    if S < 64:                          # the small case: every station in its own lane
+        return [("all NaN", 0, fill((slice(None), nan))),
+                ("a[0] NaN, maximum at 2", 2, both(top(2), fill((0, nan)))),
+                ("a[0] NaN, the rest -inf", 1, fill((slice(None), -inf), (0, nan))),
+                ("all -inf", 0, fill((slice(None), -inf))),
+                ("-inf, NaN, -1e301", 2, fill((0, -inf), (1, nan), (2, -1e301))),
+                ("amplitudes and their errors 0", 0, zero_amp),
+                ("equal maxima at 0 and 2", 0, top(0, 2)),
+                ("-0.0 at 0, +0.0 at 1", 0, signed_zeros(0, 1)),
+                ("maximum at the station at depth z_guess", kz, top(kz)),
+                ("maximum at 1, t_err 0 at 0", 1, both(top(1), t_err_zero(0))),
+                ("+inf at 1", 1, fill((1, inf))),
+                ("maximum at 0", 0, top(0))]
+    mix = fill((slice(0, None, 3), -inf), (slice(1, None, 3), nan), (slice(2, None, 3), -1e302), (40, -1e301))
+    return [("all NaN", 0, fill((slice(None), nan))),
+            ("a[0] NaN, maximum at 66", 66, both(top(66), fill((0, nan)))),
+            ("a[0] NaN, the rest -inf", 1, fill((slice(None), -inf), (0, nan))),
+            ("all -inf", 0, fill((slice(None), -inf))),
+            ("-inf / NaN / -1e302, maximum -1e301 at 40", 40, mix),
+            ("amplitudes and their errors 0", 0, zero_amp),
+            ("equal maxima at 2 and 65", 2, top(2, 65)),
+            ("equal maxima at 1 and 65", 1, top(1, 65)),
+            ("equal maxima at 3 and 64", 3, top(3, 64)),
+            ("-0.0 at 5, +0.0 at 9, the rest negative", 5, signed_zeros(5, 9)),
+            ("maximum at the station at depth z_guess", kz, top(kz)),
+            ("maximum at 30, t_err 0 at 11", 30, both(top(30), t_err_zero(11))),
+            ("+inf at 20", 20, fill((20, inf))),
+            ("maximum at 0", 0, top(0)),
+            ("maximum at 63", 63, top(63)),
+            ("maximum at 64", 64, top(64)),
+            ("maximum at 69", 69, top(69))]
+
+
+def edge_inputs(spec):
+    """generic, distinct stations (one at depth z_guess) and per-window t, t_err, a, a_err edited per edge_rows"""
+    S, kz, zg = spec["n_sta"], spec["z_station"], spec["z_guess"]
+    rng = np.random.default_rng(spec["seed"])
+    sx, sy, sz = rng.uniform(-50.0, 50.0, S), rng.uniform(-50.0, 50.0, S), rng.uniform(0.0, 2.0, S)
+    sz[kz] = zg
+    rows = edge_rows(S, kz)
+    W = len(rows)
+    ev = np.stack([rng.uniform(-40.0, 40.0, W), rng.uniform(-40.0, 40.0, W), rng.uniform(3.0, 15.0, W)], axis=1)
+    d = np.sqrt((ev[:, None, 0] - sx) ** 2 + (ev[:, None, 1] - sy) ** 2 + (ev[:, None, 2] - sz) ** 2)
+    t = 5.0 + d / 3.0 + rng.normal(0.0, 0.1, (W, S))
+    a = 2.0 - 0.03 * d - np.log(d) + rng.normal(0.0, 0.05, (W, S))
+    t_err, a_err = rng.uniform(0.05, 0.2, (W, S)), rng.uniform(0.02, 0.1, (W, S))
+    for w, (_, _, edit) in enumerate(rows):
+        edit(t[w], t_err[w], a[w], a_err[w])
+    return sx, sy, sz, t, t_err, a, a_err, rows
+
+
+def nearest_from_dist_plot(path, sx, sy, sz, zg):
+    """the station whose distances reproduce the first column of the reference's dist_plot.NNNNNN.dat"""
+    col = np.array([float(v) for v in open(path).read().split()]).reshape(sx.size, 5)[:, 0]
+    hits = [k for k in range(sx.size)
+            if np.array_equal(np.sqrt((sx - sx[k]) * (sx - sx[k]) + (sy - sy[k]) * (sy - sy[k]) + (sz - zg) * (sz - zg)), col)]
+    assert len(hits) == 1, (path, hits)
+    return hits[0]
+
+
+def run_edge_once(work, spec, inputs, n_procs):
+    """reference step 4 under mpiexec -np n_procs -> regress rows, selected ids, nearest station per window (0-based)"""
+    sx, sy, sz, t, t_err, a, a_err, rows = inputs
+    S, W = sx.size, t.shape[0]
+    with open(os.path.join(work, "station_xy.list"), "w") as f:
+        for j in range(S):
+            f.write("S%03d %.17g %.17g %.17g 1.0 1.0\n" % (j + 1, sx[j], sy[j], sz[j]))
+    with open(os.path.join(work, "detected_win.dat"), "w") as f:
+        for w in range(W):
+            f.write("%d %.1f\n" % (w + 1, 150.0 * w))
+    for w in range(W):
+        with open(os.path.join(work, "opt_data.%06d.dat" % (w + 1)), "w") as f:
+            for j in range(S):
+                f.write("%.17g %.17g %.17g %.17g %.17g %.17g %.17g\n" % (sx[j], sy[j], sz[j], t[w, j], t_err[w, j], a[w, j], a_err[w, j]))
+    keys = ("z_guess", "vs_min", "vs_max", "b_min", "b_max")
+    with open(os.path.join(work, "select.in"), "w") as fh:
+        fh.write("n_procs = %d\nstation_file = station_xy.list\n" % n_procs)
+        for k in keys:
+            fh.write("%s = %r\n" % (k, spec[k]))
+    subprocess.check_call([MPIEXEC, "-np", str(n_procs), SELECT_BIN, "select.in"], cwd=work,
+                          stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    reg = np.array([float(x) for x in open(os.path.join(work, "regress.dat")).read().split()]).reshape(-1, 7)
+    sel = [int(ln.split()[0]) for ln in open(os.path.join(work, "selected_win.dat")) if ln.strip()]
+    near = [nearest_from_dist_plot(os.path.join(work, "dist_plot.%06d.dat" % (w + 1)), sx, sy, sz, spec["z_guess"])
+            for w in range(W)]
+    return reg, sel, near
+
+
+def run_edge_case(name, spec):
+    """Reference step 4, unmodified, on constructed degenerate windows under 1 and 3 ranks (outputs must be equal, NaN
+    equal to NaN).  Stored: the inputs, regress.dat rows, the selected ids, and each window's nearest station as the
+    reference's own dist_plot file shows it."""
+    inputs = edge_inputs(spec)
+    outs = []
+    for n_procs in (1, 3):
+        work = tempfile.mkdtemp(prefix="htm_golden_edge_")
+        try:
+            outs.append(run_edge_once(work, spec, inputs, n_procs))
+        finally:
+            shutil.rmtree(work, ignore_errors=True)
+    (reg, sel, near), (reg3, sel3, near3) = outs
+    assert np.array_equal(reg[:, :5], reg3[:, :5], equal_nan=True) and sel == sel3 and near == near3, "1 and 3 ranks differ"
+    # The reference zeroes vs, b, t0 and a0 before its MPI_SUM reduction but not cc_t and cc_a
+    # (src/hypo_tremor_select.f90:71-80): under several ranks those two columns also carry what the other ranks'
+    # untouched arrays happened to hold.  The 1-rank run is stored; the 3-rank one must equal it wherever it is not NaN.
+    cc, cc3 = reg[:, 5:], reg3[:, 5:]
+    assert np.all((cc == cc3) | np.isnan(cc3)), "cc columns of 1 and 3 ranks differ beyond the reference's NaN"
+    if np.any(np.isnan(cc3) & ~np.isnan(cc)):
+        print(name, "3 ranks: NaN from the reference's uninitialised cc arrays at", np.argwhere(np.isnan(cc3) & ~np.isnan(cc)).tolist())
+    sx, sy, sz, t, t_err, a, a_err, rows = inputs
+    assert near == [r[1] for r in rows], (near, [r[1] for r in rows])     # the rule DESIGN.md §3.3 states
+    assert np.array_equal(reg[:, 0], np.arange(1, len(rows) + 1))
+    assert 0 < len(sel) < len(rows), sel
+    keys = ("z_guess", "vs_min", "vs_max", "b_min", "b_max")
+    fx = dict(regress=reg, selected=np.array(sel, dtype=np.int32), nearest=np.array(near, dtype=np.int32),
+              labels=np.array([r[0] for r in rows]), in_sta_x=sx, in_sta_y=sy, in_sta_z=sz, in_t=t, in_t_err=t_err,
+              in_a=a, in_a_err=a_err, param_keys=np.array(list(keys)), param_vals=np.array([spec[k] for k in keys]))
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **fx)
+    print(name, "ok:", reg.shape, "selected", sel, "nearest", near)
+
+
 CORRELATE_BIN = os.path.join(ROOT, "oracle", "_ref", "hypo_tremor_correlate_ref")
 MEASURE_BIN = os.path.join(ROOT, "oracle", "_ref", "hypo_tremor_measure_ref")
 XCORR_CASES = {
@@ -343,9 +510,11 @@ def run_xcorr_case(name, spec):
 if __name__ == "__main__":
     if not all(os.path.exists(b) for b in (REF_BIN, PROBE_BIN, STATS_BIN, SELECT_BIN, CORRELATE_BIN, MEASURE_BIN)):
         subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"])
-    for nm in (sys.argv[1:] or list(CASES) + list(SELECT_CASES) + list(XCORR_CASES)):
+    for nm in (sys.argv[1:] or list(CASES) + list(SELECT_CASES) + list(EDGE_CASES) + list(XCORR_CASES)):
         if nm in SELECT_CASES:
             run_select_case(nm, SELECT_CASES[nm])
+        elif nm in EDGE_CASES:
+            run_edge_case(nm, EDGE_CASES[nm])
         elif nm in XCORR_CASES:
             run_xcorr_case(nm, XCORR_CASES[nm])
         else:

@@ -172,6 +172,32 @@ def _outputs(d):
     return out
 
 
+def _select_files(d, param_file):
+    """regress.dat and selected_win.dat that `select` wrote in d, against oracle.select_regress and select() on the
+    opt_data files there: 1e-10 relative, NaN in place, the same windows.  -> (regress rows, the opt_data inputs)"""
+    from oracle import oracle
+
+    from hypotremormcmc_amd.obs_data import ObsData
+    from hypotremormcmc_amd.param import Param
+    from hypotremormcmc_amd.select import select
+
+    para = Param(str(d / param_file), from_where="select")
+    g = para.values
+    ids, times = read_detected_win(str(d / "detected_win.dat"))
+    obs = ObsData(ids, para.n_stations, para.sta_x, para.sta_y, directory=str(d))
+    ref = oracle.select_regress(para.sta_x, para.sta_y, para.sta_z, g["z_guess"], obs.t_obs, obs.t_stdv, obs.a_obs,
+                                obs.a_stdv)
+    reg = np.array([float(x) for x in open(d / "regress.dat").read().split()]).reshape(-1, 7)
+    assert reg[:, 0].astype(int).tolist() == ids
+    assert np.array_equal(np.isnan(reg[:, 1:]), np.isnan(ref))
+    np.testing.assert_allclose(reg[:, 1:], ref, rtol=1e-10, atol=0)
+    keep = select(ref, g["vs_min"], g["vs_max"], g["b_min"], g["b_max"])
+    rows = [ln.split() for ln in open(d / "selected_win.dat") if ln.strip()]
+    assert [int(r[0]) for r in rows] == [i for i, k in zip(ids, keep) if k]
+    assert [float(r[1]) for r in rows] == [tm for tm, k in zip(times, keep) if k]
+    return reg, obs
+
+
 def test_pipeline_end_to_end(tmp_path):
     S, n, n_win = 6, 100, 40
     delay = np.array([0, 2, -1, 3, 1, -5])
@@ -201,6 +227,15 @@ def test_pipeline_end_to_end(tmp_path):
         np.testing.assert_allclose(rows[:, 5], ra, rtol=1e-10)
     _run(["hypotremormcmc_amd.select", "tremor.in"], a)
     assert os.path.exists(a / "selected_win.dat")
+    # every station at depth z_guess = 0: log(0) at the nearest station, so the amplitude columns are NaN; the lags of
+    # these bursts are consistent, t_stdv = 0 gives weights of inf and the time columns are NaN too
+    reg, _ = _select_files(a, "tremor.in")
+    assert np.all(np.isnan(reg[:, [2, 4, 6]]))
+    # with the source below the stations the amplitude regression is finite
+    (a / "deeper.in").write_text(open(a / "tremor.in").read().replace("z_guess = 0.0", "z_guess = 2.5"))
+    _run(["hypotremormcmc_amd.select", "deeper.in"], a)
+    reg, _ = _select_files(a, "deeper.in")
+    assert np.all(np.isfinite(reg[:, [2, 4, 6]]))
     # no .corr file, same bits; and many small batches, same bits
     _run(["hypotremormcmc_amd.measure", "tremor.in", "--from-envelopes"], b)
     _run(["hypotremormcmc_amd.measure", "tremor.in", "--from-envelopes"], c, env={"HTM_XCORR_MB": "0.01"})
@@ -213,6 +248,59 @@ def test_pipeline_end_to_end(tmp_path):
     for f in os.listdir(a):
         if f.endswith((".corr", ".max_corr")):
             assert open(a / f, "rb").read() == open(c / f, "rb").read(), f
+
+
+def test_pipeline_select_keeps_some_windows(tmp_path):
+    """noisier, wider bursts: the lags are not all consistent, every t_stdv > 0 and both regressions are finite; the vs
+    window keeps two of the three detections (vs of about -4.6, -5.0 and -5.3 in the restatement)"""
+    S, n, n_win = 6, 100, 40
+    delay = np.array([0, 2, -1, 3, 1, -5])
+    la = np.array([0.0, 0.3, -0.2, 0.1, -0.4, 0.2])
+    bursts = [5, 17, 30]
+    env = synth.make_tremor_envelopes(S, n_win, n, n, bursts, delay, la, noise=1.0, width=6.0, seed=9)
+    synth.write_envelopes(str(tmp_path), env, t_win_corr=100.0, t_step_corr=100.0, alpha=0.998, n_pair_thred=10,
+                          z_guess=2.5, vs_min=-5.15, vs_max=0.0)
+    _run(["hypotremormcmc_amd.measure", "tremor.in", "--from-envelopes"], tmp_path)
+    ids, _ = read_detected_win(str(tmp_path / "detected_win.dat"))
+    assert ids == bursts
+    _run(["hypotremormcmc_amd.select", "tremor.in"], tmp_path)
+    reg, obs = _select_files(tmp_path, "tremor.in")
+    assert np.all(obs.t_stdv > 0) and np.all(np.isfinite(reg))
+    assert [int(ln.split()[0]) for ln in open(tmp_path / "selected_win.dat") if ln.strip()] == [5, 17]
+
+
+def test_pipeline_dead_first_station(tmp_path):
+    """station 1 records nothing: step 3 gives every amplitude of a window NaN (0/0), step 4's maxloc
+    then has no candidate and takes station 1.  select must run, regress on the times from station 1,
+    write NaN amplitude columns, and keep none of those windows."""
+    from hypotremormcmc_amd.obs_data import maxloc
+
+    S, n, n_win = 6, 100, 40
+    delay = np.array([0, 2, -1, 3, 1, -5])
+    la = np.array([0.0, 0.3, -0.2, 0.1, -0.4, 0.2])
+    bursts = [5, 17, 30]
+    env = synth.make_tremor_envelopes(S, n_win, n, n, bursts, delay, la, noise=0.2, width=3.0, seed=9)
+    env.amps[0] = 0.0
+    # the five pairs with station 1 have zero correlograms; the ten live pairs detect the bursts
+    synth.write_envelopes(str(tmp_path), env, t_win_corr=100.0, t_step_corr=100.0, alpha=0.998, n_pair_thred=8,
+                          z_guess=2.5, vs_min=-1.0e9)
+    _run(["hypotremormcmc_amd.measure", "tremor.in", "--from-envelopes"], tmp_path)
+    ids, _ = read_detected_win(str(tmp_path / "detected_win.dat"))
+    assert ids == bursts
+    _run(["hypotremormcmc_amd.select", "tremor.in"], tmp_path)
+    reg, obs = _select_files(tmp_path, "tremor.in")
+    assert np.all(np.isnan(obs.a_obs)) and np.all(maxloc(obs.a_obs) == 0)
+    assert np.all(np.isfinite(obs.t_obs)) and np.all(np.isfinite(obs.t_stdv)) and np.all(obs.t_stdv > 0)
+    assert np.all(np.isnan(reg[:, [2, 4, 6]])) and np.all(np.isfinite(reg[:, [1, 3, 5]]))
+    # the time columns are those of station 1 as the nearest: not those of any other station
+    from oracle import oracle
+
+    for k in range(1, S):
+        a_k = np.full_like(obs.a_obs, -1.0)
+        a_k[:, k] = 0.0
+        other = oracle.select_regress(obs.sta_x, obs.sta_y, np.zeros(S), 2.5, obs.t_obs, obs.t_stdv, a_k, obs.a_stdv)
+        assert not np.allclose(other[:, [0, 2, 4]], reg[:, [1, 3, 5]], rtol=1e-10, atol=0)
+    assert open(tmp_path / "selected_win.dat").read().strip() == ""
 
 
 # ---- steps 2 and 3 against the compiled reference (tests/golden/xcorr_*.npz, make_golden.py) ---------------------------
