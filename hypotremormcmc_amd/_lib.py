@@ -108,6 +108,12 @@ SIGNATURES = {
                                 C.c_long, vp, vp]),
     "htm_xcorr": (C.c_int, [C.c_int, dp, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp]),
     "htm_measure_windows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp, dp, dp, dp, dp]),
+    "htm_fft_dev": (C.c_int, [C.c_int, vp, C.c_long, vp, C.c_long, C.c_long, C.c_long, C.c_int, vp]),
+    "htm_fft": (C.c_int, [C.c_int, dp, C.c_long, dp, C.c_long, C.c_long, C.c_long, C.c_int]),
+    "htm_convert_dev": (C.c_int, [C.c_int, vp, vp, C.c_long, C.c_int, C.c_int, C.c_int, ip, C.c_double, C.c_double,
+                                  C.c_long, C.c_long, vp, vp]),
+    "htm_convert": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_long, C.c_int, C.c_int, C.c_int,
+                              ip, C.c_double, C.c_double, C.c_long, C.c_long, dp]),
     "htm_selftest": (C.c_int, [C.c_int]),
     "htm_selftest_math": (C.c_int, [C.c_int, C.c_int, dp, dp, C.c_int]),
     "htm_rng_jump": (C.c_int, [up, C.c_ulonglong, up]),

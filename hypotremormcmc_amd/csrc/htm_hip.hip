@@ -16,10 +16,14 @@
 #include <chrono>
 #include <climits>
 #include <cstring>
+#include <map>
+#include <memory>
+#include <mutex>
 #include <thread>
 #include <string>
 #include <vector>
 
+#include "htm_convert.hpp"
 #include "htm_kernels.hpp"
 #include "htm_pipe.hpp"
 #include "htm_select.hpp"
@@ -2404,6 +2408,327 @@ int htm_measure_windows(int device, int n_sta, int n, double dt, int n_det, cons
             if (hipMemcpy(outs[k] + (size_t)w0 * n_sta, dout + k * (size_t)chunk * n_sta, ns * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
                 return done(fail(HTM_EHIP, "k_measure or its download failed"));
     }
+    return done(HTM_OK);
+}
+
+}  // extern "C"
+
+// ---- step 1: FFT plans (htm_fft.hpp) and the convert pipeline (htm_convert.hpp) ---------------------------------------
+namespace {
+
+struct FftPlan {
+    long n = 0;
+    std::vector<int> radix;          // Stockham passes (empty for n = 1 and for Bluestein lengths)
+    std::vector<long> tw_off;        // first twiddle of each pass in d_tw
+    double2 *d_tw = nullptr;
+    long m = 0;                      // Bluestein: inner power-of-two length (0: Stockham)
+    const FftPlan *inner = nullptr;
+    double2 *d_chirp = nullptr, *d_b = nullptr;
+};
+
+std::mutex g_fft_mu;
+std::map<std::pair<int, long>, FftPlan *> g_fft_plans;   // per (device, n); kept for the life of the process
+
+bool fft_factor(long n, std::vector<int> &r)
+{
+    r.clear();
+    while (n % 4 == 0) { r.push_back(4); n /= 4; }
+    if (n % 2 == 0) { r.push_back(2); n /= 2; }
+    for (int p : {3, 5, 7})
+        while (n % p == 0) { r.push_back(p); n /= p; }
+    return n == 1;
+}
+
+long fft_inner_len(long n)
+{
+    long m = 1;
+    while (m < 2 * n - 1) m <<= 1;
+    return m;
+}
+
+// complex elements of workspace fft_run needs for `rows` rows of n, and the most work-items one of its launches takes
+size_t fft_ws_elems(long n, long rows)
+{
+    std::vector<int> r;
+    return fft_factor(n, r) ? (size_t)rows * n : 2 * (size_t)rows * fft_inner_len(n);
+}
+long fft_max_items(long n, long rows)
+{
+    std::vector<int> r;
+    return fft_factor(n, r) ? rows * n : rows * fft_inner_len(n);
+}
+
+dim3 fft_grid(long total) { return dim3((unsigned)((total + kFftThreads - 1) / kFftThreads)); }
+
+int fft_run(const FftPlan &p, const double2 *in, long ld_in, double2 *out, long ld_out, long rows, int sign, double2 *ws,
+            hipStream_t st)
+{
+    const long n = p.n;
+    if (p.m == 0) {
+        const int P = (int)p.radix.size();
+        if (P == 0) {
+            if (in != out) hipLaunchKernelGGL(k_fft_copy, fft_grid(rows * n), dim3(kFftThreads), 0, st, in, ld_in, out, ld_out, n, rows * n);
+            HIPCHK(hipGetLastError());
+            return HTM_OK;
+        }
+        // the last pass writes `out`; in place with an odd pass count the passes end in ws and a copy follows
+        const bool extra = in == out && P % 2 == 1;
+        const double2 *src = in;
+        long lds = ld_in, ns = 1;
+        for (int i = 0; i < P; ++i) {
+            const bool to_out = extra ? (i % 2 == 1) : ((P - 1 - i) % 2 == 0);
+            double2 *dst = to_out ? out : ws;
+            const long ldd = to_out ? ld_out : n;
+            const int R = p.radix[i];
+            const long total = rows * (n / R);
+            const double2 *tw = p.d_tw + p.tw_off[i];
+            switch (R) {
+            case 2: hipLaunchKernelGGL(k_fft_pass<2>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n, (int)ns, tw, sign, total); break;
+            case 3: hipLaunchKernelGGL(k_fft_pass<3>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n, (int)ns, tw, sign, total); break;
+            case 4: hipLaunchKernelGGL(k_fft_pass<4>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n, (int)ns, tw, sign, total); break;
+            case 5: hipLaunchKernelGGL(k_fft_pass<5>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n, (int)ns, tw, sign, total); break;
+            default: hipLaunchKernelGGL(k_fft_pass<7>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n, (int)ns, tw, sign, total); break;
+            }
+            src = dst; lds = ldd; ns *= R;
+        }
+        if (extra) hipLaunchKernelGGL(k_fft_copy, fft_grid(rows * n), dim3(kFftThreads), 0, st, ws, n, out, ld_out, n, rows * n);
+        HIPCHK(hipGetLastError());
+        return HTM_OK;
+    }
+    // Bluestein: backward(x) = conj(forward(conj(x))); ws holds a [rows][m] and the inner transforms' own rows * m
+    const long m = p.m;
+    double2 *a = ws, *ws2 = ws + (size_t)rows * m;
+    hipLaunchKernelGGL(k_blue_pre, fft_grid(rows * m), dim3(kFftThreads), 0, st, in, ld_in, a, n, m, p.d_chirp, sign > 0 ? 1 : 0, rows * m);
+    int rc = fft_run(*p.inner, a, m, a, m, rows, -1, ws2, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_blue_mul, fft_grid(rows * m), dim3(kFftThreads), 0, st, a, m, p.d_b, rows * m);
+    if ((rc = fft_run(*p.inner, a, m, a, m, rows, +1, ws2, st))) return rc;
+    hipLaunchKernelGGL(k_blue_post, fft_grid(rows * n), dim3(kFftThreads), 0, st, a, m, out, ld_out, n, p.d_chirp, sign > 0 ? 1 : 0, rows * n);
+    HIPCHK(hipGetLastError());
+    return HTM_OK;
+}
+
+const long double kPiL = 3.141592653589793238462643383279502884L;
+
+// the plan of length n on the current device, built once (g_fft_mu held); tables in long double, rounded once
+int fft_plan_locked(int device, long n, const FftPlan **out)
+{
+    auto it = g_fft_plans.find(std::make_pair(device, n));
+    if (it != g_fft_plans.end()) { *out = it->second; return HTM_OK; }
+    std::unique_ptr<FftPlan> p(new FftPlan);
+    p->n = n;
+    if (fft_factor(n, p->radix)) {
+        // tw[off + k (R-1) + r - 1] = exp(-2 pi i r k / (ns R)), k < ns
+        std::vector<double2> tw;
+        long ns = 1;
+        for (int R : p->radix) {
+            p->tw_off.push_back((long)tw.size());
+            for (long k = 0; k < ns; ++k)
+                for (int r = 1; r < R; ++r) {
+                    const long double a = -2.0L * kPiL * (long double)(r * k) / (long double)(ns * R);
+                    tw.push_back(make_double2((double)cosl(a), (double)sinl(a)));
+                }
+            ns *= R;
+        }
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&p->d_tw), std::max<size_t>(1, tw.size()) * sizeof(double2)));
+        if (!tw.empty()) HIPCHK(hipMemcpy(p->d_tw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
+    } else {
+        p->radix.clear();
+        p->m = fft_inner_len(n);
+        const long m = p->m;
+        int rc = fft_plan_locked(device, m, &p->inner);
+        if (rc) return rc;
+        // chirp w[j] = exp(-pi i (j^2 mod 2n) / n); b = conj(w) at j and m - j, divided by m (a power of two: exact)
+        std::vector<double2> w(n), b(m, make_double2(0.0, 0.0));
+        for (long j = 0; j < n; ++j) {
+            const long q = (long)(((unsigned long long)j * (unsigned long long)j) % (unsigned long long)(2 * n));
+            const long double a = -kPiL * (long double)q / (long double)n;
+            const long double c = cosl(a), s = sinl(a);
+            w[j] = make_double2((double)c, (double)s);
+            b[j] = make_double2((double)(c / m), (double)(-s / m));
+            if (j) b[m - j] = b[j];
+        }
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&p->d_chirp), n * sizeof(double2)));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&p->d_b), m * sizeof(double2)));
+        HIPCHK(hipMemcpy(p->d_chirp, w.data(), n * sizeof(double2), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(p->d_b, b.data(), m * sizeof(double2), hipMemcpyHostToDevice));
+        double2 *tmp = nullptr;
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&tmp), m * sizeof(double2)));
+        rc = fft_run(*p->inner, p->d_b, m, p->d_b, m, 1, -1, tmp, nullptr);
+        const hipError_t e = hipDeviceSynchronize();
+        (void)hipFree(tmp);
+        if (rc) return rc;
+        if (e != hipSuccess) return fail(HTM_EHIP, "Bluestein table of n = %ld: %s", n, hipGetErrorString(e));
+    }
+    *out = p.get();
+    g_fft_plans[std::make_pair(device, n)] = p.release();
+    return HTM_OK;
+}
+
+int fft_plan(int device, long n, const FftPlan **out)
+{
+    std::lock_guard<std::mutex> lk(g_fft_mu);
+    return fft_plan_locked(device, n, out);
+}
+
+// stream-ordered workspace, as htm_quantiles_dev allocates it
+struct AsyncBuf {
+    void *p = nullptr;
+    hipStream_t st = nullptr;
+    bool async = false;
+    int alloc(size_t bytes, hipStream_t s)
+    {
+        st = s;
+        async = hipMallocAsync(&p, std::max<size_t>(bytes, 1), st) == hipSuccess;
+        if (!async) {
+            (void)hipGetLastError();
+            if (hipMalloc(&p, std::max<size_t>(bytes, 1)) != hipSuccess) { p = nullptr; return fail(HTM_EHIP, "hipMalloc of %zu bytes failed", bytes); }
+        }
+        return HTM_OK;
+    }
+    int release()
+    {
+        if (!p) return HTM_OK;
+        void *q = p;
+        p = nullptr;
+        if (async) { HIPCHK(hipFreeAsync(q, st)); return HTM_OK; }
+        HIPCHK(hipStreamSynchronize(st));
+        (void)hipFree(q);
+        return HTM_OK;
+    }
+};
+
+int fft_check(const void *in, long ld_in, const void *out, long ld_out, long n, long batch, int direction)
+{
+    if (!in || !out) return fail(HTM_EINVAL, "NULL argument");
+    if (n < 1 || n > kFftMaxN) return fail(HTM_EINVAL, "FFT length n = %ld outside 1..%ld", n, kFftMaxN);
+    if (batch < 1 || ld_in < n || ld_out < n) return fail(HTM_EINVAL, "bad shape (batch %ld, ld_in %ld, ld_out %ld, n %ld)", batch, ld_in, ld_out, n);
+    if (direction != -1 && direction != 1) return fail(HTM_EINVAL, "direction must be -1 (forward) or +1 (backward), got %d", direction);
+    if (in == out && ld_in != ld_out) return fail(HTM_EINVAL, "in place needs ld_in == ld_out");
+    if (fft_max_items(n, batch) > 0xffffffffL)
+        return fail(HTM_EINVAL, "%ld rows of n = %ld need %ld work-items in one launch (more than 2^32 - 1)", batch, n, fft_max_items(n, batch));
+    return HTM_OK;
+}
+
+// step 1 geometry: index of the last segment, and the kept range [start, end) of stream samples of segment j
+long cv_last(long n_total, int n) { return (n_total - n) / (n / 2) + 1; }
+long cv_start(long j, int n) { return j == 0 ? 0 : j * (n / 2) + n / 4; }
+long cv_end(long j, long n_total, int n) { return j == cv_last(n_total, n) ? n_total : j * (n / 2) + n - n / 4; }
+long ceil_div(long a, long b) { return (a + b - 1) / b; }
+
+int cv_check(long n_total, int n, int n_fac, int h, const int k_band[4], long j0, long j1)
+{
+    if (!k_band) return fail(HTM_EINVAL, "NULL argument");
+    if (n < 4 || n % 4 || n > kFftMaxN) return fail(HTM_EINVAL, "n = %d: need a multiple of 4 in 4..%ld", n, kFftMaxN);
+    if (n_total < n) return fail(HTM_EINVAL, "data length is not enough in queue (N = %ld < n = %d)", n_total, n);
+    if (n_fac < 1 || n_fac > n / 2) return fail(HTM_EINVAL, "n_fac = %d: need 1 <= n_fac <= n/2 = %d", n_fac, n / 2);
+    if (h < 0 || h > kCvMaxH || 2L * h > n) return fail(HTM_EINVAL, "half width h = %d: need 0 <= h <= %d and 2h <= n = %d", h, kCvMaxH, n);
+    if (k_band[0] < 0 || k_band[0] > k_band[1] || k_band[1] > k_band[2] || k_band[2] > k_band[3])
+        return fail(HTM_EINVAL, "band bins must satisfy 0 <= k1 <= k2 <= k3 <= k4 (got %d %d %d %d)", k_band[0], k_band[1], k_band[2], k_band[3]);
+    const long last = cv_last(n_total, n);
+    if (j0 < 0 || j0 > j1 || j1 > last) return fail(HTM_EINVAL, "segments %ld..%ld outside 0..%ld", j0, j1, last);
+    const long S = j1 - j0 + 1;
+    if (std::max(fft_max_items(n, 2 * S), 2 * S * (long)n) > 0xffffffffL)
+        return fail(HTM_EINVAL, "%ld segments of n = %d need more than 2^32 - 1 work-items in one launch", S, n);
+    return HTM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int htm_fft_dev(int device, const double *d_in, long ld_in, double *d_out, long ld_out, long n, long batch, int direction,
+                void *hip_stream)
+{
+    int rc = fft_check(d_in, ld_in, d_out, ld_out, n, batch, direction);
+    if (rc) return rc;
+    if ((rc = use_device(device))) return rc;
+    const FftPlan *p = nullptr;
+    if ((rc = fft_plan(device, n, &p))) return rc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    AsyncBuf ws;
+    if ((rc = ws.alloc(fft_ws_elems(n, batch) * sizeof(double2), st))) return rc;
+    rc = fft_run(*p, reinterpret_cast<const double2 *>(d_in), ld_in, reinterpret_cast<double2 *>(d_out), ld_out, batch, direction, static_cast<double2 *>(ws.p), st);
+    const int rc2 = ws.release();
+    return rc ? rc : rc2;
+}
+
+int htm_fft(int device, const double *in, long ld_in, double *out, long ld_out, long n, long batch, int direction)
+{
+    int rc = fft_check(in, ld_in, out, ld_out, n, batch, direction);
+    if (rc) return rc;
+    if ((rc = use_device(device))) return rc;
+    std::vector<void *> pool;
+    auto done = [&](int code) { for (void *q : pool) (void)hipFree(q); return code; };
+    const size_t ni = 2 * ((size_t)(batch - 1) * ld_in + n), no = 2 * ((size_t)(batch - 1) * ld_out + n);
+    double *di = nullptr, *dout = nullptr;
+    if ((rc = dev_upload(pool, &dout, out, no))) return done(rc);      // keeps the padding between strided rows
+    if (in == out) di = dout;
+    else if ((rc = dev_upload(pool, &di, in, ni))) return done(rc);
+    if ((rc = htm_fft_dev(device, di, ld_in, dout, ld_out, n, batch, direction, nullptr))) return done(rc);
+    if (hipMemcpy(out, dout, no * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return done(fail(HTM_EHIP, "FFT or its download failed"));
+    return done(HTM_OK);
+}
+
+int htm_convert_dev(int device, const float *d_x1, const float *d_x2, long n_total, int n, int n_fac, int h,
+                    const int k_band[4], double fac1, double fac2, long j0, long j1, double *d_out, void *hip_stream)
+{
+    if (!d_x1 || !d_x2 || !d_out) return fail(HTM_EINVAL, "NULL argument");
+    int rc = cv_check(n_total, n, n_fac, h, k_band, j0, j1);
+    if (rc) return rc;
+    if ((rc = use_device(device))) return rc;
+    const FftPlan *p = nullptr;
+    if ((rc = fft_plan(device, n, &p))) return rc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const long S = j1 - j0 + 1, n2 = n / 2, last = cv_last(n_total, n);
+    const long n_valid = std::min(n_total, j1 * n2 + n) - j0 * n2;
+    // workspace: z [S][n] (later the first smoothing [2S][n] doubles), y [2S][n], the FFT's own, 4S coefficients
+    const size_t zb = (size_t)S * n * sizeof(double2), yb = 2 * zb, fb = fft_ws_elems(n, 2 * S) * sizeof(double2);
+    AsyncBuf ws;
+    if ((rc = ws.alloc(zb + yb + fb + 4 * S * sizeof(double), st))) return rc;
+    char *base = static_cast<char *>(ws.p);
+    double2 *z = reinterpret_cast<double2 *>(base), *y = reinterpret_cast<double2 *>(base + zb);
+    double2 *fw = reinterpret_cast<double2 *>(base + zb + yb);
+    double *coef = reinterpret_cast<double *>(base + zb + yb + fb);
+    const long sn = S * n;
+    hipLaunchKernelGGL(k_cv_detrend, dim3((unsigned)S), dim3(kCvSumThreads), 0, st, d_x1, d_x2, n_valid, n, coef);
+    hipLaunchKernelGGL(k_cv_pack, fft_grid(sn), dim3(kCvThreads), 0, st, d_x1, d_x2, n_valid, n, coef, z, sn);
+    if ((rc = fft_run(*p, z, n, z, n, S, -1, fw, st))) { ws.release(); return rc; }
+    const int4 kb = make_int4(k_band[0], k_band[1], k_band[2], k_band[3]);
+    hipLaunchKernelGGL(k_cv_spectrum, fft_grid(sn), dim3(kCvThreads), 0, st, z, n, kb, y, sn);
+    if ((rc = fft_run(*p, y, n, y, n, 2 * S, +1, fw, st))) { ws.release(); return rc; }
+    const int tiles1 = (int)ceil_div(n, kCvTile), tiles2 = (int)ceil_div(n - n / 4, kCvTile);
+    const size_t lds = 2 * (size_t)(kCvTile + 2 * h) * sizeof(double);
+    double *e1 = reinterpret_cast<double *>(z);
+    const long k_base = ceil_div(cv_start(j0, n), n_fac);
+    hipLaunchKernelGGL(k_cv_smooth<false>, dim3((unsigned)(S * tiles1)), dim3(kCvThreads), lds, st, y, (const double *)nullptr, e1, n, h,
+                       tiles1, j0, last, n_total, n_fac, k_base, fac1, fac2, (double *)nullptr);
+    hipLaunchKernelGGL(k_cv_smooth<true>, dim3((unsigned)(S * tiles2)), dim3(kCvThreads), lds, st, (const double2 *)nullptr, e1,
+                       (double *)nullptr, n, h, tiles2, j0, last, n_total, n_fac, k_base, fac1, fac2, d_out);
+    const hipError_t e = hipGetLastError();
+    rc = ws.release();
+    if (e != hipSuccess) return fail(HTM_EHIP, "step-1 kernels failed to launch: %s", hipGetErrorString(e));
+    return rc;
+}
+
+int htm_convert(int device, const float *x1, const float *x2, long n_total, int n, int n_fac, int h, const int k_band[4],
+                double fac1, double fac2, long j0, long j1, double *out)
+{
+    if (!x1 || !x2 || !out) return fail(HTM_EINVAL, "NULL argument");
+    int rc = cv_check(n_total, n, n_fac, h, k_band, j0, j1);
+    if (rc) return rc;
+    if ((rc = use_device(device))) return rc;
+    std::vector<void *> pool;
+    auto done = [&](int code) { for (void *q : pool) (void)hipFree(q); return code; };
+    const long n2 = n / 2;
+    const size_t n_valid = (size_t)(std::min(n_total, j1 * n2 + n) - j0 * n2);
+    const size_t n_out = (size_t)(ceil_div(cv_end(j1, n_total, n), n_fac) - ceil_div(cv_start(j0, n), n_fac));
+    float *d1 = nullptr, *d2 = nullptr;
+    double *dout = nullptr;
+    if ((rc = dev_upload(pool, &d1, x1, n_valid)) || (rc = dev_upload(pool, &d2, x2, n_valid)) || (rc = dev_alloc(pool, &dout, n_out)))
+        return done(rc);
+    if ((rc = htm_convert_dev(device, d1, d2, n_total, n, n_fac, h, k_band, fac1, fac2, j0, j1, dout, nullptr))) return done(rc);
+    if (hipMemcpy(out, dout, n_out * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return done(fail(HTM_EHIP, "step-1 kernels or their download failed"));
     return done(HTM_OK);
 }
 

@@ -38,6 +38,9 @@ REQUIRED_SELECT = ["n_procs", "station_file", "z_guess", "vs_min", "vs_max", "b_
 # requiring them; hypotremormcmc_amd.measure checks them itself (require()).
 REQUIRED_CORRELATE = ["n_procs", "station_file", "t_win_corr", "t_step_corr"]
 REQUIRED_MEASURE = ["n_procs", "station_file", "alpha", "n_pair_thred"]
+# src/cls_param.f90:113-116
+REQUIRED_CONVERT = ["n_procs", "station_file", "data_dir", "time_id_file", "cmp1", "cmp2", "filename_format",
+                    "t_win_conv"]
 
 
 class ParamError(SystemExit):
@@ -85,7 +88,7 @@ class Param:
                     continue
                 self.set_value(*nv)
         for key in {"mcmc": REQUIRED_MCMC, "select": REQUIRED_SELECT, "correlate": REQUIRED_CORRELATE,
-                    "measure": REQUIRED_MEASURE}.get(from_where, []):
+                    "measure": REQUIRED_MEASURE, "convert": REQUIRED_CONVERT}.get(from_where, []):
             if key not in self.given:
                 raise ParamError(f"ERROR: {key} is not given.")
         base = os.path.dirname(os.path.abspath(param_file))

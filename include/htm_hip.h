@@ -362,6 +362,50 @@ int htm_xcorr(int device, const double *env, long n_smp, int n_sta, int n, int n
 int htm_measure_windows(int device, int n_sta, int n, double dt, int n_det, const double *x, double *t,
                         double *t_stdv, double *amp, double *amp_stdv);
 
+/* ------------------------------------------------------------------------------------------------
+ * Batched fp64 complex FFT (step 1's transforms)
+ * Rows of n interleaved complex values (re, im doubles), row stride ld in complex elements:
+ *     out[row][k] = sum_j in[row][j] exp(direction 2 pi i j k / n),  direction = -1 forward, +1 backward,
+ * unnormalised both ways.  Lengths whose prime factors are 2, 3, 5 and 7 run as Stockham passes of radix 2, 3, 4, 5
+ * and 7; any other length by Bluestein with a power-of-two inner transform.  Twiddle and chirp tables are built in
+ * long double on the host once per (device, n), uploaded synchronously and kept for the life of the process.
+ * 1 <= n <= 2^24, batch >= 1, ld_in, ld_out >= n; in place (d_in == d_out, ld_in == ld_out) or on disjoint buffers;
+ * one launch holds fewer than 2^32 work-items (batch * n, or batch * m for Bluestein's inner length m); anything
+ * else is HTM_EINVAL before any device call.  Only the n values of each row are written.  In place and out of place
+ * give the same bits.  Device pointers; the workspace is allocated stream-ordered on `hip_stream` (NULL = the null
+ * stream), so the call is asynchronous after a plan's first build. */
+int htm_fft_dev(int device, const double *d_in, long ld_in, double *d_out, long ld_out, long n, long batch, int direction,
+                void *hip_stream);
+/* the same with host pointers, for tests: in [batch][ld_in], out [batch][ld_out] complex (padding of out kept).
+ * Synchronous. */
+int htm_fft(int device, const double *in, long ld_in, double *out, long ld_out, long n, long batch, int direction);
+
+/* ------------------------------------------------------------------------------------------------
+ * Step 1, `hypo_tremor_convert`   reference: src/cls_convertor.f90:84-443, src/mod_signal_process.f90:10-26
+ * Smoothed, merged envelope of one station: segments of n samples every n2 = n/2 of a record of N = n_total
+ * samples; segment j covers stream samples [j n2, j n2 + n), samples at or beyond N read as 0; the segments are
+ * j = 0 .. last, last = (N - n) / n2 + 1.  Per segment and component: detrend (least-squares line in the 1-based
+ * index), cosine taper (nleng = int(0.05 n)), forward DFT X, Y[0] = 0, Y[k] = 2 w(k) X[k] for 1 <= k <= n/2, 0 above,
+ * with the band weight w of bins k1..k4 = k_band (k < k1: 0, [k1, k2): 0.5 (1 - cos((k-k1) pi / (k2-k1))),
+ * [k2, k3): 1, [k3, k4): 0.5 (1 + cos((k-k3) pi / (k4-k3))), k >= k4: 0), e = |backward DFT(Y) / n|, two box
+ * smoothings of half width h with the reference's windows (1-based i: i <= h: sum e[1..i+h] / (i+h); h < i <= n-h:
+ * sum e[i-h+1..i+h] / (2h+1); i > n-h: sum e[i-h+1..n] / (n+h-i+1)), and the merge
+ * sqrt((e1 fac1)^2 + (e2 fac2)^2).  Segment j keeps the stream samples [start(j), end(j)): start = 0 for j = 0, else
+ * j n2 + n/4; end = N for j = last, else j n2 + n - n/4.  These ranges tile [0, N).  The output holds the kept
+ * samples g that are multiples of n_fac, value k = g / n_fac.
+ * One call handles segments j0 .. j1: d_x1, d_x2 are the two components from stream sample j0 n2 on, holding
+ * min(N, j1 n2 + n) - j0 n2 float32 samples each; d_out receives values ceil(start(j0) / n_fac) ..
+ * ceil(end(j1) / n_fac) - 1.  n a multiple of 4 in 4..2^24, N >= n, 1 <= n_fac <= n/2, 0 <= h <= 4096 with 2h <= n,
+ * 0 <= k1 <= k2 <= k3 <= k4, 0 <= j0 <= j1 <= last, and 2 (j1 - j0 + 1) n (or Bluestein's 2 (j1 - j0 + 1) m) below
+ * 2^32; anything else is HTM_EINVAL before any device call.  Device memory: about 80 n bytes per segment of workspace
+ * (Bluestein lengths: 48 n + 64 m), allocated stream-ordered.  Device pointers; asynchronous on `hip_stream` (NULL =
+ * the null stream) after the FFT plan of n is built. */
+int htm_convert_dev(int device, const float *d_x1, const float *d_x2, long n_total, int n, int n_fac, int h,
+                    const int k_band[4], double fac1, double fac2, long j0, long j1, double *d_out, void *hip_stream);
+/* the same with host pointers, for tests.  Synchronous. */
+int htm_convert(int device, const float *x1, const float *x2, long n_total, int n, int n_fac, int h, const int k_band[4],
+                double fac1, double fac2, long j0, long j1, double *out);
+
 int htm_selftest(int device);
 
 /* y[i] = fn(x[i]) for n host values, fn = the forward model's own fp64 routines: which = 0 the logarithm of the amplitude
