@@ -259,6 +259,18 @@ class ChainSet:
         check(self._lib.htm_chains_master_stats(self.handle, C.byref(a), C.byref(b), C.byref(n)))
         return dict(single_rank_loop=a.value, lockstep_loop=b.value, flushes=n.value)
 
+    def fixed_master(self):
+        """True if the latest single-rank launch ran the free-running master specialised on the job's shape"""
+        on = C.c_int()
+        check(self._lib.htm_chains_fixed_master(self.handle, C.byref(on), None))
+        return bool(on.value)
+
+    @property
+    def n_worker_blocks(self) -> int:
+        on = C.c_int(); n = C.c_int()
+        check(self._lib.htm_chains_fixed_master(self.handle, C.byref(on), C.byref(n)))
+        return n.value
+
     def last_run_stats(self):
         us = C.c_double(); g = C.c_int(); f = C.c_int64(); p = C.c_int64()
         check(self._lib.htm_chains_last_run_stats(self.handle, C.byref(us), C.byref(g), C.byref(f), C.byref(p)))

@@ -396,7 +396,9 @@ __device__ __forceinline__ void load_obs_regs_nobranch(ObsRegs<NCH, F32> &ob, co
 
 // PRE: `beta` and `q` hold 1 / vs and pi f / (qs vs) already -- the caller formed them once (a worker per order, the chain master
 // per commit of vs or qs): two fp64 divisions, ~28 instructions, that the compiler does not move out of a loop over events.
-template <int NCH, int NPOS, bool F32 = false, bool PRE = false, class FW>
+// FULL: every lane has a station in every chunk and both data types are used (the caller has checked, as for
+// load_obs_regs_nobranch<.., FULL>): no `valid` selects, no branches on use_time / use_amp.  Same arithmetic, same order.
+template <int NCH, int NPOS, bool F32 = false, bool PRE = false, bool FULL = false, class FW>
 __device__ __forceinline__ void event_misfit(const FW &f, const ObsRegs<NCH, F32> &ob, int lane,
                                              const StaRegs<NCH> &st, const double (&px)[NPOS],
                                              const double (&py)[NPOS], const double (&pz)[NPOS], double beta,
@@ -426,16 +428,16 @@ __device__ __forceinline__ void event_misfit(const FW &f, const ObsRegs<NCH, F32
         for (int p = 0; p < NPOS; ++p) {
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {
-                const bool valid = (lane + 64 * c) < f.S;
+                const bool valid = FULL || (lane + 64 * c) < f.S;
                 const float dx = (float)(px[p] - st.sx[c]), dy = (float)(py[p] - st.sy[c]), dz = (float)(pz[p] - st.sz[c]);
                 float d = __builtin_amdgcn_sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)));
                 if (!valid) d = 1.0f;
                 ts[p][c] = 0.0; as[p][c] = 0.0;
-                if (f.use_time) {
+                if (FULL || f.use_time) {
                     ts[p][c] = (double)__builtin_fmaf(d, rbeta32, -(float)st.tc[c]);
                     red[2 * p] = __builtin_fma(tpr[c], ts[p][c] - tob[c], red[2 * p]);
                 }
-                if (f.use_amp) {
+                if (FULL || f.use_amp) {
                     const float lg = __builtin_fmaf(__builtin_amdgcn_logf(d), 0.69314718055994531f, (float)st.ac[c]);
                     as[p][c] = (double)(__builtin_fmaf(-d, katt32, -lg));
                     red[2 * p + 1] = __builtin_fma(apr[c], as[p][c] - aob[c], red[2 * p + 1]);
@@ -447,18 +449,18 @@ __device__ __forceinline__ void event_misfit(const FW &f, const ObsRegs<NCH, F32
     for (int p = 0; p < NPOS; ++p) {
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
-            const bool valid = (lane + 64 * c) < f.S;
+            const bool valid = FULL || (lane + 64 * c) < f.S;
             const double dx = px[p] - st.sx[c], dy = py[p] - st.sy[c], dz = pz[p] - st.sz[c];
             // (the library is built with -ffp-contract=off -- proposals and decisions are exact arithmetic; the forward
             // model's products and sums are fused here by hand: one rounding less each, a tenth of the instructions)
             double d = htm_sqrt(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)));
             if (!valid) d = 1.0;     // a lane without a station: finite synthetics, and its precisions are 0 (load_obs_regs)
             ts[p][c] = 0.0; as[p][c] = 0.0;
-            if (f.use_time) {
+            if (FULL || f.use_time) {
                 ts[p][c] = __builtin_fma(d, rbeta, -st.tc[c]);
                 red[2 * p] = __builtin_fma(tpr[c], ts[p][c] - tob[c], red[2 * p]);
             }
-            if (f.use_amp) {
+            if (FULL || f.use_amp) {
                 as[p][c] = __builtin_fma(-d, katt, -htm_log(d)) - st.ac[c];
                 red[2 * p + 1] = __builtin_fma(apr[c], as[p][c] - aob[c], red[2 * p + 1]);
             }
@@ -474,11 +476,11 @@ __device__ __forceinline__ void event_misfit(const FW &f, const ObsRegs<NCH, F32
         double m = 0.0;                       // twice the misfit: the factor 1/2 (:285, :296) is exact and applied once
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {       // (a lane without a station adds r * r * 0)
-            if (f.use_time) {
+            if (FULL || f.use_time) {
                 const double r = tob[c] - (ts[p][c] - t_mean);
                 m = __builtin_fma(r * r, tpr[c], m);
             }
-            if (f.use_amp) {
+            if (FULL || f.use_amp) {
                 const double r = aob[c] - (as[p][c] - a_mean);
                 m = __builtin_fma(r * r, apr[c], m);
             }
@@ -609,7 +611,7 @@ __device__ __forceinline__ void event_misfit_generic(const FW &f, int ev, int la
     }
 }
 
-template <int NCH>
+template <int NCH, bool FULL = false>      // (FULL: S == 64 * NCH, every lane has a station)
 __device__ __forceinline__ void load_sta_regs(StaRegs<NCH> &st, int S, int lane, const double *s_sx,
                                               const double *s_sy, const double *s_sz, const double *tc,
                                               const double *ac, int ov_kind, int ov_idx, double ov_val)
@@ -617,7 +619,7 @@ __device__ __forceinline__ void load_sta_regs(StaRegs<NCH> &st, int S, int lane,
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
         const int j = lane + 64 * c;
-        const bool valid = j < S;
+        const bool valid = FULL || j < S;
         st.sx[c] = valid ? s_sx[j] : 0.0;
         st.sy[c] = valid ? s_sy[j] : 0.0;
         st.sz[c] = valid ? s_sz[j] : 0.0;

@@ -193,19 +193,52 @@ struct FlowTop {
     double rbeta, katt;           // the chain's 1 / vs and pi f / (qs vs) (FlowShared)
 };
 
+// What a job fixes, asked through a traits type: flow_step, flow_body and the helpers they call put every such question to
+// TR.  FlowGeneric answers "not known" to all of them -- the run-time fields decide, as they always did (every loop variant that
+// existed before the traits did compiles to what it compiled to).  FlowFixed answers with constants for the single-rank
+// free-running master of a job that the host has found to be: one rank, n_sta == 64 * NCH with both data types used, the LDS
+// mirror present with its step sizes (htm_hip.hip: flow_fixed_ok).  The answers remove selects, branches, address arithmetic and
+// the scalars that feed them; not a single rounding changes.  (Measured and not kept -- a wave's chain as a launch constant, the
+// step log compiled out, two rounds of partial-sum granules instead of four: docs/experiments/fast_master_more_traits.patch.)
+struct FlowGeneric {
+    static constexpr bool full_rows = false;   // S == 64 * NCH && use_time && use_amp
+    static constexpr bool one_rank = false;    // n_procs == 1 (and no lock-step protocol)
+    static constexpr bool mirror = false;      // mirror_n == 2 nc + 2 nc S (all parameters but the hypocentres) && mirror_steps
+};
+struct FlowFixed {
+    static constexpr bool full_rows = true, one_rank = true, mirror = true;
+};
+
 constexpr int kFlowRestart = -1;  // flow_step: the step's position was disproved before its turn came: run it again
 constexpr int kFlowAbort = -2;    // flow_step: a wait gave up (sh.c.err is set)
 constexpr int kFlowStop = -3;     // flow_step (lock-step rank): the job stops after the iteration before: this step is not taken
 
 // select_pair + the judge_swap draw starting at E (cls_parallel.f90:226-230, :163): pair, draws used in all (single rank:
 // this rank draws both).  The stream service has the usual case precomputed (sw ring); more than 12 redraws follow the stream.
+// (ONE: a single rank that is not in lock-step -- n_procs == 1, rank 0, !rg.lock)
+template <bool ONE = false>
 __device__ __forceinline__ bool flow_swap_at(CsRef cs_, const StepShared &sh, const Ring &rg, int E, int limit, int &i1, int &i2, int &nd)
 {
     CsRef cs = rebase(cs_);
-    const int n_all = cs.n_procs * cs.n_chains;
+    const int n_all = ONE ? cs.n_chains : cs.n_procs * cs.n_chains;
     i1 = -1; i2 = -1; nd = 0;
     if (n_all <= 1) return true;
     if (E + 2 >= limit) return false;
+    if constexpr (ONE) {
+        const i32x4 sw = reinterpret_cast<const i32x4 *>(rg.sw)[E & rg.mask];
+        if (sw.z > 0) { i1 = sw.x; i2 = sw.y; nd = sw.z + 1; return E + nd < limit; }
+        int pos = E;
+        i1 = (int)(rg.U[pos & rg.mask] * n_all);      // (U * 1 * n_chains: the same product)
+        pos++;
+        for (;;) {
+            if (pos + 1 >= limit) return false;
+            i2 = (int)(rg.U[pos & rg.mask] * n_all);
+            pos++;
+            if (i1 != i2) break;
+        }
+        nd = pos - E + 1;
+        return true;
+    }
     if (rg.lock && cs.rank != 0) return true;     // lock-step: the pair is rank 0's; this rank draws only if the pair's first chain is its own (a bet: not)
     const i32x4 sw = reinterpret_cast<const i32x4 *>(rg.sw)[E & rg.mask];
     if (sw.z > 0) {
@@ -230,7 +263,7 @@ __device__ __forceinline__ bool flow_swap_at(CsRef cs_, const StepShared &sh, co
 // base of the next iteration when n chain steps of this one remain from pos; -1 if the window does not cover it
 // (BOUNDED: chained table entries -- n > kHops -- are read only inside the window.  Two master workgroups keep a shorter lead
 // than the three iterations of one workgroup, whose look-ups have never come near the window's end.)
-template <bool BOUNDED = false>
+template <bool BOUNDED = false, bool ONE = false>
 __device__ __forceinline__ int flow_next_base(CsRef cs, const StepShared &sh, const Ring &rg, int pos, int n, int limit)
 {
     if (pos < 0) return -1;
@@ -243,12 +276,13 @@ __device__ __forceinline__ int flow_next_base(CsRef cs, const StepShared &sh, co
         if (m > 0) { if (E + 16 >= limit) return -1; E += rg.hop[(E & rg.mask) * kHops + m - 1]; }
     }
     int i1, i2, nd;
-    if (E + 16 >= limit || !flow_swap_at(cs, sh, rg, E, limit, i1, i2, nd)) return -1;
+    if (E + 16 >= limit || !flow_swap_at<ONE>(cs, sh, rg, E, limit, i1, i2, nd)) return -1;
     return E + nd;
 }
 
 // the anchor as (iteration, chain, position of that chain's step).  A rejected LAST step of an iteration leaves pos = the
 // end of that iteration's chain steps: chain 0 of the next iteration starts after the swap's draws.
+template <bool ONE = false>
 __device__ __forceinline__ void flow_from_anchor(CsRef cs_, const FlowShared &sh, const Ring &rg, unsigned long long a, int &ia, int &ca, int &ap)
 {
     CsRef cs = rebase(cs_);
@@ -257,7 +291,7 @@ __device__ __forceinline__ void flow_from_anchor(CsRef cs_, const FlowShared &sh
     ia = sh.i0 + key / nc; ca = key - (key / nc) * nc; ap = pos;
     if (ca == 0) {
         int i1, i2, nd;
-        flow_swap_at(cs, sh, rg, pos, 1 << 30, i1, i2, nd);     // (the rejected step's own wave read these positions: covered)
+        flow_swap_at<ONE>(cs, sh, rg, pos, 1 << 30, i1, i2, nd);     // (the rejected step's own wave read these positions: covered)
         ap = pos + nd;
     }
 }
@@ -277,7 +311,7 @@ __device__ __forceinline__ void flow_void_books(CsRef cs, FlowShared &sh, int wa
 // step itself starts at or after the anchor.  Returns false if the epoch moved on meanwhile (the caller looks again).
 // (g != nullptr: a multi-block launch -- epoch and anchor are MbShared's; false: the anchor of epoch e is not there (yet, or
 // any more): the caller looks at the epoch again)
-template <bool MB = false>
+template <bool MB = false, bool ONE = false>
 __device__ __forceinline__ bool flow_adopt(CsRef cs_, FlowShared &sh, const Ring &rg, FlowWave &W, int e, int it, int c, bool in_turn, bool &stands,
                                            const MbShared *g = nullptr)
 {
@@ -295,23 +329,23 @@ __device__ __forceinline__ bool flow_adopt(CsRef cs_, FlowShared &sh, const Ring
     const int akey = (int)(unsigned)(a >> 32);
     const int key = (it - sh.i0) * nc + c;
     int ia, ca, ap;
-    flow_from_anchor(cs, sh, rg, a, ia, ca, ap);
+    flow_from_anchor<ONE>(cs, sh, rg, a, ia, ca, ap);
     const int limit = sh.fill;
     stands = in_turn && key < akey;
     W.epoch = e; W.akey = akey;
     if (!stands) {
         // the current step starts at or after the anchor: same iteration, or the anchor sits in the iteration before
         if (ia == it) { W.rc = ca; W.rpos = ap; }
-        else { W.rc = 0; W.rpos = flow_next_base<MB>(cs, sh, rg, ap, nc - ca, 1 << 30); }
-        W.rc1 = 0; W.rpos1 = flow_next_base<MB>(cs, sh, rg, W.rpos, nc - W.rc, limit);
-        W.B2 = flow_next_base<MB>(cs, sh, rg, W.rpos1, nc, limit);
+        else { W.rc = 0; W.rpos = flow_next_base<MB, ONE>(cs, sh, rg, ap, nc - ca, 1 << 30); }
+        W.rc1 = 0; W.rpos1 = flow_next_base<MB, ONE>(cs, sh, rg, W.rpos, nc - W.rc, limit);
+        W.B2 = flow_next_base<MB, ONE>(cs, sh, rg, W.rpos1, nc, limit);
     } else if (ia == it) {
         W.rc = ca; W.rpos = ap;                         // (the wave's later chains of this iteration)
-        W.rc1 = 0; W.rpos1 = flow_next_base<MB>(cs, sh, rg, ap, nc - ca, limit);
-        W.B2 = flow_next_base<MB>(cs, sh, rg, W.rpos1, nc, limit);
+        W.rc1 = 0; W.rpos1 = flow_next_base<MB, ONE>(cs, sh, rg, ap, nc - ca, limit);
+        W.B2 = flow_next_base<MB, ONE>(cs, sh, rg, W.rpos1, nc, limit);
     } else {                                            // the anchor is a step of the next iteration
         W.rc1 = ca; W.rpos1 = ap;
-        W.B2 = flow_next_base<MB>(cs, sh, rg, ap, nc - ca, limit);
+        W.B2 = flow_next_base<MB, ONE>(cs, sh, rg, ap, nc - ca, limit);
     }
     return true;
 }
@@ -487,7 +521,7 @@ __device__ __forceinline__ void flow_lock_finish(CsRef cs_, FlowShared &sh, int 
 // counterpart of chain_pass).  All 64 lanes execute with identical (uniform) values; lane <-> station only inside
 // event_misfit.  `ext`: this wave keeps the LDS window of the stream ahead (chain 0's wave, one round of <= 64 positions
 // per step, in flight under the step's own loads).  Returns the stream position after the step, kFlowRestart or kFlowAbort.
-template <int NCH, bool F32, bool LOCK, bool MB = false>
+template <int NCH, bool F32, bool LOCK, bool MB = false, class TR = FlowGeneric>
 __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, const Ring &rg, FlowWave &W, FlowNext &nx,
                                          MbShared *g_mb, MbWave &mw, double *s_gath, int wmax,
                                          const double *s_sx, const double *s_sy, const double *s_sz, int c, int p, int iter,
@@ -520,7 +554,8 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
     }
     const double *xall_ = cs.xall;
     const PriorRec *prior_ = cs.prior;
-    const int nc_ = cs.n_chains, S_ = cs.S, nh = 3 * cs.E, psame_ = cs.prior_same;
+    static_assert(!TR::full_rows || NCH > 0, "full rows: one or two stations per lane");
+    const int nc_ = cs.n_chains, S_ = TR::full_rows ? 64 * NCH : cs.S, nh = 3 * cs.E, psame_ = cs.prior_same;
     asm volatile("" : "+s"(xall_), "+s"(prior_));
     // the decoded proposal (htm_stream.hpp), its Gaussian and its judge draw: looked up during the step before (FlowNext), or here
     int type, idx, evt, dec_w;
@@ -554,8 +589,9 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
     ObsRegs<(NCH > 0 ? NCH : 1), F32> ob;
     if (partial) {
         if constexpr (NCH > 0) {
-            load_sta_regs<NCH>(st, f.S, lane, s_sx, s_sy, s_sz, tc, ac, 0, -1, 0.0);
-            load_obs_regs<NCH, F32>(ob, f, ev, lane);      // in flight while the proposal is worked out
+            load_sta_regs<NCH, TR::full_rows>(st, f.S, lane, s_sx, s_sy, s_sz, tc, ac, 0, -1, 0.0);
+            if constexpr (TR::full_rows) load_obs_regs_nobranch<NCH, F32, false, false, true>(ob, f, ev, lane);
+            else load_obs_regs<NCH, F32>(ob, f, ev, lane);      // in flight while the proposal is worked out
         }
     }
     // the book of this chain: is this step's order out already, and how
@@ -578,8 +614,9 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
             const int vzd = opaque_zero();
             const double *hypd = xall_ + off_hy + c * nh + 3 * d_e;
             d_ex = ld_state(hypd, vzd); d_ey = ld_state(hypd + 1, vzd); d_ez = ld_state(hypd + 2, vzd);
-            load_sta_regs<NCH>(st, f.S, lane, s_sx, s_sy, s_sz, tc, ac, 0, -1, 0.0);
-            load_obs_regs<NCH, F32>(ob, f, d_e, lane);
+            load_sta_regs<NCH, TR::full_rows>(st, f.S, lane, s_sx, s_sy, s_sz, tc, ac, 0, -1, 0.0);
+            if constexpr (TR::full_rows) load_obs_regs_nobranch<NCH, F32, false, false, true>(ob, f, d_e, lane);
+            else load_obs_regs<NCH, F32>(ob, f, d_e, lane);
         }
     }
     FSTAMP(0);
@@ -602,7 +639,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
     if (c == nc_ - 1) {                                         // where this iteration's swap starts, and what it draws there
         const int E = p + cnt, k4 = iter & 3;
         int i1, i2, nd;
-        flow_swap_at(cs, sh, rg, E, 1 << 30, i1, i2, nd);
+        flow_swap_at<TR::one_rank>(cs, sh, rg, E, 1 << 30, i1, i2, nd);
         if (lane == 0) {
             sh.sw_i1[k4] = i1; sh.sw_i2[k4] = i2; sh.sw_nd[k4] = nd;
             if constexpr (LOCK) {
@@ -662,7 +699,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
             // next step, of its step after that, and the end of the iteration after next -- issued here, used behind the evaluation
             // (the hop tables reach kHops steps: with more chains than that -- several master workgroups -- the positions are looked
             // up at the top of the next step instead)
-            if (NW >= nc_ && W.rpos1 >= 0 && W.B2 >= 0 && c >= W.rc1 && iter + 1 <= sh.c.iter_target && rg.mir_n > 0) {
+            if (NW >= nc_ && W.rpos1 >= 0 && W.B2 >= 0 && c >= W.rc1 && iter + 1 <= sh.c.iter_target && (TR::mirror || rg.mir_n > 0)) {
                 la = 1; la_epoch = W.epoch;
                 const int n1 = c - W.rc1;
                 // (one workgroup: a wave has one chain only with <= 8 = kHops chains, the tables reach in one entry)
@@ -685,7 +722,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
                     la = (la_p1 >= 0 && la_p2 >= 0 && la_E2 >= 0) ? 3 : 0;
                 }
             }
-            if constexpr (NCH > 0) event_misfit<NCH, 2, F32, true>(f, ob, lane, st, px, py, pz, tp.rbeta, tp.katt, out);
+            if constexpr (NCH > 0) event_misfit<NCH, 2, F32, true, TR::full_rows>(f, ob, lane, st, px, py, pz, tp.rbeta, tp.katt, out);
             else event_misfit_generic<2>(f, ev, lane, s_sx, s_sy, s_sz, tc, ac, 0, -1, 0.0, px, py, pz, beta, q, out);
             L_new = L_cur + wave_sum1(out[0] - out[1]);
             // look-ahead, second round trip: what the stream holds at those positions -- used after the commit
@@ -767,7 +804,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
                     }
                     const double pxd[1] = {d_ex}, pyd[1] = {d_ey}, pzd[1] = {d_ez};
                     double outd[1];
-                    event_misfit<NCH, 1, F32>(f, ob, lane, st, pxd, pyd, pzd, type == 1 ? x_new : beta, type == 3 ? x_new : q, outd);
+                    event_misfit<NCH, 1, F32, false, TR::full_rows>(f, ob, lane, st, pxd, pyd, pzd, type == 1 ? x_new : beta, type == 3 ? x_new : q, outd);
                     own_lane = outd[0];
                 }
             }
@@ -833,7 +870,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
             }
             if (__builtin_expect(e != W.epoch, 0)) {
                 bool stands = false;
-                if (!flow_adopt<MB>(cs, sh, rg, W, e, iter, c, true, stands, g_mb)) { if (MB) __builtin_amdgcn_s_sleep(1); continue; }
+                if (!flow_adopt<MB, TR::one_rank>(cs, sh, rg, W, e, iter, c, true, stands, g_mb)) { if (MB) __builtin_amdgcn_s_sleep(1); continue; }
                 if constexpr (MB) MB_HIST(mw, 0xC | (e & 3));
                 flow_void_books(cs, sh, wave, NW, nc_, lane);
                 if (!stands) return kFlowRestart;
@@ -1024,7 +1061,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
         }
     } else if (iter - 1 > sh.i0) {
         T = sh.T4[ppar][c]; rT = sh.rT4[ppar][c];
-        if (cs.n_procs * nc_ > 1) {
+        if ((TR::one_rank ? nc_ : cs.n_procs * nc_) > 1) {
             // (written by the last chain's wave before it published its check; this step's turn has seen that check)
             const int i1 = lds_ld(&sh.sw_i1[ppar]), i2 = sh.sw_i2[ppar];
             if (c == i1 || c == i2) {
@@ -1057,7 +1094,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
         if (cool) sh.np[c * 7 + type - 1] += 1;                 // cls_mcmc.f90:186-189
         if (acc) {                                              // :207-219
             st_agent(cs.xall + o, x_new);
-            if (o < rg.mir_n) rg.mx[o] = x_new;
+            if (TR::mirror ? type <= 4 : o < rg.mir_n) rg.mx[o] = x_new;      // (the mirror holds every parameter but the hypocentres)
             sh.L[c] = L_new;
             if (cool) sh.na[c * 7 + type - 1] += 1;
             if (__builtin_expect(type == 1 || type == 3, 0)) {      // a new vs or qs: the chain's two reciprocals with it
@@ -1106,7 +1143,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
             lds_st(&sh.epoch, e1);
         }
         // (this wave's own view: as any wave whose step stands before the anchor; a later rejection may already have moved on)
-        while (!flow_adopt(cs, sh, rg, W, lds_ld(&sh.epoch), iter, c, true, stands)) { }
+        while (!flow_adopt<false, TR::one_rank>(cs, sh, rg, W, lds_ld(&sh.epoch), iter, c, true, stands)) { }
         }
         flow_void_books(cs, sh, wave, NW, nc_, lane);
     }
@@ -1171,10 +1208,11 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
         nx.g = la_g; nx.r = la_r; nx.logr = la_logr;
         const int swz = uni(swv.z);
         // (what the swap at la_E2 draws on THIS rank: flow_swap_at's rule)
-        if (cs.n_procs * nc_ <= 1 || (rg.lock && cs.rank != 0)) nx.b3 = la_E2;
+        if constexpr (TR::one_rank) nx.b3 = nc_ <= 1 ? la_E2 : swz > 0 ? la_E2 + swz + 1 : -1;
+        else if (cs.n_procs * nc_ <= 1 || (rg.lock && cs.rank != 0)) nx.b3 = la_E2;
         else nx.b3 = swz > 0 ? la_E2 + swz + ((!rg.lock || uni(swv.x) / nc_ == 0) ? 1 : 0) : -1;
     }
-    if (rg.mir_n > 0 && sh.ob_pos[c] == -1 && iter + 1 <= sh.c.iter_target) {
+    if ((TR::mirror || rg.mir_n > 0) && sh.ob_pos[c] == -1 && iter + 1 <= sh.c.iter_target) {
         const int lim = sh.fill - 8;
         int p1 = -1, mode = 0, pj = -1, jt = 0, ji = 0;
         bool w1 = false, job1 = false;
@@ -1205,7 +1243,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
             const int jo = jgoff + c * ((jt == 1 || jt == 3) ? 1 : S_) + ji;
             const double jx_old = rg.mx[jo];                                  // LDS mirror, kept current by this wave's commits
             const int jop = cs.prior_same ? jo - c * ((jt == 1 || jt == 3) ? 1 : S_) : jo;
-            const double jstep = rg.mir_steps ? rg.mstep[jo] : ld_const(&cs.prior[jop].step);
+            const double jstep = (TR::mirror || rg.mir_steps) ? rg.mstep[jo] : ld_const(&cs.prior[jop].step);
             const double jx_new = jx_old + rg.pg[pj & M] * jstep;             // cls_model.f90:172, as the step will compute it
             if (cs.rayleigh14) {                                              // a Rayleigh prior among vs/qs/corrections (:178-187)
                 if (ld_const(&cs.prior[jop].ptype) == 1 && jx_new <= ld_const(&cs.prior[jop].mu)) mode = 0;      // prior rejects: no evaluation
@@ -1254,7 +1292,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
 // block 0 of a k_mcmc<NCH, F32, 0> launch when the host selects the free-running master (htm_hip.hip: flow_ok)
 // (MB: one of several master workgroups of the launch -- block b runs chains 8 b .. 8 b + 7; returns true in the workgroup that
 // finishes last, which has written the launch's end state and releases the workers)
-template <int NCH, bool F32, bool LOCK = false, bool MB = false>
+template <int NCH, bool F32, bool LOCK = false, bool MB = false, class TR = FlowGeneric>
 __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, int ring_size, int wmax, unsigned long long launch)
 {
     CsRef cs = rebase(cs_);
@@ -1286,6 +1324,7 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int NW = min((int)(blockDim.x >> 6), 8);      // chain waves
     const int nc = cs.n_chains;
+    static_assert(!TR::one_rank || (!LOCK && !MB), "fixed answers: the single-rank free-running master of one workgroup");
     {
         const int vz0 = opaque_zero();
         constexpr int kCtrlWords = (int)(sizeof(Ctrl) / sizeof(int));
@@ -1348,8 +1387,8 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
 
     FlowWave W;
     W.epoch = 0; W.akey = 0; W.rc = 0; W.rpos = 0;
-    W.rc1 = 0; W.rpos1 = flow_next_base<MB>(cs, sh, rg, 0, nc, sh.fill);
-    W.B2 = flow_next_base<MB>(cs, sh, rg, W.rpos1, nc, sh.fill);
+    W.rc1 = 0; W.rpos1 = flow_next_base<MB, TR::one_rank>(cs, sh, rg, 0, nc, sh.fill);
+    W.B2 = flow_next_base<MB, TR::one_rank>(cs, sh, rg, W.rpos1, nc, sh.fill);
     FlowNext nx;
     nx.p = -1; nx.it = 0; nx.c = 0; nx.epoch = 0; nx.type = 5; nx.idx = 0; nx.evt = 1; nx.dec_w = 6; nx.g = 0.0; nx.r = 0.0; nx.logr = 0.0; nx.b3 = -1;
     int iter = i0 + 1;
@@ -1385,7 +1424,7 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
             const int e = tp.epoch;
             if (__builtin_expect(e != W.epoch, 0)) {
                 bool stands = false;
-                if (!flow_adopt<MB>(cs, sh, rg, W, e, iter, c, false, stands, g_mb)) {
+                if (!flow_adopt<MB, TR::one_rank>(cs, sh, rg, W, e, iter, c, false, stands, g_mb)) {
                     if constexpr (MB) { mb_take(mw, mb_look(g_mb, nc, lane)); }      // (the anchor of that epoch is gone or not there yet: look again)
                     continue;
                 }
@@ -1396,8 +1435,8 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
         }
         if (iter > tp.last_iter || tp.err != 0) break;      // (a lock-step rank: the swap of its last iteration is applied after the loop)
         if (__builtin_expect(W.rpos1 < 0 || W.B2 < 0, 0)) {      // predictions the window did not cover when they were made
-            if (W.rpos1 < 0) { W.rpos1 = flow_next_base<MB>(cs, sh, rg, W.rpos, nc - W.rc, sh.fill); W.rc1 = 0; }
-            if (W.B2 < 0 && W.rpos1 >= 0) W.B2 = flow_next_base<MB>(cs, sh, rg, W.rpos1, nc - W.rc1, sh.fill);
+            if (W.rpos1 < 0) { W.rpos1 = flow_next_base<MB, TR::one_rank>(cs, sh, rg, W.rpos, nc - W.rc, sh.fill); W.rc1 = 0; }
+            if (W.B2 < 0 && W.rpos1 >= 0) W.B2 = flow_next_base<MB, TR::one_rank>(cs, sh, rg, W.rpos1, nc - W.rc1, sh.fill);
         }
         // where the step starts: known from the step before (FlowNext), or from the hop table now
         const bool known = nx.p >= 0 && nx.it == iter && nx.c == c && nx.epoch == W.epoch;
@@ -1460,7 +1499,7 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
         }
         // (several master workgroups: a wave has one chain -- "wave" c of as many waves as there are chains)
         if constexpr (MB) MB_HIST(mw, (known ? 4 : 0) | (W.epoch & 3));
-        const int r = flow_step<NCH, F32, LOCK, MB>(f, cs, sh, rg, W, nx, g_mb, mw, s_gath, wmax, s_sx, s_sy, s_sz, c, p, iter, lane, MB ? c : wave,
+        const int r = flow_step<NCH, F32, LOCK, MB, TR>(f, cs, sh, rg, W, nx, g_mb, mw, s_gath, wmax, s_sx, s_sy, s_sz, c, p, iter, lane, MB ? c : wave,
                                               MB ? 64 : NW, launch, wave == 0, look, back, rec_phase == 1, tp);
         if (r == kFlowRestart) continue;
         if (r == kFlowAbort || r == kFlowStop) break;
@@ -1474,14 +1513,14 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
             iter += 1;
             rec_phase = rec_phase + 1 == n_int ? 0 : rec_phase + 1;
             if (W.rpos1 < 0) {    // (the window did not cover the prediction when it was made: it does now)
-                W.rpos1 = flow_next_base<MB>(cs, sh, rg, W.rpos, nc - W.rc, 1 << 30); W.rc1 = 0;
+                W.rpos1 = flow_next_base<MB, TR::one_rank>(cs, sh, rg, W.rpos, nc - W.rc, 1 << 30); W.rc1 = 0;
                 W.B2 = -1;
             }
             W.rc = W.rc1; W.rpos = W.rpos1;
-            W.rc1 = 0; W.rpos1 = W.B2 >= 0 ? W.B2 : flow_next_base<MB>(cs, sh, rg, W.rpos, nc - W.rc, sh.fill);
+            W.rc1 = 0; W.rpos1 = W.B2 >= 0 ? W.B2 : flow_next_base<MB, TR::one_rank>(cs, sh, rg, W.rpos, nc - W.rc, sh.fill);
             // (the base of the iteration after next: looked up during the step, or from the tables now)
             if (nx.p >= 0 && nx.epoch == W.epoch && nx.it == iter && nx.b3 >= 0 && W.rpos1 >= 0) W.B2 = nx.b3;
-            else W.B2 = flow_next_base<MB>(cs, sh, rg, W.rpos1, nc, sh.fill);
+            else W.B2 = flow_next_base<MB, TR::one_rank>(cs, sh, rg, W.rpos1, nc, sh.fill);
         }
     }
 #ifdef HTM_STAMPS

@@ -174,6 +174,8 @@ struct htm_chains {
     unsigned long long launch_seq = 0;         // k_mcmc launches of this chain set so far (the kernels' launch index)
     bool persist = true;                       // k_mcmc (master + resident full-evaluation workers) vs k_step + k_full
     bool flow = false;                         // single-rank loop on the free-running master (htm_flow.hpp) instead of step_body
+    bool flow_fixed = false;                   // ... and the job's shape allows its specialised instantiation (k_mcmc<.., 8>; flow_fixed_ok decides per launch)
+    bool last_fixed = false;                   // the latest MODE_RUN launch was that instantiation
     bool wide = false;                         // more than kMaxChains chains: the loop with barriers at kMaxWideChains (k_mcmc_wide, k_step_wide)
     int worker_cap = 250;                      // most worker blocks a launch takes (HTM_WORKER_CAP)
     long blocks_fit = 0;                       // resident blocks of a k_mcmc launch on this device (htm_chains_share_gpu)
@@ -236,6 +238,13 @@ int launch_full(htm_forward *h, const FullJob &jb, int gy)
     return HTM_OK;
 }
 
+// The free-running master specialised on what the job fixes (flow_body<.., FlowFixed>): what htm_chains_create found
+// (hc->flow_fixed) and what can change afterwards -- the step log (diagnostic runs take the generic instantiation).
+static bool flow_fixed_ok(const htm_chains *hc)
+{
+    return hc->flow && hc->flow_fixed && hc->mb_blocks <= 1 && !hc->pipe && hc->h_ctrl.slog_cap == 0;
+}
+
 int launch_mcmc(htm_chains *hc, int mode, int target, const double *gathered)
 {
     htm_forward *h = hc->fwd;
@@ -289,7 +298,13 @@ int launch_mcmc(htm_chains *hc, int mode, int target, const double *gathered)
         else if (h->nch == 1) HTM_LAUNCH_MCMC(1, false, 7);
         else HTM_LAUNCH_MCMC(2, false, 7);
     }
-    else if (mode == MODE_RUN && hc->flow) HTM_LAUNCH_MCMC_K(3);
+    else if (mode == MODE_RUN && flow_fixed_ok(hc)) {      // (one or two stations per lane: flow_fixed)
+        hc->last_fixed = true;
+        if (h->dev.fp32) { if (h->nch == 1) HTM_LAUNCH_MCMC(1, true, 8); else HTM_LAUNCH_MCMC(2, true, 8); }
+        else if (h->nch == 1) HTM_LAUNCH_MCMC(1, false, 8);
+        else HTM_LAUNCH_MCMC(2, false, 8);
+    }
+    else if (mode == MODE_RUN && hc->flow) { hc->last_fixed = false; HTM_LAUNCH_MCMC_K(3); }
     else if (mode == MODE_RUN) HTM_LAUNCH_MCMC_K(0);
     else if (mode == MODE_LOCKRUN && hc->flow_lock) HTM_LAUNCH_MCMC_K(4);
     else if (mode == MODE_LOCKRUN) HTM_LAUNCH_MCMC_K(2);
@@ -1035,6 +1050,9 @@ int htm_chains_create(htm_forward *h, const htm_chains_init *init, htm_chains **
         // (several master workgroups, k_mcmc<.., 7>: one or two stations per lane)
         if (!hc->wide && h->nch == 1) fns.push_back(h->dev.fp32 ? (const void *)k_mcmc<1, true, 7> : (const void *)k_mcmc<1, false, 7>);
         else if (!hc->wide && h->nch == 2) fns.push_back(h->dev.fp32 ? (const void *)k_mcmc<2, true, 7> : (const void *)k_mcmc<2, false, 7>);
+        // (the free-running master specialised on the job's shape, k_mcmc<.., 8>: likewise)
+        if (!hc->wide && h->nch == 1) fns.push_back(h->dev.fp32 ? (const void *)k_mcmc<1, true, 8> : (const void *)k_mcmc<1, false, 8>);
+        else if (!hc->wide && h->nch == 2) fns.push_back(h->dev.fp32 ? (const void *)k_mcmc<2, true, 8> : (const void *)k_mcmc<2, false, 8>);
         if (hc->step_smem > 48 * 1024)
             for (const void *g : fns) HIPCHK(hipFuncSetAttribute(g, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hc->step_smem));
         // the residency bound holds for whichever main loop gets launched: the smallest of the instantiations' occupancies
@@ -1069,6 +1087,15 @@ int htm_chains_create(htm_forward *h, const htm_chains_init *init, htm_chains **
         const bool window_ok = hc->persist && !hc->wide && !(e && e[0] == '0') && d.dbg == 0 && hc->dev.mirror_n > 0 &&
                                hc->ring_size >= 4 * wd + 32 + 2 * c_max + 16;
         hc->flow = window_ok && d.n_procs == 1;
+        // Its instantiation specialised on what the job fixes (FlowFixed, htm_flow.hpp): one rank, up to eight chains (a wave per
+        // chain: the shapes it is tested and measured at), full rows of 64 or 128 stations with both data types, the mirror with its
+        // step sizes.  Chosen from what the library observes; HTM_FAST=0 only forces the generic instantiation (A/B runs, tests).
+        // The step log can be switched on after this point: launch_mcmc looks at it (flow_fixed_ok).
+        {
+            const char *ef = getenv("HTM_FAST");
+            hc->flow_fixed = hc->flow && !(ef && ef[0] == '0') && nc <= 8 && (h->nch == 1 || h->nch == 2) && h->S == 64 * h->nch &&
+                             h->dev.use_time != 0 && h->dev.use_amp != 0 && hc->dev.mirror_n == (int)mir && hc->dev.mirror_steps != 0;
+        }
         // More than eight chains on a rank: a master workgroup for every eight (k_mcmc<.., 7>, htm_flow.hpp MbShared) instead of
         // rounds on the same eight waves.
         {
@@ -2150,6 +2177,16 @@ int htm_chains_last_run_stats(htm_chains *hc, double *device_us, int *graph_laun
     if (graph_launches) *graph_launches = hc->last_graph_launches;
     if (full_evals) *full_evals = hc->last_full;
     if (partial_evals) *partial_evals = hc->last_part;
+    return HTM_OK;
+}
+
+// 1: the latest single-rank launch ran the free-running master's specialised instantiation (k_mcmc<.., 8>; master_stats reports
+// loop 3 for it as for the generic one); 0: any other loop, or nothing launched yet
+int htm_chains_fixed_master(htm_chains *hc, int *on, int *worker_blocks)
+{
+    if (!hc || !on) return fail(HTM_EINVAL, "NULL argument");
+    *on = (hc->last_fixed && hc->flow) ? 1 : 0;
+    if (worker_blocks) *worker_blocks = hc->dev.n_workers;
     return HTM_OK;
 }
 

@@ -288,6 +288,12 @@ int htm_chains_handoff_stats(htm_chains *hc, int64_t *orders_put_aside);
  * counterpart (diagnostics).  Synchronises with the handle's stream. */
 int htm_chains_master_stats(htm_chains *hc, int *single_rank_loop, int *lockstep_loop, int64_t *flushes);
 
+/* *on = 1 if the latest single-rank launch of this chain set ran the free-running master's instantiation that is specialised on
+ * what the job fixes (one rank, at most 8 chains, 64 or 128 stations with both data types, no step log: DESIGN.md 3.0; htm_chains_master_stats reports loop 3 for it as for the generic one), else 0.  The library selects
+ * it from what it observes; HTM_FAST=0 in the environment at htm_chains_create forces the generic instantiation.
+ * *worker_blocks (may be NULL) = the worker blocks of a launch.  No reference counterpart (diagnostics). */
+int htm_chains_fixed_master(htm_chains *hc, int *on, int *worker_blocks);
+
 /* Same work as htm_chains_run, but every kernel is launched eagerly and bracketed by its own pair of HIP
  * events on the handle's stream, so that the average duration of each kernel comes from the run itself:
  * k_step (proposals + partial updates + judge + swap; may cover several iterations per launch) and k_full
