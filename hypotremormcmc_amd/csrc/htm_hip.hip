@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "htm_convert.hpp"
+#include "htm_diag.hpp"
 #include "htm_kernels.hpp"
 #include "htm_pipe.hpp"
 #include "htm_select.hpp"
@@ -2332,6 +2333,103 @@ int htm_quantiles(int device, const double *samples, long n_mod, long n_par, con
     if (rc == HTM_OK && hipMemcpy(out, d_o, ob, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HTM_EHIP, "download failed");
     (void)hipFree(d_x); (void)hipFree(d_o);
     return rc;
+}
+
+// ---- convergence diagnostics (htm_diag.hpp) ---------------------------------------------------------------------
+namespace {
+// shapes both forms refuse before any device call
+int diag_check(long n_seq, long n_draws, long n_par, int max_lag)
+{
+    if (n_draws < 4 || n_seq < 1 || n_par < 1 || max_lag < 1)
+        return fail(HTM_EINVAL, "bad shape (n_seq %ld, n_draws %ld, n_par %ld, max_lag %d): need n_draws >= 4, the others >= 1",
+                    n_seq, n_draws, n_par, max_lag);
+    if (n_seq > INT_MAX / n_draws) return fail(HTM_EINVAL, "n_seq * n_draws = %ld * %ld exceeds %d rows", n_seq, n_draws, INT_MAX);
+    return HTM_OK;
+}
+}  // namespace
+
+int htm_diagnose_dev(int device, const double *d_samples, long n_seq, long n_draws, long n_par, long ld, int max_lag,
+                     double *d_out, double *d_acov, void *hip_stream)
+{
+    if (!d_samples || !d_out) return fail(HTM_EINVAL, "NULL argument");
+    int rc = diag_check(n_seq, n_draws, n_par, max_lag);
+    if (rc) return rc;
+    if (ld < n_par) return fail(HTM_EINVAL, "bad shape (n_par %ld, ld %ld)", n_par, ld);
+    const long n = n_draws / 2, S = 2 * n_seq;
+    const int L = (int)std::min(n - 1, (long)max_lag);
+    // lags per thread: HTM_DIAG_LAGS=16|32 picks the other instantiation (tests, tools/bench_diagnose.py)
+    int kb = 32;
+    if (const char *e = getenv("HTM_DIAG_LAGS")) {
+        kb = atoi(e);
+        if (kb != 16 && kb != 32) return fail(HTM_EINVAL, "HTM_DIAG_LAGS = %s: 16 or 32", e);
+    }
+    const long n_cg = (n_par + 63) / 64, n_blk = L / kb + 1, n_lagwg = (n_blk + kDiagLW - 1) / kDiagLW;
+    if (n_cg > INT_MAX / S || n_cg > INT_MAX / n_lagwg)
+        return fail(HTM_EINVAL, "n_par %ld, %ld split sequences, %d lags need more than 2^32 - 1 work-items in one launch", n_par, S, L + 1);
+    // slabs of split sequences: waves enough to fill the chip many times over, so that the last round of workgroups costs
+    // little; a workspace of at most 256 MiB or half the samples' size
+    long slabs = std::min(S, (65536 + n_cg * n_blk - 1) / (n_cg * n_blk));
+    const double lag_bytes = (double)(L + 1) * (double)n_par * sizeof(double);
+    const double ws_cap = std::max((double)(256L << 20), (double)(n_seq * n_draws) * (double)n_par * sizeof(double) / 2);
+    slabs = std::max(1L, std::min(slabs, (long)(ws_cap / lag_bytes)));
+    if (const char *e = getenv("HTM_DIAG_SLABS")) slabs = std::max(1L, std::min(atol(e), S));
+    const long seq_per_slab = (S + slabs - 1) / slabs;
+    slabs = (S + seq_per_slab - 1) / seq_per_slab;          // no empty slab
+    if (n_cg * n_lagwg > INT_MAX / slabs || n_cg * S * 64 * kDiagRG > 0xffffffffL || n_cg * n_lagwg * slabs * 64 * kDiagLW > 0xffffffffL)
+        return fail(HTM_EINVAL, "n_par %ld, %ld split sequences, %d lags need more than 2^32 - 1 work-items in one launch", n_par, S, L + 1);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
+    HIPCHK(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    // workspace: the means [S][n_par], the slabs' lag sums [slabs][L+1][n_par] (stream-ordered, as htm_quantiles_dev's)
+    const size_t mean_n = (size_t)S * n_par, part_n = (size_t)slabs * (L + 1) * n_par, total = (mean_n + part_n) * sizeof(double);
+    double *ws = nullptr;
+    bool async_alloc = hipMallocAsync(reinterpret_cast<void **>(&ws), total, st) == hipSuccess;
+    if (!async_alloc) {
+        (void)hipGetLastError();
+        if (hipMalloc(reinterpret_cast<void **>(&ws), total) != hipSuccess) return fail(HTM_EHIP, "hipMalloc of %zu bytes failed", total);
+    }
+    double *d_mean = ws, *d_part = ws + mean_n;
+    hipLaunchKernelGGL(k_diag_mean, dim3((unsigned)(n_cg * S)), dim3(64 * kDiagRG), 0, st, d_samples, n_draws, n, n_par, ld, n_cg, d_mean);
+    const dim3 grid((unsigned)(n_cg * n_lagwg * slabs)), block(64 * kDiagLW);
+    if (kb == 16)
+        hipLaunchKernelGGL(k_diag_acov<16>, grid, block, 0, st, d_samples, n_draws, n, n_par, ld, L, (int)S, (int)seq_per_slab, n_lagwg, n_cg, d_mean, d_part);
+    else
+        hipLaunchKernelGGL(k_diag_acov<32>, grid, block, 0, st, d_samples, n_draws, n, n_par, ld, L, (int)S, (int)seq_per_slab, n_lagwg, n_cg, d_mean, d_part);
+    hipLaunchKernelGGL(k_diag_finish, dim3((unsigned)n_cg), dim3(64), 0, st, d_part, d_mean, n, n_par, L, (int)S, (int)slabs,
+                       1.0 / std::log10((double)S * (double)n), d_out, d_acov);
+    HIPCHK(hipGetLastError());
+    if (async_alloc) {
+        HIPCHK(hipFreeAsync(ws, st));
+    } else {
+        HIPCHK(hipStreamSynchronize(st));
+        (void)hipFree(ws);
+    }
+    return HTM_OK;
+}
+
+int htm_diagnose(int device, const double *samples, long n_seq, long n_draws, long n_par, int max_lag, double *out, double *acov)
+{
+    if (!samples || !out) return fail(HTM_EINVAL, "NULL argument");
+    int rc = diag_check(n_seq, n_draws, n_par, max_lag);
+    if (rc) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
+    HIPCHK(hipSetDevice(device));
+    const long L = std::min(n_draws / 2 - 1, (long)max_lag);
+    const size_t xb = (size_t)n_seq * n_draws * n_par * sizeof(double), ob = (size_t)n_par * 4 * sizeof(double),
+                 ab = acov ? (size_t)(L + 1) * n_par * sizeof(double) : 0;
+    std::vector<void *> pool;
+    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
+    double *d_x = nullptr, *d_o = nullptr, *d_a = nullptr;
+    if ((rc = dev_upload(pool, &d_x, samples, xb / sizeof(double))) || (rc = dev_alloc(pool, &d_o, ob / sizeof(double))) ||
+        (acov && (rc = dev_alloc(pool, &d_a, ab / sizeof(double)))))
+        return done(rc);
+    rc = htm_diagnose_dev(device, d_x, n_seq, n_draws, n_par, n_par, max_lag, d_o, d_a, nullptr);
+    if (rc == HTM_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(HTM_EHIP, "the diagnostics kernels failed");
+    if (rc == HTM_OK && hipMemcpy(out, d_o, ob, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HTM_EHIP, "download failed");
+    if (rc == HTM_OK && acov && hipMemcpy(acov, d_a, ab, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HTM_EHIP, "download failed");
+    return done(rc);
 }
 
 int htm_select_regress(int device, int n_sta, int n_win, const double *sta_x, const double *sta_y, const double *sta_z,

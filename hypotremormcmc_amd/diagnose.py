@@ -1,0 +1,156 @@
+"""Convergence diagnostics of a step-5 run on the GPU: split R-hat and effective sample size of every parameter
+step 6 summarises, from the same sample files (Vehtari et al. 2021 / Stan, without rank normalisation; the
+definitions are in DESIGN.md §3.6, the kernels in hypotremormcmc_amd/csrc/htm_diag.hpp).
+
+    python -m hypotremormcmc_amd.diagnose <parameter file> [--max-lag N] [--rhat 1.01]
+
+run in the directory of the step-5 outputs, writes `convergence.stat` next to the `.stat` files of
+`hypotremormcmc_amd.statistics`: one line per parameter with R-hat, ESS, the autocorrelation time tau (ESS =
+samples / tau) and the lag at which Geyer's pair sums went negative (-1: they did not within --max-lag, the ESS is
+then an upper bound).  Parameters the job fixes (`solve_vs = F`, ...) are constant and are written as NaN.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+
+from . import _lib
+from .param import Param
+from .statistics import INT_MAX, read_sample_file
+
+STAT_HEADER = "# parameter, R-hat (split), ESS, tau, lag of the first negative pair sum (-1: none up to the last lag)"
+
+
+def diagnose(samples, n_seq: int, max_lag: int = 1000, device: int = 0, return_acov: bool = False):
+    """[n_par][4] = (rhat, ess, tau, lags) of every column of samples [n_seq * n_draws][n_par], sequence m in rows
+    m * n_draws .. (m + 1) * n_draws - 1, on the GPU.  With return_acov also the averaged autocovariances
+    [(L + 1)][n_par], L = min(n_draws // 2 - 1, max_lag)."""
+    shape = np.shape(samples)
+    if len(shape) == 1:
+        shape = (shape[0], 1)
+    if len(shape) != 2:
+        raise ValueError(f"samples must be [rows][n_par], got shape {shape}")
+    n_rows, n_par = shape
+    n_seq, max_lag = int(n_seq), int(max_lag)
+    if n_rows > INT_MAX:      # ctypes would pass it on; htm_diagnose counts rows in int
+        raise ValueError(f"rows = {n_rows} exceeds {INT_MAX}: htm_diagnose takes at most {INT_MAX} rows")
+    if n_seq < 1 or n_par < 1 or max_lag < 1 or max_lag > INT_MAX:
+        raise ValueError(f"need n_seq >= 1, n_par >= 1 and 1 <= max_lag <= {INT_MAX} (got {n_seq}, {n_par}, {max_lag})")
+    if n_rows % n_seq:
+        raise ValueError(f"{n_rows} rows are not {n_seq} sequences of equal length")
+    n_draws = n_rows // n_seq
+    if n_draws < 4:
+        raise ValueError(f"n_draws = {n_draws}: a sequence needs at least 4 draws to be split")
+    x = np.ascontiguousarray(samples, dtype=np.float64).reshape(n_rows, n_par)
+    if not np.isfinite(x).all():
+        raise ValueError("samples hold NaN or inf")
+    n_lag = min(n_draws // 2 - 1, max_lag) + 1
+    out = np.empty((n_par, 4))
+    acov = np.empty((n_lag, n_par)) if return_acov else None
+    lib = _lib.load()
+    _lib.check(lib.htm_diagnose(device, x.ctypes.data_as(_lib.dp), n_seq, n_draws, n_par, max_lag, out.ctypes.data_as(_lib.dp),
+                                acov.ctypes.data_as(_lib.dp) if return_acov else None))
+    return (out, acov) if return_acov else out
+
+
+def sequences_by_iteration(iters, values, k: int):
+    """The sequence-major sample matrix `diagnose` takes, from the records of all ranks' sample files.
+
+    iters [n_rec], values [n_rec][n_par]: what `statistics.read_sample_file` returns per rank, stacked in rank order.
+    The records are stable-sorted by iteration; every recorded iteration must hold exactly k = n_procs * n_cool
+    records (the swaps conserve the multiset of temperatures, so this holds over all ranks although the T = 1 role
+    moves between them).  Sequence j is the j-th record of every iteration, so a sequence is a T = 1 *slot*, not one
+    chain's trajectory: the diagnostics describe the sample set that step 6 summarises."""
+    iters = np.asarray(iters)
+    values = np.asarray(values, dtype=np.float64)
+    if values.ndim == 1:
+        values = values[:, None]
+    if iters.ndim != 1 or len(iters) != len(values):
+        raise ValueError(f"{len(iters)} iterations for {len(values)} records")
+    order = np.argsort(iters, kind="stable")
+    it_u, counts = np.unique(iters[order], return_counts=True)
+    bad = np.nonzero(counts != k)[0]
+    if len(bad):
+        raise ValueError(f"iteration {int(it_u[bad[0]])} holds {int(counts[bad[0]])} records, not n_procs * n_cool = {k}")
+    n_it, n_par = len(it_u), values.shape[1]
+    return np.ascontiguousarray(values[order].reshape(n_it, k, n_par).transpose(1, 0, 2)).reshape(k * n_it, n_par)
+
+
+def parameter_names(station_names, win_id):
+    names = ["vs", "qs"]
+    names += ["t_corr %s" % s.strip() for s in station_names]
+    names += ["a_corr %s" % s.strip() for s in station_names]
+    names += ["%s %d" % (c, w) for w in win_id for c in "xyz"]
+    return names + ["log_likelihood"]
+
+
+def stat_text(names, out) -> str:
+    """the text of convergence.stat for out [n_par][4]; a row of NaN (a constant column) is written as NaN"""
+    lines = [STAT_HEADER]
+    for name, (rhat, ess, tau, lags) in zip(names, np.asarray(out, dtype=np.float64)):
+        if np.isnan(rhat):
+            lines.append("%-24s" % name + "%13s" % "NaN" * 3 + "%7s" % "NaN")
+        else:
+            lines.append("%-24s" % name + "%13.6f%13.6f%13.6f" % (rhat, ess, tau) + "%7d" % int(lags))
+    return "\n".join(lines) + "\n"
+
+
+def summary_text(names, out, rhat_limit: float) -> str:
+    out = np.asarray(out, dtype=np.float64)
+    live = np.nonzero(~np.isnan(out[:, 0]))[0]
+    if not len(live):
+        return "no parameter varies: nothing to diagnose\n"
+    worst, small = live[np.argmax(out[live, 0])], live[np.argmin(out[live, 1])]
+    return (f"{len(live)} parameters ({len(out) - len(live)} constant)\n"
+            f"largest R-hat  {out[worst, 0]:.6f}  ({names[worst]})\n"
+            f"smallest ESS   {out[small, 1]:.1f}  ({names[small]})\n"
+            f"R-hat > {rhat_limit:g}: {int(np.sum(out[live, 0] > rhat_limit))} parameters\n"
+            f"pair sums not negative within the lags examined (ESS is an upper bound): "
+            f"{int(np.sum(out[live, 3] < 0))} parameters\n")
+
+
+def gather_sequences(work_dir, n_procs, n_sta, n_events, n_burn, k):
+    """all ranks' sample files and the recorded part of their log-likelihood traces as one sequence-major matrix:
+    columns vs, qs, t_corr, a_corr, hypo, log-likelihood"""
+    its, vals = [], []
+    for r in range(n_procs):
+        cols, it_r = [], None
+        for nm, nv in (("vs", 1), ("qs", 1), ("t_corr", n_sta), ("a_corr", n_sta), ("hypo", 3 * n_events)):
+            it, v = read_sample_file(os.path.join(work_dir, "%s.%02d.out" % (nm, r)), nv)
+            if it_r is not None and not np.array_equal(it, it_r):
+                raise ValueError(f"{nm}.{r:02d}.out records other iterations than vs.{r:02d}.out")
+            it_r = it
+            cols.append(v)
+        it, v = read_sample_file(os.path.join(work_dir, "likelihood%02d.out" % r), 1)
+        keep = it > n_burn               # the trace also covers the burn-in (src/hypo_tremor_mcmc.f90:270-280)
+        if not np.array_equal(it[keep], it_r):
+            raise ValueError(f"likelihood{r:02d}.out records other iterations after the burn-in than vs.{r:02d}.out")
+        cols.append(v[keep])
+        its.append(it_r)
+        vals.append(np.concatenate(cols, axis=1))
+    return sequences_by_iteration(np.concatenate(its), np.concatenate(vals, axis=0), k)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m hypotremormcmc_amd.diagnose", description=__doc__.split("\n\n")[0])
+    ap.add_argument("parameter_file")
+    ap.add_argument("--max-lag", type=int, default=1000)
+    ap.add_argument("--rhat", type=float, default=1.01, help="R-hat above which a parameter is counted in the summary")
+    args = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    par = Param(args.parameter_file)
+    work = os.path.dirname(os.path.abspath(args.parameter_file))
+    win_id = [int(ln.split()[0]) for ln in open(os.path.join(work, "selected_win.dat")) if ln.strip()]
+    k = par.get_n_procs() * par.get_n_cool()
+    x = gather_sequences(work, par.get_n_procs(), par.n_stations, len(win_id), par.get_n_burn(), k)
+    out = diagnose(x, k, max_lag=args.max_lag, device=int(os.environ.get("HTM_DEVICE", "0")))
+    names = parameter_names(par.stations, win_id)
+    with open(os.path.join(work, "convergence.stat"), "w") as fh:
+        fh.write(stat_text(names, out))
+    sys.stdout.write(summary_text(names, out, args.rhat))
+
+
+if __name__ == "__main__":
+    main()

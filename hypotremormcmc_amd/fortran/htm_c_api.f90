@@ -15,7 +15,7 @@ module htm_c_api
   public :: htm_chains_xchg_handle, htm_chains_xchg_connect, htm_chains_xchg_probe, htm_chains_run_lockstep_direct
   public :: HTM_XCHG_HANDLE_BYTES, HTM_COMM_ID_BYTES
   public :: htm_comm_unique_id, htm_comm_create, htm_comm_destroy, htm_chains_run_lockstep_comm
-  public :: htm_device_count, htm_device_physical_id, htm_quantiles, htm_select_regress
+  public :: htm_device_count, htm_device_physical_id, htm_quantiles, htm_diagnose, htm_select_regress
   public :: htm_chains_checkpoint_size, htm_chains_checkpoint_save, htm_chains_checkpoint_load
 
   integer(c_size_t), parameter :: HTM_XCHG_HANDLE_BYTES = 64_c_size_t, HTM_COMM_ID_BYTES = 128_c_size_t
@@ -235,6 +235,18 @@ module htm_c_api
        real(c_double), intent(out) :: out(*)
        integer(c_int) :: rc
      end function htm_quantiles
+     !> convergence diagnostics (include/htm_hip.h): samples [n_seq*n_draws][n_par] row-major, out [n_par][4] =
+     !> rhat, ess, tau, lags; acov [(L+1)][n_par], L = min(n_draws/2 - 1, max_lag), or c_null_ptr
+     function htm_diagnose(device, samples, n_seq, n_draws, n_par, max_lag, out, acov) bind(C, name="htm_diagnose") result(rc)
+       import :: c_int, c_long, c_double, c_ptr
+       integer(c_int), value :: device
+       real(c_double), intent(in) :: samples(*)
+       integer(c_long), value :: n_seq, n_draws, n_par
+       integer(c_int), value :: max_lag
+       real(c_double), intent(out) :: out(*)
+       type(c_ptr), value :: acov
+       integer(c_int) :: rc
+     end function htm_diagnose
      !> step-4 regressions (include/htm_hip.h): t, t_err, a, a_err (n_sta, n_win); out (6, n_win) = vs, b, t0, a0, cc_t, cc_a
      function htm_select_regress(device, n_sta, n_win, sta_x, sta_y, sta_z, z_guess, t, t_err, a, a_err, out) &
           & bind(C, name="htm_select_regress") result(rc)

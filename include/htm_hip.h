@@ -319,6 +319,22 @@ int htm_quantiles_dev(int device, const double *d_samples, long n_mod, long n_pa
                       const int ranks_1based[3], double *d_out, void *hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Convergence diagnostics of recorded samples: split R-hat and effective sample size per parameter,
+ * Vehtari et al. 2021 / Stan without rank normalisation.  samples [n_seq*n_draws][n_par] row-major, sequence m in
+ * rows m*n_draws .. (m+1)*n_draws - 1.  Every sequence is split into its first and its last n = n_draws/2 draws; the
+ * biased autocovariances of the 2 n_seq split sequences are averaged for lags 0..L, L = min(n - 1, max_lag).
+ * out [n_par][4] = {rhat, ess, tau, lags}: ess = 2 n_seq n / tau; lags = the lag at which Geyer's pair sums first went
+ * negative, or -1 if none did by L (ess is then an upper bound); a constant column gives four NaN.  acov, if not
+ * NULL, receives the averaged autocovariances [(L+1)][n_par].  n_draws >= 4, n_seq, n_par, max_lag >= 1,
+ * n_seq * n_draws <= INT_MAX, else HTM_EINVAL before any device call.  Every sum has a fixed order: two calls give
+ * the same bits.  Host pointers; synchronous.  The _dev form takes device pointers (ld = row stride in doubles) and
+ * is asynchronous on `hip_stream` (NULL = the null stream). */
+int htm_diagnose(int device, const double *samples, long n_seq, long n_draws, long n_par, int max_lag,
+                 double *out, double *acov);
+int htm_diagnose_dev(int device, const double *d_samples, long n_seq, long n_draws, long n_par, long ld,
+                     int max_lag, double *d_out, double *d_acov, void *hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Step 4, `hypo_tremor_select`   reference: src/cls_selector.f90:75-132, src/mod_regress.f90
  * For every detected window: the station of largest amplitude is taken as the epicentre (depth z_guess), the
  * amplitudes are corrected for geometrical spreading (+ ln d), and arrival time and amplitude are regressed
