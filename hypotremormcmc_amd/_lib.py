@@ -49,6 +49,7 @@ SIGNATURES = {
     "htm_forward_create": (C.c_int, [C.c_int, C.c_int] + [dp] * 7 + [C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
     "htm_forward_destroy": (C.c_int, [vp]),
     "htm_forward_set_precision": (C.c_int, [vp, C.c_int]),
+    "htm_forward_obs_pack_bytes": (C.c_int, [vp, C.POINTER(C.c_int64)]),
     "htm_forward_set_stream": (C.c_int, [vp, vp]),
     "htm_forward_reset_stream": (C.c_int, [vp]),
     "htm_forward_loglik_full": (C.c_int, [vp, dp, dp, C.c_double, dp, C.c_double, dp]),

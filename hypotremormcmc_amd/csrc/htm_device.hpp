@@ -258,7 +258,16 @@ struct FwdDev {
     // Demean sums, residuals, the misfit sum and the Metropolis decision stay fp64 (:125-132, :281-299).
     const float *t_obs32, *t_prec32, *a_obs32, *a_prec32;
     int fp32;           // host-side dispatch only: the F32 = true instantiations of the kernels are launched
+    // One packed record per event for the specialised chain master (htm_flow.hpp FlowFixed; load_obs_pack below), in the
+    // element type of the forward in use: [t_obs row | t_prec row | a_obs row | a_prec row | rpsum_t, rpsum_a (double)],
+    // obs_pack_stride bytes apart.  nullptr unless a chain set that can run that master was created on this forward.
+    const void *obs_pack;
 };
+
+// bytes from one event's packed record to the next: four rows of 64 * NCH elements and two doubles, padded to 64 bytes
+template <int NCH, bool F32>
+constexpr size_t obs_pack_stride() { return ((size_t)4 * 64 * NCH * (F32 ? 4 : 8) + 16 + 63) & ~size_t(63); }
+inline constexpr size_t obs_pack_stride(int nch, bool f32) { return ((size_t)4 * 64 * nch * (f32 ? 4 : 8) + 16 + 63) & ~size_t(63); }
 
 // Immutable inputs (priors, step sizes, precision sums) at a wave-uniform address: a load through the constant
 // address space is selected as a SCALAR load (K$), which costs no vector-memory slot and no VGPR.  Only for data
@@ -392,6 +401,38 @@ __device__ __forceinline__ void load_obs_regs_nobranch(ObsRegs<NCH, F32> &ob, co
         ob.rpst = ut ? ld_const(f.rpsum_t + ev) : 1.0;
         ob.rpsa = ua ? ld_const(f.rpsum_a + ev) : 1.0;
     }
+}
+
+// The same values from the event's packed record (FwdDev::obs_pack; full rows of 64 * NCH stations, both data types): ONE
+// 64-bit address per lane, the four rows at immediate offsets from it, the two reciprocal sums with one 16-byte scalar load
+// from the same base -- no row pointers, no run-time row length, no pointer chase to the sums.  The chain master's only
+// (a worker reads its rows once per launch and keeps load_obs_regs_nobranch).
+// a load from device memory through a pointer whose address space the compiler has lost sight of (it came through a register
+// constraint): as a GLOBAL load, not a flat one -- a flat load counts as an LDS / scalar-memory operation too, so the wait for
+// the next scalar load would wait for it as well
+template <class T>
+__device__ __forceinline__ T ld_global(const T *p)
+{
+    typedef const T __attribute__((address_space(1))) *GP;
+    return *(GP)(unsigned long long)p;
+}
+
+template <int NCH, bool F32>
+__device__ __forceinline__ void load_obs_pack(ObsRegs<NCH, F32> &ob, const void *pack, int ev, int lane)
+{
+    typedef typename ObsRegs<NCH, F32>::T T;
+    typedef double f64x2_ __attribute__((ext_vector_type(2)));
+    typedef const f64x2_ __attribute__((address_space(4))) *CP;
+    constexpr int S = 64 * NCH;
+    const char *rec = reinterpret_cast<const char *>(pack) + (size_t)ev * obs_pack_stride<NCH, F32>();
+    const T *row = reinterpret_cast<const T *>(rec) + lane;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        ob.tob[c] = ld_global(row + 64 * c); ob.tpr[c] = ld_global(row + S + 64 * c);
+        ob.aob[c] = ld_global(row + 2 * S + 64 * c); ob.apr[c] = ld_global(row + 3 * S + 64 * c);
+    }
+    const f64x2_ s = *(CP)(unsigned long long)(rec + (size_t)4 * S * sizeof(T));
+    ob.rpst = s[0]; ob.rpsa = s[1];
 }
 
 // PRE: `beta` and `q` hold 1 / vs and pi f / (qs vs) already -- the caller formed them once (a worker per order, the chain master

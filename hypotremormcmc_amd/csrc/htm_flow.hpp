@@ -191,6 +191,7 @@ struct FlowTop {
     unsigned book_tag;
     double L;
     double rbeta, katt;           // the chain's 1 / vs and pi f / (qs vs) (FlowShared)
+    int n_lik, n_smp, avail;      // (the specialised master) what chain 0's wave decides the launch's end from: three more round trips there
 };
 
 // What a job fixes, asked through a traits type: flow_step, flow_body and the helpers they call put every such question to
@@ -207,6 +208,18 @@ struct FlowGeneric {
 };
 struct FlowFixed {
     static constexpr bool full_rows = true, one_rank = true, mirror = true;
+};
+
+// every answer fixed: the specialised master (k_mcmc<.., 8>)
+template <class TR> constexpr bool flow_fixed_v = TR::full_rows && TR::one_rank && TR::mirror;
+
+// the lane's station coordinates, kept in registers for the launch by the specialised master with one station per lane
+struct FlowSta {
+    double x, y, z;
+    // the lane's part in the step's gather of six chain-state values (lane 0 the perturbed element, 1..3 the event's x, y, z,
+    // 4 vs, 5 qs), as masks in vector registers: m_el / m_hyp / m_sc all ones where the lane reads the element / a coordinate /
+    // vs or qs; d_hyp = lane - 1; m_qs all ones on lane 5
+    int m_el, m_hyp, m_sc, d_hyp, m_qs;
 };
 
 constexpr int kFlowRestart = -1;  // flow_step: the step's position was disproved before its turn came: run it again
@@ -526,7 +539,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
                                          MbShared *g_mb, MbWave &mw, double *s_gath, int wmax,
                                          const double *s_sx, const double *s_sy, const double *s_sz, int c, int p, int iter,
                                          int lane, int wave, int NW, unsigned long long launch, bool ext, int look, int back,
-                                         bool rec_now, const FlowTop &tp)
+                                         bool rec_now, const FlowTop &tp, const FlowSta &fs)
 {
     CsRef cs = rebase(cs_);
     FwRef f = rebase(f_);
@@ -555,8 +568,15 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
     const double *xall_ = cs.xall;
     const PriorRec *prior_ = cs.prior;
     static_assert(!TR::full_rows || NCH > 0, "full rows: one or two stations per lane");
-    const int nc_ = cs.n_chains, S_ = TR::full_rows ? 64 * NCH : cs.S, nh = 3 * cs.E, psame_ = cs.prior_same;
-    asm volatile("" : "+s"(xall_), "+s"(prior_));
+    constexpr bool FX = flow_fixed_v<TR>;
+    constexpr int LS = NCH == 2 ? 7 : 6;        // (full rows: log2 of the row length)
+    int nc_ = cs.n_chains, nh = 3 * cs.E, psame_ = cs.prior_same;
+    const int S_ = TR::full_rows ? 64 * NCH : cs.S;
+    const void *pack_ = nullptr;
+    if constexpr (FX) pack_ = f.obs_pack;
+    // (the specialised master: everything the step takes from the kernel arguments in ONE batch of scalar loads -- one wait)
+    if constexpr (FX) asm volatile("" : "+s"(xall_), "+s"(prior_), "+s"(pack_), "+s"(nc_), "+s"(nh), "+s"(psame_));
+    else asm volatile("" : "+s"(xall_), "+s"(prior_));
     // the decoded proposal (htm_stream.hpp), its Gaussian and its judge draw: looked up during the step before (FlowNext), or here
     int type, idx, evt, dec_w;
     double g, r_ring, logr_ring;
@@ -572,27 +592,56 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
     nx.p = -1;
     const bool partial = evt > 0 && iter > 1;       // hypo_tremor_mcmc.f90:246
     const int off_tc = nc_, off_qs = nc_ + nc_ * S_, off_ac = 2 * nc_ + nc_ * S_, off_hy = 2 * nc_ + 2 * nc_ * S_;
-    const int goff = type == 1 ? 0 : type == 2 ? off_tc : type == 3 ? off_qs : type == 4 ? off_ac : off_hy;
-    const int gnx = (type == 1 || type == 3) ? 1 : (type == 2 || type == 4) ? S_ : nh;
+    int goff, gnx;
+    if constexpr (FX) {
+        // [vs | t_corr | qs | a_corr | hypo]: groups 2 and 4 start a row of scalars further, 3 and 5 a block of rows further --
+        // arithmetic on the type (5, 6, 7: the hypocentres), not a ladder of compares
+        const int tm = min(type, 5), hyp = -((type + 3) >> 3), even = (type & 1) ^ 1;      // (hyp: all ones for a hypocentre step)
+        goff = (tm >> 1) * nc_ + ((((tm - 1) >> 1) * nc_) << LS);
+        gnx = (nh & hyp) | (((even << LS) | (even ^ 1)) & ~hyp);
+    } else {
+        goff = type == 1 ? 0 : type == 2 ? off_tc : type == 3 ? off_qs : type == 4 ? off_ac : off_hy;
+        gnx = (type == 1 || type == 3) ? 1 : (type == 2 || type == 4) ? S_ : nh;
+    }
     const int o = goff + c * gnx + idx;             // element of the rank's parameter vector this step perturbs
     const int ev = partial ? evt - 1 : 0;
     const int o_h = off_hy + c * nh + 3 * ev;
     int goffs = o;
+    if constexpr (FX) {
+        // (the lane's part as masks in vector registers, formed once per launch: FlowSta.  A chain of selects on the lane id keeps
+        // five loop-invariant lane masks in scalar registers the loop does not have: they were spilled and reloaded every step)
+        goffs = (o & fs.m_el) | ((o_h + fs.d_hyp) & fs.m_hyp) | ((c + (off_qs & fs.m_qs)) & fs.m_sc);
+    } else {
     goffs = lane == 1 ? o_h : goffs; goffs = lane == 2 ? o_h + 1 : goffs; goffs = lane == 3 ? o_h + 2 : goffs;
     goffs = lane == 4 ? c : goffs; goffs = lane == 5 ? off_qs + c : goffs;
-    const double gathered_v = xall_[goffs];
+    }
+    double gathered_v;
+    if constexpr (FX) gathered_v = ld_global(xall_ + goffs);      // (global, not flat: htm_device.hpp ld_global)
+    else gathered_v = xall_[goffs];
     const PriorRec prr = ld_prior(prior_ + (psame_ ? o - c * gnx : o));      // (one 32-byte scalar load: PriorRec)
     const double mu = prr.mu, rs2 = prr.rs2, step = prr.step;
     const int ptype = prr.ptype;
     const double *tc = xall_ + off_tc + c * S_, *ac = xall_ + off_ac + c * S_;
     StaRegs<(NCH > 0 ? NCH : 1)> st;
     ObsRegs<(NCH > 0 ? NCH : 1), F32> ob;
-    if (partial) {
-        if constexpr (NCH > 0) {
-            load_sta_regs<NCH, TR::full_rows>(st, f.S, lane, s_sx, s_sy, s_sz, tc, ac, 0, -1, 0.0);
-            if constexpr (TR::full_rows) load_obs_regs_nobranch<NCH, F32, false, false, true>(ob, f, ev, lane);
-            else load_obs_regs<NCH, F32>(ob, f, ev, lane);      // in flight while the proposal is worked out
+    // (the specialised master: the event's packed record; with one station per lane the coordinates are in registers)
+    auto load_inputs = [&](int e_) __attribute__((always_inline)) {
+        if constexpr (FX) {
+#pragma unroll
+            for (int k = 0; k < (NCH > 0 ? NCH : 1); ++k) {
+                const int j = lane + 64 * k;
+                if constexpr (NCH == 1) { st.sx[k] = fs.x; st.sy[k] = fs.y; st.sz[k] = fs.z; }
+                else { st.sx[k] = s_sx[j]; st.sy[k] = s_sy[j]; st.sz[k] = s_sz[j]; }
+                st.tc[k] = ld_global(tc + j); st.ac[k] = ld_global(ac + j);
+            }
         }
+        else load_sta_regs<(NCH > 0 ? NCH : 1), TR::full_rows>(st, f.S, lane, s_sx, s_sy, s_sz, tc, ac, 0, -1, 0.0);
+        if constexpr (FX) load_obs_pack<(NCH > 0 ? NCH : 1), F32>(ob, pack_, e_, lane);
+        else if constexpr (TR::full_rows) load_obs_regs_nobranch<(NCH > 0 ? NCH : 1), F32, false, false, true>(ob, f, e_, lane);
+        else load_obs_regs<(NCH > 0 ? NCH : 1), F32>(ob, f, e_, lane);      // in flight while the proposal is worked out
+    };
+    if (partial) {
+        if constexpr (NCH > 0) load_inputs(ev);
     }
     // the book of this chain: is this step's order out already, and how
     const int book_pos = tp.book_pos, book_mode = tp.book_mode, book_mid = tp.book_mid;
@@ -614,9 +663,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
             const int vzd = opaque_zero();
             const double *hypd = xall_ + off_hy + c * nh + 3 * d_e;
             d_ex = ld_state(hypd, vzd); d_ey = ld_state(hypd + 1, vzd); d_ez = ld_state(hypd + 2, vzd);
-            load_sta_regs<NCH, TR::full_rows>(st, f.S, lane, s_sx, s_sy, s_sz, tc, ac, 0, -1, 0.0);
-            if constexpr (TR::full_rows) load_obs_regs_nobranch<NCH, F32, false, false, true>(ob, f, d_e, lane);
-            else load_obs_regs<NCH, F32>(ob, f, d_e, lane);
+            load_inputs(d_e);
         }
     }
     FSTAMP(0);
@@ -1239,10 +1286,17 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
             }
         }
         if (mode) {
-            const int jgoff = jt == 1 ? 0 : jt == 2 ? nc_ : jt == 3 ? nc_ + nc_ * S_ : 2 * nc_ + nc_ * S_;
-            const int jo = jgoff + c * ((jt == 1 || jt == 3) ? 1 : S_) + ji;
+            int jgoff, jgnx;
+            if constexpr (FX) {      // (as goff / gnx of the step's front; jt is 1..4 here)
+                jgoff = (jt >> 1) * nc_ + ((((jt - 1) >> 1) * nc_) << LS);
+                jgnx = (((jt & 1) ^ 1) << LS) | (jt & 1);
+            } else {
+                jgoff = jt == 1 ? 0 : jt == 2 ? nc_ : jt == 3 ? nc_ + nc_ * S_ : 2 * nc_ + nc_ * S_;
+                jgnx = (jt == 1 || jt == 3) ? 1 : S_;
+            }
+            const int jo = jgoff + c * jgnx + ji;
             const double jx_old = rg.mx[jo];                                  // LDS mirror, kept current by this wave's commits
-            const int jop = cs.prior_same ? jo - c * ((jt == 1 || jt == 3) ? 1 : S_) : jo;
+            const int jop = (FX ? psame_ : cs.prior_same) ? jo - c * jgnx : jo;
             const double jstep = (TR::mirror || rg.mir_steps) ? rg.mstep[jo] : ld_const(&cs.prior[jop].step);
             const double jx_new = jx_old + rg.pg[pj & M] * jstep;             // cls_model.f90:172, as the step will compute it
             if (cs.rayleigh14) {                                              // a Rayleigh prior among vs/qs/corrections (:178-187)
@@ -1389,6 +1443,14 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
     W.epoch = 0; W.akey = 0; W.rc = 0; W.rpos = 0;
     W.rc1 = 0; W.rpos1 = flow_next_base<MB, TR::one_rank>(cs, sh, rg, 0, nc, sh.fill);
     W.B2 = flow_next_base<MB, TR::one_rank>(cs, sh, rg, W.rpos1, nc, sh.fill);
+    FlowSta fs = {0.0, 0.0, 0.0, 0, 0, 0, 0, 0};
+    if constexpr (flow_fixed_v<TR>) {
+        fs.m_hyp = (lane >= 1 && lane <= 3) ? -1 : 0; fs.m_sc = (lane == 4 || lane == 5) ? -1 : 0; fs.m_el = ~(fs.m_hyp | fs.m_sc);
+        fs.d_hyp = lane - 1; fs.m_qs = lane == 5 ? -1 : 0;
+        asm volatile("" : "+v"(fs.m_el), "+v"(fs.m_hyp), "+v"(fs.m_sc), "+v"(fs.d_hyp), "+v"(fs.m_qs));      // (kept as values, not re-derived from compares)
+    }
+    // (one station per lane: 6 registers of 256, the kernel has no vector spills and no scratch; two stations per lane keep the LDS reads)
+    if constexpr (flow_fixed_v<TR> && NCH == 1) { fs.x = s_sx[lane]; fs.y = s_sy[lane]; fs.z = s_sz[lane]; }
     FlowNext nx;
     nx.p = -1; nx.it = 0; nx.c = 0; nx.epoch = 0; nx.type = 5; nx.idx = 0; nx.evt = 1; nx.dec_w = 6; nx.g = 0.0; nx.r = 0.0; nx.logr = 0.0; nx.b3 = -1;
     int iter = i0 + 1;
@@ -1418,6 +1480,7 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
             tp.pv_mid = sh.pv_mid[c];
             tp.L = sh.L[c];
             tp.rbeta = sh.rbeta[c]; tp.katt = sh.katt[c];
+            if constexpr (flow_fixed_v<TR>) { tp.n_lik = lds_ld(&sh.c.n_lik); tp.n_smp = lds_ld(&sh.c.n_smp); tp.avail = lds_ld(&sh.avail); }
             asm volatile("" ::: "memory");
         }
         {
@@ -1465,6 +1528,10 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
                     st_agent(&g_mb->word[MW_STOP], (unsigned long long)(unsigned)code);
                     st_agent(&g_mb->word[MW_LAST], (unsigned long long)(unsigned)iter);
                 }
+            } else if constexpr (flow_fixed_v<TR>) {      // (read with the batch at the top)
+                if (tp.n_lik + 3 * nc > cs.cap_lik || tp.n_smp + 3 * nc > cs.cap_smp) code = 1;
+                else if (tp.avail < p + 3 * wd + 32) code = 2;
+                if (code && lds_ld(&sh.last_iter) > iter) { sh.stop_code = code; lds_st(&sh.last_iter, iter); }
             } else {
             if (sh.c.n_lik + 3 * nc > cs.cap_lik || sh.c.n_smp + 3 * nc > cs.cap_smp) code = 1;
             else if (sh.avail < p + 3 * wd + 32) code = 2;
@@ -1500,7 +1567,7 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
         // (several master workgroups: a wave has one chain -- "wave" c of as many waves as there are chains)
         if constexpr (MB) MB_HIST(mw, (known ? 4 : 0) | (W.epoch & 3));
         const int r = flow_step<NCH, F32, LOCK, MB, TR>(f, cs, sh, rg, W, nx, g_mb, mw, s_gath, wmax, s_sx, s_sy, s_sz, c, p, iter, lane, MB ? c : wave,
-                                              MB ? 64 : NW, launch, wave == 0, look, back, rec_phase == 1, tp);
+                                              MB ? 64 : NW, launch, wave == 0, look, back, rec_phase == 1, tp, fs);
         if (r == kFlowRestart) continue;
         if (r == kFlowAbort || r == kFlowStop) break;
         // ---- this wave's next step

@@ -143,6 +143,10 @@ struct htm_forward {
     double *d_bpartial = nullptr; size_t bpartial_cap = 0;
     double *d_bmodels = nullptr;  size_t bmodels_cap = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_wd = nullptr;
+    // packed per-event records of the specialised chain master (FwdDev::obs_pack), fp64 and fp32 forward: built when a chain set
+    // that can run that master is created on this forward (ensure_obs_pack), and for the other precision when it is switched to
+    void *d_pack64 = nullptr, *d_pack32 = nullptr;
+    bool pack_wanted = false;
 };
 
 struct htm_chains {
@@ -300,6 +304,7 @@ int launch_mcmc(htm_chains *hc, int mode, int target, const double *gathered)
         else HTM_LAUNCH_MCMC(2, false, 7);
     }
     else if (mode == MODE_RUN && flow_fixed_ok(hc)) {      // (one or two stations per lane: flow_fixed)
+        if (!h->dev.obs_pack) return fail(HTM_EINVAL, "the specialised chain master needs the forward's packed records");
         hc->last_fixed = true;
         if (h->dev.fp32) { if (h->nch == 1) HTM_LAUNCH_MCMC(1, true, 8); else HTM_LAUNCH_MCMC(2, true, 8); }
         else if (h->nch == 1) HTM_LAUNCH_MCMC(1, false, 8);
@@ -549,12 +554,56 @@ int htm_forward_destroy(htm_forward *h)
     return HTM_OK;
 }
 
+// The packed records (FwdDev::obs_pack, htm_device.hpp) for the precision in use, from the device's own rows -- the same bits
+// the row loads return.  The observations never change after htm_forward_create, so neither do the records.  They repeat the
+// four streams: 2 MB more at 1000 events x 64 stations in fp64, 41 MB at 10 000 x 128 -- only for a forward
+// whose chain set can run the specialised master (htm_chains_create asks for them).
+static int ensure_obs_pack(htm_forward *h)
+{
+    if (!h->pack_wanted) { h->dev.obs_pack = nullptr; return HTM_OK; }
+    const bool f32 = h->dev.fp32 != 0;
+    void *&slot = f32 ? h->d_pack32 : h->d_pack64;
+    if (!slot) {
+        if ((h->nch != 1 && h->nch != 2) || h->S != 64 * h->nch) return fail(HTM_EINVAL, "packed records need full rows of 64 or 128 stations");
+        const size_t S = (size_t)h->S, E = (size_t)h->E, n = S * E, es = f32 ? sizeof(float) : sizeof(double);
+        const size_t stride = obs_pack_stride(h->nch, f32);
+        const void *src[4] = {f32 ? (const void *)h->dev.t_obs32 : (const void *)h->dev.t_obs, f32 ? (const void *)h->dev.t_prec32 : (const void *)h->dev.t_prec,
+                              f32 ? (const void *)h->dev.a_obs32 : (const void *)h->dev.a_obs, f32 ? (const void *)h->dev.a_prec32 : (const void *)h->dev.a_prec};
+        std::vector<char> rows(n * es), buf(stride * E, 0);
+        for (int k = 0; k < 4; ++k) {
+            HIPCHK(hipMemcpy(rows.data(), src[k], n * es, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < E; ++i) std::memcpy(buf.data() + i * stride + (size_t)k * S * es, rows.data() + i * S * es, S * es);
+        }
+        std::vector<double> rt(E), ra(E);
+        HIPCHK(hipMemcpy(rt.data(), h->dev.rpsum_t, E * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(ra.data(), h->dev.rpsum_a, E * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < E; ++i) {
+            std::memcpy(buf.data() + i * stride + 4 * S * es, &rt[i], sizeof(double));
+            std::memcpy(buf.data() + i * stride + 4 * S * es + sizeof(double), &ra[i], sizeof(double));
+        }
+        char *p = nullptr;
+        int rc = dev_upload(h->pool, &p, buf.data(), buf.size());
+        if (rc) return rc;
+        slot = p;
+    }
+    h->dev.obs_pack = slot;
+    return HTM_OK;
+}
+
+int htm_forward_obs_pack_bytes(htm_forward *h, int64_t *bytes)
+{
+    if (!h || !bytes) return fail(HTM_EINVAL, "NULL argument");
+    *bytes = (h->d_pack64 ? (int64_t)(obs_pack_stride(h->nch, false) * (size_t)h->E) : 0) +
+             (h->d_pack32 ? (int64_t)(obs_pack_stride(h->nch, true) * (size_t)h->E) : 0);
+    return HTM_OK;
+}
+
 int htm_forward_set_precision(htm_forward *h, int forward_fp32)
 {
     if (!h) return fail(HTM_EINVAL, "NULL handle");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (!forward_fp32) { h->dev.fp32 = 0; return HTM_OK; }
+    if (!forward_fp32) { h->dev.fp32 = 0; return ensure_obs_pack(h); }
     if (h->nch != 1 && h->nch != 2) return fail(HTM_EINVAL, "the fp32 forward covers n_sta <= 128 (this handle has %d stations)", h->S);
     if (!h->dev.t_obs32) {
         // the four observation streams once more as float: the bytes a full evaluation reads are halved
@@ -573,7 +622,7 @@ int htm_forward_set_precision(htm_forward *h, int forward_fp32)
         }
     }
     h->dev.fp32 = 1;
-    return HTM_OK;
+    return ensure_obs_pack(h);
 }
 
 int htm_forward_set_stream(htm_forward *h, void *hip_stream)
@@ -1096,6 +1145,11 @@ int htm_chains_create(htm_forward *h, const htm_chains_init *init, htm_chains **
             const char *ef = getenv("HTM_FAST");
             hc->flow_fixed = hc->flow && !(ef && ef[0] == '0') && nc <= 8 && (h->nch == 1 || h->nch == 2) && h->S == 64 * h->nch &&
                              h->dev.use_time != 0 && h->dev.use_amp != 0 && hc->dev.mirror_n == (int)mir && hc->dev.mirror_steps != 0;
+            // (its steps read an event's observations from one packed record: built here, once per forward and precision)
+            if (hc->flow_fixed) {
+                h->pack_wanted = true;
+                if ((rc = ensure_obs_pack(h))) return cleanup(rc);
+            }
         }
         // More than eight chains on a rank: a master workgroup for every eight (k_mcmc<.., 7>, htm_flow.hpp MbShared) instead of
         // rounds on the same eight waves.

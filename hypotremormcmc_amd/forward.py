@@ -72,6 +72,12 @@ class Forward:
         check(self._lib.htm_forward_set_precision(self.handle, int(fp32)))
         self.forward_precision = "fp32" if fp32 else "fp64"
 
+    def obs_pack_bytes(self) -> int:
+        """Bytes of the packed per-event observation records (the specialised chain master's; 0: none were built)."""
+        n = C.c_int64(0)
+        check(self._lib.htm_forward_obs_pack_bytes(self.handle, C.byref(n)))
+        return int(n.value)
+
     def set_stream(self, hip_stream: int):
         """Use the caller's HIP stream (0 = the default stream, e.g. torch.cuda.current_stream().cuda_stream)."""
         check(self._lib.htm_forward_set_stream(self.handle, C.c_void_p(int(hip_stream))))

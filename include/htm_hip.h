@@ -73,6 +73,10 @@ int htm_forward_destroy(htm_forward *h);
  * decision (src/cls_mcmc.f90:194-199) stay fp64.  n_sta <= 128.  Call before htm_chains_create. */
 int htm_forward_set_precision(htm_forward *h, int forward_fp32);
 
+/* Bytes of the packed per-event observation records this handle holds: built when a chain set that can run
+ * the specialised chain master is created on the handle, one copy per forward precision used since; 0 otherwise. */
+int htm_forward_obs_pack_bytes(htm_forward *h, int64_t *bytes);
+
 /* Run all work of this handle (and of chain sets created from it) on the caller's HIP stream, e.g.
  * torch's current stream so that RCCL collectives enqueued by torch.distributed order with our kernels.
  * hip_stream is used as given: NULL is HIP's default (null) stream -- which is what torch's default
