@@ -1343,7 +1343,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
     return p + cnt;
 }
 
-// block 0 of a k_mcmc<NCH, F32, 0> launch when the host selects the free-running master (htm_hip.hip: flow_ok)
+// block 0 of a k_mcmc<NCH, F32, 0> launch when the host selects the free-running master (htm_hip.hip: hc->flow)
 // (MB: one of several master workgroups of the launch -- block b runs chains 8 b .. 8 b + 7; returns true in the workgroup that
 // finishes last, which has written the launch's end state and releases the workers)
 template <int NCH, bool F32, bool LOCK = false, bool MB = false, class TR = FlowGeneric>
@@ -1709,23 +1709,6 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
     for (int k = tid; k < nc; k += blockDim.x) cs.prev_mid[k] = sh.pv_mid[k];
     if (tid == 0) *cs.ctrl = sh.c;
     return true;
-}
-
-// before a launch with several master workgroups (one wave): MbShared as the first step finds it
-__global__ __launch_bounds__(64) void k_mb_init(ChainsDev cs, int target_arg)
-{
-    MbShared *g = cs.mb;
-    const int lane = threadIdx.x;
-    unsigned long long *w = reinterpret_cast<unsigned long long *>(g);
-    for (int k = lane; k < (int)(sizeof(MbShared) / sizeof(unsigned long long)); k += 64) w[k] = 0ull;
-    __syncthreads();
-    for (int c = lane; c < kMaxChains; c += 64) g->prog[c] = (unsigned long long)(unsigned)c;          // key(i0, c), epoch 0, prior ok
-    if (lane == 0) {
-        const Ctrl c = *cs.ctrl;
-        g->word[MW_LAST] = (unsigned long long)(unsigned)(target_arg >= 0 ? target_arg : c.iter_target);
-        g->word[MW_NLIK] = (unsigned long long)(unsigned)c.n_lik; g->word[MW_NSMP] = (unsigned long long)(unsigned)c.n_smp;
-        g->word[7] = c.jobs_total;
-    }
 }
 
 }  // namespace htm

@@ -1,246 +1,48 @@
-// htm_hip.hip -- C ABI (include/htm_hip.h) over the gfx950 kernels in htm_kernels.hpp.
-//
-// Host code is plain C++17 + the HIP runtime: no torch, no third-party dependency.  There is no CPU
-// fallback on purpose: every entry point needs a usable HIP device and fails with HTM_ENODEVICE otherwise.
-#include "htm_hip.h"
+// htm_hip.hip -- the chain sets' part of the C ABI (include/htm_hip.h): htm_chains_* and htm_comm_*.  (The forward model's part
+// is htm_forward.hip, the other steps' htm_steps.hip; this file keeps its name because most of it stayed where it was.)  Decides which chain-master
+// loop a launch takes (launch_mcmc) and looks its kernel up in the table of htm_host.hpp; the instantiations themselves are
+// compiled by the loop units (htm_loop_*.hip), none here.  This unit owns the small kernels of htm_chains_kernels.hpp.
+#include "htm_host.hpp"
+#include "htm_chains_kernels.hpp"
+#include "htm_pipe.hpp"
 
-#include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
-#include <algorithm>
-#include <array>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
 #include <chrono>
 #include <climits>
-#include <cstring>
+#include <cmath>
+#include <cstdarg>
 #include <map>
 #include <memory>
 #include <mutex>
-#include <thread>
 #include <string>
-#include <vector>
-
-#include "htm_convert.hpp"
-#include "htm_diag.hpp"
-#include "htm_kernels.hpp"
-#include "htm_pipe.hpp"
-#include "htm_select.hpp"
-#include "htm_xcorr.hpp"
+#include <thread>
 
 using namespace htm;
 
-namespace {
+namespace htm {
 
-thread_local std::string g_err;
-
-int fail(int code, const char *fmt, ...)
+// ---- the kernel table's two lookups (htm_host.hpp): the rows of every loop unit -------------------------------------------
+// Three or more stations per lane run the instantiation for any station count (<0, ..>), as they always have; the fp32
+// forward and the masters of htm_flow.hpp / htm_pipe.hpp other than MK 3 and 4 exist for one or two stations per lane only.
+static const LoopKernel *find_row(bool step, bool wide, int nch, bool fp32, int mk)
 {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define HIPCHK(call)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess)                                                                          \
-            return fail(HTM_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__,     \
-                        __LINE__);                                                                     \
-    } while (0)
-
-int use_device(int device)
-{
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0)
-        return fail(HTM_ENODEVICE, "no HIP device available (%s); libhtm_hip has no CPU fallback",
-                    e == hipSuccess ? "device count 0" : hipGetErrorString(e));
-    if (device < 0 || device >= n) return fail(HTM_EINVAL, "device %d out of range (0..%d)", device, n - 1);
-    HIPCHK(hipSetDevice(device));
-    return HTM_OK;
-}
-
-template <typename T>
-int dev_alloc(std::vector<void *> &pool, T **p, size_t n)
-{
-    void *q = nullptr;
-    HIPCHK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
-    pool.push_back(q);
-    *p = static_cast<T *>(q);
-    return HTM_OK;
-}
-
-template <typename T>
-int dev_upload(std::vector<void *> &pool, T **p, const T *src, size_t n)
-{
-    int rc = dev_alloc(pool, p, n);
-    if (rc) return rc;
-    if (n) HIPCHK(hipMemcpy(*p, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return HTM_OK;
-}
-
-int nch_for(int S) { return S <= 64 ? 1 : S <= 128 ? 2 : S <= 256 ? 4 : 0; }
-
-// ---- GF(2) algebra of mod_random's xorshift128 (reference src/mod_random.f90:63-71) ----------------------------
-// One step is linear in the 128 state bits (x | y << 32 | z << 64 | w << 96): state' = T * state.  Powers of T let
-// the device start any 64-draw segment of the stream directly (htm_stream.hpp, k_rawgen) and the host jump over any
-// number of draws (htm_rng_jump).  A matrix is stored as its 128 columns.
-struct Bits128 { uint32_t w[4]; };
-using Mat128 = std::array<Bits128, 128>;
-
-Bits128 xs_step(Bits128 s)
-{
-    const uint32_t t = s.w[0] ^ (s.w[0] << 11);
-    Bits128 r;
-    r.w[0] = s.w[1]; r.w[1] = s.w[2]; r.w[2] = s.w[3];
-    r.w[3] = (s.w[3] ^ (s.w[3] >> 19)) ^ (t ^ (t >> 8));
-    return r;
-}
-Bits128 gf2_matvec(const Mat128 &M, const Bits128 &v)
-{
-    Bits128 a{{0, 0, 0, 0}};
-    for (int j = 0; j < 128; ++j)
-        if ((v.w[j >> 5] >> (j & 31)) & 1u)
-            for (int k = 0; k < 4; ++k) a.w[k] ^= M[j].w[k];
-    return a;
-}
-// P[k] = T^(2^k), k = 0..63
-const std::vector<Mat128> &xs_powers()
-{
-    static const std::vector<Mat128> P = [] {
-        std::vector<Mat128> p(64);
-        for (int j = 0; j < 128; ++j) {
-            Bits128 e{{0, 0, 0, 0}};
-            e.w[j >> 5] = 1u << (j & 31);
-            p[0][j] = xs_step(e);
+    const int n = (nch == 1 || nch == 2) ? nch : 0;
+    const LoopRows units[] = {loop_rows_free(), loop_rows_lock(), loop_rows_barrier(), loop_rows_wide(), loop_rows_pipe()};
+    for (const LoopRows &u : units)
+        for (size_t k = 0; k < u.n; ++k) {
+            const LoopRow &r = u.rows[k];
+            if (r.step == step && r.wide == wide && r.nch == n && r.fp32 == fp32 && r.mk == mk) return &r.k;
         }
-        for (int k = 1; k < 64; ++k)
-            for (int j = 0; j < 128; ++j) p[k][j] = gf2_matvec(p[k - 1], p[k - 1][j]);
-        return p;
-    }();
-    return P;
+    return nullptr;
 }
+const LoopKernel *mcmc_kernel(int nch, bool fp32, int mk, bool wide) { return find_row(false, wide, nch, fp32, mk); }
+const LoopKernel *step_kernel(int nch, bool fp32, bool wide) { return find_row(true, wide, nch, fp32, 0); }
 
-}  // namespace
-
-struct htm_forward {
-    int device = 0, S = 0, E = 0, nch = 1;
-    hipStream_t own_stream = nullptr, stream = nullptr;
-    FwdDev dev{};
-    std::vector<void *> pool;
-    int n_wg = 0, epw = 1;
-    // scratch for the host-pointer entry points (one model)
-    double *d_hypo = nullptr, *d_tc = nullptr, *d_ac = nullptr, *d_scal = nullptr, *d_partial = nullptr;
-    double *d_syn = nullptr;
-    // scratch for batches
-    double *d_bpartial = nullptr; size_t bpartial_cap = 0;
-    double *d_bmodels = nullptr;  size_t bmodels_cap = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_wd = nullptr;
-    // packed per-event records of the specialised chain master (FwdDev::obs_pack), fp64 and fp32 forward: built when a chain set
-    // that can run that master is created on this forward (ensure_obs_pack), and for the other precision when it is switched to
-    void *d_pack64 = nullptr, *d_pack32 = nullptr;
-    bool pack_wanted = false;
-};
-
-struct htm_chains {
-    htm_forward *fwd = nullptr;
-    ChainsDev dev{};
-    Ctrl h_ctrl{};
-    std::vector<void *> pool;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t gexec = nullptr;
-    int pairs = 32;
-    int nw = 1;                // chain waves of k_step (one more wave is the RNG producer)
-    int ring_size = 512, wmax = 64;
-    size_t step_smem = 0;
-    int h_target = 0;          // host copy of the iteration target
-    int rec_len = 0;
-    std::vector<int32_t> lik_iter, lik_chain, smp_iter, smp_chain;
-    std::vector<double> lik_val, smp_data;
-    double last_device_us = 0.0;
-    int last_graph_launches = 0;
-    long long run_full0 = 0, run_part0 = 0, last_full = 0, last_part = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_wd = nullptr;
-    // random-stream service (htm_stream.hpp): produced on a side stream ahead of consumption
-    hipStream_t side = nullptr;
-    hipEvent_t ev_side = nullptr;
-    long long cap = 0;                         // ring capacity (positions)
-    long long n_raw = 0, n_tr = 0, n_rec = 0, n_hop = 0;   // positions produced per stage (host view)
-    long long spos_lo = 0, spos_hi = 0;        // bounds on the consumed position since the last sync
-    const double *pending_gathered = nullptr;  // lock-step: records whose swap the next k_step applies
-    double *d_gath_host = nullptr, *h_gath_pinned = nullptr;   // staging buffers of htm_chains_step_end_host
-    unsigned long long launch_seq = 0;         // k_mcmc launches of this chain set so far (the kernels' launch index)
-    bool persist = true;                       // k_mcmc (master + resident full-evaluation workers) vs k_step + k_full
-    bool flow = false;                         // single-rank loop on the free-running master (htm_flow.hpp) instead of step_body
-    bool flow_fixed = false;                   // ... and the job's shape allows its specialised instantiation (k_mcmc<.., 8>; flow_fixed_ok decides per launch)
-    bool last_fixed = false;                   // the latest MODE_RUN launch was that instantiation
-    bool wide = false;                         // more than kMaxChains chains: the loop with barriers at kMaxWideChains (k_mcmc_wide, k_step_wide)
-    int worker_cap = 250;                      // most worker blocks a launch takes (HTM_WORKER_CAP)
-    long blocks_fit = 0;                       // resident blocks of a k_mcmc launch on this device (htm_chains_share_gpu)
-    bool flow_lock = false;                    // lock-step ranks (MODE_LOCKRUN) on the free-running master too
-    int mb_blocks = 1;                         // master workgroups of the single-rank loop (> 1: k_mcmc<.., 7>, eight chains each)
-    bool pipe = false;                         // single-rank loop on the pipelined master (htm_pipe.hpp)
-    bool pipe_lock = false;                    // lock-step ranks (MODE_LOCKRUN) on it too
-    size_t pipe_smem = 0; int pipe_ring = 512; // its LDS size and stream window
-    bool ctrl_fresh = false;                   // h_ctrl is the device's control block as of an idle stream (no launch since it was read)
-    ChainsDev dev_np{};                        // view for the non-persistent kernels (partial sums per k_full tile)
-    uint32_t init_state[4] = {0, 0, 0, 0};     // mod_random state at stream position 0
-    // in-kernel exchange of the swap records (persistent lock-step): this rank's inbox, the peers' inboxes as mapped here
-    unsigned long long *d_inbox = nullptr;
-    size_t inbox_bytes = 0;
-    std::vector<void *> peer_maps;             // hipIpcOpenMemHandle mappings to close
-    unsigned probe_calls = 0;                  // htm_chains_xchg_probe calls so far (part of the probe's tokens)
-    unsigned long long **d_outbox = nullptr;
-    bool xchg_ready = false;
-    u32x4 *d_jump = nullptr;                   // [kJumpLevels][128] columns of T^(64 * 2^b) (k_rawgen)
-    int gen_par = 0;                           // which half of StreamDev::gen holds the current generator state
-    double th[4] = {0, 0, 0, 0};
-};
-
-namespace {
-
-int launch_full(htm_forward *h, const FullJob &jb, int gy)
+static int no_kernel(const htm_chains *hc, const char *what, int mk)
 {
-    dim3 grid(h->n_wg, gy), block(256);
-    const size_t smem = 0;
-    if (h->dev.fp32 && (h->nch == 1 || h->nch == 2 || h->nch == 4)) {        // fp32 forward (htm_forward_set_precision)
-        if (jb.desc) {
-            switch (h->nch) {
-            case 1: hipLaunchKernelGGL((k_full<1, false, true>), grid, block, smem, h->stream, h->dev, jb); break;
-            case 2: hipLaunchKernelGGL((k_full<2, false, true>), grid, block, smem, h->stream, h->dev, jb); break;
-            default: hipLaunchKernelGGL((k_full<4, false, true>), grid, block, smem, h->stream, h->dev, jb); break;
-            }
-        } else {
-            switch (h->nch) {
-            case 1: hipLaunchKernelGGL((k_full<1, true, true>), grid, block, smem, h->stream, h->dev, jb); break;
-            case 2: hipLaunchKernelGGL((k_full<2, true, true>), grid, block, smem, h->stream, h->dev, jb); break;
-            default: hipLaunchKernelGGL((k_full<4, true, true>), grid, block, smem, h->stream, h->dev, jb); break;
-            }
-        }
-    } else if (jb.desc) {
-        switch (h->nch) {
-        case 1: hipLaunchKernelGGL((k_full<1, false>), grid, block, smem, h->stream, h->dev, jb); break;
-        case 2: hipLaunchKernelGGL((k_full<2, false>), grid, block, smem, h->stream, h->dev, jb); break;
-        case 4: hipLaunchKernelGGL((k_full<4, false>), grid, block, smem, h->stream, h->dev, jb); break;
-        default: hipLaunchKernelGGL((k_full<0, false>), grid, block, smem, h->stream, h->dev, jb); break;
-        }
-    } else {
-        switch (h->nch) {
-        case 1: hipLaunchKernelGGL((k_full<1, true>), grid, block, smem, h->stream, h->dev, jb); break;
-        case 2: hipLaunchKernelGGL((k_full<2, true>), grid, block, smem, h->stream, h->dev, jb); break;
-        case 4: hipLaunchKernelGGL((k_full<4, true>), grid, block, smem, h->stream, h->dev, jb); break;
-        default: hipLaunchKernelGGL((k_full<0, true>), grid, block, smem, h->stream, h->dev, jb); break;
-        }
-    }
-    HIPCHK(hipGetLastError());
-    return HTM_OK;
+    return fail(HTM_EINVAL, "no %s kernel is built for %d stations with the %s forward%s (loop %d)", what, hc->fwd->S,
+                hc->fwd->dev.fp32 ? "fp32" : "fp64", hc->wide ? ", more than 32 chains" : "", mk);
 }
 
 // The free-running master specialised on what the job fixes (flow_body<.., FlowFixed>): what htm_chains_create found
@@ -254,69 +56,35 @@ int launch_mcmc(htm_chains *hc, int mode, int target, const double *gathered)
 {
     htm_forward *h = hc->fwd;
     const bool mb = mode == MODE_RUN && hc->flow && hc->mb_blocks > 1 && !hc->pipe;
-    dim3 grid((mb ? hc->mb_blocks : 1) + hc->dev.n_workers), block(512);
     hc->ctrl_fresh = false;
-    const unsigned long long seq = ++hc->launch_seq;      // this chain set's k_mcmc launches, counted from 1
-#define HTM_LAUNCH_MCMC(N, F, K) hipLaunchKernelGGL((k_mcmc<N, F, K>), grid, block, hc->step_smem, h->stream, h->dev, hc->dev, mode, target, gathered, hc->ring_size, hc->wmax, seq)
-#define HTM_LAUNCH_MCMC_K(K)                                                                              \
-    do {                                                                                                   \
-        if (h->dev.fp32) { if (h->nch == 1) HTM_LAUNCH_MCMC(1, true, K); else HTM_LAUNCH_MCMC(2, true, K); } \
-        else if (h->nch == 1) HTM_LAUNCH_MCMC(1, false, K);                                                \
-        else if (h->nch == 2) HTM_LAUNCH_MCMC(2, false, K);                                                \
-        else HTM_LAUNCH_MCMC(0, false, K);                                                                 \
-    } while (0)
-    // one instantiation per main loop: the single-rank loop, one lock-step iteration per launch, persistent lock-step
-    if (hc->wide) {
-#define HTM_LAUNCH_WIDE(N, F, K) hipLaunchKernelGGL((k_mcmc_wide<N, F, K>), grid, block, hc->step_smem, h->stream, h->dev, hc->dev, mode, target, gathered, hc->ring_size, hc->wmax, seq)
-#define HTM_LAUNCH_WIDE_K(K)                                                                              \
-    do {                                                                                                   \
-        if (h->dev.fp32) { if (h->nch == 1) HTM_LAUNCH_WIDE(1, true, K); else HTM_LAUNCH_WIDE(2, true, K); } \
-        else if (h->nch == 1) HTM_LAUNCH_WIDE(1, false, K);                                                \
-        else if (h->nch == 2) HTM_LAUNCH_WIDE(2, false, K);                                                \
-        else HTM_LAUNCH_WIDE(0, false, K);                                                                 \
-    } while (0)
-        if (mode == MODE_RUN) HTM_LAUNCH_WIDE_K(0);
-        else if (mode == MODE_LOCKRUN) HTM_LAUNCH_WIDE_K(2);
-        else HTM_LAUNCH_WIDE_K(1);
-#undef HTM_LAUNCH_WIDE_K
-#undef HTM_LAUNCH_WIDE
-    }
-    else if (mode == MODE_RUN && hc->pipe) {
-        // the pipelined master (htm_pipe.hpp): one or two stations per lane only
-#define HTM_LAUNCH_PIPE(N, F) hipLaunchKernelGGL((k_mcmc<N, F, 5>), grid, dim3(mcmc_threads<N, 5>()), hc->pipe_smem, h->stream, h->dev, hc->dev, mode, target, gathered, hc->pipe_ring, hc->wmax, seq)
-        if (h->dev.fp32) { if (h->nch == 1) HTM_LAUNCH_PIPE(1, true); else HTM_LAUNCH_PIPE(2, true); }
-        else if (h->nch == 1) HTM_LAUNCH_PIPE(1, false);
-        else HTM_LAUNCH_PIPE(2, false);
-#undef HTM_LAUNCH_PIPE
-    }
-    else if (mode == MODE_LOCKRUN && hc->pipe_lock) {
-#define HTM_LAUNCH_PIPE(N, F) hipLaunchKernelGGL((k_mcmc<N, F, 6>), grid, dim3(mcmc_threads<N, 6>()), hc->pipe_smem, h->stream, h->dev, hc->dev, mode, target, gathered, hc->pipe_ring, hc->wmax, seq)
-        if (h->dev.fp32) { if (h->nch == 1) HTM_LAUNCH_PIPE(1, true); else HTM_LAUNCH_PIPE(2, true); }
-        else if (h->nch == 1) HTM_LAUNCH_PIPE(1, false);
-        else HTM_LAUNCH_PIPE(2, false);
-#undef HTM_LAUNCH_PIPE
-    }
-    else if (mb) {
-        // several master workgroups: what their chains share lives in memory (MbShared), set up by a one-wave kernel first
-        hipLaunchKernelGGL(k_mb_init, dim3(1), dim3(64), 0, h->stream, hc->dev, target);
-        if (h->dev.fp32) { if (h->nch == 1) HTM_LAUNCH_MCMC(1, true, 7); else HTM_LAUNCH_MCMC(2, true, 7); }
-        else if (h->nch == 1) HTM_LAUNCH_MCMC(1, false, 7);
-        else HTM_LAUNCH_MCMC(2, false, 7);
-    }
+    LoopLaunch l{};
+    l.grid = dim3((mb ? hc->mb_blocks : 1) + hc->dev.n_workers);
+    l.smem = hc->step_smem; l.stream = h->stream; l.f = &h->dev; l.cs = &hc->dev;
+    l.mode = mode; l.target = target; l.gathered = gathered; l.ring_size = hc->ring_size; l.wmax = hc->wmax;
+    l.seq = ++hc->launch_seq;      // this chain set's k_mcmc launches, counted from 1
+    // one instantiation per main loop (MK, htm_pipe.hpp k_mcmc): the single-rank loop, one lock-step iteration per launch, persistent lock-step
+    int mk;
+    if (hc->wide) mk = mode == MODE_RUN ? 0 : mode == MODE_LOCKRUN ? 2 : 1;
+    else if (mode == MODE_RUN && hc->pipe) mk = 5;      // the pipelined master (htm_pipe.hpp): one or two stations per lane only
+    else if (mode == MODE_LOCKRUN && hc->pipe_lock) mk = 6;
+    else if (mb) mk = 7;
     else if (mode == MODE_RUN && flow_fixed_ok(hc)) {      // (one or two stations per lane: flow_fixed)
         if (!h->dev.obs_pack) return fail(HTM_EINVAL, "the specialised chain master needs the forward's packed records");
         hc->last_fixed = true;
-        if (h->dev.fp32) { if (h->nch == 1) HTM_LAUNCH_MCMC(1, true, 8); else HTM_LAUNCH_MCMC(2, true, 8); }
-        else if (h->nch == 1) HTM_LAUNCH_MCMC(1, false, 8);
-        else HTM_LAUNCH_MCMC(2, false, 8);
+        mk = 8;
     }
-    else if (mode == MODE_RUN && hc->flow) { hc->last_fixed = false; HTM_LAUNCH_MCMC_K(3); }
-    else if (mode == MODE_RUN) HTM_LAUNCH_MCMC_K(0);
-    else if (mode == MODE_LOCKRUN && hc->flow_lock) HTM_LAUNCH_MCMC_K(4);
-    else if (mode == MODE_LOCKRUN) HTM_LAUNCH_MCMC_K(2);
-    else HTM_LAUNCH_MCMC_K(1);
-#undef HTM_LAUNCH_MCMC_K
-#undef HTM_LAUNCH_MCMC
+    else if (mode == MODE_RUN && hc->flow) { hc->last_fixed = false; mk = 3; }
+    else if (mode == MODE_RUN) mk = 0;
+    else if (mode == MODE_LOCKRUN && hc->flow_lock) mk = 4;
+    else if (mode == MODE_LOCKRUN) mk = 2;
+    else mk = 1;
+    if (mk == 5 || mk == 6) { l.smem = hc->pipe_smem; l.ring_size = hc->pipe_ring; }      // (its own LDS layout and stream window)
+    const LoopKernel *k = mcmc_kernel(h->nch, h->dev.fp32 != 0, mk, hc->wide);
+    if (!k) return no_kernel(hc, "k_mcmc", mk);
+    // several master workgroups: what their chains share lives in memory (MbShared), set up by a one-wave kernel first
+    if (mk == 7) hipLaunchKernelGGL(k_mb_init, dim3(1), dim3(64), 0, h->stream, hc->dev, target);
+    l.block = dim3(k->threads);
+    k->launch(l);
     HIPCHK(hipGetLastError());
     return HTM_OK;
 }
@@ -325,32 +93,19 @@ int launch_step(htm_chains *hc, int mode, int target, const double *gathered)
 {
     htm_forward *h = hc->fwd;
     hc->ctrl_fresh = false;
-    dim3 grid(1), block(64 * hc->nw);
-    if (hc->wide) {
-        const size_t sm = hc->step_smem;
-        if (h->dev.fp32) {
-            if (h->nch == 1) hipLaunchKernelGGL((k_step_wide<1, true>), grid, block, sm, h->stream, h->dev, hc->dev_np, mode, target, gathered, hc->ring_size, hc->wmax);
-            else hipLaunchKernelGGL((k_step_wide<2, true>), grid, block, sm, h->stream, h->dev, hc->dev_np, mode, target, gathered, hc->ring_size, hc->wmax);
-        } else if (h->nch == 1) hipLaunchKernelGGL(k_step_wide<1>, grid, block, sm, h->stream, h->dev, hc->dev_np, mode, target, gathered, hc->ring_size, hc->wmax);
-        else if (h->nch == 2) hipLaunchKernelGGL(k_step_wide<2>, grid, block, sm, h->stream, h->dev, hc->dev_np, mode, target, gathered, hc->ring_size, hc->wmax);
-        else hipLaunchKernelGGL(k_step_wide<0>, grid, block, sm, h->stream, h->dev, hc->dev_np, mode, target, gathered, hc->ring_size, hc->wmax);
-        HIPCHK(hipGetLastError());
-        return HTM_OK;
-    }
-    if (h->dev.fp32) {
-        if (h->nch == 1) hipLaunchKernelGGL((k_step<1, true>), grid, block, hc->step_smem, h->stream, h->dev, hc->dev_np, mode, target, gathered, hc->ring_size, hc->wmax);
-        else hipLaunchKernelGGL((k_step<2, true>), grid, block, hc->step_smem, h->stream, h->dev, hc->dev_np, mode, target, gathered, hc->ring_size, hc->wmax);
-        HIPCHK(hipGetLastError());
-        return HTM_OK;
-    }
-    switch (h->nch) {
-    case 1: hipLaunchKernelGGL(k_step<1>, grid, block, hc->step_smem, h->stream, h->dev, hc->dev_np, mode, target, gathered, hc->ring_size, hc->wmax); break;
-    case 2: hipLaunchKernelGGL(k_step<2>, grid, block, hc->step_smem, h->stream, h->dev, hc->dev_np, mode, target, gathered, hc->ring_size, hc->wmax); break;
-    default: hipLaunchKernelGGL(k_step<0>, grid, block, hc->step_smem, h->stream, h->dev, hc->dev_np, mode, target, gathered, hc->ring_size, hc->wmax); break;
-    }
+    const LoopKernel *k = step_kernel(h->nch, h->dev.fp32 != 0, hc->wide);
+    if (!k) return no_kernel(hc, "k_step", 0);
+    LoopLaunch l{};
+    l.grid = dim3(1); l.block = dim3(64 * hc->nw);
+    l.smem = hc->step_smem; l.stream = h->stream; l.f = &h->dev; l.cs = &hc->dev_np;
+    l.mode = mode; l.target = target; l.gathered = gathered; l.ring_size = hc->ring_size; l.wmax = hc->wmax;
+    k->launch(l);
     HIPCHK(hipGetLastError());
     return HTM_OK;
 }
+}  // namespace htm
+
+namespace {
 
 // Append n (multiple of 64) positions to the rank's random stream on the side stream.  Asynchronous; the
 // new coverage is published to the device (StreamDev::hop_end) by the last kernel of the sequence.
@@ -399,398 +154,10 @@ FullJob chain_full_job(htm_chains *hc)
     return jb;
 }
 
-int ensure_batch_scratch(htm_forward *h, int n_models)
-{
-    const size_t need = (size_t)n_models * h->n_wg;
-    if (need > h->bpartial_cap) {
-        if (h->d_bpartial) HIPCHK(hipFree(h->d_bpartial));
-        h->d_bpartial = nullptr;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&h->d_bpartial), need * sizeof(double)));
-        h->bpartial_cap = need;
-    }
-    return HTM_OK;
-}
-
-int full_batch_dev(htm_forward *h, int n_models, const double *d_hypo, const double *d_tc, const double *d_vs,
-                   const double *d_ac, const double *d_qs, double *d_L)
-{
-    int rc = ensure_batch_scratch(h, n_models);
-    if (rc) return rc;
-    FullJob jb{};
-    jb.hypo = d_hypo; jb.hypo_stride = 3L * h->E;
-    jb.tc = d_tc; jb.tc_stride = h->S;
-    jb.ac = d_ac; jb.ac_stride = h->S;
-    jb.vs = d_vs; jb.qs = d_qs;
-    jb.n_models = n_models;
-    jb.partial = h->d_bpartial; jb.n_wg = h->n_wg; jb.epw = h->epw;
-    int gy = std::max(1, std::min(n_models, 2048 / std::max(1, h->n_wg)));
-    if (const char *e = getenv("HTM_FULL_BLOCKS")) gy = std::max(1, std::min(n_models, atoi(e) / std::max(1, h->n_wg)));      // (tuning: blocks per launch)
-    rc = launch_full(h, jb, gy);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_sum_partials, dim3(n_models), dim3(64), 0, h->stream, h->d_bpartial, h->n_wg,
-                       h->dev.const_sum, d_L);
-    HIPCHK(hipGetLastError());
-    return HTM_OK;
-}
-
 }  // namespace
 
 // ====================================================================================================
 extern "C" {
-
-const char *htm_last_error(void) { return g_err.c_str(); }
-int htm_abi_version(void) { return 1; }
-
-int htm_device_count(int *n)
-{
-    if (!n) return fail(HTM_EINVAL, "n is NULL");
-    *n = 0;
-    hipError_t e = hipGetDeviceCount(n);
-    if (e != hipSuccess) { *n = 0; return fail(HTM_ENODEVICE, "hipGetDeviceCount: %s", hipGetErrorString(e)); }
-    return HTM_OK;
-}
-
-int htm_device_physical_id(int device, int *id)
-{
-    if (!id) return fail(HTM_EINVAL, "id is NULL");
-    *id = -1;
-    int dom = 0, bus = 0, dv = 0;
-    if (hipDeviceGetAttribute(&dom, hipDeviceAttributePciDomainID, device) != hipSuccess ||
-        hipDeviceGetAttribute(&bus, hipDeviceAttributePciBusId, device) != hipSuccess ||
-        hipDeviceGetAttribute(&dv, hipDeviceAttributePciDeviceId, device) != hipSuccess)
-        return fail(HTM_ENODEVICE, "no PCI address for HIP device %d", device);
-    *id = ((dom & 0x7fff) << 16) | ((bus & 0xff) << 8) | (dv & 0xff);
-    return HTM_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------
-int htm_forward_create(int n_sta, int n_events, const double *sta_x, const double *sta_y, const double *sta_z,
-                       const double *t_obs, const double *t_stdv, const double *a_obs, const double *a_stdv,
-                       int use_time, int use_amp, int device, htm_forward **out)
-{
-    if (!out) return fail(HTM_EINVAL, "out is NULL");
-    *out = nullptr;
-    if (n_sta <= 0 || n_events <= 0) return fail(HTM_EINVAL, "n_sta and n_events must be positive");
-    if (!sta_x || !sta_y || !sta_z || !t_obs || !t_stdv || !a_obs || !a_stdv)
-        return fail(HTM_EINVAL, "NULL input array");
-    int rc = use_device(device);
-    if (rc) return rc;
-
-    htm_forward *h = new htm_forward();
-    h->device = device; h->S = n_sta; h->E = n_events; h->nch = nch_for(n_sta);
-    const size_t n = (size_t)n_sta * n_events;
-
-    // init_forward, cls_forward.f90:76-92: precision, log-stdv and the missing-data rule (keyed on t_stdv
-    // only; log-stdv := 1.0 (sic), stdv := 1, precision := 1 for BOTH data types)
-    std::vector<double> tpr(n), apr(n), pst(n_events), psa(n_events);
-    const double log_2pi_half = 0.5 * std::log(2.0 * std::acos(-1.0));
-    double const_t = 0.0, const_a = 0.0;
-    for (int i = 0; i < n_events; ++i) {
-        double st = 0.0, sa = 0.0;
-        for (int j = 0; j < n_sta; ++j) {
-            const size_t k = (size_t)i * n_sta + j;
-            double lts, las;
-            if (t_stdv[k] > 1.e-16) {
-                lts = std::log(t_stdv[k]); tpr[k] = 1.0 / (t_stdv[k] * t_stdv[k]);
-                las = std::log(a_stdv[k]); apr[k] = 1.0 / (a_stdv[k] * a_stdv[k]);
-            } else {
-                lts = 1.0; tpr[k] = 1.0; las = 1.0; apr[k] = 1.0;
-            }
-            st += tpr[k]; sa += apr[k];
-            const_t += log_2pi_half + lts;
-            const_a += log_2pi_half + las;
-        }
-        pst[i] = st; psa[i] = sa;
-    }
-
-    auto cleanup = [&](int code) { htm_forward_destroy(h); return code; };
-    double *p = nullptr;
-#define UP(dst, src, cnt)                                          \
-    if ((rc = dev_upload(h->pool, &p, (src), (cnt)))) return cleanup(rc); \
-    dst = p;
-    UP(h->dev.sx, sta_x, n_sta) UP(h->dev.sy, sta_y, n_sta) UP(h->dev.sz, sta_z, n_sta)
-    UP(h->dev.t_obs, t_obs, n) UP(h->dev.t_prec, tpr.data(), n)
-    UP(h->dev.a_obs, a_obs, n) UP(h->dev.a_prec, apr.data(), n)
-    UP(h->dev.psum_t, pst.data(), n_events) UP(h->dev.psum_a, psa.data(), n_events)
-    {
-        std::vector<double> rt(n_events), ra(n_events);
-        for (int i = 0; i < n_events; ++i) { rt[i] = 1.0 / pst[i]; ra[i] = 1.0 / psa[i]; }
-        UP(h->dev.rpsum_t, rt.data(), n_events) UP(h->dev.rpsum_a, ra.data(), n_events)
-    }
-#undef UP
-    h->dev.S = n_sta; h->dev.E = n_events; h->dev.use_time = use_time ? 1 : 0; h->dev.use_amp = use_amp ? 1 : 0;
-    h->dev.const_sum = (use_time ? const_t : 0.0) + (use_amp ? const_a : 0.0);
-
-    h->epw = std::max(1, (n_events + 4 * 1024 - 1) / (4 * 1024));
-    h->n_wg = (n_events + 4 * h->epw - 1) / (4 * h->epw);
-
-    if ((rc = dev_alloc(h->pool, &h->d_hypo, 3 * (size_t)n_events))) return cleanup(rc);
-    if ((rc = dev_alloc(h->pool, &h->d_tc, n_sta))) return cleanup(rc);
-    if ((rc = dev_alloc(h->pool, &h->d_ac, n_sta))) return cleanup(rc);
-    if ((rc = dev_alloc(h->pool, &h->d_scal, 16))) return cleanup(rc);
-    if ((rc = dev_alloc(h->pool, &h->d_partial, h->n_wg))) return cleanup(rc);
-    if ((rc = dev_alloc(h->pool, &h->d_syn, n))) return cleanup(rc);
-    hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) return cleanup(fail(HTM_EHIP, "hipStreamCreate: %s", hipGetErrorString(e)));
-    h->stream = h->own_stream;
-    if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess)
-        return cleanup(fail(HTM_EHIP, "hipEventCreate failed"));
-    *out = h;
-    return HTM_OK;
-}
-
-int htm_forward_destroy(htm_forward *h)
-{
-    if (!h) return HTM_OK;
-    (void)hipSetDevice(h->device);
-    if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
-    for (void *p : h->pool) (void)hipFree(p);
-    if (h->d_bpartial) (void)hipFree(h->d_bpartial);
-    if (h->d_bmodels) (void)hipFree(h->d_bmodels);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    delete h;
-    return HTM_OK;
-}
-
-// The packed records (FwdDev::obs_pack, htm_device.hpp) for the precision in use, from the device's own rows -- the same bits
-// the row loads return.  The observations never change after htm_forward_create, so neither do the records.  They repeat the
-// four streams: 2 MB more at 1000 events x 64 stations in fp64, 41 MB at 10 000 x 128 -- only for a forward
-// whose chain set can run the specialised master (htm_chains_create asks for them).
-static int ensure_obs_pack(htm_forward *h)
-{
-    if (!h->pack_wanted) { h->dev.obs_pack = nullptr; return HTM_OK; }
-    const bool f32 = h->dev.fp32 != 0;
-    void *&slot = f32 ? h->d_pack32 : h->d_pack64;
-    if (!slot) {
-        if ((h->nch != 1 && h->nch != 2) || h->S != 64 * h->nch) return fail(HTM_EINVAL, "packed records need full rows of 64 or 128 stations");
-        const size_t S = (size_t)h->S, E = (size_t)h->E, n = S * E, es = f32 ? sizeof(float) : sizeof(double);
-        const size_t stride = obs_pack_stride(h->nch, f32);
-        const void *src[4] = {f32 ? (const void *)h->dev.t_obs32 : (const void *)h->dev.t_obs, f32 ? (const void *)h->dev.t_prec32 : (const void *)h->dev.t_prec,
-                              f32 ? (const void *)h->dev.a_obs32 : (const void *)h->dev.a_obs, f32 ? (const void *)h->dev.a_prec32 : (const void *)h->dev.a_prec};
-        std::vector<char> rows(n * es), buf(stride * E, 0);
-        for (int k = 0; k < 4; ++k) {
-            HIPCHK(hipMemcpy(rows.data(), src[k], n * es, hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < E; ++i) std::memcpy(buf.data() + i * stride + (size_t)k * S * es, rows.data() + i * S * es, S * es);
-        }
-        std::vector<double> rt(E), ra(E);
-        HIPCHK(hipMemcpy(rt.data(), h->dev.rpsum_t, E * sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(ra.data(), h->dev.rpsum_a, E * sizeof(double), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < E; ++i) {
-            std::memcpy(buf.data() + i * stride + 4 * S * es, &rt[i], sizeof(double));
-            std::memcpy(buf.data() + i * stride + 4 * S * es + sizeof(double), &ra[i], sizeof(double));
-        }
-        char *p = nullptr;
-        int rc = dev_upload(h->pool, &p, buf.data(), buf.size());
-        if (rc) return rc;
-        slot = p;
-    }
-    h->dev.obs_pack = slot;
-    return HTM_OK;
-}
-
-int htm_forward_obs_pack_bytes(htm_forward *h, int64_t *bytes)
-{
-    if (!h || !bytes) return fail(HTM_EINVAL, "NULL argument");
-    *bytes = (h->d_pack64 ? (int64_t)(obs_pack_stride(h->nch, false) * (size_t)h->E) : 0) +
-             (h->d_pack32 ? (int64_t)(obs_pack_stride(h->nch, true) * (size_t)h->E) : 0);
-    return HTM_OK;
-}
-
-int htm_forward_set_precision(htm_forward *h, int forward_fp32)
-{
-    if (!h) return fail(HTM_EINVAL, "NULL handle");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (!forward_fp32) { h->dev.fp32 = 0; return ensure_obs_pack(h); }
-    if (h->nch != 1 && h->nch != 2) return fail(HTM_EINVAL, "the fp32 forward covers n_sta <= 128 (this handle has %d stations)", h->S);
-    if (!h->dev.t_obs32) {
-        // the four observation streams once more as float: the bytes a full evaluation reads are halved
-        const size_t n = (size_t)h->S * h->E;
-        std::vector<double> tmp(n);
-        std::vector<float> f32(n);
-        const double *src[4] = {h->dev.t_obs, h->dev.t_prec, h->dev.a_obs, h->dev.a_prec};
-        const float **dst[4] = {&h->dev.t_obs32, &h->dev.t_prec32, &h->dev.a_obs32, &h->dev.a_prec32};
-        for (int k = 0; k < 4; ++k) {
-            HIPCHK(hipMemcpy(tmp.data(), src[k], n * sizeof(double), hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < n; ++i) f32[i] = (float)tmp[i];
-            float *p = nullptr;
-            int rc = dev_upload(h->pool, &p, f32.data(), n);
-            if (rc) return rc;
-            *dst[k] = p;
-        }
-    }
-    h->dev.fp32 = 1;
-    return ensure_obs_pack(h);
-}
-
-int htm_forward_set_stream(htm_forward *h, void *hip_stream)
-{
-    if (!h) return fail(HTM_EINVAL, "NULL handle");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->stream = static_cast<hipStream_t>(hip_stream);
-    return HTM_OK;
-}
-
-int htm_forward_reset_stream(htm_forward *h)
-{
-    if (!h) return fail(HTM_EINVAL, "NULL handle");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->stream = h->own_stream;
-    return HTM_OK;
-}
-
-int htm_forward_sync(htm_forward *h)
-{
-    if (!h) return fail(HTM_EINVAL, "NULL handle");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return HTM_OK;
-}
-
-int htm_forward_loglik_full(htm_forward *h, const double *hypo, const double *t_corr, double vs,
-                            const double *a_corr, double qs, double *log_likelihood)
-{
-    if (!h || !hypo || !t_corr || !a_corr || !log_likelihood) return fail(HTM_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(h->device));
-    const double sc[2] = {vs, qs};
-    HIPCHK(hipMemcpyAsync(h->d_hypo, hypo, 3 * (size_t)h->E * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_tc, t_corr, h->S * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_ac, a_corr, h->S * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_scal, sc, sizeof(sc), hipMemcpyHostToDevice, h->stream));
-    int rc = full_batch_dev(h, 1, h->d_hypo, h->d_tc, h->d_scal, h->d_ac, h->d_scal + 1, h->d_scal + 2);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(log_likelihood, h->d_scal + 2, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return HTM_OK;
-}
-
-int htm_forward_loglik_partial(htm_forward *h, int evt_id, const double hypo_old_xyz[3],
-                               double log_likelihood_old, const double hypo_xyz[3], const double *t_corr,
-                               double vs, const double *a_corr, double qs, double *log_likelihood)
-{
-    if (!h || !hypo_old_xyz || !hypo_xyz || !t_corr || !a_corr || !log_likelihood)
-        return fail(HTM_EINVAL, "NULL argument");
-    if (evt_id < 1 || evt_id > h->E) return fail(HTM_EINVAL, "evt_id %d out of range 1..%d", evt_id, h->E);
-    HIPCHK(hipSetDevice(h->device));
-    const double sc[6] = {hypo_old_xyz[0], hypo_old_xyz[1], hypo_old_xyz[2], hypo_xyz[0], hypo_xyz[1], hypo_xyz[2]};
-    HIPCHK(hipMemcpyAsync(h->d_tc, t_corr, h->S * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_ac, a_corr, h->S * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_scal + 4, sc, sizeof(sc), hipMemcpyHostToDevice, h->stream));
-    if (h->dev.fp32 && h->nch <= 2 && h->nch >= 1) {
-        if (h->nch == 1) hipLaunchKernelGGL((k_partial_one<1, true>), dim3(1), dim3(64), 0, h->stream, h->dev, evt_id - 1, h->d_scal + 4, h->d_scal + 7, h->d_tc, h->d_ac, vs, qs, log_likelihood_old, h->d_scal + 2);
-        else hipLaunchKernelGGL((k_partial_one<2, true>), dim3(1), dim3(64), 0, h->stream, h->dev, evt_id - 1, h->d_scal + 4, h->d_scal + 7, h->d_tc, h->d_ac, vs, qs, log_likelihood_old, h->d_scal + 2);
-    } else
-    switch (h->nch) {
-    case 1: hipLaunchKernelGGL(k_partial_one<1>, dim3(1), dim3(64), 0, h->stream, h->dev, evt_id - 1, h->d_scal + 4, h->d_scal + 7, h->d_tc, h->d_ac, vs, qs, log_likelihood_old, h->d_scal + 2); break;
-    case 2: hipLaunchKernelGGL(k_partial_one<2>, dim3(1), dim3(64), 0, h->stream, h->dev, evt_id - 1, h->d_scal + 4, h->d_scal + 7, h->d_tc, h->d_ac, vs, qs, log_likelihood_old, h->d_scal + 2); break;
-    case 4: hipLaunchKernelGGL(k_partial_one<4>, dim3(1), dim3(64), 0, h->stream, h->dev, evt_id - 1, h->d_scal + 4, h->d_scal + 7, h->d_tc, h->d_ac, vs, qs, log_likelihood_old, h->d_scal + 2); break;
-    default: hipLaunchKernelGGL(k_partial_one<0>, dim3(1), dim3(64), 0, h->stream, h->dev, evt_id - 1, h->d_scal + 4, h->d_scal + 7, h->d_tc, h->d_ac, vs, qs, log_likelihood_old, h->d_scal + 2); break;
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(log_likelihood, h->d_scal + 2, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return HTM_OK;
-}
-
-static int syn_common(htm_forward *h, const double *hypo, const double *corr, double beta, double q, int which,
-                      int evt_id, double *out)
-{
-    if (!h || !hypo || !corr || !out) return fail(HTM_EINVAL, "NULL argument");
-    if (evt_id != 0 && (evt_id < 1 || evt_id > h->E))
-        return fail(HTM_EINVAL, "evt_id %d out of range 1..%d", evt_id, h->E);
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpyAsync(h->d_hypo, hypo, 3 * (size_t)h->E * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_tc, corr, h->S * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    const int nblk = evt_id ? 1 : (h->E + 3) / 4;
-    hipLaunchKernelGGL(k_syn, dim3(nblk), dim3(256), 0, h->stream, h->dev, h->d_hypo, h->d_tc, beta, q, which,
-                       evt_id ? evt_id - 1 : -1, h->d_syn);
-    HIPCHK(hipGetLastError());
-    const size_t cnt = evt_id ? (size_t)h->S : (size_t)h->S * h->E;
-    HIPCHK(hipMemcpyAsync(out, h->d_syn, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return HTM_OK;
-}
-
-int htm_forward_travel_time(htm_forward *h, const double *hypo, const double *t_corr, double vs, double *t_syn)
-{ return syn_common(h, hypo, t_corr, vs, 1.0, 0, 0, t_syn); }
-int htm_forward_amp(htm_forward *h, const double *hypo, const double *a_corr, double qs, double vs, double *a_syn)
-{ return syn_common(h, hypo, a_corr, vs, qs, 1, 0, a_syn); }
-int htm_forward_travel_time_single(htm_forward *h, int evt_id, const double *hypo, const double *t_corr,
-                                   double vs, double *t_syn)
-{
-    if (h && (evt_id < 1 || evt_id > h->E)) return fail(HTM_EINVAL, "evt_id %d out of range", evt_id);
-    return syn_common(h, hypo, t_corr, vs, 1.0, 0, evt_id, t_syn);
-}
-int htm_forward_amp_single(htm_forward *h, int evt_id, const double *hypo, const double *a_corr, double qs,
-                           double vs, double *a_syn)
-{
-    if (h && (evt_id < 1 || evt_id > h->E)) return fail(HTM_EINVAL, "evt_id %d out of range", evt_id);
-    return syn_common(h, hypo, a_corr, vs, qs, 1, evt_id, a_syn);
-}
-
-int htm_forward_loglik_full_batch_dev(htm_forward *h, int n_models, const double *d_hypo, const double *d_t_corr,
-                                      const double *d_vs, const double *d_a_corr, const double *d_qs,
-                                      double *d_log_likelihood)
-{
-    if (!h || !d_hypo || !d_t_corr || !d_vs || !d_a_corr || !d_qs || !d_log_likelihood)
-        return fail(HTM_EINVAL, "NULL argument");
-    if (n_models <= 0) return fail(HTM_EINVAL, "n_models must be positive");
-    HIPCHK(hipSetDevice(h->device));
-    return full_batch_dev(h, n_models, d_hypo, d_t_corr, d_vs, d_a_corr, d_qs, d_log_likelihood);
-}
-
-int htm_forward_loglik_full_batch(htm_forward *h, int n_models, const double *hypo, const double *t_corr,
-                                  const double *vs, const double *a_corr, const double *qs, double *log_likelihood)
-{
-    if (!h || !hypo || !t_corr || !vs || !a_corr || !qs || !log_likelihood) return fail(HTM_EINVAL, "NULL argument");
-    if (n_models <= 0) return fail(HTM_EINVAL, "n_models must be positive");
-    HIPCHK(hipSetDevice(h->device));
-    const size_t nh = 3 * (size_t)h->E, ns = h->S;
-    const size_t per = nh + 2 * ns + 3, need = per * n_models;
-    if (need > h->bmodels_cap) {
-        if (h->d_bmodels) HIPCHK(hipFree(h->d_bmodels));
-        h->d_bmodels = nullptr;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&h->d_bmodels), need * sizeof(double)));
-        h->bmodels_cap = need;
-    }
-    double *dh = h->d_bmodels, *dt = dh + nh * n_models, *da = dt + ns * n_models, *dv = da + ns * n_models,
-           *dq = dv + n_models, *dL = dq + n_models;
-    HIPCHK(hipMemcpyAsync(dh, hypo, nh * n_models * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dt, t_corr, ns * n_models * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(da, a_corr, ns * n_models * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dv, vs, n_models * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dq, qs, n_models * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    int rc = full_batch_dev(h, n_models, dh, dt, dv, da, dq, dL);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(log_likelihood, dL, n_models * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return HTM_OK;
-}
-
-int htm_forward_time_full_batch_dev(htm_forward *h, int n_models, const double *d_hypo, const double *d_t_corr,
-                                    const double *d_vs, const double *d_a_corr, const double *d_qs,
-                                    double *d_log_likelihood, int reps, double *avg_us)
-{
-    if (!h || !avg_us || reps <= 0) return fail(HTM_EINVAL, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    int rc = htm_forward_loglik_full_batch_dev(h, n_models, d_hypo, d_t_corr, d_vs, d_a_corr, d_qs, d_log_likelihood);
-    if (rc) return rc;   // warm-up, also sizes the scratch
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    for (int r = 0; r < reps; ++r) {
-        rc = full_batch_dev(h, n_models, d_hypo, d_t_corr, d_vs, d_a_corr, d_qs, d_log_likelihood);
-        if (rc) return rc;
-    }
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    HIPCHK(hipEventSynchronize(h->ev1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    *avg_us = 1000.0 * ms / reps;
-    return HTM_OK;
-}
 
 // ---------------------------------------------------------------------------------------------------
 // chains
@@ -1072,12 +439,9 @@ int htm_chains_create(htm_forward *h, const htm_chains_init *init, htm_chains **
                             hc->step_smem, lds_cap));
     if (hc->step_smem > lds_cap) return cleanup(fail(HTM_EINVAL, "n_chains / n_sta too large for k_step's LDS budget"));
     if (hc->step_smem > 48 * 1024) {
-        const void *fn = h->dev.fp32 ? (h->nch == 1 ? (const void *)k_step<1, true> : (const void *)k_step<2, true>)
-                         : h->nch == 1 ? (const void *)k_step<1> : h->nch == 2 ? (const void *)k_step<2> : (const void *)k_step<0>;
-        if (hc->wide)
-            fn = h->dev.fp32 ? (h->nch == 1 ? (const void *)k_step_wide<1, true> : (const void *)k_step_wide<2, true>)
-                 : h->nch == 1 ? (const void *)k_step_wide<1> : h->nch == 2 ? (const void *)k_step_wide<2> : (const void *)k_step_wide<0>;
-        HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hc->step_smem));
+        const LoopKernel *ks = step_kernel(h->nch, h->dev.fp32 != 0, hc->wide);
+        if (!ks) return cleanup(no_kernel(hc, "k_step", 0));
+        HIPCHK(hipFuncSetAttribute(ks->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hc->step_smem));
     }
     if (hipEventCreateWithFlags(&hc->ev_wd, hipEventDisableTiming) != hipSuccess) return cleanup(fail(HTM_EHIP, "hipEventCreate failed"));
     if (hipEventCreate(&hc->ev0) != hipSuccess || hipEventCreate(&hc->ev1) != hipSuccess)
@@ -1088,21 +452,17 @@ int htm_chains_create(htm_forward *h, const htm_chains_init *init, htm_chains **
         // Master and workers of a k_mcmc launch wait for each other, so every block must be RESIDENT: never ask for more
         // worker blocks than the device can hold next to the master (a partitioned or CU-masked GPU has fewer CUs; every
         // block carries the master's LDS size).  Workers take events round-robin, so fewer of them only take longer.
-#define HTM_MCMC_FN(K) (h->dev.fp32 ? (h->nch == 1 ? (const void *)k_mcmc<1, true, K> : (const void *)k_mcmc<2, true, K>)                  \
-                        : h->nch == 1 ? (const void *)k_mcmc<1, false, K> : h->nch == 2 ? (const void *)k_mcmc<2, false, K> : (const void *)k_mcmc<0, false, K>)
-#define HTM_MCMC_WIDE_FN(K) (h->dev.fp32 ? (h->nch == 1 ? (const void *)k_mcmc_wide<1, true, K> : (const void *)k_mcmc_wide<2, true, K>)                  \
-                             : h->nch == 1 ? (const void *)k_mcmc_wide<1, false, K> : h->nch == 2 ? (const void *)k_mcmc_wide<2, false, K> : (const void *)k_mcmc_wide<0, false, K>)
+        // every loop a launch of this chain set can take (launch_mcmc); several master workgroups (MK 7) and the free-running
+        // master specialised on the job's shape (MK 8) exist for one or two stations per lane
+        std::vector<int> mks = {0, 1, 2};
+        if (!hc->wide) { mks.push_back(3); mks.push_back(4); }
+        if (!hc->wide && (h->nch == 1 || h->nch == 2)) { mks.push_back(7); mks.push_back(8); }
         std::vector<const void *> fns;
-        if (hc->wide) fns = {HTM_MCMC_WIDE_FN(0), HTM_MCMC_WIDE_FN(1), HTM_MCMC_WIDE_FN(2)};
-        else fns = {HTM_MCMC_FN(0), HTM_MCMC_FN(1), HTM_MCMC_FN(2), HTM_MCMC_FN(3), HTM_MCMC_FN(4)};
-#undef HTM_MCMC_WIDE_FN
-#undef HTM_MCMC_FN
-        // (several master workgroups, k_mcmc<.., 7>: one or two stations per lane)
-        if (!hc->wide && h->nch == 1) fns.push_back(h->dev.fp32 ? (const void *)k_mcmc<1, true, 7> : (const void *)k_mcmc<1, false, 7>);
-        else if (!hc->wide && h->nch == 2) fns.push_back(h->dev.fp32 ? (const void *)k_mcmc<2, true, 7> : (const void *)k_mcmc<2, false, 7>);
-        // (the free-running master specialised on the job's shape, k_mcmc<.., 8>: likewise)
-        if (!hc->wide && h->nch == 1) fns.push_back(h->dev.fp32 ? (const void *)k_mcmc<1, true, 8> : (const void *)k_mcmc<1, false, 8>);
-        else if (!hc->wide && h->nch == 2) fns.push_back(h->dev.fp32 ? (const void *)k_mcmc<2, true, 8> : (const void *)k_mcmc<2, false, 8>);
+        for (int mk : mks) {
+            const LoopKernel *k = mcmc_kernel(h->nch, h->dev.fp32 != 0, mk, hc->wide);
+            if (!k) return cleanup(no_kernel(hc, "k_mcmc", mk));
+            fns.push_back(k->fn);
+        }
         if (hc->step_smem > 48 * 1024)
             for (const void *g : fns) HIPCHK(hipFuncSetAttribute(g, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hc->step_smem));
         // the residency bound holds for whichever main loop gets launched: the smallest of the instantiations' occupancies
@@ -1200,10 +560,9 @@ int htm_chains_create(htm_forward *h, const htm_chains_init *init, htm_chains **
                     hc->dev.n_workers = std::min(hc->dev.n_workers, nw); hc->dev.n_wg = hc->dev.n_workers;
                 }
                 for (int lk = 5; lk <= 6; ++lk) {
-                    const void *pfn = lk == 5 ? (h->dev.fp32 ? (h->nch == 1 ? (const void *)k_mcmc<1, true, 5> : (const void *)k_mcmc<2, true, 5>)
-                                                            : (h->nch == 1 ? (const void *)k_mcmc<1, false, 5> : (const void *)k_mcmc<2, false, 5>))
-                                              : (h->dev.fp32 ? (h->nch == 1 ? (const void *)k_mcmc<1, true, 6> : (const void *)k_mcmc<2, true, 6>)
-                                                            : (h->nch == 1 ? (const void *)k_mcmc<1, false, 6> : (const void *)k_mcmc<2, false, 6>));
+                    const LoopKernel *pk = mcmc_kernel(h->nch, h->dev.fp32 != 0, lk, false);
+                    if (!pk) return cleanup(no_kernel(hc, "k_mcmc", lk));
+                    const void *pfn = pk->fn;
                     int pc = 0;
                     if (smem > 48 * 1024) HIPCHK(hipFuncSetAttribute(pfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
                     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, pfn, pthreads, smem));
@@ -2304,726 +1663,5 @@ int htm_chains_read_handoff(htm_chains *hc, int chain, unsigned long long out[64
     return HTM_OK;
 }
 #endif
-
-int htm_quantiles_dev(int device, const double *d_samples, long n_mod, long n_par, long ld, const int ranks_1based[3],
-                      double *d_out, void *hip_stream)
-{
-    if (!d_samples || !d_out || !ranks_1based) return fail(HTM_EINVAL, "NULL argument");
-    if (n_mod < 1 || n_par < 1 || ld < n_par) return fail(HTM_EINVAL, "bad shape (n_mod %ld, n_par %ld, ld %ld)", n_mod, n_par, ld);
-    // the select kernels count rows in int (LDS counters, the slab histogram's atomics) and take int ranks
-    if (n_mod > INT_MAX) return fail(HTM_EINVAL, "n_mod %ld exceeds %d rows per column", n_mod, INT_MAX);
-    for (int r = 0; r < 3; ++r)
-        if (ranks_1based[r] < 1 || ranks_1based[r] > n_mod)
-            return fail(HTM_EINVAL, "rank %d outside 1..%ld (the reference would index outside its sorted column)", ranks_1based[r], n_mod);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
-    HIPCHK(hipSetDevice(device));
-    const dim3 grid((unsigned)((n_par + 63) / 64)), block(64 * kSelRG);
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const char *force = getenv("HTM_SELECT_SLABS");
-    // small sets: one launch, a column group per workgroup; large sets: row slabs over the whole chip, a launch per digit
-    long slabs = 1;
-    if ((double)n_mod * (double)n_par >= (double)(1 << 22)) {
-        slabs = std::max(1L, std::min((n_mod + 255) / 256, (long)(2048 / grid.x)));
-        slabs = std::min(slabs, 1024L);
-    }
-    if (force) slabs = std::max(1L, std::min(atol(force), std::min(n_mod, 65535L)));
-    if (slabs <= 1 && !force) {
-        hipLaunchKernelGGL(k_select, grid, block, 0, st, d_samples, n_mod, n_par, ld,
-                           ranks_1based[0] - 1, ranks_1based[1] - 1, ranks_1based[2] - 1, d_out);
-        HIPCHK(hipGetLastError());
-        return HTM_OK;
-    }
-    // workspace: three histograms, two prefix/remaining states (stream-ordered allocation keeps the call asynchronous)
-    const size_t hist_b = (size_t)grid.x * kSelHistPerGroup * sizeof(int);
-    const size_t st_b = (size_t)n_par * kSelRanks * sizeof(unsigned long long);
-    const size_t total = 3 * hist_b + 4 * st_b;
-    char *ws = nullptr;
-    bool async_alloc = hipMallocAsync(reinterpret_cast<void **>(&ws), total, st) == hipSuccess;
-    if (!async_alloc) {
-        (void)hipGetLastError();
-        if (hipMalloc(reinterpret_cast<void **>(&ws), total) != hipSuccess) return fail(HTM_EHIP, "hipMalloc of %zu bytes failed", total);
-    }
-    HIPCHK(hipMemsetAsync(ws, 0, total, st));
-    SelWork w;
-    for (int k = 0; k < 3; ++k) w.hist[k] = reinterpret_cast<int *>(ws + k * hist_b);
-    for (int k = 0; k < 2; ++k) {
-        w.prefix[k] = reinterpret_cast<unsigned long long *>(ws + 3 * hist_b + (2 * k) * st_b);
-        w.remaining[k] = reinterpret_cast<long *>(ws + 3 * hist_b + (2 * k + 1) * st_b);
-    }
-    const long slab_rows = (n_mod + slabs - 1) / slabs;
-    const dim3 grid2(grid.x, (unsigned)slabs);
-    int pass = 0;
-    for (int shift = 60; shift >= 0; shift -= 4, ++pass)
-        hipLaunchKernelGGL(k_select_pass, grid2, block, 0, st, d_samples, n_mod, n_par, ld, ranks_1based[0] - 1,
-                           ranks_1based[1] - 1, ranks_1based[2] - 1, shift, pass, slab_rows, w, (double *)nullptr);
-    hipLaunchKernelGGL(k_select_pass, grid, block, 0, st, d_samples, n_mod, n_par, ld, ranks_1based[0] - 1,
-                       ranks_1based[1] - 1, ranks_1based[2] - 1, -4, pass, slab_rows, w, d_out);
-    HIPCHK(hipGetLastError());
-    if (async_alloc) {
-        HIPCHK(hipFreeAsync(ws, st));
-    } else {
-        HIPCHK(hipStreamSynchronize(st));
-        (void)hipFree(ws);
-    }
-    return HTM_OK;
-}
-
-int htm_quantiles(int device, const double *samples, long n_mod, long n_par, const int ranks_1based[3], double *out)
-{
-    if (!samples || !out) return fail(HTM_EINVAL, "NULL argument");
-    if (n_mod < 1 || n_par < 1) return fail(HTM_EINVAL, "bad shape");
-    if (n_mod > INT_MAX) return fail(HTM_EINVAL, "n_mod %ld exceeds %d rows per column", n_mod, INT_MAX);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
-    HIPCHK(hipSetDevice(device));
-    double *d_x = nullptr, *d_o = nullptr;
-    const size_t nb = (size_t)n_mod * n_par * sizeof(double), ob = (size_t)n_par * 3 * sizeof(double);
-    if (hipMalloc(reinterpret_cast<void **>(&d_x), nb) != hipSuccess) return fail(HTM_EHIP, "hipMalloc of %zu bytes failed", nb);
-    if (hipMalloc(reinterpret_cast<void **>(&d_o), ob) != hipSuccess) { (void)hipFree(d_x); return fail(HTM_EHIP, "hipMalloc failed"); }
-    int rc = HTM_OK;
-    if (hipMemcpy(d_x, samples, nb, hipMemcpyHostToDevice) != hipSuccess) rc = fail(HTM_EHIP, "upload failed");
-    if (rc == HTM_OK) rc = htm_quantiles_dev(device, d_x, n_mod, n_par, n_par, ranks_1based, d_o, nullptr);
-    if (rc == HTM_OK && hipMemcpy(out, d_o, ob, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HTM_EHIP, "download failed");
-    (void)hipFree(d_x); (void)hipFree(d_o);
-    return rc;
-}
-
-// ---- convergence diagnostics (htm_diag.hpp) ---------------------------------------------------------------------
-namespace {
-// shapes both forms refuse before any device call
-int diag_check(long n_seq, long n_draws, long n_par, int max_lag)
-{
-    if (n_draws < 4 || n_seq < 1 || n_par < 1 || max_lag < 1)
-        return fail(HTM_EINVAL, "bad shape (n_seq %ld, n_draws %ld, n_par %ld, max_lag %d): need n_draws >= 4, the others >= 1",
-                    n_seq, n_draws, n_par, max_lag);
-    if (n_seq > INT_MAX / n_draws) return fail(HTM_EINVAL, "n_seq * n_draws = %ld * %ld exceeds %d rows", n_seq, n_draws, INT_MAX);
-    return HTM_OK;
-}
-}  // namespace
-
-int htm_diagnose_dev(int device, const double *d_samples, long n_seq, long n_draws, long n_par, long ld, int max_lag,
-                     double *d_out, double *d_acov, void *hip_stream)
-{
-    if (!d_samples || !d_out) return fail(HTM_EINVAL, "NULL argument");
-    int rc = diag_check(n_seq, n_draws, n_par, max_lag);
-    if (rc) return rc;
-    if (ld < n_par) return fail(HTM_EINVAL, "bad shape (n_par %ld, ld %ld)", n_par, ld);
-    const long n = n_draws / 2, S = 2 * n_seq;
-    const int L = (int)std::min(n - 1, (long)max_lag);
-    // lags per thread: HTM_DIAG_LAGS=16|32 picks the other instantiation (tests, tools/bench_diagnose.py)
-    int kb = 32;
-    if (const char *e = getenv("HTM_DIAG_LAGS")) {
-        kb = atoi(e);
-        if (kb != 16 && kb != 32) return fail(HTM_EINVAL, "HTM_DIAG_LAGS = %s: 16 or 32", e);
-    }
-    const long n_cg = (n_par + 63) / 64, n_blk = L / kb + 1, n_lagwg = (n_blk + kDiagLW - 1) / kDiagLW;
-    if (n_cg > INT_MAX / S || n_cg > INT_MAX / n_lagwg)
-        return fail(HTM_EINVAL, "n_par %ld, %ld split sequences, %d lags need more than 2^32 - 1 work-items in one launch", n_par, S, L + 1);
-    // slabs of split sequences: waves enough to fill the chip many times over, so that the last round of workgroups costs
-    // little; a workspace of at most 256 MiB or half the samples' size
-    long slabs = std::min(S, (65536 + n_cg * n_blk - 1) / (n_cg * n_blk));
-    const double lag_bytes = (double)(L + 1) * (double)n_par * sizeof(double);
-    const double ws_cap = std::max((double)(256L << 20), (double)(n_seq * n_draws) * (double)n_par * sizeof(double) / 2);
-    slabs = std::max(1L, std::min(slabs, (long)(ws_cap / lag_bytes)));
-    if (const char *e = getenv("HTM_DIAG_SLABS")) slabs = std::max(1L, std::min(atol(e), S));
-    const long seq_per_slab = (S + slabs - 1) / slabs;
-    slabs = (S + seq_per_slab - 1) / seq_per_slab;          // no empty slab
-    if (n_cg * n_lagwg > INT_MAX / slabs || n_cg * S * 64 * kDiagRG > 0xffffffffL || n_cg * n_lagwg * slabs * 64 * kDiagLW > 0xffffffffL)
-        return fail(HTM_EINVAL, "n_par %ld, %ld split sequences, %d lags need more than 2^32 - 1 work-items in one launch", n_par, S, L + 1);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
-    HIPCHK(hipSetDevice(device));
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    // workspace: the means [S][n_par], the slabs' lag sums [slabs][L+1][n_par] (stream-ordered, as htm_quantiles_dev's)
-    const size_t mean_n = (size_t)S * n_par, part_n = (size_t)slabs * (L + 1) * n_par, total = (mean_n + part_n) * sizeof(double);
-    double *ws = nullptr;
-    bool async_alloc = hipMallocAsync(reinterpret_cast<void **>(&ws), total, st) == hipSuccess;
-    if (!async_alloc) {
-        (void)hipGetLastError();
-        if (hipMalloc(reinterpret_cast<void **>(&ws), total) != hipSuccess) return fail(HTM_EHIP, "hipMalloc of %zu bytes failed", total);
-    }
-    double *d_mean = ws, *d_part = ws + mean_n;
-    hipLaunchKernelGGL(k_diag_mean, dim3((unsigned)(n_cg * S)), dim3(64 * kDiagRG), 0, st, d_samples, n_draws, n, n_par, ld, n_cg, d_mean);
-    const dim3 grid((unsigned)(n_cg * n_lagwg * slabs)), block(64 * kDiagLW);
-    if (kb == 16)
-        hipLaunchKernelGGL(k_diag_acov<16>, grid, block, 0, st, d_samples, n_draws, n, n_par, ld, L, (int)S, (int)seq_per_slab, n_lagwg, n_cg, d_mean, d_part);
-    else
-        hipLaunchKernelGGL(k_diag_acov<32>, grid, block, 0, st, d_samples, n_draws, n, n_par, ld, L, (int)S, (int)seq_per_slab, n_lagwg, n_cg, d_mean, d_part);
-    hipLaunchKernelGGL(k_diag_finish, dim3((unsigned)n_cg), dim3(64), 0, st, d_part, d_mean, n, n_par, L, (int)S, (int)slabs,
-                       1.0 / std::log10((double)S * (double)n), d_out, d_acov);
-    HIPCHK(hipGetLastError());
-    if (async_alloc) {
-        HIPCHK(hipFreeAsync(ws, st));
-    } else {
-        HIPCHK(hipStreamSynchronize(st));
-        (void)hipFree(ws);
-    }
-    return HTM_OK;
-}
-
-int htm_diagnose(int device, const double *samples, long n_seq, long n_draws, long n_par, int max_lag, double *out, double *acov)
-{
-    if (!samples || !out) return fail(HTM_EINVAL, "NULL argument");
-    int rc = diag_check(n_seq, n_draws, n_par, max_lag);
-    if (rc) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
-    HIPCHK(hipSetDevice(device));
-    const long L = std::min(n_draws / 2 - 1, (long)max_lag);
-    const size_t xb = (size_t)n_seq * n_draws * n_par * sizeof(double), ob = (size_t)n_par * 4 * sizeof(double),
-                 ab = acov ? (size_t)(L + 1) * n_par * sizeof(double) : 0;
-    std::vector<void *> pool;
-    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
-    double *d_x = nullptr, *d_o = nullptr, *d_a = nullptr;
-    if ((rc = dev_upload(pool, &d_x, samples, xb / sizeof(double))) || (rc = dev_alloc(pool, &d_o, ob / sizeof(double))) ||
-        (acov && (rc = dev_alloc(pool, &d_a, ab / sizeof(double)))))
-        return done(rc);
-    rc = htm_diagnose_dev(device, d_x, n_seq, n_draws, n_par, n_par, max_lag, d_o, d_a, nullptr);
-    if (rc == HTM_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(HTM_EHIP, "the diagnostics kernels failed");
-    if (rc == HTM_OK && hipMemcpy(out, d_o, ob, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HTM_EHIP, "download failed");
-    if (rc == HTM_OK && acov && hipMemcpy(acov, d_a, ab, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HTM_EHIP, "download failed");
-    return done(rc);
-}
-
-int htm_select_regress(int device, int n_sta, int n_win, const double *sta_x, const double *sta_y, const double *sta_z,
-                       double z_guess, const double *t, const double *t_err, const double *a, const double *a_err, double *out)
-{
-    if (!sta_x || !sta_y || !sta_z || !t || !t_err || !a || !a_err || !out) return fail(HTM_EINVAL, "NULL argument");
-    if (n_sta < 3 || n_win < 1) return fail(HTM_EINVAL, "need n_sta >= 3 and n_win >= 1 (got %d, %d)", n_sta, n_win);
-    // a wave per window, four per workgroup: the dispatch packet holds the grid in work-items as a uint32_t
-    if (256L * ((n_win + 3L) / 4) > 0xffffffffL)
-        return fail(HTM_EINVAL, "n_win = %d windows need %ld work-items: more than one launch holds (2^32 - 1)", n_win,
-                    256L * ((n_win + 3L) / 4));
-    int rc = use_device(device);
-    if (rc) return rc;
-    std::vector<void *> pool;
-    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
-    const size_t n = (size_t)n_sta * n_win;
-    double *dx = nullptr, *dy = nullptr, *dz = nullptr, *dt = nullptr, *dte = nullptr, *da = nullptr, *dae = nullptr, *dout = nullptr;
-    if ((rc = dev_upload(pool, &dx, sta_x, n_sta)) || (rc = dev_upload(pool, &dy, sta_y, n_sta)) || (rc = dev_upload(pool, &dz, sta_z, n_sta)) ||
-        (rc = dev_upload(pool, &dt, t, n)) || (rc = dev_upload(pool, &dte, t_err, n)) || (rc = dev_upload(pool, &da, a, n)) ||
-        (rc = dev_upload(pool, &dae, a_err, n)) || (rc = dev_alloc(pool, &dout, 6 * (size_t)n_win))) return done(rc);
-    hipLaunchKernelGGL(k_regress, dim3((n_win + 3) / 4), dim3(256), 0, 0, n_sta, n_win, dx, dy, dz, z_guess, dt, dte, da, dae, dout);
-    if (hipGetLastError() != hipSuccess) return done(fail(HTM_EHIP, "k_regress launch failed"));
-    if (hipMemcpy(out, dout, 6 * (size_t)n_win * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return done(fail(HTM_EHIP, "download failed"));
-    return done(HTM_OK);
-}
-
-static int xcorr_check(long ld_env, long n_smp, int n_sta, int n, int n_step, int n_win, int pair0, int n_pairs, long ld_cc)
-{
-    if (n < 2 || n > kXcMaxN || n % 2) return fail(HTM_EINVAL, "window length n = %d: need an even n in 2..%d (the reference refuses odd n)", n, kXcMaxN);
-    if (n_sta < 2 || n_step < 1 || n_win < 1 || n_pairs < 1 || pair0 < 0)
-        return fail(HTM_EINVAL, "bad shape (n_sta %d, n_step %d, n_win %d, pair0 %d, n_pairs %d)", n_sta, n_step, n_win, pair0, n_pairs);
-    if ((long)pair0 + n_pairs > (long)n_sta * (n_sta - 1) / 2)
-        return fail(HTM_EINVAL, "pairs %d..%d outside the %d pairs of %d stations", pair0, pair0 + n_pairs - 1, n_sta * (n_sta - 1) / 2, n_sta);
-    if ((long)(n_win - 1) * n_step + n > n_smp || n_smp > ld_env)
-        return fail(HTM_EINVAL, "%d windows of %d samples every %d do not fit in %ld samples (row stride %ld)", n_win, n, n_step, n_smp, ld_env);
-    if (ld_cc < n_pairs) return fail(HTM_EINVAL, "ld_cc %ld < n_pairs %d", ld_cc, n_pairs);
-    if ((long)n_win * n_pairs > 0x7fffffffL) return fail(HTM_EINVAL, "n_win * n_pairs = %ld exceeds one launch", (long)n_win * n_pairs);
-    // the dispatch packet holds the grid in work-items as a uint32_t (hsa_kernel_dispatch_packet_t::grid_size_x)
-    if ((long)n_win * n_pairs * xc_threads(n) > 0xffffffffL)
-        return fail(HTM_EINVAL, "n_win * n_pairs * %d threads = %ld work-items exceed one launch (2^32 - 1)", xc_threads(n),
-                    (long)n_win * n_pairs * xc_threads(n));
-    return HTM_OK;
-}
-
-int htm_xcorr_dev(int device, const double *d_env, long ld_env, long n_smp, int n_sta, int n, int n_step, int n_win, int pair0,
-                  int n_pairs, double *d_cc, long ld_cc, double *d_cc_max, void *hip_stream)
-{
-    if (!d_env || !d_cc || !d_cc_max) return fail(HTM_EINVAL, "NULL argument");
-    int rc = xcorr_check(ld_env, n_smp, n_sta, n, n_step, n_win, pair0, n_pairs, ld_cc);
-    if (rc) return rc;
-    if ((rc = use_device(device))) return rc;
-    const int threads = xc_threads(n);
-    hipLaunchKernelGGL(k_xcorr, dim3((unsigned)((long)n_win * n_pairs)), dim3(threads), 2 * (size_t)n * sizeof(double),
-                       static_cast<hipStream_t>(hip_stream), d_env, ld_env, n_sta, n, n_step, n_win, pair0, n_pairs, d_cc, ld_cc,
-                       d_cc_max);
-    HIPCHK(hipGetLastError());
-    return HTM_OK;
-}
-
-int htm_xcorr(int device, const double *env, long n_smp, int n_sta, int n, int n_step, int n_win, int pair0, int n_pairs,
-              double *cc, double *cc_max)
-{
-    if (!env || !cc || !cc_max) return fail(HTM_EINVAL, "NULL argument");
-    int rc = xcorr_check(n_smp, n_smp, n_sta, n, n_step, n_win, pair0, n_pairs, n_pairs);
-    if (rc) return rc;
-    if ((rc = use_device(device))) return rc;
-    std::vector<void *> pool;
-    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
-    double *de = nullptr, *dc = nullptr, *dm = nullptr;
-    const size_t n_cc = (size_t)n_win * n * n_pairs, n_m = (size_t)n_win * n_pairs;
-    if ((rc = dev_upload(pool, &de, env, (size_t)n_sta * n_smp)) || (rc = dev_alloc(pool, &dc, n_cc)) || (rc = dev_alloc(pool, &dm, n_m)))
-        return done(rc);
-    if ((rc = htm_xcorr_dev(device, de, n_smp, n_smp, n_sta, n, n_step, n_win, pair0, n_pairs, dc, n_pairs, dm, nullptr))) return done(rc);
-    if (hipMemcpy(cc, dc, n_cc * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(cc_max, dm, n_m * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-        return done(fail(HTM_EHIP, "k_xcorr or its download failed"));
-    return done(HTM_OK);
-}
-
-int htm_measure_windows(int device, int n_sta, int n, double dt, int n_det, const double *x, double *t, double *t_stdv,
-                        double *amp, double *amp_stdv)
-{
-    if (!x || !t || !t_stdv || !amp || !amp_stdv) return fail(HTM_EINVAL, "NULL argument");
-    if (n_sta < 3 || n < 2 || n > kXcMaxN || n_det < 0 || !(dt > 0.0))
-        return fail(HTM_EINVAL, "need n_sta >= 3, n in 2..%d, n_det >= 0, dt > 0 (got %d, %d, %d, %g)", kXcMaxN, n_sta, n, n_det, dt);
-    if (n_det == 0) return HTM_OK;
-    int rc = use_device(device);
-    if (rc) return rc;
-    std::vector<void *> pool;
-    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
-    // windows in launches of at most HTM_MEASURE_MB MiB of inputs and workspace (default 256: every window of a usual
-    // run in one launch; at least one window per launch)
-    const size_t per_win = ((size_t)n_sta * n + (size_t)n_sta * n_sta + 5 * (size_t)n_sta) * sizeof(double);
-    const char *mb_env = getenv("HTM_MEASURE_MB");
-    const double mb = mb_env ? atof(mb_env) : 256.0;
-    const size_t budget = mb > 0.0 ? (size_t)std::min(mb * 1048576.0, 1e18) : 0;
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_det, budget / per_win));
-    double *dx = nullptr, *dws = nullptr, *dout = nullptr;
-    if ((rc = dev_alloc(pool, &dx, (size_t)chunk * n_sta * n)) || (rc = dev_alloc(pool, &dws, (size_t)chunk * ((size_t)n_sta * n_sta + n_sta))) ||
-        (rc = dev_alloc(pool, &dout, 4 * (size_t)chunk * n_sta)))
-        return done(rc);
-    double *outs[4] = {t, t_stdv, amp, amp_stdv};
-    for (int w0 = 0; w0 < n_det; w0 += chunk) {
-        const int nw = std::min(chunk, n_det - w0);
-        const size_t ns = (size_t)nw * n_sta;
-        HIPCHK(hipMemcpy(dx, x + (size_t)w0 * n_sta * n, ns * n * sizeof(double), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_measure, dim3(nw), dim3(xc_threads(n)), 2 * (size_t)n * sizeof(double), 0, dx, n_sta, n, dt, nw, dws,
-                           dout, dout + (size_t)chunk * n_sta, dout + 2 * (size_t)chunk * n_sta, dout + 3 * (size_t)chunk * n_sta);
-        if (hipGetLastError() != hipSuccess) return done(fail(HTM_EHIP, "k_measure launch failed"));
-        for (int k = 0; k < 4; ++k)
-            if (hipMemcpy(outs[k] + (size_t)w0 * n_sta, dout + k * (size_t)chunk * n_sta, ns * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-                return done(fail(HTM_EHIP, "k_measure or its download failed"));
-    }
-    return done(HTM_OK);
-}
-
-}  // extern "C"
-
-// ---- step 1: FFT plans (htm_fft.hpp) and the convert pipeline (htm_convert.hpp) ---------------------------------------
-namespace {
-
-struct FftPlan {
-    long n = 0;
-    std::vector<int> radix;          // Stockham passes (empty for n = 1 and for Bluestein lengths)
-    std::vector<long> tw_off;        // first twiddle of each pass in d_tw
-    double2 *d_tw = nullptr;
-    long m = 0;                      // Bluestein: inner power-of-two length (0: Stockham)
-    const FftPlan *inner = nullptr;
-    double2 *d_chirp = nullptr, *d_b = nullptr;
-};
-
-std::mutex g_fft_mu;
-std::map<std::pair<int, long>, FftPlan *> g_fft_plans;   // per (device, n); kept for the life of the process
-
-bool fft_factor(long n, std::vector<int> &r)
-{
-    r.clear();
-    while (n % 4 == 0) { r.push_back(4); n /= 4; }
-    if (n % 2 == 0) { r.push_back(2); n /= 2; }
-    for (int p : {3, 5, 7})
-        while (n % p == 0) { r.push_back(p); n /= p; }
-    return n == 1;
-}
-
-long fft_inner_len(long n)
-{
-    long m = 1;
-    while (m < 2 * n - 1) m <<= 1;
-    return m;
-}
-
-// complex elements of workspace fft_run needs for `rows` rows of n, and the most work-items one of its launches takes
-size_t fft_ws_elems(long n, long rows)
-{
-    std::vector<int> r;
-    return fft_factor(n, r) ? (size_t)rows * n : 2 * (size_t)rows * fft_inner_len(n);
-}
-long fft_max_items(long n, long rows)
-{
-    std::vector<int> r;
-    return fft_factor(n, r) ? rows * n : rows * fft_inner_len(n);
-}
-
-dim3 fft_grid(long total) { return dim3((unsigned)((total + kFftThreads - 1) / kFftThreads)); }
-
-int fft_run(const FftPlan &p, const double2 *in, long ld_in, double2 *out, long ld_out, long rows, int sign, double2 *ws,
-            hipStream_t st)
-{
-    const long n = p.n;
-    if (p.m == 0) {
-        const int P = (int)p.radix.size();
-        if (P == 0) {
-            if (in != out) hipLaunchKernelGGL(k_fft_copy, fft_grid(rows * n), dim3(kFftThreads), 0, st, in, ld_in, out, ld_out, n, rows * n);
-            HIPCHK(hipGetLastError());
-            return HTM_OK;
-        }
-        // the last pass writes `out`; in place with an odd pass count the passes end in ws and a copy follows
-        const bool extra = in == out && P % 2 == 1;
-        const double2 *src = in;
-        long lds = ld_in, ns = 1;
-        for (int i = 0; i < P; ++i) {
-            const bool to_out = extra ? (i % 2 == 1) : ((P - 1 - i) % 2 == 0);
-            double2 *dst = to_out ? out : ws;
-            const long ldd = to_out ? ld_out : n;
-            const int R = p.radix[i];
-            const long total = rows * (n / R);
-            const double2 *tw = p.d_tw + p.tw_off[i];
-            switch (R) {
-            case 2: hipLaunchKernelGGL(k_fft_pass<2>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n, (int)ns, tw, sign, total); break;
-            case 3: hipLaunchKernelGGL(k_fft_pass<3>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n, (int)ns, tw, sign, total); break;
-            case 4: hipLaunchKernelGGL(k_fft_pass<4>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n, (int)ns, tw, sign, total); break;
-            case 5: hipLaunchKernelGGL(k_fft_pass<5>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n, (int)ns, tw, sign, total); break;
-            default: hipLaunchKernelGGL(k_fft_pass<7>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n, (int)ns, tw, sign, total); break;
-            }
-            src = dst; lds = ldd; ns *= R;
-        }
-        if (extra) hipLaunchKernelGGL(k_fft_copy, fft_grid(rows * n), dim3(kFftThreads), 0, st, ws, n, out, ld_out, n, rows * n);
-        HIPCHK(hipGetLastError());
-        return HTM_OK;
-    }
-    // Bluestein: backward(x) = conj(forward(conj(x))); ws holds a [rows][m] and the inner transforms' own rows * m
-    const long m = p.m;
-    double2 *a = ws, *ws2 = ws + (size_t)rows * m;
-    hipLaunchKernelGGL(k_blue_pre, fft_grid(rows * m), dim3(kFftThreads), 0, st, in, ld_in, a, n, m, p.d_chirp, sign > 0 ? 1 : 0, rows * m);
-    int rc = fft_run(*p.inner, a, m, a, m, rows, -1, ws2, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_blue_mul, fft_grid(rows * m), dim3(kFftThreads), 0, st, a, m, p.d_b, rows * m);
-    if ((rc = fft_run(*p.inner, a, m, a, m, rows, +1, ws2, st))) return rc;
-    hipLaunchKernelGGL(k_blue_post, fft_grid(rows * n), dim3(kFftThreads), 0, st, a, m, out, ld_out, n, p.d_chirp, sign > 0 ? 1 : 0, rows * n);
-    HIPCHK(hipGetLastError());
-    return HTM_OK;
-}
-
-const long double kPiL = 3.141592653589793238462643383279502884L;
-
-// the plan of length n on the current device, built once (g_fft_mu held); tables in long double, rounded once
-int fft_plan_locked(int device, long n, const FftPlan **out)
-{
-    auto it = g_fft_plans.find(std::make_pair(device, n));
-    if (it != g_fft_plans.end()) { *out = it->second; return HTM_OK; }
-    std::unique_ptr<FftPlan> p(new FftPlan);
-    p->n = n;
-    if (fft_factor(n, p->radix)) {
-        // tw[off + k (R-1) + r - 1] = exp(-2 pi i r k / (ns R)), k < ns
-        std::vector<double2> tw;
-        long ns = 1;
-        for (int R : p->radix) {
-            p->tw_off.push_back((long)tw.size());
-            for (long k = 0; k < ns; ++k)
-                for (int r = 1; r < R; ++r) {
-                    const long double a = -2.0L * kPiL * (long double)(r * k) / (long double)(ns * R);
-                    tw.push_back(make_double2((double)cosl(a), (double)sinl(a)));
-                }
-            ns *= R;
-        }
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&p->d_tw), std::max<size_t>(1, tw.size()) * sizeof(double2)));
-        if (!tw.empty()) HIPCHK(hipMemcpy(p->d_tw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
-    } else {
-        p->radix.clear();
-        p->m = fft_inner_len(n);
-        const long m = p->m;
-        int rc = fft_plan_locked(device, m, &p->inner);
-        if (rc) return rc;
-        // chirp w[j] = exp(-pi i (j^2 mod 2n) / n); b = conj(w) at j and m - j, divided by m (a power of two: exact)
-        std::vector<double2> w(n), b(m, make_double2(0.0, 0.0));
-        for (long j = 0; j < n; ++j) {
-            const long q = (long)(((unsigned long long)j * (unsigned long long)j) % (unsigned long long)(2 * n));
-            const long double a = -kPiL * (long double)q / (long double)n;
-            const long double c = cosl(a), s = sinl(a);
-            w[j] = make_double2((double)c, (double)s);
-            b[j] = make_double2((double)(c / m), (double)(-s / m));
-            if (j) b[m - j] = b[j];
-        }
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&p->d_chirp), n * sizeof(double2)));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&p->d_b), m * sizeof(double2)));
-        HIPCHK(hipMemcpy(p->d_chirp, w.data(), n * sizeof(double2), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(p->d_b, b.data(), m * sizeof(double2), hipMemcpyHostToDevice));
-        double2 *tmp = nullptr;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&tmp), m * sizeof(double2)));
-        rc = fft_run(*p->inner, p->d_b, m, p->d_b, m, 1, -1, tmp, nullptr);
-        const hipError_t e = hipDeviceSynchronize();
-        (void)hipFree(tmp);
-        if (rc) return rc;
-        if (e != hipSuccess) return fail(HTM_EHIP, "Bluestein table of n = %ld: %s", n, hipGetErrorString(e));
-    }
-    *out = p.get();
-    g_fft_plans[std::make_pair(device, n)] = p.release();
-    return HTM_OK;
-}
-
-int fft_plan(int device, long n, const FftPlan **out)
-{
-    std::lock_guard<std::mutex> lk(g_fft_mu);
-    return fft_plan_locked(device, n, out);
-}
-
-// stream-ordered workspace, as htm_quantiles_dev allocates it
-struct AsyncBuf {
-    void *p = nullptr;
-    hipStream_t st = nullptr;
-    bool async = false;
-    int alloc(size_t bytes, hipStream_t s)
-    {
-        st = s;
-        async = hipMallocAsync(&p, std::max<size_t>(bytes, 1), st) == hipSuccess;
-        if (!async) {
-            (void)hipGetLastError();
-            if (hipMalloc(&p, std::max<size_t>(bytes, 1)) != hipSuccess) { p = nullptr; return fail(HTM_EHIP, "hipMalloc of %zu bytes failed", bytes); }
-        }
-        return HTM_OK;
-    }
-    int release()
-    {
-        if (!p) return HTM_OK;
-        void *q = p;
-        p = nullptr;
-        if (async) { HIPCHK(hipFreeAsync(q, st)); return HTM_OK; }
-        HIPCHK(hipStreamSynchronize(st));
-        (void)hipFree(q);
-        return HTM_OK;
-    }
-};
-
-int fft_check(const void *in, long ld_in, const void *out, long ld_out, long n, long batch, int direction)
-{
-    if (!in || !out) return fail(HTM_EINVAL, "NULL argument");
-    if (n < 1 || n > kFftMaxN) return fail(HTM_EINVAL, "FFT length n = %ld outside 1..%ld", n, kFftMaxN);
-    if (batch < 1 || ld_in < n || ld_out < n) return fail(HTM_EINVAL, "bad shape (batch %ld, ld_in %ld, ld_out %ld, n %ld)", batch, ld_in, ld_out, n);
-    if (direction != -1 && direction != 1) return fail(HTM_EINVAL, "direction must be -1 (forward) or +1 (backward), got %d", direction);
-    if (in == out && ld_in != ld_out) return fail(HTM_EINVAL, "in place needs ld_in == ld_out");
-    if (fft_max_items(n, batch) > 0xffffffffL)
-        return fail(HTM_EINVAL, "%ld rows of n = %ld need %ld work-items in one launch (more than 2^32 - 1)", batch, n, fft_max_items(n, batch));
-    return HTM_OK;
-}
-
-// step 1 geometry: index of the last segment, and the kept range [start, end) of stream samples of segment j
-long cv_last(long n_total, int n) { return (n_total - n) / (n / 2) + 1; }
-long cv_start(long j, int n) { return j == 0 ? 0 : j * (n / 2) + n / 4; }
-long cv_end(long j, long n_total, int n) { return j == cv_last(n_total, n) ? n_total : j * (n / 2) + n - n / 4; }
-long ceil_div(long a, long b) { return (a + b - 1) / b; }
-
-int cv_check(long n_total, int n, int n_fac, int h, const int k_band[4], long j0, long j1)
-{
-    if (!k_band) return fail(HTM_EINVAL, "NULL argument");
-    if (n < 4 || n % 4 || n > kFftMaxN) return fail(HTM_EINVAL, "n = %d: need a multiple of 4 in 4..%ld", n, kFftMaxN);
-    if (n_total < n) return fail(HTM_EINVAL, "data length is not enough in queue (N = %ld < n = %d)", n_total, n);
-    if (n_fac < 1 || n_fac > n / 2) return fail(HTM_EINVAL, "n_fac = %d: need 1 <= n_fac <= n/2 = %d", n_fac, n / 2);
-    if (h < 0 || h > kCvMaxH || 2L * h > n) return fail(HTM_EINVAL, "half width h = %d: need 0 <= h <= %d and 2h <= n = %d", h, kCvMaxH, n);
-    if (k_band[0] < 0 || k_band[0] > k_band[1] || k_band[1] > k_band[2] || k_band[2] > k_band[3])
-        return fail(HTM_EINVAL, "band bins must satisfy 0 <= k1 <= k2 <= k3 <= k4 (got %d %d %d %d)", k_band[0], k_band[1], k_band[2], k_band[3]);
-    const long last = cv_last(n_total, n);
-    if (j0 < 0 || j0 > j1 || j1 > last) return fail(HTM_EINVAL, "segments %ld..%ld outside 0..%ld", j0, j1, last);
-    const long S = j1 - j0 + 1;
-    if (std::max(fft_max_items(n, 2 * S), 2 * S * (long)n) > 0xffffffffL)
-        return fail(HTM_EINVAL, "%ld segments of n = %d need more than 2^32 - 1 work-items in one launch", S, n);
-    return HTM_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int htm_fft_dev(int device, const double *d_in, long ld_in, double *d_out, long ld_out, long n, long batch, int direction,
-                void *hip_stream)
-{
-    int rc = fft_check(d_in, ld_in, d_out, ld_out, n, batch, direction);
-    if (rc) return rc;
-    if ((rc = use_device(device))) return rc;
-    const FftPlan *p = nullptr;
-    if ((rc = fft_plan(device, n, &p))) return rc;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    AsyncBuf ws;
-    if ((rc = ws.alloc(fft_ws_elems(n, batch) * sizeof(double2), st))) return rc;
-    rc = fft_run(*p, reinterpret_cast<const double2 *>(d_in), ld_in, reinterpret_cast<double2 *>(d_out), ld_out, batch, direction, static_cast<double2 *>(ws.p), st);
-    const int rc2 = ws.release();
-    return rc ? rc : rc2;
-}
-
-int htm_fft(int device, const double *in, long ld_in, double *out, long ld_out, long n, long batch, int direction)
-{
-    int rc = fft_check(in, ld_in, out, ld_out, n, batch, direction);
-    if (rc) return rc;
-    if ((rc = use_device(device))) return rc;
-    std::vector<void *> pool;
-    auto done = [&](int code) { for (void *q : pool) (void)hipFree(q); return code; };
-    const size_t ni = 2 * ((size_t)(batch - 1) * ld_in + n), no = 2 * ((size_t)(batch - 1) * ld_out + n);
-    double *di = nullptr, *dout = nullptr;
-    if ((rc = dev_upload(pool, &dout, out, no))) return done(rc);      // keeps the padding between strided rows
-    if (in == out) di = dout;
-    else if ((rc = dev_upload(pool, &di, in, ni))) return done(rc);
-    if ((rc = htm_fft_dev(device, di, ld_in, dout, ld_out, n, batch, direction, nullptr))) return done(rc);
-    if (hipMemcpy(out, dout, no * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return done(fail(HTM_EHIP, "FFT or its download failed"));
-    return done(HTM_OK);
-}
-
-int htm_convert_dev(int device, const float *d_x1, const float *d_x2, long n_total, int n, int n_fac, int h,
-                    const int k_band[4], double fac1, double fac2, long j0, long j1, double *d_out, void *hip_stream)
-{
-    if (!d_x1 || !d_x2 || !d_out) return fail(HTM_EINVAL, "NULL argument");
-    int rc = cv_check(n_total, n, n_fac, h, k_band, j0, j1);
-    if (rc) return rc;
-    if ((rc = use_device(device))) return rc;
-    const FftPlan *p = nullptr;
-    if ((rc = fft_plan(device, n, &p))) return rc;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const long S = j1 - j0 + 1, n2 = n / 2, last = cv_last(n_total, n);
-    const long n_valid = std::min(n_total, j1 * n2 + n) - j0 * n2;
-    // workspace: z [S][n] (later the first smoothing [2S][n] doubles), y [2S][n], the FFT's own, 4S coefficients
-    const size_t zb = (size_t)S * n * sizeof(double2), yb = 2 * zb, fb = fft_ws_elems(n, 2 * S) * sizeof(double2);
-    AsyncBuf ws;
-    if ((rc = ws.alloc(zb + yb + fb + 4 * S * sizeof(double), st))) return rc;
-    char *base = static_cast<char *>(ws.p);
-    double2 *z = reinterpret_cast<double2 *>(base), *y = reinterpret_cast<double2 *>(base + zb);
-    double2 *fw = reinterpret_cast<double2 *>(base + zb + yb);
-    double *coef = reinterpret_cast<double *>(base + zb + yb + fb);
-    const long sn = S * n;
-    hipLaunchKernelGGL(k_cv_detrend, dim3((unsigned)S), dim3(kCvSumThreads), 0, st, d_x1, d_x2, n_valid, n, coef);
-    hipLaunchKernelGGL(k_cv_pack, fft_grid(sn), dim3(kCvThreads), 0, st, d_x1, d_x2, n_valid, n, coef, z, sn);
-    if ((rc = fft_run(*p, z, n, z, n, S, -1, fw, st))) { ws.release(); return rc; }
-    const int4 kb = make_int4(k_band[0], k_band[1], k_band[2], k_band[3]);
-    hipLaunchKernelGGL(k_cv_spectrum, fft_grid(sn), dim3(kCvThreads), 0, st, z, n, kb, y, sn);
-    if ((rc = fft_run(*p, y, n, y, n, 2 * S, +1, fw, st))) { ws.release(); return rc; }
-    const int tiles1 = (int)ceil_div(n, kCvTile), tiles2 = (int)ceil_div(n - n / 4, kCvTile);
-    const size_t lds = 2 * (size_t)(kCvTile + 2 * h) * sizeof(double);
-    double *e1 = reinterpret_cast<double *>(z);
-    const long k_base = ceil_div(cv_start(j0, n), n_fac);
-    hipLaunchKernelGGL(k_cv_smooth<false>, dim3((unsigned)(S * tiles1)), dim3(kCvThreads), lds, st, y, (const double *)nullptr, e1, n, h,
-                       tiles1, j0, last, n_total, n_fac, k_base, fac1, fac2, (double *)nullptr);
-    hipLaunchKernelGGL(k_cv_smooth<true>, dim3((unsigned)(S * tiles2)), dim3(kCvThreads), lds, st, (const double2 *)nullptr, e1,
-                       (double *)nullptr, n, h, tiles2, j0, last, n_total, n_fac, k_base, fac1, fac2, d_out);
-    const hipError_t e = hipGetLastError();
-    rc = ws.release();
-    if (e != hipSuccess) return fail(HTM_EHIP, "step-1 kernels failed to launch: %s", hipGetErrorString(e));
-    return rc;
-}
-
-int htm_convert(int device, const float *x1, const float *x2, long n_total, int n, int n_fac, int h, const int k_band[4],
-                double fac1, double fac2, long j0, long j1, double *out)
-{
-    if (!x1 || !x2 || !out) return fail(HTM_EINVAL, "NULL argument");
-    int rc = cv_check(n_total, n, n_fac, h, k_band, j0, j1);
-    if (rc) return rc;
-    if ((rc = use_device(device))) return rc;
-    std::vector<void *> pool;
-    auto done = [&](int code) { for (void *q : pool) (void)hipFree(q); return code; };
-    const long n2 = n / 2;
-    const size_t n_valid = (size_t)(std::min(n_total, j1 * n2 + n) - j0 * n2);
-    const size_t n_out = (size_t)(ceil_div(cv_end(j1, n_total, n), n_fac) - ceil_div(cv_start(j0, n), n_fac));
-    float *d1 = nullptr, *d2 = nullptr;
-    double *dout = nullptr;
-    if ((rc = dev_upload(pool, &d1, x1, n_valid)) || (rc = dev_upload(pool, &d2, x2, n_valid)) || (rc = dev_alloc(pool, &dout, n_out)))
-        return done(rc);
-    if ((rc = htm_convert_dev(device, d1, d2, n_total, n, n_fac, h, k_band, fac1, fac2, j0, j1, dout, nullptr))) return done(rc);
-    if (hipMemcpy(out, dout, n_out * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return done(fail(HTM_EHIP, "step-1 kernels or their download failed"));
-    return done(HTM_OK);
-}
-
-int htm_rng_jump(const uint32_t state_in[4], unsigned long long n_draws, uint32_t state_out[4])
-{
-    if (!state_in || !state_out) return fail(HTM_EINVAL, "NULL argument");
-    const std::vector<Mat128> &P = xs_powers();
-    Bits128 s{{state_in[0], state_in[1], state_in[2], state_in[3]}};
-    for (int k = 0; k < 64; ++k)
-        if ((n_draws >> k) & 1ull) s = gf2_matvec(P[k], s);
-    for (int k = 0; k < 4; ++k) state_out[k] = s.w[k];
-    return HTM_OK;
-}
-
-// the parallel generator against a serial loop on the device: n draws from `seed`, ring of `cap` positions starting at `start`
-static int selftest_rawgen(const uint32_t seed[4], int n, long long start, long long cap)
-{
-    std::vector<void *> pool;
-    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
-    StreamDev sd{};
-    sd.mask = cap - 1;
-    uint32_t *d_ser = nullptr, *d_gen = nullptr;
-    u32x4 *d_jump = nullptr;
-    int rc;
-    if ((rc = dev_alloc(pool, &sd.raw, (size_t)cap)) || (rc = dev_alloc(pool, &d_ser, (size_t)n))) return done(rc);
-    uint32_t g16[16] = {seed[0], seed[1], seed[2], seed[3]};
-    if ((rc = dev_upload(pool, &d_gen, g16, 16))) return done(rc);
-    const std::vector<Mat128> &P = xs_powers();
-    std::vector<u32x4> jt((size_t)kJumpLevels * 128);
-    for (int b = 0; b < kJumpLevels; ++b)
-        for (int j = 0; j < 128; ++j) jt[(size_t)b * 128 + j] = u32x4{P[6 + b][j].w[0], P[6 + b][j].w[1], P[6 + b][j].w[2], P[6 + b][j].w[3]};
-    if ((rc = dev_upload(pool, &d_jump, jt.data(), jt.size()))) return done(rc);
-    hipLaunchKernelGGL(k_rawgen, dim3((unsigned)((n + 4095) / 4096)), dim3(64), 0, 0, sd, start, n, d_jump, d_gen, d_gen + 4);
-    hipLaunchKernelGGL(k_rawgen_serial, dim3(1), dim3(1), 0, 0, d_ser, n, d_gen, d_gen + 8);
-    if (hipDeviceSynchronize() != hipSuccess) return done(fail(HTM_EHIP, "rawgen selftest kernels failed"));
-    std::vector<uint32_t> ring((size_t)cap), ser((size_t)n);
-    uint32_t g[16];
-    if (hipMemcpy(ring.data(), sd.raw, cap * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(ser.data(), d_ser, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(g, d_gen, sizeof(g), hipMemcpyDeviceToHost) != hipSuccess) return done(fail(HTM_EHIP, "download failed"));
-    for (int k = 0; k < n; ++k)
-        if (ring[(size_t)((start + k) & (cap - 1))] != ser[k])
-            return done(fail(HTM_ESTATE, "parallel xorshift128 differs from the serial stream at draw %d of %d", k, n));
-    uint32_t hj[4];
-    htm_rng_jump(seed, (unsigned long long)n, hj);
-    for (int k = 0; k < 4; ++k)
-        if (g[4 + k] != g[8 + k] || g[4 + k] != hj[k])
-            return done(fail(HTM_ESTATE, "generator state after %d draws: parallel %08x serial %08x host jump %08x", n, g[4 + k], g[8 + k], hj[k]));
-    return done(HTM_OK);
-}
-
-int htm_selftest_math(int device, int which, const double *x, double *y, int n)
-{
-    int rc = use_device(device);
-    if (rc) return rc;
-    if (!x || !y || n < 0 || which < 0 || which > 6 || (which == 4 && n % 64 != 0) || (which >= 5 && n % 256 != 0))
-        return fail(HTM_EINVAL, "htm_selftest_math: null pointer, negative count or unknown function");
-    if (n == 0) return HTM_OK;
-    double *d = nullptr;
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&d), 2 * (size_t)n * sizeof(double)));
-    auto done = [&](int code) { (void)hipFree(d); return code; };
-    if (hipMemcpy(d, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return done(fail(HTM_EHIP, "htm_selftest_math: copy in"));
-    hipLaunchKernelGGL(k_mathtest, dim3((n + 255) / 256), dim3(256), 0, 0, which, d, d + n, n);
-    if (hipGetLastError() != hipSuccess || hipMemcpy(y, d + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-        return done(fail(HTM_EHIP, "htm_selftest_math: kernel or copy out failed"));
-    return done(HTM_OK);
-}
-
-int htm_selftest(int device)
-{
-    int rc = use_device(device);
-    if (rc) return rc;
-    std::vector<double> in(128);
-    uint32_t s = 12345u;
-    for (auto &v : in) { s = s * 1664525u + 1013904223u; v = (double)(int32_t)s / 65536.0 / 7.0; }
-    double *d_in = nullptr, *d_o = nullptr;
-    uint32_t *d_r = nullptr;
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_in), 128 * sizeof(double)));
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_o), 16 * sizeof(double)));
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_r), 8 * sizeof(uint32_t)));
-    HIPCHK(hipMemcpy(d_in, in.data(), 128 * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_selftest, dim3(1), dim3(64), 0, 0, d_in, d_o, d_o + 2, d_r, d_o + 4);
-    HIPCHK(hipGetLastError());
-    double o[16];
-    uint32_t r[8];
-    HIPCHK(hipMemcpy(o, d_o, sizeof(o), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(r, d_r, sizeof(r), hipMemcpyDeviceToHost));
-    (void)hipFree(d_in); (void)hipFree(d_o); (void)hipFree(d_r);
-    if (memcmp(&o[0], &o[2], 2 * sizeof(double)) != 0)
-        return fail(HTM_ESTATE, "DPP wave_sum mismatch: %.17g vs %.17g / %.17g vs %.17g", o[0], o[2], o[1], o[3]);
-    // SURVEY.md §8a golden vector: first five rand_u() of rank 0
-    const double want[5] = {0.55850877496413887, 0.12064291047863662, 0.58295862120576203, 0.68001799611374736,
-                            0.45020412676967681};
-    for (int i = 0; i < 5; ++i)
-        if (o[4 + i] != want[i]) return fail(HTM_ESTATE, "device rand_u[%d] = %.17g, want %.17g", i, o[4 + i], want[i]);
-    if (o[13] != 0.0) return fail(HTM_ESTATE, "DPP wave_incl_scan disagrees with the serial prefix sum");
-    if (std::fabs(o[12] - 0.78381228502204603) > 1e-15)
-        return fail(HTM_ESTATE, "device rand_g = %.17g, want 0.78381228502204603", o[12]);
-    // jump-ahead generator == serial generator: one wave, several waves with a ragged tail, a ring wrap-around
-    const uint32_t seed0[4] = {0x4b88a366u, 0x1b11733cu, 0x097044b6u, 0x00676ea2u};   // rank-0 state
-    const uint32_t seed1[4] = {0x311ce1d7u, 0x6c840a86u, 0x28236c5fu, 0x019ea85du};   // rank 1
-    if ((rc = selftest_rawgen(seed0, 64, 0, 1 << 12))) return rc;
-    if ((rc = selftest_rawgen(seed0, 4096 * 3 + 64 * 5, 0, 1 << 14))) return rc;
-    if ((rc = selftest_rawgen(seed1, 1 << 16, (1 << 16) - 4096 - 192, 1 << 16))) return rc;
-    if ((rc = selftest_rawgen(seed1, 1 << 18, 12345 * 64, 1 << 18))) return rc;
-    return HTM_OK;
-}
 
 }  // extern "C"

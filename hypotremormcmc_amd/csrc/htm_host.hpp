@@ -1,0 +1,196 @@
+// htm_host.hpp -- what the host translation units of libhtm_hip.so share.  Internal: not installed, not part of the ABI
+// (include/htm_hip.h is).
+//
+//   htm_forward.hip        htm_forward_*, htm_device_*, the last-error string, the self-tests and htm_rng_jump
+//   htm_hip.hip            htm_chains_*, htm_comm_*: which loop a launch takes (launch_mcmc); no k_mcmc is instantiated there
+//   htm_loop_*.hip         one unit per family of chain-master loops: nothing but its rows of the kernel table below
+//                          (made with htm_loop_rows.hpp)
+//   htm_steps.hip          steps 1-4, 6 and the convergence diagnostics; touches neither htm_forward nor htm_chains
+//
+// Host code is plain C++17 + the HIP runtime: no torch, no third-party dependency.  There is no CPU fallback on purpose:
+// every entry point needs a usable HIP device and fails with HTM_ENODEVICE otherwise.
+#pragma once
+#include "htm_hip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <array>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "htm_kernels.hpp"
+#include "htm_stream.hpp"
+
+// (nothing declared here is exported from the shared library: the C ABI is)
+#pragma GCC visibility push(hidden)
+
+namespace htm {
+
+// Sets the calling thread's last-error string (htm_last_error: one object for the whole library, htm_forward.hip) and returns `code`.
+int fail(int code, const char *fmt, ...);
+
+#define HIPCHK(call)                                                                                   \
+    do {                                                                                               \
+        hipError_t e_ = (call);                                                                        \
+        if (e_ != hipSuccess)                                                                          \
+            return fail(HTM_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__,     \
+                        __LINE__);                                                                     \
+    } while (0)
+
+int use_device(int device);
+
+template <typename T>
+int dev_alloc(std::vector<void *> &pool, T **p, size_t n)
+{
+    void *q = nullptr;
+    HIPCHK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
+    pool.push_back(q);
+    *p = static_cast<T *>(q);
+    return HTM_OK;
+}
+
+template <typename T>
+int dev_upload(std::vector<void *> &pool, T **p, const T *src, size_t n)
+{
+    int rc = dev_alloc(pool, p, n);
+    if (rc) return rc;
+    if (n) HIPCHK(hipMemcpy(*p, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return HTM_OK;
+}
+
+inline int nch_for(int S) { return S <= 64 ? 1 : S <= 128 ? 2 : S <= 256 ? 4 : 0; }
+
+// ---- GF(2) algebra of mod_random's xorshift128 (reference src/mod_random.f90:63-71) ----------------------------
+// One step is linear in the 128 state bits (x | y << 32 | z << 64 | w << 96): state' = T * state.  Powers of T let
+// the device start any 64-draw segment of the stream directly (htm_stream.hpp, k_rawgen) and the host jump over any
+// number of draws (htm_rng_jump).  A matrix is stored as its 128 columns.
+struct Bits128 { uint32_t w[4]; };
+using Mat128 = std::array<Bits128, 128>;
+Bits128 gf2_matvec(const Mat128 &M, const Bits128 &v);
+const std::vector<Mat128> &xs_powers();      // P[k] = T^(2^k), k = 0..63
+
+}  // namespace htm
+
+struct htm_forward {
+    int device = 0, S = 0, E = 0, nch = 1;
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    htm::FwdDev dev{};
+    std::vector<void *> pool;
+    int n_wg = 0, epw = 1;
+    // scratch for the host-pointer entry points (one model)
+    double *d_hypo = nullptr, *d_tc = nullptr, *d_ac = nullptr, *d_scal = nullptr, *d_partial = nullptr;
+    double *d_syn = nullptr;
+    // scratch for batches
+    double *d_bpartial = nullptr; size_t bpartial_cap = 0;
+    double *d_bmodels = nullptr;  size_t bmodels_cap = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_wd = nullptr;
+    // packed per-event records of the specialised chain master (FwdDev::obs_pack), fp64 and fp32 forward: built when a chain set
+    // that can run that master is created on this forward (ensure_obs_pack), and for the other precision when it is switched to
+    void *d_pack64 = nullptr, *d_pack32 = nullptr;
+    bool pack_wanted = false;
+};
+
+struct htm_chains {
+    htm_forward *fwd = nullptr;
+    htm::ChainsDev dev{};
+    htm::Ctrl h_ctrl{};
+    std::vector<void *> pool;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t gexec = nullptr;
+    int pairs = 32;
+    int nw = 1;                // chain waves of k_step (one more wave is the RNG producer)
+    int ring_size = 512, wmax = 64;
+    size_t step_smem = 0;
+    int h_target = 0;          // host copy of the iteration target
+    int rec_len = 0;
+    std::vector<int32_t> lik_iter, lik_chain, smp_iter, smp_chain;
+    std::vector<double> lik_val, smp_data;
+    double last_device_us = 0.0;
+    int last_graph_launches = 0;
+    long long run_full0 = 0, run_part0 = 0, last_full = 0, last_part = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_wd = nullptr;
+    // random-stream service (htm_stream.hpp): produced on a side stream ahead of consumption
+    hipStream_t side = nullptr;
+    hipEvent_t ev_side = nullptr;
+    long long cap = 0;                         // ring capacity (positions)
+    long long n_raw = 0, n_tr = 0, n_rec = 0, n_hop = 0;   // positions produced per stage (host view)
+    long long spos_lo = 0, spos_hi = 0;        // bounds on the consumed position since the last sync
+    const double *pending_gathered = nullptr;  // lock-step: records whose swap the next k_step applies
+    double *d_gath_host = nullptr, *h_gath_pinned = nullptr;   // staging buffers of htm_chains_step_end_host
+    unsigned long long launch_seq = 0;         // k_mcmc launches of this chain set so far (the kernels' launch index)
+    bool persist = true;                       // k_mcmc (master + resident full-evaluation workers) vs k_step + k_full
+    bool flow = false;                         // single-rank loop on the free-running master (htm_flow.hpp) instead of step_body
+    bool flow_fixed = false;                   // ... and the job's shape allows its specialised instantiation (k_mcmc<.., 8>; flow_fixed_ok decides per launch)
+    bool last_fixed = false;                   // the latest MODE_RUN launch was that instantiation
+    bool wide = false;                         // more than kMaxChains chains: the loop with barriers at kMaxWideChains (k_mcmc_wide, k_step_wide)
+    int worker_cap = 250;                      // most worker blocks a launch takes (HTM_WORKER_CAP)
+    long blocks_fit = 0;                       // resident blocks of a k_mcmc launch on this device (htm_chains_share_gpu)
+    bool flow_lock = false;                    // lock-step ranks (MODE_LOCKRUN) on the free-running master too
+    int mb_blocks = 1;                         // master workgroups of the single-rank loop (> 1: k_mcmc<.., 7>, eight chains each)
+    bool pipe = false;                         // single-rank loop on the pipelined master (htm_pipe.hpp)
+    bool pipe_lock = false;                    // lock-step ranks (MODE_LOCKRUN) on it too
+    size_t pipe_smem = 0; int pipe_ring = 512; // its LDS size and stream window
+    bool ctrl_fresh = false;                   // h_ctrl is the device's control block as of an idle stream (no launch since it was read)
+    htm::ChainsDev dev_np{};                   // view for the non-persistent kernels (partial sums per k_full tile)
+    uint32_t init_state[4] = {0, 0, 0, 0};     // mod_random state at stream position 0
+    // in-kernel exchange of the swap records (persistent lock-step): this rank's inbox, the peers' inboxes as mapped here
+    unsigned long long *d_inbox = nullptr;
+    size_t inbox_bytes = 0;
+    std::vector<void *> peer_maps;             // hipIpcOpenMemHandle mappings to close
+    unsigned probe_calls = 0;                  // htm_chains_xchg_probe calls so far (part of the probe's tokens)
+    unsigned long long **d_outbox = nullptr;
+    bool xchg_ready = false;
+    htm::u32x4 *d_jump = nullptr;              // [kJumpLevels][128] columns of T^(64 * 2^b) (k_rawgen)
+    int gen_par = 0;                           // which half of StreamDev::gen holds the current generator state
+    double th[4] = {0, 0, 0, 0};
+};
+
+namespace htm {
+
+// ---- the functions that cross units -------------------------------------------------------------------------------
+// htm_forward.hip
+int launch_full(htm_forward *h, const FullJob &jb, int gy);
+int full_batch_dev(htm_forward *h, int n_models, const double *d_hypo, const double *d_tc, const double *d_vs,
+                   const double *d_ac, const double *d_qs, double *d_L);
+int ensure_obs_pack(htm_forward *h);
+// htm_hip.hip
+int launch_mcmc(htm_chains *hc, int mode, int target, const double *gathered);
+int launch_step(htm_chains *hc, int mode, int target, const double *gathered);
+
+// ---- the kernel table ---------------------------------------------------------------------------------------------
+// Every instantiation of a chain-master kernel is written down once, as a row of the loop unit that compiles it
+// (htm_loop_*.hip, through the row templates of htm_loop_rows.hpp): the kernel's address (attributes, occupancy), the block size it is launched with and its typed launch.
+// htm_hip.hip decides WHICH loop a launch takes (launch_mcmc) and looks the instantiation up here; a combination that
+// no unit builds gives nullptr, which the caller reports -- never another instantiation in its place.
+struct LoopLaunch {
+    dim3 grid, block;
+    size_t smem;
+    hipStream_t stream;
+    const FwdDev *f;
+    const ChainsDev *cs;
+    int mode, target;
+    const double *gathered;
+    int ring_size, wmax;
+    unsigned long long seq;      // the chain set's count of k_mcmc launches (k_step takes none)
+};
+struct LoopKernel { const void *fn; int threads; int (*launch)(const LoopLaunch &); };      // threads 0: the caller chooses (k_step)
+struct LoopRow { bool step, wide; int nch; bool fp32; int mk; LoopKernel k; };
+struct LoopRows { const LoopRow *rows; size_t n; };
+
+const LoopKernel *mcmc_kernel(int nch, bool fp32, int mk, bool wide);      // nullptr: not built
+const LoopKernel *step_kernel(int nch, bool fp32, bool wide);
+
+// one per loop unit, all searched by the two lookups above (htm_hip.hip)
+LoopRows loop_rows_free();         // MK 3, 8: the free-running master of a single rank, generic and specialised
+LoopRows loop_rows_lock();         // MK 4, 7: the free-running master in lock-step, and with several master workgroups
+LoopRows loop_rows_barrier();      // MK 0, 1, 2 and k_step: the loop with barriers
+LoopRows loop_rows_wide();         // k_mcmc_wide, k_step_wide: the loop with barriers for up to kMaxWideChains chains
+LoopRows loop_rows_pipe();         // MK 5, 6: the pipelined master
+
+}  // namespace htm
+
+#pragma GCC visibility pop

@@ -1,0 +1,23 @@
+// htm_loop_free.hip -- the free-running chain master of a single rank (htm_flow.hpp): MK 3, and MK 8 specialised on what the job fixes.
+// Nothing but this family's rows of the kernel table (htm_host.hpp): one line per instantiation, compiled here and nowhere else.
+#include "htm_loop_rows.hpp"
+
+namespace htm {
+
+LoopRows loop_rows_free()
+{
+    static const LoopRow rows[] = {
+        mcmc_row<1, false, 3>(),
+        mcmc_row<2, false, 3>(),
+        mcmc_row<0, false, 3>(),
+        mcmc_row<1, true, 3>(),
+        mcmc_row<2, true, 3>(),
+        mcmc_row<1, false, 8>(),
+        mcmc_row<2, false, 8>(),
+        mcmc_row<1, true, 8>(),
+        mcmc_row<2, true, 8>(),
+    };
+    return {rows, sizeof(rows) / sizeof(rows[0])};
+}
+
+}  // namespace htm

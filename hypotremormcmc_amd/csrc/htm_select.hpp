@@ -12,6 +12,8 @@
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
+#include "htm_device.hpp"      // wave_sum
+
 namespace htm {
 
 constexpr int kSelRanks = 3;      // il, im, iu

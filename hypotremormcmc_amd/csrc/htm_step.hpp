@@ -1833,30 +1833,4 @@ __device__ __forceinline__ void worker_body(FwRef f_, CsRef cs_, unsigned long l
     }
 }
 
-// Probe of the peer-mapped inboxes (htm_chains_xchg_probe): one wave writes a token record into every rank's inbox and
-// waits (bounded, `ticks` of the 100 MHz clock) until the tokens of all ranks have arrived in its own -- the same
-// stores, loads and scopes exchange_post / exchange_finish use, so a mapping whose writes are not visible to a polling kernel is
-// found at set-up, not inside a run.  Token tags have the top bit set: no iteration number ever matches them.
-__global__ __launch_bounds__(64) void k_xchg_probe(ChainsDev cs, unsigned token, unsigned long long ticks, int *result)
-{
-    const int lane = threadIdx.x, np = cs.n_procs, G = cs.xg;
-    const unsigned tag = 0x80000000u | token;
-    if (lane < 2)
-        for (int q = 0; q < np; ++q)
-            st_sys(ld_const(cs.outbox + q) + (size_t)(0 * np + cs.rank) * G + lane, ((unsigned long long)tag << 32) | (unsigned)cs.rank);
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    bool ok = false;
-    for (;;) {
-        bool mine = true;
-        for (int r = lane >> 1; r < np; r += 32) {
-            const unsigned long long v = ld_sys(cs.inbox + (size_t)r * G + (lane & 1));
-            mine = mine && (unsigned)(v >> 32) == tag && (unsigned)v == (unsigned)r;
-        }
-        if (__all(mine)) { ok = true; break; }
-        if (__builtin_amdgcn_s_memrealtime() - t0 > ticks) break;
-        __builtin_amdgcn_s_sleep(8);
-    }
-    if (lane == 0) *result = ok ? 1 : 0;
-}
-
 }  // namespace htm

@@ -1,0 +1,643 @@
+// htm_steps.hip -- the C ABI (include/htm_hip.h) of the pipeline's other steps: step 1 (htm_fft*, htm_convert*), steps 2 and 3
+// (htm_xcorr*, htm_measure_windows), step 4 (htm_select_regress), the convergence diagnostics (htm_diagnose*) and step 6
+// (htm_quantiles*).  None of them touches a forward or a chain set.
+#include "htm_host.hpp"
+
+#include <dlfcn.h>
+
+#include <chrono>
+#include <climits>
+#include <cmath>
+#include <cstdarg>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+
+#include "htm_convert.hpp"
+#include "htm_diag.hpp"
+#include "htm_select.hpp"
+#include "htm_xcorr.hpp"
+
+using namespace htm;
+
+extern "C" {
+
+int htm_quantiles_dev(int device, const double *d_samples, long n_mod, long n_par, long ld, const int ranks_1based[3],
+                      double *d_out, void *hip_stream)
+{
+    if (!d_samples || !d_out || !ranks_1based) return fail(HTM_EINVAL, "NULL argument");
+    if (n_mod < 1 || n_par < 1 || ld < n_par) return fail(HTM_EINVAL, "bad shape (n_mod %ld, n_par %ld, ld %ld)", n_mod, n_par, ld);
+    // the select kernels count rows in int (LDS counters, the slab histogram's atomics) and take int ranks
+    if (n_mod > INT_MAX) return fail(HTM_EINVAL, "n_mod %ld exceeds %d rows per column", n_mod, INT_MAX);
+    for (int r = 0; r < 3; ++r)
+        if (ranks_1based[r] < 1 || ranks_1based[r] > n_mod)
+            return fail(HTM_EINVAL, "rank %d outside 1..%ld (the reference would index outside its sorted column)", ranks_1based[r], n_mod);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
+    HIPCHK(hipSetDevice(device));
+    const dim3 grid((unsigned)((n_par + 63) / 64)), block(64 * kSelRG);
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const char *force = getenv("HTM_SELECT_SLABS");
+    // small sets: one launch, a column group per workgroup; large sets: row slabs over the whole chip, a launch per digit
+    long slabs = 1;
+    if ((double)n_mod * (double)n_par >= (double)(1 << 22)) {
+        slabs = std::max(1L, std::min((n_mod + 255) / 256, (long)(2048 / grid.x)));
+        slabs = std::min(slabs, 1024L);
+    }
+    if (force) slabs = std::max(1L, std::min(atol(force), std::min(n_mod, 65535L)));
+    if (slabs <= 1 && !force) {
+        hipLaunchKernelGGL(k_select, grid, block, 0, st, d_samples, n_mod, n_par, ld,
+                           ranks_1based[0] - 1, ranks_1based[1] - 1, ranks_1based[2] - 1, d_out);
+        HIPCHK(hipGetLastError());
+        return HTM_OK;
+    }
+    // workspace: three histograms, two prefix/remaining states (stream-ordered allocation keeps the call asynchronous)
+    const size_t hist_b = (size_t)grid.x * kSelHistPerGroup * sizeof(int);
+    const size_t st_b = (size_t)n_par * kSelRanks * sizeof(unsigned long long);
+    const size_t total = 3 * hist_b + 4 * st_b;
+    char *ws = nullptr;
+    bool async_alloc = hipMallocAsync(reinterpret_cast<void **>(&ws), total, st) == hipSuccess;
+    if (!async_alloc) {
+        (void)hipGetLastError();
+        if (hipMalloc(reinterpret_cast<void **>(&ws), total) != hipSuccess) return fail(HTM_EHIP, "hipMalloc of %zu bytes failed", total);
+    }
+    HIPCHK(hipMemsetAsync(ws, 0, total, st));
+    SelWork w;
+    for (int k = 0; k < 3; ++k) w.hist[k] = reinterpret_cast<int *>(ws + k * hist_b);
+    for (int k = 0; k < 2; ++k) {
+        w.prefix[k] = reinterpret_cast<unsigned long long *>(ws + 3 * hist_b + (2 * k) * st_b);
+        w.remaining[k] = reinterpret_cast<long *>(ws + 3 * hist_b + (2 * k + 1) * st_b);
+    }
+    const long slab_rows = (n_mod + slabs - 1) / slabs;
+    const dim3 grid2(grid.x, (unsigned)slabs);
+    int pass = 0;
+    for (int shift = 60; shift >= 0; shift -= 4, ++pass)
+        hipLaunchKernelGGL(k_select_pass, grid2, block, 0, st, d_samples, n_mod, n_par, ld, ranks_1based[0] - 1,
+                           ranks_1based[1] - 1, ranks_1based[2] - 1, shift, pass, slab_rows, w, (double *)nullptr);
+    hipLaunchKernelGGL(k_select_pass, grid, block, 0, st, d_samples, n_mod, n_par, ld, ranks_1based[0] - 1,
+                       ranks_1based[1] - 1, ranks_1based[2] - 1, -4, pass, slab_rows, w, d_out);
+    HIPCHK(hipGetLastError());
+    if (async_alloc) {
+        HIPCHK(hipFreeAsync(ws, st));
+    } else {
+        HIPCHK(hipStreamSynchronize(st));
+        (void)hipFree(ws);
+    }
+    return HTM_OK;
+}
+
+int htm_quantiles(int device, const double *samples, long n_mod, long n_par, const int ranks_1based[3], double *out)
+{
+    if (!samples || !out) return fail(HTM_EINVAL, "NULL argument");
+    if (n_mod < 1 || n_par < 1) return fail(HTM_EINVAL, "bad shape");
+    if (n_mod > INT_MAX) return fail(HTM_EINVAL, "n_mod %ld exceeds %d rows per column", n_mod, INT_MAX);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
+    HIPCHK(hipSetDevice(device));
+    double *d_x = nullptr, *d_o = nullptr;
+    const size_t nb = (size_t)n_mod * n_par * sizeof(double), ob = (size_t)n_par * 3 * sizeof(double);
+    if (hipMalloc(reinterpret_cast<void **>(&d_x), nb) != hipSuccess) return fail(HTM_EHIP, "hipMalloc of %zu bytes failed", nb);
+    if (hipMalloc(reinterpret_cast<void **>(&d_o), ob) != hipSuccess) { (void)hipFree(d_x); return fail(HTM_EHIP, "hipMalloc failed"); }
+    int rc = HTM_OK;
+    if (hipMemcpy(d_x, samples, nb, hipMemcpyHostToDevice) != hipSuccess) rc = fail(HTM_EHIP, "upload failed");
+    if (rc == HTM_OK) rc = htm_quantiles_dev(device, d_x, n_mod, n_par, n_par, ranks_1based, d_o, nullptr);
+    if (rc == HTM_OK && hipMemcpy(out, d_o, ob, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HTM_EHIP, "download failed");
+    (void)hipFree(d_x); (void)hipFree(d_o);
+    return rc;
+}
+
+// ---- convergence diagnostics (htm_diag.hpp) ---------------------------------------------------------------------
+namespace {
+// shapes both forms refuse before any device call
+int diag_check(long n_seq, long n_draws, long n_par, int max_lag)
+{
+    if (n_draws < 4 || n_seq < 1 || n_par < 1 || max_lag < 1)
+        return fail(HTM_EINVAL, "bad shape (n_seq %ld, n_draws %ld, n_par %ld, max_lag %d): need n_draws >= 4, the others >= 1",
+                    n_seq, n_draws, n_par, max_lag);
+    if (n_seq > INT_MAX / n_draws) return fail(HTM_EINVAL, "n_seq * n_draws = %ld * %ld exceeds %d rows", n_seq, n_draws, INT_MAX);
+    return HTM_OK;
+}
+}  // namespace
+
+int htm_diagnose_dev(int device, const double *d_samples, long n_seq, long n_draws, long n_par, long ld, int max_lag,
+                     double *d_out, double *d_acov, void *hip_stream)
+{
+    if (!d_samples || !d_out) return fail(HTM_EINVAL, "NULL argument");
+    int rc = diag_check(n_seq, n_draws, n_par, max_lag);
+    if (rc) return rc;
+    if (ld < n_par) return fail(HTM_EINVAL, "bad shape (n_par %ld, ld %ld)", n_par, ld);
+    const long n = n_draws / 2, S = 2 * n_seq;
+    const int L = (int)std::min(n - 1, (long)max_lag);
+    // lags per thread: HTM_DIAG_LAGS=16|32 picks the other instantiation (tests, tools/bench_diagnose.py)
+    int kb = 32;
+    if (const char *e = getenv("HTM_DIAG_LAGS")) {
+        kb = atoi(e);
+        if (kb != 16 && kb != 32) return fail(HTM_EINVAL, "HTM_DIAG_LAGS = %s: 16 or 32", e);
+    }
+    const long n_cg = (n_par + 63) / 64, n_blk = L / kb + 1, n_lagwg = (n_blk + kDiagLW - 1) / kDiagLW;
+    if (n_cg > INT_MAX / S || n_cg > INT_MAX / n_lagwg)
+        return fail(HTM_EINVAL, "n_par %ld, %ld split sequences, %d lags need more than 2^32 - 1 work-items in one launch", n_par, S, L + 1);
+    // slabs of split sequences: waves enough to fill the chip many times over, so that the last round of workgroups costs
+    // little; a workspace of at most 256 MiB or half the samples' size
+    long slabs = std::min(S, (65536 + n_cg * n_blk - 1) / (n_cg * n_blk));
+    const double lag_bytes = (double)(L + 1) * (double)n_par * sizeof(double);
+    const double ws_cap = std::max((double)(256L << 20), (double)(n_seq * n_draws) * (double)n_par * sizeof(double) / 2);
+    slabs = std::max(1L, std::min(slabs, (long)(ws_cap / lag_bytes)));
+    if (const char *e = getenv("HTM_DIAG_SLABS")) slabs = std::max(1L, std::min(atol(e), S));
+    const long seq_per_slab = (S + slabs - 1) / slabs;
+    slabs = (S + seq_per_slab - 1) / seq_per_slab;          // no empty slab
+    if (n_cg * n_lagwg > INT_MAX / slabs || n_cg * S * 64 * kDiagRG > 0xffffffffL || n_cg * n_lagwg * slabs * 64 * kDiagLW > 0xffffffffL)
+        return fail(HTM_EINVAL, "n_par %ld, %ld split sequences, %d lags need more than 2^32 - 1 work-items in one launch", n_par, S, L + 1);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
+    HIPCHK(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    // workspace: the means [S][n_par], the slabs' lag sums [slabs][L+1][n_par] (stream-ordered, as htm_quantiles_dev's)
+    const size_t mean_n = (size_t)S * n_par, part_n = (size_t)slabs * (L + 1) * n_par, total = (mean_n + part_n) * sizeof(double);
+    double *ws = nullptr;
+    bool async_alloc = hipMallocAsync(reinterpret_cast<void **>(&ws), total, st) == hipSuccess;
+    if (!async_alloc) {
+        (void)hipGetLastError();
+        if (hipMalloc(reinterpret_cast<void **>(&ws), total) != hipSuccess) return fail(HTM_EHIP, "hipMalloc of %zu bytes failed", total);
+    }
+    double *d_mean = ws, *d_part = ws + mean_n;
+    hipLaunchKernelGGL(k_diag_mean, dim3((unsigned)(n_cg * S)), dim3(64 * kDiagRG), 0, st, d_samples, n_draws, n, n_par, ld, n_cg, d_mean);
+    const dim3 grid((unsigned)(n_cg * n_lagwg * slabs)), block(64 * kDiagLW);
+    if (kb == 16)
+        hipLaunchKernelGGL(k_diag_acov<16>, grid, block, 0, st, d_samples, n_draws, n, n_par, ld, L, (int)S, (int)seq_per_slab, n_lagwg, n_cg, d_mean, d_part);
+    else
+        hipLaunchKernelGGL(k_diag_acov<32>, grid, block, 0, st, d_samples, n_draws, n, n_par, ld, L, (int)S, (int)seq_per_slab, n_lagwg, n_cg, d_mean, d_part);
+    hipLaunchKernelGGL(k_diag_finish, dim3((unsigned)n_cg), dim3(64), 0, st, d_part, d_mean, n, n_par, L, (int)S, (int)slabs,
+                       1.0 / std::log10((double)S * (double)n), d_out, d_acov);
+    HIPCHK(hipGetLastError());
+    if (async_alloc) {
+        HIPCHK(hipFreeAsync(ws, st));
+    } else {
+        HIPCHK(hipStreamSynchronize(st));
+        (void)hipFree(ws);
+    }
+    return HTM_OK;
+}
+
+int htm_diagnose(int device, const double *samples, long n_seq, long n_draws, long n_par, int max_lag, double *out, double *acov)
+{
+    if (!samples || !out) return fail(HTM_EINVAL, "NULL argument");
+    int rc = diag_check(n_seq, n_draws, n_par, max_lag);
+    if (rc) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
+    HIPCHK(hipSetDevice(device));
+    const long L = std::min(n_draws / 2 - 1, (long)max_lag);
+    const size_t xb = (size_t)n_seq * n_draws * n_par * sizeof(double), ob = (size_t)n_par * 4 * sizeof(double),
+                 ab = acov ? (size_t)(L + 1) * n_par * sizeof(double) : 0;
+    std::vector<void *> pool;
+    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
+    double *d_x = nullptr, *d_o = nullptr, *d_a = nullptr;
+    if ((rc = dev_upload(pool, &d_x, samples, xb / sizeof(double))) || (rc = dev_alloc(pool, &d_o, ob / sizeof(double))) ||
+        (acov && (rc = dev_alloc(pool, &d_a, ab / sizeof(double)))))
+        return done(rc);
+    rc = htm_diagnose_dev(device, d_x, n_seq, n_draws, n_par, n_par, max_lag, d_o, d_a, nullptr);
+    if (rc == HTM_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(HTM_EHIP, "the diagnostics kernels failed");
+    if (rc == HTM_OK && hipMemcpy(out, d_o, ob, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HTM_EHIP, "download failed");
+    if (rc == HTM_OK && acov && hipMemcpy(acov, d_a, ab, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HTM_EHIP, "download failed");
+    return done(rc);
+}
+
+int htm_select_regress(int device, int n_sta, int n_win, const double *sta_x, const double *sta_y, const double *sta_z,
+                       double z_guess, const double *t, const double *t_err, const double *a, const double *a_err, double *out)
+{
+    if (!sta_x || !sta_y || !sta_z || !t || !t_err || !a || !a_err || !out) return fail(HTM_EINVAL, "NULL argument");
+    if (n_sta < 3 || n_win < 1) return fail(HTM_EINVAL, "need n_sta >= 3 and n_win >= 1 (got %d, %d)", n_sta, n_win);
+    // a wave per window, four per workgroup: the dispatch packet holds the grid in work-items as a uint32_t
+    if (256L * ((n_win + 3L) / 4) > 0xffffffffL)
+        return fail(HTM_EINVAL, "n_win = %d windows need %ld work-items: more than one launch holds (2^32 - 1)", n_win,
+                    256L * ((n_win + 3L) / 4));
+    int rc = use_device(device);
+    if (rc) return rc;
+    std::vector<void *> pool;
+    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
+    const size_t n = (size_t)n_sta * n_win;
+    double *dx = nullptr, *dy = nullptr, *dz = nullptr, *dt = nullptr, *dte = nullptr, *da = nullptr, *dae = nullptr, *dout = nullptr;
+    if ((rc = dev_upload(pool, &dx, sta_x, n_sta)) || (rc = dev_upload(pool, &dy, sta_y, n_sta)) || (rc = dev_upload(pool, &dz, sta_z, n_sta)) ||
+        (rc = dev_upload(pool, &dt, t, n)) || (rc = dev_upload(pool, &dte, t_err, n)) || (rc = dev_upload(pool, &da, a, n)) ||
+        (rc = dev_upload(pool, &dae, a_err, n)) || (rc = dev_alloc(pool, &dout, 6 * (size_t)n_win))) return done(rc);
+    hipLaunchKernelGGL(k_regress, dim3((n_win + 3) / 4), dim3(256), 0, 0, n_sta, n_win, dx, dy, dz, z_guess, dt, dte, da, dae, dout);
+    if (hipGetLastError() != hipSuccess) return done(fail(HTM_EHIP, "k_regress launch failed"));
+    if (hipMemcpy(out, dout, 6 * (size_t)n_win * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return done(fail(HTM_EHIP, "download failed"));
+    return done(HTM_OK);
+}
+
+static int xcorr_check(long ld_env, long n_smp, int n_sta, int n, int n_step, int n_win, int pair0, int n_pairs, long ld_cc)
+{
+    if (n < 2 || n > kXcMaxN || n % 2) return fail(HTM_EINVAL, "window length n = %d: need an even n in 2..%d (the reference refuses odd n)", n, kXcMaxN);
+    if (n_sta < 2 || n_step < 1 || n_win < 1 || n_pairs < 1 || pair0 < 0)
+        return fail(HTM_EINVAL, "bad shape (n_sta %d, n_step %d, n_win %d, pair0 %d, n_pairs %d)", n_sta, n_step, n_win, pair0, n_pairs);
+    if ((long)pair0 + n_pairs > (long)n_sta * (n_sta - 1) / 2)
+        return fail(HTM_EINVAL, "pairs %d..%d outside the %d pairs of %d stations", pair0, pair0 + n_pairs - 1, n_sta * (n_sta - 1) / 2, n_sta);
+    if ((long)(n_win - 1) * n_step + n > n_smp || n_smp > ld_env)
+        return fail(HTM_EINVAL, "%d windows of %d samples every %d do not fit in %ld samples (row stride %ld)", n_win, n, n_step, n_smp, ld_env);
+    if (ld_cc < n_pairs) return fail(HTM_EINVAL, "ld_cc %ld < n_pairs %d", ld_cc, n_pairs);
+    if ((long)n_win * n_pairs > 0x7fffffffL) return fail(HTM_EINVAL, "n_win * n_pairs = %ld exceeds one launch", (long)n_win * n_pairs);
+    // the dispatch packet holds the grid in work-items as a uint32_t (hsa_kernel_dispatch_packet_t::grid_size_x)
+    if ((long)n_win * n_pairs * xc_threads(n) > 0xffffffffL)
+        return fail(HTM_EINVAL, "n_win * n_pairs * %d threads = %ld work-items exceed one launch (2^32 - 1)", xc_threads(n),
+                    (long)n_win * n_pairs * xc_threads(n));
+    return HTM_OK;
+}
+
+int htm_xcorr_dev(int device, const double *d_env, long ld_env, long n_smp, int n_sta, int n, int n_step, int n_win, int pair0,
+                  int n_pairs, double *d_cc, long ld_cc, double *d_cc_max, void *hip_stream)
+{
+    if (!d_env || !d_cc || !d_cc_max) return fail(HTM_EINVAL, "NULL argument");
+    int rc = xcorr_check(ld_env, n_smp, n_sta, n, n_step, n_win, pair0, n_pairs, ld_cc);
+    if (rc) return rc;
+    if ((rc = use_device(device))) return rc;
+    const int threads = xc_threads(n);
+    hipLaunchKernelGGL(k_xcorr, dim3((unsigned)((long)n_win * n_pairs)), dim3(threads), 2 * (size_t)n * sizeof(double),
+                       static_cast<hipStream_t>(hip_stream), d_env, ld_env, n_sta, n, n_step, n_win, pair0, n_pairs, d_cc, ld_cc,
+                       d_cc_max);
+    HIPCHK(hipGetLastError());
+    return HTM_OK;
+}
+
+int htm_xcorr(int device, const double *env, long n_smp, int n_sta, int n, int n_step, int n_win, int pair0, int n_pairs,
+              double *cc, double *cc_max)
+{
+    if (!env || !cc || !cc_max) return fail(HTM_EINVAL, "NULL argument");
+    int rc = xcorr_check(n_smp, n_smp, n_sta, n, n_step, n_win, pair0, n_pairs, n_pairs);
+    if (rc) return rc;
+    if ((rc = use_device(device))) return rc;
+    std::vector<void *> pool;
+    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
+    double *de = nullptr, *dc = nullptr, *dm = nullptr;
+    const size_t n_cc = (size_t)n_win * n * n_pairs, n_m = (size_t)n_win * n_pairs;
+    if ((rc = dev_upload(pool, &de, env, (size_t)n_sta * n_smp)) || (rc = dev_alloc(pool, &dc, n_cc)) || (rc = dev_alloc(pool, &dm, n_m)))
+        return done(rc);
+    if ((rc = htm_xcorr_dev(device, de, n_smp, n_smp, n_sta, n, n_step, n_win, pair0, n_pairs, dc, n_pairs, dm, nullptr))) return done(rc);
+    if (hipMemcpy(cc, dc, n_cc * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(cc_max, dm, n_m * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        return done(fail(HTM_EHIP, "k_xcorr or its download failed"));
+    return done(HTM_OK);
+}
+
+int htm_measure_windows(int device, int n_sta, int n, double dt, int n_det, const double *x, double *t, double *t_stdv,
+                        double *amp, double *amp_stdv)
+{
+    if (!x || !t || !t_stdv || !amp || !amp_stdv) return fail(HTM_EINVAL, "NULL argument");
+    if (n_sta < 3 || n < 2 || n > kXcMaxN || n_det < 0 || !(dt > 0.0))
+        return fail(HTM_EINVAL, "need n_sta >= 3, n in 2..%d, n_det >= 0, dt > 0 (got %d, %d, %d, %g)", kXcMaxN, n_sta, n, n_det, dt);
+    if (n_det == 0) return HTM_OK;
+    int rc = use_device(device);
+    if (rc) return rc;
+    std::vector<void *> pool;
+    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
+    // windows in launches of at most HTM_MEASURE_MB MiB of inputs and workspace (default 256: every window of a usual
+    // run in one launch; at least one window per launch)
+    const size_t per_win = ((size_t)n_sta * n + (size_t)n_sta * n_sta + 5 * (size_t)n_sta) * sizeof(double);
+    const char *mb_env = getenv("HTM_MEASURE_MB");
+    const double mb = mb_env ? atof(mb_env) : 256.0;
+    const size_t budget = mb > 0.0 ? (size_t)std::min(mb * 1048576.0, 1e18) : 0;
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_det, budget / per_win));
+    double *dx = nullptr, *dws = nullptr, *dout = nullptr;
+    if ((rc = dev_alloc(pool, &dx, (size_t)chunk * n_sta * n)) || (rc = dev_alloc(pool, &dws, (size_t)chunk * ((size_t)n_sta * n_sta + n_sta))) ||
+        (rc = dev_alloc(pool, &dout, 4 * (size_t)chunk * n_sta)))
+        return done(rc);
+    double *outs[4] = {t, t_stdv, amp, amp_stdv};
+    for (int w0 = 0; w0 < n_det; w0 += chunk) {
+        const int nw = std::min(chunk, n_det - w0);
+        const size_t ns = (size_t)nw * n_sta;
+        HIPCHK(hipMemcpy(dx, x + (size_t)w0 * n_sta * n, ns * n * sizeof(double), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_measure, dim3(nw), dim3(xc_threads(n)), 2 * (size_t)n * sizeof(double), 0, dx, n_sta, n, dt, nw, dws,
+                           dout, dout + (size_t)chunk * n_sta, dout + 2 * (size_t)chunk * n_sta, dout + 3 * (size_t)chunk * n_sta);
+        if (hipGetLastError() != hipSuccess) return done(fail(HTM_EHIP, "k_measure launch failed"));
+        for (int k = 0; k < 4; ++k)
+            if (hipMemcpy(outs[k] + (size_t)w0 * n_sta, dout + k * (size_t)chunk * n_sta, ns * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+                return done(fail(HTM_EHIP, "k_measure or its download failed"));
+    }
+    return done(HTM_OK);
+}
+
+}  // extern "C"
+
+// ---- step 1: FFT plans (htm_fft.hpp) and the convert pipeline (htm_convert.hpp) ---------------------------------------
+namespace {
+
+struct FftPlan {
+    long n = 0;
+    std::vector<int> radix;          // Stockham passes (empty for n = 1 and for Bluestein lengths)
+    std::vector<long> tw_off;        // first twiddle of each pass in d_tw
+    double2 *d_tw = nullptr;
+    long m = 0;                      // Bluestein: inner power-of-two length (0: Stockham)
+    const FftPlan *inner = nullptr;
+    double2 *d_chirp = nullptr, *d_b = nullptr;
+};
+
+std::mutex g_fft_mu;
+std::map<std::pair<int, long>, FftPlan *> g_fft_plans;   // per (device, n); kept for the life of the process
+
+bool fft_factor(long n, std::vector<int> &r)
+{
+    r.clear();
+    while (n % 4 == 0) { r.push_back(4); n /= 4; }
+    if (n % 2 == 0) { r.push_back(2); n /= 2; }
+    for (int p : {3, 5, 7})
+        while (n % p == 0) { r.push_back(p); n /= p; }
+    return n == 1;
+}
+
+long fft_inner_len(long n)
+{
+    long m = 1;
+    while (m < 2 * n - 1) m <<= 1;
+    return m;
+}
+
+// complex elements of workspace fft_run needs for `rows` rows of n, and the most work-items one of its launches takes
+size_t fft_ws_elems(long n, long rows)
+{
+    std::vector<int> r;
+    return fft_factor(n, r) ? (size_t)rows * n : 2 * (size_t)rows * fft_inner_len(n);
+}
+long fft_max_items(long n, long rows)
+{
+    std::vector<int> r;
+    return fft_factor(n, r) ? rows * n : rows * fft_inner_len(n);
+}
+
+dim3 fft_grid(long total) { return dim3((unsigned)((total + kFftThreads - 1) / kFftThreads)); }
+
+int fft_run(const FftPlan &p, const double2 *in, long ld_in, double2 *out, long ld_out, long rows, int sign, double2 *ws,
+            hipStream_t st)
+{
+    const long n = p.n;
+    if (p.m == 0) {
+        const int P = (int)p.radix.size();
+        if (P == 0) {
+            if (in != out) hipLaunchKernelGGL(k_fft_copy, fft_grid(rows * n), dim3(kFftThreads), 0, st, in, ld_in, out, ld_out, n, rows * n);
+            HIPCHK(hipGetLastError());
+            return HTM_OK;
+        }
+        // the last pass writes `out`; in place with an odd pass count the passes end in ws and a copy follows
+        const bool extra = in == out && P % 2 == 1;
+        const double2 *src = in;
+        long lds = ld_in, ns = 1;
+        for (int i = 0; i < P; ++i) {
+            const bool to_out = extra ? (i % 2 == 1) : ((P - 1 - i) % 2 == 0);
+            double2 *dst = to_out ? out : ws;
+            const long ldd = to_out ? ld_out : n;
+            const int R = p.radix[i];
+            const long total = rows * (n / R);
+            const double2 *tw = p.d_tw + p.tw_off[i];
+            switch (R) {
+            case 2: hipLaunchKernelGGL(k_fft_pass<2>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n, (int)ns, tw, sign, total); break;
+            case 3: hipLaunchKernelGGL(k_fft_pass<3>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n, (int)ns, tw, sign, total); break;
+            case 4: hipLaunchKernelGGL(k_fft_pass<4>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n, (int)ns, tw, sign, total); break;
+            case 5: hipLaunchKernelGGL(k_fft_pass<5>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n, (int)ns, tw, sign, total); break;
+            default: hipLaunchKernelGGL(k_fft_pass<7>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n, (int)ns, tw, sign, total); break;
+            }
+            src = dst; lds = ldd; ns *= R;
+        }
+        if (extra) hipLaunchKernelGGL(k_fft_copy, fft_grid(rows * n), dim3(kFftThreads), 0, st, ws, n, out, ld_out, n, rows * n);
+        HIPCHK(hipGetLastError());
+        return HTM_OK;
+    }
+    // Bluestein: backward(x) = conj(forward(conj(x))); ws holds a [rows][m] and the inner transforms' own rows * m
+    const long m = p.m;
+    double2 *a = ws, *ws2 = ws + (size_t)rows * m;
+    hipLaunchKernelGGL(k_blue_pre, fft_grid(rows * m), dim3(kFftThreads), 0, st, in, ld_in, a, n, m, p.d_chirp, sign > 0 ? 1 : 0, rows * m);
+    int rc = fft_run(*p.inner, a, m, a, m, rows, -1, ws2, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_blue_mul, fft_grid(rows * m), dim3(kFftThreads), 0, st, a, m, p.d_b, rows * m);
+    if ((rc = fft_run(*p.inner, a, m, a, m, rows, +1, ws2, st))) return rc;
+    hipLaunchKernelGGL(k_blue_post, fft_grid(rows * n), dim3(kFftThreads), 0, st, a, m, out, ld_out, n, p.d_chirp, sign > 0 ? 1 : 0, rows * n);
+    HIPCHK(hipGetLastError());
+    return HTM_OK;
+}
+
+const long double kPiL = 3.141592653589793238462643383279502884L;
+
+// the plan of length n on the current device, built once (g_fft_mu held); tables in long double, rounded once
+int fft_plan_locked(int device, long n, const FftPlan **out)
+{
+    auto it = g_fft_plans.find(std::make_pair(device, n));
+    if (it != g_fft_plans.end()) { *out = it->second; return HTM_OK; }
+    std::unique_ptr<FftPlan> p(new FftPlan);
+    p->n = n;
+    if (fft_factor(n, p->radix)) {
+        // tw[off + k (R-1) + r - 1] = exp(-2 pi i r k / (ns R)), k < ns
+        std::vector<double2> tw;
+        long ns = 1;
+        for (int R : p->radix) {
+            p->tw_off.push_back((long)tw.size());
+            for (long k = 0; k < ns; ++k)
+                for (int r = 1; r < R; ++r) {
+                    const long double a = -2.0L * kPiL * (long double)(r * k) / (long double)(ns * R);
+                    tw.push_back(make_double2((double)cosl(a), (double)sinl(a)));
+                }
+            ns *= R;
+        }
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&p->d_tw), std::max<size_t>(1, tw.size()) * sizeof(double2)));
+        if (!tw.empty()) HIPCHK(hipMemcpy(p->d_tw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
+    } else {
+        p->radix.clear();
+        p->m = fft_inner_len(n);
+        const long m = p->m;
+        int rc = fft_plan_locked(device, m, &p->inner);
+        if (rc) return rc;
+        // chirp w[j] = exp(-pi i (j^2 mod 2n) / n); b = conj(w) at j and m - j, divided by m (a power of two: exact)
+        std::vector<double2> w(n), b(m, make_double2(0.0, 0.0));
+        for (long j = 0; j < n; ++j) {
+            const long q = (long)(((unsigned long long)j * (unsigned long long)j) % (unsigned long long)(2 * n));
+            const long double a = -kPiL * (long double)q / (long double)n;
+            const long double c = cosl(a), s = sinl(a);
+            w[j] = make_double2((double)c, (double)s);
+            b[j] = make_double2((double)(c / m), (double)(-s / m));
+            if (j) b[m - j] = b[j];
+        }
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&p->d_chirp), n * sizeof(double2)));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&p->d_b), m * sizeof(double2)));
+        HIPCHK(hipMemcpy(p->d_chirp, w.data(), n * sizeof(double2), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(p->d_b, b.data(), m * sizeof(double2), hipMemcpyHostToDevice));
+        double2 *tmp = nullptr;
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&tmp), m * sizeof(double2)));
+        rc = fft_run(*p->inner, p->d_b, m, p->d_b, m, 1, -1, tmp, nullptr);
+        const hipError_t e = hipDeviceSynchronize();
+        (void)hipFree(tmp);
+        if (rc) return rc;
+        if (e != hipSuccess) return fail(HTM_EHIP, "Bluestein table of n = %ld: %s", n, hipGetErrorString(e));
+    }
+    *out = p.get();
+    g_fft_plans[std::make_pair(device, n)] = p.release();
+    return HTM_OK;
+}
+
+int fft_plan(int device, long n, const FftPlan **out)
+{
+    std::lock_guard<std::mutex> lk(g_fft_mu);
+    return fft_plan_locked(device, n, out);
+}
+
+// stream-ordered workspace, as htm_quantiles_dev allocates it
+struct AsyncBuf {
+    void *p = nullptr;
+    hipStream_t st = nullptr;
+    bool async = false;
+    int alloc(size_t bytes, hipStream_t s)
+    {
+        st = s;
+        async = hipMallocAsync(&p, std::max<size_t>(bytes, 1), st) == hipSuccess;
+        if (!async) {
+            (void)hipGetLastError();
+            if (hipMalloc(&p, std::max<size_t>(bytes, 1)) != hipSuccess) { p = nullptr; return fail(HTM_EHIP, "hipMalloc of %zu bytes failed", bytes); }
+        }
+        return HTM_OK;
+    }
+    int release()
+    {
+        if (!p) return HTM_OK;
+        void *q = p;
+        p = nullptr;
+        if (async) { HIPCHK(hipFreeAsync(q, st)); return HTM_OK; }
+        HIPCHK(hipStreamSynchronize(st));
+        (void)hipFree(q);
+        return HTM_OK;
+    }
+};
+
+int fft_check(const void *in, long ld_in, const void *out, long ld_out, long n, long batch, int direction)
+{
+    if (!in || !out) return fail(HTM_EINVAL, "NULL argument");
+    if (n < 1 || n > kFftMaxN) return fail(HTM_EINVAL, "FFT length n = %ld outside 1..%ld", n, kFftMaxN);
+    if (batch < 1 || ld_in < n || ld_out < n) return fail(HTM_EINVAL, "bad shape (batch %ld, ld_in %ld, ld_out %ld, n %ld)", batch, ld_in, ld_out, n);
+    if (direction != -1 && direction != 1) return fail(HTM_EINVAL, "direction must be -1 (forward) or +1 (backward), got %d", direction);
+    if (in == out && ld_in != ld_out) return fail(HTM_EINVAL, "in place needs ld_in == ld_out");
+    if (fft_max_items(n, batch) > 0xffffffffL)
+        return fail(HTM_EINVAL, "%ld rows of n = %ld need %ld work-items in one launch (more than 2^32 - 1)", batch, n, fft_max_items(n, batch));
+    return HTM_OK;
+}
+
+// step 1 geometry: index of the last segment, and the kept range [start, end) of stream samples of segment j
+long cv_last(long n_total, int n) { return (n_total - n) / (n / 2) + 1; }
+long cv_start(long j, int n) { return j == 0 ? 0 : j * (n / 2) + n / 4; }
+long cv_end(long j, long n_total, int n) { return j == cv_last(n_total, n) ? n_total : j * (n / 2) + n - n / 4; }
+long ceil_div(long a, long b) { return (a + b - 1) / b; }
+
+int cv_check(long n_total, int n, int n_fac, int h, const int k_band[4], long j0, long j1)
+{
+    if (!k_band) return fail(HTM_EINVAL, "NULL argument");
+    if (n < 4 || n % 4 || n > kFftMaxN) return fail(HTM_EINVAL, "n = %d: need a multiple of 4 in 4..%ld", n, kFftMaxN);
+    if (n_total < n) return fail(HTM_EINVAL, "data length is not enough in queue (N = %ld < n = %d)", n_total, n);
+    if (n_fac < 1 || n_fac > n / 2) return fail(HTM_EINVAL, "n_fac = %d: need 1 <= n_fac <= n/2 = %d", n_fac, n / 2);
+    if (h < 0 || h > kCvMaxH || 2L * h > n) return fail(HTM_EINVAL, "half width h = %d: need 0 <= h <= %d and 2h <= n = %d", h, kCvMaxH, n);
+    if (k_band[0] < 0 || k_band[0] > k_band[1] || k_band[1] > k_band[2] || k_band[2] > k_band[3])
+        return fail(HTM_EINVAL, "band bins must satisfy 0 <= k1 <= k2 <= k3 <= k4 (got %d %d %d %d)", k_band[0], k_band[1], k_band[2], k_band[3]);
+    const long last = cv_last(n_total, n);
+    if (j0 < 0 || j0 > j1 || j1 > last) return fail(HTM_EINVAL, "segments %ld..%ld outside 0..%ld", j0, j1, last);
+    const long S = j1 - j0 + 1;
+    if (std::max(fft_max_items(n, 2 * S), 2 * S * (long)n) > 0xffffffffL)
+        return fail(HTM_EINVAL, "%ld segments of n = %d need more than 2^32 - 1 work-items in one launch", S, n);
+    return HTM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int htm_fft_dev(int device, const double *d_in, long ld_in, double *d_out, long ld_out, long n, long batch, int direction,
+                void *hip_stream)
+{
+    int rc = fft_check(d_in, ld_in, d_out, ld_out, n, batch, direction);
+    if (rc) return rc;
+    if ((rc = use_device(device))) return rc;
+    const FftPlan *p = nullptr;
+    if ((rc = fft_plan(device, n, &p))) return rc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    AsyncBuf ws;
+    if ((rc = ws.alloc(fft_ws_elems(n, batch) * sizeof(double2), st))) return rc;
+    rc = fft_run(*p, reinterpret_cast<const double2 *>(d_in), ld_in, reinterpret_cast<double2 *>(d_out), ld_out, batch, direction, static_cast<double2 *>(ws.p), st);
+    const int rc2 = ws.release();
+    return rc ? rc : rc2;
+}
+
+int htm_fft(int device, const double *in, long ld_in, double *out, long ld_out, long n, long batch, int direction)
+{
+    int rc = fft_check(in, ld_in, out, ld_out, n, batch, direction);
+    if (rc) return rc;
+    if ((rc = use_device(device))) return rc;
+    std::vector<void *> pool;
+    auto done = [&](int code) { for (void *q : pool) (void)hipFree(q); return code; };
+    const size_t ni = 2 * ((size_t)(batch - 1) * ld_in + n), no = 2 * ((size_t)(batch - 1) * ld_out + n);
+    double *di = nullptr, *dout = nullptr;
+    if ((rc = dev_upload(pool, &dout, out, no))) return done(rc);      // keeps the padding between strided rows
+    if (in == out) di = dout;
+    else if ((rc = dev_upload(pool, &di, in, ni))) return done(rc);
+    if ((rc = htm_fft_dev(device, di, ld_in, dout, ld_out, n, batch, direction, nullptr))) return done(rc);
+    if (hipMemcpy(out, dout, no * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return done(fail(HTM_EHIP, "FFT or its download failed"));
+    return done(HTM_OK);
+}
+
+int htm_convert_dev(int device, const float *d_x1, const float *d_x2, long n_total, int n, int n_fac, int h,
+                    const int k_band[4], double fac1, double fac2, long j0, long j1, double *d_out, void *hip_stream)
+{
+    if (!d_x1 || !d_x2 || !d_out) return fail(HTM_EINVAL, "NULL argument");
+    int rc = cv_check(n_total, n, n_fac, h, k_band, j0, j1);
+    if (rc) return rc;
+    if ((rc = use_device(device))) return rc;
+    const FftPlan *p = nullptr;
+    if ((rc = fft_plan(device, n, &p))) return rc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const long S = j1 - j0 + 1, n2 = n / 2, last = cv_last(n_total, n);
+    const long n_valid = std::min(n_total, j1 * n2 + n) - j0 * n2;
+    // workspace: z [S][n] (later the first smoothing [2S][n] doubles), y [2S][n], the FFT's own, 4S coefficients
+    const size_t zb = (size_t)S * n * sizeof(double2), yb = 2 * zb, fb = fft_ws_elems(n, 2 * S) * sizeof(double2);
+    AsyncBuf ws;
+    if ((rc = ws.alloc(zb + yb + fb + 4 * S * sizeof(double), st))) return rc;
+    char *base = static_cast<char *>(ws.p);
+    double2 *z = reinterpret_cast<double2 *>(base), *y = reinterpret_cast<double2 *>(base + zb);
+    double2 *fw = reinterpret_cast<double2 *>(base + zb + yb);
+    double *coef = reinterpret_cast<double *>(base + zb + yb + fb);
+    const long sn = S * n;
+    hipLaunchKernelGGL(k_cv_detrend, dim3((unsigned)S), dim3(kCvSumThreads), 0, st, d_x1, d_x2, n_valid, n, coef);
+    hipLaunchKernelGGL(k_cv_pack, fft_grid(sn), dim3(kCvThreads), 0, st, d_x1, d_x2, n_valid, n, coef, z, sn);
+    if ((rc = fft_run(*p, z, n, z, n, S, -1, fw, st))) { ws.release(); return rc; }
+    const int4 kb = make_int4(k_band[0], k_band[1], k_band[2], k_band[3]);
+    hipLaunchKernelGGL(k_cv_spectrum, fft_grid(sn), dim3(kCvThreads), 0, st, z, n, kb, y, sn);
+    if ((rc = fft_run(*p, y, n, y, n, 2 * S, +1, fw, st))) { ws.release(); return rc; }
+    const int tiles1 = (int)ceil_div(n, kCvTile), tiles2 = (int)ceil_div(n - n / 4, kCvTile);
+    const size_t lds = 2 * (size_t)(kCvTile + 2 * h) * sizeof(double);
+    double *e1 = reinterpret_cast<double *>(z);
+    const long k_base = ceil_div(cv_start(j0, n), n_fac);
+    hipLaunchKernelGGL(k_cv_smooth<false>, dim3((unsigned)(S * tiles1)), dim3(kCvThreads), lds, st, y, (const double *)nullptr, e1, n, h,
+                       tiles1, j0, last, n_total, n_fac, k_base, fac1, fac2, (double *)nullptr);
+    hipLaunchKernelGGL(k_cv_smooth<true>, dim3((unsigned)(S * tiles2)), dim3(kCvThreads), lds, st, (const double2 *)nullptr, e1,
+                       (double *)nullptr, n, h, tiles2, j0, last, n_total, n_fac, k_base, fac1, fac2, d_out);
+    const hipError_t e = hipGetLastError();
+    rc = ws.release();
+    if (e != hipSuccess) return fail(HTM_EHIP, "step-1 kernels failed to launch: %s", hipGetErrorString(e));
+    return rc;
+}
+
+int htm_convert(int device, const float *x1, const float *x2, long n_total, int n, int n_fac, int h, const int k_band[4],
+                double fac1, double fac2, long j0, long j1, double *out)
+{
+    if (!x1 || !x2 || !out) return fail(HTM_EINVAL, "NULL argument");
+    int rc = cv_check(n_total, n, n_fac, h, k_band, j0, j1);
+    if (rc) return rc;
+    if ((rc = use_device(device))) return rc;
+    std::vector<void *> pool;
+    auto done = [&](int code) { for (void *q : pool) (void)hipFree(q); return code; };
+    const long n2 = n / 2;
+    const size_t n_valid = (size_t)(std::min(n_total, j1 * n2 + n) - j0 * n2);
+    const size_t n_out = (size_t)(ceil_div(cv_end(j1, n_total, n), n_fac) - ceil_div(cv_start(j0, n), n_fac));
+    float *d1 = nullptr, *d2 = nullptr;
+    double *dout = nullptr;
+    if ((rc = dev_upload(pool, &d1, x1, n_valid)) || (rc = dev_upload(pool, &d2, x2, n_valid)) || (rc = dev_alloc(pool, &dout, n_out)))
+        return done(rc);
+    if ((rc = htm_convert_dev(device, d1, d2, n_total, n, n_fac, h, k_band, fac1, fac2, j0, j1, dout, nullptr))) return done(rc);
+    if (hipMemcpy(out, dout, n_out * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return done(fail(HTM_EHIP, "step-1 kernels or their download failed"));
+    return done(HTM_OK);
+}
+
+}  // extern "C"

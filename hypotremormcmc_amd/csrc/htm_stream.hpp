@@ -45,101 +45,13 @@ __device__ __forceinline__ void jump_apply(uint32_t (&s)[4], const u32x4 *J)
     s[0] = a0; s[1] = a1; s[2] = a2; s[3] = a3;
 }
 
+// The kernels themselves are defined in htm_chains_kernels.hpp, which one unit includes.  These two are launched from the
+// self-test's unit as well:
 // grid = ceil(n / 4096) workgroups of ONE wave; n a multiple of 64.  gen_in: state after the last produced draw
 // (read by every wave); gen_out: the state after this call's last draw (a different buffer: no race with the readers).
-__global__ __launch_bounds__(64) void k_rawgen(StreamDev sd, long long start, int n, const u32x4 *jump,
-                                               const uint32_t *gen_in, uint32_t *gen_out)
-{
-    __shared__ uint32_t tile[64 * 65];
-    const int lane = threadIdx.x;
-    const int n_seg = n >> 6;
-    const int g = blockIdx.x * 64 + lane;                 // this lane's segment
-    uint32_t s[4] = {gen_in[0], gen_in[1], gen_in[2], gen_in[3]};
-    // bits 6.. of g are uniform over the wave (scalar branch), bits 0..5 differ by lane (predicated)
-    for (int b = 6; b < kJumpLevels; ++b)
-        if ((blockIdx.x >> (b - 6)) & 1) jump_apply(s, jump + (size_t)b * 128);
-    for (int b = 0; b < 6; ++b) {
-        uint32_t t[4] = {s[0], s[1], s[2], s[3]};
-        jump_apply(t, jump + (size_t)b * 128);
-        if ((lane >> b) & 1) { s[0] = t[0]; s[1] = t[1]; s[2] = t[2]; s[3] = t[3]; }
-    }
-    uint32_t x = s[0], y = s[1], z = s[2], w = s[3];
-#pragma unroll
-    for (int k = 0; k < 64; ++k) tile[lane * 65 + k] = xs128_next(x, y, z, w);
-    if (g == n_seg - 1) { gen_out[0] = x; gen_out[1] = y; gen_out[2] = z; gen_out[3] = w; }
-    __syncthreads();
-    const int seg0 = blockIdx.x * 64;
-    for (int k = 0; k < 64 && seg0 + k < n_seg; ++k)
-        sd.raw[(start + (long long)(seg0 + k) * 64 + lane) & sd.mask] = tile[k * 65 + lane];
-}
-
+__global__ void k_rawgen(StreamDev sd, long long start, int n, const u32x4 *jump, const uint32_t *gen_in, uint32_t *gen_out);
 // the same stream drawn serially by one lane (htm_selftest compares the two)
-__global__ void k_rawgen_serial(uint32_t *out, int n, const uint32_t *gen_in, uint32_t *gen_out)
-{
-    uint32_t x = gen_in[0], y = gen_in[1], z = gen_in[2], w = gen_in[3];
-    for (int k = 0; k < n; ++k) out[k] = xs128_next(x, y, z, w);
-    gen_out[0] = x; gen_out[1] = y; gen_out[2] = z; gen_out[3] = w;
-}
+__global__ void k_rawgen_serial(uint32_t *out, int n, const uint32_t *gen_in, uint32_t *gen_out);
 
-__global__ __launch_bounds__(256) void k_stream_tr(StreamDev sd, long long start, long long end)
-{
-    const long long p = start + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= end) return;
-    const uint32_t r0 = sd.raw[p & sd.mask], r1 = sd.raw[(p + 1) & sd.mask];
-    const double u = u_of(r0);
-    sd.U[p & sd.mask] = u;
-    sd.LOGU[p & sd.mask] = log(u);
-    sd.G[p & sd.mask] = g_of(r0, r1);
-}
-
-// cls_mcmc.f90:134-165: a_select, then (id,) (icmp,) then the two draws of rand_g, then the judge's rand_u
-__global__ __launch_bounds__(256) void k_stream_rec(StreamDev sd, long long start, long long end, double th1,
-                                                    double th2, double th3, double th4, int S, int E,
-                                                    int n_procs, int n_chains)
-{
-    const long long p = start + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= end) return;
-    const long long M = sd.mask;
-    const double a = sd.U[p & M], u1 = sd.U[(p + 1) & M], u2 = sd.U[(p + 2) & M];
-    int type, idx, evt = -999, goff;
-    if (a < th1) { type = 1; idx = 0; goff = 1; }
-    else if (a < th2) { type = 2; idx = (int)(u1 * S); goff = 2; }
-    else if (a < th3) { type = 3; idx = 0; goff = 1; }
-    else if (a < th4) { type = 4; idx = (int)(u1 * S); goff = 2; }
-    else {
-        const int id = (int)(u1 * E) + 1;
-        const int icmp = (int)(u2 * 3);
-        idx = 3 * id - icmp - 1; type = 5 + icmp; evt = id; goff = 3;
-    }
-    const long long gpos = p + goff, jpos = gpos + 2;
-    sd.dec[p & M] = make_int4(type, idx, evt, goff + 3);     // draws if prior_ok: ..., g(2), r
-    sd.pg[p & M] = sd.G[gpos & M];
-    sd.pr[p & M] = sd.U[jpos & M];
-    sd.plogr[p & M] = sd.LOGU[jpos & M];
-    // select_pair (cls_parallel.f90:226-230) if it started at p: i1, then i2 redrawn until it differs
-    int i1 = -1, i2 = -1, used = -1;
-    if (n_procs * n_chains > 1) {
-        i1 = (int)(a * n_procs * n_chains);
-        for (int k = 1; k <= 12; ++k) {
-            i2 = (int)(sd.U[(p + k) & M] * n_procs * n_chains);
-            if (i2 != i1) { used = k + 1; break; }
-        }
-    }
-    sd.sw[p & M] = make_int4(i1, i2, used, 0);
-}
-
-__global__ __launch_bounds__(256) void k_stream_hop(StreamDev sd, long long start, long long end)
-{
-    const long long p = start + (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= end) return;
-    long long h = p;
-#pragma unroll
-    for (int k = 0; k < kHops; ++k) {
-        h += sd.dec[h & sd.mask].w;
-        sd.hop[(p & sd.mask) * kHops + k] = (int)(h - p);      // stored relative to p
-    }
-}
-
-__global__ void k_publish(long long *dst, long long v) { *dst = v; }
 
 }  // namespace htm

@@ -44,6 +44,17 @@ def test_no_cpu_fallback_without_device():
     with pytest.raises(_lib.HtmError, match="no HIP device|CPU fallback"):
         Forward(n_sta=3, n_events=2, sta_x=np.zeros(3), sta_y=np.zeros(3), sta_z=np.zeros(3), obs=obs)
     assert lib.htm_selftest(0) == -2       # HTM_ENODEVICE
+    # The library is built from several translation units with ONE last-error string behind htm_last_error(): a failure raised
+    # in each host unit (forward with the self-test, steps, chains) is what it returns next, whichever unit failed before.
+    last = lambda: lib.htm_last_error().decode()
+    assert "no HIP device" in last()                                   # the self-test, just above
+    assert lib.htm_device_count(None) == -1 and last() == "n is NULL"  # HTM_EINVAL from a forward-unit entry point
+    x = np.zeros(64, dtype=np.float32).ctypes.data_as(C.POINTER(C.c_float))
+    out = np.zeros(64).ctypes.data_as(C.POINTER(C.c_double))
+    assert lib.htm_convert(0, x, x, 64, 16, 1, 2, None, 1.0, 1.0, 0, 0, out) == -1      # step 1 with a NULL band
+    assert last() == "NULL argument"
+    assert lib.htm_chains_run(None, 1) == -1 and last() == "NULL handle"
+    assert lib.htm_selftest(0) == -2 and "no HIP device" in last()
 
 
 def test_product_package_never_imports_the_oracle():

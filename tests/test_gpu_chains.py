@@ -344,6 +344,10 @@ _SHAPES = [
     (100, 16, 2, 1, 16, 900, {"use_amp": "F", "step_size_z": 6.0}),
     (1000, 64, 8, 1, 17, 700, {"step_size_z": 8.0, "n_interval": 2}),      # the bench shape with many rejections
     (40, 64, 6, 1, 18, 900, {"solve_t_corr": "F", "solve_a_corr": "F"}),   # only vs / qs steps need the full evaluation
+    # instantiations of the loop with barriers that no other test selects, at the smallest shapes that do (no stream window fits):
+    (33, 200, 33, 2, 19, 300, {}),                                         # k_mcmc_wide<0, false, 0>: more than 32 chains, strided stations
+    (33, 70, 32, 2, 20, 300, {}),                                          # k_mcmc<2, false, 0>
+    (33, 200, 17, 2, 21, 300, {}),                                         # k_mcmc<0, false, 0>
 ]
 
 
