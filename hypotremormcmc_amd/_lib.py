@@ -80,6 +80,10 @@ SIGNATURES = {
     "htm_quantiles_dev": (C.c_int, [C.c_int, vp, C.c_long, C.c_long, C.c_long, C.POINTER(C.c_int), vp, vp]),
     "htm_diagnose": (C.c_int, [C.c_int, dp, C.c_long, C.c_long, C.c_long, C.c_int, dp, dp]),
     "htm_diagnose_dev": (C.c_int, [C.c_int, vp, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, vp, vp, vp]),
+    "htm_rank_normalize": (C.c_int, [C.c_int, dp, C.c_long, C.c_long, C.c_int, dp, dp]),
+    "htm_rank_normalize_dev": (C.c_int, [C.c_int, vp, C.c_long, C.c_long, C.c_long, C.c_int, vp, C.c_long, vp, vp]),
+    "htm_diagnose_rank": (C.c_int, [C.c_int, dp, C.c_long, C.c_long, C.c_long, C.c_int, dp]),
+    "htm_diagnose_rank_dev": (C.c_int, [C.c_int, vp, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, vp, vp]),
     "htm_chains_swap_record_host": (C.c_int, [vp, dp]),
     "htm_chains_step_end_host": (C.c_int, [vp, dp]),
     "htm_comm_unique_id": (C.c_int, [vp, C.c_size_t]),

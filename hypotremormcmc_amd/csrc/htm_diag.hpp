@@ -1,5 +1,6 @@
 // htm_diag.hpp -- convergence diagnostics of recorded samples: split R-hat and effective sample size per parameter
-// (Vehtari et al. 2021 / Stan, without rank normalisation; definitions: DESIGN.md §3.6).
+// (Vehtari et al. 2021 / Stan, without rank normalisation -- with it: htm_rank.hpp, which runs these kernels on the normal
+// scores; definitions: DESIGN.md §3.6).
 //
 // Layout: samples are [M*N][ld] row-major, sequence m in rows m*N .. m*N + N - 1, parameter p in column p.  As in
 // k_select, lane <-> column, so every load is a coalesced 512-B row segment.  A sequence gives two split sequences

@@ -1,5 +1,5 @@
 // htm_steps.hip -- the C ABI (include/htm_hip.h) of the pipeline's other steps: step 1 (htm_fft*, htm_convert*), steps 2 and 3
-// (htm_xcorr*, htm_measure_windows), step 4 (htm_select_regress), the convergence diagnostics (htm_diagnose*) and step 6
+// (htm_xcorr*, htm_measure_windows), step 4 (htm_select_regress), the convergence diagnostics (htm_diagnose*, htm_rank_normalize*) and step 6
 // (htm_quantiles*).  None of them touches a forward or a chain set.
 #include "htm_host.hpp"
 
@@ -17,6 +17,7 @@
 
 #include "htm_convert.hpp"
 #include "htm_diag.hpp"
+#include "htm_rank.hpp"
 #include "htm_select.hpp"
 #include "htm_xcorr.hpp"
 
@@ -202,6 +203,215 @@ int htm_diagnose(int device, const double *samples, long n_seq, long n_draws, lo
     if (rc == HTM_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(HTM_EHIP, "the diagnostics kernels failed");
     if (rc == HTM_OK && hipMemcpy(out, d_o, ob, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HTM_EHIP, "download failed");
     if (rc == HTM_OK && acov && hipMemcpy(acov, d_a, ab, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HTM_EHIP, "download failed");
+    return done(rc);
+}
+
+// ---- rank-normalised diagnostics (htm_rank.hpp) ---------------------------------------------------
+namespace {
+// workspace on the stream (as htm_quantiles_dev allocates it); release() after the last launch that uses it
+struct StreamBuf {
+    char *p = nullptr;
+    bool async = false;
+    hipStream_t st = nullptr;
+    int alloc(size_t bytes, hipStream_t s)
+    {
+        st = s;
+        async = hipMallocAsync(reinterpret_cast<void **>(&p), bytes, st) == hipSuccess;
+        if (!async) {
+            (void)hipGetLastError();
+            if (hipMalloc(reinterpret_cast<void **>(&p), bytes) != hipSuccess) { p = nullptr; return fail(HTM_EHIP, "hipMalloc of %zu bytes failed", bytes); }
+        }
+        return HTM_OK;
+    }
+    int release()
+    {
+        if (!p) return HTM_OK;
+        char *q = p;
+        p = nullptr;
+        if (async) {
+            HIPCHK(hipFreeAsync(q, st));
+        } else {
+            hipError_t e = hipStreamSynchronize(st);
+            (void)hipFree(q);
+            HIPCHK(e);
+        }
+        return HTM_OK;
+    }
+};
+
+// columns per batch: the two key buffers [nb][R] stay under HTM_RANK_MB MiB (default 2048; at least one column), and no
+// launch of a batch goes beyond 2^32 - 1 work-items
+int rank_batch(long R, long n_par, long *nb_out)
+{
+    double mb = 2048.0;
+    if (const char *e = getenv("HTM_RANK_MB")) {
+        mb = atof(e);
+        if (!(mb > 0.0)) return fail(HTM_EINVAL, "HTM_RANK_MB = %s: a positive number of MiB", e);
+    }
+    const double cols = mb * 1048576.0 / (2.0 * sizeof(unsigned long long) * (double)R);
+    long nb = cols >= (double)n_par ? n_par : std::max(1L, (long)cols);
+    nb = std::min(nb, 1L << 21);                           // k_rank_sort: nb workgroups of kRankTile = 1024 threads
+    const long n_rt = (R + 63) / 64, n_cg = (nb + 63) / 64, n_rc = (R + kRankZRows - 1) / kRankZRows;
+    if (n_rt * n_cg * 256 > 0xffffffffL || n_cg * n_rc * 256 > 0xffffffffL)
+        return fail(HTM_EINVAL, "%ld rows x %ld columns per batch need more than 2^32 - 1 work-items in one launch", R, nb);
+    *nb_out = nb;
+    return HTM_OK;
+}
+
+int rank_shape_check(long n_rows, long n_par, long ld, long ld_z)
+{
+    if (n_rows < 2 || n_par < 1 || ld < n_par || ld_z < n_par)
+        return fail(HTM_EINVAL, "bad shape (n_rows %ld, n_par %ld, ld %ld, ld_z %ld): need n_rows >= 2, n_par >= 1, ld and ld_z >= n_par",
+                    n_rows, n_par, ld, ld_z);
+    if (n_rows > INT_MAX) return fail(HTM_EINVAL, "n_rows %ld exceeds %d rows per column", n_rows, INT_MAX);
+    return HTM_OK;
+}
+
+// d_med [n_par]: the medians of a folded transform, NULL for the plain one.  HTM_RANK_STOP=keys|sort ends every batch after
+// that kernel (tools/bench_diagnose_rank.py times the three parts by it; z is then not written).
+int rank_normalize_batches(const double *d_x, long R, long n_par, long ld, const double *d_med, double *d_z, long ld_z,
+                           double *d_ranks, long nb, hipStream_t st)
+{
+    int stop = 3;
+    if (const char *e = getenv("HTM_RANK_STOP")) stop = !strcmp(e, "keys") ? 1 : !strcmp(e, "sort") ? 2 : 3;
+    StreamBuf ws;
+    const size_t key_n = (size_t)nb * R;
+    int rc = ws.alloc(2 * key_n * sizeof(unsigned long long), st);
+    if (rc) return rc;
+    unsigned long long *ka = reinterpret_cast<unsigned long long *>(ws.p), *kb = ka + key_n;
+    const long n_rt = (R + 63) / 64, n_rc = (R + kRankZRows - 1) / kRankZRows;
+    for (long c0 = 0; c0 < n_par; c0 += nb) {
+        const long n = std::min(nb, n_par - c0), n_cg = (n + 63) / 64;
+        hipLaunchKernelGGL(k_rank_keys, dim3((unsigned)(n_rt * n_cg)), dim3(256), 0, st, d_x, R, ld, c0, n, n_rt, d_med, ka);
+        if (stop >= 2) hipLaunchKernelGGL(k_rank_sort, dim3((unsigned)n), dim3(kRankTile), 0, st, ka, kb, R);
+        if (stop >= 3)
+            hipLaunchKernelGGL(k_rank_z, dim3((unsigned)(n_cg * n_rc)), dim3(256), 0, st, d_x, R, ld, c0, n, n_cg, d_med,
+                               (const unsigned long long *)ka, d_z, d_ranks, ld_z);
+    }
+    hipError_t e = hipGetLastError();
+    rc = ws.release();
+    if (e != hipSuccess) return fail(HTM_EHIP, "a rank kernel's launch failed: %s", hipGetErrorString(e));
+    return rc;
+}
+}  // namespace
+
+int htm_rank_normalize_dev(int device, const double *d_samples, long n_rows, long n_par, long ld, int fold, double *d_z, long ld_z,
+                           double *d_ranks, void *hip_stream)
+{
+    if (!d_samples || !d_z) return fail(HTM_EINVAL, "NULL argument");
+    int rc = rank_shape_check(n_rows, n_par, ld, ld_z);
+    if (rc) return rc;
+    long nb = 0;
+    if ((rc = rank_batch(n_rows, n_par, &nb))) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
+    HIPCHK(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (!fold) return rank_normalize_batches(d_samples, n_rows, n_par, ld, nullptr, d_z, ld_z, d_ranks, nb, st);
+    // the medians: the order statistics (R+1)/2 and R/2+1 (the third rank is not used)
+    StreamBuf ws;
+    if ((rc = ws.alloc((size_t)n_par * 4 * sizeof(double), st))) return rc;
+    double *d_q = reinterpret_cast<double *>(ws.p), *d_med = d_q + 3 * n_par;
+    const int rk[3] = {(int)((n_rows + 1) / 2), (int)(n_rows / 2 + 1), 1};
+    rc = htm_quantiles_dev(device, d_samples, n_rows, n_par, ld, rk, d_q, hip_stream);
+    if (rc == HTM_OK) {
+        hipLaunchKernelGGL(k_rank_median, dim3((unsigned)((n_par + 63) / 64)), dim3(64), 0, st, (const double *)d_q, n_par, d_med);
+        rc = rank_normalize_batches(d_samples, n_rows, n_par, ld, d_med, d_z, ld_z, d_ranks, nb, st);
+    }
+    const int rc2 = ws.release();
+    return rc ? rc : rc2;
+}
+
+int htm_rank_normalize(int device, const double *samples, long n_rows, long n_par, int fold, double *z, double *ranks)
+{
+    if (!samples || !z) return fail(HTM_EINVAL, "NULL argument");
+    int rc = rank_shape_check(n_rows, n_par, n_par, n_par);
+    if (rc) return rc;
+    long nb = 0;
+    if ((rc = rank_batch(n_rows, n_par, &nb))) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
+    HIPCHK(hipSetDevice(device));
+    const size_t n = (size_t)n_rows * n_par;
+    std::vector<void *> pool;
+    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
+    double *d_x = nullptr, *d_z = nullptr, *d_r = nullptr;
+    if ((rc = dev_upload(pool, &d_x, samples, n)) || (rc = dev_alloc(pool, &d_z, n)) || (ranks && (rc = dev_alloc(pool, &d_r, n))))
+        return done(rc);
+    rc = htm_rank_normalize_dev(device, d_x, n_rows, n_par, n_par, fold, d_z, n_par, d_r, nullptr);
+    if (rc == HTM_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(HTM_EHIP, "the rank kernels failed");
+    if (rc == HTM_OK && hipMemcpy(z, d_z, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HTM_EHIP, "download failed");
+    if (rc == HTM_OK && ranks && hipMemcpy(ranks, d_r, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HTM_EHIP, "download failed");
+    return done(rc);
+}
+
+int htm_diagnose_rank_dev(int device, const double *d_samples, long n_seq, long n_draws, long n_par, long ld, int max_lag, double *d_out,
+                          void *hip_stream)
+{
+    if (!d_samples || !d_out) return fail(HTM_EINVAL, "NULL argument");
+    int rc = diag_check(n_seq, n_draws, n_par, max_lag);
+    if (rc) return rc;
+    if (ld < n_par) return fail(HTM_EINVAL, "bad shape (n_par %ld, ld %ld)", n_par, ld);
+    const long R = n_seq * n_draws, n_cg = (n_par + 63) / 64, n_rc = (R + kRankZRows - 1) / kRankZRows;
+    // the launches of this function's own kernels and the widest one of htm_diagnose_dev (k_diag_mean), before any device call
+    if (n_cg > INT_MAX / (2 * n_seq) || n_cg * 2 * n_seq * 64 * kDiagRG > 0xffffffffL || n_cg * n_rc * 256 > 0xffffffffL)
+        return fail(HTM_EINVAL, "n_par %ld, %ld rows in %ld sequences need more than 2^32 - 1 work-items in one launch", n_par, R, n_seq);
+    long nb = 0;
+    if ((rc = rank_batch(R, n_par, &nb))) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
+    HIPCHK(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    // workspace: one [R][n_par] matrix that holds z, zf, I05 and I95 in turn; the six order statistics, the three thresholds and
+    // the four results of htm_diagnose_dev per column
+    const size_t mat_n = (size_t)R * n_par, small_n = (size_t)n_par * (6 + 3 + 16);
+    StreamBuf ws;
+    if ((rc = ws.alloc((mat_n + small_n) * sizeof(double), st))) return rc;
+    double *d_m = reinterpret_cast<double *>(ws.p), *d_qa = d_m + mat_n, *d_qb = d_qa + 3 * n_par, *d_thr = d_qb + 3 * n_par,
+           *d_d = d_thr + 3 * n_par;
+    auto done = [&](int code) { const int rc2 = ws.release(); return code ? code : rc2; };
+    // h = (R - 1) p, k = floor(h), g = h - k; the quantile is x_(k+1) + g (x_(min(k+2, R)) - x_(k+1))
+    const double h05 = (double)(R - 1) * 0.05, h95 = (double)(R - 1) * 0.95;
+    const long k05 = (long)std::floor(h05), k95 = (long)std::floor(h95);
+    const int ra[3] = {(int)((R + 1) / 2), (int)(R / 2 + 1), (int)(k05 + 1)};
+    const int rb[3] = {(int)std::min(k05 + 2, R), (int)(k95 + 1), (int)std::min(k95 + 2, R)};
+    if ((rc = htm_quantiles_dev(device, d_samples, R, n_par, ld, ra, d_qa, hip_stream))) return done(rc);
+    if ((rc = htm_quantiles_dev(device, d_samples, R, n_par, ld, rb, d_qb, hip_stream))) return done(rc);
+    hipLaunchKernelGGL(k_rank_thresholds, dim3((unsigned)n_cg), dim3(64), 0, st, (const double *)d_qa, (const double *)d_qb, n_par,
+                       h05 - (double)k05, h95 - (double)k95, d_thr);
+    for (int part = 0; part < 4; ++part) {
+        if (part < 2) {
+            rc = rank_normalize_batches(d_samples, R, n_par, ld, part ? d_thr : nullptr, d_m, n_par, nullptr, nb, st);
+            if (rc) return done(rc);
+        } else {
+            hipLaunchKernelGGL(k_rank_indicator, dim3((unsigned)(n_cg * n_rc)), dim3(256), 0, st, d_samples, R, n_par, ld, n_cg,
+                               (const double *)(d_thr + (part - 1) * n_par), part - 2, d_m);
+        }
+        if ((rc = htm_diagnose_dev(device, d_m, n_seq, n_draws, n_par, n_par, max_lag, d_d + (size_t)part * n_par * 4, nullptr, hip_stream)))
+            return done(rc);
+    }
+    hipLaunchKernelGGL(k_rank_combine, dim3((unsigned)n_cg), dim3(64), 0, st, (const double *)d_d, n_par, d_out);
+    if (hipGetLastError() != hipSuccess) return done(fail(HTM_EHIP, "a rank kernel's launch failed"));
+    return done(HTM_OK);
+}
+
+int htm_diagnose_rank(int device, const double *samples, long n_seq, long n_draws, long n_par, int max_lag, double *out)
+{
+    if (!samples || !out) return fail(HTM_EINVAL, "NULL argument");
+    int rc = diag_check(n_seq, n_draws, n_par, max_lag);
+    if (rc) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
+    HIPCHK(hipSetDevice(device));
+    std::vector<void *> pool;
+    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
+    double *d_x = nullptr, *d_o = nullptr;
+    if ((rc = dev_upload(pool, &d_x, samples, (size_t)n_seq * n_draws * n_par)) || (rc = dev_alloc(pool, &d_o, (size_t)n_par * 4)))
+        return done(rc);
+    rc = htm_diagnose_rank_dev(device, d_x, n_seq, n_draws, n_par, n_par, max_lag, d_o, nullptr);
+    if (rc == HTM_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(HTM_EHIP, "the diagnostics kernels failed");
+    if (rc == HTM_OK && hipMemcpy(out, d_o, (size_t)n_par * 4 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(HTM_EHIP, "download failed");
     return done(rc);
 }
 

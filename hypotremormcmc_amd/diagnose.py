@@ -1,13 +1,19 @@
 """Convergence diagnostics of a step-5 run on the GPU: split R-hat and effective sample size of every parameter
-step 6 summarises, from the same sample files (Vehtari et al. 2021 / Stan, without rank normalisation; the
-definitions are in DESIGN.md §3.6, the kernels in hypotremormcmc_amd/csrc/htm_diag.hpp).
+step 6 summarises, from the same sample files (Vehtari et al. 2021 / Stan; `diagnose` is without rank normalisation,
+DESIGN.md §3.6, kernels in hypotremormcmc_amd/csrc/htm_diag.hpp; `diagnose_rank` is with it, §3.7, htm_rank.hpp).
 
-    python -m hypotremormcmc_amd.diagnose <parameter file> [--max-lag N] [--rhat 1.01]
+    python -m hypotremormcmc_amd.diagnose <parameter file> [--max-lag N] [--rhat 1.01] [--rank]
 
 run in the directory of the step-5 outputs, writes `convergence.stat` next to the `.stat` files of
 `hypotremormcmc_amd.statistics`: one line per parameter with R-hat, ESS, the autocorrelation time tau (ESS =
 samples / tau) and the lag at which Geyer's pair sums went negative (-1: they did not within --max-lag, the ESS is
 then an upper bound).  Parameters the job fixes (`solve_vs = F`, ...) are constant and are written as NaN.
+
+With --rank it also writes `convergence_rank.stat`: per parameter the larger of the rank-normalised and the folded
+R-hat, the two, the bulk-ESS and the tail-ESS (the smaller ESS of the indicators of the 5 % and the 95 % quantile).  These
+see what the plain numbers miss: sequences that differ in scale but not in location, heavy tails, and whether the ends
+of the intervals in the `.stat` files were sampled enough.  The column sort works in batches under HTM_RANK_MB MiB of
+device memory (default 2048).
 """
 from __future__ import annotations
 
@@ -21,6 +27,7 @@ from . import _lib
 from .param import Param
 from .statistics import INT_MAX, read_sample_file
 
+RANK_STAT_HEADER = "# parameter, R-hat (larger of the next two), rank-normalised R-hat, folded R-hat, bulk-ESS, tail-ESS"
 STAT_HEADER = "# parameter, R-hat (split), ESS, tau, lag of the first negative pair sum (-1: none up to the last lag)"
 
 
@@ -54,6 +61,54 @@ def diagnose(samples, n_seq: int, max_lag: int = 1000, device: int = 0, return_a
     _lib.check(lib.htm_diagnose(device, x.ctypes.data_as(_lib.dp), n_seq, n_draws, n_par, max_lag, out.ctypes.data_as(_lib.dp),
                                 acov.ctypes.data_as(_lib.dp) if return_acov else None))
     return (out, acov) if return_acov else out
+
+
+def _sample_matrix(samples, n_seq, max_lag, what):
+    """the checks `diagnose` makes before any device call, for the rank entry points: x [n_rows][n_par], n_draws"""
+    shape = np.shape(samples)
+    if len(shape) == 1:
+        shape = (shape[0], 1)
+    if len(shape) != 2:
+        raise ValueError(f"samples must be [rows][n_par], got shape {shape}")
+    n_rows, n_par = shape
+    n_seq, max_lag = int(n_seq), int(max_lag)
+    if n_rows > INT_MAX:
+        raise ValueError(f"rows = {n_rows} exceeds {INT_MAX}: {what} takes at most {INT_MAX} rows")
+    if n_seq < 1 or n_par < 1 or max_lag < 1 or max_lag > INT_MAX:
+        raise ValueError(f"need n_seq >= 1, n_par >= 1 and 1 <= max_lag <= {INT_MAX} (got {n_seq}, {n_par}, {max_lag})")
+    if n_rows % n_seq:
+        raise ValueError(f"{n_rows} rows are not {n_seq} sequences of equal length")
+    x = np.ascontiguousarray(samples, dtype=np.float64).reshape(n_rows, n_par)
+    if not np.isfinite(x).all():
+        raise ValueError("samples hold NaN or inf")
+    return x, n_rows // n_seq
+
+
+def rank_normalize(samples, fold: bool = False, return_ranks: bool = False, device: int = 0):
+    """z [n_rows][n_par] = Phi^-1((r - 3/8) / (n_rows + 1/4)), r the 1-based average rank of an element within its column
+    (of |x - median| with fold), on the GPU.  With return_ranks also r."""
+    x, n_rows = _sample_matrix(samples, 1, 1, "htm_rank_normalize")
+    if n_rows < 2:
+        raise ValueError(f"n_rows = {n_rows}: ranking needs at least 2 rows")
+    z = np.empty_like(x)
+    ranks = np.empty_like(x) if return_ranks else None
+    lib = _lib.load()
+    _lib.check(lib.htm_rank_normalize(device, x.ctypes.data_as(_lib.dp), n_rows, x.shape[1], 1 if fold else 0,
+                                      z.ctypes.data_as(_lib.dp), ranks.ctypes.data_as(_lib.dp) if return_ranks else None))
+    return (z, ranks) if return_ranks else z
+
+
+def diagnose_rank(samples, n_seq: int, max_lag: int = 1000, device: int = 0):
+    """[n_par][4] = (rhat_bulk, rhat_folded, ess_bulk, ess_tail) of every column of samples, laid out as for `diagnose`,
+    on the GPU.  The R-hat to report is the larger of the first two."""
+    x, n_draws = _sample_matrix(samples, n_seq, max_lag, "htm_diagnose_rank")
+    if n_draws < 4:
+        raise ValueError(f"n_draws = {n_draws}: a sequence needs at least 4 draws to be split")
+    out = np.empty((x.shape[1], 4))
+    lib = _lib.load()
+    _lib.check(lib.htm_diagnose_rank(device, x.ctypes.data_as(_lib.dp), int(n_seq), n_draws, x.shape[1], int(max_lag),
+                                     out.ctypes.data_as(_lib.dp)))
+    return out
 
 
 def sequences_by_iteration(iters, values, k: int):
@@ -112,6 +167,32 @@ def summary_text(names, out, rhat_limit: float) -> str:
             f"{int(np.sum(out[live, 3] < 0))} parameters\n")
 
 
+def rank_stat_text(names, out) -> str:
+    """the text of convergence_rank.stat for out [n_par][4] of `diagnose_rank`; an entry that is NaN is written as NaN"""
+    lines = [RANK_STAT_HEADER]
+    for name, (rb, rf, eb, et) in zip(names, np.asarray(out, dtype=np.float64)):
+        rmax = np.fmax(rb, rf)          # of the two that are defined: |x - med| of a two-valued column can be constant
+        lines.append("%-24s" % name + "".join("%13s" % "NaN" if np.isnan(v) else "%13.6f" % v for v in (rmax, rb, rf, eb, et)))
+    return "\n".join(lines) + "\n"
+
+
+def rank_summary_text(names, out, rhat_limit: float) -> str:
+    """three lines: the largest rank R-hat, the smallest bulk-ESS and tail-ESS, the count above the limit"""
+    out = np.asarray(out, dtype=np.float64)
+    rmax = np.fmax(out[:, 0], out[:, 1])
+    live = np.nonzero(~np.isnan(rmax))[0]
+    if not len(live):
+        return "no parameter varies: no rank-normalised diagnostics\n"
+    worst = live[np.argmax(rmax[live])]
+    bulks = np.nonzero(~np.isnan(out[:, 2]))[0]
+    bulk = bulks[np.argmin(out[bulks, 2])]
+    tails = np.nonzero(~np.isnan(out[:, 3]))[0]
+    tail_txt = "none defined" if not len(tails) else "%.1f  (%s)" % (out[tails, 3].min(), names[tails[np.argmin(out[tails, 3])]])
+    return (f"largest rank-normalised R-hat  {rmax[worst]:.6f}  ({names[worst]})\n"
+            f"smallest bulk-ESS  {out[bulk, 2]:.1f}  ({names[bulk]}), smallest tail-ESS  {tail_txt}\n"
+            f"rank-normalised R-hat > {rhat_limit:g}: {int(np.sum(rmax[live] > rhat_limit))} parameters\n")
+
+
 def gather_sequences(work_dir, n_procs, n_sta, n_events, n_burn, k):
     """all ranks' sample files and the recorded part of their log-likelihood traces as one sequence-major matrix:
     columns vs, qs, t_corr, a_corr, hypo, log-likelihood"""
@@ -139,6 +220,7 @@ def main(argv=None):
     ap.add_argument("parameter_file")
     ap.add_argument("--max-lag", type=int, default=1000)
     ap.add_argument("--rhat", type=float, default=1.01, help="R-hat above which a parameter is counted in the summary")
+    ap.add_argument("--rank", action="store_true", help="also write convergence_rank.stat: rank-normalised R-hat, bulk- and tail-ESS")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
     par = Param(args.parameter_file)
     work = os.path.dirname(os.path.abspath(args.parameter_file))
@@ -150,6 +232,11 @@ def main(argv=None):
     with open(os.path.join(work, "convergence.stat"), "w") as fh:
         fh.write(stat_text(names, out))
     sys.stdout.write(summary_text(names, out, args.rhat))
+    if args.rank:
+        rk = diagnose_rank(x, k, max_lag=args.max_lag, device=int(os.environ.get("HTM_DEVICE", "0")))
+        with open(os.path.join(work, "convergence_rank.stat"), "w") as fh:
+            fh.write(rank_stat_text(names, rk))
+        sys.stdout.write(rank_summary_text(names, rk, args.rhat))
 
 
 if __name__ == "__main__":

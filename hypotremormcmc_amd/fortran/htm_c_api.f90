@@ -16,6 +16,7 @@ module htm_c_api
   public :: HTM_XCHG_HANDLE_BYTES, HTM_COMM_ID_BYTES
   public :: htm_comm_unique_id, htm_comm_create, htm_comm_destroy, htm_chains_run_lockstep_comm
   public :: htm_device_count, htm_device_physical_id, htm_quantiles, htm_diagnose, htm_select_regress
+  public :: htm_rank_normalize, htm_rank_normalize_dev, htm_diagnose_rank, htm_diagnose_rank_dev
   public :: htm_chains_checkpoint_size, htm_chains_checkpoint_save, htm_chains_checkpoint_load
 
   integer(c_size_t), parameter :: HTM_XCHG_HANDLE_BYTES = 64_c_size_t, HTM_COMM_ID_BYTES = 128_c_size_t
@@ -247,6 +248,51 @@ module htm_c_api
        type(c_ptr), value :: acov
        integer(c_int) :: rc
      end function htm_diagnose
+     !> rank normalisation (include/htm_hip.h): samples, z [n_rows][n_par] row-major; ranks as z, or c_null_ptr
+     function htm_rank_normalize(device, samples, n_rows, n_par, fold, z, ranks) bind(C, name="htm_rank_normalize") result(rc)
+       import :: c_int, c_long, c_double, c_ptr
+       integer(c_int), value :: device
+       real(c_double), intent(in) :: samples(*)
+       integer(c_long), value :: n_rows, n_par
+       integer(c_int), value :: fold
+       real(c_double), intent(out) :: z(*)
+       type(c_ptr), value :: ranks
+       integer(c_int) :: rc
+     end function htm_rank_normalize
+     !> the same on device pointers with row strides ld (samples) and ld_z (z, ranks), asynchronous on hip_stream
+     function htm_rank_normalize_dev(device, d_samples, n_rows, n_par, ld, fold, d_z, ld_z, d_ranks, hip_stream) &
+          & bind(C, name="htm_rank_normalize_dev") result(rc)
+       import :: c_int, c_long, c_ptr
+       integer(c_int), value :: device
+       type(c_ptr), value :: d_samples
+       integer(c_long), value :: n_rows, n_par, ld
+       integer(c_int), value :: fold
+       type(c_ptr), value :: d_z
+       integer(c_long), value :: ld_z
+       type(c_ptr), value :: d_ranks, hip_stream
+       integer(c_int) :: rc
+     end function htm_rank_normalize_dev
+     !> rank-normalised diagnostics (include/htm_hip.h): samples as htm_diagnose, out [n_par][4] =
+     !> rhat_bulk, rhat_folded, ess_bulk, ess_tail
+     function htm_diagnose_rank(device, samples, n_seq, n_draws, n_par, max_lag, out) bind(C, name="htm_diagnose_rank") result(rc)
+       import :: c_int, c_long, c_double
+       integer(c_int), value :: device
+       real(c_double), intent(in) :: samples(*)
+       integer(c_long), value :: n_seq, n_draws, n_par
+       integer(c_int), value :: max_lag
+       real(c_double), intent(out) :: out(*)
+       integer(c_int) :: rc
+     end function htm_diagnose_rank
+     function htm_diagnose_rank_dev(device, d_samples, n_seq, n_draws, n_par, ld, max_lag, d_out, hip_stream) &
+          & bind(C, name="htm_diagnose_rank_dev") result(rc)
+       import :: c_int, c_long, c_ptr
+       integer(c_int), value :: device
+       type(c_ptr), value :: d_samples
+       integer(c_long), value :: n_seq, n_draws, n_par, ld
+       integer(c_int), value :: max_lag
+       type(c_ptr), value :: d_out, hip_stream
+       integer(c_int) :: rc
+     end function htm_diagnose_rank_dev
      !> step-4 regressions (include/htm_hip.h): t, t_err, a, a_err (n_sta, n_win); out (6, n_win) = vs, b, t0, a0, cc_t, cc_a
      function htm_select_regress(device, n_sta, n_win, sta_x, sta_y, sta_z, z_guess, t, t_err, a, a_err, out) &
           & bind(C, name="htm_select_regress") result(rc)

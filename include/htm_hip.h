@@ -324,7 +324,7 @@ int htm_quantiles_dev(int device, const double *d_samples, long n_mod, long n_pa
 
 /* ------------------------------------------------------------------------------------------------
  * Convergence diagnostics of recorded samples: split R-hat and effective sample size per parameter,
- * Vehtari et al. 2021 / Stan without rank normalisation.  samples [n_seq*n_draws][n_par] row-major, sequence m in
+ * Vehtari et al. 2021 / Stan without rank normalisation (with it: htm_diagnose_rank below).  samples [n_seq*n_draws][n_par] row-major, sequence m in
  * rows m*n_draws .. (m+1)*n_draws - 1.  Every sequence is split into its first and its last n = n_draws/2 draws; the
  * biased autocovariances of the 2 n_seq split sequences are averaged for lags 0..L, L = min(n - 1, max_lag).
  * out [n_par][4] = {rhat, ess, tau, lags}: ess = 2 n_seq n / tau; lags = the lag at which Geyer's pair sums first went
@@ -337,6 +337,29 @@ int htm_diagnose(int device, const double *samples, long n_seq, long n_draws, lo
                  double *out, double *acov);
 int htm_diagnose_dev(int device, const double *d_samples, long n_seq, long n_draws, long n_par, long ld,
                      int max_lag, double *d_out, double *d_acov, void *hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Rank-normalised diagnostics (Vehtari et al. 2021): what the split R-hat and ESS above miss -- sequences
+ * that agree in location but not in scale, heavy tails, and whether the ends of the 2.5 % / 97.5 % intervals of the .stat
+ * files were sampled enough.
+ * htm_rank_normalize: samples [n_rows][n_par] row-major; r = the 1-based average rank of an element among the n_rows of
+ * its column (ties share the mean of their positions, -0.0 = +0.0), z [n_rows][n_par] = Phi^-1((r - 3/8) / (n_rows + 1/4));
+ * fold != 0 ranks |x - med| instead, med = the mean of the order statistics (n_rows+1)/2 and n_rows/2+1.  ranks, if not
+ * NULL, receives r (exact half-integers).  2 <= n_rows <= INT_MAX, n_par >= 1.  The _dev form: ld, ld_z = row strides in
+ * doubles of d_samples and of d_z and d_ranks; columns n_par .. ld_z - 1 are not touched.
+ * htm_diagnose_rank: samples and shape rules as htm_diagnose; out [n_par][4] = {rhat_bulk, rhat_folded, ess_bulk, ess_tail}:
+ * htm_diagnose's R-hat and ESS of z and of the folded z, and the smaller ESS of the indicators [x <= q05], [x >= q95] of
+ * the column's 5 % and 95 % quantiles.  An entry is NaN where its matrix's column is constant.  The R-hat to report is
+ * the larger of the two.  All rows are ranked, also the middle row that an odd n_draws drops from the split.
+ * The columns are sorted in batches whose workspace stays under HTM_RANK_MB MiB (environment, default 2048); the result
+ * does not depend on it, and two calls give the same bits.  A shape that needs a launch beyond 2^32 - 1 work-items is
+ * HTM_EINVAL before any device call.  Host pointers: synchronous; _dev: device pointers, asynchronous on `hip_stream`. */
+int htm_rank_normalize(int device, const double *samples, long n_rows, long n_par, int fold, double *z, double *ranks);
+int htm_rank_normalize_dev(int device, const double *d_samples, long n_rows, long n_par, long ld, int fold,
+                           double *d_z, long ld_z, double *d_ranks, void *hip_stream);
+int htm_diagnose_rank(int device, const double *samples, long n_seq, long n_draws, long n_par, int max_lag, double *out);
+int htm_diagnose_rank_dev(int device, const double *d_samples, long n_seq, long n_draws, long n_par, long ld,
+                          int max_lag, double *d_out, void *hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Step 4, `hypo_tremor_select`   reference: src/cls_selector.f90:75-132, src/mod_regress.f90
