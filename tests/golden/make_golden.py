@@ -13,6 +13,13 @@ Cases
   c2      100 ev x 16 stn, seed 2, 1 rank  x 2 chains,  4000 it   (BASELINE config #2; 2 chains: quirk 1)
   missing   6 ev x 10 stn, seed 7, 5 entries with t_stdv = 0, 1 rank x 3 chains (missing-data rule)
   timeonly  8 ev x 12 stn, seed 3, use_amp = F, solve_qs = solve_a_corr = F, 3 ranks x 2 chains
+  amponly   8 ev x 12 stn, seed 13, use_time = F, solve_t_corr = F (solve_vs stays T: vs enters the attenuation term),
+         4 entries with t_stdv = 0, 3 ranks x 2 chains (run under mpiexec -np 3).  Pins that the missing-data rule stays
+         keyed on t_stdv when travel times are unused.
+  missing64 9 ev x 64 stn, seed 17, 1 rank x 3 chains, 1500 it; missing entries from an explicit index list
+         (`missing_idx`, stored as in_missing_idx): station 0 of event 0, station 63 of event 8, event 4 with every station
+         but one missing, station 17 missing in every event, three scattered ones -- 76 entries (the four patterns alone
+         take 73).  Full rows of 64 with both data types: the shape of the specialised chain master's packed records.
   fixedcorr 7 ev x  9 stn, seed 4, solve_t_corr = solve_vs = F, 2 ranks x 3 chains, n_cool = 2
   c3     1000 ev x 64 stn, seed 1, 1 rank x 8 chains, 600 it: inputs are NOT stored (2 MB) -- the seeded
          generator reproduces them; a checksum of the inputs is stored instead.
@@ -61,6 +68,13 @@ CASES = {
     "timeonly": dict(n_events=8, n_sta=12, seed=3, n_missing=0,
                      params=dict(n_procs=3, n_chains=2, n_cool=1, n_iter=6000, n_burn=3000, n_interval=40,
                                  use_amp="F", solve_qs="F", solve_a_corr="F")),
+    "amponly": dict(n_events=8, n_sta=12, seed=13, n_missing=4,
+                    params=dict(n_procs=3, n_chains=2, n_cool=1, n_iter=6000, n_burn=3000, n_interval=40,
+                                use_time="F", solve_t_corr="F", solve_vs="T")),
+    "missing64": dict(n_events=9, n_sta=64, seed=17, n_missing=0,
+                      missing_idx=([(0, 0), (8, 63)] + [(4, j) for j in range(64) if j != 40] + [(i, 17) for i in range(9)]
+                                   + [(2, 31), (2, 32), (6, 5)]),
+                      params=dict(n_procs=1, n_chains=3, n_cool=1, n_iter=1500, n_burn=500, n_interval=25)),
     "fixedcorr": dict(n_events=7, n_sta=9, seed=4, n_missing=0,
                       params=dict(n_procs=2, n_chains=3, n_cool=2, n_iter=5000, n_burn=0, n_interval=20,
                                   solve_t_corr="F", solve_vs="F", temp_high="50.0")),
@@ -159,6 +173,8 @@ def probe(workdir, data, params, n_cases=4):
 
 def run_case(name, spec):
     data = synth.make_synthetic(spec["n_events"], spec["n_sta"], spec["seed"], spec["n_missing"])
+    missing_idx = np.array(sorted(set(spec.get("missing_idx", []))), dtype=np.int64).reshape(-1, 2)
+    data.t_stdv[missing_idx[:, 0], missing_idx[:, 1]] = 0.0      # (event, station) pairs set by hand
     work = tempfile.mkdtemp(prefix="htm_golden_")
     try:
         synth.write_dataset(work, data)
@@ -205,6 +221,8 @@ def run_case(name, spec):
         fx["in_checksum"] = np.array(checksum(data))
         fx["in_seed"] = np.array(spec["seed"])
         fx["in_n_missing"] = np.array(spec["n_missing"])
+        if len(missing_idx):
+            fx["in_missing_idx"] = missing_idx
         fx["in_shape"] = np.array([E, S])
         fx["param_keys"] = np.array(list(params.keys()))
         fx["param_vals"] = np.array([str(v) for v in params.values()])

@@ -56,7 +56,7 @@ def _check_against_fixture(fx, params, sets):
     assert np.array_equal(nac, fx["n_accept"])
 
 
-@pytest.mark.parametrize("name", ["c2", "missing", "c3"])
+@pytest.mark.parametrize("name", ["c2", "missing", "missing64", "c3"])
 def test_single_rank_run_matches_reference_trace(name):
     fx, data, params = load_case(name)
     fwd, sets = _build_world(data, params)
@@ -65,7 +65,7 @@ def test_single_rank_run_matches_reference_trace(name):
     _check_against_fixture(fx, params, sets)
 
 
-@pytest.mark.parametrize("name", ["c1", "timeonly", "fixedcorr", "rejects", "c4"])
+@pytest.mark.parametrize("name", ["c1", "timeonly", "amponly", "fixedcorr", "rejects", "c4"])
 def test_multi_rank_lockstep_matches_reference_trace(name):
     """2-8 simulated ranks on one GPU; the record exchange is a device copy instead of the RCCL all-gather.
     c4 = BASELINE configs[3]: 1000 x 64, 8 ranks x 8 chains, temp_high 200, against the reference under mpiexec -np 8"""

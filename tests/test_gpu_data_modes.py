@@ -1,0 +1,291 @@
+"""GPU parity of the two run-time switches that change what every likelihood kernel loads and sums: the data modes
+(use_time / use_amp: time only, amplitude only) and missing data (t_stdv <= 1e-16 marks BOTH data types of an entry: precision 1,
+log-stdv 1.0; reference src/cls_forward.f90:76-92), through the call-level forward API and through every chain loop.
+
+Modes of the chain jobs: A = amplitude only (use_time = F), T = time only (use_amp = F), M = both types with missing entries
+placed as fixture `missing64` has them (tests/helpers.py missing_pattern: the first and the last station, a nearly empty event,
+a station missing in every event).  The forward tests place the same missing entries in the single-type modes too.
+
+Criteria: those of tests/test_gpu_forward.py (call level) and of tests/test_gpu_chains.py::test_assorted_shapes_against_oracle
+(chain loops: every recorded log-likelihood, the iteration lists, counters, RNG state, every chain's final hypocentres and
+temperature against the oracle).  Which loop a job runs on is asserted through master_stats() / fixed_master()."""
+import numpy as np
+import pytest
+
+from tests.helpers import tf, with_missing
+from tests.test_gpu_chains import RTOL_TRACE, _build_world
+from tests.test_gpu_fast_master import RTOL_FP32, _assert_same_bits, _bits
+from tests.test_gpu_forward import RTOL_L, _mk, _orc
+from tests.test_gpu_forward import test_reference_known_answers as _reference_known_answers
+from tests.test_gpu_step_front import _pack_bytes
+
+pytestmark = pytest.mark.gpu
+
+SINGLE = {"time only": dict(use_amp="F"), "amplitude only": dict(use_time="F")}
+MODE = {"A": dict(use_time="F"), "T": dict(use_amp="F"), "M": {}}
+
+
+# ---- call-level forward API ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["amponly", "missing64"])
+def test_reference_known_answers_of_the_new_fixtures(name):
+    """tests/test_gpu_forward.py::test_reference_known_answers, its tolerances, on the amplitude-only fixture and on full rows
+    of 64 stations with missing entries"""
+    _reference_known_answers(name)
+
+
+def _forward_case(E, S, seed):
+    from hypotremormcmc_amd import synth
+
+    return with_missing(synth.make_synthetic(E, S, seed=seed))
+
+
+def _models(data, rng, n):
+    S = data.n_sta
+    H = np.stack([(data.ev_xyz + rng.normal(0, 1.0, data.ev_xyz.shape)).reshape(-1) for _ in range(n)])
+    return H, rng.normal(0, 0.2, (n, S)), 3 + rng.normal(0, 0.2, n), rng.normal(0, 0.02, (n, S)), 250 + rng.normal(0, 30, n)
+
+
+@pytest.mark.parametrize("shape", [(1, 1), (3, 2), (37, 64), (50, 65), (9, 200), (5, 300)])
+@pytest.mark.parametrize("mode", list(SINGLE))
+def test_single_type_forward_with_missing_entries_vs_oracle(mode, shape):
+    """full and partial evaluations at the tolerance of test_full_and_partial_vs_oracle_ragged_shapes, travel_time, amp and their
+    _single forms at that of test_reference_known_answers (the synthetics do not depend on the switches: cls_forward.f90:100-264).
+    RTOL_L is relative to the result, and with amplitudes only the result is a difference that partly cancels: the misfits'
+    sum against the constants' (-log stdv - log_2pi_half > 0 per entry).  In these cases |L| is 0.03 to 0.27 of the summed
+    magnitudes of its terms (time only: 0.36 to 0.81), which makes 1e-12 |L| as tight as 5.9 eps * (M + D) in the scale of
+    tests/test_forward_data_modes.py (5 x 300, second model; 14.6 and more elsewhere), where the oracle itself was measured
+    up to 9 from the longdouble value.  The tolerance stays the one of the both-types test all the same; a case that cancelled
+    further would have to be judged in that scale."""
+    E, S = shape
+    data = _forward_case(E, S, 400 + E + S)
+    f, o = _mk(data, SINGLE[mode]), _orc(data, SINGLE[mode])
+    rng = np.random.default_rng(E * 1000 + S + len(mode))
+    H, TC, VS, AC, QS = _models(data, rng, 3)
+    for k in range(3):
+        h, tc, vs, ac, qs = H[k], TC[k], VS[k], AC[k], QS[k]
+        Lg, Lo = f.calc_log_likelihood(h, tc, vs, ac, qs), o.calc_log_likelihood(h, tc, vs, ac, qs)
+        print("%s %dx%d full: library %.17g oracle %.17g" % (mode, E, S, Lg, Lo))
+        assert abs(Lg - Lo) <= RTOL_L * abs(Lo)
+        # (the nearly empty event first, then random ones: its row holds one entry that is not missing)
+        evt = E // 2 + 1 if k == 0 else int(rng.integers(1, E + 1))
+        h2 = h.copy(); h2[3 * (evt - 1) + int(rng.integers(0, 3))] += rng.normal(0, 1.0)
+        Pg = f.partially_update_log_likelihood(evt, h, Lo, h2, tc, vs, ac, qs)
+        Po = o.partially_update_log_likelihood(evt, h, Lo, h2, tc, vs, ac, qs)
+        assert abs(Pg - Po) <= RTOL_L * abs(Po)
+        np.testing.assert_allclose(f.calc_travel_time(h, tc, vs), o.calc_travel_time(h, tc, vs), rtol=0, atol=1e-12)
+        np.testing.assert_allclose(f.calc_amp(h, ac, qs, vs), o.calc_amp(h, ac, qs, vs), rtol=0, atol=1e-12)
+        np.testing.assert_allclose(f.calc_travel_time_single(evt, h, tc, vs), o.calc_travel_time_single(evt, h, tc, vs), rtol=0, atol=1e-12)
+        np.testing.assert_allclose(f.calc_amp_single(evt, h, ac, qs, vs), o.calc_amp_single(evt, h, ac, qs, vs), rtol=0, atol=1e-12)
+
+
+@pytest.mark.parametrize("shape", [(37, 64), (50, 65), (1001, 64)])
+@pytest.mark.parametrize("n", [2, 5])
+@pytest.mark.parametrize("mode", list(SINGLE))
+def test_stacked_models_equal_one_by_one_in_single_type_modes(mode, n, shape):
+    """event_misfit_models (pairs of stacked models, the odd one alone) zeroes the unused type's terms in its own way: the same
+    bits as one model at a time.  (Against the oracle: the test above, one model at a time.)"""
+    E, S = shape
+    data = _forward_case(E, S, 500 + E + S)
+    f = _mk(data, SINGLE[mode])
+    H, TC, VS, AC, QS = _models(data, np.random.default_rng(E * 31 + S + n), n)
+    Lb = f.calc_log_likelihood_batch(H, TC, VS, AC, QS)
+    Ls = np.array([f.calc_log_likelihood(H[k], TC[k], VS[k], AC[k], QS[k]) for k in range(n)])
+    assert np.all(np.isfinite(Lb)) and np.array_equal(Lb, Ls)
+
+
+@pytest.mark.parametrize("shape", [(37, 64), (20, 128)])
+@pytest.mark.parametrize("mode", list(SINGLE))
+def test_fp32_forward_in_single_type_modes_within_T1(mode, shape):
+    """tests/test_gpu_fp32.py T1 (|L32 - L64| <= 3e-6 |L64|, L64 the fp64 oracle's) with one data type and missing entries, full
+    evaluations one by one and stacked (the fp32 branch of event_misfit_models: the same bits).
+    A numpy restatement with float32 synthetics and fp64 sums (tests/test_forward_data_modes.py, syn_dtype) against the same
+    oracle values gives, on the CPU: 6.8e-7 (time only) and 5.2e-7 (amplitude only) at 37 x 64, 9.9e-7 and 3.2e-7 at
+    20 x 128 -- the arithmetic itself comes within a factor 3 of T1 at these models (1 km from the truth)."""
+    from hypotremormcmc_amd.forward import Forward
+    from hypotremormcmc_amd.obs_data import ObsData
+
+    E, S = shape
+    data = _forward_case(E, S, 600 + E + S)
+    obs = ObsData.from_arrays(data.sta_x, data.sta_y, data.t_obs, data.t_stdv, data.a_obs, data.a_stdv)
+    f32 = Forward(n_sta=S, n_events=E, sta_x=data.sta_x, sta_y=data.sta_y, sta_z=data.sta_z, obs=obs, forward_precision="fp32",
+                  use_amp=tf(SINGLE[mode].get("use_amp", "T")), use_time=tf(SINGLE[mode].get("use_time", "T")))
+    assert f32.forward_precision == "fp32"
+    o = _orc(data, SINGLE[mode])
+    H, TC, VS, AC, QS = _models(data, np.random.default_rng(E + S + len(mode)), 4)
+    Lo = np.array([o.calc_log_likelihood(H[k], TC[k], VS[k], AC[k], QS[k]) for k in range(4)])
+    L1 = np.array([f32.calc_log_likelihood(H[k], TC[k], VS[k], AC[k], QS[k]) for k in range(4)])
+    Lb = f32.calc_log_likelihood_batch(H, TC, VS, AC, QS)
+    print("%s %dx%d fp32: max |L32 - L64| / |L64| = %.3e" % (mode, E, S, float(np.max(np.abs(L1 - Lo) / np.abs(Lo)))))
+    assert np.array_equal(Lb, L1)
+    assert np.all(np.abs(L1 - Lo) <= RTOL_FP32 * np.abs(Lo))
+
+
+# ---- chain loops --------------------------------------------------------------------------------------------------------
+def _job(E, S, nc, mode, seed, n_iter, n_procs=1, **kw):
+    """step_size_z = 6.0: depth steps of half the prior width and more, so Rayleigh-prior rejections occur"""
+    from hypotremormcmc_amd import synth
+
+    data = synth.make_synthetic(E, S, 700 + seed)
+    if mode == "M":
+        data = with_missing(data)
+    params = dict(synth.DEFAULT_PARAMS, n_procs=n_procs, n_chains=nc, n_cool=min(2, nc), n_iter=n_iter, n_burn=n_iter // 3,
+                  n_interval=5, step_size_z=6.0)
+    params.update(MODE[mode])
+    params.update(kw)
+    return data, params
+
+
+def _oracle(params, data, n_iter):
+    from oracle import oracle
+
+    job = oracle.Job({k: v for k, v in params.items() if k != "forward_precision"}, data)
+    job.run(n_iter)
+    return job
+
+
+def _assert_equals_oracle(sets, job, n_iter, rtol=RTOL_TRACE):
+    """every rank of the job: trace, iteration list, RNG state, every chain's final hypocentres and temperature; the counters summed
+    over the ranks; every proposal type (vs, t_corr, qs, a_corr, x, y, z: all enabled in these jobs) was proposed"""
+    npr = np.zeros(7, np.int64); nac = np.zeros(7, np.int64)
+    for r, cs in enumerate(sets):
+        it, lk = job.likelihood_trace(r)
+        gi, _, gl = cs.likelihood_trace()
+        assert len(gi) > 20 and np.array_equal(gi, it), "rank %d: recorded iterations differ" % r
+        np.testing.assert_allclose(gl, lk, rtol=rtol, atol=0)
+        assert cs.rng_state() == job.rng_state(r)
+        for c in range(cs.n_chains):
+            s, o = cs.state(c), job.chain(r, c)
+            np.testing.assert_allclose(s.hypo, o["hypo"], rtol=1e-11, atol=1e-12)
+            assert s.temp == o["temp"]
+        a, b = cs.counts()
+        npr += a; nac += b
+    oa, ob = job.counts()
+    assert np.array_equal(npr, oa) and np.array_equal(nac, ob)
+    assert np.all(npr > 0), "a proposal type did not occur: %s" % npr
+    assert np.any(npr[6] > nac[6]), "no depth step was rejected"
+
+
+def _single_rank(monkeypatch, E, S, nc, mode, seed, n_iter, env=None, loop=3, fixed=False, fp32=False, workers=None):
+    """one job on one rank: selection asserted, then the oracle.  env: the switches that select the loop.  A job with both data
+    types that is meant for the generic instantiation sets HTM_FAST=0; a job with one type leaves it unset, so that it is the
+    library that finds the specialisation and its packed records barred"""
+    for k in ("HTM_FAST", "HTM_MB", "HTM_FLOW", "HTM_PERSIST", "HTM_PIPE", "HTM_PIPE_LOCK", "HTM_MAX_WORKERS"):
+        monkeypatch.delenv(k, raising=False)
+    if not fixed and mode == "M":      # (A and T bar the specialisation by themselves: asserted below without the switch)
+        monkeypatch.setenv("HTM_FAST", "0")
+    for k, v in (env or {}).items():
+        monkeypatch.setenv(k, v)
+    data, params = _job(E, S, nc, mode, seed, n_iter, **(dict(forward_precision="fp32") if fp32 else {}))
+    _, sets = _build_world(data, params)
+    cs = sets[0]
+    assert cs.fwd.forward_precision == ("fp32" if fp32 else "fp64")
+    assert cs.master_stats()["single_rank_loop"] == loop, cs.master_stats()
+    if workers is not None:
+        assert cs.n_worker_blocks == workers
+    cs.run(n_iter)
+    assert cs.iterations_done == n_iter
+    assert cs.fixed_master() == fixed
+    if fixed:
+        assert cs.fwd.obs_pack_bytes() == _pack_bytes(E, S, fp32)
+    elif mode != "M":
+        assert cs.fwd.obs_pack_bytes() == 0, "one data type: no packed records"
+    _assert_equals_oracle([cs], _oracle(params, data, n_iter), n_iter, RTOL_FP32 if fp32 else RTOL_TRACE)
+    return cs
+
+
+@pytest.mark.parametrize("prec", ["fp64", "fp32"])
+@pytest.mark.parametrize("E,S,nc", [(3, 64, 1), (3, 64, 5), (3, 64, 8), (3, 128, 5)])
+def test_specialised_master_with_missing_entries(E, S, nc, prec, monkeypatch):
+    """k_mcmc<1 | 2, fp32?, 8>: missing data does not bar the specialisation; its packed records carry the precision-1 entries and
+    the reciprocal precision sums of the rows with missing data (load_obs_pack).  Equal to the oracle, and the same bits as the
+    generic instantiation (HTM_FAST=0), which reads the rows"""
+    n_iter = 600
+    fast = _single_rank(monkeypatch, E, S, nc, "M", 1, n_iter, fixed=True, fp32=prec == "fp32")
+    ref = _bits(fast)
+    gen = _single_rank(monkeypatch, E, S, nc, "M", 1, n_iter, fixed=False, fp32=prec == "fp32")
+    assert gen.fwd.obs_pack_bytes() == 0, "the generic master does not read packed records: none are built for it"
+    _assert_same_bits(ref, _bits(gen), "specialised vs generic")
+
+
+@pytest.mark.parametrize("mode", ["A", "T", "M"])
+@pytest.mark.parametrize("E,S,nc", [(7, 5, 3), (33, 64, 5), (33, 70, 5), (33, 200, 4)])
+def test_generic_free_running_master(E, S, nc, mode, monkeypatch):
+    """k_mcmc<1 | 2 | 4, false, 3>: fewer events than waves of a worker block, full rows, two stations per lane with a ragged
+    second chunk, four chunks"""
+    _single_rank(monkeypatch, E, S, nc, mode, 2, 700 if E == 7 else 500)
+
+
+@pytest.mark.parametrize("mode", ["A", "T"])
+@pytest.mark.parametrize("E,S,nc", [(3, 64, 8), (3, 128, 5)])
+def test_one_data_type_bars_the_specialised_master(E, S, nc, mode, monkeypatch):
+    """the shapes of test_specialised_master_with_missing_entries with one data type and no switch set: the library itself must
+    leave the specialised instantiation and its packed records (built for both types) alone -- k_mcmc<1 | 2, false, 3> -- as it
+    must at 33 x 64 x 5 in the test above"""
+    cs = _single_rank(monkeypatch, E, S, nc, mode, 6, 600)
+    assert not cs.fixed_master() and cs.fwd.obs_pack_bytes() == 0
+
+
+@pytest.mark.parametrize("mode", ["A", "M"])
+@pytest.mark.parametrize("loop", ["two chains on a wave", "two master workgroups", "barrier loop", "two-kernel path", "wide loop",
+                                  "pipelined master", "fp32 generic master", "fp32 workers, one block", "fp32 workers, one block, ragged rows"])
+def test_every_other_single_rank_loop(loop, mode, monkeypatch):
+    """the smallest shape that selects each loop (events x stations x chains, switches, asserted loop id, instantiation)"""
+    E, S, nc, env, code, kw = {
+        "two chains on a wave": (33, 64, 9, {"HTM_MB": "0"}, 3, {}),                    # k_mcmc<1, false, 3>, nine chains on eight waves
+        "two master workgroups": (33, 64, 12, {"HTM_MB": "1"}, 7, {}),                  # k_mcmc<1, false, 7>
+        "barrier loop": (33, 70, 5, {"HTM_FLOW": "0"}, 0, {}),                          # k_mcmc<2, false, 0>
+        "two-kernel path": (33, 64, 3, {"HTM_PERSIST": "0"}, -1, {}),                   # k_step<1, false> + k_full
+        "wide loop": (33, 70, 33, {}, 0, {}),                                           # k_mcmc_wide<2, false, 0>
+        "pipelined master": (33, 64, 8, {"HTM_PIPE": "1"}, 5, {}),                      # k_mcmc<1, false, 5>
+        "fp32 generic master": (33, 64, 5, {}, 3, dict(fp32=True)),                     # k_mcmc<1, true, 3>
+        # (one worker block: a worker wave takes four or five events, so the fp32 workers' two-ahead pipeline and its loads
+        # without branches run -- load_obs_regs_nobranch; with a block per eight events no wave has a second event)
+        "fp32 workers, one block": (33, 64, 5, {"HTM_MAX_WORKERS": "1"}, 3, dict(fp32=True, workers=1)),
+        "fp32 workers, one block, ragged rows": (33, 70, 5, {"HTM_MAX_WORKERS": "1"}, 3, dict(fp32=True, workers=1)),
+    }[loop]
+    _single_rank(monkeypatch, E, S, nc, mode, 3, 400 if nc > 8 else 500, env=env, loop=code, **kw)
+
+
+@pytest.mark.parametrize("mode", ["A", "M"])
+def test_lockstep_ranks(mode, monkeypatch):
+    """two ranks of four chains, one lock-step iteration per launch (k_mcmc<1, false, 1>), records exchanged by device copies"""
+    from hypotremormcmc_amd.parallel import LocalWorld
+
+    for k in ("HTM_FAST", "HTM_FLOW", "HTM_FLOW_LOCK", "HTM_MB", "HTM_PERSIST", "HTM_PIPE", "HTM_PIPE_LOCK", "HTM_MAX_WORKERS"):
+        monkeypatch.delenv(k, raising=False)
+    n_iter = 500
+    data, params = _job(33, 64, 4, mode, 4, n_iter, n_procs=2)
+    _, sets = _build_world(data, params)
+    # (what a persistent lock-step launch of these chain sets would run: the free-running master, k_mcmc<1, false, 4>;
+    # LocalWorld launches one iteration at a time, k_mcmc<1, false, 1>)
+    assert len(sets) == 2 and all(cs.master_stats()["lockstep_loop"] == 4 for cs in sets)
+    LocalWorld(sets).run(n_iter)
+    assert not any(cs.fixed_master() for cs in sets)
+    if mode == "A":
+        assert sets[0].fwd.obs_pack_bytes() == 0, "one data type: no packed records"
+    _assert_equals_oracle(sets, _oracle(params, data, n_iter), n_iter)
+
+
+def test_both_data_types_off_runs_on_the_prior_alone(monkeypatch):
+    """use_time = F and use_amp = F: the reference sums nothing (cls_forward.f90:277-300): a full evaluation gives exactly 0, a
+    one-event update hands the old value on, and every proposal the prior allows is accepted.  A chain starts at -9e300
+    (cls_mcmc.f90:88) and keeps that value through its hypocentre steps until a vs / qs / correction step evaluates in full, so
+    the oracle's records hold 0 and -9e300, nothing else.  The library takes the job and does the same: every record the very
+    same value, iterations, counters, RNG state and final states equal to the oracle's."""
+    n_iter = 700
+    data, params = _job(7, 5, 3, "A", 5, n_iter, use_amp="F")
+    for k in ("HTM_FAST", "HTM_FLOW", "HTM_PERSIST", "HTM_PIPE", "HTM_PIPE_LOCK", "HTM_MAX_WORKERS", "HTM_MB"):
+        monkeypatch.delenv(k, raising=False)
+    _, sets = _build_world(data, params)
+    cs = sets[0]
+    assert cs.master_stats()["single_rank_loop"] == 3
+    cs.run(n_iter)
+    assert not cs.fixed_master() and cs.fwd.obs_pack_bytes() == 0
+    job = _oracle(params, data, n_iter)
+    lk = job.likelihood_trace(0)[1]
+    assert set(lk.tolist()) <= {0.0, -9.0e300} and np.any(lk == 0.0)
+    gl = cs.likelihood_trace()[2]
+    assert np.array_equal(gl, lk)
+    _assert_equals_oracle([cs], job, n_iter)
+    h = data.ev_xyz.reshape(-1)
+    assert cs.fwd.calc_log_likelihood(h, np.zeros(5), 3.0, np.zeros(5), 250.0) == 0.0

@@ -23,7 +23,7 @@ def _need(binary):
     return path
 
 
-@pytest.mark.parametrize("name", ["c1", "missing", "timeonly"])
+@pytest.mark.parametrize("name", ["c1", "missing", "timeonly", "amponly"])
 def test_fortran_forward_shim_known_answers(name, tmp_path):
     fx, data, params = load_case(name)
     synth.write_dataset(str(tmp_path), data)

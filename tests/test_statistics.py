@@ -7,7 +7,7 @@ import pytest
 
 from tests.helpers import load_case
 
-STAT_CASES = ["c1", "c2", "missing", "timeonly", "fixedcorr"]
+STAT_CASES = ["c1", "c2", "missing", "timeonly", "amponly", "missing64", "fixedcorr"]
 
 
 def _samples_from_fixture(fx, n_procs):
