@@ -40,6 +40,20 @@ class ChainsInit(C.Structure):
     ]
 
 
+class PlanJob(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_chains", "n_procs", "n_sta", "n_events", "forward_fp32", "use_time", "use_amp")]
+
+
+class PlanDevice(C.Structure):
+    _fields_ = [("n_cu", C.c_int32), ("blocks_per_cu", C.c_int32), ("pipe_blocks_per_cu", C.c_int32 * 2)]
+
+
+class LaunchPlan(C.Structure):
+    SCALARS = ("persist", "flow", "flow_fixed", "wide", "flow_lock", "mb_blocks", "pipe", "pipe_lock", "pipe_smem", "pipe_ring",
+               "ring_size", "wmax", "step_smem", "worker_cap", "blocks_fit", "nw", "n_workers", "mirror_n", "mirror_steps")
+    _fields_ = [(n, C.c_int64) for n in SCALARS] + [("loop", (C.c_int64 * 2) * 3), ("loop_built", (C.c_int64 * 2) * 3)]
+
+
 # every symbol include/htm_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "htm_last_error": (C.c_char_p, []),
@@ -108,6 +122,8 @@ SIGNATURES = {
     "htm_chains_handoff_stats": (C.c_int, [vp, C.POINTER(C.c_int64)]),
     "htm_chains_master_stats": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "htm_chains_fixed_master": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "htm_chains_plan": (C.c_int, [C.POINTER(PlanJob), C.POINTER(PlanDevice), C.POINTER(LaunchPlan)]),
+    "htm_chains_get_plan": (C.c_int, [vp, C.POINTER(LaunchPlan), C.POINTER(PlanDevice)]),
     "htm_chains_last_run_stats": (C.c_int, [vp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "htm_chains_profile": (C.c_int, [vp, C.c_int, dp, C.POINTER(C.c_int), dp, C.POINTER(C.c_int),
                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -33,6 +33,35 @@ def _stack(models, attr, dtype):
     return np.ascontiguousarray(np.stack([getattr(m, attr) for m in models]).astype(dtype))
 
 
+def _plan_dict(p: _lib.LaunchPlan) -> dict:
+    d = {n: int(getattr(p, n)) for n in _lib.LaunchPlan.SCALARS}
+    d["loop"] = [[int(v) for v in row] for row in p.loop]      # [RUN, ADVANCE, LOCKRUN][without, with a step log]
+    d["loop_built"] = [[int(v) for v in row] for row in p.loop_built]
+    return d
+
+
+def _facts_dict(f: _lib.PlanDevice) -> dict:
+    return dict(n_cu=int(f.n_cu), blocks_per_cu=int(f.blocks_per_cu), pipe_blocks_per_cu=[int(v) for v in f.pipe_blocks_per_cu])
+
+
+def plan_chains(job: dict, device: dict) -> dict:
+    """The launch plan htm_chains_create would make for `job` (n_chains, n_procs, n_sta, n_events, forward_fp32, use_time,
+    use_amp) on a device with the facts `device` (n_cu, blocks_per_cu, pipe_blocks_per_cu), under the current HTM_*
+    environment.  Needs no GPU.  Raises HtmError with htm_chains_create's text for a shape it refuses."""
+    j = _lib.PlanJob(**{k: int(v) for k, v in job.items()})
+    f = _lib.PlanDevice(int(device["n_cu"]), int(device["blocks_per_cu"]), (C.c_int32 * 2)(*device["pipe_blocks_per_cu"]))
+    p = _lib.LaunchPlan()
+    check(_lib.load().htm_chains_plan(C.byref(j), C.byref(f), C.byref(p)))
+    return _plan_dict(p)
+
+
+def get_plan(handle):
+    """(plan, device facts seen) of the chain set behind a C handle"""
+    p = _lib.LaunchPlan(); f = _lib.PlanDevice()
+    check(_lib.load().htm_chains_get_plan(handle, C.byref(p), C.byref(f)))
+    return _plan_dict(p), _facts_dict(f)
+
+
 class ChainSet:
     """n_chains chains of one rank.  `models` is a list (one entry per chain) of dicts with the five
     reference models: hypo, t_corr, vs, a_corr, qs (each a `Model`)."""
@@ -258,6 +287,10 @@ class ChainSet:
         a = C.c_int(); b = C.c_int(); n = C.c_int64()
         check(self._lib.htm_chains_master_stats(self.handle, C.byref(a), C.byref(b), C.byref(n)))
         return dict(single_rank_loop=a.value, lockstep_loop=b.value, flushes=n.value)
+
+    def plan(self):
+        """the launch plan this chain set was created with and the device facts it saw (plan_chains gives the same from them)"""
+        return get_plan(self.handle)
 
     def fixed_master(self):
         """True if the latest single-rank launch ran the free-running master specialised on the job's shape"""

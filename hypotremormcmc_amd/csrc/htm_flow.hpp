@@ -198,7 +198,7 @@ struct FlowTop {
 // TR.  FlowGeneric answers "not known" to all of them -- the run-time fields decide, as they always did (every loop variant that
 // existed before the traits did compiles to what it compiled to).  FlowFixed answers with constants for the single-rank
 // free-running master of a job that the host has found to be: one rank, n_sta == 64 * NCH with both data types used, the LDS
-// mirror present with its step sizes (htm_hip.hip: flow_fixed_ok).  The answers remove selects, branches, address arithmetic and
+// mirror present with its step sizes (htm_plan.hpp: loop_for).  The answers remove selects, branches, address arithmetic and
 // the scalars that feed them; not a single rounding changes.  (Measured and not kept -- a wave's chain as a launch constant, the
 // step log compiled out, two rounds of partial-sum granules instead of four: docs/experiments/fast_master_more_traits.patch.)
 struct FlowGeneric {
@@ -1343,7 +1343,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
     return p + cnt;
 }
 
-// block 0 of a k_mcmc<NCH, F32, 0> launch when the host selects the free-running master (htm_hip.hip: hc->flow)
+// block 0 of a k_mcmc<NCH, F32, 0> launch when the host selects the free-running master (htm_plan.hpp: LoopPlan::flow)
 // (MB: one of several master workgroups of the launch -- block b runs chains 8 b .. 8 b + 7; returns true in the workgroup that
 // finishes last, which has written the launch's end state and releases the workers)
 template <int NCH, bool F32, bool LOCK = false, bool MB = false, class TR = FlowGeneric>

@@ -221,7 +221,12 @@ int htm_forward_create(int n_sta, int n_events, const double *sta_x, const doubl
     int rc = use_device(device);
     if (rc) return rc;
 
-    htm_forward *h = new htm_forward();
+    // (owns the handle until it is handed out: every early return destroys what was made so far)
+    struct Guard {
+        htm_forward *h;
+        ~Guard() { if (h) htm_forward_destroy(h); }
+    } guard{new htm_forward()};
+    htm_forward *h = guard.h;
     h->device = device; h->S = n_sta; h->E = n_events; h->nch = nch_for(n_sta);
     const size_t n = (size_t)n_sta * n_events;
 
@@ -248,10 +253,9 @@ int htm_forward_create(int n_sta, int n_events, const double *sta_x, const doubl
         pst[i] = st; psa[i] = sa;
     }
 
-    auto cleanup = [&](int code) { htm_forward_destroy(h); return code; };
     double *p = nullptr;
 #define UP(dst, src, cnt)                                          \
-    if ((rc = dev_upload(h->pool, &p, (src), (cnt)))) return cleanup(rc); \
+    if ((rc = dev_upload(h->pool, &p, (src), (cnt)))) return rc; \
     dst = p;
     UP(h->dev.sx, sta_x, n_sta) UP(h->dev.sy, sta_y, n_sta) UP(h->dev.sz, sta_z, n_sta)
     UP(h->dev.t_obs, t_obs, n) UP(h->dev.t_prec, tpr.data(), n)
@@ -269,18 +273,19 @@ int htm_forward_create(int n_sta, int n_events, const double *sta_x, const doubl
     h->epw = std::max(1, (n_events + 4 * 1024 - 1) / (4 * 1024));
     h->n_wg = (n_events + 4 * h->epw - 1) / (4 * h->epw);
 
-    if ((rc = dev_alloc(h->pool, &h->d_hypo, 3 * (size_t)n_events))) return cleanup(rc);
-    if ((rc = dev_alloc(h->pool, &h->d_tc, n_sta))) return cleanup(rc);
-    if ((rc = dev_alloc(h->pool, &h->d_ac, n_sta))) return cleanup(rc);
-    if ((rc = dev_alloc(h->pool, &h->d_scal, 16))) return cleanup(rc);
-    if ((rc = dev_alloc(h->pool, &h->d_partial, h->n_wg))) return cleanup(rc);
-    if ((rc = dev_alloc(h->pool, &h->d_syn, n))) return cleanup(rc);
+    if ((rc = dev_alloc(h->pool, &h->d_hypo, 3 * (size_t)n_events))) return rc;
+    if ((rc = dev_alloc(h->pool, &h->d_tc, n_sta))) return rc;
+    if ((rc = dev_alloc(h->pool, &h->d_ac, n_sta))) return rc;
+    if ((rc = dev_alloc(h->pool, &h->d_scal, 16))) return rc;
+    if ((rc = dev_alloc(h->pool, &h->d_partial, h->n_wg))) return rc;
+    if ((rc = dev_alloc(h->pool, &h->d_syn, n))) return rc;
     hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) return cleanup(fail(HTM_EHIP, "hipStreamCreate: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(HTM_EHIP, "hipStreamCreate: %s", hipGetErrorString(e));
     h->stream = h->own_stream;
     if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess)
-        return cleanup(fail(HTM_EHIP, "hipEventCreate failed"));
+        return fail(HTM_EHIP, "hipEventCreate failed");
     *out = h;
+    guard.h = nullptr;
     return HTM_OK;
 }
 

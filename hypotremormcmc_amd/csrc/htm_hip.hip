@@ -1,6 +1,6 @@
 // htm_hip.hip -- the chain sets' part of the C ABI (include/htm_hip.h): htm_chains_* and htm_comm_*.  (The forward model's part
-// is htm_forward.hip, the other steps' htm_steps.hip; this file keeps its name because most of it stayed where it was.)  Decides which chain-master
-// loop a launch takes (launch_mcmc) and looks its kernel up in the table of htm_host.hpp; the instantiations themselves are
+// is htm_forward.hip, the other steps' htm_steps.hip; this file keeps its name because most of it stayed where it was.)  Sets a chain set up from
+// its launch plan (htm_plan.hpp: which chain-master loop a launch takes, and its shape) and looks the loop's kernel up in the table of htm_host.hpp; the instantiations themselves are
 // compiled by the loop units (htm_loop_*.hip), none here.  This unit owns the small kernels of htm_chains_kernels.hpp.
 #include "htm_host.hpp"
 #include "htm_chains_kernels.hpp"
@@ -42,44 +42,25 @@ const LoopKernel *step_kernel(int nch, bool fp32, bool wide) { return find_row(t
 static int no_kernel(const htm_chains *hc, const char *what, int mk)
 {
     return fail(HTM_EINVAL, "no %s kernel is built for %d stations with the %s forward%s (loop %d)", what, hc->fwd->S,
-                hc->fwd->dev.fp32 ? "fp32" : "fp64", hc->wide ? ", more than 32 chains" : "", mk);
-}
-
-// The free-running master specialised on what the job fixes (flow_body<.., FlowFixed>): what htm_chains_create found
-// (hc->flow_fixed) and what can change afterwards -- the step log (diagnostic runs take the generic instantiation).
-static bool flow_fixed_ok(const htm_chains *hc)
-{
-    return hc->flow && hc->flow_fixed && hc->mb_blocks <= 1 && !hc->pipe && hc->h_ctrl.slog_cap == 0;
+                hc->fwd->dev.fp32 ? "fp32" : "fp64", hc->plan.wide ? ", more than 32 chains" : "", mk);
 }
 
 int launch_mcmc(htm_chains *hc, int mode, int target, const double *gathered)
 {
     htm_forward *h = hc->fwd;
-    const bool mb = mode == MODE_RUN && hc->flow && hc->mb_blocks > 1 && !hc->pipe;
+    const LoopPlan &lp = hc->plan;
     hc->ctrl_fresh = false;
+    // one instantiation per main loop (MK, htm_pipe.hpp k_mcmc); the step log can be switched on after htm_chains_create
+    const int mk = loop_for(lp, mode, hc->h_ctrl.slog_cap != 0);
     LoopLaunch l{};
-    l.grid = dim3((mb ? hc->mb_blocks : 1) + hc->dev.n_workers);
-    l.smem = hc->step_smem; l.stream = h->stream; l.f = &h->dev; l.cs = &hc->dev;
-    l.mode = mode; l.target = target; l.gathered = gathered; l.ring_size = hc->ring_size; l.wmax = hc->wmax;
+    l.grid = dim3((mk == 7 ? lp.mb_blocks : 1) + hc->dev.n_workers);
+    l.smem = lp.step_smem; l.stream = h->stream; l.f = &h->dev; l.cs = &hc->dev;
+    l.mode = mode; l.target = target; l.gathered = gathered; l.ring_size = lp.ring_size; l.wmax = lp.wmax;
     l.seq = ++hc->launch_seq;      // this chain set's k_mcmc launches, counted from 1
-    // one instantiation per main loop (MK, htm_pipe.hpp k_mcmc): the single-rank loop, one lock-step iteration per launch, persistent lock-step
-    int mk;
-    if (hc->wide) mk = mode == MODE_RUN ? 0 : mode == MODE_LOCKRUN ? 2 : 1;
-    else if (mode == MODE_RUN && hc->pipe) mk = 5;      // the pipelined master (htm_pipe.hpp): one or two stations per lane only
-    else if (mode == MODE_LOCKRUN && hc->pipe_lock) mk = 6;
-    else if (mb) mk = 7;
-    else if (mode == MODE_RUN && flow_fixed_ok(hc)) {      // (one or two stations per lane: flow_fixed)
-        if (!h->dev.obs_pack) return fail(HTM_EINVAL, "the specialised chain master needs the forward's packed records");
-        hc->last_fixed = true;
-        mk = 8;
-    }
-    else if (mode == MODE_RUN && hc->flow) { hc->last_fixed = false; mk = 3; }
-    else if (mode == MODE_RUN) mk = 0;
-    else if (mode == MODE_LOCKRUN && hc->flow_lock) mk = 4;
-    else if (mode == MODE_LOCKRUN) mk = 2;
-    else mk = 1;
-    if (mk == 5 || mk == 6) { l.smem = hc->pipe_smem; l.ring_size = hc->pipe_ring; }      // (its own LDS layout and stream window)
-    const LoopKernel *k = mcmc_kernel(h->nch, h->dev.fp32 != 0, mk, hc->wide);
+    if (mk == 8 && !h->dev.obs_pack) return fail(HTM_EINVAL, "the specialised chain master needs the forward's packed records");
+    if (mode == MODE_RUN) hc->last_fixed = mk == 8;
+    if (mk == 5 || mk == 6) { l.smem = lp.pipe_smem; l.ring_size = lp.pipe_ring; }      // (its own LDS layout and stream window)
+    const LoopKernel *k = mcmc_kernel(h->nch, h->dev.fp32 != 0, mk, lp.wide);
     if (!k) return no_kernel(hc, "k_mcmc", mk);
     // several master workgroups: what their chains share lives in memory (MbShared), set up by a one-wave kernel first
     if (mk == 7) hipLaunchKernelGGL(k_mb_init, dim3(1), dim3(64), 0, h->stream, hc->dev, target);
@@ -93,12 +74,12 @@ int launch_step(htm_chains *hc, int mode, int target, const double *gathered)
 {
     htm_forward *h = hc->fwd;
     hc->ctrl_fresh = false;
-    const LoopKernel *k = step_kernel(h->nch, h->dev.fp32 != 0, hc->wide);
+    const LoopKernel *k = step_kernel(h->nch, h->dev.fp32 != 0, hc->plan.wide);
     if (!k) return no_kernel(hc, "k_step", 0);
     LoopLaunch l{};
-    l.grid = dim3(1); l.block = dim3(64 * hc->nw);
-    l.smem = hc->step_smem; l.stream = h->stream; l.f = &h->dev; l.cs = &hc->dev_np;
-    l.mode = mode; l.target = target; l.gathered = gathered; l.ring_size = hc->ring_size; l.wmax = hc->wmax;
+    l.grid = dim3(1); l.block = dim3(64 * hc->plan.nw);
+    l.smem = hc->plan.step_smem; l.stream = h->stream; l.f = &h->dev; l.cs = &hc->dev_np;
+    l.mode = mode; l.target = target; l.gathered = gathered; l.ring_size = hc->plan.ring_size; l.wmax = hc->plan.wmax;
     k->launch(l);
     HIPCHK(hipGetLastError());
     return HTM_OK;
@@ -156,24 +137,50 @@ FullJob chain_full_job(htm_chains *hc)
 
 }  // namespace
 
-// ====================================================================================================
-extern "C" {
-
 // ---------------------------------------------------------------------------------------------------
 // chains
 // ---------------------------------------------------------------------------------------------------
-// Worker blocks of a persistent launch: as many as fit (one per CU next to the master's), at most one per `waves_per_block` events.
-// A full evaluation takes as long as its busiest wave, which evaluates ceil(E / (waves per block x blocks)) events: at 10 000
-// events and 8 waves per block 250 blocks give five rounds where 240 gave six (+8 % at 10 000 x 128 x 16 fp32, +6 % at 10 000 x 64 x 8).
-// (Taking the SMALLEST block count that reaches the same number of rounds was measured too: -1 % -- the waves with a round less
-// leave the memory system to the others sooner.)
-static int worker_blocks(int E, int waves_per_block, long cap)
+namespace {
+
+static_assert(MODE_RUN == kPlanModeRun && MODE_ADVANCE == kPlanModeAdvance && MODE_LOCKRUN == kPlanModeLockrun,
+              "htm_plan.hpp and htm_device.hpp disagree on the modes");
+
+// Owns a handle under construction: every early return of htm_chains_create and of the functions it calls destroys what was
+// made so far (htm_chains_destroy tolerates a half-built handle); released on success.
+struct ChainsGuard {
+    htm_chains *hc;
+    ~ChainsGuard() { if (hc) htm_chains_destroy(hc); }
+    htm_chains *release() { htm_chains *p = hc; hc = nullptr; return p; }
+};
+
+PlanSizes plan_sizes(int nc)
 {
-    return (int)std::max<long>(1, std::min<long>(std::max<long>(1, cap), (E + waves_per_block - 1) / waves_per_block));
+    PlanSizes s;
+    s.flow_shared = sizeof(FlowShared); s.wide_shared = sizeof(StepSharedT<kMaxWideChains>); s.pipe_shared = sizeof(PipeShared);
+    s.pipe_ring_bytes = pipe_ring_bytes(nc);
+    s.gath_stage = kGathStage; s.hops = kHops; s.pipe_threads_nch1 = mcmc_threads<1, 5>();
+    s.max_chains = kMaxChains; s.gran_per_slot = kGranPerSlot; s.max_slot_replicas = kMaxSlotReplicas;
+    return s;
+}
+
+void export_plan(const LoopPlan &lp, int n_workers, int mirror_n, int mirror_steps, int nch, bool fp32, htm_launch_plan *o)
+{
+    *o = htm_launch_plan{};
+    o->persist = lp.persist; o->flow = lp.flow; o->flow_fixed = lp.flow_fixed; o->wide = lp.wide; o->flow_lock = lp.flow_lock;
+    o->mb_blocks = lp.mb_blocks; o->pipe = lp.pipe; o->pipe_lock = lp.pipe_lock; o->pipe_smem = (int64_t)lp.pipe_smem;
+    o->pipe_ring = lp.pipe_ring; o->ring_size = lp.ring_size; o->wmax = lp.wmax; o->step_smem = (int64_t)lp.step_smem;
+    o->worker_cap = lp.worker_cap; o->blocks_fit = lp.blocks_fit; o->nw = lp.nw;
+    o->n_workers = n_workers; o->mirror_n = mirror_n; o->mirror_steps = mirror_steps;
+    const int modes[3] = {MODE_RUN, MODE_ADVANCE, MODE_LOCKRUN};
+    for (int m = 0; m < 3; ++m)
+        for (int s = 0; s < 2; ++s) {
+            o->loop[m][s] = loop_for(lp, modes[m], s != 0);
+            o->loop_built[m][s] = mcmc_kernel(nch, fp32, (int)o->loop[m][s], lp.wide) ? 1 : 0;
+        }
 }
 
 // one group of the rank's parameter vector: a window [off, off + nx*nc) of the five per-field allocations
-static int upload_model(htm_chains *hc, ModelDev &m, const htm_model_init &in, int nx, int nc, size_t off, const char *name)
+int upload_model(htm_chains *hc, ModelDev &m, const htm_model_init &in, int nx, int nc, size_t off, const char *name)
 {
     if (!in.x) return fail(HTM_EINVAL, "%s.x is NULL", name);
     const size_t n = (size_t)nx * nc;
@@ -191,6 +198,280 @@ static int upload_model(htm_chains *hc, ModelDev &m, const htm_model_init &in, i
     return HTM_OK;
 }
 
+// ---- what htm_chains_create allocates and uploads, group by group.  Each returns at its first failure; the caller's guard
+// ---- frees what was made.
+int alloc_params(htm_chains *hc, const htm_chains_init *init, const Knobs &kn)
+{
+    htm_forward *h = hc->fwd;
+    ChainsDev &d = hc->dev;
+    const int nc = d.n_chains;
+    int rc;
+    // [vs | t_corr | qs | a_corr | hypo], the order of the proposal types (chain_pass computes these offsets too)
+    const size_t S = (size_t)h->S, E = (size_t)h->E, n = (size_t)nc;
+    const size_t total = 2 * n + 2 * n * S + 3 * E * n;
+    if ((rc = dev_alloc(hc->pool, &d.xall, total)) || (rc = dev_alloc(hc->pool, &d.muall, total)) ||
+        (rc = dev_alloc(hc->pool, &d.sgall, total)) || (rc = dev_alloc(hc->pool, &d.stall, total)) ||
+        (rc = dev_alloc(hc->pool, &d.ptall, total))) return rc;
+    if ((rc = upload_model(hc, d.vs, init->vs, 1, nc, 0, "vs"))) return rc;
+    if ((rc = upload_model(hc, d.tc, init->t_corr, h->S, nc, n, "t_corr"))) return rc;
+    if ((rc = upload_model(hc, d.qs, init->qs, 1, nc, n + n * S, "qs"))) return rc;
+    if ((rc = upload_model(hc, d.ac, init->a_corr, h->S, nc, 2 * n + n * S, "a_corr"))) return rc;
+    if ((rc = upload_model(hc, d.hypo, init->hypo, 3 * h->E, nc, 2 * n + 2 * n * S, "hypo"))) return rc;
+    {
+        std::vector<double> sg(total), r2(total);
+        HIPCHK(hipMemcpy(sg.data(), d.sgall, total * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < total; ++k) r2[k] = 1.0 / (2.0 * sg[k] * sg[k]);
+        if ((rc = dev_upload(hc->pool, &d.rs2all, r2.data(), total))) return rc;
+        // the packed records the chain steps read (PriorRec), and whether every chain has chain 0's
+        std::vector<double> mu(total), stp(total);
+        std::vector<int32_t> pt(total);
+        HIPCHK(hipMemcpy(mu.data(), d.muall, total * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(stp.data(), d.stall, total * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(pt.data(), d.ptall, total * sizeof(int32_t), hipMemcpyDeviceToHost));
+        std::vector<PriorRec> pr(total);
+        for (size_t k = 0; k < total; ++k) { pr[k].mu = mu[k]; pr[k].rs2 = r2[k]; pr[k].step = stp[k]; pr[k].ptype = pt[k]; pr[k].pad = 0; }
+        bool same = true;
+        const size_t goffs[5] = {0, n, n + n * S, 2 * n + n * S, 2 * n + 2 * n * S}, gnx[5] = {1, S, 1, S, 3 * E};
+        for (int gi = 0; gi < 5 && same; ++gi)
+            for (size_t c = 1; c < n && same; ++c)
+                same = memcmp(&pr[goffs[gi] + c * gnx[gi]], &pr[goffs[gi]], gnx[gi] * sizeof(PriorRec)) == 0;
+        if (!kn.prior_same) same = false;      // (diagnostics: every chain reads its own records)
+        PriorRec *dp = nullptr;
+        if ((rc = dev_upload(hc->pool, &dp, pr.data(), total))) return rc;
+        d.prior = dp; d.prior_same = same ? 1 : 0;
+    }
+    d.rayleigh14 = 0;
+    auto any_rayleigh = [](const htm_model_init &m, size_t cnt) {
+        if (!m.prior_type) return false;
+        for (size_t k = 0; k < cnt; ++k) if (m.prior_type[k] == 1) return true;
+        return false;
+    };
+    if (any_rayleigh(init->vs, n) || any_rayleigh(init->qs, n) || any_rayleigh(init->t_corr, n * S) ||
+        any_rayleigh(init->a_corr, n * S)) d.rayleigh14 = 1;
+    return HTM_OK;
+}
+
+int alloc_chain_state(htm_chains *hc, const htm_chains_init *init)
+{
+    htm_forward *h = hc->fwd;
+    ChainsDev &d = hc->dev;
+    const int nc = d.n_chains;
+    int rc;
+    if ((rc = dev_upload(hc->pool, &d.temp, init->temp, nc))) return rc;
+    std::vector<double> L0(nc, -9.e+300);   // cls_mcmc.f90:88
+    if ((rc = dev_upload(hc->pool, &d.L, L0.data(), nc))) return rc;
+    std::vector<int32_t> z7(7 * (size_t)nc, 0);
+    if ((rc = dev_upload(hc->pool, &d.n_propose, z7.data(), z7.size()))) return rc;
+    if ((rc = dev_upload(hc->pool, &d.n_accept, z7.data(), z7.size()))) return rc;
+    // proposal probabilities, cls_mcmc.f90:91-106, and the cumulative sums of :139-153 in the same order
+    const double p_vs = init->solve_vs ? 0.025 : 0.0, p_tc = init->solve_t_corr ? 0.025 : 0.0;
+    const double p_qs = init->solve_qs ? 0.025 : 0.0, p_ac = init->solve_a_corr ? 0.025 : 0.0;
+    d.th1 = p_vs; d.th2 = p_vs + p_tc; d.th3 = p_vs + p_tc + p_qs; d.th4 = p_vs + p_tc + p_qs + p_ac;
+    d.n_burn = init->n_burn; d.n_interval = init->n_interval;
+    if ((rc = dev_alloc(hc->pool, &d.prop, nc))) return rc;
+    HIPCHK(hipMemset(d.prop, 0, nc * sizeof(Proposal)));
+    if ((rc = dev_alloc(hc->pool, &d.desc, 1))) return rc;
+    HIPCHK(hipMemset(d.desc, 0, sizeof(FullDesc)));
+    if ((rc = dev_alloc(hc->pool, &d.partial, (size_t)nc * std::max(h->n_wg, 256)))) return rc;      // (<= 256 workers whatever the launch shape)
+    if ((rc = dev_alloc(hc->pool, &d.ps, 1))) return rc;
+    HIPCHK(hipMemset(d.ps, 0, sizeof(PSync)));
+    return HTM_OK;
+}
+
+// the control block: last, as it always was (the groups allocate in the order htm_chains_create has always allocated in, so
+// that a chain set's buffers lie where they lay)
+int upload_ctrl(htm_chains *hc)
+{
+    Ctrl c{};
+    c.spos = 0;
+    c.stage = ST_IDLE;
+    hc->h_ctrl = c;
+    return dev_upload(hc->pool, &hc->dev.ctrl, &c, 1);
+}
+
+// the hand-off area between the master's chain waves and the worker blocks (its geometry: the plan), and the
+// swap record that the rank hands to the other ranks
+int alloc_handoff(htm_chains *hc)
+{
+    ChainsDev &d = hc->dev;
+    const int nc = d.n_chains;
+    int rc;
+    if ((rc = dev_alloc(hc->pool, &d.slots, (size_t)d.slot_rep * d.slot_stride))) return rc;
+    HIPCHK(hipMemset(d.slots, 0, (size_t)d.slot_rep * d.slot_stride * sizeof(unsigned long long)));
+    unsigned long long *mbw = nullptr;
+    if ((rc = dev_alloc(hc->pool, &mbw, sizeof(MbShared) / sizeof(unsigned long long)))) return rc;
+    d.mb = reinterpret_cast<MbShared *>(mbw);
+    if ((rc = dev_alloc(hc->pool, &d.prev_mid, (size_t)nc))) return rc;
+    HIPCHK(hipMemset(d.prev_mid, 0, (size_t)nc * sizeof(int)));
+    if ((rc = dev_alloc(hc->pool, &d.lo_gran, (size_t)nc * 16))) return rc;
+    HIPCHK(hipMemset(d.lo_gran, 0, (size_t)nc * 16 * sizeof(unsigned long long)));
+    if ((rc = dev_alloc(hc->pool, &d.pgran, (size_t)nc * 256 * d.pgran_stride))) return rc;
+    HIPCHK(hipMemset(d.pgran, 0, (size_t)nc * 256 * d.pgran_stride * sizeof(unsigned long long)));
+    if ((rc = dev_alloc(hc->pool, &d.swap_rec, 4 + 2 * (size_t)nc))) return rc;
+    HIPCHK(hipMemset(d.swap_rec, 0, (4 + 2 * (size_t)nc) * sizeof(double)));
+    return HTM_OK;
+}
+
+int alloc_records(htm_chains *hc, const htm_chains_init *init)
+{
+    htm_forward *h = hc->fwd;
+    ChainsDev &d = hc->dev;
+    const int nc = d.n_chains;
+    int rc;
+    hc->rec_len = 3 * h->E + 2 * h->S + 2;
+    d.cap_lik = init->lik_capacity > 0 ? init->lik_capacity : 1 << 16;
+    if (init->sample_capacity > 0) d.cap_smp = init->sample_capacity;
+    else d.cap_smp = (int)std::max<size_t>(4 * (size_t)nc, std::min<size_t>(4096, (size_t(128) << 20) / (hc->rec_len * sizeof(double))));
+    if (d.cap_lik < 2 * nc || d.cap_smp < 2 * nc) return fail(HTM_EINVAL, "record capacities must be >= 2*n_chains");
+    if ((rc = dev_alloc(hc->pool, &d.lik_iter, d.cap_lik))) return rc;
+    if ((rc = dev_alloc(hc->pool, &d.lik_chain, d.cap_lik))) return rc;
+    if ((rc = dev_alloc(hc->pool, &d.lik_val, d.cap_lik))) return rc;
+    if ((rc = dev_alloc(hc->pool, &d.smp_iter, d.cap_smp))) return rc;
+    if ((rc = dev_alloc(hc->pool, &d.smp_chain, d.cap_smp))) return rc;
+    if ((rc = dev_alloc(hc->pool, &d.smp_data, (size_t)d.cap_smp * hc->rec_len))) return rc;
+    d.slog_i = nullptr; d.slog_d = nullptr;
+    // (and the diagnostic words: ChainsDev::diag, the phase stamps of a diagnostic build)
+    if ((rc = dev_alloc(hc->pool, &d.diag, 32))) return rc;
+    HIPCHK(hipMemset(d.diag, 0, 32 * sizeof(unsigned long long)));
+    d.stamps = nullptr;
+#ifdef HTM_STAMPS
+    if ((rc = dev_alloc(hc->pool, &d.stamps, 128 + 2 * 8192))) return rc;      // (+ the event trace of htm_pipe.hpp)
+    HIPCHK(hipMemset(d.stamps, 0, (128 + 2 * 8192) * sizeof(unsigned long long)));
+#endif
+    return HTM_OK;
+}
+
+// random-stream service: hc->cap positions of every table (htm_stream.hpp), the generator state and its jump table
+int alloc_stream(htm_chains *hc, const htm_chains_init *init)
+{
+    ChainsDev &d = hc->dev;
+    int rc;
+    hc->th[0] = d.th1; hc->th[1] = d.th2; hc->th[2] = d.th3; hc->th[3] = d.th4;
+    for (int k = 0; k < 4; ++k) hc->init_state[k] = init->rng_state[k];
+    StreamDev &sd = d.stream;
+    const size_t n = (size_t)hc->cap;
+    sd.mask = hc->cap - 1;
+    if ((rc = dev_alloc(hc->pool, &sd.raw, n))) return rc;
+    if ((rc = dev_alloc(hc->pool, &sd.U, n))) return rc;
+    if ((rc = dev_alloc(hc->pool, &sd.LOGU, n))) return rc;
+    if ((rc = dev_alloc(hc->pool, &sd.G, n))) return rc;
+    if ((rc = dev_alloc(hc->pool, &sd.pg, n))) return rc;
+    if ((rc = dev_alloc(hc->pool, &sd.pr, n))) return rc;
+    if ((rc = dev_alloc(hc->pool, &sd.plogr, n))) return rc;
+    if ((rc = dev_alloc(hc->pool, &sd.dec, n))) return rc;
+    if ((rc = dev_alloc(hc->pool, &sd.hop, n * kHops))) return rc;
+    if ((rc = dev_alloc(hc->pool, &sd.sw, n))) return rc;
+    uint32_t g8[8] = {hc->init_state[0], hc->init_state[1], hc->init_state[2], hc->init_state[3], 0, 0, 0, 0};
+    if ((rc = dev_upload(hc->pool, &sd.gen, g8, 8))) return rc;
+    hc->gen_par = 0;
+    const std::vector<Mat128> &P = xs_powers();
+    std::vector<u32x4> jt((size_t)kJumpLevels * 128);
+    for (int b = 0; b < kJumpLevels; ++b)
+        for (int j = 0; j < 128; ++j) {
+            const Bits128 &c = P[6 + b][j];
+            jt[(size_t)b * 128 + j] = u32x4{c.w[0], c.w[1], c.w[2], c.w[3]};
+        }
+    if ((rc = dev_upload(hc->pool, &hc->d_jump, jt.data(), jt.size()))) return rc;
+    const long long zero = 0;
+    return dev_upload(hc->pool, &sd.hop_end, &zero, 1);
+}
+
+int create_events(htm_chains *hc)
+{
+    hipError_t e1 = hipStreamCreateWithFlags(&hc->side, hipStreamNonBlocking);
+    hipError_t e2 = hipEventCreateWithFlags(&hc->ev_side, hipEventDisableTiming);
+    if (e1 != hipSuccess || e2 != hipSuccess) return fail(HTM_EHIP, "side stream/event creation failed");
+    if (hipEventCreateWithFlags(&hc->ev_wd, hipEventDisableTiming) != hipSuccess) return fail(HTM_EHIP, "hipEventCreate failed");
+    if (hipEventCreate(&hc->ev0) != hipSuccess || hipEventCreate(&hc->ev1) != hipSuccess) return fail(HTM_EHIP, "hipEventCreate failed");
+    return HTM_OK;
+}
+
+// What phase B of the plan needs from the device (PlanDevice).  A kernel that is to be launched with more than 48 KiB of
+// dynamic LDS has its limit raised here, before its occupancy is asked.
+int device_facts(htm_chains *hc, const Plan &a, const PlanJob &job, const Knobs &kn, PlanDevice *f)
+{
+    htm_forward *h = hc->fwd;
+    const bool fp32 = h->dev.fp32 != 0, wide = a.loop.wide;
+    const size_t smem = a.loop.step_smem;
+    if (smem > 48 * 1024) {
+        const LoopKernel *ks = step_kernel(h->nch, fp32, wide);
+        if (!ks) return no_kernel(hc, "k_step", 0);
+        HIPCHK(hipFuncSetAttribute(ks->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    }
+    if (!a.loop.persist) return HTM_OK;
+    // every loop a launch of this chain set can take (loop_for); several master workgroups (MK 7) and the free-running
+    // master specialised on the job's shape (MK 8) exist for one or two stations per lane
+    std::vector<int> mks = {0, 1, 2};
+    if (!wide) { mks.push_back(3); mks.push_back(4); }
+    if (!wide && (h->nch == 1 || h->nch == 2)) { mks.push_back(7); mks.push_back(8); }
+    // the residency bound holds for whichever main loop gets launched: the smallest of the instantiations' occupancies
+    std::vector<const void *> fns;
+    for (int mk : mks) {
+        const LoopKernel *k = mcmc_kernel(h->nch, fp32, mk, wide);
+        if (!k) return no_kernel(hc, "k_mcmc", mk);
+        fns.push_back(k->fn);
+    }
+    if (smem > 48 * 1024)
+        for (const void *g : fns) HIPCHK(hipFuncSetAttribute(g, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    int per_cu = 1 << 20;
+    for (const void *g : fns) {
+        int pc = 0;
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, g, 512, smem));
+        per_cu = std::min(per_cu, pc);
+    }
+    HIPCHK(hipDeviceGetAttribute(&f->n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
+    f->blocks_per_cu = per_cu;
+    // the pipelined master's two loops, when one is asked for and the persistent launch stands (which these facts decide)
+    Plan r = a;
+    plan_residency(r, job, kn, *f);
+    if (!a.pipe_asked || !r.loop.persist) return HTM_OK;
+    for (int lk = 5; lk <= 6; ++lk) {
+        const LoopKernel *pk = mcmc_kernel(h->nch, fp32, lk, false);
+        if (!pk) return no_kernel(hc, "k_mcmc", lk);
+        if (a.pipe_smem_want > 48 * 1024) HIPCHK(hipFuncSetAttribute(pk->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.pipe_smem_want));
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&f->pipe_blocks_per_cu[lk - 5], pk->fn, a.pipe_threads, a.pipe_smem_want));
+    }
+    return HTM_OK;
+}
+
+}  // namespace
+
+// ====================================================================================================
+extern "C" {
+
+int htm_chains_plan(const htm_plan_job *job, const htm_plan_device *device, htm_launch_plan *plan)
+{
+    if (!job || !device || !plan) return fail(HTM_EINVAL, "NULL argument");
+    if (job->n_chains < 1 || job->n_chains > HTM_MAX_CHAINS)
+        return fail(HTM_EINVAL, "n_chains must be in 1..%d (HTM_MAX_CHAINS), got %d", HTM_MAX_CHAINS, job->n_chains);
+    if (job->n_procs < 1) return fail(HTM_EINVAL, "bad rank/n_procs");
+    if (job->n_sta <= 0 || job->n_events <= 0) return fail(HTM_EINVAL, "n_sta and n_events must be positive");
+    PlanJob j;
+    j.nc = job->n_chains; j.n_procs = job->n_procs; j.S = job->n_sta; j.E = job->n_events; j.nch = nch_for(job->n_sta);
+    j.fp32 = job->forward_fp32 != 0; j.use_time = job->use_time != 0; j.use_amp = job->use_amp != 0;
+    if (j.fp32 && j.nch != 1 && j.nch != 2) return fail(HTM_EINVAL, "the fp32 forward covers n_sta <= 128 (this handle has %d stations)", j.S);
+    const Knobs kn = read_knobs();
+    const Plan a = plan_phase_a(j, kn, plan_sizes(j.nc));
+    if (a.refused[0]) return fail(HTM_EINVAL, "%s", a.refused);
+    PlanDevice f;
+    f.n_cu = device->n_cu; f.blocks_per_cu = device->blocks_per_cu;
+    f.pipe_blocks_per_cu[0] = device->pipe_blocks_per_cu[0]; f.pipe_blocks_per_cu[1] = device->pipe_blocks_per_cu[1];
+    const Plan p = plan_phase_b(a, j, kn, f);
+    export_plan(p.loop, p.n_workers, p.mirror_n, p.mirror_steps, j.nch, j.fp32, plan);
+    return HTM_OK;
+}
+
+int htm_chains_get_plan(htm_chains *hc, htm_launch_plan *plan, htm_plan_device *seen)
+{
+    if (!hc || !plan) return fail(HTM_EINVAL, "NULL argument");
+    export_plan(hc->plan, hc->dev.n_workers, hc->dev.mirror_n, hc->dev.mirror_steps, hc->fwd->nch, hc->fwd->dev.fp32 != 0, plan);
+    if (seen) {
+        seen->n_cu = hc->seen.n_cu; seen->blocks_per_cu = hc->seen.blocks_per_cu;
+        seen->pipe_blocks_per_cu[0] = hc->seen.pipe_blocks_per_cu[0]; seen->pipe_blocks_per_cu[1] = hc->seen.pipe_blocks_per_cu[1];
+    }
+    return HTM_OK;
+}
+
 int htm_chains_create(htm_forward *h, const htm_chains_init *init, htm_chains **out)
 {
     if (!out) return fail(HTM_EINVAL, "out is NULL");
@@ -202,380 +483,52 @@ int htm_chains_create(htm_forward *h, const htm_chains_init *init, htm_chains **
     if (init->n_procs < 1 || init->rank < 0 || init->rank >= init->n_procs) return fail(HTM_EINVAL, "bad rank/n_procs");
     if (init->n_interval < 1) return fail(HTM_EINVAL, "n_interval must be >= 1");
     if (!init->temp) return fail(HTM_EINVAL, "temp is NULL");
-    if (h->nch == 4) {
-        // k_step holds two candidate positions in registers; 256 stations exceed the budget -> generic path
-    }
     HIPCHK(hipSetDevice(h->device));
-    htm_chains *hc = new htm_chains();
+
+    const Knobs kn = read_knobs();
+    PlanJob job;
+    job.nc = nc; job.n_procs = init->n_procs; job.S = h->S; job.E = h->E; job.nch = h->nch;
+    job.fp32 = h->dev.fp32 != 0; job.use_time = h->dev.use_time != 0; job.use_amp = h->dev.use_amp != 0;
+    const Plan a = plan_phase_a(job, kn, plan_sizes(nc));
+
+    ChainsGuard guard{new htm_chains()};
+    htm_chains *hc = guard.hc;
     hc->fwd = h;
-    hc->wide = nc > kMaxChains;
-    auto cleanup = [&](int code) { htm_chains_destroy(hc); return code; };
-    int rc;
+    hc->plan = a.loop;
+    hc->cap = a.stream_cap;
     ChainsDev &d = hc->dev;
     d.n_chains = nc; d.n_procs = init->n_procs; d.rank = init->rank; d.S = h->S; d.E = h->E;
-    {
-        // [vs | t_corr | qs | a_corr | hypo], the order of the proposal types (chain_pass computes these offsets too)
-        const size_t S = (size_t)h->S, E = (size_t)h->E, n = (size_t)nc;
-        const size_t total = 2 * n + 2 * n * S + 3 * E * n;
-        if ((rc = dev_alloc(hc->pool, &d.xall, total)) || (rc = dev_alloc(hc->pool, &d.muall, total)) ||
-            (rc = dev_alloc(hc->pool, &d.sgall, total)) || (rc = dev_alloc(hc->pool, &d.stall, total)) ||
-            (rc = dev_alloc(hc->pool, &d.ptall, total))) return cleanup(rc);
-        if ((rc = upload_model(hc, d.vs, init->vs, 1, nc, 0, "vs"))) return cleanup(rc);
-        if ((rc = upload_model(hc, d.tc, init->t_corr, h->S, nc, n, "t_corr"))) return cleanup(rc);
-        if ((rc = upload_model(hc, d.qs, init->qs, 1, nc, n + n * S, "qs"))) return cleanup(rc);
-        if ((rc = upload_model(hc, d.ac, init->a_corr, h->S, nc, 2 * n + n * S, "a_corr"))) return cleanup(rc);
-        if ((rc = upload_model(hc, d.hypo, init->hypo, 3 * h->E, nc, 2 * n + 2 * n * S, "hypo"))) return cleanup(rc);
-        {
-            std::vector<double> sg(total), r2(total);
-            HIPCHK(hipMemcpy(sg.data(), d.sgall, total * sizeof(double), hipMemcpyDeviceToHost));
-            for (size_t k = 0; k < total; ++k) r2[k] = 1.0 / (2.0 * sg[k] * sg[k]);
-            if ((rc = dev_upload(hc->pool, &d.rs2all, r2.data(), total))) return cleanup(rc);
-            // the packed records the chain steps read (PriorRec), and whether every chain has chain 0's
-            std::vector<double> mu(total), stp(total);
-            std::vector<int32_t> pt(total);
-            HIPCHK(hipMemcpy(mu.data(), d.muall, total * sizeof(double), hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(stp.data(), d.stall, total * sizeof(double), hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(pt.data(), d.ptall, total * sizeof(int32_t), hipMemcpyDeviceToHost));
-            std::vector<PriorRec> pr(total);
-            for (size_t k = 0; k < total; ++k) { pr[k].mu = mu[k]; pr[k].rs2 = r2[k]; pr[k].step = stp[k]; pr[k].ptype = pt[k]; pr[k].pad = 0; }
-            bool same = true;
-            const size_t goffs[5] = {0, n, n + n * S, 2 * n + n * S, 2 * n + 2 * n * S}, gnx[5] = {1, S, 1, S, 3 * E};
-            for (int gi = 0; gi < 5 && same; ++gi)
-                for (size_t c = 1; c < n && same; ++c)
-                    same = memcmp(&pr[goffs[gi] + c * gnx[gi]], &pr[goffs[gi]], gnx[gi] * sizeof(PriorRec)) == 0;
-            if (const char *e = getenv("HTM_PRIOR_SAME")) { if (e[0] == '0') same = false; }      // (diagnostics: every chain reads its own records)
-            PriorRec *dp = nullptr;
-            if ((rc = dev_upload(hc->pool, &dp, pr.data(), total))) return cleanup(rc);
-            d.prior = dp; d.prior_same = same ? 1 : 0;
-        }
-        d.rayleigh14 = 0;
-        auto any_rayleigh = [](const htm_model_init &m, size_t cnt) {
-            if (!m.prior_type) return false;
-            for (size_t k = 0; k < cnt; ++k) if (m.prior_type[k] == 1) return true;
-            return false;
-        };
-        if (any_rayleigh(init->vs, n) || any_rayleigh(init->qs, n) || any_rayleigh(init->t_corr, n * S) ||
-            any_rayleigh(init->a_corr, n * S)) d.rayleigh14 = 1;
-    }
-    if ((rc = dev_upload(hc->pool, &d.temp, init->temp, nc))) return cleanup(rc);
-    std::vector<double> L0(nc, -9.e+300);   // cls_mcmc.f90:88
-    if ((rc = dev_upload(hc->pool, &d.L, L0.data(), nc))) return cleanup(rc);
-    std::vector<int32_t> z7(7 * (size_t)nc, 0);
-    if ((rc = dev_upload(hc->pool, &d.n_propose, z7.data(), z7.size()))) return cleanup(rc);
-    if ((rc = dev_upload(hc->pool, &d.n_accept, z7.data(), z7.size()))) return cleanup(rc);
-    // proposal probabilities, cls_mcmc.f90:91-106, and the cumulative sums of :139-153 in the same order
-    const double p_vs = init->solve_vs ? 0.025 : 0.0, p_tc = init->solve_t_corr ? 0.025 : 0.0;
-    const double p_qs = init->solve_qs ? 0.025 : 0.0, p_ac = init->solve_a_corr ? 0.025 : 0.0;
-    d.th1 = p_vs; d.th2 = p_vs + p_tc; d.th3 = p_vs + p_tc + p_qs; d.th4 = p_vs + p_tc + p_qs + p_ac;
-    d.n_burn = init->n_burn; d.n_interval = init->n_interval;
     d.n_wg = h->n_wg;
-    if ((rc = dev_alloc(hc->pool, &d.prop, nc))) return cleanup(rc);
-    if ((rc = dev_alloc(hc->pool, &d.desc, 1))) return cleanup(rc);
-    HIPCHK(hipMemset(d.desc, 0, sizeof(FullDesc)));
-    int worker_cap = 250;          // of 256 CUs: the master's, and a few to spare
-    if (const char *e = getenv("HTM_WORKER_CAP")) worker_cap = std::max(1, std::min(255, atoi(e)));      // (tuning)
-    hc->worker_cap = worker_cap;
-    d.n_workers = worker_blocks(h->E, 8, worker_cap);
-    if (const char *e = getenv("HTM_MAX_WORKERS")) d.n_workers = std::max(1, std::min(d.n_workers, atoi(e)));   // GPUs shared between ranks
-    if ((rc = dev_alloc(hc->pool, &d.partial, (size_t)nc * std::max(h->n_wg, 256)))) return cleanup(rc);      // (<= 256 workers whatever the launch shape)
-    if ((rc = dev_alloc(hc->pool, &d.ps, 1))) return cleanup(rc);
-    HIPCHK(hipMemset(d.ps, 0, sizeof(PSync)));
-    {
-        // hand-off geometry (tuning knobs; defaults measured on MI355X)
-        auto env_int = [](const char *name, int dflt, int lo, int hi) {
-            const char *e = getenv(name);
-            const int v = e ? atoi(e) : dflt;
-            return std::max(lo, std::min(hi, v));
-        };
-        d.slot_rep = env_int("HTM_SLOT_REPLICAS", 1, 1, kMaxSlotReplicas);
-        d.slot_stride = env_int("HTM_SLOT_STRIDE", 4096, std::max(nc, kMaxChains) * kGranPerSlot * 8, 1 << 22) / 8;     // bytes -> words
-        d.pgran_stride = env_int("HTM_PGRAN_STRIDE", 16, 16, 4096) / 8;
-        d.npoll = env_int("HTM_NPOLL", 1, 1, 3);
-    }
-    if ((rc = dev_alloc(hc->pool, &d.slots, (size_t)d.slot_rep * d.slot_stride))) return cleanup(rc);
-    HIPCHK(hipMemset(d.slots, 0, (size_t)d.slot_rep * d.slot_stride * sizeof(unsigned long long)));
-    {
-        unsigned long long *mbw = nullptr;
-        if ((rc = dev_alloc(hc->pool, &mbw, sizeof(MbShared) / sizeof(unsigned long long)))) return cleanup(rc);
-        d.mb = reinterpret_cast<MbShared *>(mbw);
-    }
-    if ((rc = dev_alloc(hc->pool, &d.prev_mid, (size_t)nc))) return cleanup(rc);
-    HIPCHK(hipMemset(d.prev_mid, 0, (size_t)nc * sizeof(int)));
-    if ((rc = dev_alloc(hc->pool, &d.lo_gran, (size_t)nc * 16))) return cleanup(rc);
-    HIPCHK(hipMemset(d.lo_gran, 0, (size_t)nc * 16 * sizeof(unsigned long long)));
-    if ((rc = dev_alloc(hc->pool, &d.pgran, (size_t)nc * 256 * d.pgran_stride))) return cleanup(rc);
-    HIPCHK(hipMemset(d.pgran, 0, (size_t)nc * 256 * d.pgran_stride * sizeof(unsigned long long)));
-    {
-        const char *env = getenv("HTM_PERSIST");
-        hc->persist = !(env && env[0] == '0');
-    }
-    if ((rc = dev_alloc(hc->pool, &d.swap_rec, 4 + 2 * (size_t)nc))) return cleanup(rc);
-    HIPCHK(hipMemset(d.prop, 0, nc * sizeof(Proposal)));
-    HIPCHK(hipMemset(d.swap_rec, 0, (4 + 2 * (size_t)nc) * sizeof(double)));
+    d.n_workers = a.n_workers; d.mirror_n = a.mirror_n; d.mirror_steps = a.mirror_steps;
+    d.slot_rep = a.slot_rep; d.slot_stride = a.slot_stride; d.pgran_stride = a.pgran_stride; d.npoll = a.npoll;
+    d.dbg = kn.dbg; d.xwait_ticks = kn.xwait_ticks; d.dbg_xfail_iter = kn.xfail_iter; d.xown = kn.xown;
 
-    hc->rec_len = 3 * h->E + 2 * h->S + 2;
-    d.cap_lik = init->lik_capacity > 0 ? init->lik_capacity : 1 << 16;
-    if (init->sample_capacity > 0) d.cap_smp = init->sample_capacity;
-    else d.cap_smp = (int)std::max<size_t>(4 * (size_t)nc, std::min<size_t>(4096, (size_t(128) << 20) / (hc->rec_len * sizeof(double))));
-    if (d.cap_lik < 2 * nc || d.cap_smp < 2 * nc) return cleanup(fail(HTM_EINVAL, "record capacities must be >= 2*n_chains"));
-    if ((rc = dev_alloc(hc->pool, &d.lik_iter, d.cap_lik))) return cleanup(rc);
-    if ((rc = dev_alloc(hc->pool, &d.lik_chain, d.cap_lik))) return cleanup(rc);
-    if ((rc = dev_alloc(hc->pool, &d.lik_val, d.cap_lik))) return cleanup(rc);
-    if ((rc = dev_alloc(hc->pool, &d.smp_iter, d.cap_smp))) return cleanup(rc);
-    if ((rc = dev_alloc(hc->pool, &d.smp_chain, d.cap_smp))) return cleanup(rc);
-    if ((rc = dev_alloc(hc->pool, &d.smp_data, (size_t)d.cap_smp * hc->rec_len))) return cleanup(rc);
-    d.slog_i = nullptr; d.slog_d = nullptr;
-    { const char *e = getenv("HTM_DEBUG_NO_DROP"); d.dbg = (e && atoi(e) != 0) ? 1 : 0; }
-    { const char *e = getenv("HTM_XCHG_TIMEOUT_MS"); const double ms = e ? atof(e) : 20000.0; d.xwait_ticks = (unsigned long long)(std::max(1.0, ms) * 1.0e5); }
-    { const char *e = getenv("HTM_DEBUG_XCHG_FAIL_ITER"); d.dbg_xfail_iter = e ? atoi(e) : 0; }
-    { const char *e = getenv("HTM_XOWN"); d.xown = (e && e[0] == '0') ? 0 : 1; }
-    if ((rc = dev_alloc(hc->pool, &d.diag, 32))) return cleanup(rc);
-    HIPCHK(hipMemset(d.diag, 0, 32 * sizeof(unsigned long long)));
-    d.stamps = nullptr;
-#ifdef HTM_STAMPS
-    if ((rc = dev_alloc(hc->pool, &d.stamps, 128 + 2 * 8192))) return cleanup(rc);      // (+ the event trace of htm_pipe.hpp)
-    HIPCHK(hipMemset(d.stamps, 0, (128 + 2 * 8192) * sizeof(unsigned long long)));
-#endif
+    int rc;
+    if ((rc = alloc_params(hc, init, kn))) return rc;
+    if ((rc = alloc_chain_state(hc, init))) return rc;
+    if ((rc = alloc_handoff(hc))) return rc;
+    if ((rc = alloc_records(hc, init))) return rc;
+    if ((rc = alloc_stream(hc, init))) return rc;
+    if ((rc = create_events(hc))) return rc;
+    if ((rc = upload_ctrl(hc))) return rc;
+    // (where the LDS budget has always been checked: after the arguments that the allocations above look at)
+    if (a.refused[0]) return fail(HTM_EINVAL, "%s", a.refused);
 
-    // random-stream service
-    hc->th[0] = d.th1; hc->th[1] = d.th2; hc->th[2] = d.th3; hc->th[3] = d.th4;
-    for (int k = 0; k < 4; ++k) hc->init_state[k] = init->rng_state[k];
-    hc->cap = 1 << 20;     // stream positions kept in HBM (~100 B each)
-    if (const char *e = getenv("HTM_STREAM_CAP")) {          // power of two >= 2^17 (tests: ring wrap-around in short runs)
-        long long v = atoll(e), c2 = 1 << 17;
-        while (c2 < v && c2 < (1ll << 24)) c2 <<= 1;
-        hc->cap = c2;
-    }
-    {
-        StreamDev &sd = d.stream;
-        const size_t n = (size_t)hc->cap;
-        sd.mask = hc->cap - 1;
-        if ((rc = dev_alloc(hc->pool, &sd.raw, n))) return cleanup(rc);
-        if ((rc = dev_alloc(hc->pool, &sd.U, n))) return cleanup(rc);
-        if ((rc = dev_alloc(hc->pool, &sd.LOGU, n))) return cleanup(rc);
-        if ((rc = dev_alloc(hc->pool, &sd.G, n))) return cleanup(rc);
-        if ((rc = dev_alloc(hc->pool, &sd.pg, n))) return cleanup(rc);
-        if ((rc = dev_alloc(hc->pool, &sd.pr, n))) return cleanup(rc);
-        if ((rc = dev_alloc(hc->pool, &sd.plogr, n))) return cleanup(rc);
-        if ((rc = dev_alloc(hc->pool, &sd.dec, n))) return cleanup(rc);
-        if ((rc = dev_alloc(hc->pool, &sd.hop, n * kHops))) return cleanup(rc);
-        if ((rc = dev_alloc(hc->pool, &sd.sw, n))) return cleanup(rc);
-        {
-            uint32_t g8[8] = {hc->init_state[0], hc->init_state[1], hc->init_state[2], hc->init_state[3], 0, 0, 0, 0};
-            if ((rc = dev_upload(hc->pool, &sd.gen, g8, 8))) return cleanup(rc);
-            hc->gen_par = 0;
-            const std::vector<Mat128> &P = xs_powers();
-            std::vector<u32x4> jt((size_t)kJumpLevels * 128);
-            for (int b = 0; b < kJumpLevels; ++b)
-                for (int j = 0; j < 128; ++j) {
-                    const Bits128 &c = P[6 + b][j];
-                    jt[(size_t)b * 128 + j] = u32x4{c.w[0], c.w[1], c.w[2], c.w[3]};
-                }
-            if ((rc = dev_upload(hc->pool, &hc->d_jump, jt.data(), jt.size()))) return cleanup(rc);
-        }
-        const long long zero = 0;
-        if ((rc = dev_upload(hc->pool, &sd.hop_end, &zero, 1))) return cleanup(rc);
-    }
-    {
-        hipError_t e1 = hipStreamCreateWithFlags(&hc->side, hipStreamNonBlocking);
-        hipError_t e2 = hipEventCreateWithFlags(&hc->ev_side, hipEventDisableTiming);
-        if (e1 != hipSuccess || e2 != hipSuccess) return cleanup(fail(HTM_EHIP, "side stream/event creation failed"));
-    }
-
-    Ctrl c{};
-    c.spos = 0;
-    c.stage = ST_IDLE;
-    hc->h_ctrl = c;
-    if ((rc = dev_upload(hc->pool, &d.ctrl, &c, 1))) return cleanup(rc);
-
-    hc->nw = std::min(nc, 8);
-    // stream window: a chain step draws <= 6 numbers, select_pair/judge_swap a few more (cls_parallel.f90:226-230)
-    hc->wmax = ((6 * nc + 16 + 63) / 64) * 64;
-    // LDS of the master: the stream window -- two iterations + their swaps ahead where it fits (role P sends orders two
-    // iterations ahead), else one -- and the mirror of (vs, t_corr, qs, a_corr) x all chains + their step sizes that
-    // role P reads (without it no orders are sent ahead).  Per ring position: U, LOGU, pg, pr, plogr (5 doubles), dec,
-    // sw (int4), hop (kHops ints).
-    // (the wide kernels' LDS layout is step_body's at kMaxWideChains; every narrow loop shares FlowShared's)
-    const size_t shared_bytes = hc->wide ? sizeof(StepSharedT<kMaxWideChains>) : sizeof(FlowShared);
-    const size_t lds_fixed = ((shared_bytes + 15) & ~size_t(15)) + 3 * (size_t)h->S * sizeof(double) + kGathStage * sizeof(double);
-    const size_t lds_pos = 5 * sizeof(double) + 2 * sizeof(int4) + kHops * sizeof(int);
-    const size_t mir = 2 * (size_t)nc + 2 * (size_t)nc * h->S;
-    const size_t lds_cap = 156 * 1024;
-    // (sized by what an iteration can really draw, 6 per chain step + the swap's, not by wmax's rounding to 64: at 16 chains
-    // the two-iteration window then fits a 512-position ring instead of 1024 -- half the LDS, so the mirror fits too)
-    const int wdraw = 6 * nc + 16;
-    // Several master workgroups (9..16 chains, k_mcmc<.., 7>): a workgroup's window is kept by the wave of its FIRST chain, and
-    // that chain can be two iterations ahead of a chain of its own workgroup that sat in a full evaluation (its turn asks the
-    // later chains for their checks of the iteration before only).  The late chain then adopts an anchor that lies up to three
-    // iterations behind the keeper's position: the ring must hold the look-ahead (3 wd + 24) AND three iterations + the spread of
-    // eight chains behind it, or the anchor's table entries have been overwritten by positions one ring further on (the
-    // mismatch of profiles/r04_z_mb_open_issue.txt: a base computed from evicted entries).  With two chains per wave -- one
-    // workgroup -- the keeper cannot get further than one iteration ahead, and up to eight chains leave the ring mostly empty.
-    const int mb_need = (3 * wdraw + 24) + (3 * wdraw + 16) + 6 * 8 + 16;
-    bool mb_want = nc > 8 && nc <= 16 && d.n_procs == 1 && (h->nch == 1 || h->nch == 2) && !(getenv("HTM_MB") && getenv("HTM_MB")[0] == '0');
-    // The same rule for the free-running loop of ONE workgroup with a wave per chain (up to eight chains; single rank and lock-step
-    // ranks): the keeper's wave runs chain 0 only and gets as far ahead of a late chain.  (More than eight chains on one
-    // workgroup: the keeper's wave has two chains and meets every other chain's check within an iteration.)  Rings of 256
-    // positions -- 4 and 5 chains -- were too short for it by this count; HTM_RING_SLACK=0 keeps the old sizes (A/B only).
-    const bool slack = !(getenv("HTM_RING_SLACK") && getenv("HTM_RING_SLACK")[0] == '0');
-    const int fr_need = (nc <= 8 && slack) ? (3 * wdraw + 24) + (3 * wdraw + 16) : 0;
-    auto ring_for = [&](int look) { int r = 256; while (r < look * wdraw + 64 || r < fr_need || (mb_want && r < mb_need)) r *= 2; return r; };
-    hc->dev.mirror_n = 0; hc->dev.mirror_steps = 0;
-    for (int pass = 0; pass < 2; ++pass) {
-        hc->ring_size = ring_for(2);
-        // preference: long window + values + step sizes, long window + values, short window + both, short + values, nothing
-        const int looks[4] = {4, 4, 2, 2}, steps[4] = {1, 0, 1, 0};
-        for (int k = 0; k < 4; ++k)
-            if (lds_fixed + (size_t)ring_for(looks[k]) * lds_pos + (1 + steps[k]) * mir * sizeof(double) <= lds_cap) {
-                hc->ring_size = ring_for(looks[k]); hc->dev.mirror_n = (int)mir; hc->dev.mirror_steps = steps[k];
-                break;
-            }
-        if (hc->dev.mirror_n > 0 || !mb_want) break;
-        mb_want = false;      // (the longer ring does not fit beside the mirror: one workgroup, the usual ring)
-    }
-    hc->step_smem = lds_fixed + (size_t)hc->ring_size * lds_pos + (1 + hc->dev.mirror_steps) * (size_t)hc->dev.mirror_n * sizeof(double);
-    if (hc->step_smem > lds_cap && hc->wide)
-        return cleanup(fail(HTM_EINVAL, "%d chains x %d stations: the loop with barriers needs %zu B of LDS, more than the %zu B budget", nc, h->S,
-                            hc->step_smem, lds_cap));
-    if (hc->step_smem > lds_cap) return cleanup(fail(HTM_EINVAL, "n_chains / n_sta too large for k_step's LDS budget"));
-    if (hc->step_smem > 48 * 1024) {
-        const LoopKernel *ks = step_kernel(h->nch, h->dev.fp32 != 0, hc->wide);
-        if (!ks) return cleanup(no_kernel(hc, "k_step", 0));
-        HIPCHK(hipFuncSetAttribute(ks->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hc->step_smem));
-    }
-    if (hipEventCreateWithFlags(&hc->ev_wd, hipEventDisableTiming) != hipSuccess) return cleanup(fail(HTM_EHIP, "hipEventCreate failed"));
-    if (hipEventCreate(&hc->ev0) != hipSuccess || hipEventCreate(&hc->ev1) != hipSuccess)
-        return cleanup(fail(HTM_EHIP, "hipEventCreate failed"));
-    hc->dev_np = hc->dev;                       // same state; partial sums laid out per k_full tile
-    if (hc->step_smem < 1024) hc->step_smem = 1024;
-    if (hc->persist) {
-        // Master and workers of a k_mcmc launch wait for each other, so every block must be RESIDENT: never ask for more
-        // worker blocks than the device can hold next to the master (a partitioned or CU-masked GPU has fewer CUs; every
-        // block carries the master's LDS size).  Workers take events round-robin, so fewer of them only take longer.
-        // every loop a launch of this chain set can take (launch_mcmc); several master workgroups (MK 7) and the free-running
-        // master specialised on the job's shape (MK 8) exist for one or two stations per lane
-        std::vector<int> mks = {0, 1, 2};
-        if (!hc->wide) { mks.push_back(3); mks.push_back(4); }
-        if (!hc->wide && (h->nch == 1 || h->nch == 2)) { mks.push_back(7); mks.push_back(8); }
-        std::vector<const void *> fns;
-        for (int mk : mks) {
-            const LoopKernel *k = mcmc_kernel(h->nch, h->dev.fp32 != 0, mk, hc->wide);
-            if (!k) return cleanup(no_kernel(hc, "k_mcmc", mk));
-            fns.push_back(k->fn);
-        }
-        if (hc->step_smem > 48 * 1024)
-            for (const void *g : fns) HIPCHK(hipFuncSetAttribute(g, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hc->step_smem));
-        // the residency bound holds for whichever main loop gets launched: the smallest of the instantiations' occupancies
-        int per_cu = 1 << 20, n_cu = 0;
-        for (const void *g : fns) {
-            int pc = 0;
-            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, g, 512, hc->step_smem));
-            per_cu = std::min(per_cu, pc);
-        }
-        HIPCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
-        hc->blocks_fit = (long)per_cu * n_cu;
-        long room = (long)per_cu * n_cu - 1;
-        // Several ranks on one GPU (more masters instead of more rounds per master: 4 ranks x 8 chains run 2.7 M steps/s where one
-        // rank x 32 chains runs 1.7 M): every rank's blocks must be resident at once, so each takes its share of the CUs
-        if (const char *e = getenv("HTM_RANKS_PER_GPU")) {
-            const int k = atoi(e);
-            const long per_xcd = (long)per_cu * n_cu / 8;      // (blocks are dealt to the 8 XCDs in turn: htm_chains_share_gpu)
-            if (k > 1) room = per_xcd >= k ? 8 * (per_xcd / k) - 1 : (long)per_cu * n_cu / k - 1;
-        }
-        if (room < 1) hc->persist = false;      // not even one worker fits next to the master: two-kernel path
-        else if (hc->dev.n_workers > room) hc->dev.n_workers = worker_blocks(h->E, 8, room);
-    }
-    hc->dev.n_wg = hc->dev.n_workers;           // persistent kernel: one partial per worker block
-    {
-        // The free-running master (htm_flow.hpp) runs the single-rank loop when its stream window fits: three iterations of
-        // look-ahead + one behind + the spread of chain 0's wave over its chains (flow_step's window extension), and the LDS
-        // mirror the orders are computed from.  HTM_FLOW=0 keeps the loop with barriers (step_body); so do the hand-off tests'
-        // debug switches.
-        const char *e = getenv("HTM_FLOW");
-        const int wd = 6 * nc + 16, c_max = 8 * ((nc - 1) / 8);
-        // More than kMaxChains chains: the loop with barriers whatever HTM_FLOW / HTM_MB / HTM_PIPE say (hc->wide).
-        const bool window_ok = hc->persist && !hc->wide && !(e && e[0] == '0') && d.dbg == 0 && hc->dev.mirror_n > 0 &&
-                               hc->ring_size >= 4 * wd + 32 + 2 * c_max + 16;
-        hc->flow = window_ok && d.n_procs == 1;
-        // Its instantiation specialised on what the job fixes (FlowFixed, htm_flow.hpp): one rank, up to eight chains (a wave per
-        // chain: the shapes it is tested and measured at), full rows of 64 or 128 stations with both data types, the mirror with its
-        // step sizes.  Chosen from what the library observes; HTM_FAST=0 only forces the generic instantiation (A/B runs, tests).
-        // The step log can be switched on after this point: launch_mcmc looks at it (flow_fixed_ok).
-        {
-            const char *ef = getenv("HTM_FAST");
-            hc->flow_fixed = hc->flow && !(ef && ef[0] == '0') && nc <= 8 && (h->nch == 1 || h->nch == 2) && h->S == 64 * h->nch &&
-                             h->dev.use_time != 0 && h->dev.use_amp != 0 && hc->dev.mirror_n == (int)mir && hc->dev.mirror_steps != 0;
-            // (its steps read an event's observations from one packed record: built here, once per forward and precision)
-            if (hc->flow_fixed) {
-                h->pack_wanted = true;
-                if ((rc = ensure_obs_pack(h))) return cleanup(rc);
-            }
-        }
-        // More than eight chains on a rank: a master workgroup for every eight (k_mcmc<.., 7>, htm_flow.hpp MbShared) instead of
-        // rounds on the same eight waves.
-        {
-            // (HTM_MB=0: one workgroup.  The ring was sized for several above: mb_want, mb_need)
-            const bool on = mb_want && hc->ring_size >= mb_need;
-            // (9..16 chains: two workgroups.  More would need more of the stream window per step than the one wave of a workgroup that
-            // keeps it can load -- 128 positions, an iteration of 16 chains takes ~90)
-            if (hc->flow && on && nc > 8 && nc <= 16 && (h->nch == 1 || h->nch == 2)) {
-                const int nb = (nc + 7) / 8;
-                if (hc->blocks_fit - nb >= 1) {
-                    hc->mb_blocks = nb;
-                    const long room = hc->blocks_fit - nb;
-                    if (hc->dev.n_workers > room) { hc->dev.n_workers = worker_blocks(h->E, 8, room); hc->dev.n_wg = hc->dev.n_workers; }
-                }
-            }
-        }
-        hc->flow_lock = window_ok && d.n_procs <= 60 && !(getenv("HTM_FLOW_LOCK") && getenv("HTM_FLOW_LOCK")[0] == '0');      // (MODE_LOCKRUN: up to 60 ranks -- a lane per rank reads its stop word, flow_xload)
-        // The pipelined master (htm_pipe.hpp; HTM_PIPE=0 keeps the free-running one): front / evaluators / decider over an LDS ring
-        // of iteration slots.  Needs the LDS mirror of the non-hypocentre parameters (what its evaluators read) and one or two
-        // stations per lane.
-        {
-            const char *ep = getenv("HTM_PIPE");
-            const int wdp = 6 * nc + 16;
-            int ring = 512;
-            while (ring < 2 * wdp + 160) ring *= 2;
-            const size_t mirp = 2 * (size_t)nc + 2 * (size_t)nc * h->S;
-            const size_t smem = ((sizeof(PipeShared) + 15) & ~size_t(15)) + (size_t)ring * lds_pos + (3 * (size_t)h->S + kGathStage) * sizeof(double) +
-                                mirp * sizeof(double) + pipe_ring_bytes(nc);
-            // (opt-in, HTM_PIPE=1 / HTM_PIPE_LOCK=1: on one CU it matches the free-running master -- 4.8 us per iteration at 1000 x 64 x 8,
-            // +8 % at 16 chains, profiles/r04_pipe_*.txt -- and does not beat it; DESIGN.md 3.6 says what it is for)
-            const char *epl = getenv("HTM_PIPE_LOCK");
-            const bool usable = hc->persist && !hc->wide && d.dbg == 0 && (h->nch == 1 || h->nch == 2) && smem <= lds_cap &&
-                                hc->dev.mirror_n == (int)mirp;      // (the mirror is part of every loop's LDS layout: one size for all)
-            hc->pipe = usable && d.n_procs == 1 && ep && ep[0] == '1';
-            hc->pipe_lock = usable && epl && epl[0] == '1' &&
-                            (size_t)d.n_procs * (4 + 2 * (size_t)nc) <= (size_t)kGathStage;      // (MODE_LOCKRUN: any number of ranks)
-            if (hc->pipe || hc->pipe_lock) {
-                hc->pipe_smem = smem; hc->pipe_ring = ring;
-                int n_cu2 = 0;
-                HIPCHK(hipDeviceGetAttribute(&n_cu2, hipDeviceAttributeMultiprocessorCount, h->device));
-                const int pthreads = h->nch == 1 ? mcmc_threads<1, 5>() : 512;
-                if (pthreads == 768) {
-                    // (12-wave blocks: a worker block takes 12 events; every loop of this chain set then runs with this many blocks)
-                    int nw = worker_blocks(h->E, 12, hc->worker_cap);
-                    if (const char *e3 = getenv("HTM_MAX_WORKERS")) nw = std::max(1, std::min(nw, atoi(e3)));
-                    if (const char *e4 = getenv("HTM_RANKS_PER_GPU")) { const int k = atoi(e4); if (k > 1) nw = std::min<long>(nw, std::max<long>(1, hc->blocks_fit / k - 1)); }
-                    hc->dev.n_workers = std::min(hc->dev.n_workers, nw); hc->dev.n_wg = hc->dev.n_workers;
-                }
-                for (int lk = 5; lk <= 6; ++lk) {
-                    const LoopKernel *pk = mcmc_kernel(h->nch, h->dev.fp32 != 0, lk, false);
-                    if (!pk) return cleanup(no_kernel(hc, "k_mcmc", lk));
-                    const void *pfn = pk->fn;
-                    int pc = 0;
-                    if (smem > 48 * 1024) HIPCHK(hipFuncSetAttribute(pfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-                    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, pfn, pthreads, smem));
-                    hc->blocks_fit = std::min<long>(hc->blocks_fit, (long)pc * n_cu2);
-                    if ((long)pc * n_cu2 - 1 < hc->dev.n_workers) { if (lk == 5) hc->pipe = false; else hc->pipe_lock = false; }      // (the launch shape was sized for the other loops: keep it)
-                }
-            }
-        }
+    hc->dev_np = hc->dev;                       // same state; partial sums laid out per k_full tile, the worker count before its residency cap
+    if ((rc = device_facts(hc, a, job, kn, &hc->seen))) return rc;
+    const Plan p = plan_phase_b(a, job, kn, hc->seen);
+    hc->plan = p.loop;
+    d.n_workers = p.n_workers;
+    d.n_wg = d.n_workers;                       // persistent kernel: one partial per worker block
+    // (the specialised master's steps read an event's observations from one packed record: built here, once per forward and precision)
+    if (p.loop.flow_fixed) {
+        h->pack_wanted = true;
+        if ((rc = ensure_obs_pack(h))) return rc;
     }
     // first stretch of the random stream (synchronous)
-    if ((rc = stream_produce(hc, 1 << 16))) return cleanup(rc);
+    if ((rc = stream_produce(hc, 1 << 16))) return rc;
     HIPCHK(hipStreamSynchronize(hc->side));
-    *out = hc;
+    *out = guard.release();
     return HTM_OK;
 }
 
@@ -730,7 +683,7 @@ static int drain_records(htm_chains *hc)
         HIPCHK(hipMemcpy(hc->smp_data.data() + o * hc->rec_len, d.smp_data, (size_t)ns * hc->rec_len * sizeof(double),
                          hipMemcpyDeviceToHost));
     }
-    if (hc->flow || hc->flow_lock) {
+    if (hc->plan.flow || hc->plan.flow_lock) {
         // the free-running master hands out record slots as its waves get to them: put the drained records into the
         // reference's order, iteration by iteration and chain by chain (hypo_tremor_mcmc.f90:270-280)
         auto order = [](size_t n, const int32_t *it, const int32_t *ch) {
@@ -843,7 +796,7 @@ int htm_chains_run(htm_chains *hc, int n_iter)
     int rc = read_ctrl(hc);
     if (rc) return rc;
     if (hc->h_ctrl.stage == ST_WAIT_SWAP) return fail(HTM_ESTATE, "a lock-step iteration is in flight");
-    if (hc->persist && hc->h_ctrl.stage == ST_IDLE) return run_persistent(hc, n_iter);
+    if (hc->plan.persist && hc->h_ctrl.stage == ST_IDLE) return run_persistent(hc, n_iter);
     if ((rc = build_graph(hc))) return rc;
     hc->h_target = hc->h_ctrl.iter_done + n_iter;
     HIPCHK(hipMemcpyAsync(&hc->dev.ctrl->iter_target, &hc->h_target, sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -947,15 +900,15 @@ int htm_chains_step_begin(htm_chains *hc)
     hc->h_target += 1;
     int rc;
     // an iteration consumes at most wmax draws; keep the produced stream safely ahead of that bound
-    hc->spos_hi += hc->wmax;
-    if (hc->n_hop - hc->spos_hi < 4 * (long long)hc->wmax) {
+    hc->spos_hi += hc->plan.wmax;
+    if (hc->n_hop - hc->spos_hi < 4 * (long long)hc->plan.wmax) {
         if ((rc = read_ctrl(hc))) return rc;              // exact position (also frees ring capacity)
         if ((rc = ctrl_error(hc))) return rc;
-        hc->spos_hi += hc->wmax;
+        hc->spos_hi += hc->plan.wmax;
         if ((rc = stream_produce(hc, 1 << 16))) return rc;
         HIPCHK(hipStreamWaitEvent(h->stream, hc->ev_side, 0));
     }
-    if (hc->persist) {       // whole iteration (full evaluations included) in one launch
+    if (hc->plan.persist) {       // whole iteration (full evaluations included) in one launch
         rc = launch_mcmc(hc, MODE_ADVANCE, hc->h_target, hc->pending_gathered);
         hc->pending_gathered = nullptr;
         return rc;
@@ -1044,7 +997,7 @@ int htm_chains_xchg_connect(htm_chains *hc, const void *handles, size_t handle_b
     const ChainsDev &d0 = hc->dev;
     if (d0.n_procs > 1 && (!handles || handle_bytes < sizeof(hipIpcMemHandle_t)))
         return fail(HTM_EINVAL, "handles of all %d ranks are needed", d0.n_procs);
-    if (!hc->persist) return fail(HTM_ESTATE, "the in-kernel exchange needs the persistent kernel (HTM_PERSIST=0 is set)");
+    if (!hc->plan.persist) return fail(HTM_ESTATE, "the in-kernel exchange needs the persistent kernel (HTM_PERSIST=0 is set)");
     if ((size_t)d0.n_procs * (4 + 2 * d0.n_chains) > (size_t)kGathStage)
         return fail(HTM_EINVAL, "%d ranks x %d chains: the gathered records do not fit the kernel's staging area", d0.n_procs, d0.n_chains);
     HIPCHK(hipSetDevice(hc->fwd->device));
@@ -1464,14 +1417,10 @@ int htm_chains_get_state(htm_chains *hc, int chain, double *hypo, double *t_corr
 int htm_chains_share_gpu(htm_chains *hc, int ranks_on_this_gpu)
 {
     if (!hc || ranks_on_this_gpu < 1) return fail(HTM_EINVAL, "bad argument");
-    if (getenv("HTM_RANKS_PER_GPU") || !hc->persist || ranks_on_this_gpu == 1) return HTM_OK;      // (an explicit setting stands)
+    if (ranks_per_gpu_knob(nullptr) || !hc->plan.persist || ranks_on_this_gpu == 1) return HTM_OK;      // (an explicit setting, HTM_RANKS_PER_GPU, stands)
     // (a chain set that has already run keeps the launch shape it ran with: ADVICE r3 -- a world built around it must not fail)
     if (hc->launch_seq > 0) return HTM_OK;
-    // Blocks go to the 8 XCDs of the GPU in turn, every launch starting with the first: a rank's blocks must be spread evenly over
-    // them (a multiple of 8) and the ranks' shares of one XCD's CUs must add up to no more than it has -- 5 ranks x 51 blocks are
-    // 255 of 256 CUs and still do not fit (7 blocks x 5 ranks on XCDs 0..2: the launches wait for each other's CUs forever).
-    const long per_xcd = hc->blocks_fit / 8;
-    const long room = per_xcd >= ranks_on_this_gpu ? 8 * (per_xcd / ranks_on_this_gpu) - 1 : hc->blocks_fit / ranks_on_this_gpu - 1;
+    const long room = room_for_workers(hc->plan.blocks_fit, ranks_on_this_gpu);
     if (room < 1) return fail(HTM_ESTATE, "%d ranks on one GPU: not even one worker block per rank fits next to the masters", ranks_on_this_gpu);
     if (hc->dev.n_workers > room) hc->dev.n_workers = worker_blocks(hc->fwd->E, 8, room);
     hc->dev.n_wg = hc->dev.n_workers;
@@ -1599,7 +1548,7 @@ int htm_chains_last_run_stats(htm_chains *hc, double *device_us, int *graph_laun
 int htm_chains_fixed_master(htm_chains *hc, int *on, int *worker_blocks)
 {
     if (!hc || !on) return fail(HTM_EINVAL, "NULL argument");
-    *on = (hc->last_fixed && hc->flow) ? 1 : 0;
+    *on = hc->last_fixed ? 1 : 0;      // (set by launch_mcmc from loop_for's answer)
     if (worker_blocks) *worker_blocks = hc->dev.n_workers;
     return HTM_OK;
 }
@@ -1607,8 +1556,10 @@ int htm_chains_fixed_master(htm_chains *hc, int *on, int *worker_blocks)
 int htm_chains_master_stats(htm_chains *hc, int *single_rank_loop, int *lockstep_loop, int64_t *flushes)
 {
     if (!hc) return fail(HTM_EINVAL, "NULL argument");
-    if (single_rank_loop) *single_rank_loop = !hc->persist ? -1 : hc->pipe ? 5 : (hc->flow && hc->mb_blocks > 1) ? 7 : hc->flow ? 3 : 0;
-    if (lockstep_loop) *lockstep_loop = !hc->persist ? -1 : hc->pipe_lock ? 6 : hc->flow_lock ? 4 : 2;
+    // (the specialised instantiation, 8, is reported as the free-running master it is: htm_chains_fixed_master tells them apart)
+    const int run = loop_for(hc->plan, MODE_RUN, false), lock = loop_for(hc->plan, MODE_LOCKRUN, false);
+    if (single_rank_loop) *single_rank_loop = !hc->plan.persist ? -1 : run == 8 ? 3 : run;
+    if (lockstep_loop) *lockstep_loop = !hc->plan.persist ? -1 : lock;
     if (flushes) {
         HIPCHK(hipStreamSynchronize(hc->fwd->stream));
         unsigned long long v = 0;

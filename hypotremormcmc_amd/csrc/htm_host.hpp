@@ -2,7 +2,10 @@
 // (include/htm_hip.h is).
 //
 //   htm_forward.hip        htm_forward_*, htm_device_*, the last-error string, the self-tests and htm_rng_jump
-//   htm_hip.hip            htm_chains_*, htm_comm_*: which loop a launch takes (launch_mcmc); no k_mcmc is instantiated there
+//   htm_hip.hip            htm_chains_*, htm_comm_*: sets a chain set up and launches its loops; no k_mcmc is instantiated there
+//   htm_plan.hpp           the launch plan of a chain set: which loop each mode takes (loop_for) and the launch shape, worked out
+//                          by plain functions without a device; kept in htm_chains::plan.  Ask for the plan of a shape with
+//                          htm_chains_plan (no GPU needed), for the plan of a chain set with htm_chains_get_plan
 //   htm_loop_*.hip         one unit per family of chain-master loops: nothing but its rows of the kernel table below
 //                          (made with htm_loop_rows.hpp)
 //   htm_steps.hip          steps 1-4, 6 and the convergence diagnostics; touches neither htm_forward nor htm_chains
@@ -23,6 +26,7 @@
 #include <vector>
 
 #include "htm_kernels.hpp"
+#include "htm_plan.hpp"
 #include "htm_stream.hpp"
 
 // (nothing declared here is exported from the shared library: the C ABI is)
@@ -102,9 +106,8 @@ struct htm_chains {
     hipGraph_t graph = nullptr;
     hipGraphExec_t gexec = nullptr;
     int pairs = 32;
-    int nw = 1;                // chain waves of k_step (one more wave is the RNG producer)
-    int ring_size = 512, wmax = 64;
-    size_t step_smem = 0;
+    htm::LoopPlan plan;        // which loop a launch takes and its shape (htm_plan.hpp), as htm_chains_create planned it
+    htm::PlanDevice seen;      // the device facts it planned with
     int h_target = 0;          // host copy of the iteration target
     int rec_len = 0;
     std::vector<int32_t> lik_iter, lik_chain, smp_iter, smp_chain;
@@ -122,18 +125,7 @@ struct htm_chains {
     const double *pending_gathered = nullptr;  // lock-step: records whose swap the next k_step applies
     double *d_gath_host = nullptr, *h_gath_pinned = nullptr;   // staging buffers of htm_chains_step_end_host
     unsigned long long launch_seq = 0;         // k_mcmc launches of this chain set so far (the kernels' launch index)
-    bool persist = true;                       // k_mcmc (master + resident full-evaluation workers) vs k_step + k_full
-    bool flow = false;                         // single-rank loop on the free-running master (htm_flow.hpp) instead of step_body
-    bool flow_fixed = false;                   // ... and the job's shape allows its specialised instantiation (k_mcmc<.., 8>; flow_fixed_ok decides per launch)
-    bool last_fixed = false;                   // the latest MODE_RUN launch was that instantiation
-    bool wide = false;                         // more than kMaxChains chains: the loop with barriers at kMaxWideChains (k_mcmc_wide, k_step_wide)
-    int worker_cap = 250;                      // most worker blocks a launch takes (HTM_WORKER_CAP)
-    long blocks_fit = 0;                       // resident blocks of a k_mcmc launch on this device (htm_chains_share_gpu)
-    bool flow_lock = false;                    // lock-step ranks (MODE_LOCKRUN) on the free-running master too
-    int mb_blocks = 1;                         // master workgroups of the single-rank loop (> 1: k_mcmc<.., 7>, eight chains each)
-    bool pipe = false;                         // single-rank loop on the pipelined master (htm_pipe.hpp)
-    bool pipe_lock = false;                    // lock-step ranks (MODE_LOCKRUN) on it too
-    size_t pipe_smem = 0; int pipe_ring = 512; // its LDS size and stream window
+    bool last_fixed = false;                   // the latest MODE_RUN launch was the specialised instantiation (k_mcmc<.., 8>)
     bool ctrl_fresh = false;                   // h_ctrl is the device's control block as of an idle stream (no launch since it was read)
     htm::ChainsDev dev_np{};                   // view for the non-persistent kernels (partial sums per k_full tile)
     uint32_t init_state[4] = {0, 0, 0, 0};     // mod_random state at stream position 0
@@ -164,7 +156,7 @@ int launch_step(htm_chains *hc, int mode, int target, const double *gathered);
 // ---- the kernel table ---------------------------------------------------------------------------------------------
 // Every instantiation of a chain-master kernel is written down once, as a row of the loop unit that compiles it
 // (htm_loop_*.hip, through the row templates of htm_loop_rows.hpp): the kernel's address (attributes, occupancy), the block size it is launched with and its typed launch.
-// htm_hip.hip decides WHICH loop a launch takes (launch_mcmc) and looks the instantiation up here; a combination that
+// htm_plan.hpp decides WHICH loop a launch takes (loop_for); launch_mcmc looks the instantiation up here; a combination that
 // no unit builds gives nullptr, which the caller reports -- never another instantiation in its place.
 struct LoopLaunch {
     dim3 grid, block;

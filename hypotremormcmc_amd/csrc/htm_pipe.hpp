@@ -1214,7 +1214,7 @@ __global__ __launch_bounds__((mcmc_threads<NCH, MK>())) void k_mcmc(FwdDev f, Ch
     if ((int)blockIdx.x < n_mb) {
         // MK 3: the single-rank loop on the free-running master (flow_body); 0: the same loop with barriers (step_body)
         // 4: a lock-step rank (MODE_LOCKRUN, swap records exchanged inside the launch) on the free-running master; 2: with barriers
-        // 8: MK 3 for a job whose shape the host has found fixed (flow_body<.., FlowFixed>: htm_flow.hpp, htm_hip.hip flow_fixed_ok)
+        // 8: MK 3 for a job whose shape the host has found fixed (flow_body<.., FlowFixed>: htm_flow.hpp, htm_plan.hpp loop_for)
         if constexpr (MK == 3) flow_body<NCH, F32, false>(ka.f, ka.cs, target_arg, ring_size, wmax, launch);
         else if constexpr (MK == 8) flow_body<NCH, F32, false, false, FlowFixed>(ka.f, ka.cs, target_arg, ring_size, wmax, launch);
         else if constexpr (MK == 4) flow_body<NCH, F32, true>(ka.f, ka.cs, target_arg, ring_size, wmax, launch);

@@ -298,6 +298,33 @@ int htm_chains_master_stats(htm_chains *hc, int *single_rank_loop, int *lockstep
  * *worker_blocks (may be NULL) = the worker blocks of a launch.  No reference counterpart (diagnostics). */
 int htm_chains_fixed_master(htm_chains *hc, int *on, int *worker_blocks);
 
+/* The launch plan of a chain set: which chain-master loop each mode runs and the shape it is launched with.  htm_chains_create
+ * works it out from the job, the environment (the HTM_* switches) and a few facts it asks the device; htm_chains_plan runs the
+ * same rules on facts the caller supplies and needs no device, so the plan of any shape can be asked on a machine without a GPU.
+ * No reference counterpart (diagnostics, tests). */
+typedef struct htm_plan_job {
+    int32_t n_chains, n_procs, n_sta, n_events;
+    int32_t forward_fp32, use_time, use_amp;
+} htm_plan_job;
+typedef struct htm_plan_device {      /* all 0 where htm_chains_create does not ask (HTM_PERSIST=0; no pipelined master) */
+    int32_t n_cu;                     /* compute units */
+    int32_t blocks_per_cu;            /* resident blocks per CU of a k_mcmc launch at (512 threads, step_smem): the smallest over the loops */
+    int32_t pipe_blocks_per_cu[2];    /* ... of the pipelined master's two loops at their own LDS size, when one is asked for */
+} htm_plan_device;
+typedef struct htm_launch_plan {
+    int64_t persist, flow, flow_fixed, wide, flow_lock, mb_blocks, pipe, pipe_lock, pipe_smem, pipe_ring;
+    int64_t ring_size, wmax, step_smem, worker_cap, blocks_fit, nw;
+    int64_t n_workers, mirror_n, mirror_steps;
+    int64_t loop[3][2];               /* the loop (0..8, csrc/htm_plan.hpp loop_for) of the single-rank run, one lock-step iteration
+                                       * per launch and persistent lock-step, [..][0] without and [..][1] with a step log */
+    int64_t loop_built[3][2];         /* 1: the library holds that loop's kernel for this job */
+} htm_launch_plan;
+/* A shape that htm_chains_create refuses gives the same code here, and htm_last_error() the same text. */
+int htm_chains_plan(const htm_plan_job *job, const htm_plan_device *device, htm_launch_plan *plan);
+/* the plan this chain set was created with (htm_chains_share_gpu may have lowered n_workers since) and, if `seen` is not NULL,
+ * the device facts it was planned with */
+int htm_chains_get_plan(htm_chains *hc, htm_launch_plan *plan, htm_plan_device *seen);
+
 /* Same work as htm_chains_run, but every kernel is launched eagerly and bracketed by its own pair of HIP
  * events on the handle's stream, so that the average duration of each kernel comes from the run itself:
  * k_step (proposals + partial updates + judge + swap; may cover several iterations per launch) and k_full
