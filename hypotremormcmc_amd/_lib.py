@@ -98,6 +98,8 @@ SIGNATURES = {
     "htm_rank_normalize_dev": (C.c_int, [C.c_int, vp, C.c_long, C.c_long, C.c_long, C.c_int, vp, C.c_long, vp, vp]),
     "htm_diagnose_rank": (C.c_int, [C.c_int, dp, C.c_long, C.c_long, C.c_long, C.c_int, dp]),
     "htm_diagnose_rank_dev": (C.c_int, [C.c_int, vp, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, vp, vp]),
+    "htm_hypo_ellipsoid": (C.c_int, [C.c_int, dp, dp, C.c_long, C.c_long, C.c_int, C.c_long, dp, dp]),
+    "htm_hypo_ellipsoid_dev": (C.c_int, [C.c_int, vp, C.c_long, vp, C.c_long, C.c_long, C.c_long, C.c_int, C.c_long, vp, vp, vp]),
     "htm_chains_swap_record_host": (C.c_int, [vp, dp]),
     "htm_chains_step_end_host": (C.c_int, [vp, dp]),
     "htm_comm_unique_id": (C.c_int, [vp, C.c_size_t]),

@@ -8,7 +8,8 @@
 //                          htm_chains_plan (no GPU needed), for the plan of a chain set with htm_chains_get_plan
 //   htm_loop_*.hip         one unit per family of chain-master loops: nothing but its rows of the kernel table below
 //                          (made with htm_loop_rows.hpp)
-//   htm_steps.hip          steps 1-4, 6 and the convergence diagnostics; touches neither htm_forward nor htm_chains
+//   htm_steps.hip          steps 1-4, 6, the convergence diagnostics and the location error ellipsoids (htm_hypo_ellipsoid*);
+//                          touches neither htm_forward nor htm_chains
 //
 // Host code is plain C++17 + the HIP runtime: no torch, no third-party dependency.  There is no CPU fallback on purpose:
 // every entry point needs a usable HIP device and fails with HTM_ENODEVICE otherwise.

@@ -1,6 +1,6 @@
 // htm_steps.hip -- the C ABI (include/htm_hip.h) of the pipeline's other steps: step 1 (htm_fft*, htm_convert*), steps 2 and 3
-// (htm_xcorr*, htm_measure_windows), step 4 (htm_select_regress), the convergence diagnostics (htm_diagnose*, htm_rank_normalize*) and step 6
-// (htm_quantiles*).  None of them touches a forward or a chain set.
+// (htm_xcorr*, htm_measure_windows), step 4 (htm_select_regress), the convergence diagnostics (htm_diagnose*, htm_rank_normalize*), step 6
+// (htm_quantiles*) and the location error ellipsoids (htm_hypo_ellipsoid*).  None of them touches a forward or a chain set.
 #include "htm_host.hpp"
 
 #include <dlfcn.h>
@@ -17,6 +17,7 @@
 
 #include "htm_convert.hpp"
 #include "htm_diag.hpp"
+#include "htm_ellipsoid.hpp"
 #include "htm_rank.hpp"
 #include "htm_select.hpp"
 #include "htm_xcorr.hpp"
@@ -411,6 +412,133 @@ int htm_diagnose_rank(int device, const double *samples, long n_seq, long n_draw
     rc = htm_diagnose_rank_dev(device, d_x, n_seq, n_draws, n_par, n_par, max_lag, d_o, nullptr);
     if (rc == HTM_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(HTM_EHIP, "the diagnostics kernels failed");
     if (rc == HTM_OK && hipMemcpy(out, d_o, (size_t)n_par * 4 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(HTM_EHIP, "download failed");
+    return done(rc);
+}
+
+// ---- location error ellipsoids (htm_ellipsoid.hpp) ----------------------------------------------------
+namespace {
+struct EllPlan { long slabs, slab_rows, nb; };
+
+// what both forms refuse before any device call, and the launch plan: row slabs of the streaming kernels, windows per batch
+int ell_plan(const double *hypo, const double *pivots, long n_mod, long n_win, int n_piv, long rank, long ld, long ld_piv,
+             const double *out, const double *piv_corr, EllPlan *p)
+{
+    if (!hypo || !out || (n_piv > 0 && (!pivots || !piv_corr))) return fail(HTM_EINVAL, "NULL argument");
+    if (n_mod < 4 || n_win < 1 || n_piv < 0 || n_piv > kEllMaxPiv)
+        return fail(HTM_EINVAL, "bad shape (n_mod %ld, n_win %ld, n_piv %d): need n_mod >= 4, n_win >= 1, 0 <= n_piv <= %d", n_mod, n_win,
+                    n_piv, kEllMaxPiv);
+    // htm_quantiles_dev counts rows in int and takes int ranks
+    if (n_mod > INT_MAX) return fail(HTM_EINVAL, "n_mod %ld exceeds %d rows per column", n_mod, INT_MAX);
+    if (rank < 1 || rank > n_mod) return fail(HTM_EINVAL, "rank %ld outside 1..%ld", rank, n_mod);
+    if (n_win > INT_MAX / 3) return fail(HTM_EINVAL, "n_win %ld needs more than 2^32 - 1 work-items in one launch", n_win);
+    if (ld < 3 * n_win || ld_piv < n_piv)
+        return fail(HTM_EINVAL, "bad row stride (ld %ld < 3 n_win = %ld or ld_piv %ld < n_piv = %d)", ld, 3 * n_win, ld_piv, n_piv);
+    double mb = 1024.0;
+    if (const char *e = getenv("HTM_ELLIPSOID_MB")) {
+        mb = atof(e);
+        if (!(mb > 0.0)) return fail(HTM_EINVAL, "HTM_ELLIPSOID_MB = %s: a positive number of MiB", e);
+    }
+    // windows per batch: d2 [n_mod][nb] under the cap, a multiple of 64 and at least one wave's 64
+    const long n_grp = (n_win + 63) / 64;
+    const double cap = mb * 1048576.0 / (sizeof(double) * (double)n_mod) / 64.0;
+    p->nb = 64 * (cap >= (double)n_grp ? n_grp : std::max(1L, (long)cap));
+    // row slabs: waves enough to fill the chip several times over, of at least 256 rows; HTM_ELL_SLABS forces the count
+    long slabs = std::max(1L, std::min((4096 + n_grp - 1) / n_grp, (n_mod + 255) / 256));
+    if (const char *e = getenv("HTM_ELL_SLABS")) slabs = std::max(1L, std::min(atol(e), n_mod));
+    slabs = std::min(slabs, 65535L);
+    p->slab_rows = (n_mod + slabs - 1) / slabs;
+    p->slabs = (n_mod + p->slab_rows - 1) / p->slab_rows;          // no empty slab
+    const long n_cg = (3 * n_win + 63) / 64 + (n_piv > 0), n_wg = (n_grp + kEllWG - 1) / kEllWG;
+    if ((n_cg + kEllWG - 1) / kEllWG * p->slabs * 64 * kEllWG > 0xffffffffL || n_wg * p->slabs * 64 * kEllWG > 0xffffffffL)
+        return fail(HTM_EINVAL, "n_win %ld in %ld row slabs needs more than 2^32 - 1 work-items in one launch", n_win, p->slabs);
+    return HTM_OK;
+}
+
+}  // namespace
+
+int htm_hypo_ellipsoid_dev(int device, const double *d_hypo, long ld, const double *d_pivots, long ld_piv, long n_mod, long n_win,
+                           int n_piv, long rank_1based, double *d_out, double *d_piv_corr, void *hip_stream)
+{
+    EllPlan pl;
+    int rc = ell_plan(d_hypo, d_pivots, n_mod, n_win, n_piv, rank_1based, ld, ld_piv, d_out, d_piv_corr, &pl);
+    if (rc) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
+    HIPCHK(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const long n_col = 3 * n_win + n_piv, n_hcg = (3 * n_win + 63) / 64, n_cg = n_hcg + (n_piv > 0), n_grp = (n_win + 63) / 64;
+    const int nacc = ell_nacc(n_piv), n_slab = (int)pl.slabs;
+    // workspace (stream-ordered, as htm_quantiles_dev's): stats [3][n_col], the slabs' sum/min/max [slabs][3][n_col] and
+    // residual sums [slabs][n_col], the slabs' moments [slabs][nacc][n_win] and their sums [nacc][n_win], d2 [n_mod][nb], its
+    // order statistics [nb][3]
+    const size_t stats_n = 3 * (size_t)n_col, rng_n = (size_t)pl.slabs * 3 * n_col, res_n = (size_t)pl.slabs * n_col,
+                 mom_n = (size_t)pl.slabs * nacc * n_win, sum_n = (size_t)nacc * n_win, d2_n = (size_t)n_mod * pl.nb, q_n = 3 * (size_t)pl.nb;
+    StreamBuf ws;
+    if ((rc = ws.alloc((stats_n + rng_n + res_n + mom_n + sum_n + d2_n + q_n) * sizeof(double), st))) return rc;
+    double *d_stats = reinterpret_cast<double *>(ws.p), *d_rng = d_stats + stats_n, *d_res = d_rng + rng_n, *d_mom = d_res + res_n,
+           *d_sum = d_mom + mom_n, *d_d2 = d_sum + sum_n, *d_q = d_d2 + d2_n;
+    auto done = [&](int code) { const int rc2 = ws.release(); return code ? code : rc2; };
+    // HTM_ELL_STOP=mean|moments|finish ends the call after that part (tools/bench_ellipsoid.py times the parts by it)
+    int stop = 4;
+    if (const char *e = getenv("HTM_ELL_STOP")) stop = !strcmp(e, "mean") ? 1 : !strcmp(e, "moments") ? 2 : !strcmp(e, "finish") ? 3 : 4;
+    const EllCols cols{d_hypo, d_pivots, ld, ld_piv, 3 * n_win, n_hcg, n_piv};
+    const dim3 grid_c((unsigned)((n_cg + kEllWG - 1) / kEllWG), (unsigned)pl.slabs), grid_w((unsigned)((n_grp + kEllWG - 1) / kEllWG), (unsigned)pl.slabs);
+    hipLaunchKernelGGL(k_ell_range, grid_c, dim3(64 * kEllWG), 0, st, cols, n_mod, pl.slab_rows, d_rng);
+    hipLaunchKernelGGL(k_ell_mean, grid_c, dim3(64 * kEllWG), 0, st, cols, n_mod, pl.slab_rows, (const double *)d_rng, n_slab, d_res);
+    hipLaunchKernelGGL(k_ell_stats, dim3((unsigned)((n_col + 63) / 64)), dim3(64), 0, st, (const double *)d_rng, (const double *)d_res,
+                       n_col, n_slab, n_mod, d_stats);
+    if (stop >= 2) {
+#define ELL_MOMENTS(NPIV)                                                                                                        \
+    hipLaunchKernelGGL(k_ell_moments<NPIV>, grid_w, dim3(64 * kEllWG), 0, st, d_hypo, ld, d_pivots, ld_piv, n_mod, n_win, pl.slab_rows, \
+                       (const double *)d_stats, d_mom)
+        switch (n_piv) {
+        case 0: ELL_MOMENTS(0); break;
+        case 1: ELL_MOMENTS(1); break;
+        case 2: ELL_MOMENTS(2); break;
+        case 3: ELL_MOMENTS(3); break;
+        default: ELL_MOMENTS(4); break;
+        }
+#undef ELL_MOMENTS
+    }
+    if (stop >= 3) {
+        hipLaunchKernelGGL(k_ell_slabs, dim3((unsigned)((sum_n + 63) / 64)), dim3(64), 0, st, (const double *)d_mom, (long)sum_n, n_slab, d_sum);
+        hipLaunchKernelGGL(k_ell_finish, dim3((unsigned)n_grp), dim3(64), 0, st, (const double *)d_sum, (const double *)d_stats, n_mod, n_win,
+                           n_piv, d_out, d_piv_corr);
+    }
+    if (hipGetLastError() != hipSuccess) return done(fail(HTM_EHIP, "an ellipsoid kernel's launch failed"));
+    const int rk[3] = {(int)rank_1based, (int)rank_1based, (int)rank_1based};
+    for (long w0 = 0; stop >= 4 && w0 < n_win; w0 += pl.nb) {
+        const long nb = std::min(pl.nb, n_win - w0), nb_grp = (nb + 63) / 64;
+        hipLaunchKernelGGL(k_ell_maha, dim3((unsigned)((nb_grp + kEllWG - 1) / kEllWG), (unsigned)pl.slabs), dim3(64 * kEllWG), 0, st, d_hypo,
+                           ld, n_mod, n_win, w0, nb, pl.slab_rows, (const double *)d_out, d_d2, pl.nb);
+        if ((rc = htm_quantiles_dev(device, d_d2, n_mod, nb, pl.nb, rk, d_q, hip_stream))) return done(rc);
+        hipLaunchKernelGGL(k_ell_setq, dim3((unsigned)nb_grp), dim3(64), 0, st, (const double *)d_q, w0, nb, d_out);
+    }
+    if (hipGetLastError() != hipSuccess) return done(fail(HTM_EHIP, "an ellipsoid kernel's launch failed"));
+    return done(HTM_OK);
+}
+
+int htm_hypo_ellipsoid(int device, const double *hypo, const double *pivots, long n_mod, long n_win, int n_piv, long rank_1based,
+                       double *out, double *piv_corr)
+{
+    EllPlan pl;
+    int rc = ell_plan(hypo, pivots, n_mod, n_win, n_piv, rank_1based, 3 * n_win, n_piv, out, piv_corr, &pl);
+    if (rc) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
+    HIPCHK(hipSetDevice(device));
+    std::vector<void *> pool;
+    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
+    const size_t on = (size_t)n_win * kEllOut, cn = (size_t)n_win * 3 * n_piv;
+    double *d_x = nullptr, *d_p = nullptr, *d_o = nullptr, *d_c = nullptr;
+    if ((rc = dev_upload(pool, &d_x, hypo, (size_t)n_mod * 3 * n_win)) || (rc = dev_alloc(pool, &d_o, on)) ||
+        (n_piv > 0 && ((rc = dev_upload(pool, &d_p, pivots, (size_t)n_mod * n_piv)) || (rc = dev_alloc(pool, &d_c, cn)))))
+        return done(rc);
+    rc = htm_hypo_ellipsoid_dev(device, d_x, 3 * n_win, d_p, n_piv, n_mod, n_win, n_piv, rank_1based, d_o, d_c, nullptr);
+    if (rc == HTM_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(HTM_EHIP, "the ellipsoid kernels failed");
+    if (rc == HTM_OK && hipMemcpy(out, d_o, on * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HTM_EHIP, "download failed");
+    if (rc == HTM_OK && n_piv > 0 && hipMemcpy(piv_corr, d_c, cn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
         rc = fail(HTM_EHIP, "download failed");
     return done(rc);
 }

@@ -17,6 +17,7 @@ module htm_c_api
   public :: htm_comm_unique_id, htm_comm_create, htm_comm_destroy, htm_chains_run_lockstep_comm
   public :: htm_device_count, htm_device_physical_id, htm_quantiles, htm_diagnose, htm_select_regress
   public :: htm_rank_normalize, htm_rank_normalize_dev, htm_diagnose_rank, htm_diagnose_rank_dev
+  public :: htm_hypo_ellipsoid, htm_hypo_ellipsoid_dev
   public :: htm_chains_checkpoint_size, htm_chains_checkpoint_save, htm_chains_checkpoint_load
 
   integer(c_size_t), parameter :: HTM_XCHG_HANDLE_BYTES = 64_c_size_t, HTM_COMM_ID_BYTES = 128_c_size_t
@@ -293,6 +294,35 @@ module htm_c_api
        type(c_ptr), value :: d_out, hip_stream
        integer(c_int) :: rc
      end function htm_diagnose_rank_dev
+     !> location error ellipsoids (include/htm_hip.h): hypo [n_mod][3 n_win] row-major, pivots [n_mod][n_piv] or c_null_ptr;
+     !> out (22, n_win) = mean, cov, lambda, V, q; piv_corr (n_piv, 3, n_win) or c_null_ptr
+     function htm_hypo_ellipsoid(device, hypo, pivots, n_mod, n_win, n_piv, rank_1based, out, piv_corr) &
+          & bind(C, name="htm_hypo_ellipsoid") result(rc)
+       import :: c_int, c_long, c_double, c_ptr
+       integer(c_int), value :: device
+       real(c_double), intent(in) :: hypo(*)
+       type(c_ptr), value :: pivots
+       integer(c_long), value :: n_mod, n_win
+       integer(c_int), value :: n_piv
+       integer(c_long), value :: rank_1based
+       real(c_double), intent(out) :: out(*)
+       type(c_ptr), value :: piv_corr
+       integer(c_int) :: rc
+     end function htm_hypo_ellipsoid
+     !> the same on device pointers with row strides ld (hypo) and ld_piv (pivots), asynchronous on hip_stream
+     function htm_hypo_ellipsoid_dev(device, d_hypo, ld, d_pivots, ld_piv, n_mod, n_win, n_piv, rank_1based, d_out, d_piv_corr, &
+          & hip_stream) bind(C, name="htm_hypo_ellipsoid_dev") result(rc)
+       import :: c_int, c_long, c_ptr
+       integer(c_int), value :: device
+       type(c_ptr), value :: d_hypo
+       integer(c_long), value :: ld
+       type(c_ptr), value :: d_pivots
+       integer(c_long), value :: ld_piv, n_mod, n_win
+       integer(c_int), value :: n_piv
+       integer(c_long), value :: rank_1based
+       type(c_ptr), value :: d_out, d_piv_corr, hip_stream
+       integer(c_int) :: rc
+     end function htm_hypo_ellipsoid_dev
      !> step-4 regressions (include/htm_hip.h): t, t_err, a, a_err (n_sta, n_win); out (6, n_win) = vs, b, t0, a0, cc_t, cc_a
      function htm_select_regress(device, n_sta, n_win, sta_x, sta_y, sta_z, z_guess, t, t_err, a, a_err, out) &
           & bind(C, name="htm_select_regress") result(rc)

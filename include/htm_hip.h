@@ -389,6 +389,28 @@ int htm_diagnose_rank_dev(int device, const double *d_samples, long n_seq, long 
                           int max_lag, double *d_out, void *hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Location error ellipsoids of recorded samples.  hypo [n_mod][3 n_win] row-major, one recorded model per
+ * row, window w in columns 3w, 3w+1, 3w+2 (the record of hypo.RR.out); pivots [n_mod][n_piv] pair with it row by row (vs, qs;
+ * NULL when n_piv = 0).  out [n_win][22] = mean[3], cov[6] (xx, xy, xz, yy, yz, zz; divisor n_mod - 1), lambda[3] (the
+ * covariance's eigenvalues, descending), V[9] (row-major, column k = the unit axis of lambda_k, its component of largest
+ * magnitude positive), q = the rank_1based-th smallest squared Mahalanobis distance sum_k ((x - mean) . v_k)^2 / lambda_k of
+ * the window's n_mod samples: the ellipsoid with semi-axes sqrt(q lambda_k) along v_k holds exactly rank_1based of them.
+ * piv_corr [n_win][3][n_piv] = the correlation coefficients of x, y, z with every pivot (NULL when n_piv = 0), NaN where the
+ * pivot or the coordinate is constant.  A window with a constant coordinate, or whose smallest eigenvalue is not positive,
+ * keeps its mean and covariance (the entries of a constant coordinate are exactly 0); its lambda, V and q are NaN.
+ * 4 <= n_mod <= INT_MAX, n_win >= 1, 0 <= n_piv <= 4, 1 <= rank_1based <= n_mod, ld >= 3 n_win, ld_piv >= n_piv, else
+ * HTM_EINVAL before any device call, as for a shape that needs a launch beyond 2^32 - 1 work-items.  The distances are
+ * taken in batches of windows (multiples of 64) whose workspace stays under HTM_ELLIPSOID_MB MiB (environment, default
+ * 1024; one wave's 64 windows at the least); the result does not depend on it, and two calls give the same bits.  Host
+ * pointers: synchronous; _dev: device pointers (ld, ld_piv = row strides in doubles; columns beyond 3 n_win are never read),
+ * asynchronous on `hip_stream`. */
+int htm_hypo_ellipsoid(int device, const double *hypo, const double *pivots, long n_mod, long n_win, int n_piv,
+                       long rank_1based, double *out, double *piv_corr);
+int htm_hypo_ellipsoid_dev(int device, const double *d_hypo, long ld, const double *d_pivots, long ld_piv,
+                           long n_mod, long n_win, int n_piv, long rank_1based,
+                           double *d_out, double *d_piv_corr, void *hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Step 4, `hypo_tremor_select`   reference: src/cls_selector.f90:75-132, src/mod_regress.f90
  * For every detected window: the station of largest amplitude is taken as the epicentre (depth z_guess), the
  * amplitudes are corrected for geometrical spreading (+ ln d), and arrival time and amplitude are regressed
