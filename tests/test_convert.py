@@ -1,6 +1,6 @@
 """CPU: step 1 (hypotremormcmc_amd.convert) -- the numpy restatement against a literal transcription of the reference's
-loops, the constants, the SAC reader, file names, time IDs and the parameter keys.  The GPU side is in
-test_gpu_convert.py."""
+loops, the constants, the SAC reader, file names, time IDs and the parameter keys; the exact FFT references and bounds
+of tests/fft_restatement.py against np.fft.  The GPU side is in test_gpu_convert.py and test_gpu_fft.py."""
 import ctypes as C
 import math
 
@@ -10,6 +10,7 @@ import pytest
 from hypotremormcmc_amd import _lib, convert, synth
 from hypotremormcmc_amd.param import REQUIRED_CONVERT, Param
 from tests import convert_restatement as cr
+from tests import fft_restatement as fr
 
 
 @pytest.mark.parametrize("n", [12, 20, 40])
@@ -228,3 +229,47 @@ def test_batches_budget():
     assert convert.batch_segments(300000, 512) >= 10
     assert convert.batch_segments(300000, 1) == 1
     assert convert.batch_segments(4 * 75011, 512) >= 1
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 7, 12, 105, 343, 1024, 3000])
+def test_numpy_fft_within_stockham_bound_of_exact_dft(n):
+    rng = np.random.default_rng(n)
+    x = rng.standard_normal((2, n)) + 1j * rng.standard_normal((2, n))
+    for d, got in ((-1, np.fft.fft(x, axis=1)), (1, np.fft.ifft(x, axis=1) * n)):
+        ref = fr.dft_exact(x, d)
+        assert ref.dtype == np.clongdouble
+        err = np.linalg.norm((got - ref).astype(np.complex128), axis=1) / np.linalg.norm(ref.astype(np.complex128), axis=1)
+        assert np.all(err <= fr.stockham_bound(n)), (n, d, err, fr.stockham_bound(n))
+
+
+def test_fft_restatement_pass_lists_and_bounds():
+    assert fr.passes(300000) == [4, 4, 2, 3, 5, 5, 5, 5, 5]
+    assert fr.passes(1) == [] and fr.passes(2) == [2] and fr.passes(1024) == [4] * 5 and fr.passes(2048) == [4] * 5 + [2]
+    assert fr.passes(105) == [3, 5, 7] and fr.passes(28) == [4, 7]
+    assert fr.passes(11) is None and fr.passes(4 * 75011) is None
+    assert (fr.inner_length(11), fr.inner_length(33), fr.inner_length(1009), fr.inner_length(2018)) == (32, 128, 2048, 4096)
+    u = 2.0 ** -53
+    assert fr.stockham_bound(1) == 0.0 and fr.stockham_bound(2048) == 29 * u
+    assert abs(fr.stockham_bound(28) / u - (8 + 9 * math.sqrt(7))) < 1e-12
+    assert abs(fr.stockham_bound(300000) / u - (5 + 5 + 4 + 3 + 5 * math.sqrt(3) + 5 * (3 + 7 * math.sqrt(5)))) < 1e-12
+    for n in (11, 33, 129, 1009):
+        assert 2.0 < fr.kappa(n) < 2.3
+        three = fr.kappa(n) * (3 * fr.stockham_bound(fr.inner_length(n)) + 7 * u) + 3 * u      # three equal transforms
+        assert abs(fr.bluestein_bound(n) / three - 1) < 1e-12
+        assert fr.bluestein_bound(n, 4.0) < 1e-12
+
+
+def test_fft_restatement_impulse_and_tone_are_the_exact_dft():
+    for n in (1, 2, 7, 12, 33):
+        for d in (-1, 1):
+            for j in sorted({0, 1 % n, n - 1}):
+                e = np.zeros(n)
+                e[j] = 1.0
+                assert np.max(np.abs(fr.dft_exact(e, d) - fr.impulse_spectrum(n, j, d))) == 0
+                line = fr.dft_exact(fr.tone(n, j, d), d)
+                want = np.zeros(n)
+                want[j] = n
+                assert np.max(np.abs(line - want)) < 1e-17 * n * n
+    c, s = fr.roots(16)
+    assert c[4] == 0 and s[4] == 1 and c[8] == -1 and s[8] == 0 and c[2] == s[2] and c[14] == -s[14]
+    assert fr.impulse_spectrum(24, 5, -1, 3, 7).shape == (4,)

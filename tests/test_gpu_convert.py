@@ -144,6 +144,192 @@ def test_convert_100hz_flagship_and_closed_form():
     assert np.max(np.abs(e[n4:n - n4] - cr.closed_form(A, c.h))) / cr.closed_form(A, c.h) < 1e-9
 
 
+# ---- edge shapes: the k_cv_* kernels where an index can go wrong ---------------------------------------------------------
+# References: the literal transcription of the reference's loops for n <= 40, the vectorised restatement above.  The
+# tolerance is the project's 1e-11 of the largest reference value, the scale taken over each segment's kept range:
+# an indexing error at these shapes is O(1).  A band without a pass band (expecting zeros) must give exact zeros.
+
+def _noise(N, seed):
+    rng = np.random.default_rng(seed)
+    return rng.standard_normal(N).astype(np.float32), (rng.standard_normal(N) * 3 + 5.0).astype(np.float32)
+
+
+def _check_record(c, x1, x2, fac, tag=""):
+    """counts and positions; the whole record in one call, segment by segment, the middle run 1 .. last - 1 and the last
+    segment alone, bit-equal where they overlap; every segment's kept range against the reference -> (values, worst
+    error as a fraction of 1e-11 of the segment's scale)"""
+    N = x1.size
+    ref = (cr.convert_literal if c.n <= 40 else cr.convert)(x1, x2, c.n, c.n_fac, c.h, c.k_band, fac)
+    assert np.all(np.isfinite(ref))
+    last = convert.last_segment(N, c.n)
+    k0, got = _htm_convert(x1, x2, c, fac, 0, last)
+    assert k0 == 0 and got.size == ref.size == math.ceil(N / c.n_fac)
+    pos = [convert.outputs(N, c.n, c.n_fac, j, j) for j in range(last + 1)]
+    assert pos[0][0] == 0 and pos[-1][0] + pos[-1][1] == got.size
+    worst = 0.0
+    for j, (kj, cnt) in enumerate(pos):
+        pk, piece = _htm_convert(x1, x2, c, fac, j, j)
+        assert (pk, piece.size) == (kj, cnt), (tag, j)
+        assert np.array_equal(piece, got[kj:kj + cnt]), (tag, j)
+        if cnt == 0:
+            continue
+        r = ref[kj:kj + cnt]
+        scale = np.max(np.abs(r))
+        if scale == 0.0:
+            assert np.all(piece == 0.0), (tag, j)
+        else:
+            err = np.max(np.abs(piece - r)) / scale
+            worst = max(worst, err / 1e-11)
+            assert err <= 1e-11, (tag, j, err)
+    if last >= 2:
+        km, mid = _htm_convert(x1, x2, c, fac, 1, last - 1)
+        assert km == pos[1][0] and mid.size == pos[-1][0] - km
+        assert np.array_equal(mid, got[km:km + mid.size]), tag
+    kl, tail = _htm_convert(x1, x2, c, fac, last, last)
+    assert np.array_equal(tail, got[kl:]), tag
+    return got, worst
+
+
+def _small_bands(n):
+    return [(1, 2, max(2, n // 3), max(2, n // 2 - 1)), (0, 0, 0, 0), (2, 2, 2, 2), (1, 1, n // 2, n // 2),
+            (0, 0, n // 2 + 1, n + 3)]
+
+
+@pytest.mark.parametrize("n", [4, 8, 12, 16, 40])
+def test_convert_small_grid_against_literal(n):
+    """every h in {0, 1, n/4, n/2}, n_fac in {1, 3, n/2}, record length around the segment boundaries and band, the
+    degenerate ones included: n below one scan round, 2h == n, n_fac == n/2"""
+    n2 = n // 2
+    worst, cases = 0.0, 0
+    for h in sorted({0, 1, n // 4, n2}):
+        for n_fac in sorted({1, 3, n2}):
+            if n_fac > n2:
+                continue
+            for N in (n, n + 1, n + n2 - 1, n + n2, n + 3 * n2 + 1):
+                for b, kb in enumerate(_small_bands(n)):
+                    c = convert.Constants(1.0, n, n_fac, h, kb)
+                    x1, x2 = _noise(N, 100000 * n + 1000 * h + 100 * n_fac + N)
+                    got, w = _check_record(c, x1, x2, (1.3, 0.7), tag=(n, h, n_fac, N, kb))
+                    if b in (1, 2):
+                        assert np.all(got == 0.0), (n, h, n_fac, N, kb)
+                    worst = max(worst, w)
+                    cases += 1
+    print("CONVERT small grid n=%d: %d cases, worst %.3g of 1e-11" % (n, cases, worst))
+
+
+def _band(n):
+    return (max(1, n // 50), n // 20, n // 5, n // 4)
+
+
+# (n, h): one scan round of 256 and either side of it; a tile of 1024 exactly, 4 past it, two tiles and 4 (h within a
+# tile and a halo that spans tiles); 2h == n beyond a tile; 2h == n at kCvMaxH; kCvMaxH with the halo clipped on one side
+LARGER = [(252, 5), (252, 126), (256, 5), (256, 128), (260, 5), (260, 130), (1024, 5), (1024, 300), (1028, 5),
+          (1028, 300), (2052, 5), (2052, 300), (4100, 2050), (8192, 4096), (12000, 4096)]
+
+
+@pytest.mark.parametrize("n,h", LARGER)
+def test_convert_scan_rounds_tiles_and_wide_windows(n, h):
+    n2 = n // 2
+    N = n + 2 * n2 + 17
+    x1, x2 = _tremor(N, 0.01, seed=n + h)
+    worst = 0.0
+    for n_fac in (1, 7, n2):
+        c = convert.Constants(0.01, n, n_fac, h, _band(n))
+        worst = max(worst, _check_record(c, x1, x2, (1.0, 0.7), tag=(n, h, n_fac))[1])
+    print("CONVERT n=%d h=%d: worst %.3g of 1e-11" % (n, h, worst))
+
+
+def test_convert_dev_writes_only_its_outputs():
+    """htm_convert_dev on device pointers and a non-default torch stream, into the middle of a buffer filled with a
+    sentinel: the 8 doubles on either side keep it, the middle has the bits of the host form"""
+    import torch
+
+    lib = _lib.load()
+    n, h, n_fac = 1028, 5, 7
+    N = n + 3 * (n // 2) + 17
+    c = convert.Constants(0.01, n, n_fac, h, _band(n))
+    x1, x2 = _tremor(N, 0.01, seed=21)
+    last = convert.last_segment(N, n)
+    kb = (C.c_int * 4)(*c.k_band)
+    stream = torch.cuda.Stream()
+    for j0, j1 in ((0, last), (1, last - 1), (last, last)):
+        _, want = _htm_convert(x1, x2, c, (1.0, 0.7), j0, j1)
+        g0, g1 = j0 * (n // 2), min(N, j1 * (n // 2) + n)
+        with torch.cuda.stream(stream):
+            d1, d2 = torch.from_numpy(x1[g0:g1].copy()).cuda(), torch.from_numpy(x2[g0:g1].copy()).cuda()
+            buf = torch.full((want.size + 16,), -12345.5, dtype=torch.float64, device="cuda")
+            _lib.check(lib.htm_convert_dev(0, C.c_void_p(d1.data_ptr()), C.c_void_p(d2.data_ptr()), N, n, n_fac, h, kb,
+                                           1.0, 0.7, j0, j1, C.c_void_p(buf.data_ptr() + 8 * 8),
+                                           C.c_void_p(stream.cuda_stream)))
+            stream.synchronize()
+            v = buf.cpu().numpy()
+        assert np.all(v[:8] == -12345.5) and np.all(v[-8:] == -12345.5), (j0, j1)
+        assert np.array_equal(v[8:-8], want), (j0, j1)
+
+
+DEGENERATE = [(40, 3, 3, (1, 2, 13, 19)), (1028, 5, 7, (10, 30, 200, 257))]
+
+
+@pytest.mark.parametrize("n,h,n_fac,kb", DEGENERATE)
+def test_convert_degenerate_records(n, h, n_fac, kb):
+    """All zero: exact zeros.  A constant and a pure ramp are detrended away wherever a segment lies inside the record:
+    |out| <= 1e-11 max |x| in the kept ranges of every segment but the last.  The last segment always reads zeros
+    beyond N (N - j n/2 < n), so its window holds a step, not a line; there the restatement is the reference.  A
+    signal of size 1 on an offset of 1e6: against the restatement at 1e-11 of the largest value."""
+    c = convert.Constants(0.01, n, n_fac, h, kb)
+    fac = (1.0, 0.7)
+    N = n + 3 * (n // 2) + 5
+    last = convert.last_segment(N, n)
+    z = np.zeros(N, dtype=np.float32)
+    got, _ = _check_record(c, z, z, fac, "zero")
+    assert np.all(got == 0.0)
+    i = np.arange(N, dtype=np.float64)
+    k_last = convert.outputs(N, n, n_fac, last, last)[0]
+    for name, f1, f2 in (("constant", np.full(N, 1e4), np.full(N, 1e4)), ("ramp", 3.0 * i - 7.0, 11.0 - 2.0 * i)):
+        x1, x2 = f1.astype(np.float32), f2.astype(np.float32)
+        assert np.array_equal(x1, f1) and np.array_equal(x2, f2), "the record is exact in float32"
+        ref = cr.convert(x1, x2, n, n_fac, h, kb, fac)
+        _, got = _htm_convert(x1, x2, c, fac, 0, last)
+        top = float(np.max(np.abs(got[:k_last]))) / float(max(np.max(np.abs(x1)), np.max(np.abs(x2))))
+        err = float(np.max(np.abs(got[k_last:] - ref[k_last:])) / np.max(np.abs(ref[k_last:])))
+        print("CONVERT n=%d %s: %.3g of 1e-11 max|x|; last segment %.3g of 1e-11" % (n, name, top / 1e-11, err / 1e-11))
+        assert top <= 1e-11, (name, top)
+        assert err <= 1e-11, (name, err)
+    x1, x2 = _noise(N, n)
+    x1, x2 = (x1 + np.float32(1e6)).astype(np.float32), (x2 - np.float32(1e6)).astype(np.float32)
+    ref = cr.convert(x1, x2, n, n_fac, h, kb, fac)
+    _, got = _htm_convert(x1, x2, c, fac, 0, last)
+    err = np.max(np.abs(got - ref)) / np.max(np.abs(ref))
+    print("CONVERT n=%d offset 1e6: %.3g of 1e-11" % (n, err / 1e-11))
+    assert err <= 1e-11, err
+
+
+@pytest.mark.parametrize("n,h,n_fac,kb", DEGENERATE)
+def test_convert_nan_stays_in_its_segments(n, h, n_fac, kb):
+    """one NaN in component 1 at stream sample q: NaN exactly in the kept ranges of the segments that contain q,
+    the bits of the clean run everywhere else.  q = n/2 + 3 lies in segments 0 and 1, q = N - 1 in the last alone."""
+    c = convert.Constants(0.01, n, n_fac, h, kb)
+    fac = (1.0, 0.7)
+    n2 = n // 2
+    N = n + 3 * n2 + 5
+    last = convert.last_segment(N, n)
+    x1, x2 = _noise(N, 3 * n)
+    _, clean = _htm_convert(x1, x2, c, fac, 0, last)
+    assert np.all(np.isfinite(clean))
+    for q in (n2 + 3, N - 1):
+        y1 = x1.copy()
+        y1[q] = np.nan
+        _, got = _htm_convert(y1, x2, c, fac, 0, last)
+        want_nan = np.zeros(got.size, dtype=bool)
+        hit = [j for j in range(last + 1) if j * n2 <= q < j * n2 + n]
+        assert hit == ([0, 1] if q == n2 + 3 else [last])
+        for j in hit:
+            kj, cnt = convert.outputs(N, n, n_fac, j, j)
+            want_nan[kj:kj + cnt] = True
+        assert np.array_equal(np.isnan(got), want_nan), q
+        assert np.array_equal(got[~want_nan], clean[~want_nan]), q
+
+
 def _run(args, cwd, env=None, timeout=300):
     e = dict(os.environ, PYTHONPATH=ROOT, **(env or {}))
     r = subprocess.run([sys.executable, "-m"] + args, cwd=cwd, env=e, capture_output=True, text=True, timeout=timeout)
