@@ -20,6 +20,11 @@ up = C.POINTER(C.c_uint32)
 vp = C.c_void_p
 
 
+def ptr(a):
+    """the double * of a float64 array (NULL for None), as the host-pointer entry points take it"""
+    return None if a is None else a.ctypes.data_as(dp)
+
+
 class HtmError(RuntimeError):
     pass
 

@@ -10,6 +10,9 @@
 //                          (made with htm_loop_rows.hpp)
 //   htm_steps.hip          steps 1-4, 6, the convergence diagnostics and the location error ellipsoids (htm_hypo_ellipsoid*);
 //                          touches neither htm_forward nor htm_chains
+//   htm_steps_host.hpp     htm_steps.hip's own host idioms (no other unit includes it): StreamBuf, a stream-ordered workspace
+//                          that hands out typed pieces; DevPool, the device arrays of a host-pointer form (alloc, upload,
+//                          download); kMaxWorkItems, the limit of one launch; env_mib, an HTM_x_MB switch
 //
 // Host code is plain C++17 + the HIP runtime: no torch, no third-party dependency.  There is no CPU fallback on purpose:
 // every entry point needs a usable HIP device and fails with HTM_ENODEVICE otherwise.

@@ -1,7 +1,7 @@
 // htm_steps.hip -- the C ABI (include/htm_hip.h) of the pipeline's other steps: step 1 (htm_fft*, htm_convert*), steps 2 and 3
 // (htm_xcorr*, htm_measure_windows), step 4 (htm_select_regress), the convergence diagnostics (htm_diagnose*, htm_rank_normalize*), step 6
-// (htm_quantiles*) and the location error ellipsoids (htm_hypo_ellipsoid*).  None of them touches a forward or a chain set.
-#include "htm_host.hpp"
+// (htm_quantiles*), the error ellipsoids (htm_hypo_ellipsoid*).  None touches a forward or a chain set; host idioms: htm_steps_host.hpp.
+#include "htm_steps_host.hpp"
 
 #include <dlfcn.h>
 
@@ -36,9 +36,8 @@ int htm_quantiles_dev(int device, const double *d_samples, long n_mod, long n_pa
     for (int r = 0; r < 3; ++r)
         if (ranks_1based[r] < 1 || ranks_1based[r] > n_mod)
             return fail(HTM_EINVAL, "rank %d outside 1..%ld (the reference would index outside its sorted column)", ranks_1based[r], n_mod);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
-    HIPCHK(hipSetDevice(device));
+    int rc = use_device(device);
+    if (rc) return rc;
     const dim3 grid((unsigned)((n_par + 63) / 64)), block(64 * kSelRG);
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const char *force = getenv("HTM_SELECT_SLABS");
@@ -56,22 +55,17 @@ int htm_quantiles_dev(int device, const double *d_samples, long n_mod, long n_pa
         return HTM_OK;
     }
     // workspace: three histograms, two prefix/remaining states (stream-ordered allocation keeps the call asynchronous)
-    const size_t hist_b = (size_t)grid.x * kSelHistPerGroup * sizeof(int);
-    const size_t st_b = (size_t)n_par * kSelRanks * sizeof(unsigned long long);
-    const size_t total = 3 * hist_b + 4 * st_b;
-    char *ws = nullptr;
-    bool async_alloc = hipMallocAsync(reinterpret_cast<void **>(&ws), total, st) == hipSuccess;
-    if (!async_alloc) {
-        (void)hipGetLastError();
-        if (hipMalloc(reinterpret_cast<void **>(&ws), total) != hipSuccess) return fail(HTM_EHIP, "hipMalloc of %zu bytes failed", total);
-    }
-    HIPCHK(hipMemsetAsync(ws, 0, total, st));
+    const size_t hist_n = (size_t)grid.x * kSelHistPerGroup, st_n = (size_t)n_par * kSelRanks;
+    StreamBuf ws;
     SelWork w;
-    for (int k = 0; k < 3; ++k) w.hist[k] = reinterpret_cast<int *>(ws + k * hist_b);
-    for (int k = 0; k < 2; ++k) {
-        w.prefix[k] = reinterpret_cast<unsigned long long *>(ws + 3 * hist_b + (2 * k) * st_b);
-        w.remaining[k] = reinterpret_cast<long *>(ws + 3 * hist_b + (2 * k + 1) * st_b);
-    }
+    if ((rc = ws.alloc(st, [&](StreamBuf &b) {
+            for (int k = 0; k < 3; ++k) b.take(w.hist[k], hist_n);
+            for (int k = 0; k < 2; ++k) {
+                b.take(w.prefix[k], st_n);
+                b.take(w.remaining[k], st_n);
+            }
+        }))) return rc;
+    HIPCHK(hipMemsetAsync(ws.data(), 0, ws.bytes(), st));
     const long slab_rows = (n_mod + slabs - 1) / slabs;
     const dim3 grid2(grid.x, (unsigned)slabs);
     int pass = 0;
@@ -81,13 +75,7 @@ int htm_quantiles_dev(int device, const double *d_samples, long n_mod, long n_pa
     hipLaunchKernelGGL(k_select_pass, grid, block, 0, st, d_samples, n_mod, n_par, ld, ranks_1based[0] - 1,
                        ranks_1based[1] - 1, ranks_1based[2] - 1, -4, pass, slab_rows, w, d_out);
     HIPCHK(hipGetLastError());
-    if (async_alloc) {
-        HIPCHK(hipFreeAsync(ws, st));
-    } else {
-        HIPCHK(hipStreamSynchronize(st));
-        (void)hipFree(ws);
-    }
-    return HTM_OK;
+    return ws.release();
 }
 
 int htm_quantiles(int device, const double *samples, long n_mod, long n_par, const int ranks_1based[3], double *out)
@@ -95,19 +83,13 @@ int htm_quantiles(int device, const double *samples, long n_mod, long n_par, con
     if (!samples || !out) return fail(HTM_EINVAL, "NULL argument");
     if (n_mod < 1 || n_par < 1) return fail(HTM_EINVAL, "bad shape");
     if (n_mod > INT_MAX) return fail(HTM_EINVAL, "n_mod %ld exceeds %d rows per column", n_mod, INT_MAX);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
-    HIPCHK(hipSetDevice(device));
+    int rc = use_device(device);
+    if (rc) return rc;
+    DevPool pool;
     double *d_x = nullptr, *d_o = nullptr;
-    const size_t nb = (size_t)n_mod * n_par * sizeof(double), ob = (size_t)n_par * 3 * sizeof(double);
-    if (hipMalloc(reinterpret_cast<void **>(&d_x), nb) != hipSuccess) return fail(HTM_EHIP, "hipMalloc of %zu bytes failed", nb);
-    if (hipMalloc(reinterpret_cast<void **>(&d_o), ob) != hipSuccess) { (void)hipFree(d_x); return fail(HTM_EHIP, "hipMalloc failed"); }
-    int rc = HTM_OK;
-    if (hipMemcpy(d_x, samples, nb, hipMemcpyHostToDevice) != hipSuccess) rc = fail(HTM_EHIP, "upload failed");
-    if (rc == HTM_OK) rc = htm_quantiles_dev(device, d_x, n_mod, n_par, n_par, ranks_1based, d_o, nullptr);
-    if (rc == HTM_OK && hipMemcpy(out, d_o, ob, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HTM_EHIP, "download failed");
-    (void)hipFree(d_x); (void)hipFree(d_o);
-    return rc;
+    if ((rc = pool.upload(&d_x, samples, (size_t)n_mod * n_par)) || (rc = pool.alloc(&d_o, (size_t)n_par * 3))) return rc;
+    if ((rc = htm_quantiles_dev(device, d_x, n_mod, n_par, n_par, ranks_1based, d_o, nullptr))) return rc;
+    return pool.download(out, d_o, (size_t)n_par * 3, "the select kernels or their");
 }
 
 // ---- convergence diagnostics (htm_diag.hpp) ---------------------------------------------------------------------
@@ -150,21 +132,14 @@ int htm_diagnose_dev(int device, const double *d_samples, long n_seq, long n_dra
     if (const char *e = getenv("HTM_DIAG_SLABS")) slabs = std::max(1L, std::min(atol(e), S));
     const long seq_per_slab = (S + slabs - 1) / slabs;
     slabs = (S + seq_per_slab - 1) / seq_per_slab;          // no empty slab
-    if (n_cg * n_lagwg > INT_MAX / slabs || n_cg * S * 64 * kDiagRG > 0xffffffffL || n_cg * n_lagwg * slabs * 64 * kDiagLW > 0xffffffffL)
+    if (n_cg * n_lagwg > INT_MAX / slabs || n_cg * S * 64 * kDiagRG > kMaxWorkItems || n_cg * n_lagwg * slabs * 64 * kDiagLW > kMaxWorkItems)
         return fail(HTM_EINVAL, "n_par %ld, %ld split sequences, %d lags need more than 2^32 - 1 work-items in one launch", n_par, S, L + 1);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
-    HIPCHK(hipSetDevice(device));
+    if ((rc = use_device(device))) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     // workspace: the means [S][n_par], the slabs' lag sums [slabs][L+1][n_par] (stream-ordered, as htm_quantiles_dev's)
-    const size_t mean_n = (size_t)S * n_par, part_n = (size_t)slabs * (L + 1) * n_par, total = (mean_n + part_n) * sizeof(double);
-    double *ws = nullptr;
-    bool async_alloc = hipMallocAsync(reinterpret_cast<void **>(&ws), total, st) == hipSuccess;
-    if (!async_alloc) {
-        (void)hipGetLastError();
-        if (hipMalloc(reinterpret_cast<void **>(&ws), total) != hipSuccess) return fail(HTM_EHIP, "hipMalloc of %zu bytes failed", total);
-    }
-    double *d_mean = ws, *d_part = ws + mean_n;
+    StreamBuf ws;
+    double *d_mean = nullptr, *d_part = nullptr;
+    if ((rc = ws.alloc(st, [&](StreamBuf &b) { b.take(d_mean, (size_t)S * n_par); b.take(d_part, (size_t)slabs * (L + 1) * n_par); }))) return rc;
     hipLaunchKernelGGL(k_diag_mean, dim3((unsigned)(n_cg * S)), dim3(64 * kDiagRG), 0, st, d_samples, n_draws, n, n_par, ld, n_cg, d_mean);
     const dim3 grid((unsigned)(n_cg * n_lagwg * slabs)), block(64 * kDiagLW);
     if (kb == 16)
@@ -174,13 +149,7 @@ int htm_diagnose_dev(int device, const double *d_samples, long n_seq, long n_dra
     hipLaunchKernelGGL(k_diag_finish, dim3((unsigned)n_cg), dim3(64), 0, st, d_part, d_mean, n, n_par, L, (int)S, (int)slabs,
                        1.0 / std::log10((double)S * (double)n), d_out, d_acov);
     HIPCHK(hipGetLastError());
-    if (async_alloc) {
-        HIPCHK(hipFreeAsync(ws, st));
-    } else {
-        HIPCHK(hipStreamSynchronize(st));
-        (void)hipFree(ws);
-    }
-    return HTM_OK;
+    return ws.release();
 }
 
 int htm_diagnose(int device, const double *samples, long n_seq, long n_draws, long n_par, int max_lag, double *out, double *acov)
@@ -188,72 +157,32 @@ int htm_diagnose(int device, const double *samples, long n_seq, long n_draws, lo
     if (!samples || !out) return fail(HTM_EINVAL, "NULL argument");
     int rc = diag_check(n_seq, n_draws, n_par, max_lag);
     if (rc) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
-    HIPCHK(hipSetDevice(device));
+    if ((rc = use_device(device))) return rc;
     const long L = std::min(n_draws / 2 - 1, (long)max_lag);
-    const size_t xb = (size_t)n_seq * n_draws * n_par * sizeof(double), ob = (size_t)n_par * 4 * sizeof(double),
-                 ab = acov ? (size_t)(L + 1) * n_par * sizeof(double) : 0;
-    std::vector<void *> pool;
-    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
+    const size_t on = (size_t)n_par * 4, an = (size_t)(L + 1) * n_par;
+    DevPool pool;
     double *d_x = nullptr, *d_o = nullptr, *d_a = nullptr;
-    if ((rc = dev_upload(pool, &d_x, samples, xb / sizeof(double))) || (rc = dev_alloc(pool, &d_o, ob / sizeof(double))) ||
-        (acov && (rc = dev_alloc(pool, &d_a, ab / sizeof(double)))))
-        return done(rc);
-    rc = htm_diagnose_dev(device, d_x, n_seq, n_draws, n_par, n_par, max_lag, d_o, d_a, nullptr);
-    if (rc == HTM_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(HTM_EHIP, "the diagnostics kernels failed");
-    if (rc == HTM_OK && hipMemcpy(out, d_o, ob, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HTM_EHIP, "download failed");
-    if (rc == HTM_OK && acov && hipMemcpy(acov, d_a, ab, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HTM_EHIP, "download failed");
-    return done(rc);
+    if ((rc = pool.upload(&d_x, samples, (size_t)n_seq * n_draws * n_par)) || (rc = pool.alloc(&d_o, on)) || (acov && (rc = pool.alloc(&d_a, an))))
+        return rc;
+    if ((rc = htm_diagnose_dev(device, d_x, n_seq, n_draws, n_par, n_par, max_lag, d_o, d_a, nullptr))) return rc;
+    if (hipStreamSynchronize(nullptr) != hipSuccess) return fail(HTM_EHIP, "the diagnostics kernels failed");
+    if ((rc = pool.download(out, d_o, on, "the diagnostics'")) || (acov && (rc = pool.download(acov, d_a, an, "the autocovariances'")))) return rc;
+    return HTM_OK;
 }
 
 // ---- rank-normalised diagnostics (htm_rank.hpp) ---------------------------------------------------
 namespace {
-// workspace on the stream (as htm_quantiles_dev allocates it); release() after the last launch that uses it
-struct StreamBuf {
-    char *p = nullptr;
-    bool async = false;
-    hipStream_t st = nullptr;
-    int alloc(size_t bytes, hipStream_t s)
-    {
-        st = s;
-        async = hipMallocAsync(reinterpret_cast<void **>(&p), bytes, st) == hipSuccess;
-        if (!async) {
-            (void)hipGetLastError();
-            if (hipMalloc(reinterpret_cast<void **>(&p), bytes) != hipSuccess) { p = nullptr; return fail(HTM_EHIP, "hipMalloc of %zu bytes failed", bytes); }
-        }
-        return HTM_OK;
-    }
-    int release()
-    {
-        if (!p) return HTM_OK;
-        char *q = p;
-        p = nullptr;
-        if (async) {
-            HIPCHK(hipFreeAsync(q, st));
-        } else {
-            hipError_t e = hipStreamSynchronize(st);
-            (void)hipFree(q);
-            HIPCHK(e);
-        }
-        return HTM_OK;
-    }
-};
-
 // columns per batch: the two key buffers [nb][R] stay under HTM_RANK_MB MiB (default 2048; at least one column), and no
 // launch of a batch goes beyond 2^32 - 1 work-items
 int rank_batch(long R, long n_par, long *nb_out)
 {
-    double mb = 2048.0;
-    if (const char *e = getenv("HTM_RANK_MB")) {
-        mb = atof(e);
-        if (!(mb > 0.0)) return fail(HTM_EINVAL, "HTM_RANK_MB = %s: a positive number of MiB", e);
-    }
+    double mb;
+    if (int rc = env_mib("HTM_RANK_MB", 2048.0, &mb)) return rc;
     const double cols = mb * 1048576.0 / (2.0 * sizeof(unsigned long long) * (double)R);
     long nb = cols >= (double)n_par ? n_par : std::max(1L, (long)cols);
     nb = std::min(nb, 1L << 21);                           // k_rank_sort: nb workgroups of kRankTile = 1024 threads
     const long n_rt = (R + 63) / 64, n_cg = (nb + 63) / 64, n_rc = (R + kRankZRows - 1) / kRankZRows;
-    if (n_rt * n_cg * 256 > 0xffffffffL || n_cg * n_rc * 256 > 0xffffffffL)
+    if (n_rt * n_cg * 256 > kMaxWorkItems || n_cg * n_rc * 256 > kMaxWorkItems)
         return fail(HTM_EINVAL, "%ld rows x %ld columns per batch need more than 2^32 - 1 work-items in one launch", R, nb);
     *nb_out = nb;
     return HTM_OK;
@@ -276,10 +205,8 @@ int rank_normalize_batches(const double *d_x, long R, long n_par, long ld, const
     int stop = 3;
     if (const char *e = getenv("HTM_RANK_STOP")) stop = !strcmp(e, "keys") ? 1 : !strcmp(e, "sort") ? 2 : 3;
     StreamBuf ws;
-    const size_t key_n = (size_t)nb * R;
-    int rc = ws.alloc(2 * key_n * sizeof(unsigned long long), st);
-    if (rc) return rc;
-    unsigned long long *ka = reinterpret_cast<unsigned long long *>(ws.p), *kb = ka + key_n;
+    unsigned long long *ka = nullptr, *kb = nullptr;
+    if (int rc = ws.alloc(st, [&](StreamBuf &b) { b.take(ka, (size_t)nb * R); b.take(kb, (size_t)nb * R); })) return rc;
     const long n_rt = (R + 63) / 64, n_rc = (R + kRankZRows - 1) / kRankZRows;
     for (long c0 = 0; c0 < n_par; c0 += nb) {
         const long n = std::min(nb, n_par - c0), n_cg = (n + 63) / 64;
@@ -289,10 +216,9 @@ int rank_normalize_batches(const double *d_x, long R, long n_par, long ld, const
             hipLaunchKernelGGL(k_rank_z, dim3((unsigned)(n_cg * n_rc)), dim3(256), 0, st, d_x, R, ld, c0, n, n_cg, d_med,
                                (const unsigned long long *)ka, d_z, d_ranks, ld_z);
     }
-    hipError_t e = hipGetLastError();
-    rc = ws.release();
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(HTM_EHIP, "a rank kernel's launch failed: %s", hipGetErrorString(e));
-    return rc;
+    return ws.release();
 }
 }  // namespace
 
@@ -304,23 +230,18 @@ int htm_rank_normalize_dev(int device, const double *d_samples, long n_rows, lon
     if (rc) return rc;
     long nb = 0;
     if ((rc = rank_batch(n_rows, n_par, &nb))) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
-    HIPCHK(hipSetDevice(device));
+    if ((rc = use_device(device))) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     if (!fold) return rank_normalize_batches(d_samples, n_rows, n_par, ld, nullptr, d_z, ld_z, d_ranks, nb, st);
     // the medians: the order statistics (R+1)/2 and R/2+1 (the third rank is not used)
     StreamBuf ws;
-    if ((rc = ws.alloc((size_t)n_par * 4 * sizeof(double), st))) return rc;
-    double *d_q = reinterpret_cast<double *>(ws.p), *d_med = d_q + 3 * n_par;
+    double *d_q = nullptr, *d_med = nullptr;
+    if ((rc = ws.alloc(st, [&](StreamBuf &b) { b.take(d_q, 3 * (size_t)n_par); b.take(d_med, (size_t)n_par); }))) return rc;
     const int rk[3] = {(int)((n_rows + 1) / 2), (int)(n_rows / 2 + 1), 1};
-    rc = htm_quantiles_dev(device, d_samples, n_rows, n_par, ld, rk, d_q, hip_stream);
-    if (rc == HTM_OK) {
-        hipLaunchKernelGGL(k_rank_median, dim3((unsigned)((n_par + 63) / 64)), dim3(64), 0, st, (const double *)d_q, n_par, d_med);
-        rc = rank_normalize_batches(d_samples, n_rows, n_par, ld, d_med, d_z, ld_z, d_ranks, nb, st);
-    }
-    const int rc2 = ws.release();
-    return rc ? rc : rc2;
+    if ((rc = htm_quantiles_dev(device, d_samples, n_rows, n_par, ld, rk, d_q, hip_stream))) return rc;
+    hipLaunchKernelGGL(k_rank_median, dim3((unsigned)((n_par + 63) / 64)), dim3(64), 0, st, (const double *)d_q, n_par, d_med);
+    if ((rc = rank_normalize_batches(d_samples, n_rows, n_par, ld, d_med, d_z, ld_z, d_ranks, nb, st))) return rc;
+    return ws.release();
 }
 
 int htm_rank_normalize(int device, const double *samples, long n_rows, long n_par, int fold, double *z, double *ranks)
@@ -330,20 +251,16 @@ int htm_rank_normalize(int device, const double *samples, long n_rows, long n_pa
     if (rc) return rc;
     long nb = 0;
     if ((rc = rank_batch(n_rows, n_par, &nb))) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
-    HIPCHK(hipSetDevice(device));
+    if ((rc = use_device(device))) return rc;
     const size_t n = (size_t)n_rows * n_par;
-    std::vector<void *> pool;
-    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
+    DevPool pool;
     double *d_x = nullptr, *d_z = nullptr, *d_r = nullptr;
-    if ((rc = dev_upload(pool, &d_x, samples, n)) || (rc = dev_alloc(pool, &d_z, n)) || (ranks && (rc = dev_alloc(pool, &d_r, n))))
-        return done(rc);
-    rc = htm_rank_normalize_dev(device, d_x, n_rows, n_par, n_par, fold, d_z, n_par, d_r, nullptr);
-    if (rc == HTM_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(HTM_EHIP, "the rank kernels failed");
-    if (rc == HTM_OK && hipMemcpy(z, d_z, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HTM_EHIP, "download failed");
-    if (rc == HTM_OK && ranks && hipMemcpy(ranks, d_r, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HTM_EHIP, "download failed");
-    return done(rc);
+    if ((rc = pool.upload(&d_x, samples, n)) || (rc = pool.alloc(&d_z, n)) || (ranks && (rc = pool.alloc(&d_r, n))))
+        return rc;
+    if ((rc = htm_rank_normalize_dev(device, d_x, n_rows, n_par, n_par, fold, d_z, n_par, d_r, nullptr))) return rc;
+    if (hipStreamSynchronize(nullptr) != hipSuccess) return fail(HTM_EHIP, "the rank kernels failed");
+    if ((rc = pool.download(z, d_z, n, "the z scores'")) || (ranks && (rc = pool.download(ranks, d_r, n, "the ranks'")))) return rc;
+    return HTM_OK;
 }
 
 int htm_diagnose_rank_dev(int device, const double *d_samples, long n_seq, long n_draws, long n_par, long ld, int max_lag, double *d_out,
@@ -355,45 +272,46 @@ int htm_diagnose_rank_dev(int device, const double *d_samples, long n_seq, long 
     if (ld < n_par) return fail(HTM_EINVAL, "bad shape (n_par %ld, ld %ld)", n_par, ld);
     const long R = n_seq * n_draws, n_cg = (n_par + 63) / 64, n_rc = (R + kRankZRows - 1) / kRankZRows;
     // the launches of this function's own kernels and the widest one of htm_diagnose_dev (k_diag_mean), before any device call
-    if (n_cg > INT_MAX / (2 * n_seq) || n_cg * 2 * n_seq * 64 * kDiagRG > 0xffffffffL || n_cg * n_rc * 256 > 0xffffffffL)
+    if (n_cg > INT_MAX / (2 * n_seq) || n_cg * 2 * n_seq * 64 * kDiagRG > kMaxWorkItems || n_cg * n_rc * 256 > kMaxWorkItems)
         return fail(HTM_EINVAL, "n_par %ld, %ld rows in %ld sequences need more than 2^32 - 1 work-items in one launch", n_par, R, n_seq);
     long nb = 0;
     if ((rc = rank_batch(R, n_par, &nb))) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
-    HIPCHK(hipSetDevice(device));
+    if ((rc = use_device(device))) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     // workspace: one [R][n_par] matrix that holds z, zf, I05 and I95 in turn; the six order statistics, the three thresholds and
     // the four results of htm_diagnose_dev per column
-    const size_t mat_n = (size_t)R * n_par, small_n = (size_t)n_par * (6 + 3 + 16);
     StreamBuf ws;
-    if ((rc = ws.alloc((mat_n + small_n) * sizeof(double), st))) return rc;
-    double *d_m = reinterpret_cast<double *>(ws.p), *d_qa = d_m + mat_n, *d_qb = d_qa + 3 * n_par, *d_thr = d_qb + 3 * n_par,
-           *d_d = d_thr + 3 * n_par;
-    auto done = [&](int code) { const int rc2 = ws.release(); return code ? code : rc2; };
+    double *d_m = nullptr, *d_qa = nullptr, *d_qb = nullptr, *d_thr = nullptr, *d_d = nullptr;
+    if ((rc = ws.alloc(st, [&](StreamBuf &b) {
+            b.take(d_m, (size_t)R * n_par);
+            b.take(d_qa, 3 * (size_t)n_par);
+            b.take(d_qb, 3 * (size_t)n_par);
+            b.take(d_thr, 3 * (size_t)n_par);
+            b.take(d_d, 16 * (size_t)n_par);
+        }))) return rc;
     // h = (R - 1) p, k = floor(h), g = h - k; the quantile is x_(k+1) + g (x_(min(k+2, R)) - x_(k+1))
     const double h05 = (double)(R - 1) * 0.05, h95 = (double)(R - 1) * 0.95;
     const long k05 = (long)std::floor(h05), k95 = (long)std::floor(h95);
     const int ra[3] = {(int)((R + 1) / 2), (int)(R / 2 + 1), (int)(k05 + 1)};
     const int rb[3] = {(int)std::min(k05 + 2, R), (int)(k95 + 1), (int)std::min(k95 + 2, R)};
-    if ((rc = htm_quantiles_dev(device, d_samples, R, n_par, ld, ra, d_qa, hip_stream))) return done(rc);
-    if ((rc = htm_quantiles_dev(device, d_samples, R, n_par, ld, rb, d_qb, hip_stream))) return done(rc);
+    if ((rc = htm_quantiles_dev(device, d_samples, R, n_par, ld, ra, d_qa, hip_stream))) return rc;
+    if ((rc = htm_quantiles_dev(device, d_samples, R, n_par, ld, rb, d_qb, hip_stream))) return rc;
     hipLaunchKernelGGL(k_rank_thresholds, dim3((unsigned)n_cg), dim3(64), 0, st, (const double *)d_qa, (const double *)d_qb, n_par,
                        h05 - (double)k05, h95 - (double)k95, d_thr);
     for (int part = 0; part < 4; ++part) {
         if (part < 2) {
             rc = rank_normalize_batches(d_samples, R, n_par, ld, part ? d_thr : nullptr, d_m, n_par, nullptr, nb, st);
-            if (rc) return done(rc);
+            if (rc) return rc;
         } else {
             hipLaunchKernelGGL(k_rank_indicator, dim3((unsigned)(n_cg * n_rc)), dim3(256), 0, st, d_samples, R, n_par, ld, n_cg,
                                (const double *)(d_thr + (part - 1) * n_par), part - 2, d_m);
         }
         if ((rc = htm_diagnose_dev(device, d_m, n_seq, n_draws, n_par, n_par, max_lag, d_d + (size_t)part * n_par * 4, nullptr, hip_stream)))
-            return done(rc);
+            return rc;
     }
     hipLaunchKernelGGL(k_rank_combine, dim3((unsigned)n_cg), dim3(64), 0, st, (const double *)d_d, n_par, d_out);
-    if (hipGetLastError() != hipSuccess) return done(fail(HTM_EHIP, "a rank kernel's launch failed"));
-    return done(HTM_OK);
+    if (hipGetLastError() != hipSuccess) return fail(HTM_EHIP, "a rank kernel's launch failed");
+    return ws.release();
 }
 
 int htm_diagnose_rank(int device, const double *samples, long n_seq, long n_draws, long n_par, int max_lag, double *out)
@@ -401,19 +319,14 @@ int htm_diagnose_rank(int device, const double *samples, long n_seq, long n_draw
     if (!samples || !out) return fail(HTM_EINVAL, "NULL argument");
     int rc = diag_check(n_seq, n_draws, n_par, max_lag);
     if (rc) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
-    HIPCHK(hipSetDevice(device));
-    std::vector<void *> pool;
-    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
+    if ((rc = use_device(device))) return rc;
+    DevPool pool;
     double *d_x = nullptr, *d_o = nullptr;
-    if ((rc = dev_upload(pool, &d_x, samples, (size_t)n_seq * n_draws * n_par)) || (rc = dev_alloc(pool, &d_o, (size_t)n_par * 4)))
-        return done(rc);
-    rc = htm_diagnose_rank_dev(device, d_x, n_seq, n_draws, n_par, n_par, max_lag, d_o, nullptr);
-    if (rc == HTM_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(HTM_EHIP, "the diagnostics kernels failed");
-    if (rc == HTM_OK && hipMemcpy(out, d_o, (size_t)n_par * 4 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(HTM_EHIP, "download failed");
-    return done(rc);
+    if ((rc = pool.upload(&d_x, samples, (size_t)n_seq * n_draws * n_par)) || (rc = pool.alloc(&d_o, (size_t)n_par * 4)))
+        return rc;
+    if ((rc = htm_diagnose_rank_dev(device, d_x, n_seq, n_draws, n_par, n_par, max_lag, d_o, nullptr))) return rc;
+    if (hipStreamSynchronize(nullptr) != hipSuccess) return fail(HTM_EHIP, "the diagnostics kernels failed");
+    return pool.download(out, d_o, (size_t)n_par * 4, "the rank diagnostics'");
 }
 
 // ---- location error ellipsoids (htm_ellipsoid.hpp) ----------------------------------------------------
@@ -434,11 +347,8 @@ int ell_plan(const double *hypo, const double *pivots, long n_mod, long n_win, i
     if (n_win > INT_MAX / 3) return fail(HTM_EINVAL, "n_win %ld needs more than 2^32 - 1 work-items in one launch", n_win);
     if (ld < 3 * n_win || ld_piv < n_piv)
         return fail(HTM_EINVAL, "bad row stride (ld %ld < 3 n_win = %ld or ld_piv %ld < n_piv = %d)", ld, 3 * n_win, ld_piv, n_piv);
-    double mb = 1024.0;
-    if (const char *e = getenv("HTM_ELLIPSOID_MB")) {
-        mb = atof(e);
-        if (!(mb > 0.0)) return fail(HTM_EINVAL, "HTM_ELLIPSOID_MB = %s: a positive number of MiB", e);
-    }
+    double mb;
+    if (int rc = env_mib("HTM_ELLIPSOID_MB", 1024.0, &mb)) return rc;
     // windows per batch: d2 [n_mod][nb] under the cap, a multiple of 64 and at least one wave's 64
     const long n_grp = (n_win + 63) / 64;
     const double cap = mb * 1048576.0 / (sizeof(double) * (double)n_mod) / 64.0;
@@ -450,7 +360,7 @@ int ell_plan(const double *hypo, const double *pivots, long n_mod, long n_win, i
     p->slab_rows = (n_mod + slabs - 1) / slabs;
     p->slabs = (n_mod + p->slab_rows - 1) / p->slab_rows;          // no empty slab
     const long n_cg = (3 * n_win + 63) / 64 + (n_piv > 0), n_wg = (n_grp + kEllWG - 1) / kEllWG;
-    if ((n_cg + kEllWG - 1) / kEllWG * p->slabs * 64 * kEllWG > 0xffffffffL || n_wg * p->slabs * 64 * kEllWG > 0xffffffffL)
+    if ((n_cg + kEllWG - 1) / kEllWG * p->slabs * 64 * kEllWG > kMaxWorkItems || n_wg * p->slabs * 64 * kEllWG > kMaxWorkItems)
         return fail(HTM_EINVAL, "n_win %ld in %ld row slabs needs more than 2^32 - 1 work-items in one launch", n_win, p->slabs);
     return HTM_OK;
 }
@@ -463,22 +373,25 @@ int htm_hypo_ellipsoid_dev(int device, const double *d_hypo, long ld, const doub
     EllPlan pl;
     int rc = ell_plan(d_hypo, d_pivots, n_mod, n_win, n_piv, rank_1based, ld, ld_piv, d_out, d_piv_corr, &pl);
     if (rc) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
-    HIPCHK(hipSetDevice(device));
+    if ((rc = use_device(device))) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const long n_col = 3 * n_win + n_piv, n_hcg = (3 * n_win + 63) / 64, n_cg = n_hcg + (n_piv > 0), n_grp = (n_win + 63) / 64;
     const int nacc = ell_nacc(n_piv), n_slab = (int)pl.slabs;
     // workspace (stream-ordered, as htm_quantiles_dev's): stats [3][n_col], the slabs' sum/min/max [slabs][3][n_col] and
     // residual sums [slabs][n_col], the slabs' moments [slabs][nacc][n_win] and their sums [nacc][n_win], d2 [n_mod][nb], its
     // order statistics [nb][3]
-    const size_t stats_n = 3 * (size_t)n_col, rng_n = (size_t)pl.slabs * 3 * n_col, res_n = (size_t)pl.slabs * n_col,
-                 mom_n = (size_t)pl.slabs * nacc * n_win, sum_n = (size_t)nacc * n_win, d2_n = (size_t)n_mod * pl.nb, q_n = 3 * (size_t)pl.nb;
+    const size_t sum_n = (size_t)nacc * n_win;
     StreamBuf ws;
-    if ((rc = ws.alloc((stats_n + rng_n + res_n + mom_n + sum_n + d2_n + q_n) * sizeof(double), st))) return rc;
-    double *d_stats = reinterpret_cast<double *>(ws.p), *d_rng = d_stats + stats_n, *d_res = d_rng + rng_n, *d_mom = d_res + res_n,
-           *d_sum = d_mom + mom_n, *d_d2 = d_sum + sum_n, *d_q = d_d2 + d2_n;
-    auto done = [&](int code) { const int rc2 = ws.release(); return code ? code : rc2; };
+    double *d_stats = nullptr, *d_rng = nullptr, *d_res = nullptr, *d_mom = nullptr, *d_sum = nullptr, *d_d2 = nullptr, *d_q = nullptr;
+    if ((rc = ws.alloc(st, [&](StreamBuf &b) {
+            b.take(d_stats, 3 * (size_t)n_col);
+            b.take(d_rng, (size_t)pl.slabs * 3 * n_col);
+            b.take(d_res, (size_t)pl.slabs * n_col);
+            b.take(d_mom, (size_t)pl.slabs * sum_n);
+            b.take(d_sum, sum_n);
+            b.take(d_d2, (size_t)n_mod * pl.nb);
+            b.take(d_q, 3 * (size_t)pl.nb);
+        }))) return rc;
     // HTM_ELL_STOP=mean|moments|finish ends the call after that part (tools/bench_ellipsoid.py times the parts by it)
     int stop = 4;
     if (const char *e = getenv("HTM_ELL_STOP")) stop = !strcmp(e, "mean") ? 1 : !strcmp(e, "moments") ? 2 : !strcmp(e, "finish") ? 3 : 4;
@@ -489,34 +402,34 @@ int htm_hypo_ellipsoid_dev(int device, const double *d_hypo, long ld, const doub
     hipLaunchKernelGGL(k_ell_stats, dim3((unsigned)((n_col + 63) / 64)), dim3(64), 0, st, (const double *)d_rng, (const double *)d_res,
                        n_col, n_slab, n_mod, d_stats);
     if (stop >= 2) {
-#define ELL_MOMENTS(NPIV)                                                                                                        \
-    hipLaunchKernelGGL(k_ell_moments<NPIV>, grid_w, dim3(64 * kEllWG), 0, st, d_hypo, ld, d_pivots, ld_piv, n_mod, n_win, pl.slab_rows, \
-                       (const double *)d_stats, d_mom)
+        auto moments = [&](auto npiv) {
+            hipLaunchKernelGGL(k_ell_moments<decltype(npiv)::value>, grid_w, dim3(64 * kEllWG), 0, st, d_hypo, ld, d_pivots, ld_piv, n_mod,
+                               n_win, pl.slab_rows, (const double *)d_stats, d_mom);
+        };
         switch (n_piv) {
-        case 0: ELL_MOMENTS(0); break;
-        case 1: ELL_MOMENTS(1); break;
-        case 2: ELL_MOMENTS(2); break;
-        case 3: ELL_MOMENTS(3); break;
-        default: ELL_MOMENTS(4); break;
+        case 0: moments(Int<0>()); break;
+        case 1: moments(Int<1>()); break;
+        case 2: moments(Int<2>()); break;
+        case 3: moments(Int<3>()); break;
+        default: moments(Int<4>()); break;
         }
-#undef ELL_MOMENTS
     }
     if (stop >= 3) {
         hipLaunchKernelGGL(k_ell_slabs, dim3((unsigned)((sum_n + 63) / 64)), dim3(64), 0, st, (const double *)d_mom, (long)sum_n, n_slab, d_sum);
         hipLaunchKernelGGL(k_ell_finish, dim3((unsigned)n_grp), dim3(64), 0, st, (const double *)d_sum, (const double *)d_stats, n_mod, n_win,
                            n_piv, d_out, d_piv_corr);
     }
-    if (hipGetLastError() != hipSuccess) return done(fail(HTM_EHIP, "an ellipsoid kernel's launch failed"));
+    if (hipGetLastError() != hipSuccess) return fail(HTM_EHIP, "an ellipsoid kernel's launch failed");
     const int rk[3] = {(int)rank_1based, (int)rank_1based, (int)rank_1based};
     for (long w0 = 0; stop >= 4 && w0 < n_win; w0 += pl.nb) {
         const long nb = std::min(pl.nb, n_win - w0), nb_grp = (nb + 63) / 64;
         hipLaunchKernelGGL(k_ell_maha, dim3((unsigned)((nb_grp + kEllWG - 1) / kEllWG), (unsigned)pl.slabs), dim3(64 * kEllWG), 0, st, d_hypo,
                            ld, n_mod, n_win, w0, nb, pl.slab_rows, (const double *)d_out, d_d2, pl.nb);
-        if ((rc = htm_quantiles_dev(device, d_d2, n_mod, nb, pl.nb, rk, d_q, hip_stream))) return done(rc);
+        if ((rc = htm_quantiles_dev(device, d_d2, n_mod, nb, pl.nb, rk, d_q, hip_stream))) return rc;
         hipLaunchKernelGGL(k_ell_setq, dim3((unsigned)nb_grp), dim3(64), 0, st, (const double *)d_q, w0, nb, d_out);
     }
-    if (hipGetLastError() != hipSuccess) return done(fail(HTM_EHIP, "an ellipsoid kernel's launch failed"));
-    return done(HTM_OK);
+    if (hipGetLastError() != hipSuccess) return fail(HTM_EHIP, "an ellipsoid kernel's launch failed");
+    return ws.release();
 }
 
 int htm_hypo_ellipsoid(int device, const double *hypo, const double *pivots, long n_mod, long n_win, int n_piv, long rank_1based,
@@ -525,22 +438,18 @@ int htm_hypo_ellipsoid(int device, const double *hypo, const double *pivots, lon
     EllPlan pl;
     int rc = ell_plan(hypo, pivots, n_mod, n_win, n_piv, rank_1based, 3 * n_win, n_piv, out, piv_corr, &pl);
     if (rc) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HTM_ENODEVICE, "no HIP device");
-    HIPCHK(hipSetDevice(device));
-    std::vector<void *> pool;
-    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
+    if ((rc = use_device(device))) return rc;
+    DevPool pool;
     const size_t on = (size_t)n_win * kEllOut, cn = (size_t)n_win * 3 * n_piv;
     double *d_x = nullptr, *d_p = nullptr, *d_o = nullptr, *d_c = nullptr;
-    if ((rc = dev_upload(pool, &d_x, hypo, (size_t)n_mod * 3 * n_win)) || (rc = dev_alloc(pool, &d_o, on)) ||
-        (n_piv > 0 && ((rc = dev_upload(pool, &d_p, pivots, (size_t)n_mod * n_piv)) || (rc = dev_alloc(pool, &d_c, cn)))))
-        return done(rc);
-    rc = htm_hypo_ellipsoid_dev(device, d_x, 3 * n_win, d_p, n_piv, n_mod, n_win, n_piv, rank_1based, d_o, d_c, nullptr);
-    if (rc == HTM_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(HTM_EHIP, "the ellipsoid kernels failed");
-    if (rc == HTM_OK && hipMemcpy(out, d_o, on * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(HTM_EHIP, "download failed");
-    if (rc == HTM_OK && n_piv > 0 && hipMemcpy(piv_corr, d_c, cn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(HTM_EHIP, "download failed");
-    return done(rc);
+    if ((rc = pool.upload(&d_x, hypo, (size_t)n_mod * 3 * n_win)) || (rc = pool.alloc(&d_o, on)) ||
+        (n_piv > 0 && ((rc = pool.upload(&d_p, pivots, (size_t)n_mod * n_piv)) || (rc = pool.alloc(&d_c, cn)))))
+        return rc;
+    if ((rc = htm_hypo_ellipsoid_dev(device, d_x, 3 * n_win, d_p, n_piv, n_mod, n_win, n_piv, rank_1based, d_o, d_c, nullptr))) return rc;
+    if (hipStreamSynchronize(nullptr) != hipSuccess) return fail(HTM_EHIP, "the ellipsoid kernels failed");
+    if ((rc = pool.download(out, d_o, on, "the ellipsoids'")) || (n_piv > 0 && (rc = pool.download(piv_corr, d_c, cn, "the pivot correlations'"))))
+        return rc;
+    return HTM_OK;
 }
 
 int htm_select_regress(int device, int n_sta, int n_win, const double *sta_x, const double *sta_y, const double *sta_z,
@@ -549,22 +458,20 @@ int htm_select_regress(int device, int n_sta, int n_win, const double *sta_x, co
     if (!sta_x || !sta_y || !sta_z || !t || !t_err || !a || !a_err || !out) return fail(HTM_EINVAL, "NULL argument");
     if (n_sta < 3 || n_win < 1) return fail(HTM_EINVAL, "need n_sta >= 3 and n_win >= 1 (got %d, %d)", n_sta, n_win);
     // a wave per window, four per workgroup: the dispatch packet holds the grid in work-items as a uint32_t
-    if (256L * ((n_win + 3L) / 4) > 0xffffffffL)
+    if (256L * ((n_win + 3L) / 4) > kMaxWorkItems)
         return fail(HTM_EINVAL, "n_win = %d windows need %ld work-items: more than one launch holds (2^32 - 1)", n_win,
                     256L * ((n_win + 3L) / 4));
     int rc = use_device(device);
     if (rc) return rc;
-    std::vector<void *> pool;
-    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
+    DevPool pool;
     const size_t n = (size_t)n_sta * n_win;
     double *dx = nullptr, *dy = nullptr, *dz = nullptr, *dt = nullptr, *dte = nullptr, *da = nullptr, *dae = nullptr, *dout = nullptr;
-    if ((rc = dev_upload(pool, &dx, sta_x, n_sta)) || (rc = dev_upload(pool, &dy, sta_y, n_sta)) || (rc = dev_upload(pool, &dz, sta_z, n_sta)) ||
-        (rc = dev_upload(pool, &dt, t, n)) || (rc = dev_upload(pool, &dte, t_err, n)) || (rc = dev_upload(pool, &da, a, n)) ||
-        (rc = dev_upload(pool, &dae, a_err, n)) || (rc = dev_alloc(pool, &dout, 6 * (size_t)n_win))) return done(rc);
+    if ((rc = pool.upload(&dx, sta_x, n_sta)) || (rc = pool.upload(&dy, sta_y, n_sta)) || (rc = pool.upload(&dz, sta_z, n_sta)) ||
+        (rc = pool.upload(&dt, t, n)) || (rc = pool.upload(&dte, t_err, n)) || (rc = pool.upload(&da, a, n)) ||
+        (rc = pool.upload(&dae, a_err, n)) || (rc = pool.alloc(&dout, 6 * (size_t)n_win))) return rc;
     hipLaunchKernelGGL(k_regress, dim3((n_win + 3) / 4), dim3(256), 0, 0, n_sta, n_win, dx, dy, dz, z_guess, dt, dte, da, dae, dout);
-    if (hipGetLastError() != hipSuccess) return done(fail(HTM_EHIP, "k_regress launch failed"));
-    if (hipMemcpy(out, dout, 6 * (size_t)n_win * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return done(fail(HTM_EHIP, "download failed"));
-    return done(HTM_OK);
+    if (hipGetLastError() != hipSuccess) return fail(HTM_EHIP, "k_regress launch failed");
+    return pool.download(out, dout, 6 * (size_t)n_win, "k_regress or its");
 }
 
 static int xcorr_check(long ld_env, long n_smp, int n_sta, int n, int n_step, int n_win, int pair0, int n_pairs, long ld_cc)
@@ -579,7 +486,7 @@ static int xcorr_check(long ld_env, long n_smp, int n_sta, int n, int n_step, in
     if (ld_cc < n_pairs) return fail(HTM_EINVAL, "ld_cc %ld < n_pairs %d", ld_cc, n_pairs);
     if ((long)n_win * n_pairs > 0x7fffffffL) return fail(HTM_EINVAL, "n_win * n_pairs = %ld exceeds one launch", (long)n_win * n_pairs);
     // the dispatch packet holds the grid in work-items as a uint32_t (hsa_kernel_dispatch_packet_t::grid_size_x)
-    if ((long)n_win * n_pairs * xc_threads(n) > 0xffffffffL)
+    if ((long)n_win * n_pairs * xc_threads(n) > kMaxWorkItems)
         return fail(HTM_EINVAL, "n_win * n_pairs * %d threads = %ld work-items exceed one launch (2^32 - 1)", xc_threads(n),
                     (long)n_win * n_pairs * xc_threads(n));
     return HTM_OK;
@@ -607,17 +514,14 @@ int htm_xcorr(int device, const double *env, long n_smp, int n_sta, int n, int n
     int rc = xcorr_check(n_smp, n_smp, n_sta, n, n_step, n_win, pair0, n_pairs, n_pairs);
     if (rc) return rc;
     if ((rc = use_device(device))) return rc;
-    std::vector<void *> pool;
-    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
+    DevPool pool;
     double *de = nullptr, *dc = nullptr, *dm = nullptr;
     const size_t n_cc = (size_t)n_win * n * n_pairs, n_m = (size_t)n_win * n_pairs;
-    if ((rc = dev_upload(pool, &de, env, (size_t)n_sta * n_smp)) || (rc = dev_alloc(pool, &dc, n_cc)) || (rc = dev_alloc(pool, &dm, n_m)))
-        return done(rc);
-    if ((rc = htm_xcorr_dev(device, de, n_smp, n_smp, n_sta, n, n_step, n_win, pair0, n_pairs, dc, n_pairs, dm, nullptr))) return done(rc);
-    if (hipMemcpy(cc, dc, n_cc * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(cc_max, dm, n_m * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-        return done(fail(HTM_EHIP, "k_xcorr or its download failed"));
-    return done(HTM_OK);
+    if ((rc = pool.upload(&de, env, (size_t)n_sta * n_smp)) || (rc = pool.alloc(&dc, n_cc)) || (rc = pool.alloc(&dm, n_m)))
+        return rc;
+    if ((rc = htm_xcorr_dev(device, de, n_smp, n_smp, n_sta, n, n_step, n_win, pair0, n_pairs, dc, n_pairs, dm, nullptr))) return rc;
+    if ((rc = pool.download(cc, dc, n_cc, "k_xcorr or its")) || (rc = pool.download(cc_max, dm, n_m, "k_xcorr or its"))) return rc;
+    return HTM_OK;
 }
 
 int htm_measure_windows(int device, int n_sta, int n, double dt, int n_det, const double *x, double *t, double *t_stdv,
@@ -629,8 +533,7 @@ int htm_measure_windows(int device, int n_sta, int n, double dt, int n_det, cons
     if (n_det == 0) return HTM_OK;
     int rc = use_device(device);
     if (rc) return rc;
-    std::vector<void *> pool;
-    auto done = [&](int code) { for (void *p : pool) (void)hipFree(p); return code; };
+    DevPool pool;
     // windows in launches of at most HTM_MEASURE_MB MiB of inputs and workspace (default 256: every window of a usual
     // run in one launch; at least one window per launch)
     const size_t per_win = ((size_t)n_sta * n + (size_t)n_sta * n_sta + 5 * (size_t)n_sta) * sizeof(double);
@@ -639,9 +542,9 @@ int htm_measure_windows(int device, int n_sta, int n, double dt, int n_det, cons
     const size_t budget = mb > 0.0 ? (size_t)std::min(mb * 1048576.0, 1e18) : 0;
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_det, budget / per_win));
     double *dx = nullptr, *dws = nullptr, *dout = nullptr;
-    if ((rc = dev_alloc(pool, &dx, (size_t)chunk * n_sta * n)) || (rc = dev_alloc(pool, &dws, (size_t)chunk * ((size_t)n_sta * n_sta + n_sta))) ||
-        (rc = dev_alloc(pool, &dout, 4 * (size_t)chunk * n_sta)))
-        return done(rc);
+    if ((rc = pool.alloc(&dx, (size_t)chunk * n_sta * n)) || (rc = pool.alloc(&dws, (size_t)chunk * ((size_t)n_sta * n_sta + n_sta))) ||
+        (rc = pool.alloc(&dout, 4 * (size_t)chunk * n_sta)))
+        return rc;
     double *outs[4] = {t, t_stdv, amp, amp_stdv};
     for (int w0 = 0; w0 < n_det; w0 += chunk) {
         const int nw = std::min(chunk, n_det - w0);
@@ -649,12 +552,11 @@ int htm_measure_windows(int device, int n_sta, int n, double dt, int n_det, cons
         HIPCHK(hipMemcpy(dx, x + (size_t)w0 * n_sta * n, ns * n * sizeof(double), hipMemcpyHostToDevice));
         hipLaunchKernelGGL(k_measure, dim3(nw), dim3(xc_threads(n)), 2 * (size_t)n * sizeof(double), 0, dx, n_sta, n, dt, nw, dws,
                            dout, dout + (size_t)chunk * n_sta, dout + 2 * (size_t)chunk * n_sta, dout + 3 * (size_t)chunk * n_sta);
-        if (hipGetLastError() != hipSuccess) return done(fail(HTM_EHIP, "k_measure launch failed"));
+        if (hipGetLastError() != hipSuccess) return fail(HTM_EHIP, "k_measure launch failed");
         for (int k = 0; k < 4; ++k)
-            if (hipMemcpy(outs[k] + (size_t)w0 * n_sta, dout + k * (size_t)chunk * n_sta, ns * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-                return done(fail(HTM_EHIP, "k_measure or its download failed"));
+            if ((rc = pool.download(outs[k] + (size_t)w0 * n_sta, dout + k * (size_t)chunk * n_sta, ns, "k_measure or its"))) return rc;
     }
-    return done(HTM_OK);
+    return HTM_OK;
 }
 
 }  // extern "C"
@@ -670,6 +572,10 @@ struct FftPlan {
     long m = 0;                      // Bluestein: inner power-of-two length (0: Stockham)
     const FftPlan *inner = nullptr;
     double2 *d_chirp = nullptr, *d_b = nullptr;
+    FftPlan() = default;
+    FftPlan(const FftPlan &) = delete; FftPlan &operator=(const FftPlan &) = delete;
+    // only a plan whose build failed is destroyed: the plans in g_fft_plans are never deleted, on purpose (no hipFree at exit)
+    ~FftPlan() { (void)hipFree(d_tw); (void)hipFree(d_chirp); (void)hipFree(d_b); }
 };
 
 std::mutex g_fft_mu;
@@ -728,12 +634,16 @@ int fft_run(const FftPlan &p, const double2 *in, long ld_in, double2 *out, long 
             const int R = p.radix[i];
             const long total = rows * (n / R);
             const double2 *tw = p.d_tw + p.tw_off[i];
+            auto pass = [&](auto radix) {
+                hipLaunchKernelGGL(k_fft_pass<decltype(radix)::value>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n,
+                                   (int)ns, tw, sign, total);
+            };
             switch (R) {
-            case 2: hipLaunchKernelGGL(k_fft_pass<2>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n, (int)ns, tw, sign, total); break;
-            case 3: hipLaunchKernelGGL(k_fft_pass<3>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n, (int)ns, tw, sign, total); break;
-            case 4: hipLaunchKernelGGL(k_fft_pass<4>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n, (int)ns, tw, sign, total); break;
-            case 5: hipLaunchKernelGGL(k_fft_pass<5>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n, (int)ns, tw, sign, total); break;
-            default: hipLaunchKernelGGL(k_fft_pass<7>, fft_grid(total), dim3(kFftThreads), 0, st, src, lds, dst, ldd, (int)n, (int)ns, tw, sign, total); break;
+            case 2: pass(Int<2>()); break;
+            case 3: pass(Int<3>()); break;
+            case 4: pass(Int<4>()); break;
+            case 5: pass(Int<5>()); break;
+            default: pass(Int<7>()); break;
             }
             src = dst; lds = ldd; ns *= R;
         }
@@ -798,11 +708,11 @@ int fft_plan_locked(int device, long n, const FftPlan **out)
         HIPCHK(hipMalloc(reinterpret_cast<void **>(&p->d_b), m * sizeof(double2)));
         HIPCHK(hipMemcpy(p->d_chirp, w.data(), n * sizeof(double2), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(p->d_b, b.data(), m * sizeof(double2), hipMemcpyHostToDevice));
+        DevPool pool;
         double2 *tmp = nullptr;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&tmp), m * sizeof(double2)));
+        if ((rc = pool.alloc(&tmp, m))) return rc;
         rc = fft_run(*p->inner, p->d_b, m, p->d_b, m, 1, -1, tmp, nullptr);
         const hipError_t e = hipDeviceSynchronize();
-        (void)hipFree(tmp);
         if (rc) return rc;
         if (e != hipSuccess) return fail(HTM_EHIP, "Bluestein table of n = %ld: %s", n, hipGetErrorString(e));
     }
@@ -817,33 +727,6 @@ int fft_plan(int device, long n, const FftPlan **out)
     return fft_plan_locked(device, n, out);
 }
 
-// stream-ordered workspace, as htm_quantiles_dev allocates it
-struct AsyncBuf {
-    void *p = nullptr;
-    hipStream_t st = nullptr;
-    bool async = false;
-    int alloc(size_t bytes, hipStream_t s)
-    {
-        st = s;
-        async = hipMallocAsync(&p, std::max<size_t>(bytes, 1), st) == hipSuccess;
-        if (!async) {
-            (void)hipGetLastError();
-            if (hipMalloc(&p, std::max<size_t>(bytes, 1)) != hipSuccess) { p = nullptr; return fail(HTM_EHIP, "hipMalloc of %zu bytes failed", bytes); }
-        }
-        return HTM_OK;
-    }
-    int release()
-    {
-        if (!p) return HTM_OK;
-        void *q = p;
-        p = nullptr;
-        if (async) { HIPCHK(hipFreeAsync(q, st)); return HTM_OK; }
-        HIPCHK(hipStreamSynchronize(st));
-        (void)hipFree(q);
-        return HTM_OK;
-    }
-};
-
 int fft_check(const void *in, long ld_in, const void *out, long ld_out, long n, long batch, int direction)
 {
     if (!in || !out) return fail(HTM_EINVAL, "NULL argument");
@@ -851,7 +734,7 @@ int fft_check(const void *in, long ld_in, const void *out, long ld_out, long n, 
     if (batch < 1 || ld_in < n || ld_out < n) return fail(HTM_EINVAL, "bad shape (batch %ld, ld_in %ld, ld_out %ld, n %ld)", batch, ld_in, ld_out, n);
     if (direction != -1 && direction != 1) return fail(HTM_EINVAL, "direction must be -1 (forward) or +1 (backward), got %d", direction);
     if (in == out && ld_in != ld_out) return fail(HTM_EINVAL, "in place needs ld_in == ld_out");
-    if (fft_max_items(n, batch) > 0xffffffffL)
+    if (fft_max_items(n, batch) > kMaxWorkItems)
         return fail(HTM_EINVAL, "%ld rows of n = %ld need %ld work-items in one launch (more than 2^32 - 1)", batch, n, fft_max_items(n, batch));
     return HTM_OK;
 }
@@ -874,7 +757,7 @@ int cv_check(long n_total, int n, int n_fac, int h, const int k_band[4], long j0
     const long last = cv_last(n_total, n);
     if (j0 < 0 || j0 > j1 || j1 > last) return fail(HTM_EINVAL, "segments %ld..%ld outside 0..%ld", j0, j1, last);
     const long S = j1 - j0 + 1;
-    if (std::max(fft_max_items(n, 2 * S), 2 * S * (long)n) > 0xffffffffL)
+    if (std::max(fft_max_items(n, 2 * S), 2 * S * (long)n) > kMaxWorkItems)
         return fail(HTM_EINVAL, "%ld segments of n = %d need more than 2^32 - 1 work-items in one launch", S, n);
     return HTM_OK;
 }
@@ -892,11 +775,12 @@ int htm_fft_dev(int device, const double *d_in, long ld_in, double *d_out, long 
     const FftPlan *p = nullptr;
     if ((rc = fft_plan(device, n, &p))) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    AsyncBuf ws;
-    if ((rc = ws.alloc(fft_ws_elems(n, batch) * sizeof(double2), st))) return rc;
-    rc = fft_run(*p, reinterpret_cast<const double2 *>(d_in), ld_in, reinterpret_cast<double2 *>(d_out), ld_out, batch, direction, static_cast<double2 *>(ws.p), st);
-    const int rc2 = ws.release();
-    return rc ? rc : rc2;
+    StreamBuf ws;
+    double2 *fw = nullptr;
+    if ((rc = ws.alloc(st, [&](StreamBuf &b) { b.take(fw, fft_ws_elems(n, batch)); }))) return rc;
+    if ((rc = fft_run(*p, reinterpret_cast<const double2 *>(d_in), ld_in, reinterpret_cast<double2 *>(d_out), ld_out, batch, direction, fw, st)))
+        return rc;
+    return ws.release();
 }
 
 int htm_fft(int device, const double *in, long ld_in, double *out, long ld_out, long n, long batch, int direction)
@@ -904,16 +788,14 @@ int htm_fft(int device, const double *in, long ld_in, double *out, long ld_out, 
     int rc = fft_check(in, ld_in, out, ld_out, n, batch, direction);
     if (rc) return rc;
     if ((rc = use_device(device))) return rc;
-    std::vector<void *> pool;
-    auto done = [&](int code) { for (void *q : pool) (void)hipFree(q); return code; };
+    DevPool pool;
     const size_t ni = 2 * ((size_t)(batch - 1) * ld_in + n), no = 2 * ((size_t)(batch - 1) * ld_out + n);
     double *di = nullptr, *dout = nullptr;
-    if ((rc = dev_upload(pool, &dout, out, no))) return done(rc);      // keeps the padding between strided rows
+    if ((rc = pool.upload(&dout, out, no))) return rc;      // keeps the padding between strided rows
     if (in == out) di = dout;
-    else if ((rc = dev_upload(pool, &di, in, ni))) return done(rc);
-    if ((rc = htm_fft_dev(device, di, ld_in, dout, ld_out, n, batch, direction, nullptr))) return done(rc);
-    if (hipMemcpy(out, dout, no * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return done(fail(HTM_EHIP, "FFT or its download failed"));
-    return done(HTM_OK);
+    else if ((rc = pool.upload(&di, in, ni))) return rc;
+    if ((rc = htm_fft_dev(device, di, ld_in, dout, ld_out, n, batch, direction, nullptr))) return rc;
+    return pool.download(out, dout, no, "FFT or its");
 }
 
 int htm_convert_dev(int device, const float *d_x1, const float *d_x2, long n_total, int n, int n_fac, int h,
@@ -929,20 +811,22 @@ int htm_convert_dev(int device, const float *d_x1, const float *d_x2, long n_tot
     const long S = j1 - j0 + 1, n2 = n / 2, last = cv_last(n_total, n);
     const long n_valid = std::min(n_total, j1 * n2 + n) - j0 * n2;
     // workspace: z [S][n] (later the first smoothing [2S][n] doubles), y [2S][n], the FFT's own, 4S coefficients
-    const size_t zb = (size_t)S * n * sizeof(double2), yb = 2 * zb, fb = fft_ws_elems(n, 2 * S) * sizeof(double2);
-    AsyncBuf ws;
-    if ((rc = ws.alloc(zb + yb + fb + 4 * S * sizeof(double), st))) return rc;
-    char *base = static_cast<char *>(ws.p);
-    double2 *z = reinterpret_cast<double2 *>(base), *y = reinterpret_cast<double2 *>(base + zb);
-    double2 *fw = reinterpret_cast<double2 *>(base + zb + yb);
-    double *coef = reinterpret_cast<double *>(base + zb + yb + fb);
     const long sn = S * n;
+    StreamBuf ws;
+    double2 *z = nullptr, *y = nullptr, *fw = nullptr;
+    double *coef = nullptr;
+    if ((rc = ws.alloc(st, [&](StreamBuf &b) {
+            b.take(z, (size_t)sn);
+            b.take(y, 2 * (size_t)sn);
+            b.take(fw, fft_ws_elems(n, 2 * S));
+            b.take(coef, 4 * (size_t)S);
+        }))) return rc;
     hipLaunchKernelGGL(k_cv_detrend, dim3((unsigned)S), dim3(kCvSumThreads), 0, st, d_x1, d_x2, n_valid, n, coef);
     hipLaunchKernelGGL(k_cv_pack, fft_grid(sn), dim3(kCvThreads), 0, st, d_x1, d_x2, n_valid, n, coef, z, sn);
-    if ((rc = fft_run(*p, z, n, z, n, S, -1, fw, st))) { ws.release(); return rc; }
+    if ((rc = fft_run(*p, z, n, z, n, S, -1, fw, st))) return rc;
     const int4 kb = make_int4(k_band[0], k_band[1], k_band[2], k_band[3]);
     hipLaunchKernelGGL(k_cv_spectrum, fft_grid(sn), dim3(kCvThreads), 0, st, z, n, kb, y, sn);
-    if ((rc = fft_run(*p, y, n, y, n, 2 * S, +1, fw, st))) { ws.release(); return rc; }
+    if ((rc = fft_run(*p, y, n, y, n, 2 * S, +1, fw, st))) return rc;
     const int tiles1 = (int)ceil_div(n, kCvTile), tiles2 = (int)ceil_div(n - n / 4, kCvTile);
     const size_t lds = 2 * (size_t)(kCvTile + 2 * h) * sizeof(double);
     double *e1 = reinterpret_cast<double *>(z);
@@ -952,9 +836,8 @@ int htm_convert_dev(int device, const float *d_x1, const float *d_x2, long n_tot
     hipLaunchKernelGGL(k_cv_smooth<true>, dim3((unsigned)(S * tiles2)), dim3(kCvThreads), lds, st, (const double2 *)nullptr, e1,
                        (double *)nullptr, n, h, tiles2, j0, last, n_total, n_fac, k_base, fac1, fac2, d_out);
     const hipError_t e = hipGetLastError();
-    rc = ws.release();
     if (e != hipSuccess) return fail(HTM_EHIP, "step-1 kernels failed to launch: %s", hipGetErrorString(e));
-    return rc;
+    return ws.release();
 }
 
 int htm_convert(int device, const float *x1, const float *x2, long n_total, int n, int n_fac, int h, const int k_band[4],
@@ -964,18 +847,16 @@ int htm_convert(int device, const float *x1, const float *x2, long n_total, int 
     int rc = cv_check(n_total, n, n_fac, h, k_band, j0, j1);
     if (rc) return rc;
     if ((rc = use_device(device))) return rc;
-    std::vector<void *> pool;
-    auto done = [&](int code) { for (void *q : pool) (void)hipFree(q); return code; };
+    DevPool pool;
     const long n2 = n / 2;
     const size_t n_valid = (size_t)(std::min(n_total, j1 * n2 + n) - j0 * n2);
     const size_t n_out = (size_t)(ceil_div(cv_end(j1, n_total, n), n_fac) - ceil_div(cv_start(j0, n), n_fac));
     float *d1 = nullptr, *d2 = nullptr;
     double *dout = nullptr;
-    if ((rc = dev_upload(pool, &d1, x1, n_valid)) || (rc = dev_upload(pool, &d2, x2, n_valid)) || (rc = dev_alloc(pool, &dout, n_out)))
-        return done(rc);
-    if ((rc = htm_convert_dev(device, d1, d2, n_total, n, n_fac, h, k_band, fac1, fac2, j0, j1, dout, nullptr))) return done(rc);
-    if (hipMemcpy(out, dout, n_out * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return done(fail(HTM_EHIP, "step-1 kernels or their download failed"));
-    return done(HTM_OK);
+    if ((rc = pool.upload(&d1, x1, n_valid)) || (rc = pool.upload(&d2, x2, n_valid)) || (rc = pool.alloc(&dout, n_out)))
+        return rc;
+    if ((rc = htm_convert_dev(device, d1, d2, n_total, n, n_fac, h, k_band, fac1, fac2, j0, j1, dout, nullptr))) return rc;
+    return pool.download(out, dout, n_out, "step-1 kernels or their");
 }
 
 }  // extern "C"

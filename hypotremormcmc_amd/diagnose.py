@@ -25,7 +25,7 @@ import numpy as np
 
 from . import _lib
 from .param import Param
-from .statistics import INT_MAX, read_sample_file
+from .statistics import read_sample_file, sample_matrix
 
 RANK_STAT_HEADER = "# parameter, R-hat (larger of the next two), rank-normalised R-hat, folded R-hat, bulk-ESS, tail-ESS"
 STAT_HEADER = "# parameter, R-hat (split), ESS, tau, lag of the first negative pair sum (-1: none up to the last lag)"
@@ -35,79 +35,37 @@ def diagnose(samples, n_seq: int, max_lag: int = 1000, device: int = 0, return_a
     """[n_par][4] = (rhat, ess, tau, lags) of every column of samples [n_seq * n_draws][n_par], sequence m in rows
     m * n_draws .. (m + 1) * n_draws - 1, on the GPU.  With return_acov also the averaged autocovariances
     [(L + 1)][n_par], L = min(n_draws // 2 - 1, max_lag)."""
-    shape = np.shape(samples)
-    if len(shape) == 1:
-        shape = (shape[0], 1)
-    if len(shape) != 2:
-        raise ValueError(f"samples must be [rows][n_par], got shape {shape}")
-    n_rows, n_par = shape
-    n_seq, max_lag = int(n_seq), int(max_lag)
-    if n_rows > INT_MAX:      # ctypes would pass it on; htm_diagnose counts rows in int
-        raise ValueError(f"rows = {n_rows} exceeds {INT_MAX}: htm_diagnose takes at most {INT_MAX} rows")
-    if n_seq < 1 or n_par < 1 or max_lag < 1 or max_lag > INT_MAX:
-        raise ValueError(f"need n_seq >= 1, n_par >= 1 and 1 <= max_lag <= {INT_MAX} (got {n_seq}, {n_par}, {max_lag})")
-    if n_rows % n_seq:
-        raise ValueError(f"{n_rows} rows are not {n_seq} sequences of equal length")
-    n_draws = n_rows // n_seq
+    x, n_draws = sample_matrix(samples, "htm_diagnose takes", n_seq=n_seq, max_lag=max_lag)
     if n_draws < 4:
         raise ValueError(f"n_draws = {n_draws}: a sequence needs at least 4 draws to be split")
-    x = np.ascontiguousarray(samples, dtype=np.float64).reshape(n_rows, n_par)
-    if not np.isfinite(x).all():
-        raise ValueError("samples hold NaN or inf")
+    n_par = x.shape[1]
     n_lag = min(n_draws // 2 - 1, max_lag) + 1
     out = np.empty((n_par, 4))
     acov = np.empty((n_lag, n_par)) if return_acov else None
-    lib = _lib.load()
-    _lib.check(lib.htm_diagnose(device, x.ctypes.data_as(_lib.dp), n_seq, n_draws, n_par, max_lag, out.ctypes.data_as(_lib.dp),
-                                acov.ctypes.data_as(_lib.dp) if return_acov else None))
+    _lib.check(_lib.load().htm_diagnose(device, _lib.ptr(x), int(n_seq), n_draws, n_par, int(max_lag), _lib.ptr(out), _lib.ptr(acov)))
     return (out, acov) if return_acov else out
-
-
-def _sample_matrix(samples, n_seq, max_lag, what):
-    """the checks `diagnose` makes before any device call, for the rank entry points: x [n_rows][n_par], n_draws"""
-    shape = np.shape(samples)
-    if len(shape) == 1:
-        shape = (shape[0], 1)
-    if len(shape) != 2:
-        raise ValueError(f"samples must be [rows][n_par], got shape {shape}")
-    n_rows, n_par = shape
-    n_seq, max_lag = int(n_seq), int(max_lag)
-    if n_rows > INT_MAX:
-        raise ValueError(f"rows = {n_rows} exceeds {INT_MAX}: {what} takes at most {INT_MAX} rows")
-    if n_seq < 1 or n_par < 1 or max_lag < 1 or max_lag > INT_MAX:
-        raise ValueError(f"need n_seq >= 1, n_par >= 1 and 1 <= max_lag <= {INT_MAX} (got {n_seq}, {n_par}, {max_lag})")
-    if n_rows % n_seq:
-        raise ValueError(f"{n_rows} rows are not {n_seq} sequences of equal length")
-    x = np.ascontiguousarray(samples, dtype=np.float64).reshape(n_rows, n_par)
-    if not np.isfinite(x).all():
-        raise ValueError("samples hold NaN or inf")
-    return x, n_rows // n_seq
 
 
 def rank_normalize(samples, fold: bool = False, return_ranks: bool = False, device: int = 0):
     """z [n_rows][n_par] = Phi^-1((r - 3/8) / (n_rows + 1/4)), r the 1-based average rank of an element within its column
     (of |x - median| with fold), on the GPU.  With return_ranks also r."""
-    x, n_rows = _sample_matrix(samples, 1, 1, "htm_rank_normalize")
+    x, n_rows = sample_matrix(samples, "htm_rank_normalize takes")
     if n_rows < 2:
         raise ValueError(f"n_rows = {n_rows}: ranking needs at least 2 rows")
     z = np.empty_like(x)
     ranks = np.empty_like(x) if return_ranks else None
-    lib = _lib.load()
-    _lib.check(lib.htm_rank_normalize(device, x.ctypes.data_as(_lib.dp), n_rows, x.shape[1], 1 if fold else 0,
-                                      z.ctypes.data_as(_lib.dp), ranks.ctypes.data_as(_lib.dp) if return_ranks else None))
+    _lib.check(_lib.load().htm_rank_normalize(device, _lib.ptr(x), n_rows, x.shape[1], 1 if fold else 0, _lib.ptr(z), _lib.ptr(ranks)))
     return (z, ranks) if return_ranks else z
 
 
 def diagnose_rank(samples, n_seq: int, max_lag: int = 1000, device: int = 0):
     """[n_par][4] = (rhat_bulk, rhat_folded, ess_bulk, ess_tail) of every column of samples, laid out as for `diagnose`,
     on the GPU.  The R-hat to report is the larger of the first two."""
-    x, n_draws = _sample_matrix(samples, n_seq, max_lag, "htm_diagnose_rank")
+    x, n_draws = sample_matrix(samples, "htm_diagnose_rank takes", n_seq=n_seq, max_lag=max_lag)
     if n_draws < 4:
         raise ValueError(f"n_draws = {n_draws}: a sequence needs at least 4 draws to be split")
     out = np.empty((x.shape[1], 4))
-    lib = _lib.load()
-    _lib.check(lib.htm_diagnose_rank(device, x.ctypes.data_as(_lib.dp), int(n_seq), n_draws, x.shape[1], int(max_lag),
-                                     out.ctypes.data_as(_lib.dp)))
+    _lib.check(_lib.load().htm_diagnose_rank(device, _lib.ptr(x), int(n_seq), n_draws, x.shape[1], int(max_lag), _lib.ptr(out)))
     return out
 
 

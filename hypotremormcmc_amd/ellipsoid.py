@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from .param import Param
-from .statistics import INT_MAX, read_sample_file
+from .statistics import read_sample_file, sample_matrix
 
 N_OUT = 22
 MAX_PIVOTS = 4
@@ -66,26 +66,12 @@ def level_rank(level: float, n_mod: int) -> int:
     return min(n_mod, max(1, math.ceil(level * n_mod)))
 
 
-def _sample_matrix(samples, what):
-    shape = np.shape(samples)
-    if len(shape) == 1:
-        shape = (shape[0], 1)
-    if len(shape) != 2:
-        raise ValueError(f"{what} must be [n_mod][columns], got shape {shape}")
-    if shape[0] > INT_MAX:
-        raise ValueError(f"rows = {shape[0]} exceeds {INT_MAX}: htm_hypo_ellipsoid takes at most {INT_MAX} rows")
-    x = np.ascontiguousarray(samples, dtype=np.float64).reshape(shape)
-    if not np.isfinite(x).all():
-        raise ValueError(f"{what} hold NaN or inf")
-    return x
-
-
 def ellipsoid(hypo, pivots=None, level: float = 0.68, device: int = 0):
     """hypo [n_mod][3 n_win] (window w in columns 3w .. 3w+2), pivots [n_mod][n_piv] or None, on the GPU.  Returns a dict:
     mean [n_win][3], cov [n_win][3][3], lam [n_win][3] (descending), axes [n_win][3][3] (column k = unit axis k), q [n_win]
     (the ellipsoid with semi-axes sqrt(q lam_k) holds `rank` = level_rank(level, n_mod) of the samples), piv_corr
     [n_win][3][n_piv], rank.  lam, axes and q of a window that does not span three dimensions are NaN."""
-    x = _sample_matrix(hypo, "hypo")
+    x, _ = sample_matrix(hypo, "htm_hypo_ellipsoid takes", n_seq=None, name="hypo", layout="[n_mod][columns]")
     n_mod, n_col = x.shape
     if n_col < 3 or n_col % 3:
         raise ValueError(f"hypo has {n_col} columns: need x, y, z of every window")
@@ -95,16 +81,15 @@ def ellipsoid(hypo, pivots=None, level: float = 0.68, device: int = 0):
     if pivots is None:
         p, n_piv = None, 0
     else:
-        p = _sample_matrix(pivots, "pivots")
+        p, _ = sample_matrix(pivots, "htm_hypo_ellipsoid takes", n_seq=None, name="pivots", layout="[n_mod][columns]")
         n_piv = p.shape[1]
         if p.shape[0] != n_mod or not 1 <= n_piv <= MAX_PIVOTS:
             raise ValueError(f"pivots {p.shape}: need {n_mod} rows and 1..{MAX_PIVOTS} columns")
     rank = level_rank(level, n_mod)
     out = np.empty((n_win, N_OUT))
     corr = np.empty((n_win, 3, n_piv))
-    lib = _lib.load()
-    _lib.check(lib.htm_hypo_ellipsoid(device, x.ctypes.data_as(_lib.dp), p.ctypes.data_as(_lib.dp) if n_piv else None, n_mod, n_win,
-                                      n_piv, rank, out.ctypes.data_as(_lib.dp), corr.ctypes.data_as(_lib.dp) if n_piv else None))
+    _lib.check(_lib.load().htm_hypo_ellipsoid(device, _lib.ptr(x), _lib.ptr(p), n_mod, n_win, n_piv, rank, _lib.ptr(out),
+                                              _lib.ptr(corr) if n_piv else None))
     return unpack(out, corr, rank)
 
 

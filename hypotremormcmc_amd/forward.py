@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check, dp
+from ._lib import check, ptr
 
 
 def _arr(a, n=None):
@@ -19,10 +19,6 @@ def _arr(a, n=None):
     if n is not None and a.size != n:
         raise ValueError(f"expected {n} values, got {a.size}")
     return a
-
-
-def _p(a):
-    return a.ctypes.data_as(dp)
 
 
 class ObsArrays:
@@ -46,7 +42,7 @@ class Forward:
         arrs = [_arr(sta_x, n_sta), _arr(sta_y, n_sta), _arr(sta_z, n_sta), _arr(obs.get_t_obs(), n),
                 _arr(obs.get_t_stdv(), n), _arr(obs.get_a_obs(), n), _arr(obs.get_a_stdv(), n)]
         h = C.c_void_p()
-        check(self._lib.htm_forward_create(self.n_sta, self.n_events, *[_p(a) for a in arrs],
+        check(self._lib.htm_forward_create(self.n_sta, self.n_events, *[ptr(a) for a in arrs],
                                            int(bool(use_time)), int(bool(use_amp)), int(device), C.byref(h)))
         self.handle = h
         self.device = device
@@ -91,9 +87,9 @@ class Forward:
     # -- reference bound procedures -------------------------------------------------------------------
     def calc_log_likelihood(self, hypo, t_corr, vs, a_corr, qs) -> float:
         out = C.c_double()
-        check(self._lib.htm_forward_loglik_full(self.handle, _p(_arr(hypo, 3 * self.n_events)),
-                                                _p(_arr(t_corr, self.n_sta)), float(vs),
-                                                _p(_arr(a_corr, self.n_sta)), float(qs), C.byref(out)))
+        check(self._lib.htm_forward_loglik_full(self.handle, ptr(_arr(hypo, 3 * self.n_events)),
+                                                ptr(_arr(t_corr, self.n_sta)), float(vs),
+                                                ptr(_arr(a_corr, self.n_sta)), float(qs), C.byref(out)))
         return out.value
 
     def partially_update_log_likelihood(self, evt_id, hypo_old, log_likelihood_old, hypo, t_corr, vs, a_corr,
@@ -106,33 +102,33 @@ class Forward:
         xo = np.ascontiguousarray(ho[3 * (e - 1):3 * e])
         xn = np.ascontiguousarray(hn[3 * (e - 1):3 * e])
         out = C.c_double()
-        check(self._lib.htm_forward_loglik_partial(self.handle, e, _p(xo), float(log_likelihood_old), _p(xn),
-                                                   _p(_arr(t_corr, self.n_sta)), float(vs),
-                                                   _p(_arr(a_corr, self.n_sta)), float(qs), C.byref(out)))
+        check(self._lib.htm_forward_loglik_partial(self.handle, e, ptr(xo), float(log_likelihood_old), ptr(xn),
+                                                   ptr(_arr(t_corr, self.n_sta)), float(vs),
+                                                   ptr(_arr(a_corr, self.n_sta)), float(qs), C.byref(out)))
         return out.value
 
     def calc_travel_time(self, hypo, t_corr, vs) -> np.ndarray:
         out = np.empty((self.n_events, self.n_sta))
-        check(self._lib.htm_forward_travel_time(self.handle, _p(_arr(hypo, 3 * self.n_events)),
-                                                _p(_arr(t_corr, self.n_sta)), float(vs), _p(out)))
+        check(self._lib.htm_forward_travel_time(self.handle, ptr(_arr(hypo, 3 * self.n_events)),
+                                                ptr(_arr(t_corr, self.n_sta)), float(vs), ptr(out)))
         return out
 
     def calc_amp(self, hypo, a_corr, qs, vs) -> np.ndarray:
         out = np.empty((self.n_events, self.n_sta))
-        check(self._lib.htm_forward_amp(self.handle, _p(_arr(hypo, 3 * self.n_events)),
-                                        _p(_arr(a_corr, self.n_sta)), float(qs), float(vs), _p(out)))
+        check(self._lib.htm_forward_amp(self.handle, ptr(_arr(hypo, 3 * self.n_events)),
+                                        ptr(_arr(a_corr, self.n_sta)), float(qs), float(vs), ptr(out)))
         return out
 
     def calc_travel_time_single(self, evt_id, hypo, t_corr, vs) -> np.ndarray:
         out = np.empty(self.n_sta)
-        check(self._lib.htm_forward_travel_time_single(self.handle, int(evt_id), _p(_arr(hypo, 3 * self.n_events)),
-                                                       _p(_arr(t_corr, self.n_sta)), float(vs), _p(out)))
+        check(self._lib.htm_forward_travel_time_single(self.handle, int(evt_id), ptr(_arr(hypo, 3 * self.n_events)),
+                                                       ptr(_arr(t_corr, self.n_sta)), float(vs), ptr(out)))
         return out
 
     def calc_amp_single(self, evt_id, hypo, a_corr, qs, vs) -> np.ndarray:
         out = np.empty(self.n_sta)
-        check(self._lib.htm_forward_amp_single(self.handle, int(evt_id), _p(_arr(hypo, 3 * self.n_events)),
-                                               _p(_arr(a_corr, self.n_sta)), float(qs), float(vs), _p(out)))
+        check(self._lib.htm_forward_amp_single(self.handle, int(evt_id), ptr(_arr(hypo, 3 * self.n_events)),
+                                               ptr(_arr(a_corr, self.n_sta)), float(qs), float(vs), ptr(out)))
         return out
 
     # -- batched extension ----------------------------------------------------------------------------
@@ -140,9 +136,9 @@ class Forward:
         vs = _arr(vs)
         n = vs.size
         out = np.empty(n)
-        check(self._lib.htm_forward_loglik_full_batch(self.handle, n, _p(_arr(hypo, n * 3 * self.n_events)),
-                                                      _p(_arr(t_corr, n * self.n_sta)), _p(vs),
-                                                      _p(_arr(a_corr, n * self.n_sta)), _p(_arr(qs, n)), _p(out)))
+        check(self._lib.htm_forward_loglik_full_batch(self.handle, n, ptr(_arr(hypo, n * 3 * self.n_events)),
+                                                      ptr(_arr(t_corr, n * self.n_sta)), ptr(vs),
+                                                      ptr(_arr(a_corr, n * self.n_sta)), ptr(_arr(qs, n)), ptr(out)))
         return out
 
     def calc_log_likelihood_batch_dev(self, n, d_hypo, d_t_corr, d_vs, d_a_corr, d_qs, d_out):

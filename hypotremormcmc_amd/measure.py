@@ -35,14 +35,10 @@ import sys
 import numpy as np
 
 from . import _lib, correlate as corr
-from ._lib import check, dp
+from ._lib import check, ptr
 from .param import Param
 
 INT_MAX = 2 ** 31 - 1      # htm_quantiles_dev takes int ranks and counts rows in int
-
-
-def _p(a):
-    return a.ctypes.data_as(dp)
 
 
 def envelope_dt(path):
@@ -90,7 +86,7 @@ def measure_windows(x, dt, device=0):
     x = np.ascontiguousarray(x, dtype=np.float64)
     n_det, n_sta, n = x.shape
     out = [np.empty((n_det, n_sta)) for _ in range(4)]
-    check(_lib.load().htm_measure_windows(int(device), n_sta, n, float(dt), n_det, _p(x), *(_p(o) for o in out)))
+    check(_lib.load().htm_measure_windows(int(device), n_sta, n, float(dt), n_det, ptr(x), *(ptr(o) for o in out)))
     return tuple(out)
 
 

@@ -18,13 +18,9 @@ import sys
 import numpy as np
 
 from . import _lib
-from ._lib import check, dp
+from ._lib import check, ptr
 from .obs_data import ObsData
 from .param import Param
-
-
-def _p(a):
-    return a.ctypes.data_as(dp)
 
 
 def regress(sta_x, sta_y, sta_z, z_guess, t, t_err, a, a_err, device=0):
@@ -43,8 +39,8 @@ def regress(sta_x, sta_y, sta_z, z_guess, t, t_err, a, a_err, device=0):
         if v.shape != t.shape:
             raise ValueError("%s has shape %s, t has %s" % (name, v.shape, t.shape))
     out = np.empty((n_win, 6))
-    check(_lib.load().htm_select_regress(int(device), n_sta, n_win, _p(arrs[0]), _p(arrs[1]), _p(arrs[2]), float(z_guess),
-                                         _p(arrs[3]), _p(arrs[4]), _p(arrs[5]), _p(arrs[6]), _p(out)))
+    check(_lib.load().htm_select_regress(int(device), n_sta, n_win, ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), float(z_guess),
+                                         ptr(arrs[3]), ptr(arrs[4]), ptr(arrs[5]), ptr(arrs[6]), ptr(out)))
     return out
 
 

@@ -43,20 +43,41 @@ def ranks(n_mod: int):
     return tuple(int(f(c) * f(n_mod)) for c in (0.025, 0.5, 0.975))
 
 
+def sample_matrix(samples, what, *, n_seq=1, max_lag=1, name="samples", layout="[rows][n_par]", finite=True):
+    """x [n_rows][n_par] float64 C-contiguous and n_draws = n_rows // n_seq: what every entry point that takes a sample matrix
+    checks before any device call.  `what` says which C entry point counts the rows in int and how ("htm_diagnose takes"),
+    `name` and `layout` name the argument.  n_seq None: the rows are no sequences (nothing about n_seq, n_par, max_lag is
+    refused; n_draws is n_rows).  Quantiles of NaN are defined: `finite=False`."""
+    shape = np.shape(samples)
+    if len(shape) == 1:
+        shape = (shape[0], 1)
+    if len(shape) != 2:
+        raise ValueError(f"{name} must be {layout}, got shape {shape}")
+    n_rows, n_par = shape
+    if n_rows > INT_MAX:      # ctypes would pass it on
+        raise ValueError(f"rows = {n_rows} exceeds {INT_MAX}: {what} at most {INT_MAX} rows")
+    if n_seq is not None:
+        n_seq, max_lag = int(n_seq), int(max_lag)
+        if n_seq < 1 or n_par < 1 or max_lag < 1 or max_lag > INT_MAX:
+            raise ValueError(f"need n_seq >= 1, n_par >= 1 and 1 <= max_lag <= {INT_MAX} (got {n_seq}, {n_par}, {max_lag})")
+        if n_rows % n_seq:
+            raise ValueError(f"{n_rows} rows are not {n_seq} sequences of equal length")
+    x = np.ascontiguousarray(samples, dtype=np.float64).reshape(shape)
+    if finite and not np.isfinite(x).all():
+        raise ValueError(f"{name} hold NaN or inf")
+    return x, n_rows // (n_seq or 1)
+
+
 def quantiles(samples: np.ndarray, n_mod: int | None = None, device: int = 0) -> np.ndarray:
     """[n_par][3] = (il-th, im-th, iu-th smallest) of every column of samples [n_rows][n_par], on the GPU."""
-    x = np.ascontiguousarray(samples, dtype=np.float64)
-    if x.ndim == 1:
-        x = x[:, None]
-    n_rows, n_par = x.shape
+    x, n_rows = sample_matrix(samples, "htm_quantiles selects over", n_seq=None, finite=False)
     il, im, iu = ranks(n_rows if n_mod is None else n_mod)
-    for what, v in (("rows", n_rows), ("n_mod", n_mod or 0), ("rank", max(il, im, iu))):
+    for what, v in (("n_mod", n_mod or 0), ("rank", max(il, im, iu))):
         if v > INT_MAX:        # ctypes.c_int would wrap silently; htm_quantiles counts rows in int
             raise ValueError(f"{what} = {v} exceeds {INT_MAX}: htm_quantiles selects over at most {INT_MAX} rows")
     rk = (C.c_int * 3)(il, im, iu)
-    out = np.empty((n_par, 3))
-    lib = _lib.load()
-    _lib.check(lib.htm_quantiles(device, x.ctypes.data_as(_lib.dp), n_rows, n_par, rk, out.ctypes.data_as(_lib.dp)))
+    out = np.empty((x.shape[1], 3))
+    _lib.check(_lib.load().htm_quantiles(device, _lib.ptr(x), n_rows, x.shape[1], rk, _lib.ptr(out)))
     return out          # columns: il (2.5 %), im (50 %), iu (97.5 %)
 
 

@@ -57,6 +57,31 @@ def test_no_cpu_fallback_without_device():
     assert lib.htm_selftest(0) == -2 and "no HIP device" in last()
 
 
+@pytest.mark.gpu
+def test_device_ordinal_past_the_last_is_einval():
+    """one entry point of each family of the steps' unit, smallest valid shapes, device = htm_device_count(): HTM_EINVAL with
+    "out of range" from the shared device selection, before anything is allocated or launched"""
+    from hypotremormcmc_amd import _lib
+
+    lib = _lib.load()
+    n = C.c_int(-1)
+    assert lib.htm_device_count(C.byref(n)) == 0 and n.value >= 1
+    bad = n.value
+    x, out = np.arange(16.0), np.zeros(32)
+    px, po = _lib.ptr(x), _lib.ptr(out)
+    calls = {
+        "htm_quantiles": lambda: lib.htm_quantiles(bad, px, 4, 1, (C.c_int * 3)(1, 2, 4), po),
+        "htm_diagnose": lambda: lib.htm_diagnose(bad, px, 1, 4, 1, 1, po, None),
+        "htm_rank_normalize": lambda: lib.htm_rank_normalize(bad, px, 4, 1, 0, po, None),
+        "htm_hypo_ellipsoid": lambda: lib.htm_hypo_ellipsoid(bad, px, None, 4, 1, 0, 3, po, None),
+        "htm_xcorr": lambda: lib.htm_xcorr(bad, px, 2, 2, 2, 1, 1, 0, 1, po, po),
+        "htm_fft": lambda: lib.htm_fft(bad, px, 2, po, 2, 2, 1, -1),
+    }
+    for name, call in calls.items():
+        assert call() == -1, name                   # HTM_EINVAL
+        assert "out of range" in lib.htm_last_error().decode(), name
+
+
 def test_product_package_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "hypotremormcmc_amd")
     for dp_, _, files in os.walk(pkg):

@@ -91,6 +91,35 @@ def test_device_select_equals_sorted_column(slabs, monkeypatch):
 
 
 @pytest.mark.gpu
+def test_device_select_on_a_stream_with_forced_slabs(monkeypatch):
+    """htm_quantiles_dev on a stream other than the null stream, its workspace allocated and released on that stream, the
+    slab path forced: 257 rows x 65 columns (two column groups, the second nearly empty; slabs of 86, 86 and 85 rows) at row
+    stride 68.  Equal to the sorted columns and to the host form, bit for bit."""
+    import ctypes as C
+
+    import torch
+
+    from hypotremormcmc_amd import _lib, statistics as st
+
+    monkeypatch.setenv("HTM_SELECT_SLABS", "3")
+    n_mod, n_par, ld = 257, 65, 68
+    x = np.random.default_rng(5).normal(size=(n_mod, n_par))
+    x[:, 0] = np.round(x[:, 0])                     # many duplicates
+    ranks = st.ranks(n_mod)
+    d_x = torch.full((n_mod, ld), float("nan"), dtype=torch.float64, device="cuda")
+    d_x[:, :n_par] = torch.from_numpy(x).cuda()
+    d_out = torch.full((n_par, 3), -7.0, dtype=torch.float64, device="cuda")
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    _lib.check(_lib.load().htm_quantiles_dev(0, C.c_void_p(d_x.data_ptr()), n_mod, n_par, ld, (C.c_int * 3)(*ranks),
+                                             C.c_void_p(d_out.data_ptr()), C.c_void_p(stream.cuda_stream)))
+    stream.synchronize()
+    got = d_out.cpu().numpy()
+    assert np.array_equal(got, np.sort(x, axis=0)[[r - 1 for r in ranks]].T)
+    assert np.array_equal(got, st.quantiles(x))
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("name", ["c1", "fixedcorr"])
 def test_gpu_step5_plus_step6_writes_the_reference_stat_files(name, tmp_path):
     """step 5 on the GPU (all ranks of the job on one device), then step 6 on the GPU: the four .stat files
