@@ -17,6 +17,7 @@ HTM_MAX_CHAINS = 64
 dp = C.POINTER(C.c_double)
 ip = C.POINTER(C.c_int32)
 up = C.POINTER(C.c_uint32)
+u64p = C.POINTER(C.c_uint64)
 vp = C.c_void_p
 
 
@@ -105,6 +106,8 @@ SIGNATURES = {
     "htm_diagnose_rank_dev": (C.c_int, [C.c_int, vp, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, vp, vp]),
     "htm_hypo_ellipsoid": (C.c_int, [C.c_int, dp, dp, C.c_long, C.c_long, C.c_int, C.c_long, dp, dp]),
     "htm_hypo_ellipsoid_dev": (C.c_int, [C.c_int, vp, C.c_long, vp, C.c_long, C.c_long, C.c_long, C.c_int, C.c_long, vp, vp, vp]),
+    "htm_hypo_density": (C.c_int, [C.c_int, dp, C.c_long, C.c_long, ip, C.c_int, dp, u64p, u64p, u64p, u64p, u64p]),
+    "htm_hypo_density_dev": (C.c_int, [C.c_int, vp, C.c_long, C.c_long, C.c_long, vp, C.c_int, dp, vp, vp, vp, vp, vp, vp]),
     "htm_chains_swap_record_host": (C.c_int, [vp, dp]),
     "htm_chains_step_end_host": (C.c_int, [vp, dp]),
     "htm_comm_unique_id": (C.c_int, [vp, C.c_size_t]),

@@ -1,6 +1,6 @@
 // htm_steps.hip -- the C ABI (include/htm_hip.h) of the pipeline's other steps: step 1 (htm_fft*, htm_convert*), steps 2 and 3
 // (htm_xcorr*, htm_measure_windows), step 4 (htm_select_regress), the convergence diagnostics (htm_diagnose*, htm_rank_normalize*), step 6
-// (htm_quantiles*), the error ellipsoids (htm_hypo_ellipsoid*).  None touches a forward or a chain set; host idioms: htm_steps_host.hpp.
+// (htm_quantiles*), the error ellipsoids (htm_hypo_ellipsoid*), the density maps (htm_hypo_density*).  None touches a forward or a chain set; host idioms: htm_steps_host.hpp.
 #include "htm_steps_host.hpp"
 
 #include <dlfcn.h>
@@ -16,6 +16,7 @@
 #include <thread>
 
 #include "htm_convert.hpp"
+#include "htm_density.hpp"
 #include "htm_diag.hpp"
 #include "htm_ellipsoid.hpp"
 #include "htm_rank.hpp"
@@ -449,6 +450,145 @@ int htm_hypo_ellipsoid(int device, const double *hypo, const double *pivots, lon
     if (hipStreamSynchronize(nullptr) != hipSuccess) return fail(HTM_EHIP, "the ellipsoid kernels failed");
     if ((rc = pool.download(out, d_o, on, "the ellipsoids'")) || (n_piv > 0 && (rc = pool.download(piv_corr, d_c, cn, "the pivot correlations'"))))
         return rc;
+    return HTM_OK;
+}
+
+// ---- stacked density maps (htm_density.hpp) ------------------------------------------------------------
+namespace {
+struct DensPlan {
+    DensGrid g;
+    long slabs, slab_rows, nxy, nxz, nyz, nvol;      // nvol = 0 without the volume
+    int path;                                         // 0 plain, 1 LDS, 2 naive
+};
+
+// what both forms refuse before any device call, and the launch plan: the grid, the counting path, the row slabs
+int dens_plan(const double *hypo, long ld, long n_mod, long n_win, const int *layer, int n_layer, const double *grid9,
+              const unsigned long long *xy, const unsigned long long *xz, const unsigned long long *yz, const unsigned long long *vol,
+              const unsigned long long *tally, DensPlan *p)
+{
+    if (!hypo || !grid9 || !xy || !xz || !yz || !tally) return fail(HTM_EINVAL, "NULL argument");
+    if (n_mod < 1 || n_win < 1 || n_layer < 1)
+        return fail(HTM_EINVAL, "bad shape (n_mod %ld, n_win %ld, n_layer %d): need n_mod >= 1, n_win >= 1, n_layer >= 1", n_mod, n_win, n_layer);
+    if (!layer && n_layer != 1) return fail(HTM_EINVAL, "n_layer %d without a layer per window: NULL puts every window in layer 0 of 1", n_layer);
+    if (n_win > INT_MAX / 3) return fail(HTM_EINVAL, "n_win %ld needs more than 2^32 - 1 work-items in one launch", n_win);
+    if (ld < 3 * n_win) return fail(HTM_EINVAL, "bad row stride (ld %ld < 3 n_win = %ld)", ld, 3 * n_win);
+    int n[3];
+    for (int a = 0; a < 3; ++a) {
+        const double v0 = grid9[3 * a], dv = grid9[3 * a + 1], cnt = grid9[3 * a + 2];
+        if (!std::isfinite(v0) || !std::isfinite(dv) || !(dv > 0.0))
+            return fail(HTM_EINVAL, "grid axis %c: origin %g, cell size %g: need a finite origin and a finite cell size > 0", "xyz"[a], v0, dv);
+        if (!(cnt >= 1.0 && cnt <= (double)kDensMaxCells) || cnt != std::floor(cnt))
+            return fail(HTM_EINVAL, "grid axis %c: %g cells: need an integer in 1..%d", "xyz"[a], cnt, kDensMaxCells);
+        n[a] = (int)cnt;
+    }
+    p->g = DensGrid{grid9[0], grid9[1], grid9[3], grid9[4], grid9[6], grid9[7], n[0], n[1], n[2]};
+    p->nxy = (long)n[1] * n[0];
+    p->nxz = (long)n[2] * n[0];
+    p->nyz = (long)n[2] * n[1];
+    p->nvol = vol ? p->nxy * n[2] : 0;
+    const long cells = p->nxy + p->nxz + p->nyz + p->nvol;
+    if (cells > INT_MAX / n_layer)
+        return fail(HTM_EINVAL, "%d layers of %ld cells: more than 2^31 - 1 counters", n_layer, cells);
+    // the counting path: the LDS maps where a layer's three 2-D maps fit; HTM_DENSITY_LDS=0|1 forbids or forces them,
+    // HTM_DENSITY_NAIVE=1 is the yardstick of tools/bench_density.py
+    const bool fits = p->nxy + p->nxz + p->nyz <= kDensLdsCells;
+    p->path = fits ? 1 : 0;
+    if (const char *e = getenv("HTM_DENSITY_LDS")) {
+        if (strcmp(e, "0") && strcmp(e, "1")) return fail(HTM_EINVAL, "HTM_DENSITY_LDS = %s: 0 or 1", e);
+        p->path = e[0] == '1';
+        if (p->path && !fits)
+            return fail(HTM_EINVAL, "HTM_DENSITY_LDS = 1, but the grid's 2-D maps hold %ld cells: the LDS path takes %d", p->nxy + p->nxz + p->nyz,
+                        kDensLdsCells);
+    }
+    if (const char *e = getenv("HTM_DENSITY_NAIVE"))
+        if (!strcmp(e, "1")) p->path = 2;
+    // row slabs: the plain kernel's as ell_plan's (4096 waves); the LDS kernel's workgroups each add their counters to the global
+    // maps, so it takes as few as keep every CU busy (512 workgroups).  HTM_DENSITY_SLABS forces the count.  A slab is at most
+    // kDensMaxSlabRows rows, whatever is forced.
+    const long n_grp = (n_win + 63) / 64, n_wg = p->path == 1 ? n_grp : (n_grp + kDensWG - 1) / kDensWG;
+    long slabs = std::max(1L, std::min(((p->path == 1 ? 512 : 4096) + n_grp - 1) / n_grp, (n_mod + 255) / 256));
+    if (const char *e = getenv("HTM_DENSITY_SLABS")) slabs = std::max(1L, std::min(atol(e), n_mod));
+    slabs = std::max(slabs, (n_mod + kDensMaxSlabRows - 1) / kDensMaxSlabRows);
+    if (slabs > 65535L) {
+        if ((n_mod + 65534L) / 65535L > kDensMaxSlabRows) return fail(HTM_EINVAL, "n_mod %ld needs more than 2^32 - 1 work-items in one launch", n_mod);
+        slabs = 65535L;
+    }
+    p->slab_rows = (n_mod + slabs - 1) / slabs;
+    p->slabs = (n_mod + p->slab_rows - 1) / p->slab_rows;          // no empty slab
+    if (n_wg * p->slabs * 64 * kDensWG > kMaxWorkItems)
+        return fail(HTM_EINVAL, "n_win %ld in %ld row slabs needs more than 2^32 - 1 work-items in one launch", n_win, p->slabs);
+    return HTM_OK;
+}
+
+}  // namespace
+
+int htm_hypo_density_dev(int device, const double *d_hypo, long ld, long n_mod, long n_win, const int *d_layer, int n_layer,
+                         const double *grid9, unsigned long long *d_xy, unsigned long long *d_xz, unsigned long long *d_yz,
+                         unsigned long long *d_vol, unsigned long long *d_tally, void *hip_stream)
+{
+    DensPlan pl;
+    int rc = dens_plan(d_hypo, ld, n_mod, n_win, d_layer, n_layer, grid9, d_xy, d_xz, d_yz, d_vol, d_tally, &pl);
+    if (rc) return rc;
+    if ((rc = use_device(device))) return rc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const size_t u = sizeof(unsigned long long);
+    HIPCHK(hipMemsetAsync(d_xy, 0, (size_t)n_layer * pl.nxy * u, st));
+    HIPCHK(hipMemsetAsync(d_xz, 0, (size_t)n_layer * pl.nxz * u, st));
+    HIPCHK(hipMemsetAsync(d_yz, 0, (size_t)n_layer * pl.nyz * u, st));
+    if (d_vol) HIPCHK(hipMemsetAsync(d_vol, 0, (size_t)n_layer * pl.nvol * u, st));
+    HIPCHK(hipMemsetAsync(d_tally, 0, (size_t)n_layer * 2 * u, st));
+    const long n_grp = (n_win + 63) / 64;
+    const dim3 grid((unsigned)((n_grp + kDensWG - 1) / kDensWG), (unsigned)pl.slabs), grid_lds((unsigned)n_grp, (unsigned)pl.slabs), block(64 * kDensWG);
+    const DensOut o{d_xy, d_xz, d_yz, d_vol, d_tally};
+    if (pl.path == 1)
+        hipLaunchKernelGGL(k_dens_lds, grid_lds, block, 0, st, d_hypo, ld, n_mod, n_win, pl.slab_rows, d_layer, n_layer, pl.g, o);
+    else if (pl.path == 2)
+        hipLaunchKernelGGL(k_dens_plain<true>, grid, block, 0, st, d_hypo, ld, n_mod, n_win, pl.slab_rows, d_layer, n_layer, pl.g, o);
+    else
+        hipLaunchKernelGGL(k_dens_plain<false>, grid, block, 0, st, d_hypo, ld, n_mod, n_win, pl.slab_rows, d_layer, n_layer, pl.g, o);
+    if (hipGetLastError() != hipSuccess) return fail(HTM_EHIP, "the density kernel's launch failed");
+    return HTM_OK;
+}
+
+int htm_hypo_density(int device, const double *hypo, long n_mod, long n_win, const int *layer, int n_layer, const double *grid9,
+                     unsigned long long *xy, unsigned long long *xz, unsigned long long *yz, unsigned long long *vol,
+                     unsigned long long *tally)
+{
+    DensPlan pl;
+    int rc = dens_plan(hypo, 3 * n_win, n_mod, n_win, layer, n_layer, grid9, xy, xz, yz, vol, tally, &pl);
+    if (rc) return rc;
+    double mb;
+    if ((rc = env_mib("HTM_DENSITY_MB", 1024.0, &mb))) return rc;
+    if ((rc = use_device(device))) return rc;
+    // the rows go to the device in batches under HTM_DENSITY_MB MiB (one row at the least); the batches' counts are added here
+    const double cap = mb * 1048576.0 / (sizeof(double) * 3.0 * (double)n_win);
+    const long rows = cap >= (double)n_mod ? n_mod : std::max(1L, (long)cap);
+    const size_t on[5] = {(size_t)n_layer * pl.nxy, (size_t)n_layer * pl.nxz, (size_t)n_layer * pl.nyz, (size_t)n_layer * pl.nvol, (size_t)n_layer * 2};
+    unsigned long long *host[5] = {xy, xz, yz, vol, tally}, *dev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    DevPool pool;
+    double *d_x = nullptr;
+    int *d_l = nullptr;
+    if ((rc = pool.alloc(&d_x, (size_t)rows * 3 * n_win)) || (layer && (rc = pool.upload(&d_l, layer, (size_t)n_win)))) return rc;
+    for (int k = 0; k < 5; ++k)
+        if (host[k] && (rc = pool.alloc(&dev[k], on[k]))) return rc;
+    std::vector<unsigned long long> part;
+    for (long r0 = 0; r0 < n_mod; r0 += rows) {
+        const long nr = std::min(rows, n_mod - r0);
+        HIPCHK(hipMemcpy(d_x, hypo + (size_t)r0 * 3 * n_win, (size_t)nr * 3 * n_win * sizeof(double), hipMemcpyHostToDevice));
+        if ((rc = htm_hypo_density_dev(device, d_x, 3 * n_win, nr, n_win, d_l, n_layer, grid9, dev[0], dev[1], dev[2], dev[3], dev[4], nullptr)))
+            return rc;
+        if (hipStreamSynchronize(nullptr) != hipSuccess) return fail(HTM_EHIP, "the density kernel failed");
+        for (int k = 0; k < 5; ++k) {
+            if (!host[k]) continue;
+            if (r0 == 0) {
+                if ((rc = pool.download(host[k], dev[k], on[k], "the density maps'"))) return rc;
+                continue;
+            }
+            part.resize(on[k]);
+            if ((rc = pool.download(part.data(), dev[k], on[k], "the density maps'"))) return rc;
+            for (size_t i = 0; i < on[k]; ++i) host[k][i] += part[i];
+        }
+    }
     return HTM_OK;
 }
 

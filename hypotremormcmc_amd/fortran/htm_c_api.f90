@@ -18,6 +18,7 @@ module htm_c_api
   public :: htm_device_count, htm_device_physical_id, htm_quantiles, htm_diagnose, htm_select_regress
   public :: htm_rank_normalize, htm_rank_normalize_dev, htm_diagnose_rank, htm_diagnose_rank_dev
   public :: htm_hypo_ellipsoid, htm_hypo_ellipsoid_dev
+  public :: htm_hypo_density, htm_hypo_density_dev
   public :: htm_chains_checkpoint_size, htm_chains_checkpoint_save, htm_chains_checkpoint_load
 
   integer(c_size_t), parameter :: HTM_XCHG_HANDLE_BYTES = 64_c_size_t, HTM_COMM_ID_BYTES = 128_c_size_t
@@ -323,6 +324,36 @@ module htm_c_api
        type(c_ptr), value :: d_out, d_piv_corr, hip_stream
        integer(c_int) :: rc
      end function htm_hypo_ellipsoid_dev
+     !> stacked density maps (include/htm_hip.h): hypo [n_mod][3 n_win] row-major, layer (n_win) or c_null_ptr, grid9 =
+     !> x0, dx, nx, y0, dy, ny, z0, dz, nz; counts xy (nx, ny, n_layer), xz (nx, nz, n_layer), yz (ny, nz, n_layer),
+     !> vol (nx, ny, nz, n_layer) or c_null_ptr, tally (2, n_layer) = inside, outside
+     function htm_hypo_density(device, hypo, n_mod, n_win, layer, n_layer, grid9, xy, xz, yz, vol, tally) &
+          & bind(C, name="htm_hypo_density") result(rc)
+       import :: c_int, c_long, c_long_long, c_double, c_ptr
+       integer(c_int), value :: device
+       real(c_double), intent(in) :: hypo(*)
+       integer(c_long), value :: n_mod, n_win
+       type(c_ptr), value :: layer
+       integer(c_int), value :: n_layer
+       real(c_double), intent(in) :: grid9(9)
+       integer(c_long_long), intent(out) :: xy(*), xz(*), yz(*)
+       type(c_ptr), value :: vol
+       integer(c_long_long), intent(out) :: tally(*)
+       integer(c_int) :: rc
+     end function htm_hypo_density
+     !> the same on device pointers with the row stride ld (grid9 stays in host memory), asynchronous on hip_stream
+     function htm_hypo_density_dev(device, d_hypo, ld, n_mod, n_win, d_layer, n_layer, grid9, d_xy, d_xz, d_yz, d_vol, d_tally, &
+          & hip_stream) bind(C, name="htm_hypo_density_dev") result(rc)
+       import :: c_int, c_long, c_double, c_ptr
+       integer(c_int), value :: device
+       type(c_ptr), value :: d_hypo
+       integer(c_long), value :: ld, n_mod, n_win
+       type(c_ptr), value :: d_layer
+       integer(c_int), value :: n_layer
+       real(c_double), intent(in) :: grid9(9)
+       type(c_ptr), value :: d_xy, d_xz, d_yz, d_vol, d_tally, hip_stream
+       integer(c_int) :: rc
+     end function htm_hypo_density_dev
      !> step-4 regressions (include/htm_hip.h): t, t_err, a, a_err (n_sta, n_win); out (6, n_win) = vs, b, t0, a0, cc_t, cc_a
      function htm_select_regress(device, n_sta, n_win, sta_x, sta_y, sta_z, z_guess, t, t_err, a, a_err, out) &
           & bind(C, name="htm_select_regress") result(rc)

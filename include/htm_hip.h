@@ -411,6 +411,30 @@ int htm_hypo_ellipsoid_dev(int device, const double *d_hypo, long ld, const doub
                            double *d_out, double *d_piv_corr, void *hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Stacked density maps of recorded samples.  hypo as for the ellipsoids; layer [n_win] gives every window
+ * its layer (a time bin, say), NULL puts every window in layer 0 of n_layer = 1; a window whose layer lies outside
+ * 0 .. n_layer - 1 takes no part and is in nobody's tally.  grid9 = {x0, dx, nx, y0, dy, ny, z0, dz, nz} (host memory in both
+ * forms; the counts as doubles with integral values).  On an axis {v0, dv, n} a coordinate v has q = (v - v0) / dv (a true
+ * fp64 division); it is inside iff 0 <= q < n (cells are half-open, the box's top edge is outside, as are NaN and +-inf) and
+ * then lies in cell floor(q).  A sample counts iff its three coordinates are inside, and then once in each output:
+ * xy [n_layer][ny][nx], xz [n_layer][nz][nx], yz [n_layer][nz][ny], vol [n_layer][nz][ny][nx] (or NULL), and
+ * tally [n_layer][2] = {inside, outside}.  So every map of a layer sums to the layer's inside, and inside + outside is n_mod
+ * times the layer's windows.  The call zeroes the outputs before it counts; the counts are exact and the same for every
+ * order of the adds, row-slab count (HTM_DENSITY_SLABS) and counting path (HTM_DENSITY_LDS = 0 | 1 forbids or forces the
+ * LDS-resident maps, which take a grid with nx ny + nx nz + ny nz <= 8192; forced on a larger grid: HTM_EINVAL).
+ * n_mod, n_win, n_layer >= 1; ld >= 3 n_win; finite origins, finite cell sizes > 0; 1..4096 cells per axis; at most
+ * 2^31 - 1 counters over all layers and requested outputs; else HTM_EINVAL before any device call, as for a shape that needs a
+ * launch beyond 2^32 - 1 work-items.  Host pointers: synchronous, the rows in batches under HTM_DENSITY_MB MiB (environment,
+ * default 1024) whose counts are added on the host; _dev: device pointers (ld = row stride in doubles; columns beyond
+ * 3 n_win are never read), asynchronous on `hip_stream`. */
+int htm_hypo_density(int device, const double *hypo, long n_mod, long n_win, const int *layer, int n_layer,
+                     const double *grid9, unsigned long long *xy, unsigned long long *xz, unsigned long long *yz,
+                     unsigned long long *vol, unsigned long long *tally);
+int htm_hypo_density_dev(int device, const double *d_hypo, long ld, long n_mod, long n_win, const int *d_layer, int n_layer,
+                         const double *grid9, unsigned long long *d_xy, unsigned long long *d_xz, unsigned long long *d_yz,
+                         unsigned long long *d_vol, unsigned long long *d_tally, void *hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Step 4, `hypo_tremor_select`   reference: src/cls_selector.f90:75-132, src/mod_regress.f90
  * For every detected window: the station of largest amplitude is taken as the epicentre (depth z_guess), the
  * amplitudes are corrected for geometrical spreading (+ ln d), and arrival time and amplitude are regressed
