@@ -222,6 +222,21 @@ struct FlowSta {
     int m_el, m_hyp, m_sc, d_hyp, m_qs;
 };
 
+// The lane's t_corr and a_corr of the wave's chain, carried by the specialised master's chain wave with one station per lane (one
+// chain per wave: htm_plan.hpp flow_fixed, up to eight chains on the eight waves of htm_loop_rows.hpp's 512 threads) in registers
+// from step to step: only this wave's own accepted t_corr / a_corr step changes the chain's two correction rows, so the two
+// loads every step issued for them, and their addresses, go.  Seeded from xall where the launch seeds LDS; renewed at the
+// wave's own commit.  A step that is run again and an adopted epoch commit nothing: the copies stand across them.  xall and
+// the mirror are written as before (the workers, the records and the launch's end read them).
+// (Measured and not kept -- the chain's wave-uniform own state carried the same way: L, the two reciprocals, the temperature,
+// the previous step's type word, the order book.  The compiler keeps them in scalar registers, which the loop does not have: 2 %
+// slower; pinned to vector registers they count as lane-dependent and every branch behind them runs under a lane mask: 6 %
+// slower.  docs/experiments/own_state_switches.patch, profiles/own_state_ab.txt.)
+struct FlowOwn {
+    double tc, ac;
+};
+template <class TR, int NCH> constexpr bool flow_own_row_v = flow_fixed_v<TR> && NCH == 1;
+
 constexpr int kFlowRestart = -1;  // flow_step: the step's position was disproved before its turn came: run it again
 constexpr int kFlowAbort = -2;    // flow_step: a wait gave up (sh.c.err is set)
 constexpr int kFlowStop = -3;     // flow_step (lock-step rank): the job stops after the iteration before: this step is not taken
@@ -539,7 +554,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
                                          MbShared *g_mb, MbWave &mw, double *s_gath, int wmax,
                                          const double *s_sx, const double *s_sy, const double *s_sz, int c, int p, int iter,
                                          int lane, int wave, int NW, unsigned long long launch, bool ext, int look, int back,
-                                         bool rec_now, const FlowTop &tp, const FlowSta &fs)
+                                         bool rec_now, const FlowTop &tp, const FlowSta &fs, FlowOwn &own)
 {
     CsRef cs = rebase(cs_);
     FwRef f = rebase(f_);
@@ -569,6 +584,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
     const PriorRec *prior_ = cs.prior;
     static_assert(!TR::full_rows || NCH > 0, "full rows: one or two stations per lane");
     constexpr bool FX = flow_fixed_v<TR>;
+    constexpr bool OWN_ROW = flow_own_row_v<TR, NCH>;      // the lane's two corrections in registers (FlowOwn)
     constexpr int LS = NCH == 2 ? 7 : 6;        // (full rows: log2 of the row length)
     int nc_ = cs.n_chains, nh = 3 * cs.E, psame_ = cs.prior_same;
     const int S_ = TR::full_rows ? 64 * NCH : cs.S;
@@ -632,7 +648,8 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
                 const int j = lane + 64 * k;
                 if constexpr (NCH == 1) { st.sx[k] = fs.x; st.sy[k] = fs.y; st.sz[k] = fs.z; }
                 else { st.sx[k] = s_sx[j]; st.sy[k] = s_sy[j]; st.sz[k] = s_sz[j]; }
-                st.tc[k] = ld_global(tc + j); st.ac[k] = ld_global(ac + j);
+                if constexpr (OWN_ROW) { st.tc[k] = own.tc; st.ac[k] = own.ac; }
+                else { st.tc[k] = ld_global(tc + j); st.ac[k] = ld_global(ac + j); }
             }
         }
         else load_sta_regs<(NCH > 0 ? NCH : 1), TR::full_rows>(st, f.S, lane, s_sx, s_sy, s_sz, tc, ac, 0, -1, 0.0);
@@ -669,6 +686,8 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
     FSTAMP(0);
     const double x_old = rl_f64(gathered_v, 0);
     const double hx = rl_f64(gathered_v, 1), hy = rl_f64(gathered_v, 2), hz = rl_f64(gathered_v, 3);
+    // (vs and qs: a partial update multiplies by the chain's two reciprocals and needs neither, but reading them only behind the
+    // full-evaluation and accepted-vs/qs branches was measured inside the spread: docs/experiments/own_state_switches.patch)
     const double beta = rl_f64(gathered_v, 4), q = rl_f64(gathered_v, 5);
     const double L_cur = tp.L;
     const double x_new = x_old + g * step;                      // cls_model.f90:172
@@ -1152,6 +1171,14 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
         sh.L4[par][c] = L_post;
         lds_st(&sh.done[c], key);
     }
+    if constexpr (OWN_ROW) {      // an accepted correction: the wave's own copy, on the lane of its station
+        if (acc) {
+            // (selects, not two stores under conditions: those become one store through a selected address, and the pair lives in scratch)
+            const double tc_ = own.tc, ac_ = own.ac;
+            own.tc = (type == 2 && lane == idx) ? x_new : tc_;
+            own.ac = (type == 4 && lane == idx) ? x_new : ac_;
+        }
+    }
     if constexpr (LOCK) {
         // this chain's (T, L) after the iteration (the rank's header went out before the decision, from the wave of its last chain)
         unsigned long long *const *xout = reinterpret_cast<unsigned long long *const *>(s_gath);
@@ -1259,7 +1286,19 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
         else if (cs.n_procs * nc_ <= 1 || (rg.lock && cs.rank != 0)) nx.b3 = la_E2;
         else nx.b3 = swz > 0 ? la_E2 + swz + ((!rg.lock || uni(swv.x) / nc_ == 0) ? 1 : 0) : -1;
     }
-    if ((TR::mirror || rg.mir_n > 0) && sh.ob_pos[c] == -1 && iter + 1 <= sh.c.iter_target) {
+    // (the specialised master: whether an order can go out at all follows from the two decoded types of the look-ahead, which are
+    // in registers -- nine steps in ten it cannot, and neither the book nor the launch's target is looked at)
+    bool order_open;
+    if constexpr (FX) {
+        bool may_order = true;
+        if (la_ok) {
+            const int d2x = uni(d2v.x);
+            may_order = (d1.x >= 1 && d1.x <= 4) || (HTM_ALLOW2 && NCH > 0 && d2x >= 1 && d2x <= 4);
+        }
+        order_open = may_order && sh.ob_pos[c] == -1 && iter + 1 <= sh.c.iter_target;
+    }
+    else order_open = (TR::mirror || rg.mir_n > 0) && sh.ob_pos[c] == -1 && iter + 1 <= sh.c.iter_target;
+    if (order_open) {
         const int lim = sh.fill - 8;
         int p1 = -1, mode = 0, pj = -1, jt = 0, ji = 0;
         bool w1 = false, job1 = false;
@@ -1456,6 +1495,15 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
     int iter = i0 + 1;
     int c = MB ? 8 * mb_b + wave : wave;
     bool alive = MB ? (wave < 8 && c < nc) : (wave < nc && wave < NW);
+    // (one chain per wave, NW >= n_chains: the wave's chain never changes.  htm_plan.hpp flow_fixed admits up to eight chains, the
+    // kernel table launches 512 threads, and launch_mcmc refuses a specialised launch with more chains than chain waves)
+    FlowOwn own = {0.0, 0.0};
+    if constexpr (flow_own_row_v<TR, NCH>) {
+        if (alive) {
+            const int S = 64 * NCH;      // [vs | t_corr | qs | a_corr | hypo]
+            own.tc = ld_global(cs.xall + nc + c * S + lane); own.ac = ld_global(cs.xall + 2 * nc + nc * S + c * S + lane);
+        }
+    }
     MbWave mw;
 #ifdef HTM_MB_DIAG
     mw.hist = 0u;
@@ -1567,8 +1615,8 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
         // (several master workgroups: a wave has one chain -- "wave" c of as many waves as there are chains)
         if constexpr (MB) MB_HIST(mw, (known ? 4 : 0) | (W.epoch & 3));
         const int r = flow_step<NCH, F32, LOCK, MB, TR>(f, cs, sh, rg, W, nx, g_mb, mw, s_gath, wmax, s_sx, s_sy, s_sz, c, p, iter, lane, MB ? c : wave,
-                                              MB ? 64 : NW, launch, wave == 0, look, back, rec_phase == 1, tp, fs);
-        if (r == kFlowRestart) continue;
+                                              MB ? 64 : NW, launch, wave == 0, look, back, rec_phase == 1, tp, fs, own);
+        if (r == kFlowRestart) continue;      // (nothing was committed: the wave's copies of its chain's corrections stand)
         if (r == kFlowAbort || r == kFlowStop) break;
         // ---- this wave's next step
 #ifdef HTM_MB_DIAG

@@ -58,10 +58,13 @@ int launch_mcmc(htm_chains *hc, int mode, int target, const double *gathered)
     l.mode = mode; l.target = target; l.gathered = gathered; l.ring_size = lp.ring_size; l.wmax = lp.wmax;
     l.seq = ++hc->launch_seq;      // this chain set's k_mcmc launches, counted from 1
     if (mk == 8 && !h->dev.obs_pack) return fail(HTM_EINVAL, "the specialised chain master needs the forward's packed records");
-    if (mode == MODE_RUN) hc->last_fixed = mk == 8;
-    if (mk == 5 || mk == 6) { l.smem = lp.pipe_smem; l.ring_size = lp.pipe_ring; }      // (its own LDS layout and stream window)
     const LoopKernel *k = mcmc_kernel(h->nch, h->dev.fp32 != 0, mk, lp.wide);
     if (!k) return no_kernel(hc, "k_mcmc", mk);
+    // (the specialised master's chain wave keeps its chain's correction pair in registers, htm_flow.hpp FlowOwn: a wave per chain)
+    if (mk == 8 && hc->dev.n_chains > std::min(k->threads / 64, 8))
+        return fail(HTM_EINVAL, "the specialised chain master runs one chain per wave: %d chains, %d threads", hc->dev.n_chains, k->threads);
+    if (mode == MODE_RUN) hc->last_fixed = mk == 8;
+    if (mk == 5 || mk == 6) { l.smem = lp.pipe_smem; l.ring_size = lp.pipe_ring; }      // (its own LDS layout and stream window)
     // several master workgroups: what their chains share lives in memory (MbShared), set up by a one-wave kernel first
     if (mk == 7) hipLaunchKernelGGL(k_mb_init, dim3(1), dim3(64), 0, h->stream, hc->dev, target);
     l.block = dim3(k->threads);
