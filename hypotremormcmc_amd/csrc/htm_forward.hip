@@ -1,7 +1,9 @@
 // htm_forward.hip -- the C ABI (include/htm_hip.h) of the forward model over the kernels in htm_kernels.hpp: htm_forward_*,
-// htm_device_*, the library's one last-error string, htm_rng_jump and the self-tests.  What the units share: htm_host.hpp.
-#include "htm_host.hpp"
+// htm_device_*, the library's one last-error string, htm_rng_jump and the self-tests; htm_forward_locate over the kernels in
+// htm_locate.hpp.  What the units share: htm_host.hpp.
+#include "htm_steps_host.hpp"
 #include "htm_forward_kernels.hpp"
+#include "htm_locate.hpp"
 
 #include <cmath>
 #include <cstdarg>
@@ -232,11 +234,11 @@ int htm_forward_create(int n_sta, int n_events, const double *sta_x, const doubl
 
     // init_forward, cls_forward.f90:76-92: precision, log-stdv and the missing-data rule (keyed on t_stdv
     // only; log-stdv := 1.0 (sic), stdv := 1, precision := 1 for BOTH data types)
-    std::vector<double> tpr(n), apr(n), pst(n_events), psa(n_events);
+    std::vector<double> tpr(n), apr(n), pst(n_events), psa(n_events), lct(n_events), lca(n_events);
     const double log_2pi_half = 0.5 * std::log(2.0 * std::acos(-1.0));
     double const_t = 0.0, const_a = 0.0;
     for (int i = 0; i < n_events; ++i) {
-        double st = 0.0, sa = 0.0;
+        double st = 0.0, sa = 0.0, ct = 0.0, ca = 0.0;
         for (int j = 0; j < n_sta; ++j) {
             const size_t k = (size_t)i * n_sta + j;
             double lts, las;
@@ -249,8 +251,9 @@ int htm_forward_create(int n_sta, int n_events, const double *sta_x, const doubl
             st += tpr[k]; sa += apr[k];
             const_t += log_2pi_half + lts;
             const_a += log_2pi_half + las;
+            ct += log_2pi_half + lts; ca += log_2pi_half + las;
         }
-        pst[i] = st; psa[i] = sa;
+        pst[i] = st; psa[i] = sa; lct[i] = ct; lca[i] = ca;
     }
 
     double *p = nullptr;
@@ -266,6 +269,7 @@ int htm_forward_create(int n_sta, int n_events, const double *sta_x, const doubl
         for (int i = 0; i < n_events; ++i) { rt[i] = 1.0 / pst[i]; ra[i] = 1.0 / psa[i]; }
         UP(h->dev.rpsum_t, rt.data(), n_events) UP(h->dev.rpsum_a, ra.data(), n_events)
     }
+    UP(h->d_lconst_t, lct.data(), n_events) UP(h->d_lconst_a, lca.data(), n_events)
 #undef UP
     h->dev.S = n_sta; h->dev.E = n_events; h->dev.use_time = use_time ? 1 : 0; h->dev.use_amp = use_amp ? 1 : 0;
     h->dev.const_sum = (use_time ? const_t : 0.0) + (use_amp ? const_a : 0.0);
@@ -503,6 +507,110 @@ int htm_forward_time_full_batch_dev(htm_forward *h, int n_models, const double *
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
     *avg_us = 1000.0 * ms / reps;
+    return HTM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The location posterior of every event of the handle on a grid, under a fixed structure (include/htm_hip.h; kernels and
+// the partial records: htm_locate.hpp).  The prior is separable: its three tables per event are made here, on the host.
+int htm_forward_locate(htm_forward *h, const double *t_corr, double vs, const double *a_corr, double qs, const double *grid9,
+                       const double *prior5, double *loc, double *marg, double *vol)
+{
+    if (!h) return fail(HTM_EINVAL, "NULL handle");
+    if (!t_corr || !a_corr || !grid9 || !loc) return fail(HTM_EINVAL, "NULL argument");
+    if (!std::isfinite(vs) || !std::isfinite(qs) || !(vs > 0.0) || !(qs > 0.0))
+        return fail(HTM_EINVAL, "vs = %g, qs = %g: need finite values > 0", vs, qs);
+    int n[3];
+    for (int a = 0; a < 3; ++a) {
+        const double v0 = grid9[3 * a], dv = grid9[3 * a + 1], cnt = grid9[3 * a + 2];
+        if (!std::isfinite(v0) || !std::isfinite(dv) || !(dv > 0.0))
+            return fail(HTM_EINVAL, "grid axis %c: origin %g, cell size %g: need a finite origin and a finite cell size > 0", "xyz"[a], v0, dv);
+        if (!(cnt >= 1.0 && cnt <= (double)kLocMaxCells) || cnt != std::floor(cnt))
+            return fail(HTM_EINVAL, "grid axis %c: %g cells: need an integer in 1..%d", "xyz"[a], cnt, kLocMaxCells);
+        n[a] = (int)cnt;
+    }
+    const long cells = (long)n[0] * n[1] * n[2];
+    if (cells > (long)INT_MAX) return fail(HTM_EINVAL, "%d x %d x %d cells: more than 2^31 - 1", n[0], n[1], n[2]);
+    const int E = h->E, S = h->S;
+    if (prior5)
+        for (int i = 0; i < E; ++i)
+            if (!(prior5[5 * i + 2] > 0.0) || !(prior5[5 * i + 4] > 0.0))
+                return fail(HTM_EINVAL, "event %d: prior widths w_xy = %g, w_z = %g: need values > 0", i, prior5[5 * i + 2], prior5[5 * i + 4]);
+    double mb;
+    int rc = env_mib("HTM_LOCATE_MB", 1024.0, &mb);
+    if (rc) return rc;
+    // tiles: whole x-rows of one z-layer, at most kLocRows of them and kLocTile cells
+    LocGrid g{grid9[0], grid9[1], grid9[3], grid9[4], grid9[6], grid9[7], n[0], n[1], n[2], 0, 0, 0};
+    g.rows = std::max(1, std::min(std::min(n[1], kLocRows), kLocTile / n[0]));
+    g.tpl = (n[1] + g.rows - 1) / g.rows;
+    g.stride = kLocHead + n[0] + 2 * g.rows;
+    const long n_tiles = (long)n[2] * g.tpl;
+    // (a tile that is not a layer's last holds more than 2048 cells or 256 rows of at most 16: at most 2^31 / 256 + 4096 tiles, 2^31 work-items per event)
+    // events per batch: a launch's grid (y <= 65535, 2^32 - 1 work-items) and the workspace under HTM_LOCATE_MB MiB
+    const long nm = (long)n[0] + n[1] + n[2];
+    const double per_event = sizeof(double) * ((double)n_tiles * g.stride + (vol ? (double)cells : 0.0) + 2.0 * nm + 16.0) + sizeof(LocSta) * (double)S + sizeof(LocEv);
+    long nb = std::min<long>(E, 65535L);
+    nb = std::min(nb, kMaxWorkItems / (n_tiles * kLocThreads));
+    nb = std::min(nb, (kMaxWorkItems - 256) / S);
+    nb = std::min(nb, (long)std::min(mb * 1048576.0 / per_event, 65535.0));
+    nb = std::max(nb, 1L);
+
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    DevPool pool;
+    LocSta *d_sta = nullptr;
+    LocEv *d_ev = nullptr;
+    double *d_prior = nullptr, *d_part = nullptr, *d_vol = nullptr, *d_loc = nullptr, *d_marg = nullptr;
+    if ((rc = pool.alloc(&d_sta, (size_t)nb * S)) || (rc = pool.alloc(&d_ev, (size_t)nb)) || (rc = pool.alloc(&d_part, (size_t)nb * n_tiles * g.stride)) ||
+        (rc = pool.alloc(&d_loc, (size_t)nb * 16)) || (rc = pool.alloc(&d_marg, (size_t)nb * nm)))
+        return rc;
+    if (prior5 && (rc = pool.alloc(&d_prior, (size_t)nb * nm))) return rc;
+    if (vol && (rc = pool.alloc(&d_vol, (size_t)nb * cells))) return rc;
+    HIPCHK(hipMemcpy(h->d_tc, t_corr, (size_t)S * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_ac, a_corr, (size_t)S * sizeof(double), hipMemcpyHostToDevice));
+
+    LocJob jb{};
+    jb.sta = d_sta; jb.ev = d_ev; jb.prior = d_prior; jb.part = d_part; jb.vol = d_vol; jb.S = S;
+    jb.rbeta = 1.0 / vs; jb.katt = (kPi * kFreq) / (qs * vs);          // as event_misfit forms them
+    const double log_cell = std::log(g.dx * g.dy * g.dz);
+    const double log_2pi_half = 0.5 * std::log(2.0 * std::acos(-1.0));
+    const int mode = (h->dev.use_time ? 1 : 0) | (h->dev.use_amp ? 2 : 0);
+    std::vector<double> tab;
+    for (long e0 = 0; e0 < E; e0 += nb) {
+        const long m = std::min(nb, (long)E - e0);
+        if (prior5) {
+            // log densities per ix, iy (normalised Gaussians) and iz (the depth prior of cls_model.f90:178-185, normalised;
+            // -inf at and below z0)
+            tab.resize((size_t)m * nm);
+            for (long b = 0; b < m; ++b) {
+                const double *p = prior5 + 5 * (e0 + b);
+                double *q = tab.data() + (size_t)b * nm;
+                const double lw = std::log(p[2]), lwz = std::log(p[4]);
+                for (int i = 0; i < n[0]; ++i) { const double d = loc_centre(g.x0, g.dx, i) - p[0]; q[i] = (-log_2pi_half - lw) - d * d / (2.0 * p[2] * p[2]); }
+                for (int i = 0; i < n[1]; ++i) { const double d = loc_centre(g.y0, g.dy, i) - p[1]; q[n[0] + i] = (-log_2pi_half - lw) - d * d / (2.0 * p[2] * p[2]); }
+                for (int i = 0; i < n[2]; ++i) {
+                    const double d = loc_centre(g.z0, g.dz, i) - p[3];
+                    q[n[0] + n[1] + i] = d > 0.0 ? (std::log(d) - 2.0 * lwz) - d * d / (2.0 * p[4] * p[4]) : -INFINITY;
+                }
+            }
+            HIPCHK(hipMemcpy(d_prior, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+        }
+        hipLaunchKernelGGL(k_locate_pack, dim3((unsigned)((m * S + 255) / 256)), dim3(256), 0, h->stream, h->dev, (int)e0, (int)m, h->d_tc, h->d_ac,
+                           h->d_lconst_t, h->d_lconst_a, d_sta, d_ev);
+        const dim3 grid((unsigned)n_tiles, (unsigned)m), block(kLocThreads);
+        switch (mode) {
+        case 0: hipLaunchKernelGGL(k_locate<0>, grid, block, 0, h->stream, g, jb); break;
+        case 1: hipLaunchKernelGGL(k_locate<1>, grid, block, 0, h->stream, g, jb); break;
+        case 2: hipLaunchKernelGGL(k_locate<2>, grid, block, 0, h->stream, g, jb); break;
+        default: hipLaunchKernelGGL(k_locate<3>, grid, block, 0, h->stream, g, jb); break;
+        }
+        hipLaunchKernelGGL(k_locate_combine, dim3((unsigned)m), dim3(256), 0, h->stream, g, d_part, log_cell, d_loc, d_marg);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if ((rc = pool.download(loc + (size_t)e0 * 16, d_loc, (size_t)m * 16, "the locations'"))) return rc;
+        if (marg && (rc = pool.download(marg + (size_t)e0 * nm, d_marg, (size_t)m * nm, "the marginals'"))) return rc;
+        if (vol && (rc = pool.download(vol + (size_t)e0 * cells, d_vol, (size_t)m * cells, "the volume's"))) return rc;
+    }
     return HTM_OK;
 }
 

@@ -1,7 +1,8 @@
 // htm_host.hpp -- what the host translation units of libhtm_hip.so share.  Internal: not installed, not part of the ABI
 // (include/htm_hip.h is).
 //
-//   htm_forward.hip        htm_forward_*, htm_device_*, the last-error string, the self-tests and htm_rng_jump
+//   htm_forward.hip        htm_forward_*, htm_device_*, the last-error string, the self-tests and htm_rng_jump; htm_forward_locate
+//                          (the location posteriors on a grid, kernels: htm_locate.hpp)
 //   htm_hip.hip            htm_chains_*, htm_comm_*: sets a chain set up and launches its loops; no k_mcmc is instantiated there
 //   htm_plan.hpp           the launch plan of a chain set: which loop each mode takes (loop_for) and the launch shape, worked out
 //                          by plain functions without a device; kept in htm_chains::plan.  Ask for the plan of a shape with
@@ -10,9 +11,9 @@
 //                          (made with htm_loop_rows.hpp)
 //   htm_steps.hip          steps 1-4, 6, the convergence diagnostics and the location error ellipsoids (htm_hypo_ellipsoid*);
 //                          touches neither htm_forward nor htm_chains
-//   htm_steps_host.hpp     htm_steps.hip's own host idioms (no other unit includes it): StreamBuf, a stream-ordered workspace
-//                          that hands out typed pieces; DevPool, the device arrays of a host-pointer form (alloc, upload,
-//                          download); kMaxWorkItems, the limit of one launch; env_mib, an HTM_x_MB switch
+//   htm_steps_host.hpp     the host idioms of htm_steps.hip, and of htm_forward_locate in htm_forward.hip: StreamBuf, a
+//                          stream-ordered workspace that hands out typed pieces; DevPool, the device arrays of a host-pointer
+//                          form (alloc, upload, download); kMaxWorkItems, the limit of one launch; env_mib, an HTM_x_MB switch
 //
 // Host code is plain C++17 + the HIP runtime: no torch, no third-party dependency.  There is no CPU fallback on purpose:
 // every entry point needs a usable HIP device and fails with HTM_ENODEVICE otherwise.
@@ -100,6 +101,9 @@ struct htm_forward {
     // that can run that master is created on this forward (ensure_obs_pack), and for the other precision when it is switched to
     void *d_pack64 = nullptr, *d_pack32 = nullptr;
     bool pack_wanted = false;
+    // [E] every event's own share of dev.const_sum, per data type: sum_j (log_2pi_half + log stdv(j, event)) in station order
+    // (htm_forward_locate: an event's term of the log-likelihood)
+    double *d_lconst_t = nullptr, *d_lconst_a = nullptr;
 };
 
 struct htm_chains {

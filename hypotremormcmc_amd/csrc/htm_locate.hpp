@@ -1,0 +1,405 @@
+// htm_locate.hpp -- every window's location posterior on a grid under a FIXED structure (vs, qs, station corrections): the
+// kernels of htm_forward_locate (htm_forward.hip; rule, choices and measurements: DESIGN.md §3.10).  With the global parameters
+// fixed the log-likelihood is a sum of independent per-event terms (each event is demeaned on its own: cls_forward.f90:113-133,
+// :199-218, :268-303), so an event's term is a function of its position alone and is tabulated at the cell centres.
+//
+// The mapping is the opposite of event_misfit's: a lane owns CELLS, the stations are the serial inner loop in the reference's
+// own order 0 .. n_sta - 1, and no sum over stations crosses lanes.
+//
+//   k_locate_pack     one record per (event of the batch, station): what the evaluation reads of a station, packed so that a
+//                     workgroup reads it with uniform SCALAR loads (ld_const), and one record of constants per event
+//   k_locate<MODE>    grid = (tiles, events of the batch).  A tile is up to kLocRows whole x-rows of ONE z-layer, at most
+//                     kLocTile cells; a thread owns the cells t, t + 256, ... of it, kLocChunk at a time (independent
+//                     dependency chains).  The demeaned misfit comes in one pass from the shifted identity
+//                     sum p (r - m)^2 = sum p u^2 - (sum p u)^2 / sum p, u = r - r_0 (r_0: the first station's residual).
+//                     The lanes keep their cells' log posteriors in registers, the workgroup finds the tile's maximum and
+//                     its first cell, puts the weights exp(lp - max) in LDS and sums them there in a fixed order: per x-row
+//                     (a wave per row, the fixed-tree wave sum) and per ix over the rows.  One partial record per tile.
+//   k_locate_combine  one workgroup per event: the event's maximum over its tiles in tile order, every partial rescaled by
+//                     exp(max_tile - max_event); marginals, mean, covariance, log evidence.
+// No floating-point atomics anywhere: the bits do not depend on timing.  The volume of log posteriors is written only when it
+// is asked for.
+//
+// Partial record of a tile (doubles): [0] the tile's maximum lp (-inf: no included cell; k_locate_combine overwrites it with
+// the tile's scale), [1] its first cell's linear index (-1: none), [2] that cell's log-likelihood term, [3] the tile's weight
+// sum, then mx[nx] (weight per ix over the tile's rows), S[rows_per_tile] (weight per row), T[rows_per_tile] (weight times x
+// per row).
+#pragma once
+#include <climits>
+
+#include "htm_device.hpp"
+
+namespace htm {
+
+#ifndef HTM_LOC_DEMEAN
+#define HTM_LOC_DEMEAN 0   // 0: the shifted one-pass identity; 1: two passes, the synthetics computed twice (measured: DESIGN.md 3.10)
+#endif
+constexpr int kLocMaxCells = 4096;      // cells per axis: the limit of htm_hypo_density (kDensMaxCells)
+constexpr int kLocThreads = 256;
+constexpr int kLocPerThread = 16;       // cells of a tile per thread
+constexpr int kLocChunk = 4;            // of them evaluated side by side
+constexpr int kLocTile = kLocThreads * kLocPerThread;
+constexpr int kLocRows = 256;           // x-rows per tile at the most
+constexpr int kLocHead = 4;
+static_assert(kLocTile >= kLocMaxCells, "a tile holds at least one whole x-row");
+static_assert(kLocPerThread % kLocChunk == 0, "whole chunks");
+
+// what the evaluation reads of one station for one event; 80 bytes, read with scalar loads
+struct __attribute__((aligned(16))) LocSta {
+    double sx, sy, sz, tc, ac, tob, tpr, aob, apr, pad;
+};
+// per event: 1 / sum of precisions (time, amplitude) and sum_j (log_2pi_half + log stdv_j) (time, amplitude)
+struct __attribute__((aligned(16))) LocEv {
+    double rpst, rpsa, ct, ca;
+};
+
+struct LocGrid {
+    double x0, dx, y0, dy, z0, dz;
+    int nx, ny, nz;
+    int rows;        // x-rows per tile
+    int tpl;         // tiles per z-layer
+    int stride;      // doubles per partial record
+};
+
+struct LocJob {
+    const LocSta *sta;      // [nb][S]
+    const LocEv *ev;        // [nb]
+    const double *prior;    // [nb][nx + ny + nz] log prior per ix, iy, iz, or nullptr: flat
+    double *part;           // [nb][nz * tpl][stride]
+    double *vol;            // [nb][nz][ny][nx] or nullptr
+    int S;
+    double rbeta, katt;     // 1 / vs, pi f / (qs vs)
+};
+
+// the centre of cell i: one multiplication, then one addition (the library is built with -ffp-contract=off)
+__host__ __device__ __forceinline__ double loc_centre(double v0, double dv, int i)
+{
+    const double t = ((double)i + 0.5) * dv;
+    return v0 + t;
+}
+
+// a record at a wave-uniform address through the constant address space: scalar loads, as ld_const (the doubles travel in pairs)
+typedef double loc_f64x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ LocSta loc_ld_sta(const LocSta *p)
+{
+    typedef const loc_f64x2 __attribute__((address_space(4))) *CP;
+    const CP q = (CP)(unsigned long long)p;
+    const loc_f64x2 a = q[0], b = q[1], c = q[2], d = q[3], e = q[4];
+    return LocSta{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1], e[0], e[1]};
+}
+__device__ __forceinline__ LocEv loc_ld_ev(const LocEv *p)
+{
+    typedef const loc_f64x2 __attribute__((address_space(4))) *CP;
+    const CP q = (CP)(unsigned long long)p;
+    const loc_f64x2 a = q[0], b = q[1];
+    return LocEv{a[0], a[1], b[0], b[1]};
+}
+
+__device__ __forceinline__ bool loc_included(double lp) { return lp == lp && lp != -__builtin_inf(); }
+
+__global__ __launch_bounds__(256) void k_locate_pack(FwdDev f, int e0, int nb, const double *tc, const double *ac, const double *lct,
+                                                     const double *lca, LocSta *sta, LocEv *ev)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)nb * f.S) return;
+    const int b = (int)(i / f.S), j = (int)(i - (long)b * f.S);
+    const size_t k = (size_t)(e0 + b) * f.S + j;
+    LocSta r;
+    r.sx = f.sx[j]; r.sy = f.sy[j]; r.sz = f.sz[j]; r.tc = tc[j]; r.ac = ac[j];
+    r.tob = f.t_obs[k]; r.tpr = f.t_prec[k]; r.aob = f.a_obs[k]; r.apr = f.a_prec[k]; r.pad = 0.0;
+    sta[i] = r;
+    if (j == 0) ev[b] = LocEv{f.rpsum_t[e0 + b], f.rpsum_a[e0 + b], lct[e0 + b], lca[e0 + b]};
+}
+
+// (value, index) of the larger value, of the lower index among equal values: the same whatever the order of the comparisons
+struct LocBest {
+    double lp, ell;
+    int idx;
+};
+__device__ __forceinline__ void loc_better(LocBest &a, double lp, double ell, int idx)
+{
+    const bool take = lp > a.lp || (lp == a.lp && idx < a.idx);
+    a.lp = take ? lp : a.lp; a.ell = take ? ell : a.ell; a.idx = take ? idx : a.idx;
+}
+__device__ __forceinline__ void loc_best_wave(LocBest &a)
+{
+#pragma unroll
+    for (int off = 32; off; off >>= 1) loc_better(a, __shfl_xor(a.lp, off), __shfl_xor(a.ell, off), __shfl_xor(a.idx, off));
+}
+
+// sum over the block's 256 threads in a fixed order: the wave sums' tree, then (w0 + w1) + (w2 + w3); every thread gets it
+__device__ __forceinline__ double loc_block_sum(double v, double *s_red4)
+{
+    const double w = wave_sum1(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s_red4[threadIdx.x >> 6] = w;
+    __syncthreads();
+    return (s_red4[0] + s_red4[1]) + (s_red4[2] + s_red4[3]);
+}
+
+// MODE: 1 travel times only, 2 amplitudes only, 3 both
+template <int MODE>
+__global__ __launch_bounds__(256) void k_locate(LocGrid g, LocJob jb)
+{
+    constexpr bool UT = (MODE & 1) != 0, UA = (MODE & 2) != 0;
+    __shared__ double s_w[kLocTile];
+    __shared__ double s_S[kLocRows];
+    __shared__ double s_blp[4], s_bell[4];
+    __shared__ int s_bidx[4];
+    const int t = threadIdx.x, lane = t & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int tile = blockIdx.x, b = blockIdx.y;
+    const int iz = tile / g.tpl, iy0 = (tile - iz * g.tpl) * g.rows;
+    const int rows = min(g.rows, g.ny - iy0), ncell = rows * g.nx;
+    const long cell0 = ((long)iz * g.ny + iy0) * g.nx;            // linear index of the tile's first cell
+    const double zc = loc_centre(g.z0, g.dz, iz);
+    const LocSta *sta = jb.sta + (size_t)b * jb.S;
+    const LocEv ev = loc_ld_ev(jb.ev + b);
+    const double *prior = jb.prior ? jb.prior + (size_t)b * (g.nx + g.ny + g.nz) : nullptr;
+    const double pz = prior ? prior[g.nx + g.ny + iz] : 0.0;
+
+    double lp[kLocPerThread];
+    LocBest best{-__builtin_inf(), 0.0, INT_MAX};
+#pragma unroll
+    for (int ch = 0; ch < kLocPerThread / kLocChunk; ++ch) {
+        double x[kLocChunk], y[kLocChunk], pxy[kLocChunk];
+        double r0t[kLocChunk], r0a[kLocChunk], t1[kLocChunk], t2[kLocChunk], a1[kLocChunk], a2[kLocChunk];
+        if (ch * kLocChunk * kLocThreads >= ncell) {      // (block-uniform: no cell of this chunk exists)
+#pragma unroll
+            for (int k = 0; k < kLocChunk; ++k) lp[ch * kLocChunk + k] = __builtin_nan("");
+            continue;
+        }
+#pragma unroll
+        for (int k = 0; k < kLocChunk; ++k) {
+            const int c = t + kLocThreads * (ch * kLocChunk + k), cc = c < ncell ? c : 0;      // (a thread without a cell evaluates cell 0 and drops it)
+            const int r = cc / g.nx, ix = cc - r * g.nx;
+            x[k] = loc_centre(g.x0, g.dx, ix);
+            y[k] = loc_centre(g.y0, g.dy, iy0 + r);
+            pxy[k] = prior ? prior[ix] + prior[g.nx + iy0 + r] : 0.0;
+            t1[k] = t2[k] = a1[k] = a2[k] = r0t[k] = r0a[k] = 0.0;
+        }
+        // a station's residuals (synthetic minus observation) at cell k of the chunk: cls_forward.f90:115-118, :201-204 as event_misfit
+        auto resid = [&](const LocSta &st, int k, double &rt, double &ra) {
+            const double dx = x[k] - st.sx, dy = y[k] - st.sy, dz = zc - st.sz;
+            const double d = htm_sqrt(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)));
+            if constexpr (UT) rt = __builtin_fma(d, jb.rbeta, -st.tc) - st.tob;
+            if constexpr (UA) ra = (__builtin_fma(-d, jb.katt, -htm_log(d)) - st.ac) - st.aob;
+        };
+#if HTM_LOC_DEMEAN == 0
+        // station 0 gives the shifts (its own u is exactly 0), stations 1 .. S - 1 add to the sums
+        for (int j = 0; j < jb.S; ++j) {
+            const LocSta st = loc_ld_sta(sta + j);
+#pragma unroll
+            for (int k = 0; k < kLocChunk; ++k) {
+                double rt = 0.0, ra = 0.0;
+                resid(st, k, rt, ra);
+                if constexpr (UT) {
+                    if (j == 0) r0t[k] = rt;
+                    const double u = rt - r0t[k], pu = st.tpr * u;
+                    t1[k] += pu;
+                    t2[k] = __builtin_fma(pu, u, t2[k]);
+                }
+                if constexpr (UA) {
+                    if (j == 0) r0a[k] = ra;
+                    const double u = ra - r0a[k], pu = st.apr * u;
+                    a1[k] += pu;
+                    a2[k] = __builtin_fma(pu, u, a2[k]);
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kLocChunk; ++k) {       // sum p (r - m)^2 = sum p u^2 - (sum p u)^2 / sum p
+            t2[k] -= (t1[k] * t1[k]) * ev.rpst;
+            a2[k] -= (a1[k] * a1[k]) * ev.rpsa;
+        }
+#else
+        // the reference's two passes, the synthetics computed twice
+        for (int j = 0; j < jb.S; ++j) {
+            const LocSta st = loc_ld_sta(sta + j);
+#pragma unroll
+            for (int k = 0; k < kLocChunk; ++k) {
+                double rt = 0.0, ra = 0.0;
+                resid(st, k, rt, ra);
+                if constexpr (UT) t1[k] = __builtin_fma(st.tpr, rt, t1[k]);
+                if constexpr (UA) a1[k] = __builtin_fma(st.apr, ra, a1[k]);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kLocChunk; ++k) { r0t[k] = t1[k] * ev.rpst; r0a[k] = a1[k] * ev.rpsa; }
+        for (int j = 0; j < jb.S; ++j) {
+            const LocSta st = loc_ld_sta(sta + j);
+#pragma unroll
+            for (int k = 0; k < kLocChunk; ++k) {
+                double rt = 0.0, ra = 0.0;
+                resid(st, k, rt, ra);
+                if constexpr (UT) { const double e = rt - r0t[k]; t2[k] = __builtin_fma(st.tpr * e, e, t2[k]); }
+                if constexpr (UA) { const double e = ra - r0a[k]; a2[k] = __builtin_fma(st.apr * e, e, a2[k]); }
+            }
+        }
+#endif
+#pragma unroll
+        for (int k = 0; k < kLocChunk; ++k) {
+            const int c = t + kLocThreads * (ch * kLocChunk + k);
+            double ell = 0.0;
+            if constexpr (UT) ell -= 0.5 * t2[k] + ev.ct;
+            if constexpr (UA) ell -= 0.5 * a2[k] + ev.ca;
+            const double v = prior ? ell + (pxy[k] + pz) : ell;
+            const bool live = c < ncell;
+            lp[ch * kLocChunk + k] = live ? v : __builtin_nan("");
+            if (live) {
+                if (jb.vol) jb.vol[(size_t)b * ((size_t)g.nx * g.ny * g.nz) + (size_t)(cell0 + c)] = v;
+                if (loc_included(v)) loc_better(best, v, ell, c);      // (a thread's cells come in ascending order)
+            }
+        }
+    }
+
+    // the tile's maximum and its first cell
+    loc_best_wave(best);
+    if (lane == 0) { s_blp[wv] = best.lp; s_bell[wv] = best.ell; s_bidx[wv] = best.idx; }
+    __syncthreads();
+    best = LocBest{s_blp[0], s_bell[0], s_bidx[0]};
+#pragma unroll
+    for (int w = 1; w < 4; ++w) loc_better(best, s_blp[w], s_bell[w], s_bidx[w]);
+    double *rec = jb.part + ((size_t)b * ((size_t)g.nz * g.tpl) + tile) * g.stride;
+    double *mx = rec + kLocHead, *pS = mx + g.nx, *pT = pS + g.rows;
+    const bool none = best.idx == INT_MAX;      // (block-uniform)
+    if (t == 0) {
+        rec[0] = none ? -__builtin_inf() : best.lp;
+        rec[1] = none ? -1.0 : (double)(cell0 + best.idx);
+        rec[2] = none ? 0.0 : best.ell;
+    }
+    if (none) {
+        if (t == 0) rec[3] = 0.0;
+        for (int i = t; i < g.nx + 2 * g.rows; i += kLocThreads) mx[i] = 0.0;
+        return;
+    }
+    // weights relative to the tile's maximum, into LDS
+#pragma unroll
+    for (int k = 0; k < kLocPerThread; ++k) {
+        const int c = t + kLocThreads * k;
+        if (c < ncell) s_w[c] = loc_included(lp[k]) ? exp(lp[k] - best.lp) : 0.0;
+    }
+    __syncthreads();
+    // a wave per x-row: the row's weight and weight times x, lane-strided in ascending ix, then the wave sums' fixed tree
+    for (int r = wv; r < g.rows; r += 4) {       // (wave-uniform; rows beyond the tile's give zeros)
+        double v[2] = {0.0, 0.0};
+        if (r < rows)
+            for (int ix = lane; ix < g.nx; ix += 64) {
+                const double w = s_w[r * g.nx + ix];
+                v[0] += w;
+                v[1] = __builtin_fma(w, loc_centre(g.x0, g.dx, ix), v[1]);
+            }
+        wave_sum<2>(v);
+        if (lane == 0) { s_S[r] = v[0]; pS[r] = v[0]; pT[r] = v[1]; }
+    }
+    // a thread per ix: the weight over the tile's rows, in ascending row order
+    for (int ix = t; ix < g.nx; ix += kLocThreads) {
+        double a = 0.0;
+        for (int r = 0; r < rows; ++r) a += s_w[r * g.nx + ix];
+        mx[ix] = a;
+    }
+    __syncthreads();
+    if (wv == 0) {      // the tile's weight: the rows lane-strided, then the tree
+        double a = 0.0;
+        for (int r = lane; r < rows; r += 64) a += s_S[r];
+        a = wave_sum1(a);
+        if (lane == 0) rec[3] = a;
+    }
+}
+
+// One workgroup of 256 threads per event of the batch.  loc [nb][16], marg [nb][nx + ny + nz] (always there: the moments are
+// taken from the marginals).
+__global__ __launch_bounds__(256) void k_locate_combine(LocGrid g, double *part, double log_cell, double *loc, double *marg)
+{
+    __shared__ double s_red4[4];
+    __shared__ double s_blp[4], s_bell[4], s_bidx[4];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6, b = blockIdx.x;
+    const int n_tiles = g.nz * g.tpl, nm = g.nx + g.ny + g.nz;
+    double *P = part + (size_t)b * n_tiles * g.stride;
+    double *L = loc + (size_t)b * 16, *M = marg + (size_t)b * nm;
+    const double nan = __builtin_nan("");
+
+    // the event's maximum and its first cell: the tiles are in ascending order of their cells' indices
+    double blp = -__builtin_inf(), bell = 0.0, bidx = -1.0;
+    auto better = [&](double lp, double ell, double idx) {
+        const bool take = idx >= 0.0 && (lp > blp || bidx < 0.0 || (lp == blp && idx < bidx));
+        blp = take ? lp : blp; bell = take ? ell : bell; bidx = take ? idx : bidx;
+    };
+    for (int k = t; k < n_tiles; k += 256) { const double *r = P + (size_t)k * g.stride; better(r[0], r[2], r[1]); }
+#pragma unroll
+    for (int off = 32; off; off >>= 1) better(__shfl_xor(blp, off), __shfl_xor(bell, off), __shfl_xor(bidx, off));
+    if (lane == 0) { s_blp[wv] = blp; s_bell[wv] = bell; s_bidx[wv] = bidx; }
+    __syncthreads();
+    blp = s_blp[0]; bell = s_bell[0]; bidx = s_bidx[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) better(s_blp[w], s_bell[w], s_bidx[w]);
+    if (bidx < 0.0) {       // (block-uniform) no included cell
+        if (t < 16) L[t] = t == 0 ? -1.0 : nan;
+        for (int i = t; i < nm; i += 256) M[i] = nan;
+        return;
+    }
+    // every tile's scale exp(max_tile - max_event) takes the place of its maximum (an empty tile: exp(-inf) = 0)
+    for (int k = t; k < n_tiles; k += 256) { double *r = P + (size_t)k * g.stride; r[0] = exp(r[0] - blp); }
+    __syncthreads();
+    // the weight sum: tiles thread-strided in ascending order, then the fixed tree
+    double acc = 0.0;
+    for (int k = t; k < n_tiles; k += 256) { const double *r = P + (size_t)k * g.stride; acc = __builtin_fma(r[0], r[3], acc); }
+    const double W = loc_block_sum(acc, s_red4);
+    // the marginals, every entry by one thread in tile order, divided by the weight sum
+    for (int ix = t; ix < g.nx; ix += 256) {
+        double a = 0.0;
+        for (int k = 0; k < n_tiles; ++k) { const double *r = P + (size_t)k * g.stride; a = __builtin_fma(r[0], r[kLocHead + ix], a); }
+        M[ix] = a / W;
+    }
+    for (int iy = t; iy < g.ny; iy += 256) {
+        const int tl = iy / g.rows, rr = iy - tl * g.rows;
+        double a = 0.0;
+        for (int iz = 0; iz < g.nz; ++iz) { const double *r = P + (size_t)(iz * g.tpl + tl) * g.stride; a = __builtin_fma(r[0], r[kLocHead + g.nx + rr], a); }
+        M[g.nx + iy] = a / W;
+    }
+    for (int iz = t; iz < g.nz; iz += 256) {
+        double a = 0.0;
+        for (int tl = 0; tl < g.tpl; ++tl) { const double *r = P + (size_t)(iz * g.tpl + tl) * g.stride; a = __builtin_fma(r[0], r[3], a); }
+        M[g.nx + g.ny + iz] = a / W;
+    }
+    __syncthreads();
+    // mean and variances from the marginals: the mean as the best cell's centre plus the mean offset from it (a posterior that
+    // sits in one cell of an axis has that centre for its mean, exactly), the variances about the mean
+    const long cb = (long)bidx;
+    const int bz = (int)(cb / ((long)g.nx * g.ny)), by = (int)((cb - (long)bz * g.nx * g.ny) / g.nx), bx = (int)(cb - ((long)bz * g.ny + by) * g.nx);
+    const double v0[3] = {g.x0, g.y0, g.z0}, dv[3] = {g.dx, g.dy, g.dz};
+    const int n[3] = {g.nx, g.ny, g.nz}, off[3] = {0, g.nx, g.nx + g.ny}, bi[3] = {bx, by, bz};
+    double mean[3], var[3], bc[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        bc[a] = loc_centre(v0[a], dv[a], bi[a]);
+        double s = 0.0;
+        for (int i = t; i < n[a]; i += 256) s = __builtin_fma(M[off[a] + i], loc_centre(v0[a], dv[a], i) - bc[a], s);
+        mean[a] = bc[a] + loc_block_sum(s, s_red4);
+        s = 0.0;
+        for (int i = t; i < n[a]; i += 256) { const double d = loc_centre(v0[a], dv[a], i) - mean[a]; s = __builtin_fma(M[off[a] + i] * d, d, s); }
+        var[a] = loc_block_sum(s, s_red4);
+    }
+    // the mixed moments about the mean from the rows' sums: tiles thread-strided, a tile's rows in order
+    double cxy = 0.0, cxz = 0.0, cyz = 0.0;
+    for (int k = t; k < n_tiles; k += 256) {
+        const double *r = P + (size_t)k * g.stride, *pS = r + kLocHead + g.nx, *pT = pS + g.rows;
+        const int iz = k / g.tpl, iy0 = (k - iz * g.tpl) * g.rows, rows = min(g.rows, g.ny - iy0);
+        double A = 0.0, B = 0.0, C = 0.0;
+        for (int rr = 0; rr < rows; ++rr) {
+            const double ex = pT[rr] - mean[0] * pS[rr], ey = loc_centre(g.y0, g.dy, iy0 + rr) - mean[1];
+            A += ex; B = __builtin_fma(ey, ex, B); C = __builtin_fma(ey, pS[rr], C);
+        }
+        const double ez = loc_centre(g.z0, g.dz, iz) - mean[2];
+        cxy = __builtin_fma(r[0], B, cxy); cxz = __builtin_fma(r[0] * ez, A, cxz); cyz = __builtin_fma(r[0] * ez, C, cyz);
+    }
+    cxy = loc_block_sum(cxy, s_red4) / W; cxz = loc_block_sum(cxz, s_red4) / W; cyz = loc_block_sum(cyz, s_red4) / W;
+    if (t == 0) {
+        L[0] = bidx; L[1] = bc[0]; L[2] = bc[1]; L[3] = bc[2];
+        L[4] = blp; L[5] = bell; L[6] = (blp + htm_log(W)) + log_cell;
+        L[7] = mean[0]; L[8] = mean[1]; L[9] = mean[2];
+        L[10] = var[0]; L[11] = cxy; L[12] = cxz; L[13] = var[1]; L[14] = cyz; L[15] = var[2];
+    }
+}
+
+}  // namespace htm

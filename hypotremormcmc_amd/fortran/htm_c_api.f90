@@ -19,6 +19,7 @@ module htm_c_api
   public :: htm_rank_normalize, htm_rank_normalize_dev, htm_diagnose_rank, htm_diagnose_rank_dev
   public :: htm_hypo_ellipsoid, htm_hypo_ellipsoid_dev
   public :: htm_hypo_density, htm_hypo_density_dev
+  public :: htm_forward_locate
   public :: htm_chains_checkpoint_size, htm_chains_checkpoint_save, htm_chains_checkpoint_load
 
   integer(c_size_t), parameter :: HTM_XCHG_HANDLE_BYTES = 64_c_size_t, HTM_COMM_ID_BYTES = 128_c_size_t
@@ -354,6 +355,21 @@ module htm_c_api
        type(c_ptr), value :: d_xy, d_xz, d_yz, d_vol, d_tally, hip_stream
        integer(c_int) :: rc
      end function htm_hypo_density_dev
+     !> location posteriors on a grid under a fixed structure (include/htm_hip.h): t_corr, a_corr (n_sta); grid9 as above;
+     !> prior5 (5, n_events) = mu_x, mu_y, w_xy, z0, w_z or c_null_ptr (flat); loc (16, n_events); marg (nx + ny + nz, n_events)
+     !> or c_null_ptr; vol (nx, ny, nz, n_events) or c_null_ptr
+     function htm_forward_locate(handle, t_corr, vs, a_corr, qs, grid9, prior5, loc, marg, vol) &
+          & bind(C, name="htm_forward_locate") result(rc)
+       import :: c_int, c_double, c_ptr
+       type(c_ptr), value :: handle
+       real(c_double), intent(in) :: t_corr(*), a_corr(*)
+       real(c_double), value :: vs, qs
+       real(c_double), intent(in) :: grid9(9)
+       type(c_ptr), value :: prior5
+       real(c_double), intent(out) :: loc(*)
+       type(c_ptr), value :: marg, vol
+       integer(c_int) :: rc
+     end function htm_forward_locate
      !> step-4 regressions (include/htm_hip.h): t, t_err, a, a_err (n_sta, n_win); out (6, n_win) = vs, b, t0, a0, cc_t, cc_a
      function htm_select_regress(device, n_sta, n_win, sta_x, sta_y, sta_z, z_guess, t, t_err, a, a_err, out) &
           & bind(C, name="htm_select_regress") result(rc)

@@ -1,0 +1,247 @@
+"""Locate windows on a grid under a FIXED structure on the GPU: with vs, qs and the station corrections fixed (a calibration
+run's medians), a window's location posterior is a function of its position alone and is tabulated at the cell centres of a
+grid -- no MCMC, any number of windows (kernels in hypotremormcmc_amd/csrc/htm_locate.hpp).
+
+    python -m hypotremormcmc_amd.locate <parameter file> --cell DX [DY DZ] [--bounds x0 x1 y0 y1 z0 z1] [--structure DIR]
+                                        [--windows FILE] [--flat-prior] [--volume-of WIN]
+
+run in the data directory (station file, opt_data.NNNNNN.dat).  --structure DIR holds `uniform_structure.stat` and
+`station_corrections.stat` of the calibration run (default: the parameter file's directory); --windows FILE lists the window
+ids in its first column (default `selected_win.dat`).  Without --bounds the box is density.default_bounds.  The prior is step
+5's: Gaussians of prior_width_xy about the station of largest amplitude in x and y, the depth prior of prior_z and
+prior_width_z; --flat-prior turns it off.  use_time / use_amp come from the parameter file.  Writes `hypo_grid.stat` (the
+layout of hypo.stat: median, 2.5 % and 97.5 % of every axis, from the marginals) and `hypo_grid.best.dat` (one line per
+window: the best cell's centre, its log posterior and log-likelihood term, the log evidence, the posterior mean, and 1 when
+the best cell lies on a face of the box: that window is not resolved by this grid).  --volume-of WIN also writes that
+window's log posterior of every cell to `hypo_grid.WIN.vol.dat`.  The windows go to the device in batches whose workspace
+stays under HTM_LOCATE_MB MiB (default 1024); the result does not depend on it.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+
+from . import _lib
+from .density import default_bounds, grid9, grid_counts, make_grid
+from .forward import Forward
+from .obs_data import ObsData
+from .param import Param
+from .statistics import HYPO_HEADER
+
+INT_MAX = 2 ** 31 - 1
+BEST_HEADER = ("# window ID, best cell's centre x y z, log posterior there, log-likelihood term there, log evidence, "
+               "posterior mean x y z, 1: the best cell lies on a face of the box")
+
+
+def centres(grid, axis: int):
+    """the cell centres of one axis, v0 + (i + 0.5) * dv: one multiplication, then one addition, as the library forms them"""
+    g = grid9(grid)
+    return g[3 * axis] + (np.arange(int(g[3 * axis + 2])) + 0.5) * g[3 * axis + 1]
+
+
+def locate(fwd, t_corr, vs, a_corr, qs, grid, prior=None, marginals=True, volume=False):
+    """The location posterior of every event of the Forward `fwd` on `grid` = x0, dx, nx, y0, dy, ny, z0, dz, nz under the fixed
+    structure t_corr [n_sta], vs, a_corr [n_sta], qs; prior [n_events][5] = mu_x, mu_y, w_xy, z0, w_z or None (flat).  Returns
+    a dict: index [E] (int64; the best cell's ix + nx (iy + ny iz), -1: every cell excluded), best [E][3] its centre, lp and
+    ell [E] the log posterior and the log-likelihood term there, log_evidence [E], mean [E][3], cov [E][3][3], loc [E][16]
+    the library's record, marg_x / marg_y / marg_z [E][n] (None without `marginals`), vol [E][nz][ny][nx] (None without
+    `volume`)."""
+    g = grid9(grid)
+    nx, ny, nz = grid_counts(g)
+    if nx * ny * nz > INT_MAX:
+        raise ValueError(f"{nx} x {ny} x {nz} cells: more than 2^31 - 1")
+    E, S = fwd.n_events, fwd.n_sta
+    tc = np.ascontiguousarray(np.asarray(t_corr, dtype=np.float64).reshape(-1))
+    ac = np.ascontiguousarray(np.asarray(a_corr, dtype=np.float64).reshape(-1))
+    if tc.size != S or ac.size != S:
+        raise ValueError(f"t_corr and a_corr have {tc.size} and {ac.size} values: need one per station ({S})")
+    pr = None
+    if prior is not None:
+        pr = np.ascontiguousarray(prior, dtype=np.float64)
+        if pr.shape != (E, 5):
+            raise ValueError(f"prior is {pr.shape}: need mu_x, mu_y, w_xy, z0, w_z of every event ({E})")
+    loc = np.empty((E, 16))
+    marg = np.empty((E, nx + ny + nz)) if marginals else None
+    vol = np.empty((E, nz, ny, nx)) if volume else None
+    _lib.check(_lib.load().htm_forward_locate(fwd.handle, _lib.ptr(tc), float(vs), _lib.ptr(ac), float(qs), _lib.ptr(g), _lib.ptr(pr),
+                                              _lib.ptr(loc), _lib.ptr(marg), _lib.ptr(vol)))
+    cov = np.empty((E, 3, 3))
+    for (i, j), k in zip(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2)), range(10, 16)):
+        cov[:, i, j] = cov[:, j, i] = loc[:, k]
+    return {"index": loc[:, 0].astype(np.int64), "best": loc[:, 1:4].copy(), "lp": loc[:, 4].copy(), "ell": loc[:, 5].copy(),
+            "log_evidence": loc[:, 6].copy(), "mean": loc[:, 7:10].copy(), "cov": cov, "loc": loc,
+            "marg_x": None if marg is None else marg[:, :nx], "marg_y": None if marg is None else marg[:, nx:nx + ny],
+            "marg_z": None if marg is None else marg[:, nx + ny:], "vol": vol}
+
+
+def marginal_quantiles(marg, grid, levels=(0.025, 0.5, 0.975)):
+    """marg [E][nx + ny + nz] (or one row): the quantiles of the three axis marginals, [E][3][len(levels)].  On an axis the
+    quantile q lies in the first cell k whose cumulative mass c_k reaches q, and linearly inside it:
+    v0 + dv (k + (q - c_{k-1}) / m_k).  A marginal of NaN gives NaN."""
+    g = grid9(grid)
+    n = grid_counts(g)
+    m = np.asarray(marg, dtype=np.float64)
+    one = m.ndim == 1
+    m = m.reshape(-1, sum(n))
+    out = np.full((m.shape[0], 3, len(levels)), np.nan)
+    off = 0
+    for a in range(3):
+        for e in range(m.shape[0]):
+            ma = m[e, off:off + n[a]]
+            if np.isnan(ma).any():
+                continue
+            c = np.cumsum(ma)
+            for j, q in enumerate(levels):
+                k = min(int(np.searchsorted(c, q, side="left")), n[a] - 1)
+                while k > 0 and ma[k] == 0.0:          # (rounding left the last cells' sum below q: the last cell with mass)
+                    k -= 1
+                before = c[k - 1] if k > 0 else 0.0
+                out[e, a, j] = g[3 * a] + g[3 * a + 1] * (k + min((q - before) / ma[k], 1.0))
+        off += n[a]
+    return out[0] if one else out
+
+
+def read_structure(directory, station_names):
+    """vs, qs, t_corr [n_sta], a_corr [n_sta]: the medians of `uniform_structure.stat` and `station_corrections.stat` in
+    `directory` (the first and fourth number of a data line), the stations matched by name with `station_names`"""
+    def data_lines(name):
+        path = os.path.join(directory, name)
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"{path} is missing: --structure names the directory of a calibration run's .stat files")
+        return path, [ln.split() for ln in open(path) if ln.strip() and not ln.lstrip().startswith("#")]
+
+    path, rows = data_lines("uniform_structure.stat")
+    if not rows or len(rows[0]) < 6:
+        raise ValueError(f"{path}: no data line of six numbers")
+    vs, qs = float(rows[0][0]), float(rows[0][3])
+    path, rows = data_lines("station_corrections.stat")
+    by_name = {}
+    for r in rows:
+        if len(r) < 7:
+            raise ValueError(f"{path}: a data line is a station name and six numbers, got {' '.join(r)!r}")
+        by_name[r[0]] = (float(r[1]), float(r[4]))
+    tc, ac = [], []
+    for nm in station_names:
+        key = str(nm).strip()[:12]                 # (station_corrections.stat keeps 12 characters of a name)
+        if key not in by_name:
+            raise ValueError(f"station {str(nm).strip()} of the station file is not in {path}")
+        tc.append(by_name[key][0])
+        ac.append(by_name[key][1])
+    return vs, qs, np.array(tc), np.array(ac)
+
+
+def step5_prior(par, obs):
+    """[n_events][5] = mu_x, mu_y, w_xy, z0, w_z as step 5 sets the hypocentre priors (the station of largest amplitude)"""
+    mu_x, mu_y = obs.make_initial_guess()
+    p = np.empty((obs.n_events, 5))
+    p[:, 0], p[:, 1] = mu_x, mu_y
+    p[:, 2], p[:, 3], p[:, 4] = par.get_prior_width_xy(), par.get_prior_z(), par.get_prior_width_z()
+    return p
+
+
+def _field(v, width=13):
+    return "%*s" % (width, "NaN") if np.isnan(v) else "%*.6f" % (width, v)
+
+
+def stat_text(win_id, quant) -> str:
+    """the text of hypo_grid.stat from quant [E][3][3] = 2.5 %, 50 %, 97.5 % of x, y, z: hypo.stat's header and layout (median,
+    2.5 %, 97.5 % per axis); NaN is written as NaN in the field's width"""
+    lines = [HYPO_HEADER]
+    for w, q in zip(win_id, np.asarray(quant, dtype=np.float64)):
+        lines.append("%9d" % w + "".join(_field(q[a][j]) for a in range(3) for j in (1, 0, 2)))
+    return "\n".join(lines) + "\n"
+
+
+def on_face(index, grid):
+    """per window whether the best cell lies on a face of the box (False for a window without a cell)"""
+    nx, ny, nz = grid_counts(grid)
+    idx = np.asarray(index, dtype=np.int64)
+    ix, iy, iz = idx % nx, (idx // nx) % ny, idx // (nx * ny)
+    return (idx >= 0) & ((ix == 0) | (ix == nx - 1) | (iy == 0) | (iy == ny - 1) | (iz == 0) | (iz == nz - 1))
+
+
+def best_text(win_id, res, grid) -> str:
+    """the text of hypo_grid.best.dat from locate's result"""
+    flag = on_face(res["index"], grid)
+    lines = [BEST_HEADER]
+    for i, w in enumerate(win_id):
+        vals = list(res["best"][i]) + [res["lp"][i], res["ell"][i], res["log_evidence"][i]] + list(res["mean"][i])
+        lines.append("%9d" % w + "".join(_field(v, 15) for v in vals) + "%3d" % int(flag[i]))
+    return "\n".join(lines) + "\n"
+
+
+def volume_text(vol, grid) -> str:
+    """the text of hypo_grid.WIN.vol.dat from one window's vol [nz][ny][nx]: linear index, cell centre, log posterior"""
+    nx, ny, nz = grid_counts(grid)
+    x, y, z = (centres(grid, a) for a in range(3))
+    lines = ["# cell ix + nx (iy + ny iz), centre x y z, log posterior (NaN, -inf: excluded)"]
+    v = np.asarray(vol).reshape(nz, ny, nx)
+    for iz in range(nz):
+        for iy in range(ny):
+            for ix in range(nx):
+                lines.append("%10d%14.6f%14.6f%14.6f %.17g" % (ix + nx * (iy + ny * iz), x[ix], y[iy], z[iz], v[iz, iy, ix]))
+    return "\n".join(lines) + "\n"
+
+
+def summary_text(res, grid) -> str:
+    n = len(res["index"])
+    return (f"{n} windows located on {' x '.join(str(c) for c in grid_counts(grid))} cells\n"
+            f"{int(on_face(res['index'], grid).sum())} with the best cell on a face of the box (not resolved by this grid), "
+            f"{int((res['index'] < 0).sum())} without an included cell\n")
+
+
+def read_windows(path):
+    return [int(ln.split()[0]) for ln in open(path) if ln.strip() and not ln.lstrip().startswith("#")]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m hypotremormcmc_amd.locate", description=__doc__.split("\n\n")[0])
+    ap.add_argument("parameter_file")
+    ap.add_argument("--cell", type=float, nargs="+", required=True, metavar="D", help="cell size: DX, or DX DY DZ")
+    ap.add_argument("--bounds", type=float, nargs=6, metavar=("x0", "x1", "y0", "y1", "z0", "z1"))
+    ap.add_argument("--structure", metavar="DIR", help="directory of uniform_structure.stat and station_corrections.stat")
+    ap.add_argument("--windows", metavar="FILE", help="window ids in the first column (default selected_win.dat)")
+    ap.add_argument("--flat-prior", action="store_true", help="no prior on the position")
+    ap.add_argument("--volume-of", type=int, metavar="WIN", help="also write this window's log posterior of every cell")
+    args = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    if len(args.cell) not in (1, 3):
+        ap.error("--cell takes DX, or DX DY DZ")
+    cell = args.cell * 3 if len(args.cell) == 1 else args.cell
+    par = Param(args.parameter_file)
+    work = os.path.dirname(os.path.abspath(args.parameter_file))
+    device = int(os.environ.get("HTM_DEVICE", "0"))
+    vs, qs, t_corr, a_corr = read_structure(args.structure if args.structure else work, par.stations)
+    win_id = read_windows(args.windows if args.windows else os.path.join(work, "selected_win.dat"))
+    if not win_id:
+        raise SystemExit("ERROR: no window to locate")
+    grid = make_grid(args.bounds if args.bounds else default_bounds(par), cell)
+
+    def run(ids, volume):
+        obs = ObsData(ids, par.n_stations, par.sta_x, par.sta_y, directory=work)
+        fwd = Forward(par.n_stations, len(ids), par.sta_x, par.sta_y, par.sta_z, obs, use_amp=par.get_use_amp(), use_time=par.get_use_time(),
+                      device=device)
+        try:
+            return locate(fwd, t_corr, vs, a_corr, qs, grid, prior=None if args.flat_prior else step5_prior(par, obs), volume=volume)
+        finally:
+            fwd.close()
+
+    res = run(win_id, False)
+    marg = np.concatenate([res["marg_x"], res["marg_y"], res["marg_z"]], axis=1)
+    with open(os.path.join(work, "hypo_grid.stat"), "w") as fh:
+        fh.write(stat_text(win_id, marginal_quantiles(marg, grid)))
+    with open(os.path.join(work, "hypo_grid.best.dat"), "w") as fh:
+        fh.write(best_text(win_id, res, grid))
+    if args.volume_of is not None:
+        if args.volume_of not in win_id:
+            raise SystemExit(f"ERROR: --volume-of {args.volume_of} is not among the windows")
+        one = run([args.volume_of], True)
+        with open(os.path.join(work, "hypo_grid.%d.vol.dat" % args.volume_of), "w") as fh:
+            fh.write(volume_text(one["vol"][0], grid))
+    sys.stdout.write(summary_text(res, grid))
+
+
+if __name__ == "__main__":
+    main()

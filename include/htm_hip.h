@@ -128,6 +128,31 @@ int htm_forward_time_full_batch_dev(htm_forward *h, int n_models, const double *
                                     const double *d_qs, double *d_log_likelihood, int reps,
                                     double *avg_us);
 
+/* Location posteriors on a grid under a FIXED structure.  With t_corr, vs, a_corr, qs fixed the
+ * log-likelihood of :268-303 is a sum of independent per-event terms; the term l of every event of the handle is taken at
+ * every cell centre of grid9 = {x0, dx, nx, y0, dy, ny, z0, dz, nz} (limits of htm_hypo_density, and nx ny nz <= 2^31 - 1).
+ * The centre of cell i of an axis {v0, dv, n} is v0 + (i + 0.5) * dv, one multiplication then one addition, unfused; the
+ * linear index of a cell is ix + nx (iy + ny iz).  The handle's stations, observations, use_time / use_amp and missing-data
+ * rule are used as they stand, always through its fp64 arrays (whatever htm_forward_set_precision says).  t_corr, a_corr
+ * [n_sta], host pointers.  prior5 [n_events][5] = {mu_x, mu_y, w_xy, z0, w_z} or NULL (flat prior): the log prior of a cell is
+ * the sum of the normalised Gaussian log densities N(mu_x, w_xy), N(mu_y, w_xy) in x and y and of the normalised depth prior
+ * of src/cls_model.f90:178-185, log(z - z0) - 2 log w_z - (z - z0)^2 / (2 w_z^2) for z > z0 and -inf otherwise.  The log
+ * posterior of a cell is lp = l + log prior; a cell whose lp is NaN or -inf is EXCLUDED from everything below (a centre on a
+ * station gives log 0 in the amplitude term, as in the reference).
+ * loc [n_events][16] = the best cell's linear index (ties: the lowest; -1 when every cell is excluded, and then the other 15
+ * are NaN), its centre x, y, z, lp there, l there, log(sum exp(lp) dx dy dz), the posterior mean x, y, z and the covariance
+ * xx, xy, xz, yy, yz, zz under the weights exp(lp - lp_best) of the included cells.  marg [n_events][nx + ny + nz] or NULL: the
+ * three axis marginals of those weights, each summing to 1 (NaN for an event without an included cell).  Sums of weights, the
+ * log evidence, the mean (against sum_i m_i |x_i|) and the variances are good to 1e-12 relative; a mixed moment c_ij to
+ * 1e-12 sd_i sd_j + 8 epsilon (X_i sd_j + X_j sd_i), X the largest |coordinate| of the axis (it is formed from row sums).  vol
+ * [n_events][nz][ny][nx] or NULL: every cell's lp as computed, NaN and -inf kept.
+ * NULL handle or output, vs or qs not finite or <= 0, a bad grid, w_xy or w_z <= 0: HTM_EINVAL before any device call.
+ * Synchronous.  Every sum has a fixed order: two calls give the same bits.  The events go to the device in batches so that no
+ * launch passes 2^32 - 1 work-items and the workspace, the device copy of vol included, stays under HTM_LOCATE_MB MiB
+ * (environment, default 1024; one event at the least); the result does not depend on it. */
+int htm_forward_locate(htm_forward *h, const double *t_corr, double vs, const double *a_corr, double qs,
+                       const double *grid9, const double *prior5, double *loc, double *marg, double *vol);
+
 /* ------------------------------------------------------------------------------------------------
  * Device-resident chains: `type mcmc` x n_chains inside `type parallel`
  *                          reference: src/cls_mcmc.f90, src/cls_parallel.f90, src/hypo_tremor_mcmc.f90
