@@ -46,6 +46,7 @@ from . import _lib
 from ._lib import check
 from .correlate import nint
 from .param import Param
+from .run_files import device_from_env
 
 DEFAULT_CONVERT_MB = 512
 BAND_HZ = (1.0, 3.0, 8.0, 10.0)                 # src/cls_convertor.f90:23-26
@@ -298,7 +299,7 @@ def main(argv=None):
         raise SystemExit("USAGE: hypo_tremor_convert [parameter file]")
     para = Param(argv[0], verb=True, from_where="convert")
     stations = plan(para)
-    device = int(os.environ.get("HTM_DEVICE", "0"))
+    device = device_from_env()
     for st in stations:
         print(f" {st.name}: N= {st.n_total} n= {st.c.n} n_fac= {st.c.n_fac} segments= "
               f"{last_segment(st.n_total, st.c.n) + 1}", flush=True)

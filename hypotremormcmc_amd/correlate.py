@@ -33,6 +33,7 @@ import numpy as np
 from . import _lib
 from ._lib import check
 from .param import Param
+from .run_files import device_from_env
 
 DEFAULT_XCORR_MB = 512
 
@@ -186,7 +187,7 @@ def main(argv=None):
         for s1, s2 in prs:
             open(f"{s1}.{s2}.corr", "wb").close(); open(f"{s1}.{s2}.max_corr", "wb").close()
         return
-    env = Envelopes(amps, device=int(os.environ.get("HTM_DEVICE", "0")))
+    env = Envelopes(amps, device=device_from_env())
     b = batch_pairs(n_win, n)
     for p0 in range(0, len(prs), b):
         nb = min(b, len(prs) - p0)

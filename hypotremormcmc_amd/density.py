@@ -24,12 +24,11 @@ import sys
 import numpy as np
 
 from . import _lib
-from .param import Param
-from .statistics import quantiles, read_sample_file, remove_double_counts, sample_matrix
+from .run_files import Step5Run
+from .statistics import INT_MAX, as_printed, hypo_rows, quantiles, remove_double_counts, sample_matrix
 
 MAX_CELLS = 4096          # per axis: kDensMaxCells of csrc/htm_density.hpp
 LDS_MAX_CELLS = 8192      # nx ny + nx nz + ny nz of a grid the LDS path takes: kDensLdsCells (tests/test_density.py keeps them equal)
-INT_MAX = 2 ** 31 - 1
 MAPS = ("xy", "xz", "yz", "vol")
 # the axes of a map, fastest first
 AXES = {"xy": (0, 1), "xz": (0, 2), "yz": (1, 2), "vol": (0, 1, 2)}
@@ -158,9 +157,7 @@ def removed_layer(layer, keep):
 
 def kept_windows(win_id, hypo, device: int = 0):
     """the windows that hypo.stat.removed keeps: statistics' medians and intervals, rounded as hypo.stat prints them"""
-    h = quantiles(hypo, None, device)
-    rows = [[float("%13.6f" % h[3 * i + c][j]) for c in range(3) for j in (1, 0, 2)] for i in range(len(win_id))]
-    return remove_double_counts([int(w) for w in win_id], rows)
+    return remove_double_counts([int(w) for w in win_id], as_printed(hypo_rows(quantiles(hypo, None, device))))
 
 
 HEADERS = {nm: "# layer, cell " + " ".join("i" + "xyz"[a] for a in AXES[nm]) + ", centre " + " ".join("xyz"[a] for a in AXES[nm])
@@ -199,36 +196,41 @@ def default_bounds(par):
     return [par.sta_x.min() - wxy, par.sta_x.max() + wxy, par.sta_y.min() - wxy, par.sta_y.max() + wxy, z0, z0 + 5.0 * wz]
 
 
+def add_grid_arguments(ap):
+    ap.add_argument("--cell", type=float, nargs="+", required=True, metavar="D", help="cell size: DX, or DX DY DZ")
+    ap.add_argument("--bounds", type=float, nargs=6, metavar=("x0", "x1", "y0", "y1", "z0", "z1"))
+
+
+def grid_from_args(ap, args, par):
+    """the grid of --cell and --bounds (default: default_bounds)"""
+    if len(args.cell) not in (1, 3):
+        ap.error("--cell takes DX, or DX DY DZ")
+    return make_grid(args.bounds if args.bounds else default_bounds(par), args.cell * 3 if len(args.cell) == 1 else args.cell)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m hypotremormcmc_amd.density", description=__doc__.split("\n\n")[0])
     ap.add_argument("parameter_file")
-    ap.add_argument("--cell", type=float, nargs="+", required=True, metavar="D", help="cell size: DX, or DX DY DZ")
-    ap.add_argument("--bounds", type=float, nargs=6, metavar=("x0", "x1", "y0", "y1", "z0", "z1"))
+    add_grid_arguments(ap)
     ap.add_argument("--time-bins", type=int, default=1, help="layers of equal spans of window ids")
     ap.add_argument("--removed", action="store_true", help="only the windows that hypo.stat.removed keeps")
     ap.add_argument("--volume", action="store_true", help="also the 3-D counts")
     ap.add_argument("--level", type=float, nargs="+", default=[0.68, 0.95], help="shares of a layer's mass for the regions")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
-    if len(args.cell) not in (1, 3):
-        ap.error("--cell takes DX, or DX DY DZ")
     if any(not 0.0 < v <= 1.0 for v in args.level):
         ap.error("--level must lie in (0, 1]")
     if args.time_bins < 1:
         ap.error("--time-bins must be at least 1")
-    cell = args.cell * 3 if len(args.cell) == 1 else args.cell
-    par = Param(args.parameter_file)
-    work = os.path.dirname(os.path.abspath(args.parameter_file))
-    device = int(os.environ.get("HTM_DEVICE", "0"))
-    win_id = [int(ln.split()[0]) for ln in open(os.path.join(work, "selected_win.dat")) if ln.strip()]
-    hypo = np.concatenate([read_sample_file(os.path.join(work, "hypo.%02d.out" % r), 3 * len(win_id))[1] for r in range(par.get_n_procs())], axis=0)
-    grid = make_grid(args.bounds if args.bounds else default_bounds(par), cell)
-    layer = time_layers(win_id, args.time_bins)
+    run = Step5Run.open(args.parameter_file)
+    grid = grid_from_args(ap, args, run.par)
+    hypo = run.samples(("hypo",))[1]["hypo"]
+    layer = time_layers(run.win_id, args.time_bins)
     if args.removed:
-        layer = removed_layer(layer, kept_windows(win_id, hypo, device))
-    res = density(hypo, grid, layer=layer, n_layer=args.time_bins, volume=args.volume, device=device)
+        layer = removed_layer(layer, kept_windows(run.win_id, hypo, run.device))
+    res = density(hypo, grid, layer=layer, n_layer=args.time_bins, volume=args.volume, device=run.device)
     for nm in MAPS:
         if res[nm] is not None:
-            with open(os.path.join(work, "tremor_density.%s.dat" % nm), "w") as fh:
+            with open(os.path.join(run.work, "tremor_density.%s.dat" % nm), "w") as fh:
                 fh.write(map_text(nm, res[nm], grid, len(hypo), args.level))
     sys.stdout.write(summary_text(res["tally"]))
 

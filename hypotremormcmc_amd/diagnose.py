@@ -24,8 +24,8 @@ import sys
 import numpy as np
 
 from . import _lib
-from .param import Param
-from .statistics import read_sample_file, sample_matrix
+from .run_files import Step5Run, field
+from .statistics import sample_matrix
 
 RANK_STAT_HEADER = "# parameter, R-hat (larger of the next two), rank-normalised R-hat, folded R-hat, bulk-ESS, tail-ESS"
 STAT_HEADER = "# parameter, R-hat (split), ESS, tau, lag of the first negative pair sum (-1: none up to the last lag)"
@@ -72,7 +72,7 @@ def diagnose_rank(samples, n_seq: int, max_lag: int = 1000, device: int = 0):
 def sequences_by_iteration(iters, values, k: int):
     """The sequence-major sample matrix `diagnose` takes, from the records of all ranks' sample files.
 
-    iters [n_rec], values [n_rec][n_par]: what `statistics.read_sample_file` returns per rank, stacked in rank order.
+    iters [n_rec], values [n_rec][n_par]: what `run_files.Step5Run.samples` returns.
     The records are stable-sorted by iteration; every recorded iteration must hold exactly k = n_procs * n_cool
     records (the swaps conserve the multiset of temperatures, so this holds over all ranks although the T = 1 role
     moves between them).  Sequence j is the j-th record of every iteration, so a sequence is a T = 1 *slot*, not one
@@ -103,11 +103,9 @@ def parameter_names(station_names, win_id):
 def stat_text(names, out) -> str:
     """the text of convergence.stat for out [n_par][4]; a row of NaN (a constant column) is written as NaN"""
     lines = [STAT_HEADER]
-    for name, (rhat, ess, tau, lags) in zip(names, np.asarray(out, dtype=np.float64)):
-        if np.isnan(rhat):
-            lines.append("%-24s" % name + "%13s" % "NaN" * 3 + "%7s" % "NaN")
-        else:
-            lines.append("%-24s" % name + "%13.6f%13.6f%13.6f" % (rhat, ess, tau) + "%7d" % int(lags))
+    for name, row in zip(names, np.asarray(out, dtype=np.float64)):
+        rhat, ess, tau, lags = row if not np.isnan(row[0]) else [np.nan] * 4
+        lines.append("%-24s" % name + field(rhat, 13) + field(ess, 13) + field(tau, 13) + field(lags, 7, 0))
     return "\n".join(lines) + "\n"
 
 
@@ -130,7 +128,7 @@ def rank_stat_text(names, out) -> str:
     lines = [RANK_STAT_HEADER]
     for name, (rb, rf, eb, et) in zip(names, np.asarray(out, dtype=np.float64)):
         rmax = np.fmax(rb, rf)          # of the two that are defined: |x - med| of a two-valued column can be constant
-        lines.append("%-24s" % name + "".join("%13s" % "NaN" if np.isnan(v) else "%13.6f" % v for v in (rmax, rb, rf, eb, et)))
+        lines.append("%-24s" % name + "".join(field(v, 13) for v in (rmax, rb, rf, eb, et)))
     return "\n".join(lines) + "\n"
 
 
@@ -151,28 +149,6 @@ def rank_summary_text(names, out, rhat_limit: float) -> str:
             f"rank-normalised R-hat > {rhat_limit:g}: {int(np.sum(rmax[live] > rhat_limit))} parameters\n")
 
 
-def gather_sequences(work_dir, n_procs, n_sta, n_events, n_burn, k):
-    """all ranks' sample files and the recorded part of their log-likelihood traces as one sequence-major matrix:
-    columns vs, qs, t_corr, a_corr, hypo, log-likelihood"""
-    its, vals = [], []
-    for r in range(n_procs):
-        cols, it_r = [], None
-        for nm, nv in (("vs", 1), ("qs", 1), ("t_corr", n_sta), ("a_corr", n_sta), ("hypo", 3 * n_events)):
-            it, v = read_sample_file(os.path.join(work_dir, "%s.%02d.out" % (nm, r)), nv)
-            if it_r is not None and not np.array_equal(it, it_r):
-                raise ValueError(f"{nm}.{r:02d}.out records other iterations than vs.{r:02d}.out")
-            it_r = it
-            cols.append(v)
-        it, v = read_sample_file(os.path.join(work_dir, "likelihood%02d.out" % r), 1)
-        keep = it > n_burn               # the trace also covers the burn-in (src/hypo_tremor_mcmc.f90:270-280)
-        if not np.array_equal(it[keep], it_r):
-            raise ValueError(f"likelihood{r:02d}.out records other iterations after the burn-in than vs.{r:02d}.out")
-        cols.append(v[keep])
-        its.append(it_r)
-        vals.append(np.concatenate(cols, axis=1))
-    return sequences_by_iteration(np.concatenate(its), np.concatenate(vals, axis=0), k)
-
-
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m hypotremormcmc_amd.diagnose", description=__doc__.split("\n\n")[0])
     ap.add_argument("parameter_file")
@@ -180,18 +156,18 @@ def main(argv=None):
     ap.add_argument("--rhat", type=float, default=1.01, help="R-hat above which a parameter is counted in the summary")
     ap.add_argument("--rank", action="store_true", help="also write convergence_rank.stat: rank-normalised R-hat, bulk- and tail-ESS")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
-    par = Param(args.parameter_file)
-    work = os.path.dirname(os.path.abspath(args.parameter_file))
-    win_id = [int(ln.split()[0]) for ln in open(os.path.join(work, "selected_win.dat")) if ln.strip()]
-    k = par.get_n_procs() * par.get_n_cool()
-    x = gather_sequences(work, par.get_n_procs(), par.n_stations, len(win_id), par.get_n_burn(), k)
-    out = diagnose(x, k, max_lag=args.max_lag, device=int(os.environ.get("HTM_DEVICE", "0")))
-    names = parameter_names(par.stations, win_id)
+    run = Step5Run.open(args.parameter_file)
+    work, k = run.work, run.n_procs * run.par.get_n_cool()
+    # one sequence-major matrix: columns vs, qs, t_corr, a_corr, hypo, log-likelihood
+    iters, s = run.samples(("vs", "qs", "t_corr", "a_corr", "hypo"), likelihood=True)
+    x = sequences_by_iteration(iters, np.concatenate(list(s.values()), axis=1), k)
+    out = diagnose(x, k, max_lag=args.max_lag, device=run.device)
+    names = parameter_names(run.par.stations, run.win_id)
     with open(os.path.join(work, "convergence.stat"), "w") as fh:
         fh.write(stat_text(names, out))
     sys.stdout.write(summary_text(names, out, args.rhat))
     if args.rank:
-        rk = diagnose_rank(x, k, max_lag=args.max_lag, device=int(os.environ.get("HTM_DEVICE", "0")))
+        rk = diagnose_rank(x, k, max_lag=args.max_lag, device=run.device)
         with open(os.path.join(work, "convergence_rank.stat"), "w") as fh:
             fh.write(rank_stat_text(names, rk))
         sys.stdout.write(rank_summary_text(names, rk, args.rhat))

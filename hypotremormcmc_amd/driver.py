@@ -12,10 +12,7 @@ from __future__ import annotations
 
 import math
 import os
-import struct
 import sys
-
-import numpy as np
 
 from .chains import LABELS, ChainSet
 from .forward import Forward
@@ -23,6 +20,7 @@ from .mod_random import Xorshift128
 from .model import Model
 from .obs_data import ObsData
 from .param import Param
+from .run_files import read_window_ids, sample_byte_order, write_sample_file  # noqa: F401 (sample_byte_order: re-exported)
 
 EPS = sys.float_info.epsilon  # epsilon(1.d0)
 SEEDS = (5551111, 453222, 4444431, 6765)  # src/hypo_tremor_mcmc.f90:72
@@ -44,13 +42,7 @@ def _get(params, key):
 def read_selected_win(path="selected_win.dat"):
     if not os.path.exists(path):
         raise SystemExit("cannot open selected_win.dat")
-    ids = []
-    with open(path) as f:
-        for line in f:
-            tok = line.split()
-            if len(tok) >= 2:
-                ids.append(int(tok[0]))
-    return ids
+    return read_window_ids(path)
 
 
 def build_initial_models(params, n_sta, n_events, x_mu, y_mu, rank):
@@ -127,30 +119,12 @@ def build_rank(params, sta_x, sta_y, sta_z, obs, rank, n_procs=None, device=0, f
 # ---------------------------------------------------------------------------------------------------
 # output files, src/hypo_tremor_mcmc.f90:216-233,:270-280 (stream access, unformatted: packed records)
 # ---------------------------------------------------------------------------------------------------
-def sample_byte_order(endian=None):
-    """'<' or '>' for the unformatted output files.  The reference's stock gfortran Makefile builds with
-    -fconvert=big-endian (src/Makefile:7-9), so a step 6 built that way expects big-endian sample files; any other
-    build reads native little-endian.  HTM_SAMPLE_ENDIAN=big|little (default little) picks the writer's order."""
-    e = (endian or os.environ.get("HTM_SAMPLE_ENDIAN") or "little").strip().lower()
-    if e in ("big", "big_endian", "big-endian", ">"):
-        return ">"
-    if e in ("little", "little_endian", "little-endian", "native", "<"):
-        return "<"
-    raise ValueError("HTM_SAMPLE_ENDIAN must be big or little, got %r" % e)
-
-
 def write_outputs(directory, rank, cs: ChainSet, endian=None):
-    bo = sample_byte_order(endian)
     it, _, lk = cs.likelihood_trace()
-    with open(os.path.join(directory, "likelihood%02d.out" % rank), "wb") as f:
-        for i, v in zip(it.tolist(), lk.tolist()):
-            f.write(struct.pack(bo + "id", i, v))
+    write_sample_file(os.path.join(directory, "likelihood%02d.out" % rank), it, lk, endian)
     smp = cs.samples()
-    for name, key in (("vs", "vs"), ("qs", "qs"), ("t_corr", "t_corr"), ("a_corr", "a_corr"), ("hypo", "hypo")):
-        with open(os.path.join(directory, "%s.%02d.out" % (name, rank)), "wb") as f:
-            for k in range(len(smp["iter"])):
-                f.write(struct.pack(bo + "i", int(smp["iter"][k])))
-                f.write(np.atleast_1d(smp[key][k]).astype(bo + "f8").tobytes())
+    for name in ("vs", "qs", "t_corr", "a_corr", "hypo"):
+        write_sample_file(os.path.join(directory, "%s.%02d.out" % (name, rank)), smp["iter"], smp[name], endian)
 
 
 def write_proposal_count(path, n_propose, n_accept):

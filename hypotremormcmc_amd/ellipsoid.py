@@ -22,8 +22,8 @@ import sys
 import numpy as np
 
 from . import _lib
-from .param import Param
-from .statistics import read_sample_file, sample_matrix
+from .run_files import Step5Run, field
+from .statistics import sample_matrix
 
 N_OUT = 22
 MAX_PIVOTS = 4
@@ -142,7 +142,7 @@ def stat_text(win_id, rows) -> str:
     """the text of hypo_ellipsoid.stat; NaN is written as NaN in the field's width"""
     lines = [STAT_HEADER]
     for w, row in zip(win_id, np.asarray(rows, dtype=np.float64)):
-        lines.append("%8d" % w + "".join("%*s" % (wd, "NaN") if np.isnan(v) else "%*.*f" % (wd, dc, v) for (wd, dc), v in zip(_FIELDS, row)))
+        lines.append("%8d" % w + "".join(field(v, wd, dc) for (wd, dc), v in zip(_FIELDS, row)))
     return "\n".join(lines) + "\n"
 
 
@@ -160,22 +160,6 @@ def summary_text(win_id, rows) -> str:
             f"median |corr(z, vs)|  {med}\n")
 
 
-def gather_samples(work_dir, n_procs, n_events):
-    """all ranks' hypo, vs and qs sample files stacked in rank order: hypo [n_mod][3 n_events], pivots [n_mod][2]"""
-    hyp, piv = [], []
-    for r in range(n_procs):
-        it_r, cols = None, []
-        for nm, nv in (("hypo", 3 * n_events), ("vs", 1), ("qs", 1)):
-            it, v = read_sample_file(os.path.join(work_dir, "%s.%02d.out" % (nm, r)), nv)
-            if it_r is not None and not np.array_equal(it, it_r):
-                raise ValueError(f"{nm}.{r:02d}.out records other iterations than hypo.{r:02d}.out")
-            it_r = it
-            cols.append(v)
-        hyp.append(cols[0])
-        piv.append(np.concatenate(cols[1:], axis=1))
-    return np.concatenate(hyp, axis=0), np.concatenate(piv, axis=0)
-
-
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m hypotremormcmc_amd.ellipsoid", description=__doc__.split("\n\n")[0])
     ap.add_argument("parameter_file")
@@ -183,15 +167,13 @@ def main(argv=None):
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
     if not 0.0 < args.level < 1.0:
         ap.error("--level must lie between 0 and 1")
-    par = Param(args.parameter_file)
-    work = os.path.dirname(os.path.abspath(args.parameter_file))
-    win_id = [int(ln.split()[0]) for ln in open(os.path.join(work, "selected_win.dat")) if ln.strip()]
-    hypo, piv = gather_samples(work, par.get_n_procs(), len(win_id))
-    res = ellipsoid(hypo, piv, level=args.level, device=int(os.environ.get("HTM_DEVICE", "0")))
+    run = Step5Run.open(args.parameter_file)
+    _, s = run.samples(("hypo", "vs", "qs"))
+    res = ellipsoid(s["hypo"], np.hstack([s["vs"], s["qs"]]), level=args.level, device=run.device)
     rows = stat_rows(res, args.level)
-    with open(os.path.join(work, "hypo_ellipsoid.stat"), "w") as fh:
-        fh.write(stat_text(win_id, rows))
-    sys.stdout.write(summary_text(win_id, rows))
+    with open(os.path.join(run.work, "hypo_ellipsoid.stat"), "w") as fh:
+        fh.write(stat_text(run.win_id, rows))
+    sys.stdout.write(summary_text(run.win_id, rows))
 
 
 if __name__ == "__main__":

@@ -25,13 +25,12 @@ import sys
 import numpy as np
 
 from . import _lib
-from .density import default_bounds, grid9, grid_counts, make_grid
+from .density import add_grid_arguments, grid9, grid_counts, grid_from_args
 from .forward import Forward
 from .obs_data import ObsData
-from .param import Param
-from .statistics import HYPO_HEADER
+from .run_files import Step5Run, field
+from .statistics import HYPO_HEADER, INT_MAX
 
-INT_MAX = 2 ** 31 - 1
 BEST_HEADER = ("# window ID, best cell's centre x y z, log posterior there, log-likelihood term there, log evidence, "
                "posterior mean x y z, 1: the best cell lies on a face of the box")
 
@@ -142,16 +141,12 @@ def step5_prior(par, obs):
     return p
 
 
-def _field(v, width=13):
-    return "%*s" % (width, "NaN") if np.isnan(v) else "%*.6f" % (width, v)
-
-
 def stat_text(win_id, quant) -> str:
     """the text of hypo_grid.stat from quant [E][3][3] = 2.5 %, 50 %, 97.5 % of x, y, z: hypo.stat's header and layout (median,
     2.5 %, 97.5 % per axis); NaN is written as NaN in the field's width"""
     lines = [HYPO_HEADER]
     for w, q in zip(win_id, np.asarray(quant, dtype=np.float64)):
-        lines.append("%9d" % w + "".join(_field(q[a][j]) for a in range(3) for j in (1, 0, 2)))
+        lines.append("%9d" % w + "".join(field(q[a][j], 13) for a in range(3) for j in (1, 0, 2)))
     return "\n".join(lines) + "\n"
 
 
@@ -169,7 +164,7 @@ def best_text(win_id, res, grid) -> str:
     lines = [BEST_HEADER]
     for i, w in enumerate(win_id):
         vals = list(res["best"][i]) + [res["lp"][i], res["ell"][i], res["log_evidence"][i]] + list(res["mean"][i])
-        lines.append("%9d" % w + "".join(_field(v, 15) for v in vals) + "%3d" % int(flag[i]))
+        lines.append("%9d" % w + "".join(field(v, 15) for v in vals) + "%3d" % int(flag[i]))
     return "\n".join(lines) + "\n"
 
 
@@ -193,31 +188,21 @@ def summary_text(res, grid) -> str:
             f"{int((res['index'] < 0).sum())} without an included cell\n")
 
 
-def read_windows(path):
-    return [int(ln.split()[0]) for ln in open(path) if ln.strip() and not ln.lstrip().startswith("#")]
-
-
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m hypotremormcmc_amd.locate", description=__doc__.split("\n\n")[0])
     ap.add_argument("parameter_file")
-    ap.add_argument("--cell", type=float, nargs="+", required=True, metavar="D", help="cell size: DX, or DX DY DZ")
-    ap.add_argument("--bounds", type=float, nargs=6, metavar=("x0", "x1", "y0", "y1", "z0", "z1"))
+    add_grid_arguments(ap)
     ap.add_argument("--structure", metavar="DIR", help="directory of uniform_structure.stat and station_corrections.stat")
     ap.add_argument("--windows", metavar="FILE", help="window ids in the first column (default selected_win.dat)")
     ap.add_argument("--flat-prior", action="store_true", help="no prior on the position")
     ap.add_argument("--volume-of", type=int, metavar="WIN", help="also write this window's log posterior of every cell")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
-    if len(args.cell) not in (1, 3):
-        ap.error("--cell takes DX, or DX DY DZ")
-    cell = args.cell * 3 if len(args.cell) == 1 else args.cell
-    par = Param(args.parameter_file)
-    work = os.path.dirname(os.path.abspath(args.parameter_file))
-    device = int(os.environ.get("HTM_DEVICE", "0"))
+    r5 = Step5Run.open(args.parameter_file, windows=args.windows)
+    par, work, device, win_id = r5.par, r5.work, r5.device, r5.win_id
+    grid = grid_from_args(ap, args, par)
     vs, qs, t_corr, a_corr = read_structure(args.structure if args.structure else work, par.stations)
-    win_id = read_windows(args.windows if args.windows else os.path.join(work, "selected_win.dat"))
     if not win_id:
         raise SystemExit("ERROR: no window to locate")
-    grid = make_grid(args.bounds if args.bounds else default_bounds(par), cell)
 
     def run(ids, volume):
         obs = ObsData(ids, par.n_stations, par.sta_x, par.sta_y, directory=work)

@@ -37,6 +37,7 @@ import numpy as np
 from . import _lib, correlate as corr
 from ._lib import check, ptr
 from .param import Param
+from .run_files import device_from_env
 
 INT_MAX = 2 ** 31 - 1      # htm_quantiles_dev takes int ranks and counts rows in int
 
@@ -194,7 +195,7 @@ def main(argv=None):
     para = Param(args[0], verb=True, from_where="measure")
     para.require("t_win_corr", "t_step_corr")
     g = para.values
-    device = int(os.environ.get("HTM_DEVICE", "0"))
+    device = device_from_env()
     t_win, t_step = g["t_win_corr"], g["t_step_corr"]
     dt = common_dt(para.stations)
     n, n_step = corr.nint(t_win / dt), corr.nint(t_step / dt)

@@ -11,7 +11,6 @@ windows with vs_min <= vs <= vs_max and b_min <= b <= b_max, :126-131).  The reg
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 import sys
 
@@ -21,6 +20,7 @@ from . import _lib
 from ._lib import check, ptr
 from .obs_data import ObsData
 from .param import Param
+from .run_files import device_from_env
 
 
 def regress(sta_x, sta_y, sta_z, z_guess, t, t_err, a, a_err, device=0):
@@ -71,7 +71,7 @@ def main(argv=None):
     obs = ObsData(win_id, para.n_stations, para.sta_x, para.sta_y, verb=False)
     g = para.values
     reg = regress(para.sta_x, para.sta_y, para.sta_z, g["z_guess"], obs.get_t_obs(), obs.get_t_stdv(), obs.get_a_obs(),
-                  obs.get_a_stdv(), device=int(os.environ.get("HTM_DEVICE", "0")))
+                  obs.get_a_stdv(), device=device_from_env())
     keep = select(reg, g["vs_min"], g["vs_max"], g["b_min"], g["b_max"])
     with open("regress.dat", "w") as f:
         for i, r in zip(win_id, reg):

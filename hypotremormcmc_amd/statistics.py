@@ -21,7 +21,7 @@ import sys
 import numpy as np
 
 from . import _lib
-from .param import Param
+from .run_files import Step5Run, read_sample_file  # noqa: F401 (read_sample_file: re-exported)
 
 INT_MAX = 2 ** 31 - 1      # htm_quantiles takes int ranks and counts rows in int
 
@@ -81,15 +81,16 @@ def quantiles(samples: np.ndarray, n_mod: int | None = None, device: int = 0) ->
     return out          # columns: il (2.5 %), im (50 %), iu (97.5 %)
 
 
-def read_sample_file(path: str, n_val: int, endian=None):
-    """stream-unformatted records [int32 iteration][n_val float64] (src/hypo_tremor_mcmc.f90:216-233);
-    byte order: HTM_SAMPLE_ENDIAN=big|little (driver.sample_byte_order; big = written by a stock-gfortran build of
-    the reference, src/Makefile:7-9)"""
-    from .driver import sample_byte_order
-    bo = sample_byte_order(endian)
-    rec = np.dtype([("it", bo + "i4"), ("v", bo + "f8", (n_val,))])
-    a = np.fromfile(path, dtype=rec)
-    return a["it"].astype(np.int32), a["v"].reshape(len(a), n_val).astype(np.float64)
+def hypo_rows(h):
+    """hypo.stat's rows [n_win][9] = (median, 2.5 %, 97.5 %) of x, y, z from `quantiles`' [3 n_win][3] = (2.5 %, median, 97.5 %)
+    of the columns x, y, z interleaved per window"""
+    return [[h[3 * i + c][j] for c in range(3) for j in (1, 0, 2)] for i in range(len(h) // 3)]
+
+
+def as_printed(rows):
+    """the rows as hypo.stat's F13.6 prints them: the reference re-reads the text it just wrote before removing double counts
+    (src/cls_statistics.f90:136-142)"""
+    return [[float("%13.6f" % x) for x in r] for r in rows]
 
 
 def remove_double_counts(win_id, q):
@@ -155,18 +156,9 @@ class Statistics:
                          "".join("%13.6f" % x for x in (t[k][1], t[k][0], t[k][2], a[k][1], a[k][0], a[k][2])) + "\n")
 
     def estimate_hypo(self, hypo_samples, out_dir="."):
-        h = self._q(hypo_samples)                               # [3E][3], x y z interleaved per window
-        rows = []
-        for i in range(len(self.win_id)):
-            r = []
-            for c in range(3):
-                lo, med, hi = h[3 * i + c]
-                r += [med, lo, hi]
-            rows.append(r)
+        rows = hypo_rows(self._q(hypo_samples))
         self._write_hypo(os.path.join(out_dir, "hypo.stat"), range(len(rows)), rows)
-        # the reference re-reads the F13.6 text it just wrote before removing double counts (:136-142)
-        rounded = [[float("%13.6f" % x) for x in r] for r in rows]
-        keep = remove_double_counts(self.win_id, rounded)
+        keep = remove_double_counts(self.win_id, as_printed(rows))
         self._write_hypo(os.path.join(out_dir, "hypo.stat.removed"), keep, rows)
 
     def _write_hypo(self, path, idx, rows):
@@ -176,28 +168,17 @@ class Statistics:
                 fh.write("%9d" % self.win_id[i] + "".join("%13.6f" % x for x in rows[i]) + "\n")
 
 
-def gather_output_files(work_dir, n_procs, n_sta, n_events):
-    """every rank's vs/qs/t_corr/a_corr/hypo sample files, stacked in rank order (the reference's gather)"""
-    out = {}
-    for nm, nv in (("vs", 1), ("qs", 1), ("t_corr", n_sta), ("a_corr", n_sta), ("hypo", 3 * n_events)):
-        parts = [read_sample_file(os.path.join(work_dir, "%s.%02d.out" % (nm, r)), nv)[1] for r in range(n_procs)]
-        out[nm] = np.concatenate(parts, axis=0)
-    return out
-
-
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) != 1:
         raise SystemExit("USAGE: python -m hypotremormcmc_amd.statistics [parameter file]")
-    par = Param(argv[0])
-    work = os.path.dirname(os.path.abspath(argv[0]))
-    win_id = [int(ln.split()[0]) for ln in open(os.path.join(work, "selected_win.dat")) if ln.strip()]
-    st = Statistics(par.get_n_procs(), par.get_n_iter(), par.get_n_burn(), par.get_n_interval(), par.get_n_cool(),
-                    par.stations, win_id)
-    s = gather_output_files(work, st.n_procs, par.n_stations, len(win_id))
-    st.estimate_vs_qs(s["vs"], s["qs"], work)
-    st.estimate_corr_factors(s["t_corr"], s["a_corr"], work)
-    st.estimate_hypo(s["hypo"], work)
+    run = Step5Run.open(argv[0])
+    par = run.par
+    st = Statistics(run.n_procs, par.get_n_iter(), par.get_n_burn(), par.get_n_interval(), par.get_n_cool(), par.stations, run.win_id, run.device)
+    _, s = run.samples(("vs", "qs", "t_corr", "a_corr", "hypo"))
+    st.estimate_vs_qs(s["vs"], s["qs"], run.work)
+    st.estimate_corr_factors(s["t_corr"], s["a_corr"], run.work)
+    st.estimate_hypo(s["hypo"], run.work)
 
 
 if __name__ == "__main__":

@@ -49,6 +49,25 @@ def with_missing(data):
     return data
 
 
+def write_run_dir(tmp_path, data, params, win_id, stations=None):
+    """the station file, param.in and selected_win.dat of a step-5 run of `data` in tmp_path; returns (the parameter file's
+    path, the station names)"""
+    stations = ["N.S%02d" % j for j in range(data.n_sta)] if stations is None else list(stations)
+    (tmp_path / "station_xy.list").write_text("".join(
+        "%s %.6f %.6f %.6f 1.0 1.0\n" % (s, x, y, z) for s, x, y, z in zip(stations, data.sta_x, data.sta_y, data.sta_z)))
+    (tmp_path / "selected_win.dat").write_text("".join("%d 0.0\n" % w for w in win_id))
+    (tmp_path / "param.in").write_text("".join("%s = %s\n" % kv for kv in dict(params, station_file="station_xy.list").items()))
+    return str(tmp_path / "param.in"), stations
+
+
+def write_fake_samples(tmp_path, rank, iters, values):
+    """NAME.RR.out of one rank for every name of values = {name: [n_rec][n_val]}, little-endian"""
+    from hypotremormcmc_amd.run_files import write_sample_file
+
+    for name, v in values.items():
+        write_sample_file(str(tmp_path / ("%s.%02d.out" % (name, rank))), iters, v, endian="little")
+
+
 def tf(v):
     return str(v).strip().upper().lstrip(".").startswith("T")
 

@@ -199,24 +199,3 @@ def test_horizontal_ellipse_angle():
     h = horizontal_ellipse(c(4.0, 1.0, -1e-300), 0.5)[0]
     assert 0.0 <= h[2] < 180.0
 
-
-def test_reader_refuses_mismatched_iteration_columns(tmp_path, monkeypatch):
-    from hypotremormcmc_amd import ellipsoid as el
-
-    monkeypatch.delenv("HTM_SAMPLE_ENDIAN", raising=False)
-    rng = np.random.default_rng(2)
-
-    def write(name, it, n_val):
-        a = np.zeros(len(it), dtype=np.dtype([("it", "<i4"), ("v", "<f8", (n_val,))]))
-        a["it"], a["v"] = it, rng.normal(size=(len(it), n_val))
-        a.tofile(str(tmp_path / name))
-        return a["v"].reshape(len(it), n_val)
-
-    it = np.arange(10, 60, 10)
-    parts = {(nm, r): write("%s.%02d.out" % (nm, r), it + r, nv) for r in range(2) for nm, nv in (("hypo", 6), ("vs", 1), ("qs", 1))}
-    hypo, piv = el.gather_samples(str(tmp_path), 2, 2)
-    assert np.array_equal(hypo, np.concatenate([parts["hypo", 0], parts["hypo", 1]]))
-    assert np.array_equal(piv, np.concatenate([np.hstack([parts["vs", 0], parts["qs", 0]]), np.hstack([parts["vs", 1], parts["qs", 1]])]))
-    write("qs.01.out", it + 2, 1)
-    with pytest.raises(ValueError, match=r"qs\.01\.out records other iterations than hypo\.01\.out"):
-        el.gather_samples(str(tmp_path), 2, 2)

@@ -10,7 +10,7 @@ import pytest
 
 from hypotremormcmc_amd import density as dn
 from tests import density_restatement as dr
-from tests.helpers import load_case
+from tests.helpers import load_case, write_fake_samples, write_run_dir
 
 pytestmark = pytest.mark.gpu
 
@@ -223,21 +223,19 @@ def test_program_writes_the_density_files(tmp_path, monkeypatch, capsys):
     and station files; `density.main` with three time bins, --removed, --volume and row batches of 31 rows (four of them): the
     files are what the restatement and the host helpers give for the samples read back"""
     _, data, params = load_case("fixedcorr")
-    params = dict(params, n_procs="2", station_file="station_xy.list")
+    params = dict(params, n_procs="2")
     n_ev, n_rows = data.n_events, 60
-    (tmp_path / "station_xy.list").write_text("".join(
-        "N.S%02d %.6f %.6f %.6f 1.0 1.0\n" % (j, x, y, z) for j, (x, y, z) in enumerate(zip(data.sta_x, data.sta_y, data.sta_z))))
-    (tmp_path / "param.in").write_text("".join("%s = %s\n" % kv for kv in params.items()))
+    # windows 0 and 1 (ids 10, 11) share a posterior: 11 is a double count; the others are apart.  Some samples leave the box.
+    win_id = [10, 11, 12, 20, 21, 30, 40][:n_ev] + list(range(50, 50 + max(0, n_ev - 7)))
+    param_file, _ = write_run_dir(tmp_path, data, params, win_id)
     from hypotremormcmc_amd.param import Param
 
-    par = Param(str(tmp_path / "param.in"))
+    par = Param(param_file)
     wxy, z0, wz = par.get_prior_width_xy(), par.get_prior_z(), par.get_prior_width_z()
     cell = [wxy / 2.0, wxy / 3.0, wz]
     bounds = [par.sta_x.min() - wxy, par.sta_x.max() + wxy, par.sta_y.min() - wxy, par.sta_y.max() + wxy, z0, z0 + 5.0 * wz]
     grid = [v for a in range(3) for v in (bounds[2 * a], cell[a], float(int(np.ceil((bounds[2 * a + 1] - bounds[2 * a]) / cell[a] - 1e-9))))]
     assert grid[8] == 5.0
-    # windows 0 and 1 (ids 10, 11) share a posterior: 11 is a double count; the others are apart.  Some samples leave the box.
-    win_id = [10, 11, 12, 20, 21, 30, 40][:n_ev] + list(range(50, 50 + max(0, n_ev - 7)))
     rng = np.random.default_rng(8)
     mid = np.array([0.5 * (bounds[0] + bounds[1]), 0.5 * (bounds[2] + bounds[3]), z0 + 2.5 * wz])
     centre = mid + rng.uniform(-1.0, 1.0, size=(n_ev, 3)) * [wxy, wxy, wz]
@@ -245,15 +243,11 @@ def test_program_writes_the_density_files(tmp_path, monkeypatch, capsys):
     centre[-1, 2] = z0 + 0.2 * wz                     # near the top of the box in depth: a share of it outside
     for r in range(2):
         hyp = (centre[None] + rng.normal(size=(n_rows, n_ev, 3)) * [0.4 * wxy, 0.4 * wxy, 0.4 * wz]).reshape(n_rows, 3 * n_ev)
-        for nm, v in (("hypo", hyp), ("vs", rng.normal(size=(n_rows, 1))), ("qs", rng.normal(size=(n_rows, 1)))):
-            a = np.zeros(n_rows, dtype=np.dtype([("it", "<i4"), ("v", "<f8", (v.shape[1],))]))
-            a["it"], a["v"] = 10 * np.arange(1, n_rows + 1), v
-            a.tofile(str(tmp_path / ("%s.%02d.out" % (nm, r))))
-    (tmp_path / "selected_win.dat").write_text("".join("%d 0.0\n" % w for w in win_id))
+        write_fake_samples(tmp_path, r, 10 * np.arange(1, n_rows + 1), {"hypo": hyp, "vs": rng.normal(size=(n_rows, 1)), "qs": rng.normal(size=(n_rows, 1))})
     _clean(monkeypatch)
     monkeypatch.delenv("HTM_SAMPLE_ENDIAN", raising=False)
     monkeypatch.setenv("HTM_DENSITY_MB", "%.6f" % (31.5 * 3 * n_ev * 8 / 1048576.0))
-    dn.main([str(tmp_path / "param.in"), "--cell", *["%r" % c for c in cell], "--time-bins", "3", "--removed", "--volume", "--level", "0.5", "0.9"])
+    dn.main([param_file, "--cell", *["%r" % c for c in cell], "--time-bins", "3", "--removed", "--volume", "--level", "0.5", "0.9"])
     # what is expected, from the files
     read = lambda r: np.fromfile(str(tmp_path / ("hypo.%02d.out" % r)), dtype=np.dtype([("it", "<i4"), ("v", "<f8", (3 * n_ev,))]))["v"]
     hypo = np.vstack([read(0), read(1)]).reshape(2 * n_rows, 3 * n_ev)

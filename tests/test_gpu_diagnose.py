@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 from tests import diagnose_restatement as dr
-from tests.helpers import load_case
+from tests.helpers import load_case, write_run_dir
 
 pytestmark = pytest.mark.gpu
 
@@ -199,14 +199,10 @@ def test_program_writes_convergence_stat(n_procs, tmp_path, monkeypatch, capsys)
     LocalWorld(sets).run(1500)
     for r, cs in enumerate(sets):
         driver.write_outputs(str(tmp_path), r, cs, endian="little")
-    stations = ["N.S%02d" % j for j in range(data.n_sta)]
-    (tmp_path / "station_xy.list").write_text("".join(
-        "%s %.6f %.6f %.6f 1.0 1.0\n" % (s, x, y, z) for s, x, y, z in zip(stations, data.sta_x, data.sta_y, data.sta_z)))
     win_id = [3 * j + 2 for j in range(data.n_events)]
-    (tmp_path / "selected_win.dat").write_text("".join("%d 0.0\n" % w for w in win_id))
-    (tmp_path / "param.in").write_text("".join("%s = %s\n" % kv for kv in params.items()))
+    param_file, stations = write_run_dir(tmp_path, data, params, win_id)
     monkeypatch.delenv("HTM_SAMPLE_ENDIAN", raising=False)
-    dg.main([str(tmp_path / "param.in"), "--max-lag", "40"])
+    dg.main([param_file, "--max-lag", "40"])
     got = (tmp_path / "convergence.stat").read_text().split("\n")
     names = (["vs", "qs"] + ["t_corr " + s for s in stations] + ["a_corr " + s for s in stations]
              + ["%s %d" % (c, w) for w in win_id for c in "xyz"] + ["log_likelihood"])

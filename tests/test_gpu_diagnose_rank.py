@@ -19,7 +19,7 @@ import pytest
 
 from tests import diagnose_rank_restatement as rr
 from tests import diagnose_restatement as dr
-from tests.helpers import load_case
+from tests.helpers import load_case, write_run_dir
 
 pytestmark = pytest.mark.gpu
 
@@ -266,19 +266,15 @@ def test_program_writes_convergence_rank_stat(tmp_path, monkeypatch, capsys):
     _, cs = driver.build_rank(params, data.sta_x, data.sta_y, data.sta_z, obs, 0, n_procs=1, fwd=None)
     LocalWorld([cs]).run(1500)
     driver.write_outputs(str(tmp_path), 0, cs, endian="little")
-    stations = ["N.S%02d" % j for j in range(data.n_sta)]
-    (tmp_path / "station_xy.list").write_text("".join(
-        "%s %.6f %.6f %.6f 1.0 1.0\n" % (s, x, y, z) for s, x, y, z in zip(stations, data.sta_x, data.sta_y, data.sta_z)))
     win_id = [3 * j + 2 for j in range(data.n_events)]
-    (tmp_path / "selected_win.dat").write_text("".join("%d 0.0\n" % w for w in win_id))
-    (tmp_path / "param.in").write_text("".join("%s = %s\n" % kv for kv in params.items()))
+    param_file, stations = write_run_dir(tmp_path, data, params, win_id)
     monkeypatch.delenv("HTM_SAMPLE_ENDIAN", raising=False)
-    dg.main([str(tmp_path / "param.in"), "--max-lag", "40"])
+    dg.main([param_file, "--max-lag", "40"])
     plain_stat, plain_out = (tmp_path / "convergence.stat").read_text(), capsys.readouterr().out
     assert not (tmp_path / "convergence_rank.stat").exists()
     assert len(plain_out.split("\n")) == 6 and plain_out.startswith("%d parameters (%d constant)\nlargest R-hat  " % (
         1 + data.n_sta + 3 * data.n_events + 1, 1 + data.n_sta))
-    dg.main([str(tmp_path / "param.in"), "--max-lag", "40", "--rank"])
+    dg.main([param_file, "--max-lag", "40", "--rank"])
     rank_out = capsys.readouterr().out
     assert (tmp_path / "convergence.stat").read_text() == plain_stat
     assert rank_out.startswith(plain_out)

@@ -26,7 +26,7 @@ import numpy as np
 import pytest
 
 from tests import ellipsoid_restatement as er
-from tests.helpers import load_case
+from tests.helpers import load_case, write_run_dir
 
 pytestmark = pytest.mark.gpu
 
@@ -314,16 +314,12 @@ def test_program_writes_hypo_ellipsoid_stat(n_procs, tmp_path, monkeypatch, caps
     LocalWorld(sets).run(1500)
     for r, cs in enumerate(sets):
         driver.write_outputs(str(tmp_path), r, cs, endian="little")
-    stations = ["N.S%02d" % j for j in range(data.n_sta)]
-    (tmp_path / "station_xy.list").write_text("".join(
-        "%s %.6f %.6f %.6f 1.0 1.0\n" % (s, x, y, z) for s, x, y, z in zip(stations, data.sta_x, data.sta_y, data.sta_z)))
     win_id = [3 * j + 2 for j in range(data.n_events)]
-    (tmp_path / "selected_win.dat").write_text("".join("%d 0.0\n" % w for w in win_id))
-    (tmp_path / "param.in").write_text("".join("%s = %s\n" % kv for kv in params.items()))
+    param_file, _ = write_run_dir(tmp_path, data, params, win_id)
     monkeypatch.delenv("HTM_SAMPLE_ENDIAN", raising=False)
     monkeypatch.delenv("HTM_ELL_SLABS", raising=False)
     monkeypatch.delenv("HTM_ELLIPSOID_MB", raising=False)
-    el.main([str(tmp_path / "param.in"), "--level", "0.68"])
+    el.main([param_file, "--level", "0.68"])
     got = (tmp_path / "hypo_ellipsoid.stat").read_text().split("\n")
     assert got[0].startswith("#") and got[-1] == "" and len(got) == data.n_events + 2
     rows, tols = _expected_rows(str(tmp_path), n_procs, data.n_events, 0.68)
