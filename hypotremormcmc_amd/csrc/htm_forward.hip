@@ -511,15 +511,14 @@ int htm_forward_time_full_batch_dev(htm_forward *h, int n_models, const double *
 }
 
 // ---------------------------------------------------------------------------------------------------
-// The location posterior of every event of the handle on a grid, under a fixed structure (include/htm_hip.h; kernels and
-// the partial records: htm_locate.hpp).  The prior is separable: its three tables per event are made here, on the host.
-int htm_forward_locate(htm_forward *h, const double *t_corr, double vs, const double *a_corr, double qs, const double *grid9,
-                       const double *prior5, double *loc, double *marg, double *vol)
+// The location posterior of every event of the handle on a grid, under a fixed structure or marginalised over draws of it
+// (include/htm_hip.h; kernels and the partial records: htm_locate.hpp).  The prior is separable: its three tables per event are
+// made here, on the host.  n_draws = 0: htm_forward_locate, one structure (t_corr, a_corr [S]; *vs, *qs) and k_locate;
+// n_draws >= 1: htm_forward_locate_marginal, t_corr, a_corr [n_draws][S], vs, qs [n_draws] and k_locate_marginal.
+static int locate_run(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr, const double *qs,
+                      const double *grid9, const double *prior5, double *loc, double *marg, double *vol)
 {
-    if (!h) return fail(HTM_EINVAL, "NULL handle");
-    if (!t_corr || !a_corr || !grid9 || !loc) return fail(HTM_EINVAL, "NULL argument");
-    if (!std::isfinite(vs) || !std::isfinite(qs) || !(vs > 0.0) || !(qs > 0.0))
-        return fail(HTM_EINVAL, "vs = %g, qs = %g: need finite values > 0", vs, qs);
+    const bool draws = n_draws > 0;
     int n[3];
     for (int a = 0; a < 3; ++a) {
         const double v0 = grid9[3 * a], dv = grid9[3 * a + 1], cnt = grid9[3 * a + 2];
@@ -549,10 +548,15 @@ int htm_forward_locate(htm_forward *h, const double *t_corr, double vs, const do
     // events per batch: a launch's grid (y <= 65535, 2^32 - 1 work-items) and the workspace under HTM_LOCATE_MB MiB
     const long nm = (long)n[0] + n[1] + n[2];
     const double per_event = sizeof(double) * ((double)n_tiles * g.stride + (vol ? (double)cells : 0.0) + 2.0 * nm + 16.0) + sizeof(LocSta) * (double)S + sizeof(LocEv);
+    // the draws' table and the draws as they come (the pack kernel's input) are part of the workspace, once per call
+    const int K = n_draws, Kpad = (K + kLocDraws - 1) / kLocDraws * kLocDraws;
+    const double table = draws ? sizeof(LocPair) * ((double)S + 1.0) * Kpad + sizeof(double) * (2.0 * S + 2.0) * K : 0.0;
+    if (draws && table + per_event > mb * 1048576.0)
+        return fail(HTM_EINVAL, "HTM_LOCATE_MB = %g: the table of %d draws (%.0f bytes) and one event (%.0f bytes) do not fit", mb, K, table, per_event);
     long nb = std::min<long>(E, 65535L);
     nb = std::min(nb, kMaxWorkItems / (n_tiles * kLocThreads));
     nb = std::min(nb, (kMaxWorkItems - 256) / S);
-    nb = std::min(nb, (long)std::min(mb * 1048576.0 / per_event, 65535.0));
+    nb = std::min(nb, (long)std::min((mb * 1048576.0 - table) / per_event, 65535.0));
     nb = std::max(nb, 1L);
 
     HIPCHK(hipSetDevice(h->device));
@@ -566,12 +570,27 @@ int htm_forward_locate(htm_forward *h, const double *t_corr, double vs, const do
         return rc;
     if (prior5 && (rc = pool.alloc(&d_prior, (size_t)nb * nm))) return rc;
     if (vol && (rc = pool.alloc(&d_vol, (size_t)nb * cells))) return rc;
-    HIPCHK(hipMemcpy(h->d_tc, t_corr, (size_t)S * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_ac, a_corr, (size_t)S * sizeof(double), hipMemcpyHostToDevice));
 
     LocJob jb{};
     jb.sta = d_sta; jb.ev = d_ev; jb.prior = d_prior; jb.part = d_part; jb.vol = d_vol; jb.S = S;
-    jb.rbeta = 1.0 / vs; jb.katt = (kPi * kFreq) / (qs * vs);          // as event_misfit forms them
+    LocDraws dr{};
+    if (!draws) {
+        HIPCHK(hipMemcpy(h->d_tc, t_corr, (size_t)S * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->d_ac, a_corr, (size_t)S * sizeof(double), hipMemcpyHostToDevice));
+        jb.rbeta = 1.0 / *vs; jb.katt = (kPi * kFreq) / (*qs * *vs);          // as event_misfit forms them
+    } else {
+        // (the station records' tc and ac are not read on this path: k_locate_pack fills them from whatever the handle holds)
+        std::vector<double> rk(2 * (size_t)K);
+        for (int k = 0; k < K; ++k) { rk[k] = 1.0 / vs[k]; rk[(size_t)K + k] = (kPi * kFreq) / (qs[k] * vs[k]); }
+        double *d_dtc = nullptr, *d_dac = nullptr, *d_rk = nullptr;
+        LocPair *d_corr = nullptr, *d_vq = nullptr;
+        if ((rc = pool.upload(&d_dtc, t_corr, (size_t)K * S)) || (rc = pool.upload(&d_dac, a_corr, (size_t)K * S)) || (rc = pool.upload(&d_rk, rk.data(), rk.size())) ||
+            (rc = pool.alloc(&d_corr, (size_t)S * Kpad)) || (rc = pool.alloc(&d_vq, (size_t)Kpad)))
+            return rc;
+        hipLaunchKernelGGL(k_locate_pack_draws, dim3((unsigned)((((long)S + 1) * Kpad + 255) / 256)), dim3(256), 0, h->stream, S, K, Kpad, d_dtc, d_dac, d_rk,
+                           d_rk + K, d_corr, d_vq);
+        dr.vq = d_vq; dr.corr = d_corr; dr.K = K; dr.Kpad = Kpad;
+    }
     const double log_cell = std::log(g.dx * g.dy * g.dz);
     const double log_2pi_half = 0.5 * std::log(2.0 * std::acos(-1.0));
     const int mode = (h->dev.use_time ? 1 : 0) | (h->dev.use_amp ? 2 : 0);
@@ -598,12 +617,20 @@ int htm_forward_locate(htm_forward *h, const double *t_corr, double vs, const do
         hipLaunchKernelGGL(k_locate_pack, dim3((unsigned)((m * S + 255) / 256)), dim3(256), 0, h->stream, h->dev, (int)e0, (int)m, h->d_tc, h->d_ac,
                            h->d_lconst_t, h->d_lconst_a, d_sta, d_ev);
         const dim3 grid((unsigned)n_tiles, (unsigned)m), block(kLocThreads);
-        switch (mode) {
-        case 0: hipLaunchKernelGGL(k_locate<0>, grid, block, 0, h->stream, g, jb); break;
-        case 1: hipLaunchKernelGGL(k_locate<1>, grid, block, 0, h->stream, g, jb); break;
-        case 2: hipLaunchKernelGGL(k_locate<2>, grid, block, 0, h->stream, g, jb); break;
-        default: hipLaunchKernelGGL(k_locate<3>, grid, block, 0, h->stream, g, jb); break;
-        }
+        if (!draws)
+            switch (mode) {
+            case 0: hipLaunchKernelGGL(k_locate<0>, grid, block, 0, h->stream, g, jb); break;
+            case 1: hipLaunchKernelGGL(k_locate<1>, grid, block, 0, h->stream, g, jb); break;
+            case 2: hipLaunchKernelGGL(k_locate<2>, grid, block, 0, h->stream, g, jb); break;
+            default: hipLaunchKernelGGL(k_locate<3>, grid, block, 0, h->stream, g, jb); break;
+            }
+        else
+            switch (mode) {
+            case 0: hipLaunchKernelGGL(k_locate_marginal<0>, grid, block, 0, h->stream, g, jb, dr); break;
+            case 1: hipLaunchKernelGGL(k_locate_marginal<1>, grid, block, 0, h->stream, g, jb, dr); break;
+            case 2: hipLaunchKernelGGL(k_locate_marginal<2>, grid, block, 0, h->stream, g, jb, dr); break;
+            default: hipLaunchKernelGGL(k_locate_marginal<3>, grid, block, 0, h->stream, g, jb, dr); break;
+            }
         hipLaunchKernelGGL(k_locate_combine, dim3((unsigned)m), dim3(256), 0, h->stream, g, d_part, log_cell, d_loc, d_marg);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -612,6 +639,28 @@ int htm_forward_locate(htm_forward *h, const double *t_corr, double vs, const do
         if (vol && (rc = pool.download(vol + (size_t)e0 * cells, d_vol, (size_t)m * cells, "the volume's"))) return rc;
     }
     return HTM_OK;
+}
+
+int htm_forward_locate(htm_forward *h, const double *t_corr, double vs, const double *a_corr, double qs, const double *grid9,
+                       const double *prior5, double *loc, double *marg, double *vol)
+{
+    if (!h) return fail(HTM_EINVAL, "NULL handle");
+    if (!t_corr || !a_corr || !grid9 || !loc) return fail(HTM_EINVAL, "NULL argument");
+    if (!std::isfinite(vs) || !std::isfinite(qs) || !(vs > 0.0) || !(qs > 0.0))
+        return fail(HTM_EINVAL, "vs = %g, qs = %g: need finite values > 0", vs, qs);
+    return locate_run(h, 0, t_corr, &vs, a_corr, &qs, grid9, prior5, loc, marg, vol);
+}
+
+int htm_forward_locate_marginal(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr, const double *qs,
+                                const double *grid9, const double *prior5, double *loc, double *marg, double *vol)
+{
+    if (!h) return fail(HTM_EINVAL, "NULL handle");
+    if (!t_corr || !vs || !a_corr || !qs || !grid9 || !loc) return fail(HTM_EINVAL, "NULL argument");
+    if (n_draws < 1 || n_draws > kLocMaxDraws) return fail(HTM_EINVAL, "n_draws = %d: need 1..%d", n_draws, kLocMaxDraws);
+    for (int k = 0; k < n_draws; ++k)
+        if (!std::isfinite(vs[k]) || !std::isfinite(qs[k]) || !(vs[k] > 0.0) || !(qs[k] > 0.0))
+            return fail(HTM_EINVAL, "draw %d: vs = %g, qs = %g: need finite values > 0", k, vs[k], qs[k]);
+    return locate_run(h, n_draws, t_corr, vs, a_corr, qs, grid9, prior5, loc, marg, vol);
 }
 
 // ---------------------------------------------------------------------------------------------------

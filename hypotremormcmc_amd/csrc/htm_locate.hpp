@@ -17,6 +17,9 @@
 //                     (a wave per row, the fixed-tree wave sum) and per ix over the rows.  One partial record per tile.
 //   k_locate_combine  one workgroup per event: the event's maximum over its tiles in tile order, every partial rescaled by
 //                     exp(max_tile - max_event); marginals, mean, covariance, log evidence.
+//   k_locate_pack_draws, k_locate_marginal<MODE>    htm_forward_locate_marginal: the structure marginalised over draws of it,
+//                     described where they stand, below k_locate; what follows a cell's log posterior is shared with k_locate
+//                     (loc_cell_done, loc_tile_reduce), and k_locate_combine serves both.
 // No floating-point atomics anywhere: the bits do not depend on timing.  The volume of log posteriors is written only when it
 // is asked for.
 //
@@ -26,6 +29,7 @@
 // per row).
 #pragma once
 #include <climits>
+#include <type_traits>
 
 #include "htm_device.hpp"
 
@@ -43,6 +47,18 @@ constexpr int kLocRows = 256;           // x-rows per tile at the most
 constexpr int kLocHead = 4;
 static_assert(kLocTile >= kLocMaxCells, "a tile holds at least one whole x-row");
 static_assert(kLocPerThread % kLocChunk == 0, "whole chunks");
+// k_locate_marginal: draws per block and cells of a thread side by side (the choice and its alternatives: DESIGN.md 3.11)
+#ifndef HTM_LOCM_DRAWS
+#define HTM_LOCM_DRAWS 8
+#endif
+#ifndef HTM_LOCM_CELLS
+#define HTM_LOCM_CELLS 1
+#endif
+constexpr int kLocDraws = HTM_LOCM_DRAWS;
+constexpr int kLocmCells = HTM_LOCM_CELLS;
+constexpr int kLocMaxDraws = 4096;      // draws per call (include/htm_hip.h)
+static_assert(kLocDraws >= 1 && kLocMaxDraws % kLocDraws == 0, "whole blocks of draws");
+static_assert(kLocmCells >= 1 && kLocPerThread % kLocmCells == 0, "whole chunks");
 
 // what the evaluation reads of one station for one event; 80 bytes, read with scalar loads
 struct __attribute__((aligned(16))) LocSta {
@@ -137,26 +153,118 @@ __device__ __forceinline__ double loc_block_sum(double v, double *s_red4)
     return (s_red4[0] + s_red4[1]) + (s_red4[2] + s_red4[3]);
 }
 
+// what a workgroup knows of its tile and event
+struct LocTile {
+    int tile, b, iz, iy0, rows, ncell;
+    long cell0;             // linear index of the tile's first cell
+    double zc, pz;
+    const double *prior;    // the event's tables, or nullptr
+};
+__device__ __forceinline__ LocTile loc_tile(const LocGrid &g, const LocJob &jb)
+{
+    LocTile tl;
+    tl.tile = blockIdx.x; tl.b = blockIdx.y;
+    tl.iz = tl.tile / g.tpl; tl.iy0 = (tl.tile - tl.iz * g.tpl) * g.rows;
+    tl.rows = min(g.rows, g.ny - tl.iy0); tl.ncell = tl.rows * g.nx;
+    tl.cell0 = ((long)tl.iz * g.ny + tl.iy0) * g.nx;
+    tl.zc = loc_centre(g.z0, g.dz, tl.iz);
+    tl.prior = jb.prior ? jb.prior + (size_t)tl.b * (g.nx + g.ny + g.nz) : nullptr;
+    tl.pz = tl.prior ? tl.prior[g.nx + g.ny + tl.iz] : 0.0;
+    return tl;
+}
+
+// Cell c of the tile has the log-likelihood term ell and the log prior pxy + pz: its log posterior, NaN for a thread without
+// that cell; written to the volume if that is asked for, and offered to the thread's best cell (its cells come in ascending order)
+__device__ __forceinline__ double loc_cell_done(const LocGrid &g, const LocJob &jb, const LocTile &tl, int c, double ell, double pxy, LocBest &best)
+{
+    const double v = tl.prior ? ell + (pxy + tl.pz) : ell;
+    const bool live = c < tl.ncell;
+    if (live) {
+        if (jb.vol) jb.vol[(size_t)tl.b * ((size_t)g.nx * g.ny * g.nz) + (size_t)(tl.cell0 + c)] = v;
+        if (loc_included(v)) loc_better(best, v, ell, c);
+    }
+    return live ? v : __builtin_nan("");
+}
+
+// Everything after the cells' log posteriors, for k_locate and k_locate_marginal alike: the tile's maximum and its first cell,
+// the weights exp(lp - max) in LDS (s_w [kLocTile]), the row sums, the tile's partial record.  lp_of(k) is the log posterior of
+// the thread's k-th cell t + 256 k; it may read s_w[t + 256 k] itself, which only this thread overwrites, after reading it.
+template <class LpOf>
+__device__ __forceinline__ void loc_tile_reduce(const LocGrid &g, const LocJob &jb, const LocTile &tl, LocBest best, double *s_w, LpOf lp_of)
+{
+    __shared__ double s_S[kLocRows];
+    __shared__ double s_blp[4], s_bell[4];
+    __shared__ int s_bidx[4];
+    const int t = threadIdx.x, lane = t & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int rows = tl.rows, ncell = tl.ncell;
+    // the tile's maximum and its first cell
+    loc_best_wave(best);
+    if (lane == 0) { s_blp[wv] = best.lp; s_bell[wv] = best.ell; s_bidx[wv] = best.idx; }
+    __syncthreads();
+    best = LocBest{s_blp[0], s_bell[0], s_bidx[0]};
+#pragma unroll
+    for (int w = 1; w < 4; ++w) loc_better(best, s_blp[w], s_bell[w], s_bidx[w]);
+    double *rec = jb.part + ((size_t)tl.b * ((size_t)g.nz * g.tpl) + tl.tile) * g.stride;
+    double *mx = rec + kLocHead, *pS = mx + g.nx, *pT = pS + g.rows;
+    const bool none = best.idx == INT_MAX;      // (block-uniform)
+    if (t == 0) {
+        rec[0] = none ? -__builtin_inf() : best.lp;
+        rec[1] = none ? -1.0 : (double)(tl.cell0 + best.idx);
+        rec[2] = none ? 0.0 : best.ell;
+    }
+    if (none) {
+        if (t == 0) rec[3] = 0.0;
+        for (int i = t; i < g.nx + 2 * g.rows; i += kLocThreads) mx[i] = 0.0;
+        return;
+    }
+    // weights relative to the tile's maximum, into LDS
+#pragma unroll
+    for (int k = 0; k < kLocPerThread; ++k) {
+        const int c = t + kLocThreads * k;
+        if (c < ncell) { const double v = lp_of(k); s_w[c] = loc_included(v) ? exp(v - best.lp) : 0.0; }
+    }
+    __syncthreads();
+    // a wave per x-row: the row's weight and weight times x, lane-strided in ascending ix, then the wave sums' fixed tree
+    for (int r = wv; r < g.rows; r += 4) {       // (wave-uniform; rows beyond the tile's give zeros)
+        double v[2] = {0.0, 0.0};
+        if (r < rows)
+            for (int ix = lane; ix < g.nx; ix += 64) {
+                const double w = s_w[r * g.nx + ix];
+                v[0] += w;
+                v[1] = __builtin_fma(w, loc_centre(g.x0, g.dx, ix), v[1]);
+            }
+        wave_sum<2>(v);
+        if (lane == 0) { s_S[r] = v[0]; pS[r] = v[0]; pT[r] = v[1]; }
+    }
+    // a thread per ix: the weight over the tile's rows, in ascending row order
+    for (int ix = t; ix < g.nx; ix += kLocThreads) {
+        double a = 0.0;
+        for (int r = 0; r < rows; ++r) a += s_w[r * g.nx + ix];
+        mx[ix] = a;
+    }
+    __syncthreads();
+    if (wv == 0) {      // the tile's weight: the rows lane-strided, then the tree
+        double a = 0.0;
+        for (int r = lane; r < rows; r += 64) a += s_S[r];
+        a = wave_sum1(a);
+        if (lane == 0) rec[3] = a;
+    }
+}
+
 // MODE: 1 travel times only, 2 amplitudes only, 3 both
 template <int MODE>
 __global__ __launch_bounds__(256) void k_locate(LocGrid g, LocJob jb)
 {
     constexpr bool UT = (MODE & 1) != 0, UA = (MODE & 2) != 0;
     __shared__ double s_w[kLocTile];
-    __shared__ double s_S[kLocRows];
-    __shared__ double s_blp[4], s_bell[4];
-    __shared__ int s_bidx[4];
-    const int t = threadIdx.x, lane = t & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int tile = blockIdx.x, b = blockIdx.y;
-    const int iz = tile / g.tpl, iy0 = (tile - iz * g.tpl) * g.rows;
-    const int rows = min(g.rows, g.ny - iy0), ncell = rows * g.nx;
-    const long cell0 = ((long)iz * g.ny + iy0) * g.nx;            // linear index of the tile's first cell
-    const double zc = loc_centre(g.z0, g.dz, iz);
-    const LocSta *sta = jb.sta + (size_t)b * jb.S;
-    const LocEv ev = loc_ld_ev(jb.ev + b);
-    const double *prior = jb.prior ? jb.prior + (size_t)b * (g.nx + g.ny + g.nz) : nullptr;
-    const double pz = prior ? prior[g.nx + g.ny + iz] : 0.0;
+    const int t = threadIdx.x;
+    const LocTile tl = loc_tile(g, jb);
+    const int iy0 = tl.iy0, ncell = tl.ncell;
+    const double zc = tl.zc;
+    const LocSta *sta = jb.sta + (size_t)tl.b * jb.S;
+    const LocEv ev = loc_ld_ev(jb.ev + tl.b);
+    const double *prior = tl.prior;
 
     double lp[kLocPerThread];
     LocBest best{-__builtin_inf(), 0.0, INT_MAX};
@@ -239,72 +347,159 @@ __global__ __launch_bounds__(256) void k_locate(LocGrid g, LocJob jb)
 #endif
 #pragma unroll
         for (int k = 0; k < kLocChunk; ++k) {
-            const int c = t + kLocThreads * (ch * kLocChunk + k);
             double ell = 0.0;
             if constexpr (UT) ell -= 0.5 * t2[k] + ev.ct;
             if constexpr (UA) ell -= 0.5 * a2[k] + ev.ca;
-            const double v = prior ? ell + (pxy[k] + pz) : ell;
-            const bool live = c < ncell;
-            lp[ch * kLocChunk + k] = live ? v : __builtin_nan("");
-            if (live) {
-                if (jb.vol) jb.vol[(size_t)b * ((size_t)g.nx * g.ny * g.nz) + (size_t)(cell0 + c)] = v;
-                if (loc_included(v)) loc_better(best, v, ell, c);      // (a thread's cells come in ascending order)
-            }
+            lp[ch * kLocChunk + k] = loc_cell_done(g, jb, tl, t + kLocThreads * (ch * kLocChunk + k), ell, pxy[k], best);
         }
     }
+    loc_tile_reduce(g, jb, tl, best, s_w, [&](int k) { return lp[k]; });
+}
 
-    // the tile's maximum and its first cell
-    loc_best_wave(best);
-    if (lane == 0) { s_blp[wv] = best.lp; s_bell[wv] = best.ell; s_bidx[wv] = best.idx; }
-    __syncthreads();
-    best = LocBest{s_blp[0], s_bell[0], s_bidx[0]};
+// ---- the structure marginalised over K draws -----------------------------------------------------------
+// The term of a cell becomes log((1 / K) sum_k exp(l_k)), l_k the term k_locate evaluates under draw k's structure.  The
+// distance of a (cell, station) and its logarithm do not depend on the structure: a lane forms them ONCE per block of
+// kLocDraws draws and then applies every draw's 1 / vs, pi f / (qs vs) and corrections to them, with k_locate's expressions.
+//
+//   k_locate_pack_draws  the draws' table: {1 / vs_k, pi f / (qs_k vs_k)} per draw and {t_corr_kj, a_corr_kj} per (station,
+//                        draw), [station][draw] with the draws padded to whole blocks (the padding repeats the last draw and
+//                        is never counted), so that a block's 16-byte pairs are contiguous and read with SCALAR loads
+//   k_locate_marginal    k_locate's grid and tiles.  A thread evaluates kLocmCells of its cells side by side; per block of
+//                        draws the station loop runs once.  Across the blocks a cell keeps (m, s), s = sum_k exp(l_k - m);
+//                        the cells' log posteriors go to the LDS array that holds the weights afterwards (a thread's own
+//                        words), so the loop over a thread's cells is a loop, not sixteen copies of the code.
+struct __attribute__((aligned(16))) LocPair {
+    double a, b;
+};
+struct LocDraws {
+    const LocPair *vq;      // [Kpad] {1 / vs, pi f / (qs vs)}
+    const LocPair *corr;    // [S][Kpad] {t_corr, a_corr}
+    int K, Kpad;            // draws; padded to a multiple of kLocDraws
+};
+
+__global__ __launch_bounds__(256) void k_locate_pack_draws(int S, int K, int Kpad, const double *tc, const double *ac, const double *rbeta,
+                                                           const double *katt, LocPair *corr, LocPair *vq)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)(S + 1) * Kpad) return;
+    const int j = (int)(i / Kpad), k = min((int)(i - (long)j * Kpad), K - 1);
+    if (j == S) vq[i - (long)S * Kpad] = LocPair{rbeta[k], katt[k]};
+    else corr[i] = LocPair{tc[(size_t)k * S + j], ac[(size_t)k * S + j]};
+}
+
+// kLocDraws pairs at a wave-uniform, 16-byte aligned address through the constant address space: scalar loads
+__device__ __forceinline__ void loc_ld_pairs(const LocPair *p, double (&a)[kLocDraws], double (&b)[kLocDraws])
+{
+    typedef const loc_f64x2 __attribute__((address_space(4))) *CP;
+    const CP q = (CP)(unsigned long long)p;
 #pragma unroll
-    for (int w = 1; w < 4; ++w) loc_better(best, s_blp[w], s_bell[w], s_bidx[w]);
-    double *rec = jb.part + ((size_t)b * ((size_t)g.nz * g.tpl) + tile) * g.stride;
-    double *mx = rec + kLocHead, *pS = mx + g.nx, *pT = pS + g.rows;
-    const bool none = best.idx == INT_MAX;      // (block-uniform)
-    if (t == 0) {
-        rec[0] = none ? -__builtin_inf() : best.lp;
-        rec[1] = none ? -1.0 : (double)(cell0 + best.idx);
-        rec[2] = none ? 0.0 : best.ell;
-    }
-    if (none) {
-        if (t == 0) rec[3] = 0.0;
-        for (int i = t; i < g.nx + 2 * g.rows; i += kLocThreads) mx[i] = 0.0;
-        return;
-    }
-    // weights relative to the tile's maximum, into LDS
+    for (int i = 0; i < kLocDraws; ++i) { const loc_f64x2 v = q[i]; a[i] = v[0]; b[i] = v[1]; }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_locate_marginal(LocGrid g, LocJob jb, LocDraws dr)
+{
+    constexpr bool UT = (MODE & 1) != 0, UA = (MODE & 2) != 0;
+    constexpr int C = kLocmCells, D = kLocDraws;
+    __shared__ double s_w[kLocTile];
+    const int t = threadIdx.x;
+    const LocTile tl = loc_tile(g, jb);
+    const int ncell = tl.ncell;
+    const double zc = tl.zc;
+    const LocSta *sta = jb.sta + (size_t)tl.b * jb.S;
+    const LocEv ev = loc_ld_ev(jb.ev + tl.b);
+    const double *prior = tl.prior;
+    const double log_K = htm_log((double)dr.K);
+
+    LocBest best{-__builtin_inf(), 0.0, INT_MAX};
+#pragma unroll 1
+    for (int ch = 0; ch * C * kLocThreads < ncell; ++ch) {      // (block-uniform)
+        double x[C], y[C], pxy[C], m[C], s[C];
+        bool bad[C];
 #pragma unroll
-    for (int k = 0; k < kLocPerThread; ++k) {
-        const int c = t + kLocThreads * k;
-        if (c < ncell) s_w[c] = loc_included(lp[k]) ? exp(lp[k] - best.lp) : 0.0;
-    }
-    __syncthreads();
-    // a wave per x-row: the row's weight and weight times x, lane-strided in ascending ix, then the wave sums' fixed tree
-    for (int r = wv; r < g.rows; r += 4) {       // (wave-uniform; rows beyond the tile's give zeros)
-        double v[2] = {0.0, 0.0};
-        if (r < rows)
-            for (int ix = lane; ix < g.nx; ix += 64) {
-                const double w = s_w[r * g.nx + ix];
-                v[0] += w;
-                v[1] = __builtin_fma(w, loc_centre(g.x0, g.dx, ix), v[1]);
+        for (int k = 0; k < C; ++k) {
+            const int c = t + kLocThreads * (ch * C + k), cc = c < ncell ? c : 0;      // (a thread without a cell evaluates cell 0 and drops it)
+            const int r = cc / g.nx, ix = cc - r * g.nx;
+            x[k] = loc_centre(g.x0, g.dx, ix);
+            y[k] = loc_centre(g.y0, g.dy, tl.iy0 + r);
+            pxy[k] = prior ? prior[ix] + prior[g.nx + tl.iy0 + r] : 0.0;
+            m[k] = -__builtin_inf(); s[k] = 0.0; bad[k] = false;
+        }
+#pragma unroll 1
+        for (int k0 = 0; k0 < dr.K; k0 += D) {                  // (uniform) a block of draws
+            double rbeta[D], katt[D];
+            loc_ld_pairs(dr.vq + k0, rbeta, katt);
+            double r0t[C][D], r0a[C][D], t1[C][D], t2[C][D], a1[C][D], a2[C][D];
+#pragma unroll
+            for (int k = 0; k < C; ++k)
+#pragma unroll
+                for (int q = 0; q < D; ++q) t1[k][q] = t2[k][q] = a1[k][q] = a2[k][q] = r0t[k][q] = r0a[k][q] = 0.0;
+            // station 0 gives the shifts, stations 1 .. S - 1 add to the sums: k_locate's one-pass form, per draw.  Station 0 is
+            // evaluated by a copy of the body of its own (the same operations: its u is r - r, not a constant), so that the loop
+            // carries no selection per draw
+            auto station = [&](int j, auto first) {
+                const LocSta st = loc_ld_sta(sta + j);
+                double tc[D], ac[D];
+                loc_ld_pairs(dr.corr + (size_t)j * dr.Kpad + k0, tc, ac);
+#pragma unroll
+                for (int k = 0; k < C; ++k) {
+                    const double dx = x[k] - st.sx, dy = y[k] - st.sy, dz = zc - st.sz;
+                    const double d = htm_sqrt(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)));
+                    double nld = 0.0;
+                    if constexpr (UA) nld = -htm_log(d);
+#pragma unroll
+                    for (int q = 0; q < D; ++q) {
+                        if constexpr (UT) {
+                            const double rt = __builtin_fma(d, rbeta[q], -tc[q]) - st.tob;
+                            if constexpr (first.value) r0t[k][q] = rt;
+                            const double u = rt - r0t[k][q], pu = st.tpr * u;
+                            t1[k][q] += pu;
+                            t2[k][q] = __builtin_fma(pu, u, t2[k][q]);
+                        }
+                        if constexpr (UA) {
+                            const double ra = (__builtin_fma(-d, katt[q], nld) - ac[q]) - st.aob;
+                            if constexpr (first.value) r0a[k][q] = ra;
+                            const double u = ra - r0a[k][q], pu = st.apr * u;
+                            a1[k][q] += pu;
+                            a2[k][q] = __builtin_fma(pu, u, a2[k][q]);
+                        }
+                    }
+                }
+            };
+            station(0, std::true_type());
+            for (int j = 1; j < jb.S; ++j) station(j, std::false_type());
+            // the block's terms, and into (m, s): the padding's draws (k0 + q >= K, uniform) are left out
+#pragma unroll
+            for (int k = 0; k < C; ++k) {
+                double ell[D], mb = -__builtin_inf();
+#pragma unroll
+                for (int q = 0; q < D; ++q) {
+                    double e = 0.0;
+                    if constexpr (UT) e -= 0.5 * (t2[k][q] - (t1[k][q] * t1[k][q]) * ev.rpst) + ev.ct;
+                    if constexpr (UA) e -= 0.5 * (a2[k][q] - (a1[k][q] * a1[k][q]) * ev.rpsa) + ev.ca;
+                    const bool in = k0 + q < dr.K;
+                    ell[q] = in ? e : -__builtin_inf();
+                    bad[k] = bad[k] || (in && e != e);
+                    mb = e > mb && in ? e : mb;
+                }
+                const double mn = mb > m[k] ? mb : m[k], ref = mn == -__builtin_inf() ? 0.0 : mn;
+                double acc = s[k] * exp(m[k] - ref);
+#pragma unroll
+                for (int q = 0; q < D; ++q) acc += exp(ell[q] - ref);
+                s[k] = acc; m[k] = mn;
             }
-        wave_sum<2>(v);
-        if (lane == 0) { s_S[r] = v[0]; pS[r] = v[0]; pT[r] = v[1]; }
+        }
+#pragma unroll
+        for (int k = 0; k < C; ++k) {
+            const int c = t + kLocThreads * (ch * C + k);
+            // (K equal draws: s = K exactly and the bracket is exactly 0; K = 1: the term itself)
+            double ell = s[k] > 0.0 ? m[k] + (htm_log(s[k]) - log_K) : -__builtin_inf();      // (s = 0: every draw is -inf)
+            if (bad[k] || s[k] != s[k]) ell = __builtin_nan("");
+            const double v = loc_cell_done(g, jb, tl, c, ell, pxy[k], best);
+            if (c < ncell) s_w[c] = v;
+        }
     }
-    // a thread per ix: the weight over the tile's rows, in ascending row order
-    for (int ix = t; ix < g.nx; ix += kLocThreads) {
-        double a = 0.0;
-        for (int r = 0; r < rows; ++r) a += s_w[r * g.nx + ix];
-        mx[ix] = a;
-    }
-    __syncthreads();
-    if (wv == 0) {      // the tile's weight: the rows lane-strided, then the tree
-        double a = 0.0;
-        for (int r = lane; r < rows; r += 64) a += s_S[r];
-        a = wave_sum1(a);
-        if (lane == 0) rec[3] = a;
-    }
+    loc_tile_reduce(g, jb, tl, best, s_w, [&](int k) { return s_w[t + kLocThreads * k]; });
 }
 
 // One workgroup of 256 threads per event of the batch.  loc [nb][16], marg [nb][nx + ny + nz] (always there: the moments are

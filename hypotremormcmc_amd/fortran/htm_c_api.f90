@@ -20,6 +20,7 @@ module htm_c_api
   public :: htm_hypo_ellipsoid, htm_hypo_ellipsoid_dev
   public :: htm_hypo_density, htm_hypo_density_dev
   public :: htm_forward_locate
+  public :: htm_forward_locate_marginal
   public :: htm_chains_checkpoint_size, htm_chains_checkpoint_save, htm_chains_checkpoint_load
 
   integer(c_size_t), parameter :: HTM_XCHG_HANDLE_BYTES = 64_c_size_t, HTM_COMM_ID_BYTES = 128_c_size_t
@@ -370,6 +371,20 @@ module htm_c_api
        type(c_ptr), value :: marg, vol
        integer(c_int) :: rc
      end function htm_forward_locate
+     !> the same with the structure marginalised over n_draws draws (include/htm_hip.h): t_corr, a_corr (n_sta, n_draws);
+     !> vs, qs (n_draws); the outputs as htm_forward_locate's
+     function htm_forward_locate_marginal(handle, n_draws, t_corr, vs, a_corr, qs, grid9, prior5, loc, marg, vol) &
+          & bind(C, name="htm_forward_locate_marginal") result(rc)
+       import :: c_int, c_double, c_ptr
+       type(c_ptr), value :: handle
+       integer(c_int), value :: n_draws
+       real(c_double), intent(in) :: t_corr(*), vs(*), a_corr(*), qs(*)
+       real(c_double), intent(in) :: grid9(9)
+       type(c_ptr), value :: prior5
+       real(c_double), intent(out) :: loc(*)
+       type(c_ptr), value :: marg, vol
+       integer(c_int) :: rc
+     end function htm_forward_locate_marginal
      !> step-4 regressions (include/htm_hip.h): t, t_err, a, a_err (n_sta, n_win); out (6, n_win) = vs, b, t0, a0, cc_t, cc_a
      function htm_select_regress(device, n_sta, n_win, sta_x, sta_y, sta_z, z_guess, t, t_err, a, a_err, out) &
           & bind(C, name="htm_select_regress") result(rc)

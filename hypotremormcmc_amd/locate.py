@@ -3,7 +3,7 @@ run's medians), a window's location posterior is a function of its position alon
 grid -- no MCMC, any number of windows (kernels in hypotremormcmc_amd/csrc/htm_locate.hpp).
 
     python -m hypotremormcmc_amd.locate <parameter file> --cell DX [DY DZ] [--bounds x0 x1 y0 y1 z0 z1] [--structure DIR]
-                                        [--windows FILE] [--flat-prior] [--volume-of WIN]
+                                        [--windows FILE] [--flat-prior] [--volume-of WIN] [--draws K]
 
 run in the data directory (station file, opt_data.NNNNNN.dat).  --structure DIR holds `uniform_structure.stat` and
 `station_corrections.stat` of the calibration run (default: the parameter file's directory); --windows FILE lists the window
@@ -15,6 +15,13 @@ window: the best cell's centre, its log posterior and log-likelihood term, the l
 the best cell lies on a face of the box: that window is not resolved by this grid).  --volume-of WIN also writes that
 window's log posterior of every cell to `hypo_grid.WIN.vol.dat`.  The windows go to the device in batches whose workspace
 stays under HTM_LOCATE_MB MiB (default 1024); the result does not depend on it.
+
+A fixed structure leaves the structure's uncertainty out of the intervals of `hypo_grid.stat`.  --draws K marginalises it
+(DESIGN.md §3.11): K records, evenly thinned, of the calibration run's sample files `vs.RR.out`, `qs.RR.out`, `t_corr.RR.out`
+and `a_corr.RR.out` in --structure DIR (read_structure_draws) stand for its posterior, a cell's term becomes
+log((1 / K) sum_k exp(l_k)) over them (locate_marginal, one kernel for all draws), and the results are written next to the
+others, in the same layouts: `hypo_grid_marginal.stat`, `hypo_grid_marginal.best.dat`, `hypo_grid_marginal.WIN.vol.dat`.
+Without --draws nothing changes.
 """
 from __future__ import annotations
 
@@ -68,6 +75,52 @@ def locate(fwd, t_corr, vs, a_corr, qs, grid, prior=None, marginals=True, volume
     _lib.check(_lib.load().htm_forward_locate(fwd.handle, _lib.ptr(tc), float(vs), _lib.ptr(ac), float(qs), _lib.ptr(g), _lib.ptr(pr),
                                               _lib.ptr(loc), _lib.ptr(marg), _lib.ptr(vol)))
     cov = np.empty((E, 3, 3))
+    for (i, j), k in zip(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2)), range(10, 16)):
+        cov[:, i, j] = cov[:, j, i] = loc[:, k]
+    return {"index": loc[:, 0].astype(np.int64), "best": loc[:, 1:4].copy(), "lp": loc[:, 4].copy(), "ell": loc[:, 5].copy(),
+            "log_evidence": loc[:, 6].copy(), "mean": loc[:, 7:10].copy(), "cov": cov, "loc": loc,
+            "marg_x": None if marg is None else marg[:, :nx], "marg_y": None if marg is None else marg[:, nx:nx + ny],
+            "marg_z": None if marg is None else marg[:, nx + ny:], "vol": vol}
+
+
+def locate_marginal(fwd, t_corr, vs, a_corr, qs, grid, prior=None, marginals=True, volume=False):
+    """`locate` with the structure marginalised over K draws of it: t_corr [K][n_sta], vs [K], a_corr [K][n_sta], qs [K].  A
+    cell's log-likelihood term is log((1 / K) sum_k exp(l_k)), l_k the term `locate` takes under draw k; one kernel evaluates
+    all draws (htm_forward_locate_marginal).  Returns the dict of `locate`; K = 1 gives its very bits."""
+    g = grid9(grid)
+    nx, ny, nz = grid_counts(g)
+    if nx * ny * nz > INT_MAX:
+        raise ValueError(f"{nx} x {ny} x {nz} cells: more than 2^31 - 1")
+    E, S = fwd.n_events, fwd.n_sta
+    v = np.ascontiguousarray(np.asarray(vs, dtype=np.float64).reshape(-1))
+    q = np.ascontiguousarray(np.asarray(qs, dtype=np.float64).reshape(-1))
+    K = v.size
+    tc = np.ascontiguousarray(np.asarray(t_corr, dtype=np.float64).reshape(-1))
+    ac = np.ascontiguousarray(np.asarray(a_corr, dtype=np.float64).reshape(-1))
+    if q.size != K or tc.size != K * S or ac.size != K * S:
+        raise ValueError(f"{K} draws of vs: need as many of qs (got {q.size}) and one t_corr and a_corr per draw and station "
+                         f"({K} x {S}; got {tc.size} and {ac.size} values)")
+    pr = _prior_array(prior, E)
+    loc = np.empty((E, 16))
+    marg = np.empty((E, nx + ny + nz)) if marginals else None
+    vol = np.empty((E, nz, ny, nx)) if volume else None
+    _lib.check(_lib.load().htm_forward_locate_marginal(fwd.handle, K, _lib.ptr(tc), _lib.ptr(v), _lib.ptr(ac), _lib.ptr(q), _lib.ptr(g),
+                                                       _lib.ptr(pr), _lib.ptr(loc), _lib.ptr(marg), _lib.ptr(vol)))
+    return _result(loc, marg, vol, nx, ny)
+
+
+def _prior_array(prior, E):
+    if prior is None:
+        return None
+    pr = np.ascontiguousarray(prior, dtype=np.float64)
+    if pr.shape != (E, 5):
+        raise ValueError(f"prior is {pr.shape}: need mu_x, mu_y, w_xy, z0, w_z of every event ({E})")
+    return pr
+
+
+def _result(loc, marg, vol, nx, ny):
+    """the dict of `locate` from the library's arrays"""
+    cov = np.empty((loc.shape[0], 3, 3))
     for (i, j), k in zip(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2)), range(10, 16)):
         cov[:, i, j] = cov[:, j, i] = loc[:, k]
     return {"index": loc[:, 0].astype(np.int64), "best": loc[:, 1:4].copy(), "lp": loc[:, 4].copy(), "ell": loc[:, 5].copy(),
@@ -132,6 +185,47 @@ def read_structure(directory, station_names):
     return vs, qs, np.array(tc), np.array(ac)
 
 
+def draw_records(n_rec: int, n_draws: int):
+    """the records an even thinning of n_rec to n_draws keeps: floor((i + 0.5) n_rec / n_draws), i = 0 .. n_draws - 1"""
+    return [((2 * i + 1) * n_rec) // (2 * n_draws) for i in range(n_draws)]
+
+
+def read_structure_draws(directory, station_names, n_sta, n_draws):
+    """vs [K], qs [K], t_corr [K][n_sta], a_corr [K][n_sta]: K = n_draws records of the calibration run's sample files
+    `vs.RR.out`, `qs.RR.out`, `t_corr.RR.out`, `a_corr.RR.out` in `directory`, the ranks RR = 00, 01, ... as far as `vs.RR.out`
+    is there, stacked in rank order (Step5Run.samples: a rank's four files must record the same iterations) and thinned evenly
+    (draw_records; no random numbers).  The sample files carry no station names: `station_corrections.stat` of the same
+    directory must list the stations of the station file, in its order."""
+    from types import SimpleNamespace
+
+    K = int(n_draws)
+    if K < 1:
+        raise ValueError(f"{K} draws: need at least one")
+    n_procs = 0
+    while os.path.exists(os.path.join(directory, "vs.%02d.out" % n_procs)):
+        n_procs += 1
+    if n_procs == 0:
+        raise FileNotFoundError(f"{os.path.join(directory, 'vs.00.out')} is missing: --draws needs the sample files of the calibration run "
+                                "in the directory that --structure names")
+    path = os.path.join(directory, "station_corrections.stat")
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"{path} is missing: it is what says which station a column of t_corr.RR.out belongs to")
+    listed = [ln.split()[0] for ln in open(path) if ln.strip() and not ln.lstrip().startswith("#")]
+    want = [str(nm).strip()[:12] for nm in station_names]              # (station_corrections.stat keeps 12 characters of a name)
+    if len(want) != n_sta or listed != want:
+        k = next((i for i, (a, b) in enumerate(zip(listed, want)) if a != b), min(len(listed), len(want)))
+        raise ValueError(f"{path} lists {len(listed)} stations, the station file {len(want)}; they must be the same, in the same order "
+                         f"(the first difference: entry {k + 1}, {listed[k] if k < len(listed) else 'none'!r} against "
+                         f"{want[k] if k < len(want) else 'none'!r})")
+    run = Step5Run(SimpleNamespace(get_n_procs=lambda: n_procs, n_stations=n_sta), directory, [])
+    _, smp = run.samples(["vs", "qs", "t_corr", "a_corr"])
+    n_rec = smp["vs"].shape[0]
+    if K > n_rec:
+        raise ValueError(f"{K} draws asked for, {directory} holds {n_rec} records in {n_procs} rank(s)")
+    keep = draw_records(n_rec, K)
+    return smp["vs"][keep, 0].copy(), smp["qs"][keep, 0].copy(), smp["t_corr"][keep].copy(), smp["a_corr"][keep].copy()
+
+
 def step5_prior(par, obs):
     """[n_events][5] = mu_x, mu_y, w_xy, z0, w_z as step 5 sets the hypocentre priors (the station of largest amplitude)"""
     mu_x, mu_y = obs.make_initial_guess()
@@ -181,9 +275,10 @@ def volume_text(vol, grid) -> str:
     return "\n".join(lines) + "\n"
 
 
-def summary_text(res, grid) -> str:
+def summary_text(res, grid, n_draws=None) -> str:
     n = len(res["index"])
-    return (f"{n} windows located on {' x '.join(str(c) for c in grid_counts(grid))} cells\n"
+    how = "" if n_draws is None else f", the structure marginalised over {n_draws} draws"
+    return (f"{n} windows located on {' x '.join(str(c) for c in grid_counts(grid))} cells{how}\n"
             f"{int(on_face(res['index'], grid).sum())} with the best cell on a face of the box (not resolved by this grid), "
             f"{int((res['index'] < 0).sum())} without an included cell\n")
 
@@ -196,11 +291,21 @@ def main(argv=None):
     ap.add_argument("--windows", metavar="FILE", help="window ids in the first column (default selected_win.dat)")
     ap.add_argument("--flat-prior", action="store_true", help="no prior on the position")
     ap.add_argument("--volume-of", type=int, metavar="WIN", help="also write this window's log posterior of every cell")
+    ap.add_argument("--draws", type=int, metavar="K", help="marginalise the structure over K evenly thinned records of the sample files "
+                    "in --structure DIR; writes hypo_grid_marginal.*")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    if args.draws is not None and args.draws < 1:
+        ap.error(f"--draws {args.draws}: need at least one draw")
     r5 = Step5Run.open(args.parameter_file, windows=args.windows)
     par, work, device, win_id = r5.par, r5.work, r5.device, r5.win_id
     grid = grid_from_args(ap, args, par)
-    vs, qs, t_corr, a_corr = read_structure(args.structure if args.structure else work, par.stations)
+    structure = args.structure if args.structure else work
+    if args.draws is None:
+        vs, qs, t_corr, a_corr = read_structure(structure, par.stations)
+        evaluate, stem = locate, "hypo_grid"
+    else:
+        vs, qs, t_corr, a_corr = read_structure_draws(structure, par.stations, par.n_stations, args.draws)
+        evaluate, stem = locate_marginal, "hypo_grid_marginal"
     if not win_id:
         raise SystemExit("ERROR: no window to locate")
 
@@ -209,23 +314,23 @@ def main(argv=None):
         fwd = Forward(par.n_stations, len(ids), par.sta_x, par.sta_y, par.sta_z, obs, use_amp=par.get_use_amp(), use_time=par.get_use_time(),
                       device=device)
         try:
-            return locate(fwd, t_corr, vs, a_corr, qs, grid, prior=None if args.flat_prior else step5_prior(par, obs), volume=volume)
+            return evaluate(fwd, t_corr, vs, a_corr, qs, grid, prior=None if args.flat_prior else step5_prior(par, obs), volume=volume)
         finally:
             fwd.close()
 
     res = run(win_id, False)
     marg = np.concatenate([res["marg_x"], res["marg_y"], res["marg_z"]], axis=1)
-    with open(os.path.join(work, "hypo_grid.stat"), "w") as fh:
+    with open(os.path.join(work, stem + ".stat"), "w") as fh:
         fh.write(stat_text(win_id, marginal_quantiles(marg, grid)))
-    with open(os.path.join(work, "hypo_grid.best.dat"), "w") as fh:
+    with open(os.path.join(work, stem + ".best.dat"), "w") as fh:
         fh.write(best_text(win_id, res, grid))
     if args.volume_of is not None:
         if args.volume_of not in win_id:
             raise SystemExit(f"ERROR: --volume-of {args.volume_of} is not among the windows")
         one = run([args.volume_of], True)
-        with open(os.path.join(work, "hypo_grid.%d.vol.dat" % args.volume_of), "w") as fh:
+        with open(os.path.join(work, stem + ".%d.vol.dat" % args.volume_of), "w") as fh:
             fh.write(volume_text(one["vol"][0], grid))
-    sys.stdout.write(summary_text(res, grid))
+    sys.stdout.write(summary_text(res, grid, args.draws))
 
 
 if __name__ == "__main__":

@@ -153,6 +153,23 @@ int htm_forward_time_full_batch_dev(htm_forward *h, int n_models, const double *
 int htm_forward_locate(htm_forward *h, const double *t_corr, double vs, const double *a_corr, double qs,
                        const double *grid9, const double *prior5, double *loc, double *marg, double *vol);
 
+/* The same with the structure MARGINALISED over n_draws draws of it: t_corr, a_corr [n_draws][n_sta], vs, qs
+ * [n_draws], host pointers -- draws of p(structure | calibration data), e.g. thinned records of a calibration run's sample
+ * files; 1 <= n_draws <= 4096.  The term of a cell is l = log((1 / n_draws) sum_k exp(l_k)), l_k the term htm_forward_locate
+ * takes there under draw k, evaluated as m + (log(sum_k exp(l_k - m)) - log n_draws) with m the largest l_k: one draw gives l_1
+ * itself, and the outputs of htm_forward_locate bit for bit; n equal draws give one draw's bits.  A cell where any l_k is NaN
+ * is NaN (a centre on a station, under every draw); a draw with l_k = -inf has weight 0, and a cell where every draw has is
+ * -inf.  lp = l + log prior, and everything from there on -- exclusion, loc (loc[5] is the marginalised l at the best cell),
+ * marg, vol, their layouts and error bounds -- is htm_forward_locate's; a cell's l is good to 1e-12 of the largest sum of
+ * absolute terms among its draws.
+ * Refused with HTM_EINVAL before any device call: whatever htm_forward_locate refuses; n_draws outside 1..4096; a vs[k] or
+ * qs[k] that is not finite or <= 0 (the message names the draw).  The table of the draws is part of the workspace under
+ * HTM_LOCATE_MB: when it and one event do not fit, HTM_EINVAL names the variable.  Synchronous; every sum has a fixed order,
+ * the draws are taken in their order: two calls give the same bits, and the bits do not depend on the batching. */
+int htm_forward_locate_marginal(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr,
+                                const double *qs, const double *grid9, const double *prior5, double *loc, double *marg,
+                                double *vol);
+
 /* ------------------------------------------------------------------------------------------------
  * Device-resident chains: `type mcmc` x n_chains inside `type parallel`
  *                          reference: src/cls_mcmc.f90, src/cls_parallel.f90, src/hypo_tremor_mcmc.f90
