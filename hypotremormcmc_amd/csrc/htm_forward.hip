@@ -514,11 +514,14 @@ int htm_forward_time_full_batch_dev(htm_forward *h, int n_models, const double *
 // The location posterior of every event of the handle on a grid, under a fixed structure or marginalised over draws of it
 // (include/htm_hip.h; kernels and the partial records: htm_locate.hpp).  The prior is separable: its three tables per event are
 // made here, on the host.  n_draws = 0: htm_forward_locate, one structure (t_corr, a_corr [S]; *vs, *qs) and k_locate;
-// n_draws >= 1: htm_forward_locate_marginal, t_corr, a_corr [n_draws][S], vs, qs [n_draws] and k_locate_marginal.
+// n_draws >= 1: htm_forward_locate_marginal, t_corr, a_corr [n_draws][S], vs, qs [n_draws] and k_locate_marginal; with log_z
+// htm_forward_locate_draw_evidence instead (loc, marg, vol NULL): k_locate_draw_evidence, k_locate_draw_combine, log_z [E][n_draws]
+// and summary [E][4] or NULL.
 static int locate_run(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr, const double *qs,
-                      const double *grid9, const double *prior5, double *loc, double *marg, double *vol)
+                      const double *grid9, const double *prior5, double *loc, double *marg, double *vol, double *log_z = nullptr,
+                      double *summary = nullptr)
 {
-    const bool draws = n_draws > 0;
+    const bool draws = n_draws > 0, evid = log_z != nullptr;
     int n[3];
     for (int a = 0; a < 3; ++a) {
         const double v0 = grid9[3 * a], dv = grid9[3 * a + 1], cnt = grid9[3 * a + 2];
@@ -547,9 +550,12 @@ static int locate_run(htm_forward *h, int n_draws, const double *t_corr, const d
     // (a tile that is not a layer's last holds more than 2048 cells or 256 rows of at most 16: at most 2^31 / 256 + 4096 tiles, 2^31 work-items per event)
     // events per batch: a launch's grid (y <= 65535, 2^32 - 1 work-items) and the workspace under HTM_LOCATE_MB MiB
     const long nm = (long)n[0] + n[1] + n[2];
-    const double per_event = sizeof(double) * ((double)n_tiles * g.stride + (vol ? (double)cells : 0.0) + 2.0 * nm + 16.0) + sizeof(LocSta) * (double)S + sizeof(LocEv);
     // the draws' table and the draws as they come (the pack kernel's input) are part of the workspace, once per call
     const int K = n_draws, Kpad = (K + kLocDraws - 1) / kLocDraws * kLocDraws;
+    // (the draws' evidences: a pair per tile and draw of the padded table, log_z and the summary, the prior's tables)
+    const double per_event = sizeof(double) * (evid ? (double)n_tiles * Kpad * 2.0 + K + 4.0 + nm
+                                                    : (double)n_tiles * g.stride + (vol ? (double)cells : 0.0) + 2.0 * nm + 16.0) +
+                             sizeof(LocSta) * (double)S + sizeof(LocEv);
     const double table = draws ? sizeof(LocPair) * ((double)S + 1.0) * Kpad + sizeof(double) * (2.0 * S + 2.0) * K : 0.0;
     if (draws && table + per_event > mb * 1048576.0)
         return fail(HTM_EINVAL, "HTM_LOCATE_MB = %g: the table of %d draws (%.0f bytes) and one event (%.0f bytes) do not fit", mb, K, table, per_event);
@@ -564,9 +570,13 @@ static int locate_run(htm_forward *h, int n_draws, const double *t_corr, const d
     DevPool pool;
     LocSta *d_sta = nullptr;
     LocEv *d_ev = nullptr;
-    double *d_prior = nullptr, *d_part = nullptr, *d_vol = nullptr, *d_loc = nullptr, *d_marg = nullptr;
-    if ((rc = pool.alloc(&d_sta, (size_t)nb * S)) || (rc = pool.alloc(&d_ev, (size_t)nb)) || (rc = pool.alloc(&d_part, (size_t)nb * n_tiles * g.stride)) ||
-        (rc = pool.alloc(&d_loc, (size_t)nb * 16)) || (rc = pool.alloc(&d_marg, (size_t)nb * nm)))
+    double *d_prior = nullptr, *d_part = nullptr, *d_vol = nullptr, *d_loc = nullptr, *d_marg = nullptr, *d_logz = nullptr, *d_sum = nullptr;
+    if ((rc = pool.alloc(&d_sta, (size_t)nb * S)) || (rc = pool.alloc(&d_ev, (size_t)nb))) return rc;
+    if (evid) {
+        if ((rc = pool.alloc(&d_part, (size_t)nb * n_tiles * Kpad * 2)) || (rc = pool.alloc(&d_logz, (size_t)nb * K)) || (rc = pool.alloc(&d_sum, (size_t)nb * 4)))
+            return rc;
+    } else if ((rc = pool.alloc(&d_part, (size_t)nb * n_tiles * g.stride)) || (rc = pool.alloc(&d_loc, (size_t)nb * 16)) ||
+               (rc = pool.alloc(&d_marg, (size_t)nb * nm)))
         return rc;
     if (prior5 && (rc = pool.alloc(&d_prior, (size_t)nb * nm))) return rc;
     if (vol && (rc = pool.alloc(&d_vol, (size_t)nb * cells))) return rc;
@@ -624,6 +634,13 @@ static int locate_run(htm_forward *h, int n_draws, const double *t_corr, const d
             case 2: hipLaunchKernelGGL(k_locate<2>, grid, block, 0, h->stream, g, jb); break;
             default: hipLaunchKernelGGL(k_locate<3>, grid, block, 0, h->stream, g, jb); break;
             }
+        else if (evid)
+            switch (mode) {
+            case 0: hipLaunchKernelGGL(k_locate_draw_evidence<0>, grid, block, 0, h->stream, g, jb, dr); break;
+            case 1: hipLaunchKernelGGL(k_locate_draw_evidence<1>, grid, block, 0, h->stream, g, jb, dr); break;
+            case 2: hipLaunchKernelGGL(k_locate_draw_evidence<2>, grid, block, 0, h->stream, g, jb, dr); break;
+            default: hipLaunchKernelGGL(k_locate_draw_evidence<3>, grid, block, 0, h->stream, g, jb, dr); break;
+            }
         else
             switch (mode) {
             case 0: hipLaunchKernelGGL(k_locate_marginal<0>, grid, block, 0, h->stream, g, jb, dr); break;
@@ -631,9 +648,17 @@ static int locate_run(htm_forward *h, int n_draws, const double *t_corr, const d
             case 2: hipLaunchKernelGGL(k_locate_marginal<2>, grid, block, 0, h->stream, g, jb, dr); break;
             default: hipLaunchKernelGGL(k_locate_marginal<3>, grid, block, 0, h->stream, g, jb, dr); break;
             }
-        hipLaunchKernelGGL(k_locate_combine, dim3((unsigned)m), dim3(256), 0, h->stream, g, d_part, log_cell, d_loc, d_marg);
+        if (evid)
+            hipLaunchKernelGGL(k_locate_draw_combine, dim3((unsigned)m), dim3(256), 0, h->stream, (int)n_tiles, K, Kpad, d_part, log_cell, d_logz, d_sum);
+        else
+            hipLaunchKernelGGL(k_locate_combine, dim3((unsigned)m), dim3(256), 0, h->stream, g, d_part, log_cell, d_loc, d_marg);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(h->stream));
+        if (evid) {
+            if ((rc = pool.download(log_z + (size_t)e0 * K, d_logz, (size_t)m * K, "the draws' evidences'"))) return rc;
+            if (summary && (rc = pool.download(summary + (size_t)e0 * 4, d_sum, (size_t)m * 4, "the draws' summary's"))) return rc;
+            continue;
+        }
         if ((rc = pool.download(loc + (size_t)e0 * 16, d_loc, (size_t)m * 16, "the locations'"))) return rc;
         if (marg && (rc = pool.download(marg + (size_t)e0 * nm, d_marg, (size_t)m * nm, "the marginals'"))) return rc;
         if (vol && (rc = pool.download(vol + (size_t)e0 * cells, d_vol, (size_t)m * cells, "the volume's"))) return rc;
@@ -651,16 +676,32 @@ int htm_forward_locate(htm_forward *h, const double *t_corr, double vs, const do
     return locate_run(h, 0, t_corr, &vs, a_corr, &qs, grid9, prior5, loc, marg, vol);
 }
 
+// what both entry points over draws ask of them
+static int locate_draws_ok(int n_draws, const double *vs, const double *qs)
+{
+    if (n_draws < 1 || n_draws > kLocMaxDraws) return fail(HTM_EINVAL, "n_draws = %d: need 1..%d", n_draws, kLocMaxDraws);
+    for (int k = 0; k < n_draws; ++k)
+        if (!std::isfinite(vs[k]) || !std::isfinite(qs[k]) || !(vs[k] > 0.0) || !(qs[k] > 0.0))
+            return fail(HTM_EINVAL, "draw %d: vs = %g, qs = %g: need finite values > 0", k, vs[k], qs[k]);
+    return HTM_OK;
+}
+
 int htm_forward_locate_marginal(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr, const double *qs,
                                 const double *grid9, const double *prior5, double *loc, double *marg, double *vol)
 {
     if (!h) return fail(HTM_EINVAL, "NULL handle");
     if (!t_corr || !vs || !a_corr || !qs || !grid9 || !loc) return fail(HTM_EINVAL, "NULL argument");
-    if (n_draws < 1 || n_draws > kLocMaxDraws) return fail(HTM_EINVAL, "n_draws = %d: need 1..%d", n_draws, kLocMaxDraws);
-    for (int k = 0; k < n_draws; ++k)
-        if (!std::isfinite(vs[k]) || !std::isfinite(qs[k]) || !(vs[k] > 0.0) || !(qs[k] > 0.0))
-            return fail(HTM_EINVAL, "draw %d: vs = %g, qs = %g: need finite values > 0", k, vs[k], qs[k]);
+    if (int rc = locate_draws_ok(n_draws, vs, qs)) return rc;
     return locate_run(h, n_draws, t_corr, vs, a_corr, qs, grid9, prior5, loc, marg, vol);
+}
+
+int htm_forward_locate_draw_evidence(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr, const double *qs,
+                                     const double *grid9, const double *prior5, double *log_z, double *summary)
+{
+    if (!h) return fail(HTM_EINVAL, "NULL handle");
+    if (!t_corr || !vs || !a_corr || !qs || !grid9 || !log_z) return fail(HTM_EINVAL, "NULL argument");
+    if (int rc = locate_draws_ok(n_draws, vs, qs)) return rc;
+    return locate_run(h, n_draws, t_corr, vs, a_corr, qs, grid9, prior5, nullptr, nullptr, nullptr, log_z, summary);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -20,6 +20,8 @@
 //   k_locate_pack_draws, k_locate_marginal<MODE>    htm_forward_locate_marginal: the structure marginalised over draws of it,
 //                     described where they stand, below k_locate; what follows a cell's log posterior is shared with k_locate
 //                     (loc_cell_done, loc_tile_reduce), and k_locate_combine serves both.
+//   k_locate_draw_evidence<MODE>, k_locate_draw_combine    htm_forward_locate_draw_evidence: every draw's log evidence per event
+//                     and what the draws weigh, described where they stand, below k_locate_marginal
 // No floating-point atomics anywhere: the bits do not depend on timing.  The volume of log posteriors is written only when it
 // is asked for.
 //
@@ -388,12 +390,71 @@ __global__ __launch_bounds__(256) void k_locate_pack_draws(int S, int K, int Kpa
 }
 
 // kLocDraws pairs at a wave-uniform, 16-byte aligned address through the constant address space: scalar loads
-__device__ __forceinline__ void loc_ld_pairs(const LocPair *p, double (&a)[kLocDraws], double (&b)[kLocDraws])
+template <int D>
+__device__ __forceinline__ void loc_ld_pairs(const LocPair *p, double (&a)[D], double (&b)[D])
 {
     typedef const loc_f64x2 __attribute__((address_space(4))) *CP;
     const CP q = (CP)(unsigned long long)p;
 #pragma unroll
-    for (int i = 0; i < kLocDraws; ++i) { const loc_f64x2 v = q[i]; a[i] = v[0]; b[i] = v[1]; }
+    for (int i = 0; i < D; ++i) { const loc_f64x2 v = q[i]; a[i] = v[0]; b[i] = v[1]; }
+}
+
+// k_locate_draw_evidence's station body (below).  It restates the one inside k_locate_marginal for one cell,
+// operation for operation; k_locate_marginal keeps its own copy because calling these from it changed its registers (187 ->
+// 157 VGPRs, 82 -> 98 SGPR spills in <3>), and its code is pinned.
+// The shifted one-pass demeaning of a cell under D draws, per data type: the shifts (station 0's residuals) and the running sums
+template <int D>
+struct LocSums {
+    double r0t[D], r0a[D], t1[D], t2[D], a1[D], a2[D];
+    __device__ __forceinline__ void clear()
+    {
+#pragma unroll
+        for (int q = 0; q < D; ++q) t1[q] = t2[q] = a1[q] = a2[q] = r0t[q] = r0a[q] = 0.0;
+    }
+};
+
+// Station j at the cell (x, y, zc) under the draws k0 .. k0 + D - 1 of the table, into the sums: the distance and its logarithm
+// once, then k_locate's expressions per draw.  FIRST: station 0, which gives the shifts -- the same operations (its u is
+// r - r, not a constant), so that the loop over the other stations carries no selection per draw
+template <int MODE, bool FIRST, int D>
+__device__ __forceinline__ void loc_draws_station(const LocSta *sta, const LocDraws &dr, int k0, int j, double x, double y, double zc,
+                                                  const double (&rbeta)[D], const double (&katt)[D], LocSums<D> &sm)
+{
+    constexpr bool UT = (MODE & 1) != 0, UA = (MODE & 2) != 0;
+    const LocSta st = loc_ld_sta(sta + j);
+    double tc[D], ac[D];
+    loc_ld_pairs(dr.corr + (size_t)j * dr.Kpad + k0, tc, ac);
+    const double dx = x - st.sx, dy = y - st.sy, dz = zc - st.sz;
+    const double d = htm_sqrt(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)));
+    double nld = 0.0;
+    if constexpr (UA) nld = -htm_log(d);
+#pragma unroll
+    for (int q = 0; q < D; ++q) {
+        if constexpr (UT) {
+            const double rt = __builtin_fma(d, rbeta[q], -tc[q]) - st.tob;
+            if constexpr (FIRST) sm.r0t[q] = rt;
+            const double u = rt - sm.r0t[q], pu = st.tpr * u;
+            sm.t1[q] += pu;
+            sm.t2[q] = __builtin_fma(pu, u, sm.t2[q]);
+        }
+        if constexpr (UA) {
+            const double ra = (__builtin_fma(-d, katt[q], nld) - ac[q]) - st.aob;
+            if constexpr (FIRST) sm.r0a[q] = ra;
+            const double u = ra - sm.r0a[q], pu = st.apr * u;
+            sm.a1[q] += pu;
+            sm.a2[q] = __builtin_fma(pu, u, sm.a2[q]);
+        }
+    }
+}
+
+// the cell's log-likelihood term under draw q from the finished sums, as k_locate forms it
+template <int MODE, int D>
+__device__ __forceinline__ double loc_draws_term(const LocSums<D> &sm, const LocEv &ev, int q)
+{
+    double e = 0.0;
+    if constexpr ((MODE & 1) != 0) e -= 0.5 * (sm.t2[q] - (sm.t1[q] * sm.t1[q]) * ev.rpst) + ev.ct;
+    if constexpr ((MODE & 2) != 0) e -= 0.5 * (sm.a2[q] - (sm.a1[q] * sm.a1[q]) * ev.rpsa) + ev.ca;
+    return e;
 }
 
 template <int MODE>
@@ -500,6 +561,153 @@ __global__ __launch_bounds__(256) void k_locate_marginal(LocGrid g, LocJob jb, L
         }
     }
     loc_tile_reduce(g, jb, tl, best, s_w, [&](int k) { return s_w[t + kLocThreads * k]; });
+}
+
+// ---- the evidence of every draw, and what the draws weigh for a window ----------------------------------
+// log_z[k] = log(sum over the included cells of exp(l_k + log prior) dx dy dz): what htm_forward_locate returns in loc[6] under
+// draw k.  The reduce is the opposite of k_locate_marginal's, a sum over CELLS for each draw, so the loops are swapped:
+//
+//   k_locate_draw_evidence  k_locate_marginal's grid, tiles, LocJob (vol unused), LocDraws and table.  A block of kLoceDraws
+//                           draws is the OUTER loop (block-uniform), the thread's cells t, t + 256, ... the inner one; per
+//                           (cell, station, block) the distance and its logarithm are formed once, by k_locate_marginal's
+//                           station body (restated for one cell: loc_draws_station, above).  A lane keeps (m_q, s_q), s = sum exp(v - m) over its included cells, per
+//                           draw of the block; after its cells the pairs are combined across the wave (the largest m by a xor
+//                           tree, every lane's s rescaled to it, the wave sums' fixed tree) and across the four waves (LDS,
+//                           wave order) into the tile's record part[event][tile][Kpad][2].  The padding's draws are never
+//                           written; a tile without an included cell writes (-inf, 0).
+//   k_locate_draw_combine   one workgroup per event, a thread per draw: the tiles in ascending order into log_z[k]; then over
+//                           the draws, in a fixed order, the largest log_z and its lowest index, S1 = sum exp(log_z - M),
+//                           S2 = sum exp(2 (log_z - M)): n_eff = S1^2 / S2, w_max = 1 / S1, log evidence of the mixture
+//                           M + (log S1 - log K).
+// No floating-point atomics: the bits depend on neither timing nor batching.
+#ifndef HTM_LOCE_DRAWS
+#define HTM_LOCE_DRAWS HTM_LOCM_DRAWS   // draws per block of k_locate_draw_evidence (measured: DESIGN.md 3.12)
+#endif
+constexpr int kLoceDraws = HTM_LOCE_DRAWS;
+static_assert(kLoceDraws >= 1 && kLocDraws % kLoceDraws == 0, "the table is padded to whole blocks of kLocDraws draws");
+
+// (m, s) += (mo, so), s = sum exp(v - m): the same bits whichever side is which (equal maxima: a plain sum)
+__device__ __forceinline__ void loc_ms_merge(double &m, double &s, double mo, double so)
+{
+    const bool mine = m >= mo;
+    const double hi = mine ? m : mo, lo = mine ? mo : m, s_hi = mine ? s : so, s_lo = mine ? so : s;
+    const double e = lo == -__builtin_inf() ? 0.0 : exp(lo - hi);      // (both -inf: nothing on either side)
+    m = hi; s = __builtin_fma(s_lo, e, s_hi);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_locate_draw_evidence(LocGrid g, LocJob jb, LocDraws dr)
+{
+    constexpr int D = kLoceDraws;
+    __shared__ double s_m[4][D], s_s[4][D];
+    const int t = threadIdx.x, lane = t & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
+    const LocTile tl = loc_tile(g, jb);
+    const int ncell = tl.ncell;
+    const double zc = tl.zc;
+    const LocSta *sta = jb.sta + (size_t)tl.b * jb.S;
+    const LocEv ev = loc_ld_ev(jb.ev + tl.b);
+    const double *prior = tl.prior;
+    double *rec = jb.part + ((size_t)tl.b * ((size_t)g.nz * g.tpl) + tl.tile) * ((size_t)dr.Kpad * 2);
+
+#pragma unroll 1
+    for (int k0 = 0; k0 < dr.K; k0 += D) {                      // (uniform) a block of draws
+        double rbeta[D], katt[D], m[D], s[D];
+        loc_ld_pairs(dr.vq + k0, rbeta, katt);
+#pragma unroll
+        for (int q = 0; q < D; ++q) { m[q] = -__builtin_inf(); s[q] = 0.0; }
+#pragma unroll 1
+        for (int c0 = 0; c0 < ncell; c0 += kLocThreads) {       // (block-uniform) the thread's cells
+            const int c = c0 + t, cc = c < ncell ? c : 0;      // (a thread without a cell evaluates cell 0 and drops it)
+            const int r = cc / g.nx, ix = cc - r * g.nx;
+            const double x = loc_centre(g.x0, g.dx, ix), y = loc_centre(g.y0, g.dy, tl.iy0 + r);
+            const double lpr = prior ? (prior[ix] + prior[g.nx + tl.iy0 + r]) + tl.pz : 0.0;
+            LocSums<D> sm;
+            sm.clear();
+            loc_draws_station<MODE, true>(sta, dr, k0, 0, x, y, zc, rbeta, katt, sm);
+            for (int j = 1; j < jb.S; ++j) loc_draws_station<MODE, false>(sta, dr, k0, j, x, y, zc, rbeta, katt, sm);
+#pragma unroll
+            for (int q = 0; q < D; ++q) {
+                const double ell = loc_draws_term<MODE>(sm, ev, q);
+                const double v = prior ? ell + lpr : ell;       // (loc_cell_done's log posterior)
+                if (c < ncell && loc_included(v)) {             // one exponential per (cell, draw)
+                    const bool up = v > m[q];
+                    const double e = exp(up ? m[q] - v : v - m[q]);
+                    s[q] = up ? __builtin_fma(s[q], e, 1.0) : s[q] + e;
+                    m[q] = up ? v : m[q];
+                }
+            }
+        }
+        // the block's D pairs.  Across the wave: the largest m (a xor tree of comparisons), every lane's s rescaled to it -- one
+        // exponential per draw -- and the wave sums' fixed tree; then the four waves in their order
+#pragma unroll
+        for (int q = 0; q < D; ++q) {
+            double mw = m[q];
+#pragma unroll
+            for (int off = 32; off; off >>= 1) { const double o = __shfl_xor(mw, off); mw = o > mw ? o : mw; }
+            s[q] = m[q] == -__builtin_inf() ? 0.0 : s[q] * exp(m[q] - mw);      // (a lane without an included cell: s = 0)
+            m[q] = mw;
+        }
+        wave_sum<D>(s);
+        __syncthreads();                                       // (the block before has been read)
+        if (lane == 0) {
+#pragma unroll
+            for (int q = 0; q < D; ++q) { s_m[wv][q] = m[q]; s_s[wv][q] = s[q]; }
+        }
+        __syncthreads();
+        if (t < D && k0 + t < dr.K) {                           // (the padding's draws are never written)
+            double mm = s_m[0][t], ss = s_s[0][t];
+            for (int w = 1; w < 4; ++w) loc_ms_merge(mm, ss, s_m[w][t], s_s[w][t]);
+            rec[2 * (size_t)(k0 + t)] = mm; rec[2 * (size_t)(k0 + t) + 1] = ss;
+        }
+    }
+}
+
+// One workgroup of 256 threads per event of the batch.  part [nb][n_tiles][Kpad][2], log_z [nb][K], summary [nb][4] = n_eff,
+// w_max, k_max, log evidence of the mixture.
+__global__ __launch_bounds__(256) void k_locate_draw_combine(int n_tiles, int K, int Kpad, const double *part, double log_cell, double *log_z,
+                                                             double *summary)
+{
+    __shared__ double s_red4[4];
+    __shared__ double s_blp[4];
+    __shared__ int s_bidx[4];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6, b = blockIdx.x;
+    const double *P = part + (size_t)b * n_tiles * ((size_t)Kpad * 2);
+    double *Z = log_z + (size_t)b * K;
+    // a thread per draw, the tiles in ascending order: neighbouring threads read neighbouring pairs
+    LocBest best{-__builtin_inf(), 0.0, INT_MAX};
+    for (int k = t; k < K; k += 256) {
+        double m = -__builtin_inf(), s = 0.0;
+        for (int i = 0; i < n_tiles; ++i) { const double mt = P[((size_t)i * Kpad + k) * 2]; m = mt > m ? mt : m; }
+        if (m != -__builtin_inf())
+            for (int i = 0; i < n_tiles; ++i) {
+                const double *r = P + ((size_t)i * Kpad + k) * 2;
+                s = __builtin_fma(r[1], exp(r[0] - m), s);      // (an empty tile: 0 exp(-inf))
+            }
+        const double z = m != -__builtin_inf() ? (m + htm_log(s)) + log_cell : -__builtin_inf();
+        Z[k] = z;
+        loc_better(best, z, 0.0, k);
+    }
+    // the largest log_z and its lowest index
+    loc_best_wave(best);
+    if (lane == 0) { s_blp[wv] = best.lp; s_bidx[wv] = best.idx; }
+    __syncthreads();
+    best = LocBest{s_blp[0], 0.0, s_bidx[0]};
+#pragma unroll
+    for (int w = 1; w < 4; ++w) loc_better(best, s_blp[w], 0.0, s_bidx[w]);
+    const double M = best.lp;
+    if (M == -__builtin_inf()) {        // (block-uniform) no included cell under any draw
+        if (t < 4) summary[(size_t)b * 4 + t] = t == 2 ? -1.0 : __builtin_nan("");
+        return;
+    }
+    // the weights relative to the heaviest draw: every thread its own draws in ascending order (it wrote them), then the fixed tree
+    double a1 = 0.0, a2 = 0.0;
+    for (int k = t; k < K; k += 256) { const double d = Z[k] - M; a1 += exp(d); a2 += exp(2.0 * d); }      // (exp(-inf) = 0)
+    const double S1 = loc_block_sum(a1, s_red4), S2 = loc_block_sum(a2, s_red4);
+    if (t == 0) {
+        double *R = summary + (size_t)b * 4;
+        R[0] = S1 * S1 / S2; R[1] = 1.0 / S1; R[2] = (double)best.idx; R[3] = M + (htm_log(S1) - htm_log((double)K));
+    }
 }
 
 // One workgroup of 256 threads per event of the batch.  loc [nb][16], marg [nb][nx + ny + nz] (always there: the moments are

@@ -21,6 +21,7 @@ module htm_c_api
   public :: htm_hypo_density, htm_hypo_density_dev
   public :: htm_forward_locate
   public :: htm_forward_locate_marginal
+  public :: htm_forward_locate_draw_evidence
   public :: htm_chains_checkpoint_size, htm_chains_checkpoint_save, htm_chains_checkpoint_load
 
   integer(c_size_t), parameter :: HTM_XCHG_HANDLE_BYTES = 64_c_size_t, HTM_COMM_ID_BYTES = 128_c_size_t
@@ -385,6 +386,20 @@ module htm_c_api
        type(c_ptr), value :: marg, vol
        integer(c_int) :: rc
      end function htm_forward_locate_marginal
+     !> every draw's log evidence per event and what the draws weigh (include/htm_hip.h): the inputs as above; log_z
+     !> (n_draws, n_events); summary (4, n_events) = n_eff, w_max, k_max (from 0), log evidence of the mixture, or c_null_ptr
+     function htm_forward_locate_draw_evidence(handle, n_draws, t_corr, vs, a_corr, qs, grid9, prior5, log_z, summary) &
+          & bind(C, name="htm_forward_locate_draw_evidence") result(rc)
+       import :: c_int, c_double, c_ptr
+       type(c_ptr), value :: handle
+       integer(c_int), value :: n_draws
+       real(c_double), intent(in) :: t_corr(*), vs(*), a_corr(*), qs(*)
+       real(c_double), intent(in) :: grid9(9)
+       type(c_ptr), value :: prior5
+       real(c_double), intent(out) :: log_z(*)
+       type(c_ptr), value :: summary
+       integer(c_int) :: rc
+     end function htm_forward_locate_draw_evidence
      !> step-4 regressions (include/htm_hip.h): t, t_err, a, a_err (n_sta, n_win); out (6, n_win) = vs, b, t0, a0, cc_t, cc_a
      function htm_select_regress(device, n_sta, n_win, sta_x, sta_y, sta_z, z_guess, t, t_err, a, a_err, out) &
           & bind(C, name="htm_select_regress") result(rc)

@@ -3,7 +3,7 @@ run's medians), a window's location posterior is a function of its position alon
 grid -- no MCMC, any number of windows (kernels in hypotremormcmc_amd/csrc/htm_locate.hpp).
 
     python -m hypotremormcmc_amd.locate <parameter file> --cell DX [DY DZ] [--bounds x0 x1 y0 y1 z0 z1] [--structure DIR]
-                                        [--windows FILE] [--flat-prior] [--volume-of WIN] [--draws K]
+                                        [--windows FILE] [--flat-prior] [--volume-of WIN] [--draws K [--draw-weights]]
 
 run in the data directory (station file, opt_data.NNNNNN.dat).  --structure DIR holds `uniform_structure.stat` and
 `station_corrections.stat` of the calibration run (default: the parameter file's directory); --windows FILE lists the window
@@ -22,6 +22,16 @@ and `a_corr.RR.out` in --structure DIR (read_structure_draws) stand for its post
 log((1 / K) sum_k exp(l_k)) over them (locate_marginal, one kernel for all draws), and the results are written next to the
 others, in the same layouts: `hypo_grid_marginal.stat`, `hypo_grid_marginal.best.dat`, `hypo_grid_marginal.WIN.vol.dat`.
 Without --draws nothing changes.
+
+Whether K was enough is a question per window: the mixture of a window can be carried by one or two draws, and its intervals
+are then a fixed structure's again.  --draws K --draw-weights answers it: the log evidence of every window
+under every draw (draw_evidence, one kernel for all draws), the normalised weights w_k of the draws per window and their
+effective number n_eff = 1 / sum_k w_k^2.  It writes `hypo_grid_marginal.draws.dat` (one line per window: n_eff, n_eff / K, the
+largest weight, the stacked record number of the draw that has it, the mixture's log evidence, and 1 when that weight is above
+0.5: one draw outweighs all the others together, K was too small for this window) and `hypo_grid_marginal.structure.dat` (one
+line per draw: its record number, vs, qs, and its joint weight over all windows -- the windows are independent given the
+structure, so the log weights add: which draws of the calibration posterior the located windows prefer), and adds one line to
+the summary.  Without --draw-weights nothing is written or printed that was not before.
 """
 from __future__ import annotations
 
@@ -38,6 +48,9 @@ from .obs_data import ObsData
 from .run_files import Step5Run, field
 from .statistics import HYPO_HEADER, INT_MAX
 
+DRAWS_HEADER = ("# window ID, effective number of the draws n_eff, n_eff / K, largest weight, record number of the draw that has it, "
+                "log evidence of the mixture, 1: that weight is above 0.5 (the intervals are one structure's)")
+STRUCTURE_HEADER = "# record number of the draw, vs, qs, joint log weight over all windows relative to the best draw, normalised joint weight"
 BEST_HEADER = ("# window ID, best cell's centre x y z, log posterior there, log-likelihood term there, log evidence, "
                "posterior mean x y z, 1: the best cell lies on a face of the box")
 
@@ -107,6 +120,57 @@ def locate_marginal(fwd, t_corr, vs, a_corr, qs, grid, prior=None, marginals=Tru
     _lib.check(_lib.load().htm_forward_locate_marginal(fwd.handle, K, _lib.ptr(tc), _lib.ptr(v), _lib.ptr(ac), _lib.ptr(q), _lib.ptr(g),
                                                        _lib.ptr(pr), _lib.ptr(loc), _lib.ptr(marg), _lib.ptr(vol)))
     return _result(loc, marg, vol, nx, ny)
+
+
+def draw_evidence(fwd, t_corr, vs, a_corr, qs, grid, prior=None):
+    """The inputs of `locate_marginal`.  Returns a dict: log_z [E][K], the log evidence `locate` gives under draw k alone
+    (-inf: no cell under that draw); with the normalised weights w_k = exp(log_z_k) / sum exp(log_z): n_eff [E] = 1 / sum_k
+    w_k^2, w_max [E], k_max [E] (int64; the lowest index of the largest weight, -1 for a window without a cell, whose n_eff,
+    w_max and log_evidence are NaN), log_evidence [E] = log((1 / K) sum_k exp(log_z_k)), `locate_marginal`'s
+    (htm_forward_locate_draw_evidence)."""
+    g = grid9(grid)
+    nx, ny, nz = grid_counts(g)
+    if nx * ny * nz > INT_MAX:
+        raise ValueError(f"{nx} x {ny} x {nz} cells: more than 2^31 - 1")
+    E, S = fwd.n_events, fwd.n_sta
+    v = np.ascontiguousarray(np.asarray(vs, dtype=np.float64).reshape(-1))
+    q = np.ascontiguousarray(np.asarray(qs, dtype=np.float64).reshape(-1))
+    K = v.size
+    tc = np.ascontiguousarray(np.asarray(t_corr, dtype=np.float64).reshape(-1))
+    ac = np.ascontiguousarray(np.asarray(a_corr, dtype=np.float64).reshape(-1))
+    if q.size != K or tc.size != K * S or ac.size != K * S:
+        raise ValueError(f"{K} draws of vs: need as many of qs (got {q.size}) and one t_corr and a_corr per draw and station "
+                         f"({K} x {S}; got {tc.size} and {ac.size} values)")
+    pr = _prior_array(prior, E)
+    log_z = np.empty((E, K))
+    summ = np.empty((E, 4))
+    _lib.check(_lib.load().htm_forward_locate_draw_evidence(fwd.handle, K, _lib.ptr(tc), _lib.ptr(v), _lib.ptr(ac), _lib.ptr(q), _lib.ptr(g),
+                                                            _lib.ptr(pr), _lib.ptr(log_z), _lib.ptr(summ)))
+    return {"log_z": log_z, "n_eff": summ[:, 0].copy(), "w_max": summ[:, 1].copy(), "k_max": summ[:, 2].astype(np.int64),
+            "log_evidence": summ[:, 3].copy()}
+
+
+def draw_weights(log_z):
+    """log_z [E][K] (or one row) -> the normalised weights of the draws per window, exp(log_z - max) over their sum; NaN for a
+    window without a cell (every log_z -inf)"""
+    z = np.asarray(log_z, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        w = np.exp(z - np.max(z, axis=-1, keepdims=True))
+    return w / np.sum(w, axis=-1, keepdims=True)
+
+
+def joint_draw_weights(log_z):
+    """log_z [E][K] -> (log_w [K], w [K]): the windows are independent given the structure, so a draw's joint log weight is
+    sum_w log_z[w][k] over the windows that have a cell; log_w is that minus its maximum, w = exp(log_w) normalised.  NaN when
+    no window has a cell, or no draw keeps a cell in all of them."""
+    z = np.asarray(log_z, dtype=np.float64)
+    z = z.reshape(-1, z.shape[-1])
+    tot = z[np.max(z, axis=1) > -np.inf].sum(axis=0)
+    if not (np.max(z, axis=1) > -np.inf).any() or not np.max(tot) > -np.inf:
+        return np.full(z.shape[1], np.nan), np.full(z.shape[1], np.nan)
+    log_w = tot - np.max(tot)
+    w = np.exp(log_w)
+    return log_w, w / w.sum()
 
 
 def _prior_array(prior, E):
@@ -190,12 +254,13 @@ def draw_records(n_rec: int, n_draws: int):
     return [((2 * i + 1) * n_rec) // (2 * n_draws) for i in range(n_draws)]
 
 
-def read_structure_draws(directory, station_names, n_sta, n_draws):
+def read_structure_draws(directory, station_names, n_sta, n_draws, records=False):
     """vs [K], qs [K], t_corr [K][n_sta], a_corr [K][n_sta]: K = n_draws records of the calibration run's sample files
     `vs.RR.out`, `qs.RR.out`, `t_corr.RR.out`, `a_corr.RR.out` in `directory`, the ranks RR = 00, 01, ... as far as `vs.RR.out`
     is there, stacked in rank order (Step5Run.samples: a rank's four files must record the same iterations) and thinned evenly
     (draw_records; no random numbers).  The sample files carry no station names: `station_corrections.stat` of the same
-    directory must list the stations of the station file, in its order."""
+    directory must list the stations of the station file, in its order.  With `records` the numbers of the kept records in the
+    stacked sample (draw_records) come fifth."""
     from types import SimpleNamespace
 
     K = int(n_draws)
@@ -223,7 +288,8 @@ def read_structure_draws(directory, station_names, n_sta, n_draws):
     if K > n_rec:
         raise ValueError(f"{K} draws asked for, {directory} holds {n_rec} records in {n_procs} rank(s)")
     keep = draw_records(n_rec, K)
-    return smp["vs"][keep, 0].copy(), smp["qs"][keep, 0].copy(), smp["t_corr"][keep].copy(), smp["a_corr"][keep].copy()
+    out = (smp["vs"][keep, 0].copy(), smp["qs"][keep, 0].copy(), smp["t_corr"][keep].copy(), smp["a_corr"][keep].copy())
+    return out + (keep,) if records else out
 
 
 def step5_prior(par, obs):
@@ -275,6 +341,35 @@ def volume_text(vol, grid) -> str:
     return "\n".join(lines) + "\n"
 
 
+def draws_text(win_id, ev, records) -> str:
+    """the text of hypo_grid_marginal.draws.dat from draw_evidence's result and the draws' record numbers"""
+    K = len(records)
+    lines = [DRAWS_HEADER]
+    for i, w in enumerate(win_id):
+        k = int(ev["k_max"][i])
+        lines.append("%9d" % w + field(ev["n_eff"][i], 15) + field(ev["n_eff"][i] / K, 15) + field(ev["w_max"][i], 15, 9)
+                     + "%9d" % (records[k] if k >= 0 else -1) + field(ev["log_evidence"][i], 15) + "%3d" % int(ev["w_max"][i] > 0.5))
+    return "\n".join(lines) + "\n"
+
+
+def structure_text(records, vs, qs, log_z) -> str:
+    """the text of hypo_grid_marginal.structure.dat: the draws' joint weights over all windows (joint_draw_weights)"""
+    log_w, w = joint_draw_weights(log_z)
+    lines = [STRUCTURE_HEADER]
+    for k, r in enumerate(records):
+        lines.append("%9d" % r + field(vs[k], 13) + field(qs[k], 13) + field(log_w[k], 15) + field(w[k], 15, 9))
+    return "\n".join(lines) + "\n"
+
+
+def draws_summary_text(ev, n_draws) -> str:
+    """the summary's line about the draws' weights"""
+    n_eff = ev["n_eff"][~np.isnan(ev["n_eff"])]
+    if n_eff.size == 0:
+        return f"the {n_draws} draws' effective number: no window has a cell\n"
+    return (f"the {n_draws} draws' effective number per window: median {np.median(n_eff):.2f}, smallest {n_eff.min():.2f}; "
+            f"{int((ev['w_max'] > 0.5).sum())} windows where one draw outweighs all the others (w_max > 0.5: their intervals are one structure's)\n")
+
+
 def summary_text(res, grid, n_draws=None) -> str:
     n = len(res["index"])
     how = "" if n_draws is None else f", the structure marginalised over {n_draws} draws"
@@ -293,9 +388,13 @@ def main(argv=None):
     ap.add_argument("--volume-of", type=int, metavar="WIN", help="also write this window's log posterior of every cell")
     ap.add_argument("--draws", type=int, metavar="K", help="marginalise the structure over K evenly thinned records of the sample files "
                     "in --structure DIR; writes hypo_grid_marginal.*")
+    ap.add_argument("--draw-weights", action="store_true", help="with --draws: also write what every draw weighs per window and their "
+                    "effective number (hypo_grid_marginal.draws.dat) and the draws' joint weights (hypo_grid_marginal.structure.dat)")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
     if args.draws is not None and args.draws < 1:
         ap.error(f"--draws {args.draws}: need at least one draw")
+    if args.draw_weights and args.draws is None:
+        ap.error("--draw-weights needs --draws K: the weights are those of the K draws")
     r5 = Step5Run.open(args.parameter_file, windows=args.windows)
     par, work, device, win_id = r5.par, r5.work, r5.device, r5.win_id
     grid = grid_from_args(ap, args, par)
@@ -304,21 +403,23 @@ def main(argv=None):
         vs, qs, t_corr, a_corr = read_structure(structure, par.stations)
         evaluate, stem = locate, "hypo_grid"
     else:
-        vs, qs, t_corr, a_corr = read_structure_draws(structure, par.stations, par.n_stations, args.draws)
+        vs, qs, t_corr, a_corr, records = read_structure_draws(structure, par.stations, par.n_stations, args.draws, records=True)
         evaluate, stem = locate_marginal, "hypo_grid_marginal"
     if not win_id:
         raise SystemExit("ERROR: no window to locate")
 
-    def run(ids, volume):
+    def run(ids, volume, weights=False):
         obs = ObsData(ids, par.n_stations, par.sta_x, par.sta_y, directory=work)
         fwd = Forward(par.n_stations, len(ids), par.sta_x, par.sta_y, par.sta_z, obs, use_amp=par.get_use_amp(), use_time=par.get_use_time(),
                       device=device)
         try:
-            return evaluate(fwd, t_corr, vs, a_corr, qs, grid, prior=None if args.flat_prior else step5_prior(par, obs), volume=volume)
+            prior = None if args.flat_prior else step5_prior(par, obs)
+            res = evaluate(fwd, t_corr, vs, a_corr, qs, grid, prior=prior, volume=volume)
+            return (res, draw_evidence(fwd, t_corr, vs, a_corr, qs, grid, prior=prior)) if weights else res
         finally:
             fwd.close()
 
-    res = run(win_id, False)
+    res, ev = run(win_id, False, True) if args.draw_weights else (run(win_id, False), None)
     marg = np.concatenate([res["marg_x"], res["marg_y"], res["marg_z"]], axis=1)
     with open(os.path.join(work, stem + ".stat"), "w") as fh:
         fh.write(stat_text(win_id, marginal_quantiles(marg, grid)))
@@ -331,6 +432,12 @@ def main(argv=None):
         with open(os.path.join(work, stem + ".%d.vol.dat" % args.volume_of), "w") as fh:
             fh.write(volume_text(one["vol"][0], grid))
     sys.stdout.write(summary_text(res, grid, args.draws))
+    if ev is not None:
+        with open(os.path.join(work, stem + ".draws.dat"), "w") as fh:
+            fh.write(draws_text(win_id, ev, records))
+        with open(os.path.join(work, stem + ".structure.dat"), "w") as fh:
+            fh.write(structure_text(records, vs, qs, ev["log_z"]))
+        sys.stdout.write(draws_summary_text(ev, args.draws))
 
 
 if __name__ == "__main__":

@@ -170,6 +170,28 @@ int htm_forward_locate_marginal(htm_forward *h, int n_draws, const double *t_cor
                                 const double *qs, const double *grid9, const double *prior5, double *loc, double *marg,
                                 double *vol);
 
+/* What every draw weighs for every window: the inputs of htm_forward_locate_marginal, and
+ * log_z [n_events][n_draws]: log_z[e][k] is the log evidence htm_forward_locate returns in loc[6] for event e under draw k, the
+ *   log of the sum of exp(lp) dx dy dz over the cells that are included UNDER THAT DRAW (a cell whose lp is NaN or -inf under
+ *   draw k is left out of draw k); -inf when draw k leaves no cell.  It is good to 2e-12 A, A the largest sum of absolute terms
+ *   of an included cell (1e-12 A a cell's value, as above; 1e-12 A the sums).
+ * summary [n_events][4] or NULL = {n_eff, w_max, k_max, log_evidence}: with the normalised weights w_k = exp(log_z_k) / sum_k'
+ *   exp(log_z_k'), the draws' effective number n_eff = 1 / sum_k w_k^2 (1 .. n_draws), the largest weight, the lowest index
+ *   that has it, and log((1 / n_draws) sum_k exp(log_z_k)).  log_evidence equals htm_forward_locate_marginal's loc[6] to the same
+ *   2e-12 A whenever a cell's NaN pattern is the same under all draws, which finite corrections always give.  An event with no
+ *   included cell under any draw: log_z -inf throughout, n_eff, w_max, log_evidence NaN, k_max -1.
+ * n equal draws give n equal columns bit for bit, n_eff == n_draws and w_max == 1 / n_draws exactly.  n_eff near 1 (w_max >
+ * 0.5: one draw outweighs all the others together) says that the marginalised intervals of that window are one structure's:
+ * n_draws was too small for it.
+ * Refused with HTM_EINVAL before any device call: whatever htm_forward_locate_marginal refuses, with its messages, and a NULL
+ * log_z.  The workspace of an event is n_tiles * Kpad * 2 + n_draws + 4 doubles (Kpad: n_draws padded to whole blocks of 8)
+ * next to its prior tables and station records; it and the draws' table stay under HTM_LOCATE_MB as there, and when the table
+ * and one event do not fit, HTM_EINVAL names the variable.  Synchronous; every sum has a fixed order and there are no
+ * floating-point atomics: two calls give the same bits, and the bits do not depend on the batching. */
+int htm_forward_locate_draw_evidence(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr,
+                                     const double *qs, const double *grid9, const double *prior5, double *log_z,
+                                     double *summary);
+
 /* ------------------------------------------------------------------------------------------------
  * Device-resident chains: `type mcmc` x n_chains inside `type parallel`
  *                          reference: src/cls_mcmc.f90, src/cls_parallel.f90, src/hypo_tremor_mcmc.f90
