@@ -180,6 +180,18 @@ int ensure_obs_pack(htm_forward *h)
     return HTM_OK;
 }
 
+// f(std::integral_constant<int, MODE>()) for the run-time mode 0 .. 3 (1: travel times, 2: amplitudes): a kernel family's instantiation
+template <class F>
+static void with_mode(int mode, F f)
+{
+    switch (mode) {
+    case 0: f(std::integral_constant<int, 0>()); break;
+    case 1: f(std::integral_constant<int, 1>()); break;
+    case 2: f(std::integral_constant<int, 2>()); break;
+    default: f(std::integral_constant<int, 3>()); break;
+    }
+}
+
 }  // namespace htm
 
 // ====================================================================================================
@@ -627,27 +639,12 @@ static int locate_run(htm_forward *h, int n_draws, const double *t_corr, const d
         hipLaunchKernelGGL(k_locate_pack, dim3((unsigned)((m * S + 255) / 256)), dim3(256), 0, h->stream, h->dev, (int)e0, (int)m, h->d_tc, h->d_ac,
                            h->d_lconst_t, h->d_lconst_a, d_sta, d_ev);
         const dim3 grid((unsigned)n_tiles, (unsigned)m), block(kLocThreads);
-        if (!draws)
-            switch (mode) {
-            case 0: hipLaunchKernelGGL(k_locate<0>, grid, block, 0, h->stream, g, jb); break;
-            case 1: hipLaunchKernelGGL(k_locate<1>, grid, block, 0, h->stream, g, jb); break;
-            case 2: hipLaunchKernelGGL(k_locate<2>, grid, block, 0, h->stream, g, jb); break;
-            default: hipLaunchKernelGGL(k_locate<3>, grid, block, 0, h->stream, g, jb); break;
-            }
-        else if (evid)
-            switch (mode) {
-            case 0: hipLaunchKernelGGL(k_locate_draw_evidence<0>, grid, block, 0, h->stream, g, jb, dr); break;
-            case 1: hipLaunchKernelGGL(k_locate_draw_evidence<1>, grid, block, 0, h->stream, g, jb, dr); break;
-            case 2: hipLaunchKernelGGL(k_locate_draw_evidence<2>, grid, block, 0, h->stream, g, jb, dr); break;
-            default: hipLaunchKernelGGL(k_locate_draw_evidence<3>, grid, block, 0, h->stream, g, jb, dr); break;
-            }
-        else
-            switch (mode) {
-            case 0: hipLaunchKernelGGL(k_locate_marginal<0>, grid, block, 0, h->stream, g, jb, dr); break;
-            case 1: hipLaunchKernelGGL(k_locate_marginal<1>, grid, block, 0, h->stream, g, jb, dr); break;
-            case 2: hipLaunchKernelGGL(k_locate_marginal<2>, grid, block, 0, h->stream, g, jb, dr); break;
-            default: hipLaunchKernelGGL(k_locate_marginal<3>, grid, block, 0, h->stream, g, jb, dr); break;
-            }
+        with_mode(mode, [&](auto M) {
+            constexpr int MODE = decltype(M)::value;
+            if (!draws) hipLaunchKernelGGL(k_locate<MODE>, grid, block, 0, h->stream, g, jb);
+            else if (evid) hipLaunchKernelGGL(k_locate_draw_evidence<MODE>, grid, block, 0, h->stream, g, jb, dr);
+            else hipLaunchKernelGGL(k_locate_marginal<MODE>, grid, block, 0, h->stream, g, jb, dr);
+        });
         if (evid)
             hipLaunchKernelGGL(k_locate_draw_combine, dim3((unsigned)m), dim3(256), 0, h->stream, (int)n_tiles, K, Kpad, d_part, log_cell, d_logz, d_sum);
         else

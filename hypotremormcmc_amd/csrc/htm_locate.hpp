@@ -10,8 +10,8 @@
 //                     workgroup reads it with uniform SCALAR loads (ld_const), and one record of constants per event
 //   k_locate<MODE>    grid = (tiles, events of the batch).  A tile is up to kLocRows whole x-rows of ONE z-layer, at most
 //                     kLocTile cells; a thread owns the cells t, t + 256, ... of it, kLocChunk at a time (independent
-//                     dependency chains).  The demeaned misfit comes in one pass from the shifted identity
-//                     sum p (r - m)^2 = sum p u^2 - (sum p u)^2 / sum p, u = r - r_0 (r_0: the first station's residual).
+//                     dependency chains).  The demeaned misfit comes in one pass from the shifted identity (loc_station,
+//                     loc_term: the station arithmetic of all three kernel families, stated once).
 //                     The lanes keep their cells' log posteriors in registers, the workgroup finds the tile's maximum and
 //                     its first cell, puts the weights exp(lp - max) in LDS and sums them there in a fixed order: per x-row
 //                     (a wave per row, the fixed-tree wave sum) and per ix over the rows.  One partial record per tile.
@@ -37,9 +37,6 @@
 
 namespace htm {
 
-#ifndef HTM_LOC_DEMEAN
-#define HTM_LOC_DEMEAN 0   // 0: the shifted one-pass identity; 1: two passes, the synthetics computed twice (measured: DESIGN.md 3.10)
-#endif
 constexpr int kLocMaxCells = 4096;      // cells per axis: the limit of htm_hypo_density (kDensMaxCells)
 constexpr int kLocThreads = 256;
 constexpr int kLocPerThread = 16;       // cells of a tile per thread
@@ -254,11 +251,89 @@ __device__ __forceinline__ void loc_tile_reduce(const LocGrid &g, const LocJob &
     }
 }
 
-// MODE: 1 travel times only, 2 amplitudes only, 3 both
+struct __attribute__((aligned(16))) LocPair {
+    double a, b;
+};
+// D pairs at a wave-uniform, 16-byte aligned address through the constant address space: scalar loads
+template <int D>
+__device__ __forceinline__ void loc_ld_pairs(const LocPair *p, double (&a)[D], double (&b)[D])
+{
+    typedef const loc_f64x2 __attribute__((address_space(4))) *CP;
+    const CP q = (CP)(unsigned long long)p;
+#pragma unroll
+    for (int i = 0; i < D; ++i) { const loc_f64x2 v = q[i]; a[i] = v[0]; b[i] = v[1]; }
+}
+
+// Cell c of a tile of ncell cells whose first x-row is iy0: its centre's x and y and its log prior in x and y from the event's
+// tables (nullptr: flat).  A thread without that cell takes cell 0 and drops it
+__device__ __forceinline__ void loc_cell_xy(const LocGrid &g, int iy0, int ncell, const double *prior, int c, double &x, double &y, double &pxy)
+{
+    const int cc = c < ncell ? c : 0;
+    const int r = cc / g.nx, ix = cc - r * g.nx;
+    x = loc_centre(g.x0, g.dx, ix);
+    y = loc_centre(g.y0, g.dy, iy0 + r);
+    pxy = prior ? prior[ix] + prior[g.nx + iy0 + r] : 0.0;
+}
+
+// ---- the station body of k_locate, k_locate_marginal and k_locate_draw_evidence ------------------------------------------
+// The demeaned misfit of a cell comes in one pass from the shifted identity sum p (r - m)^2 = sum p u^2 - (sum p u)^2 / sum p,
+// u = r - r_0 (r_0: the first station's residual).  Per data type and per structure (D of them side by side: one for k_locate,
+// a block of draws for the other two): the shifts and the running sums
+template <int D>
+struct LocSums {
+    double r0t[D], r0a[D], t1[D], t2[D], a1[D], a2[D];
+    __device__ __forceinline__ void clear()
+    {
+#pragma unroll
+        for (int q = 0; q < D; ++q) t1[q] = t2[q] = a1[q] = a2[q] = r0t[q] = r0a[q] = 0.0;
+    }
+};
+
+// The station st at the cell (x, y, zc) under D structures (1 / vs, pi f / (qs vs), the station's corrections tc, ac), into the
+// sums: the distance and its logarithm once, then per structure the residuals (synthetic minus observation: cls_forward.f90:
+// 115-118, :201-204 as event_misfit) and their shifted sums.  first: station 0, which gives the shifts by the same operations
+// (its u is r - r, not a constant).  MODE: 1 travel times only, 2 amplitudes only, 3 both
+template <int MODE, int D>
+__device__ __forceinline__ void loc_station(const LocSta &st, const double (&tc)[D], const double (&ac)[D], bool first, double x, double y, double zc,
+                                            const double (&rbeta)[D], const double (&katt)[D], LocSums<D> &sm)
+{
+    constexpr bool UT = (MODE & 1) != 0, UA = (MODE & 2) != 0;
+    const double dx = x - st.sx, dy = y - st.sy, dz = zc - st.sz;
+    const double d = htm_sqrt(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)));
+    double nld = 0.0;
+    if constexpr (UA) nld = -htm_log(d);
+#pragma unroll
+    for (int q = 0; q < D; ++q) {
+        if constexpr (UT) {
+            const double rt = __builtin_fma(d, rbeta[q], -tc[q]) - st.tob;
+            if (first) sm.r0t[q] = rt;
+            const double u = rt - sm.r0t[q], pu = st.tpr * u;
+            sm.t1[q] += pu;
+            sm.t2[q] = __builtin_fma(pu, u, sm.t2[q]);
+        }
+        if constexpr (UA) {
+            const double ra = (__builtin_fma(-d, katt[q], nld) - ac[q]) - st.aob;
+            if (first) sm.r0a[q] = ra;
+            const double u = ra - sm.r0a[q], pu = st.apr * u;
+            sm.a1[q] += pu;
+            sm.a2[q] = __builtin_fma(pu, u, sm.a2[q]);
+        }
+    }
+}
+
+// the cell's log-likelihood term under structure q from the finished sums
+template <int MODE, int D>
+__device__ __forceinline__ double loc_term(const LocSums<D> &sm, const LocEv &ev, int q)
+{
+    double e = 0.0;
+    if constexpr ((MODE & 1) != 0) e -= 0.5 * (sm.t2[q] - (sm.t1[q] * sm.t1[q]) * ev.rpst) + ev.ct;
+    if constexpr ((MODE & 2) != 0) e -= 0.5 * (sm.a2[q] - (sm.a1[q] * sm.a1[q]) * ev.rpsa) + ev.ca;
+    return e;
+}
+
 template <int MODE>
 __global__ __launch_bounds__(256) void k_locate(LocGrid g, LocJob jb)
 {
-    constexpr bool UT = (MODE & 1) != 0, UA = (MODE & 2) != 0;
     __shared__ double s_w[kLocTile];
     const int t = threadIdx.x;
     const LocTile tl = loc_tile(g, jb);
@@ -267,13 +342,14 @@ __global__ __launch_bounds__(256) void k_locate(LocGrid g, LocJob jb)
     const LocSta *sta = jb.sta + (size_t)tl.b * jb.S;
     const LocEv ev = loc_ld_ev(jb.ev + tl.b);
     const double *prior = tl.prior;
+    const double rbeta[1] = {jb.rbeta}, katt[1] = {jb.katt};
 
     double lp[kLocPerThread];
     LocBest best{-__builtin_inf(), 0.0, INT_MAX};
 #pragma unroll
     for (int ch = 0; ch < kLocPerThread / kLocChunk; ++ch) {
         double x[kLocChunk], y[kLocChunk], pxy[kLocChunk];
-        double r0t[kLocChunk], r0a[kLocChunk], t1[kLocChunk], t2[kLocChunk], a1[kLocChunk], a2[kLocChunk];
+        LocSums<1> sm[kLocChunk];
         if (ch * kLocChunk * kLocThreads >= ncell) {      // (block-uniform: no cell of this chunk exists)
 #pragma unroll
             for (int k = 0; k < kLocChunk; ++k) lp[ch * kLocChunk + k] = __builtin_nan("");
@@ -281,79 +357,18 @@ __global__ __launch_bounds__(256) void k_locate(LocGrid g, LocJob jb)
         }
 #pragma unroll
         for (int k = 0; k < kLocChunk; ++k) {
-            const int c = t + kLocThreads * (ch * kLocChunk + k), cc = c < ncell ? c : 0;      // (a thread without a cell evaluates cell 0 and drops it)
-            const int r = cc / g.nx, ix = cc - r * g.nx;
-            x[k] = loc_centre(g.x0, g.dx, ix);
-            y[k] = loc_centre(g.y0, g.dy, iy0 + r);
-            pxy[k] = prior ? prior[ix] + prior[g.nx + iy0 + r] : 0.0;
-            t1[k] = t2[k] = a1[k] = a2[k] = r0t[k] = r0a[k] = 0.0;
+            loc_cell_xy(g, iy0, ncell, prior, t + kLocThreads * (ch * kLocChunk + k), x[k], y[k], pxy[k]);
+            sm[k].clear();
         }
-        // a station's residuals (synthetic minus observation) at cell k of the chunk: cls_forward.f90:115-118, :201-204 as event_misfit
-        auto resid = [&](const LocSta &st, int k, double &rt, double &ra) {
-            const double dx = x[k] - st.sx, dy = y[k] - st.sy, dz = zc - st.sz;
-            const double d = htm_sqrt(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)));
-            if constexpr (UT) rt = __builtin_fma(d, jb.rbeta, -st.tc) - st.tob;
-            if constexpr (UA) ra = (__builtin_fma(-d, jb.katt, -htm_log(d)) - st.ac) - st.aob;
-        };
-#if HTM_LOC_DEMEAN == 0
-        // station 0 gives the shifts (its own u is exactly 0), stations 1 .. S - 1 add to the sums
         for (int j = 0; j < jb.S; ++j) {
             const LocSta st = loc_ld_sta(sta + j);
+            const double tc[1] = {st.tc}, ac[1] = {st.ac};
 #pragma unroll
-            for (int k = 0; k < kLocChunk; ++k) {
-                double rt = 0.0, ra = 0.0;
-                resid(st, k, rt, ra);
-                if constexpr (UT) {
-                    if (j == 0) r0t[k] = rt;
-                    const double u = rt - r0t[k], pu = st.tpr * u;
-                    t1[k] += pu;
-                    t2[k] = __builtin_fma(pu, u, t2[k]);
-                }
-                if constexpr (UA) {
-                    if (j == 0) r0a[k] = ra;
-                    const double u = ra - r0a[k], pu = st.apr * u;
-                    a1[k] += pu;
-                    a2[k] = __builtin_fma(pu, u, a2[k]);
-                }
-            }
+            for (int k = 0; k < kLocChunk; ++k) loc_station<MODE>(st, tc, ac, j == 0, x[k], y[k], zc, rbeta, katt, sm[k]);
         }
 #pragma unroll
-        for (int k = 0; k < kLocChunk; ++k) {       // sum p (r - m)^2 = sum p u^2 - (sum p u)^2 / sum p
-            t2[k] -= (t1[k] * t1[k]) * ev.rpst;
-            a2[k] -= (a1[k] * a1[k]) * ev.rpsa;
-        }
-#else
-        // the reference's two passes, the synthetics computed twice
-        for (int j = 0; j < jb.S; ++j) {
-            const LocSta st = loc_ld_sta(sta + j);
-#pragma unroll
-            for (int k = 0; k < kLocChunk; ++k) {
-                double rt = 0.0, ra = 0.0;
-                resid(st, k, rt, ra);
-                if constexpr (UT) t1[k] = __builtin_fma(st.tpr, rt, t1[k]);
-                if constexpr (UA) a1[k] = __builtin_fma(st.apr, ra, a1[k]);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < kLocChunk; ++k) { r0t[k] = t1[k] * ev.rpst; r0a[k] = a1[k] * ev.rpsa; }
-        for (int j = 0; j < jb.S; ++j) {
-            const LocSta st = loc_ld_sta(sta + j);
-#pragma unroll
-            for (int k = 0; k < kLocChunk; ++k) {
-                double rt = 0.0, ra = 0.0;
-                resid(st, k, rt, ra);
-                if constexpr (UT) { const double e = rt - r0t[k]; t2[k] = __builtin_fma(st.tpr * e, e, t2[k]); }
-                if constexpr (UA) { const double e = ra - r0a[k]; a2[k] = __builtin_fma(st.apr * e, e, a2[k]); }
-            }
-        }
-#endif
-#pragma unroll
-        for (int k = 0; k < kLocChunk; ++k) {
-            double ell = 0.0;
-            if constexpr (UT) ell -= 0.5 * t2[k] + ev.ct;
-            if constexpr (UA) ell -= 0.5 * a2[k] + ev.ca;
-            lp[ch * kLocChunk + k] = loc_cell_done(g, jb, tl, t + kLocThreads * (ch * kLocChunk + k), ell, pxy[k], best);
-        }
+        for (int k = 0; k < kLocChunk; ++k)
+            lp[ch * kLocChunk + k] = loc_cell_done(g, jb, tl, t + kLocThreads * (ch * kLocChunk + k), loc_term<MODE>(sm[k], ev, 0), pxy[k], best);
     }
     loc_tile_reduce(g, jb, tl, best, s_w, [&](int k) { return lp[k]; });
 }
@@ -361,7 +376,8 @@ __global__ __launch_bounds__(256) void k_locate(LocGrid g, LocJob jb)
 // ---- the structure marginalised over K draws -----------------------------------------------------------
 // The term of a cell becomes log((1 / K) sum_k exp(l_k)), l_k the term k_locate evaluates under draw k's structure.  The
 // distance of a (cell, station) and its logarithm do not depend on the structure: a lane forms them ONCE per block of
-// kLocDraws draws and then applies every draw's 1 / vs, pi f / (qs vs) and corrections to them, with k_locate's expressions.
+// kLocDraws draws and then applies every draw's 1 / vs, pi f / (qs vs) and corrections to them: loc_station, which k_locate
+// calls with one structure.
 //
 //   k_locate_pack_draws  the draws' table: {1 / vs_k, pi f / (qs_k vs_k)} per draw and {t_corr_kj, a_corr_kj} per (station,
 //                        draw), [station][draw] with the draws padded to whole blocks (the padding repeats the last draw and
@@ -370,9 +386,6 @@ __global__ __launch_bounds__(256) void k_locate(LocGrid g, LocJob jb)
 //                        draws the station loop runs once.  Across the blocks a cell keeps (m, s), s = sum_k exp(l_k - m);
 //                        the cells' log posteriors go to the LDS array that holds the weights afterwards (a thread's own
 //                        words), so the loop over a thread's cells is a loop, not sixteen copies of the code.
-struct __attribute__((aligned(16))) LocPair {
-    double a, b;
-};
 struct LocDraws {
     const LocPair *vq;      // [Kpad] {1 / vs, pi f / (qs vs)}
     const LocPair *corr;    // [S][Kpad] {t_corr, a_corr}
@@ -389,78 +402,9 @@ __global__ __launch_bounds__(256) void k_locate_pack_draws(int S, int K, int Kpa
     else corr[i] = LocPair{tc[(size_t)k * S + j], ac[(size_t)k * S + j]};
 }
 
-// kLocDraws pairs at a wave-uniform, 16-byte aligned address through the constant address space: scalar loads
-template <int D>
-__device__ __forceinline__ void loc_ld_pairs(const LocPair *p, double (&a)[D], double (&b)[D])
-{
-    typedef const loc_f64x2 __attribute__((address_space(4))) *CP;
-    const CP q = (CP)(unsigned long long)p;
-#pragma unroll
-    for (int i = 0; i < D; ++i) { const loc_f64x2 v = q[i]; a[i] = v[0]; b[i] = v[1]; }
-}
-
-// k_locate_draw_evidence's station body (below).  It restates the one inside k_locate_marginal for one cell,
-// operation for operation; k_locate_marginal keeps its own copy because calling these from it changed its registers (187 ->
-// 157 VGPRs, 82 -> 98 SGPR spills in <3>), and its code is pinned.
-// The shifted one-pass demeaning of a cell under D draws, per data type: the shifts (station 0's residuals) and the running sums
-template <int D>
-struct LocSums {
-    double r0t[D], r0a[D], t1[D], t2[D], a1[D], a2[D];
-    __device__ __forceinline__ void clear()
-    {
-#pragma unroll
-        for (int q = 0; q < D; ++q) t1[q] = t2[q] = a1[q] = a2[q] = r0t[q] = r0a[q] = 0.0;
-    }
-};
-
-// Station j at the cell (x, y, zc) under the draws k0 .. k0 + D - 1 of the table, into the sums: the distance and its logarithm
-// once, then k_locate's expressions per draw.  FIRST: station 0, which gives the shifts -- the same operations (its u is
-// r - r, not a constant), so that the loop over the other stations carries no selection per draw
-template <int MODE, bool FIRST, int D>
-__device__ __forceinline__ void loc_draws_station(const LocSta *sta, const LocDraws &dr, int k0, int j, double x, double y, double zc,
-                                                  const double (&rbeta)[D], const double (&katt)[D], LocSums<D> &sm)
-{
-    constexpr bool UT = (MODE & 1) != 0, UA = (MODE & 2) != 0;
-    const LocSta st = loc_ld_sta(sta + j);
-    double tc[D], ac[D];
-    loc_ld_pairs(dr.corr + (size_t)j * dr.Kpad + k0, tc, ac);
-    const double dx = x - st.sx, dy = y - st.sy, dz = zc - st.sz;
-    const double d = htm_sqrt(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)));
-    double nld = 0.0;
-    if constexpr (UA) nld = -htm_log(d);
-#pragma unroll
-    for (int q = 0; q < D; ++q) {
-        if constexpr (UT) {
-            const double rt = __builtin_fma(d, rbeta[q], -tc[q]) - st.tob;
-            if constexpr (FIRST) sm.r0t[q] = rt;
-            const double u = rt - sm.r0t[q], pu = st.tpr * u;
-            sm.t1[q] += pu;
-            sm.t2[q] = __builtin_fma(pu, u, sm.t2[q]);
-        }
-        if constexpr (UA) {
-            const double ra = (__builtin_fma(-d, katt[q], nld) - ac[q]) - st.aob;
-            if constexpr (FIRST) sm.r0a[q] = ra;
-            const double u = ra - sm.r0a[q], pu = st.apr * u;
-            sm.a1[q] += pu;
-            sm.a2[q] = __builtin_fma(pu, u, sm.a2[q]);
-        }
-    }
-}
-
-// the cell's log-likelihood term under draw q from the finished sums, as k_locate forms it
-template <int MODE, int D>
-__device__ __forceinline__ double loc_draws_term(const LocSums<D> &sm, const LocEv &ev, int q)
-{
-    double e = 0.0;
-    if constexpr ((MODE & 1) != 0) e -= 0.5 * (sm.t2[q] - (sm.t1[q] * sm.t1[q]) * ev.rpst) + ev.ct;
-    if constexpr ((MODE & 2) != 0) e -= 0.5 * (sm.a2[q] - (sm.a1[q] * sm.a1[q]) * ev.rpsa) + ev.ca;
-    return e;
-}
-
 template <int MODE>
 __global__ __launch_bounds__(256) void k_locate_marginal(LocGrid g, LocJob jb, LocDraws dr)
 {
-    constexpr bool UT = (MODE & 1) != 0, UA = (MODE & 2) != 0;
     constexpr int C = kLocmCells, D = kLocDraws;
     __shared__ double s_w[kLocTile];
     const int t = threadIdx.x;
@@ -479,65 +423,34 @@ __global__ __launch_bounds__(256) void k_locate_marginal(LocGrid g, LocJob jb, L
         bool bad[C];
 #pragma unroll
         for (int k = 0; k < C; ++k) {
-            const int c = t + kLocThreads * (ch * C + k), cc = c < ncell ? c : 0;      // (a thread without a cell evaluates cell 0 and drops it)
-            const int r = cc / g.nx, ix = cc - r * g.nx;
-            x[k] = loc_centre(g.x0, g.dx, ix);
-            y[k] = loc_centre(g.y0, g.dy, tl.iy0 + r);
-            pxy[k] = prior ? prior[ix] + prior[g.nx + tl.iy0 + r] : 0.0;
+            loc_cell_xy(g, tl.iy0, ncell, prior, t + kLocThreads * (ch * C + k), x[k], y[k], pxy[k]);
             m[k] = -__builtin_inf(); s[k] = 0.0; bad[k] = false;
         }
 #pragma unroll 1
         for (int k0 = 0; k0 < dr.K; k0 += D) {                  // (uniform) a block of draws
             double rbeta[D], katt[D];
             loc_ld_pairs(dr.vq + k0, rbeta, katt);
-            double r0t[C][D], r0a[C][D], t1[C][D], t2[C][D], a1[C][D], a2[C][D];
+            LocSums<D> sm[C];
 #pragma unroll
-            for (int k = 0; k < C; ++k)
-#pragma unroll
-                for (int q = 0; q < D; ++q) t1[k][q] = t2[k][q] = a1[k][q] = a2[k][q] = r0t[k][q] = r0a[k][q] = 0.0;
-            // station 0 gives the shifts, stations 1 .. S - 1 add to the sums: k_locate's one-pass form, per draw.  Station 0 is
-            // evaluated by a copy of the body of its own (the same operations: its u is r - r, not a constant), so that the loop
-            // carries no selection per draw
-            auto station = [&](int j, auto first) {
+            for (int k = 0; k < C; ++k) sm[k].clear();
+            // a station's records are loaded once and serve the thread's cells; station 0 has a call of its own, so that the loop
+            // over the others carries no selection per draw
+            auto station = [&](int j, bool first) {
                 const LocSta st = loc_ld_sta(sta + j);
                 double tc[D], ac[D];
                 loc_ld_pairs(dr.corr + (size_t)j * dr.Kpad + k0, tc, ac);
 #pragma unroll
-                for (int k = 0; k < C; ++k) {
-                    const double dx = x[k] - st.sx, dy = y[k] - st.sy, dz = zc - st.sz;
-                    const double d = htm_sqrt(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)));
-                    double nld = 0.0;
-                    if constexpr (UA) nld = -htm_log(d);
-#pragma unroll
-                    for (int q = 0; q < D; ++q) {
-                        if constexpr (UT) {
-                            const double rt = __builtin_fma(d, rbeta[q], -tc[q]) - st.tob;
-                            if constexpr (first.value) r0t[k][q] = rt;
-                            const double u = rt - r0t[k][q], pu = st.tpr * u;
-                            t1[k][q] += pu;
-                            t2[k][q] = __builtin_fma(pu, u, t2[k][q]);
-                        }
-                        if constexpr (UA) {
-                            const double ra = (__builtin_fma(-d, katt[q], nld) - ac[q]) - st.aob;
-                            if constexpr (first.value) r0a[k][q] = ra;
-                            const double u = ra - r0a[k][q], pu = st.apr * u;
-                            a1[k][q] += pu;
-                            a2[k][q] = __builtin_fma(pu, u, a2[k][q]);
-                        }
-                    }
-                }
+                for (int k = 0; k < C; ++k) loc_station<MODE>(st, tc, ac, first, x[k], y[k], zc, rbeta, katt, sm[k]);
             };
-            station(0, std::true_type());
-            for (int j = 1; j < jb.S; ++j) station(j, std::false_type());
+            station(0, true);
+            for (int j = 1; j < jb.S; ++j) station(j, false);
             // the block's terms, and into (m, s): the padding's draws (k0 + q >= K, uniform) are left out
 #pragma unroll
             for (int k = 0; k < C; ++k) {
                 double ell[D], mb = -__builtin_inf();
 #pragma unroll
                 for (int q = 0; q < D; ++q) {
-                    double e = 0.0;
-                    if constexpr (UT) e -= 0.5 * (t2[k][q] - (t1[k][q] * t1[k][q]) * ev.rpst) + ev.ct;
-                    if constexpr (UA) e -= 0.5 * (a2[k][q] - (a1[k][q] * a1[k][q]) * ev.rpsa) + ev.ca;
+                    const double e = loc_term<MODE>(sm[k], ev, q);
                     const bool in = k0 + q < dr.K;
                     ell[q] = in ? e : -__builtin_inf();
                     bad[k] = bad[k] || (in && e != e);
@@ -569,9 +482,8 @@ __global__ __launch_bounds__(256) void k_locate_marginal(LocGrid g, LocJob jb, L
 //
 //   k_locate_draw_evidence  k_locate_marginal's grid, tiles, LocJob (vol unused), LocDraws and table.  A block of kLoceDraws
 //                           draws is the OUTER loop (block-uniform), the thread's cells t, t + 256, ... the inner one; per
-//                           (cell, station, block) the distance and its logarithm are formed once, by k_locate_marginal's
-//                           station body (restated for one cell: loc_draws_station, above).  A lane keeps (m_q, s_q), s = sum exp(v - m) over its included cells, per
-//                           draw of the block; after its cells the pairs are combined across the wave (the largest m by a xor
+//                           (cell, station, block) the distance and its logarithm are formed once (loc_station).  A lane
+//                           keeps (m_q, s_q), s = sum exp(v - m) over its included cells, per draw of the block; after its cells the pairs are combined across the wave (the largest m by a xor
 //                           tree, every lane's s rescaled to it, the wave sums' fixed tree) and across the four waves (LDS,
 //                           wave order) into the tile's record part[event][tile][Kpad][2].  The padding's draws are never
 //                           written; a tile without an included cell writes (-inf, 0).
@@ -618,18 +530,23 @@ __global__ __launch_bounds__(256) void k_locate_draw_evidence(LocGrid g, LocJob 
         for (int q = 0; q < D; ++q) { m[q] = -__builtin_inf(); s[q] = 0.0; }
 #pragma unroll 1
         for (int c0 = 0; c0 < ncell; c0 += kLocThreads) {       // (block-uniform) the thread's cells
-            const int c = c0 + t, cc = c < ncell ? c : 0;      // (a thread without a cell evaluates cell 0 and drops it)
-            const int r = cc / g.nx, ix = cc - r * g.nx;
-            const double x = loc_centre(g.x0, g.dx, ix), y = loc_centre(g.y0, g.dy, tl.iy0 + r);
-            const double lpr = prior ? (prior[ix] + prior[g.nx + tl.iy0 + r]) + tl.pz : 0.0;
+            const int c = c0 + t;
+            double x, y, pxy;
+            loc_cell_xy(g, tl.iy0, ncell, prior, c, x, y, pxy);
             LocSums<D> sm;
             sm.clear();
-            loc_draws_station<MODE, true>(sta, dr, k0, 0, x, y, zc, rbeta, katt, sm);
-            for (int j = 1; j < jb.S; ++j) loc_draws_station<MODE, false>(sta, dr, k0, j, x, y, zc, rbeta, katt, sm);
+            auto station = [&](int j, bool first) {             // (as in k_locate_marginal)
+                const LocSta st = loc_ld_sta(sta + j);
+                double tc[D], ac[D];
+                loc_ld_pairs(dr.corr + (size_t)j * dr.Kpad + k0, tc, ac);
+                loc_station<MODE>(st, tc, ac, first, x, y, zc, rbeta, katt, sm);
+            };
+            station(0, true);
+            for (int j = 1; j < jb.S; ++j) station(j, false);
 #pragma unroll
             for (int q = 0; q < D; ++q) {
-                const double ell = loc_draws_term<MODE>(sm, ev, q);
-                const double v = prior ? ell + lpr : ell;       // (loc_cell_done's log posterior)
+                const double ell = loc_term<MODE>(sm, ev, q);
+                const double v = prior ? ell + (pxy + tl.pz) : ell;         // (loc_cell_done's log posterior)
                 if (c < ncell && loc_included(v)) {             // one exponential per (cell, draw)
                     const bool up = v > m[q];
                     const double e = exp(up ? m[q] - v : v - m[q]);

@@ -68,55 +68,28 @@ def locate(fwd, t_corr, vs, a_corr, qs, grid, prior=None, marginals=True, volume
     ell [E] the log posterior and the log-likelihood term there, log_evidence [E], mean [E][3], cov [E][3][3], loc [E][16]
     the library's record, marg_x / marg_y / marg_z [E][n] (None without `marginals`), vol [E][nz][ny][nx] (None without
     `volume`)."""
-    g = grid9(grid)
-    nx, ny, nz = grid_counts(g)
-    if nx * ny * nz > INT_MAX:
-        raise ValueError(f"{nx} x {ny} x {nz} cells: more than 2^31 - 1")
+    g, (nx, ny, nz) = _grid(grid)
     E, S = fwd.n_events, fwd.n_sta
     tc = np.ascontiguousarray(np.asarray(t_corr, dtype=np.float64).reshape(-1))
     ac = np.ascontiguousarray(np.asarray(a_corr, dtype=np.float64).reshape(-1))
     if tc.size != S or ac.size != S:
         raise ValueError(f"t_corr and a_corr have {tc.size} and {ac.size} values: need one per station ({S})")
-    pr = None
-    if prior is not None:
-        pr = np.ascontiguousarray(prior, dtype=np.float64)
-        if pr.shape != (E, 5):
-            raise ValueError(f"prior is {pr.shape}: need mu_x, mu_y, w_xy, z0, w_z of every event ({E})")
-    loc = np.empty((E, 16))
-    marg = np.empty((E, nx + ny + nz)) if marginals else None
-    vol = np.empty((E, nz, ny, nx)) if volume else None
+    pr = _prior_array(prior, E)
+    loc, marg, vol = _outputs(E, nx, ny, nz, marginals, volume)
     _lib.check(_lib.load().htm_forward_locate(fwd.handle, _lib.ptr(tc), float(vs), _lib.ptr(ac), float(qs), _lib.ptr(g), _lib.ptr(pr),
                                               _lib.ptr(loc), _lib.ptr(marg), _lib.ptr(vol)))
-    cov = np.empty((E, 3, 3))
-    for (i, j), k in zip(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2)), range(10, 16)):
-        cov[:, i, j] = cov[:, j, i] = loc[:, k]
-    return {"index": loc[:, 0].astype(np.int64), "best": loc[:, 1:4].copy(), "lp": loc[:, 4].copy(), "ell": loc[:, 5].copy(),
-            "log_evidence": loc[:, 6].copy(), "mean": loc[:, 7:10].copy(), "cov": cov, "loc": loc,
-            "marg_x": None if marg is None else marg[:, :nx], "marg_y": None if marg is None else marg[:, nx:nx + ny],
-            "marg_z": None if marg is None else marg[:, nx + ny:], "vol": vol}
+    return _result(loc, marg, vol, nx, ny)
 
 
 def locate_marginal(fwd, t_corr, vs, a_corr, qs, grid, prior=None, marginals=True, volume=False):
     """`locate` with the structure marginalised over K draws of it: t_corr [K][n_sta], vs [K], a_corr [K][n_sta], qs [K].  A
     cell's log-likelihood term is log((1 / K) sum_k exp(l_k)), l_k the term `locate` takes under draw k; one kernel evaluates
     all draws (htm_forward_locate_marginal).  Returns the dict of `locate`; K = 1 gives its very bits."""
-    g = grid9(grid)
-    nx, ny, nz = grid_counts(g)
-    if nx * ny * nz > INT_MAX:
-        raise ValueError(f"{nx} x {ny} x {nz} cells: more than 2^31 - 1")
+    g, (nx, ny, nz) = _grid(grid)
     E, S = fwd.n_events, fwd.n_sta
-    v = np.ascontiguousarray(np.asarray(vs, dtype=np.float64).reshape(-1))
-    q = np.ascontiguousarray(np.asarray(qs, dtype=np.float64).reshape(-1))
-    K = v.size
-    tc = np.ascontiguousarray(np.asarray(t_corr, dtype=np.float64).reshape(-1))
-    ac = np.ascontiguousarray(np.asarray(a_corr, dtype=np.float64).reshape(-1))
-    if q.size != K or tc.size != K * S or ac.size != K * S:
-        raise ValueError(f"{K} draws of vs: need as many of qs (got {q.size}) and one t_corr and a_corr per draw and station "
-                         f"({K} x {S}; got {tc.size} and {ac.size} values)")
+    K, tc, v, ac, q = _draws(t_corr, vs, a_corr, qs, S)
     pr = _prior_array(prior, E)
-    loc = np.empty((E, 16))
-    marg = np.empty((E, nx + ny + nz)) if marginals else None
-    vol = np.empty((E, nz, ny, nx)) if volume else None
+    loc, marg, vol = _outputs(E, nx, ny, nz, marginals, volume)
     _lib.check(_lib.load().htm_forward_locate_marginal(fwd.handle, K, _lib.ptr(tc), _lib.ptr(v), _lib.ptr(ac), _lib.ptr(q), _lib.ptr(g),
                                                        _lib.ptr(pr), _lib.ptr(loc), _lib.ptr(marg), _lib.ptr(vol)))
     return _result(loc, marg, vol, nx, ny)
@@ -128,19 +101,9 @@ def draw_evidence(fwd, t_corr, vs, a_corr, qs, grid, prior=None):
     w_k^2, w_max [E], k_max [E] (int64; the lowest index of the largest weight, -1 for a window without a cell, whose n_eff,
     w_max and log_evidence are NaN), log_evidence [E] = log((1 / K) sum_k exp(log_z_k)), `locate_marginal`'s
     (htm_forward_locate_draw_evidence)."""
-    g = grid9(grid)
-    nx, ny, nz = grid_counts(g)
-    if nx * ny * nz > INT_MAX:
-        raise ValueError(f"{nx} x {ny} x {nz} cells: more than 2^31 - 1")
+    g, (nx, ny, nz) = _grid(grid)
     E, S = fwd.n_events, fwd.n_sta
-    v = np.ascontiguousarray(np.asarray(vs, dtype=np.float64).reshape(-1))
-    q = np.ascontiguousarray(np.asarray(qs, dtype=np.float64).reshape(-1))
-    K = v.size
-    tc = np.ascontiguousarray(np.asarray(t_corr, dtype=np.float64).reshape(-1))
-    ac = np.ascontiguousarray(np.asarray(a_corr, dtype=np.float64).reshape(-1))
-    if q.size != K or tc.size != K * S or ac.size != K * S:
-        raise ValueError(f"{K} draws of vs: need as many of qs (got {q.size}) and one t_corr and a_corr per draw and station "
-                         f"({K} x {S}; got {tc.size} and {ac.size} values)")
+    K, tc, v, ac, q = _draws(t_corr, vs, a_corr, qs, S)
     pr = _prior_array(prior, E)
     log_z = np.empty((E, K))
     summ = np.empty((E, 4))
@@ -171,6 +134,33 @@ def joint_draw_weights(log_z):
     log_w = tot - np.max(tot)
     w = np.exp(log_w)
     return log_w, w / w.sum()
+
+
+def _grid(grid):
+    """`grid` as the library takes it, and its cell counts (nx, ny, nz): at most 2^31 - 1 cells"""
+    g = grid9(grid)
+    nx, ny, nz = grid_counts(g)
+    if nx * ny * nz > INT_MAX:
+        raise ValueError(f"{nx} x {ny} x {nz} cells: more than 2^31 - 1")
+    return g, (nx, ny, nz)
+
+
+def _draws(t_corr, vs, a_corr, qs, S):
+    """K and the draws' arrays t_corr, vs, a_corr, qs as the library takes them: K of vs and qs, K x S of the corrections"""
+    v = np.ascontiguousarray(np.asarray(vs, dtype=np.float64).reshape(-1))
+    q = np.ascontiguousarray(np.asarray(qs, dtype=np.float64).reshape(-1))
+    K = v.size
+    tc = np.ascontiguousarray(np.asarray(t_corr, dtype=np.float64).reshape(-1))
+    ac = np.ascontiguousarray(np.asarray(a_corr, dtype=np.float64).reshape(-1))
+    if q.size != K or tc.size != K * S or ac.size != K * S:
+        raise ValueError(f"{K} draws of vs: need as many of qs (got {q.size}) and one t_corr and a_corr per draw and station "
+                         f"({K} x {S}; got {tc.size} and {ac.size} values)")
+    return K, tc, v, ac, q
+
+
+def _outputs(E, nx, ny, nz, marginals, volume):
+    """the arrays the library fills: loc, marg and vol (None where not asked for)"""
+    return np.empty((E, 16)), np.empty((E, nx + ny + nz)) if marginals else None, np.empty((E, nz, ny, nx)) if volume else None
 
 
 def _prior_array(prior, E):

@@ -12,56 +12,38 @@ marginals, no volume come back).  The kernels' share of a call is taken from a k
 The yardstick is timed with HIP events on the handle's stream (htm_forward_time_full_batch_dev: a warm-up call, then the
 mean of 20 calls) on a slice of the grid -- 64 positions are one call, and every call costs the same.
 
-    python tools/bench_locate.py [--windows 1000] [--stations 64] [--big-windows 1000] [--reps 3]
+    python tools/bench_locate.py [--windows 1000] [--stations 64] [--big-windows 1000] [--reps 3] [--use both|time|amp]
+                                 [--lib NAME=PATH ...]     # A/B: the same with other builds of the library (HTM_LIB)
+    python tools/bench_locate.py --one         # the measurement in this process
     python tools/bench_locate.py --once        # one call on the large grid and nothing else, for a kernel trace
+
+The measurement is a process of its own under `timeout`, once per build (the job and the driver: tools/locate_bench_job.py).
 """
 import argparse
 import sys
-import time
 
 sys.path.insert(0, ".")
-import numpy as np
-import torch
-
-from hypotremormcmc_amd import locate as lc
-from hypotremormcmc_amd import synth
-from hypotremormcmc_amd.forward import Forward, ObsArrays
-
-GRIDS = {"128 x 128 x 64": np.array([-64.0, 1.0, 128, -64.0, 1.0, 128, 0.5, 0.5, 64]),
-         "32 x 32 x 16": np.array([-64.0, 4.0, 32, -64.0, 4.0, 32, 0.5, 2.0, 16])}
+import locate_bench_job as bj
 
 
-def forward_of(data, n):
-    obs = ObsArrays(data.t_obs[:n], data.t_stdv[:n], data.a_obs[:n], data.a_stdv[:n])
-    return Forward(data.n_sta, n, data.sta_x, data.sta_y, data.sta_z, obs)
+def measure(args):
+    import numpy as np
+    import torch
 
+    from hypotremormcmc_amd import locate as lc
 
-def main(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--windows", type=int, default=1000)
-    ap.add_argument("--stations", type=int, default=64)
-    ap.add_argument("--big-windows", type=int, default=1000, help="windows located on the large grid")
-    ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--once", action="store_true")
-    args = ap.parse_args(argv)
-    E, S = args.windows, args.stations
-    data = synth.make_synthetic(E, S, 3)
+    job = bj.Job(args)
+    E, S, prior = job.E, job.S, job.prior
     zero = np.zeros(S)
-    prior = np.stack([np.zeros(E), np.zeros(E), np.full(E, 30.0), np.zeros(E), np.full(E, 10.0)], axis=1)
 
     def locate_rate(name, n):
-        fwd = forward_of(data, n)
-        grid = GRIDS[name]
-        cells = int(grid[2] * grid[5] * grid[8])
+        fwd = job.forward_of(n)
+        grid, cells = job.grid(name)
         if not args.once:
-            warm = forward_of(data, min(n, 8))
+            warm = job.forward_of(min(n, 8))
             lc.locate(warm, zero, 3.0, zero, 250.0, grid, prior=prior[:min(n, 8)], marginals=False)
             warm.close()
-        times = []
-        for rep in range(1 if args.once else args.reps):
-            t0 = time.perf_counter()
-            res = lc.locate(fwd, zero, 3.0, zero, 250.0, grid, prior=prior[:n], marginals=False)
-            times.append(time.perf_counter() - t0)
+        times, res = bj.timed(lambda: lc.locate(fwd, zero, 3.0, zero, 250.0, grid, prior=prior[:n], marginals=False), 1 if args.once else args.reps)
         fwd.close()
         assert (res["index"] >= 0).all()
         t = float(np.median(times))
@@ -77,9 +59,10 @@ def main(argv=None):
     rates["128 x 128 x 64"] = locate_rate("128 x 128 x 64", min(args.big_windows, E))
 
     # the yardstick: 64 models per call, model m = every window at cell centre m of a slice of the grid
-    fwd = forward_of(data, E)
+    fwd = job.forward_of(E)
     dev = torch.device("cuda")
-    for name, grid in GRIDS.items():
+    for name in bj.GRIDS:
+        grid, _ = job.grid(name)
         x = grid[0] + (np.arange(64) + 0.5) * grid[1]                       # the first 64 cells of the row (iy, iz) = (ny / 2, nz / 2)
         pos = np.stack([x, np.full(64, grid[3] + (grid[5] // 2 + 0.5) * grid[4]), np.full(64, grid[6] + (grid[8] // 2 + 0.5) * grid[7])], axis=1)
         pos = pos[np.arange(64) % int(grid[2])]
@@ -96,5 +79,18 @@ def main(argv=None):
     fwd.close()
 
 
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    bj.add_arguments(ap)
+    ap.add_argument("--big-windows", type=int, default=1000, help="windows located on the large grid")
+    ap.add_argument("--one", action="store_true")
+    ap.add_argument("--once", action="store_true")
+    args = ap.parse_args(argv)
+    if args.one or args.once:
+        measure(args)
+        return 0
+    return bj.drive(__file__, args, [("the measurement", ["--one", "--big-windows", str(args.big_windows)])])
+
+
 if __name__ == "__main__":
-    main()
+    sys.exit(main())
