@@ -1,6 +1,6 @@
 // htm_density.hpp -- stacked density maps of recorded hypocentre samples: every sample of every window is binned on a map
-// grid and counted once in the xy, xz and yz maps (and the volume, where asked for) of its window's layer (rule and
-// measurements: DESIGN.md §3.9).  The counts are integers: exact, and the same whatever the order of the adds.
+// grid (htm_grid.hpp) and counted once in the xy, xz and yz maps (and the volume, where asked for) of its window's layer (rule
+// and measurements: DESIGN.md §3.9).  The counts are integers: exact, and the same whatever the order of the adds.
 //
 // Layout: hypo is [n_mod][ld] row-major, one recorded model per row, window w in columns 3w, 3w+1, 3w+2 (the record of
 // hypo.RR.out); layer [n_win] or NULL (every window in layer 0); xy [n_layer][ny][nx], xz [n_layer][nz][nx],
@@ -28,21 +28,17 @@
 #include <climits>
 
 #include "htm_ellipsoid.hpp"
+#include "htm_grid.hpp"
 
 namespace htm {
 
 constexpr int kDensWG = 4;                      // window groups (waves) per workgroup
 constexpr int kDensU = 4;                       // rows in flight per thread
-constexpr int kDensMaxCells = 4096;             // cells per axis
 constexpr int kDensLdsCells = 8192;             // nx ny + nx nz + ny nz of a grid the LDS path takes
 constexpr long kDensMaxSlabRows = 1L << 22;     // rows a workgroup counts between two flushes of its LDS counters
 // every lane of a workgroup can put every row of its slab into one 32-bit counter
 static_assert(64L * kDensWG * kDensMaxSlabRows <= 0xffffffffL, "a workgroup's 32-bit counter could wrap");
 
-struct DensGrid {
-    double x0, dx, y0, dy, z0, dz;
-    int nx, ny, nz;
-};
 struct DensOut {
     unsigned long long *xy, *xz, *yz, *vol, *tally;
 };
@@ -109,7 +105,7 @@ __device__ __forceinline__ int dens_layer(const int *layer, long w, long n_win, 
 
 template <bool NAIVE>
 __global__ __launch_bounds__(64 * kDensWG) void k_dens_plain(const double *hypo, long ld, long n_mod, long n_win, long slab_rows,
-                                                             const int *layer, int n_layer, DensGrid g, DensOut o)
+                                                             const int *layer, int n_layer, MapGrid g, DensOut o)
 {
     __shared__ double tiles[kDensWG][kDensU * 192];
     const int lane = threadIdx.x & 63;
@@ -172,7 +168,7 @@ __global__ __launch_bounds__(64 * kDensWG) void k_dens_plain(const double *hypo,
 
 // needs nx ny + nx nz + ny nz <= kDensLdsCells and slab_rows <= kDensMaxSlabRows
 __global__ __launch_bounds__(64 * kDensWG) void k_dens_lds(const double *hypo, long ld, long n_mod, long n_win, long slab_rows,
-                                                           const int *layer, int n_layer, DensGrid g, DensOut o)
+                                                           const int *layer, int n_layer, MapGrid g, DensOut o)
 {
     __shared__ double tiles[kDensWG][kDensU * 192];
     __shared__ unsigned maps[kDensLdsCells];

@@ -534,15 +534,9 @@ static int locate_run(htm_forward *h, int n_draws, const double *t_corr, const d
                       double *summary = nullptr)
 {
     const bool draws = n_draws > 0, evid = log_z != nullptr;
-    int n[3];
-    for (int a = 0; a < 3; ++a) {
-        const double v0 = grid9[3 * a], dv = grid9[3 * a + 1], cnt = grid9[3 * a + 2];
-        if (!std::isfinite(v0) || !std::isfinite(dv) || !(dv > 0.0))
-            return fail(HTM_EINVAL, "grid axis %c: origin %g, cell size %g: need a finite origin and a finite cell size > 0", "xyz"[a], v0, dv);
-        if (!(cnt >= 1.0 && cnt <= (double)kLocMaxCells) || cnt != std::floor(cnt))
-            return fail(HTM_EINVAL, "grid axis %c: %g cells: need an integer in 1..%d", "xyz"[a], cnt, kLocMaxCells);
-        n[a] = (int)cnt;
-    }
+    LocGrid g{};
+    if (int rc = map_grid_parse(grid9, &g)) return rc;
+    const int n[3] = {g.nx, g.ny, g.nz};
     const long cells = (long)n[0] * n[1] * n[2];
     if (cells > (long)INT_MAX) return fail(HTM_EINVAL, "%d x %d x %d cells: more than 2^31 - 1", n[0], n[1], n[2]);
     const int E = h->E, S = h->S;
@@ -554,7 +548,6 @@ static int locate_run(htm_forward *h, int n_draws, const double *t_corr, const d
     int rc = env_mib("HTM_LOCATE_MB", 1024.0, &mb);
     if (rc) return rc;
     // tiles: whole x-rows of one z-layer, at most kLocRows of them and kLocTile cells
-    LocGrid g{grid9[0], grid9[1], grid9[3], grid9[4], grid9[6], grid9[7], n[0], n[1], n[2], 0, 0, 0};
     g.rows = std::max(1, std::min(std::min(n[1], kLocRows), kLocTile / n[0]));
     g.tpl = (n[1] + g.rows - 1) / g.rows;
     g.stride = kLocHead + n[0] + 2 * g.rows;
@@ -627,10 +620,10 @@ static int locate_run(htm_forward *h, int n_draws, const double *t_corr, const d
                 const double *p = prior5 + 5 * (e0 + b);
                 double *q = tab.data() + (size_t)b * nm;
                 const double lw = std::log(p[2]), lwz = std::log(p[4]);
-                for (int i = 0; i < n[0]; ++i) { const double d = loc_centre(g.x0, g.dx, i) - p[0]; q[i] = (-log_2pi_half - lw) - d * d / (2.0 * p[2] * p[2]); }
-                for (int i = 0; i < n[1]; ++i) { const double d = loc_centre(g.y0, g.dy, i) - p[1]; q[n[0] + i] = (-log_2pi_half - lw) - d * d / (2.0 * p[2] * p[2]); }
+                for (int i = 0; i < n[0]; ++i) { const double d = map_centre(g.x0, g.dx, i) - p[0]; q[i] = (-log_2pi_half - lw) - d * d / (2.0 * p[2] * p[2]); }
+                for (int i = 0; i < n[1]; ++i) { const double d = map_centre(g.y0, g.dy, i) - p[1]; q[n[0] + i] = (-log_2pi_half - lw) - d * d / (2.0 * p[2] * p[2]); }
                 for (int i = 0; i < n[2]; ++i) {
-                    const double d = loc_centre(g.z0, g.dz, i) - p[3];
+                    const double d = map_centre(g.z0, g.dz, i) - p[3];
                     q[n[0] + n[1] + i] = d > 0.0 ? (std::log(d) - 2.0 * lwz) - d * d / (2.0 * p[4] * p[4]) : -INFINITY;
                 }
             }

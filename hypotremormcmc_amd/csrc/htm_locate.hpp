@@ -1,7 +1,7 @@
 // htm_locate.hpp -- every window's location posterior on a grid under a FIXED structure (vs, qs, station corrections): the
 // kernels of htm_forward_locate (htm_forward.hip; rule, choices and measurements: DESIGN.md §3.10).  With the global parameters
 // fixed the log-likelihood is a sum of independent per-event terms (each event is demeaned on its own: cls_forward.f90:113-133,
-// :199-218, :268-303), so an event's term is a function of its position alone and is tabulated at the cell centres.
+// :199-218, :268-303), so an event's term is a function of its position alone and is tabulated at the cell centres (htm_grid.hpp).
 //
 // The mapping is the opposite of event_misfit's: a lane owns CELLS, the stations are the serial inner loop in the reference's
 // own order 0 .. n_sta - 1, and no sum over stations crosses lanes.
@@ -34,17 +34,17 @@
 #include <type_traits>
 
 #include "htm_device.hpp"
+#include "htm_grid.hpp"
 
 namespace htm {
 
-constexpr int kLocMaxCells = 4096;      // cells per axis: the limit of htm_hypo_density (kDensMaxCells)
 constexpr int kLocThreads = 256;
 constexpr int kLocPerThread = 16;       // cells of a tile per thread
 constexpr int kLocChunk = 4;            // of them evaluated side by side
 constexpr int kLocTile = kLocThreads * kLocPerThread;
 constexpr int kLocRows = 256;           // x-rows per tile at the most
 constexpr int kLocHead = 4;
-static_assert(kLocTile >= kLocMaxCells, "a tile holds at least one whole x-row");
+static_assert(kLocTile >= kMapMaxCells, "a tile holds at least one whole x-row");
 static_assert(kLocPerThread % kLocChunk == 0, "whole chunks");
 // k_locate_marginal: draws per block and cells of a thread side by side (the choice and its alternatives: DESIGN.md 3.11)
 #ifndef HTM_LOCM_DRAWS
@@ -68,13 +68,12 @@ struct __attribute__((aligned(16))) LocEv {
     double rpst, rpsa, ct, ca;
 };
 
-struct LocGrid {
-    double x0, dx, y0, dy, z0, dz;
-    int nx, ny, nz;
+struct LocGrid : MapGrid {
     int rows;        // x-rows per tile
     int tpl;         // tiles per z-layer
     int stride;      // doubles per partial record
 };
+static_assert(sizeof(LocGrid) == 72, "rows, tpl and stride follow nz directly, in MapGrid's tail padding (htm_grid.hpp)");
 
 struct LocJob {
     const LocSta *sta;      // [nb][S]
@@ -85,13 +84,6 @@ struct LocJob {
     int S;
     double rbeta, katt;     // 1 / vs, pi f / (qs vs)
 };
-
-// the centre of cell i: one multiplication, then one addition (the library is built with -ffp-contract=off)
-__host__ __device__ __forceinline__ double loc_centre(double v0, double dv, int i)
-{
-    const double t = ((double)i + 0.5) * dv;
-    return v0 + t;
-}
 
 // a record at a wave-uniform address through the constant address space: scalar loads, as ld_const (the doubles travel in pairs)
 typedef double loc_f64x2 __attribute__((ext_vector_type(2)));
@@ -166,7 +158,7 @@ __device__ __forceinline__ LocTile loc_tile(const LocGrid &g, const LocJob &jb)
     tl.iz = tl.tile / g.tpl; tl.iy0 = (tl.tile - tl.iz * g.tpl) * g.rows;
     tl.rows = min(g.rows, g.ny - tl.iy0); tl.ncell = tl.rows * g.nx;
     tl.cell0 = ((long)tl.iz * g.ny + tl.iy0) * g.nx;
-    tl.zc = loc_centre(g.z0, g.dz, tl.iz);
+    tl.zc = map_centre(g.z0, g.dz, tl.iz);
     tl.prior = jb.prior ? jb.prior + (size_t)tl.b * (g.nx + g.ny + g.nz) : nullptr;
     tl.pz = tl.prior ? tl.prior[g.nx + g.ny + tl.iz] : 0.0;
     return tl;
@@ -231,7 +223,7 @@ __device__ __forceinline__ void loc_tile_reduce(const LocGrid &g, const LocJob &
             for (int ix = lane; ix < g.nx; ix += 64) {
                 const double w = s_w[r * g.nx + ix];
                 v[0] += w;
-                v[1] = __builtin_fma(w, loc_centre(g.x0, g.dx, ix), v[1]);
+                v[1] = __builtin_fma(w, map_centre(g.x0, g.dx, ix), v[1]);
             }
         wave_sum<2>(v);
         if (lane == 0) { s_S[r] = v[0]; pS[r] = v[0]; pT[r] = v[1]; }
@@ -270,8 +262,8 @@ __device__ __forceinline__ void loc_cell_xy(const LocGrid &g, int iy0, int ncell
 {
     const int cc = c < ncell ? c : 0;
     const int r = cc / g.nx, ix = cc - r * g.nx;
-    x = loc_centre(g.x0, g.dx, ix);
-    y = loc_centre(g.y0, g.dy, iy0 + r);
+    x = map_centre(g.x0, g.dx, ix);
+    y = map_centre(g.y0, g.dy, iy0 + r);
     pxy = prior ? prior[ix] + prior[g.nx + iy0 + r] : 0.0;
 }
 
@@ -692,12 +684,12 @@ __global__ __launch_bounds__(256) void k_locate_combine(LocGrid g, double *part,
     double mean[3], var[3], bc[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        bc[a] = loc_centre(v0[a], dv[a], bi[a]);
+        bc[a] = map_centre(v0[a], dv[a], bi[a]);
         double s = 0.0;
-        for (int i = t; i < n[a]; i += 256) s = __builtin_fma(M[off[a] + i], loc_centre(v0[a], dv[a], i) - bc[a], s);
+        for (int i = t; i < n[a]; i += 256) s = __builtin_fma(M[off[a] + i], map_centre(v0[a], dv[a], i) - bc[a], s);
         mean[a] = bc[a] + loc_block_sum(s, s_red4);
         s = 0.0;
-        for (int i = t; i < n[a]; i += 256) { const double d = loc_centre(v0[a], dv[a], i) - mean[a]; s = __builtin_fma(M[off[a] + i] * d, d, s); }
+        for (int i = t; i < n[a]; i += 256) { const double d = map_centre(v0[a], dv[a], i) - mean[a]; s = __builtin_fma(M[off[a] + i] * d, d, s); }
         var[a] = loc_block_sum(s, s_red4);
     }
     // the mixed moments about the mean from the rows' sums: tiles thread-strided, a tile's rows in order
@@ -707,10 +699,10 @@ __global__ __launch_bounds__(256) void k_locate_combine(LocGrid g, double *part,
         const int iz = k / g.tpl, iy0 = (k - iz * g.tpl) * g.rows, rows = min(g.rows, g.ny - iy0);
         double A = 0.0, B = 0.0, C = 0.0;
         for (int rr = 0; rr < rows; ++rr) {
-            const double ex = pT[rr] - mean[0] * pS[rr], ey = loc_centre(g.y0, g.dy, iy0 + rr) - mean[1];
+            const double ex = pT[rr] - mean[0] * pS[rr], ey = map_centre(g.y0, g.dy, iy0 + rr) - mean[1];
             A += ex; B = __builtin_fma(ey, ex, B); C = __builtin_fma(ey, pS[rr], C);
         }
-        const double ez = loc_centre(g.z0, g.dz, iz) - mean[2];
+        const double ez = map_centre(g.z0, g.dz, iz) - mean[2];
         cxy = __builtin_fma(r[0], B, cxy); cxz = __builtin_fma(r[0] * ez, A, cxz); cyz = __builtin_fma(r[0] * ez, C, cyz);
     }
     cxy = loc_block_sum(cxy, s_red4) / W; cxz = loc_block_sum(cxz, s_red4) / W; cyz = loc_block_sum(cyz, s_red4) / W;

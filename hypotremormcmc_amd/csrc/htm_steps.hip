@@ -456,7 +456,7 @@ int htm_hypo_ellipsoid(int device, const double *hypo, const double *pivots, lon
 // ---- stacked density maps (htm_density.hpp) ------------------------------------------------------------
 namespace {
 struct DensPlan {
-    DensGrid g;
+    MapGrid g;
     long slabs, slab_rows, nxy, nxz, nyz, nvol;      // nvol = 0 without the volume
     int path;                                         // 0 plain, 1 LDS, 2 naive
 };
@@ -472,20 +472,11 @@ int dens_plan(const double *hypo, long ld, long n_mod, long n_win, const int *la
     if (!layer && n_layer != 1) return fail(HTM_EINVAL, "n_layer %d without a layer per window: NULL puts every window in layer 0 of 1", n_layer);
     if (n_win > INT_MAX / 3) return fail(HTM_EINVAL, "n_win %ld needs more than 2^32 - 1 work-items in one launch", n_win);
     if (ld < 3 * n_win) return fail(HTM_EINVAL, "bad row stride (ld %ld < 3 n_win = %ld)", ld, 3 * n_win);
-    int n[3];
-    for (int a = 0; a < 3; ++a) {
-        const double v0 = grid9[3 * a], dv = grid9[3 * a + 1], cnt = grid9[3 * a + 2];
-        if (!std::isfinite(v0) || !std::isfinite(dv) || !(dv > 0.0))
-            return fail(HTM_EINVAL, "grid axis %c: origin %g, cell size %g: need a finite origin and a finite cell size > 0", "xyz"[a], v0, dv);
-        if (!(cnt >= 1.0 && cnt <= (double)kDensMaxCells) || cnt != std::floor(cnt))
-            return fail(HTM_EINVAL, "grid axis %c: %g cells: need an integer in 1..%d", "xyz"[a], cnt, kDensMaxCells);
-        n[a] = (int)cnt;
-    }
-    p->g = DensGrid{grid9[0], grid9[1], grid9[3], grid9[4], grid9[6], grid9[7], n[0], n[1], n[2]};
-    p->nxy = (long)n[1] * n[0];
-    p->nxz = (long)n[2] * n[0];
-    p->nyz = (long)n[2] * n[1];
-    p->nvol = vol ? p->nxy * n[2] : 0;
+    if (int rc = map_grid_parse(grid9, &p->g)) return rc;
+    p->nxy = (long)p->g.ny * p->g.nx;
+    p->nxz = (long)p->g.nz * p->g.nx;
+    p->nyz = (long)p->g.nz * p->g.ny;
+    p->nvol = vol ? p->nxy * p->g.nz : 0;
     const long cells = p->nxy + p->nxz + p->nyz + p->nvol;
     if (cells > INT_MAX / n_layer)
         return fail(HTM_EINVAL, "%d layers of %ld cells: more than 2^31 - 1 counters", n_layer, cells);

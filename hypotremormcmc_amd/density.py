@@ -17,59 +17,26 @@ printed: widen the box when it is large.  The samples go to the device in batche
 from __future__ import annotations
 
 import argparse
-import math
 import os
 import sys
 
 import numpy as np
 
 from . import _lib
+from .grid import MAX_CELLS, add_grid_arguments, centres, default_bounds, grid9, grid_counts, grid_from_args, make_grid  # noqa: F401
 from .run_files import Step5Run
 from .statistics import INT_MAX, as_printed, hypo_rows, quantiles, remove_double_counts, sample_matrix
 
-MAX_CELLS = 4096          # per axis: kDensMaxCells of csrc/htm_density.hpp
 LDS_MAX_CELLS = 8192      # nx ny + nx nz + ny nz of a grid the LDS path takes: kDensLdsCells (tests/test_density.py keeps them equal)
 MAPS = ("xy", "xz", "yz", "vol")
 # the axes of a map, fastest first
 AXES = {"xy": (0, 1), "xz": (0, 2), "yz": (1, 2), "vol": (0, 1, 2)}
 
 
-def grid9(grid):
-    """{x0, dx, nx, y0, dy, ny, z0, dz, nz} as the float64 array the library takes, after the checks that can be made here"""
-    g = np.array(grid, dtype=np.float64).reshape(-1)
-    if g.shape != (9,):
-        raise ValueError(f"grid has {g.size} numbers: need x0, dx, nx, y0, dy, ny, z0, dz, nz")
-    for a, name in enumerate("xyz"):
-        v0, dv, n = g[3 * a:3 * a + 3]
-        if not (np.isfinite(v0) and np.isfinite(dv) and dv > 0.0):
-            raise ValueError(f"grid axis {name}: origin {v0}, cell size {dv}: need a finite origin and a finite cell size > 0")
-        if not (1 <= n <= MAX_CELLS and n == math.floor(n)):
-            raise ValueError(f"grid axis {name}: {n} cells: need an integer in 1..{MAX_CELLS}")
-    return g
-
-
-def grid_counts(grid):
-    g = grid9(grid)
-    return int(g[2]), int(g[5]), int(g[8])
-
-
 def lds_fits(grid) -> bool:
     """whether the LDS path takes the grid"""
     nx, ny, nz = grid_counts(grid)
     return nx * ny + nx * nz + ny * nz <= LDS_MAX_CELLS
-
-
-def make_grid(bounds, cell):
-    """bounds = x0, x1, y0, y1, z0, z1 and cell = dx, dy, dz: the grid from the lower bounds with the fewest cells that reach
-    the upper ones"""
-    g = []
-    for a in range(3):
-        lo, hi, dv = float(bounds[2 * a]), float(bounds[2 * a + 1]), float(cell[a])
-        if not (np.isfinite(lo) and np.isfinite(hi) and hi > lo and np.isfinite(dv) and dv > 0.0):
-            raise ValueError(f"axis {'xyz'[a]}: bounds {lo} .. {hi}, cell {dv}: need lower < upper and a cell size > 0")
-        n = max(1, math.ceil((hi - lo) / dv * (1.0 - 1e-12)))
-        g += [lo, dv, float(n)]
-    return grid9(g)
 
 
 def density(hypo, grid, layer=None, n_layer: int = 1, volume: bool = False, device: int = 0):
@@ -170,12 +137,13 @@ def map_text(name, counts, grid, n_mod, levels) -> str:
     g = grid9(grid)
     c = np.asarray(counts)
     axes = AXES[name]
+    cen = [centres(g, a) for a in axes]
     lines = [HEADERS[name]]
     for L in range(c.shape[0]):
         lev = hpd_levels(c[L], levels)
         for idx in np.ndindex(*c.shape[1:]):
             cell = idx[::-1]                                         # fastest axis first
-            centre = [g[3 * a] + (i + 0.5) * g[3 * a + 1] for a, i in zip(axes, cell)]
+            centre = [v[i] for v, i in zip(cen, cell)]
             n = int(c[L][idx])
             lines.append("%5d" % L + "".join("%6d" % i for i in cell) + "".join("%14.6f" % v for v in centre)
                          + "%12d%14.6f%8.4f" % (n, n / float(n_mod), lev[idx]))
@@ -189,23 +157,6 @@ def summary_text(tally) -> str:
         share = "NaN" if tot == 0 else "%.2f %%" % (100.0 * n_out / tot)
         lines.append(f"layer {L}: {n_in} samples inside the box, {n_out} outside ({share})")
     return "\n".join(lines) + "\n"
-
-
-def default_bounds(par):
-    wxy, z0, wz = par.get_prior_width_xy(), par.get_prior_z(), par.get_prior_width_z()
-    return [par.sta_x.min() - wxy, par.sta_x.max() + wxy, par.sta_y.min() - wxy, par.sta_y.max() + wxy, z0, z0 + 5.0 * wz]
-
-
-def add_grid_arguments(ap):
-    ap.add_argument("--cell", type=float, nargs="+", required=True, metavar="D", help="cell size: DX, or DX DY DZ")
-    ap.add_argument("--bounds", type=float, nargs=6, metavar=("x0", "x1", "y0", "y1", "z0", "z1"))
-
-
-def grid_from_args(ap, args, par):
-    """the grid of --cell and --bounds (default: default_bounds)"""
-    if len(args.cell) not in (1, 3):
-        ap.error("--cell takes DX, or DX DY DZ")
-    return make_grid(args.bounds if args.bounds else default_bounds(par), args.cell * 3 if len(args.cell) == 1 else args.cell)
 
 
 def main(argv=None):

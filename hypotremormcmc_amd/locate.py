@@ -7,7 +7,7 @@ grid -- no MCMC, any number of windows (kernels in hypotremorm
 
 run in the data directory (station file, opt_data.NNNNNN.dat).  --structure DIR holds `uniform_structure.stat` and
 `station_corrections.stat` of the calibration run (default: the parameter file's directory); --windows FILE lists the window
-ids in its first column (default `selected_win.dat`).  Without --bounds the box is density.default_bounds.  The prior is step
+ids in its first column (default `selected_win.dat`).  Without --bounds the box is grid.default_bounds.  The prior is step
 5's: Gaussians of prior_width_xy about the station of largest amplitude in x and y, the depth prior of prior_z and
 prior_width_z; --flat-prior turns it off.  use_time / use_amp come from the parameter file.  Writes `hypo_grid.stat` (the
 layout of hypo.stat: median, 2.5 % and 97.5 % of every axis, from the marginals) and `hypo_grid.best.dat` (one line per
@@ -42,8 +42,8 @@ import sys
 import numpy as np
 
 from . import _lib
-from .density import add_grid_arguments, grid9, grid_counts, grid_from_args
 from .forward import Forward
+from .grid import add_grid_arguments, centres, grid9, grid_counts, grid_from_args
 from .obs_data import ObsData
 from .run_files import Step5Run, field
 from .statistics import HYPO_HEADER, INT_MAX
@@ -53,12 +53,6 @@ DRAWS_HEADER = ("# window ID, effective number of the draws n_eff, n_eff / K, la
 STRUCTURE_HEADER = "# record number of the draw, vs, qs, joint log weight over all windows relative to the best draw, normalised joint weight"
 BEST_HEADER = ("# window ID, best cell's centre x y z, log posterior there, log-likelihood term there, log evidence, "
                "posterior mean x y z, 1: the best cell lies on a face of the box")
-
-
-def centres(grid, axis: int):
-    """the cell centres of one axis, v0 + (i + 0.5) * dv: one multiplication, then one addition, as the library forms them"""
-    g = grid9(grid)
-    return g[3 * axis] + (np.arange(int(g[3 * axis + 2])) + 0.5) * g[3 * axis + 1]
 
 
 def locate(fwd, t_corr, vs, a_corr, qs, grid, prior=None, marginals=True, volume=False):

@@ -128,11 +128,14 @@ int htm_forward_time_full_batch_dev(htm_forward *h, int n_models, const double *
                                     const double *d_qs, double *d_log_likelihood, int reps,
                                     double *avg_us);
 
+/* THE MAP GRID of htm_forward_locate* and htm_hypo_density*: grid9 = {x0, dx, nx, y0, dy, ny, z0, dz, nz}, nine doubles in host
+ * memory, the counts as doubles with integral values.  Every axis {v0, dv, n} needs a finite origin v0, a finite cell size
+ * dv > 0 and an integer n in 1..4096; anything else is HTM_EINVAL before any device call.  The centre of cell i of an axis is
+ * v0 + (i + 0.5) * dv, one multiplication then one addition, unfused; the linear index of a cell is ix + nx (iy + ny iz). */
+
 /* Location posteriors on a grid under a FIXED structure.  With t_corr, vs, a_corr, qs fixed the
  * log-likelihood of :268-303 is a sum of independent per-event terms; the term l of every event of the handle is taken at
- * every cell centre of grid9 = {x0, dx, nx, y0, dy, ny, z0, dz, nz} (limits of htm_hypo_density, and nx ny nz <= 2^31 - 1).
- * The centre of cell i of an axis {v0, dv, n} is v0 + (i + 0.5) * dv, one multiplication then one addition, unfused; the
- * linear index of a cell is ix + nx (iy + ny iz).  The handle's stations, observations, use_time / use_amp and missing-data
+ * every cell centre of grid9 (the map grid, above; and nx ny nz <= 2^31 - 1).  The handle's stations, observations, use_time / use_amp and missing-data
  * rule are used as they stand, always through its fp64 arrays (whatever htm_forward_set_precision says).  t_corr, a_corr
  * [n_sta], host pointers.  prior5 [n_events][5] = {mu_x, mu_y, w_xy, z0, w_z} or NULL (flat prior): the log prior of a cell is
  * the sum of the normalised Gaussian log densities N(mu_x, w_xy), N(mu_y, w_xy) in x and y and of the normalised depth prior
@@ -477,8 +480,8 @@ int htm_hypo_ellipsoid_dev(int device, const double *d_hypo, long ld, const doub
 /* ------------------------------------------------------------------------------------------------
  * Stacked density maps of recorded samples.  hypo as for the ellipsoids; layer [n_win] gives every window
  * its layer (a time bin, say), NULL puts every window in layer 0 of n_layer = 1; a window whose layer lies outside
- * 0 .. n_layer - 1 takes no part and is in nobody's tally.  grid9 = {x0, dx, nx, y0, dy, ny, z0, dz, nz} (host memory in both
- * forms; the counts as doubles with integral values).  On an axis {v0, dv, n} a coordinate v has q = (v - v0) / dv (a true
+ * 0 .. n_layer - 1 takes no part and is in nobody's tally.  grid9: the map grid (above htm_forward_locate; host memory in both
+ * forms).  On an axis {v0, dv, n} a coordinate v has q = (v - v0) / dv (a true
  * fp64 division); it is inside iff 0 <= q < n (cells are half-open, the box's top edge is outside, as are NaN and +-inf) and
  * then lies in cell floor(q).  A sample counts iff its three coordinates are inside, and then once in each output:
  * xy [n_layer][ny][nx], xz [n_layer][nz][nx], yz [n_layer][nz][ny], vol [n_layer][nz][ny][nx] (or NULL), and
@@ -486,7 +489,7 @@ int htm_hypo_ellipsoid_dev(int device, const double *d_hypo, long ld, const doub
  * times the layer's windows.  The call zeroes the outputs before it counts; the counts are exact and the same for every
  * order of the adds, row-slab count (HTM_DENSITY_SLABS) and counting path (HTM_DENSITY_LDS = 0 | 1 forbids or forces the
  * LDS-resident maps, which take a grid with nx ny + nx nz + ny nz <= 8192; forced on a larger grid: HTM_EINVAL).
- * n_mod, n_win, n_layer >= 1; ld >= 3 n_win; finite origins, finite cell sizes > 0; 1..4096 cells per axis; at most
+ * n_mod, n_win, n_layer >= 1; ld >= 3 n_win; what the map grid asks of every axis; at most
  * 2^31 - 1 counters over all layers and requested outputs; else HTM_EINVAL before any device call, as for a shape that needs a
  * launch beyond 2^32 - 1 work-items.  Host pointers: synchronous, the rows in batches under HTM_DENSITY_MB MiB (environment,
  * default 1024) whose counts are added on the host; _dev: device pointers (ld = row stride in doubles; columns beyond

@@ -144,7 +144,7 @@ def e2e_data():
 def e2e_reference():
     """the restatement's quantiles [8][3][3] of the end-to-end job: the structure the data were made with (vs 3, qs 250, no
     corrections), step 5's prior from the default parameters"""
-    from hypotremormcmc_amd.density import make_grid
+    from hypotremormcmc_amd.grid import make_grid
     from hypotremormcmc_amd.obs_data import ObsData
 
     data = e2e_data()

@@ -199,7 +199,8 @@ def test_python_entry_checks_its_input():
 def test_module_mirrors_the_kernels_constants():
     src = open(os.path.join(ROOT, "hypotremormcmc_amd", "csrc", "htm_density.hpp")).read()
     assert int(re.search(r"constexpr int kDensLdsCells = (\d+);", src).group(1)) == dn.LDS_MAX_CELLS
-    assert int(re.search(r"constexpr int kDensMaxCells = (\d+);", src).group(1)) == dn.MAX_CELLS
+    grid_src = open(os.path.join(ROOT, "hypotremormcmc_amd", "csrc", "htm_grid.hpp")).read()
+    assert int(re.search(r"constexpr int kMapMaxCells = (\d+);", grid_src).group(1)) == dn.MAX_CELLS
     assert dn.lds_fits(_grid(nx=680.0, ny=8.0, nz=4.0)) and not dn.lds_fits(_grid(nx=681.0, ny=8.0, nz=4.0))
 
 
