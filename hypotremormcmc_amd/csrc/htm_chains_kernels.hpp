@@ -1,6 +1,6 @@
 // htm_chains_kernels.hpp -- the small non-template kernels around the chain loops: the producers of the random stream
-// (types and device helpers: htm_stream.hpp), the set-up of a launch with several master workgroups (htm_flow.hpp) and the
-// probe of the peer-mapped inboxes (htm_step.hpp).  A non-template kernel defined in a header gives every unit that includes it
+// (types and device helpers: htm_stream.hpp), the set-up of a launch with several master workgroups (htm_flow.hpp: MbShared and
+// its MW_* words are defined there) and the probe of the peer-mapped inboxes (htm_handoff.hpp).  A non-template kernel defined in a header gives every unit that includes it
 // a host stub and a copy of the device code of its own, so exactly ONE unit includes this file: htm_hip.hip.
 #pragma once
 #include "htm_flow.hpp"
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(64) void k_mb_init(ChainsDev cs, int target_arg)
     }
 }
 
-// ---- htm_step.hpp ------------------------------------------------------------------------------------------------------
+// ---- htm_handoff.hpp ---------------------------------------------------------------------------------------------------
 // Probe of the peer-mapped inboxes (htm_chains_xchg_probe): one wave writes a token record into every rank's inbox and
 // waits (bounded, `ticks` of the 100 MHz clock) until the tokens of all ranks have arrived in its own -- the same
 // stores, loads and scopes exchange_post / exchange_finish use, so a mapping whose writes are not visible to a polling kernel is

@@ -1,8 +1,8 @@
 // htm_flow.hpp -- the FREE-RUNNING chain master of k_mcmc (single rank, MODE_RUN): the main loop of a rank
 // (hypo_tremor_mcmc.f90:236-284) without workgroup barriers.
 //
-// step_body (htm_step.hpp) runs an iteration as  passes | barrier A | roles | barrier B | post : every iteration lasts as
-// long as its slowest chain step plus ~3 k cycles of roles and post (round 2: 14.7 k cycles per iteration at 8 chains, of
+// The loop with barriers (step_body, htm_step.hpp) runs an iteration as  passes | barrier A | roles | barrier B | post : every
+// iteration lasts as long as its slowest chain step plus ~3 k cycles of roles and post (round 2: 14.7 k cycles per iteration at 8 chains, of
 // which a partial update is 7-8.6 k).  Here every chain wave runs its chain's steps back to back -- proposal, evaluation,
 // decision, commit, records, the orders of its coming full evaluations, next step -- and the waves meet only where the
 // algorithm couples the chains:
@@ -20,10 +20,11 @@
 //   * records: slots by LDS atomics, sorted by (iteration, chain) on the host when drained.
 // The protocol (prog / done / epoch / anchor, the turn rule, re-prediction from the anchor alone) is model-checked on the
 // CPU against the serial loop under random interleavings: tools/flow_protocol_sim.py.
-// Full evaluations: the worker blocks and the tagged-granule hand-off of htm_step.hpp, unchanged; the orders role P sent
-// for all chains are sent by each chain's own wave right after its commit (one step ahead, or two around a hypocentre step).
+// Full evaluations: the worker blocks (htm_worker.hpp) and the tagged-granule hand-off of htm_handoff.hpp, as in the loop with
+// barriers; the orders its role P sends for all chains are sent by each chain's own wave right after its commit (one step
+// ahead, or two around a hypocentre step).
 #pragma once
-#include "htm_step.hpp"
+#include "htm_handoff.hpp"
 
 #ifndef HTM_TURN_SLEEP
 #define HTM_TURN_SLEEP 1  // s_sleep argument in the turn's wait (64 clocks each)
@@ -394,7 +395,7 @@ __device__ __forceinline__ bool flow_adopt(CsRef cs_, FlowShared &sh, const Ring
 // Ranks other than 0 bet that judge_swap's draw is not theirs (flow_swap_at); the first wave that learns the pair settles the
 // bet for the rank (xanch): lost, it anchors the next iteration one position later under a new epoch -- the very mechanism
 // of a prior rejection -- before any wave of the rank commits a step of that iteration.
-// Inbox: region A [2][n_procs][xg] is the barrier loop's (exchange_post / exchange_finish, htm_step.hpp); region B
+// Inbox: region A [2][n_procs][xg] is the barrier loop's (exchange_post / exchange_finish, htm_handoff.hpp); region B
 // [kXSlots][n_procs][xg], slot = iteration & 7, is this loop's.  Per (slot, rank): granules 0..6 = header {i1, i2, draw hi,
 // lo, its log hi, lo, control word}, 8 + 4 c .. 8 + 4 c + 3 = chain c {T hi, lo, L hi, lo}.  Eight slots: a wave still reading
 // the headers of iteration j - 4 (its decision of j - 2) may see a peer post those of j (tools/flow_protocol_sim.py found the

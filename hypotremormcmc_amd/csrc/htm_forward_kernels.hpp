@@ -3,7 +3,7 @@
 // the device code of its own, so exactly ONE unit includes this file: htm_forward.hip.
 #pragma once
 #include "htm_kernels.hpp"
-#include "htm_step.hpp"
+#include "htm_handoff.hpp"
 
 namespace htm {
 

@@ -1,10 +1,13 @@
 // htm_hip.hip -- the chain sets' part of the C ABI (include/htm_hip.h): htm_chains_* and htm_comm_*.  (The forward model's part
 // is htm_forward.hip, the other steps' htm_steps.hip; this file keeps its name because most of it stayed where it was.)  Sets a chain set up from
 // its launch plan (htm_plan.hpp: which chain-master loop a launch takes, and its shape) and looks the loop's kernel up in the table of htm_host.hpp; the instantiations themselves are
-// compiled by the loop units (htm_loop_*.hip), none here.  This unit owns the small kernels of htm_chains_kernels.hpp.
+// compiled by the loop units (htm_loop_*.hip), none here.  This unit owns the small kernels of htm_chains_kernels.hpp.  From the loops it takes
+// sizes only: FlowShared, MbShared and kXSlots (htm_flow.hpp, through htm_chains_kernels.hpp), PipeShared and pipe_ring_bytes (htm_pipe.hpp),
+// mcmc_threads (htm_mcmc.hpp); the barrier loop's StepSharedT is htm_handoff.hpp's, so htm_step.hpp is not needed.
 #include "htm_host.hpp"
 #include "htm_chains_kernels.hpp"
 #include "htm_pipe.hpp"
+#include "htm_mcmc.hpp"
 
 #include <dlfcn.h>
 
@@ -50,7 +53,7 @@ int launch_mcmc(htm_chains *hc, int mode, int target, const double *gathered)
     htm_forward *h = hc->fwd;
     const LoopPlan &lp = hc->plan;
     hc->ctrl_fresh = false;
-    // one instantiation per main loop (MK, htm_pipe.hpp k_mcmc); the step log can be switched on after htm_chains_create
+    // one instantiation per main loop (MK, htm_mcmc.hpp k_mcmc); the step log can be switched on after htm_chains_create
     const int mk = loop_for(lp, mode, hc->h_ctrl.slog_cap != 0);
     LoopLaunch l{};
     l.grid = dim3((mk == 7 ? lp.mb_blocks : 1) + hc->dev.n_workers);
@@ -958,7 +961,7 @@ int htm_chains_run_lockstep(htm_chains *hc, int n_iter, htm_allgather_fn allgath
     return HTM_OK;
 }
 
-// ---- persistent lock-step: swap records exchanged inside the launch (exchange_post / exchange_finish in htm_step.hpp) --------
+// ---- persistent lock-step: swap records exchanged inside the launch (exchange_post / exchange_finish in htm_handoff.hpp) --------
 static int xchg_alloc(htm_chains *hc)
 {
     if (hc->d_inbox) return HTM_OK;

@@ -8,7 +8,12 @@
 //                          by plain functions without a device; kept in htm_chains::plan.  Ask for the plan of a shape with
 //                          htm_chains_plan (no GPU needed), for the plan of a chain set with htm_chains_get_plan
 //   htm_loop_*.hip         one unit per family of chain-master loops: nothing but its rows of the kernel table below
-//                          (made with htm_loop_rows.hpp)
+//                          (made with htm_loop_rows.hpp).  A unit includes htm_loop_rows.hpp and the header of the ONE loop it builds
+//   device headers         htm_device.hpp -> htm_stream.hpp -> htm_handoff.hpp (what the loops and the workers share) ->
+//                          htm_worker.hpp (worker_body) -> htm_mcmc.hpp (k_mcmc, k_mcmc_wide: declares the loops, includes none).
+//                          The loops, each on htm_handoff.hpp: htm_step.hpp (with barriers: step_body, k_step, k_step_wide),
+//                          htm_flow.hpp (free-running: flow_body), htm_pipe.hpp (pipelined: pipe_body; takes flow_swap_at from
+//                          htm_flow.hpp).  tests/test_loop_unit_headers.py holds every unit to the headers of its loop
 //   htm_steps.hip          steps 1-4, 6, the convergence diagnostics and the location error ellipsoids (htm_hypo_ellipsoid*);
 //                          touches neither htm_forward nor htm_chains
 //   htm_steps_host.hpp     the host idioms of htm_steps.hip, and of htm_forward_locate in htm_forward.hip: StreamBuf, a

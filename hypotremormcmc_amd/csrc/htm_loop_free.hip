@@ -1,6 +1,7 @@
 // htm_loop_free.hip -- the free-running chain master of a single rank (htm_flow.hpp): MK 3, and MK 8 specialised on what the job fixes.
 // Nothing but this family's rows of the kernel table (htm_host.hpp): one line per instantiation, compiled here and nowhere else.
 #include "htm_loop_rows.hpp"
+#include "htm_flow.hpp"
 
 namespace htm {
 

@@ -1,6 +1,7 @@
 // htm_loop_lock.hip -- the free-running chain master (htm_flow.hpp) as a lock-step rank, MK 4, and with several master workgroups, MK 7.
 // Nothing but this family's rows of the kernel table (htm_host.hpp): one line per instantiation, compiled here and nowhere else.
 #include "htm_loop_rows.hpp"
+#include "htm_flow.hpp"
 
 namespace htm {
 

@@ -1,6 +1,7 @@
 // htm_loop_pipe.hip -- the pipelined chain master (htm_pipe.hpp): MK 5 for a single rank, MK 6 as a lock-step rank.
 // Nothing but this family's rows of the kernel table (htm_host.hpp): one line per instantiation, compiled here and nowhere else.
 #include "htm_loop_rows.hpp"
+#include "htm_pipe.hpp"
 
 namespace htm {
 

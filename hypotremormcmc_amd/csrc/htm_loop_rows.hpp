@@ -1,8 +1,9 @@
 // htm_loop_rows.hpp -- what a loop unit (htm_loop_*.hip) makes its rows of the kernel table (htm_host.hpp) from: a row names its
-// instantiation once, and its address, its block size and its typed launch all come from that one mention.
+// instantiation once, and its address, its block size and its typed launch all come from that one mention.  k_mcmc comes with this
+// header (htm_mcmc.hpp); the loop it runs is the unit's to include: htm_step.hpp, htm_flow.hpp or htm_pipe.hpp, one of them.
 #pragma once
 #include "htm_host.hpp"
-#include "htm_pipe.hpp"
+#include "htm_mcmc.hpp"
 
 #pragma GCC visibility push(hidden)
 
@@ -26,7 +27,8 @@ LoopRow mcmc_row_of(bool wide, int nch, bool fp32, int mk, int threads)
 {
     return LoopRow{false, wide, nch, fp32, mk, LoopKernel{reinterpret_cast<const void *>(KERNEL), threads, &launch_mcmc_kernel<KERNEL>}};
 }
-// (k_step takes 64 threads per chain wave, which the caller knows: threads = 0; and no launch count, LoopLaunch::seq)
+// (k_step takes 64 threads per chain wave, which the caller knows: threads = 0; and no launch count, LoopLaunch::seq.  k_step and
+// k_step_wide are the barrier loop's own, htm_step.hpp: the two units that build it name them, step_row and step_wide_row there)
 template <auto KERNEL>
 LoopRow step_row_of(bool wide, int nch, bool fp32)
 {
@@ -35,8 +37,6 @@ LoopRow step_row_of(bool wide, int nch, bool fp32)
 // (k_mcmc is launched with 512 threads; the pipelined master's instantiations with their launch bound, mcmc_threads)
 template <int N, bool F, int K> LoopRow mcmc_row() { return mcmc_row_of<k_mcmc<N, F, K>>(false, N, F, K, (K == 5 || K == 6) ? mcmc_threads<N, K>() : 512); }
 template <int N, bool F, int K> LoopRow wide_row() { return mcmc_row_of<k_mcmc_wide<N, F, K>>(true, N, F, K, 512); }
-template <int N, bool F> LoopRow step_row() { return step_row_of<k_step<N, F>>(false, N, F); }
-template <int N, bool F> LoopRow step_wide_row() { return step_row_of<k_step_wide<N, F>>(true, N, F); }
 
 }  // namespace htm
 

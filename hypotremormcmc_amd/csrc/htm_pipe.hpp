@@ -33,6 +33,7 @@
 // A full evaluation's value does not depend on when its order went out: the events of the (up to two) hypocentre steps right
 // before it are ALWAYS left out by the workers and added by the evaluator -- at both candidate positions, D picks -- in a fixed
 // association, so the bits are a function of the stream and the state alone.
+// From htm_flow.hpp: flow_swap_at (the swap the stream holds where an iteration's chain steps end), uni, lds_ld / lds_st.
 #pragma once
 #include "htm_flow.hpp"
 
@@ -153,7 +154,7 @@ __device__ __forceinline__ void pipe_window(CsRef cs, PipeShared &sh, const Ring
 }
 
 // the orders of the coming full evaluations (lanes <-> chains): the chain's oldest unsent one goes out when the chain's state
-// is final and in memory up to `ahead` steps before it -> eight tagged granules into the chain's order slot (htm_step.hpp,
+// is final and in memory up to `ahead` steps before it -> eight tagged granules into the chain's order slot (htm_worker.hpp,
 // worker_body), and the request to the collector wave (col_w)
 __device__ __forceinline__ void pipe_orders(CsRef cs_, PipeShared &sh, const PipeRings &pr, PipeFront &F, int lane, unsigned long long launch)
 {
@@ -272,7 +273,7 @@ __device__ __forceinline__ void pipe_issue(CsRef cs_, PipeShared &sh, const Ring
 
 // judge_swap's draw of the swap found at E (cls_parallel.f90:163, :292-299) as this rank's stream has it: a single rank draws it
 // right after the pair; a lock-step rank PEEKS at the draw it would take if the pair's first chain were its own (rank 0
-// knows: then it is the last of the nd draws) -- what goes into the rank's swap record (htm_step.hpp, exchange_post)
+// knows: then it is the last of the nd draws) -- what goes into the rank's swap record (htm_handoff.hpp, exchange_post)
 template <bool LOCK>
 __device__ __forceinline__ void pipe_judge_draw(CsRef cs, const Ring &rg, int E, int i1, int nd, double &sr, double &slr)
 {
@@ -903,7 +904,7 @@ __device__ __forceinline__ void pipe_decider(FwRef f_, CsRef cs_, PipeShared &sh
         }
         // ---- the temperature of this iteration: the swap of the iteration before (cls_parallel.f90:121-136, :285-302)
         if constexpr (LOCK) {
-            // a lock-step rank: decided from ALL ranks' records (htm_step.hpp, exchange_finish; posted at the end of the iteration
+            // a lock-step rank: decided from ALL ranks' records (htm_handoff.hpp, exchange_finish; posted at the end of the iteration
             // before: their round trip ran under the wait and the checks above).  It may end the job (a rank asked everybody to
             // stop, or failed) or move this rank's stream (the judge draw was this rank's after all: cls_parallel.f90:163)
             if (it - 1 > i0) {
@@ -1192,61 +1193,6 @@ __device__ __forceinline__ void pipe_body(FwRef f_, CsRef cs_, int target_arg, i
         if (sh.na[k]) atomicAdd(&cs.n_accept[k], sh.na[k]);
     }
     if (tid == 0) *cs.ctrl = sh.c;
-}
-
-// One launch = the chain master (block 0) + W full-evaluation workers (blocks 1..W), all resident.
-// `launch` = the host's count of k_mcmc launches of this chain set (1, 2, ...): orders and the quit word carry it, so
-// nothing a previous launch left in memory can be mistaken for this launch's.
-// Blocks of 8 waves; the pipelined master with one station per lane takes 12 (three per SIMD, 168 registers a wave): nine
-// evaluators instead of five -- its throughput is the evaluators' (and the worker blocks take 12 events each).
-#ifndef HTM_PIPE_THREADS
-#define HTM_PIPE_THREADS 512
-#endif
-template <int NCH, int MK> constexpr int mcmc_threads() { return (MK >= 5 && MK <= 7 && NCH == 1) ? HTM_PIPE_THREADS : 512; }
-template <int NCH, bool F32 = false, int MK = 0>
-__global__ __launch_bounds__((mcmc_threads<NCH, MK>())) void k_mcmc(FwdDev f, ChainsDev cs, int mode, int target_arg,
-                                               const double *gathered, int ring_size, int wmax,
-                                               unsigned long long launch)
-{
-    const KArgLayout __attribute__((address_space(4))) &ka = *(const KArgLayout __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
-    // MK 7: several master workgroups (blocks 0 .. n_mb - 1, eight chains each: flow_body<.., MB>); the workers follow them
-    const int n_mb = MK == 7 ? (ka.cs.n_chains + 7) / 8 : 1;
-    if ((int)blockIdx.x < n_mb) {
-        // MK 3: the single-rank loop on the free-running master (flow_body); 0: the same loop with barriers (step_body)
-        // 4: a lock-step rank (MODE_LOCKRUN, swap records exchanged inside the launch) on the free-running master; 2: with barriers
-        // 8: MK 3 for a job whose shape the host has found fixed (flow_body<.., FlowFixed>: htm_flow.hpp, htm_plan.hpp loop_for)
-        if constexpr (MK == 3) flow_body<NCH, F32, false>(ka.f, ka.cs, target_arg, ring_size, wmax, launch);
-        else if constexpr (MK == 8) flow_body<NCH, F32, false, false, FlowFixed>(ka.f, ka.cs, target_arg, ring_size, wmax, launch);
-        else if constexpr (MK == 4) flow_body<NCH, F32, true>(ka.f, ka.cs, target_arg, ring_size, wmax, launch);
-        else if constexpr (MK == 5) pipe_body<NCH, F32, false>(ka.f, ka.cs, target_arg, ring_size, wmax, launch);      // the pipelined master: single rank
-        else if constexpr (MK == 6) pipe_body<NCH, F32, true>(ka.f, ka.cs, target_arg, ring_size, wmax, launch);       // ... a lock-step rank (MODE_LOCKRUN)
-        else if constexpr (MK == 7) { if (!flow_body<NCH, F32, false, true>(ka.f, ka.cs, target_arg, ring_size, wmax, launch)) return; }      // (only the workgroup that finishes last goes on)
-        else step_body<NCH, true, F32, MK>(ka.f, ka.cs, mode, target_arg, gathered, ring_size, wmax, launch);
-        // every exit of the master comes through here (its returns are uniform over the block): release the workers
-        __syncthreads();
-        if (threadIdx.x == 0) st_agent(&ka.cs.ps->quit, launch + 1ull);
-    } else {
-        worker_body<NCH, F32, mcmc_threads<NCH, MK>() / 64, (MK == 5 || MK == 6)>(ka.f, ka.cs, launch, (int)blockIdx.x - n_mb);
-    }
-}
-
-// k_mcmc for 33..64 chains: the loop with barriers only (MK 0 single rank, 1 one lock-step iteration per launch, 2 persistent
-// lock-step), its StepShared and the workers' order polls sized for kMaxWideChains.  The free-running, several-workgroup and
-// pipelined masters keep kMaxChains: their stream windows do not fit the LDS above ~35 chains.
-template <int NCH, bool F32, int MK>
-__global__ __launch_bounds__(512) void k_mcmc_wide(FwdDev f, ChainsDev cs, int mode, int target_arg,
-                                                    const double *gathered, int ring_size, int wmax,
-                                                    unsigned long long launch)
-{
-    static_assert(MK >= 0 && MK <= 2, "the wide kernels run the loop with barriers only");
-    const KArgLayout __attribute__((address_space(4))) &ka = *(const KArgLayout __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
-    if (blockIdx.x == 0) {
-        step_body<NCH, true, F32, MK, kMaxWideChains>(ka.f, ka.cs, mode, target_arg, gathered, ring_size, wmax, launch);
-        __syncthreads();
-        if (threadIdx.x == 0) st_agent(&ka.cs.ps->quit, launch + 1ull);
-    } else {
-        worker_body<NCH, F32, 8, false, kMaxWideChains>(ka.f, ka.cs, launch, (int)blockIdx.x - 1);
-    }
 }
 
 }  // namespace htm

@@ -320,7 +320,7 @@ inline Plan plan_phase_b(const Plan &a, const PlanJob &j, const Knobs &kn, const
     return p;
 }
 
-// ---- the ladder: the chain-master loop (MK, htm_pipe.hpp k_mcmc) a launch in `mode` takes -------------------------------------
+// ---- the ladder: the chain-master loop (MK, htm_mcmc.hpp k_mcmc) a launch in `mode` takes -------------------------------------
 // 0 the single-rank loop with barriers, 1 one lock-step iteration per launch, 2 persistent lock-step, 3 / 4 the free-running
 // master (single rank / lock-step), 5 / 6 the pipelined master, 7 several master workgroups, 8 the free-running master
 // specialised on what the job fixes (one or two stations per lane; diagnostic runs with a step log take the generic 3).

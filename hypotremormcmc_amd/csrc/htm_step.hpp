@@ -1,7 +1,10 @@
-// htm_step.hpp -- k_mcmc / k_step: the main loop of a rank (hypo_tremor_mcmc.f90:236-284) on the device.
+// htm_step.hpp -- the chain master WITH BARRIERS: step_body, the main loop of a rank (hypo_tremor_mcmc.f90:236-284) as
+// passes | barrier A | roles | barrier B | post.  Nothing here is used by another loop: what the loops share is htm_handoff.hpp.
 //
-// k_mcmc (the product path): block 0 = chain MASTER, blocks 1..W = full-evaluation WORKERS, one persistent launch.
-// k_step  (fallback, HTM_PERSIST=0): the master's code alone; exits at every full evaluation, k_full is its own launch.
+// k_mcmc<.., 0 / 1 / 2>, k_mcmc_wide (htm_mcmc.hpp): block 0 = chain MASTER (step_body), blocks 1..W = full-evaluation WORKERS,
+//         one persistent launch.  MK 0: single rank; 1: one lock-step iteration per launch; 2: persistent lock-step.
+// k_step, k_step_wide (here; fallback, HTM_PERSIST=0): the master's code alone; exits at every full evaluation, k_full is its
+//         own launch.
 //
 // Master workgroup, per iteration
 //   passes   chain waves, wave <-> chain (chains c = wave, wave+NW, ...), lane <-> station: look up where the step
@@ -19,249 +22,12 @@
 //   post     swap applied by the waves owning the two chains, samples recorded.
 // The loop ends when the target is reached, a record buffer is full or the produced stream runs out.
 #pragma once
-#include "htm_device.hpp"
-#include "htm_stream.hpp"
-
-#ifndef HTM_ALLOW2
-#define HTM_ALLOW2 1     // diagnostics: 0 = role P sends orders one iteration ahead only
-#endif
+#include "htm_handoff.hpp"
 
 namespace htm {
 
-// Kernel arguments are read where they are used, through references into the kernarg segment (constant address space:
-// scalar loads), re-based at the entry of every phase by an opaque move -- so the ~190 dwords of FwdDev + ChainsDev are
-// never all alive at once.  (Taken by value they are loaded at kernel entry, hoisted out of the iteration loop and
-// carried through it in spilled lanes: ~800 v_readlane reloads in the master's loop.)
-typedef const ChainsDev __attribute__((address_space(4))) &CsRef;
-typedef const FwdDev __attribute__((address_space(4))) &FwRef;
-typedef const StreamDev __attribute__((address_space(4))) &SdRef;
-template <class T>
-__device__ __forceinline__ const T __attribute__((address_space(4))) &rebase(const T __attribute__((address_space(4))) &r)
-{
-    const T __attribute__((address_space(4))) *p = &r;
-    asm volatile("" : "+s"(p));
-    return *p;
-}
-struct KArgLayout { FwdDev f; ChainsDev cs; };
-
-constexpr int kGathStage = 512;   // doubles of LDS for the gathered swap records (else they are read in place)
-
-template <int CAP>
-struct StepSharedT {
-    static constexpr int kCap = CAP;
-    Proposal prop[CAP];
-    double temp[CAP], L[CAP];
-    double rtemp[CAP];     // 1 / temperature (the Metropolis ratio multiplies by it), renewed wherever temp is written
-    int start[CAP];        // stream position (relative) at which each chain step started
-    int start_fix[CAP];    // corrected starts for a repeat pass (written by wave 0)
-    int cnt[CAP];          // draws the step consumed (judge draw included iff prior_ok)
-    int slot_l[CAP], slot_s[CAP];
-    int redone[CAP];       // the chain repeated its step in this iteration (undo + new commit: role P stays out)
-    // role P (k_mcmc): [iteration & 1][chain]: the chain's step of that iteration, starting at position pre_p, already
-    // has its order out under pre_tag; pre_mode 1: sent one iteration ahead, 2: two iterations ahead (evaluated on
-    // the state before the step in between; see chain_pass)
-    int pre_p[2][CAP];
-    unsigned pre_tag[2][CAP];
-    int pre_mode[2][CAP];
-    int pre_pa[2][CAP];   // two-ahead orders: where the step in between was expected to start
-    int np[CAP * 7], na[CAP * 7];   // proposal / acceptance counters of this launch
-    int sw_do, sw_c1, sw_c2;      // swap decided between the barriers; applied by the waves owning the chains
-    double sw_T1, sw_T2;          // new temperatures of chains sw_c1 / sw_c2
-    long long origin;             // absolute stream position of relative position 0 (= spos at launch)
-    long long hop_end;            // StreamDev::hop_end when this launch started
-    int avail;                    // the produced stream covers relative positions < avail
-    int fill;                     // the LDS ring holds relative positions < fill
-    int base;                     // relative position at which the current iteration starts
-    int redo;                     // >= 0: chains >= redo repeat their pass; -1: validated; -2: aborted
-    int catchup;                  // written between the barriers: the LDS window must be extended first
-    int rolep_iter;               // role P has finished for this iteration (see step_body)
-    double xrec[4 + 2 * CAP];   // MODE_LOCKRUN: this rank's swap record of the iteration (what goes to every rank's inbox)
-    int xdone;                    // MODE_LOCKRUN: the swap of every iteration <= xdone has been applied (see exchange_finish)
-    int xstop, xspec;             // decided by role V: this rank asks for a stop; the next iteration starts before the swap is known
-    unsigned xctl;                // the control word this rank posted with its latest record (exchange_post; read back by exchange_finish)
-    int xctl_iter;                // ... and the iteration it belongs to
-    Ctrl c;
-#ifdef HTM_STAMPS
-    unsigned long long stamp_acc[96];   // diagnostic cycle accounting of this launch, flushed to ChainsDev::stamps at its end
-#endif
-};
-// the narrow loops (htm_flow.hpp, htm_pipe.hpp and step_body up to kMaxChains); step_body at kMaxWideChains: the wide kernels
-using StepShared = StepSharedT<kMaxChains>;
-
-struct Ring {                     // LDS window of the stream rings, index = relative position & mask
-    double *U, *LOGU, *pg, *pr, *plogr;
-    int4 *dec, *sw;
-    int *hop;
-    int mask;
-    // k_mcmc only: LDS mirror of the non-hypocentre part of the rank's parameter vector (vs, t_corr, qs, a_corr
-    // of every chain; same offsets as ChainsDev::xall) and of its step sizes, kept current by the commits, so
-    // that role P needs no memory round trip.  mir_n = 0: no mirror (too large, or not the persistent kernel)
-    double *mx, *mstep;
-    int mir_n;
-    bool mir_steps;
-    int lock;                     // htm_flow.hpp: 1 = a lock-step rank (select_pair is rank 0's, judge_swap's draw the pair's first rank's)
-};
-
 constexpr int kPassRestart = -1;  // chain_pass: the swap of the iteration before moved this rank's stream position: start again
 constexpr int kPassAbort = -2;    // chain_pass: the job stops (or failed) after the iteration before: this step is not taken
-
-
-// one stream position in flight from the global rings to the LDS window
-typedef int i32x4 __attribute__((ext_vector_type(4)));      // (a plain vector: HIP's int4 class keeps temporaries in private memory)
-struct PfRegs {
-    double U, LOGU, pg, pr, plogr;
-    i32x4 dec, sw, h0, h1;
-    int p;                        // relative position, -1: nothing to store
-};
-
-template <int CAP>
-__device__ __forceinline__ void pf_load(PfRegs &r, CsRef cs_, const StepSharedT<CAP> &sh, int p, int limit)
-{
-    CsRef cs = rebase(cs_);
-    r.p = -1;
-    if (p < limit) {
-        SdRef sd = cs.stream;
-        const long long g = (sh.origin + p) & sd.mask;
-        r.U = sd.U[g]; r.LOGU = sd.LOGU[g]; r.pg = sd.pg[g]; r.pr = sd.pr[g]; r.plogr = sd.plogr[g];
-        r.dec = reinterpret_cast<const i32x4 *>(sd.dec)[g]; r.sw = reinterpret_cast<const i32x4 *>(sd.sw)[g];
-        const i32x4 *hs = reinterpret_cast<const i32x4 *>(sd.hop + g * kHops);
-        r.h0 = hs[0]; r.h1 = hs[1];
-        r.p = p;
-    }
-}
-
-__device__ __forceinline__ void pf_store(const PfRegs &r, const Ring &rg)
-{
-    if (r.p >= 0) {
-        const int l = r.p & rg.mask;
-        rg.U[l] = r.U; rg.LOGU[l] = r.LOGU; rg.pg[l] = r.pg; rg.pr[l] = r.pr; rg.plogr[l] = r.plogr;
-        reinterpret_cast<i32x4 *>(rg.dec)[l] = r.dec; reinterpret_cast<i32x4 *>(rg.sw)[l] = r.sw;
-        i32x4 *hd = reinterpret_cast<i32x4 *>(rg.hop + l * kHops);
-        hd[0] = r.h0; hd[1] = r.h1;
-    }
-}
-
-// every thread of the workgroup: extend the LDS window to cover relative positions < target
-// (kernel start; later only if a long select_pair redraw run ate the look-ahead)
-template <int CAP>
-__device__ __forceinline__ void prefetch_all(CsRef cs_, StepSharedT<CAP> &sh, const Ring &rg, int target)
-{
-    CsRef cs = rebase(cs_);
-    if (target > sh.avail) target = sh.avail;
-    if (target > sh.base + rg.mask + 1 - 8) target = sh.base + rg.mask + 1 - 8;
-    const int fl = sh.fill;
-    for (int p = fl + (int)threadIdx.x; p < target; p += (int)blockDim.x) {
-        PfRegs r;
-        pf_load(r, cs, sh, p, target);
-        pf_store(r, rg);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && target > sh.fill) sh.fill = target;
-    __syncthreads();
-}
-
-// The rank's parameter vector is ONE allocation per field, groups in proposal-type order [vs | t_corr | qs | a_corr | hypo],
-// each [n_chains][nx] (ChainsDev::xall and friends): every element is base + integer offset -- scalar arithmetic on one
-// pointer instead of a choice between the five ModelDev windows (fewer kernel arguments alive in the loop).
-struct GroupOff { int tc, qs, ac, hy, nh; };
-__device__ __forceinline__ GroupOff group_offsets(CsRef cs_)
-{
-    CsRef cs = rebase(cs_);
-    const int nc = cs.n_chains, S = cs.S;
-    GroupOff g;
-    g.tc = nc; g.qs = nc + nc * S; g.ac = 2 * nc + nc * S; g.hy = 2 * nc + 2 * nc * S; g.nh = 3 * cs.E;
-    return g;
-}
-// element idx of chain c's model of proposal type `type` (1 vs, 2 t_corr, 3 qs, 4 a_corr, 5..7 hypo)
-__device__ __forceinline__ int elem_offset(CsRef cs_, int type, int c, int idx)
-{
-    CsRef cs = rebase(cs_);
-    const GroupOff g = group_offsets(cs);
-    const int goff = type == 1 ? 0 : type == 2 ? g.tc : type == 3 ? g.qs : type == 4 ? g.ac : g.hy;
-    const int gnx = (type == 1 || type == 3) ? 1 : (type == 2 || type == 4) ? cs.S : g.nh;
-    return goff + c * gnx + idx;
-}
-
-// inclusive prefix sum over the 64 lanes (DPP row_shr scan + row_bcast, ints)
-__device__ __forceinline__ int wave_incl_scan(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);   // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);   // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);   // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);   // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);   // row_bcast:15
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);   // row_bcast:31
-    return v;
-}
-
-// Chain state (x vectors, temperatures, log-likelihoods) is rewritten by this kernel while it loops over
-// iterations.  hipcc turns uniform-address loads into scalar (K$) loads, and the scalar cache is not
-// coherent with vector stores, so mutable state must be read with VECTOR loads.  `volatile` would do that but
-// also makes the backend wait for every single load (s_waitcnt vmcnt(0) after each), serialising ~700-cycle
-// latencies; instead the address gets a per-lane zero the compiler cannot see through, which keeps the loads
-// ordinary (L1-cached, freely overlapped) vector loads.
-__device__ __forceinline__ int opaque_zero()
-{
-    int z;
-    asm volatile("v_mov_b32 %0, 0" : "=v"(z));
-    return z;
-}
-__device__ __forceinline__ double ld_state(const double *p, int vz) { return p[vz]; }
-
-// lane l of a double, as a wave-uniform value
-__device__ __forceinline__ double rl_f64(double v, int l)
-{
-    const long long b = __double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, l);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)b >> 32), l);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-// agent-scope relaxed accesses: sc1 write-through stores / L1-bypassing loads (MI355X_MICROARCH.md,
-// inter-workgroup visibility).  Used for everything another workgroup of the same launch reads or writes.
-__device__ __forceinline__ void st_agent(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_agent(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_agent(unsigned long long *p, unsigned long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ double ld_agent(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int ld_agent(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ unsigned long long ld_agent(const unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_gran(unsigned long long *g, unsigned tag, unsigned payload)
-{
-    st_agent(g, ((unsigned long long)tag << 32) | payload);
-}
-__device__ __forceinline__ void st_gran_f64(unsigned long long *g, unsigned tag, double v)   // two granules
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    st_gran(g, tag, (unsigned)(b >> 32));
-    st_gran(g + 1, tag, (unsigned)b);
-}
-__device__ __forceinline__ double gran_f64(unsigned long long hi, unsigned long long lo)
-{
-    return __longlong_as_double((long long)(((hi & 0xffffffffull) << 32) | (lo & 0xffffffffull)));
-}
-__device__ __forceinline__ void drain_vmem() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// system-scope relaxed accesses: what another GPU (or another process on this one) writes into / reads from this
-// rank's memory over xGMI while the kernel runs (swap-record inboxes, fine-grained allocations)
-__device__ __forceinline__ void st_sys(unsigned long long *p, unsigned long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
-__device__ __forceinline__ unsigned long long ld_sys(const unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
-
-// The master takes back whatever order chain c's slot holds (k_mcmc): granule 0 loses its tag, so the slot is no longer
-// a complete order -- a worker that has not looked yet never takes it, a worker waiting for the order's named commit
-// sees the slot change and drops it.  This is how a void order is SIGNALLED (the chain repeated a pass, or the order
-// was written for a stream position the step does not start at); nothing on the hand-off path is decided by a clock.
-__device__ __forceinline__ void void_slot(CsRef cs_, int c)
-{
-    CsRef cs = rebase(cs_);
-    for (int r = 0; r < cs.slot_rep; ++r) st_gran(cs.slots + (size_t)r * cs.slot_stride + c * kGranPerSlot, 0u, 0u);
-}
-
-__device__ __forceinline__ bool metropolis(double L_new, double L_cur, double T, double lpr, double r,
-                                           double logr)
-{
-    double ratio = (L_new - L_cur) * T;     // cls_mcmc.f90:194-195; T = 1 / temperature here (formed once per swap, not per step)
-    ratio = ratio + lpr;
-    return r >= kEps && logr <= ratio;      // :198-199
-}
 
 #ifdef HTM_STAMPS
 #define CSTAMP(k) do { if (stamp_me) { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); sh.stamp_acc[32 + (k)] += n_ - t_last; t_last = n_; } } while (0)
@@ -739,15 +505,6 @@ __device__ __forceinline__ bool swap_plan(CsRef cs_, const StepSharedT<CAP> &sh,
 // one post phase and one step front (~2 us) before its own wave would send it.  Only for chains that did not
 // commit in this iteration: their state stores have provably landed (every wave drains before the commit of its pass).
 // The chain wave recognises the order by its start position and goes straight to collecting the partial sums.
-// start of the chain step n steps after the one that starts at pos (hop tables cover kHops steps at a time)
-__device__ __forceinline__ int hop_ahead(const Ring &rg, int pos, int n)
-{
-    int p = pos;
-    while (n > kHops) { p += rg.hop[(p & rg.mask) * kHops + kHops - 1]; n -= kHops; }
-    if (n > 0) p += rg.hop[(p & rg.mask) * kHops + n - 1];
-    return p;
-}
-
 struct PreOrder {            // per lane (<-> chain)
     bool job;
     int c;
@@ -910,47 +667,6 @@ __device__ __forceinline__ void post_chain(CsRef cs_, StepSharedT<CAP> &sh, int 
     }
 }
 
-// thread 0: temperature swap between chains of any two ranks from the all-gathered records
-// (cls_parallel.f90:118-213, :285-302).  Every rank evaluates the same decision from the same records.
-template <int CAP>
-__device__ __forceinline__ void apply_swap(CsRef cs_, StepSharedT<CAP> &sh, const double *gathered)
-{
-    CsRef cs = rebase(cs_);
-    const int nc = cs.n_chains, RW = 4 + 2 * nc;
-    const int iter = sh.c.iter_done + 1;
-    if (cs.n_procs * nc > 1) {
-        for (int r = 0; r < cs.n_procs; ++r)
-            if ((int)gathered[(size_t)r * RW + 3] != iter) sh.c.err = -6;
-        const int i1 = (int)gathered[0], i2 = (int)gathered[1];
-        const int rank1 = i1 / nc, chain1 = i1 % nc, rank2 = i2 / nc, chain2 = i2 % nc;
-        const double T1 = gathered[(size_t)rank1 * RW + 4 + 2 * chain1];
-        const double L1 = gathered[(size_t)rank1 * RW + 5 + 2 * chain1];
-        const double T2 = gathered[(size_t)rank2 * RW + 4 + 2 * chain2];
-        const double L2 = gathered[(size_t)rank2 * RW + 5 + 2 * chain2];
-        const double r = gathered[(size_t)rank1 * RW + 2];
-        const double del_s = (L2 - L1) * (1.0 / T1 - 1.0 / T2);
-        bool acc = false;
-        if (r >= kEps) { if (log(r) <= del_s) acc = true; }
-        if (acc) {
-            if (cs.rank == rank1) { cs.temp[chain1] = T2; sh.temp[chain1] = T2; sh.rtemp[chain1] = 1.0 / T2; }
-            if (cs.rank == rank2) { cs.temp[chain2] = T1; sh.temp[chain2] = T1; sh.rtemp[chain2] = 1.0 / T1; }
-        }
-        if (cs.rank == rank1) sh.c.spos += 1;       // judge_swap's rand_u() came from rank1's stream
-    }
-    sh.c.iter_done = iter;
-    sh.c.stage = ST_IDLE;
-}
-
-// MODE_LOCKRUN, wave 0, after the roles of iteration `iter`: this rank's swap record goes into EVERY rank's inbox
-// (its own included) as tagged 8-byte granules {iteration : 32, payload : 32} written with system-scope stores -- over
-// xGMI into the peers' memory, no collective, no kernel boundary --, then the wave polls its own inbox until all
-// n_procs records of this iteration are complete, stages them in LDS as the doubles apply_swap reads, and lane 0
-// decides the swap exactly as every other rank does (cls_parallel.f90:118-213).  Record = the (4 + 2 n_chains) words
-// of the all-gather protocol + one control word: bit 0 = this rank asks everybody to stop after this iteration
-// (record buffers or produced random stream nearly used up: the host drains / refills and launches again), bit 1 = it
-// has failed.  Inbox parity = iter & 1: a rank can be at most one iteration ahead of the slowest one.
-constexpr int kXLoads = 8;        // granule loads per lane in flight while polling
-
 // every thread, after the roles of an iteration: does this rank ask everybody to stop after it?
 template <int CAP>
 __device__ __forceinline__ bool want_stop_now(CsRef cs_, const StepSharedT<CAP> &sh, int wmax)
@@ -958,100 +674,6 @@ __device__ __forceinline__ bool want_stop_now(CsRef cs_, const StepSharedT<CAP> 
     CsRef cs = rebase(cs_);
     const int nc = cs.n_chains;
     return sh.c.n_lik + 2 * nc > cs.cap_lik || sh.c.n_smp + 2 * nc > cs.cap_smp || sh.avail < sh.base + 3 * wmax;
-}
-
-// one wave: this rank's record of iteration `iter` into every rank's inbox
-template <int CAP>
-__device__ __forceinline__ void exchange_post(CsRef cs_, StepSharedT<CAP> &sh, int iter, int lane, bool want_stop)
-{
-    CsRef cs = rebase(cs_);
-    const int nc = cs.n_chains, RW = 4 + 2 * nc, G = cs.xg, np = cs.n_procs, par = iter & 1;
-    const unsigned tag = (unsigned)iter;
-    const unsigned ctl = (want_stop ? 1u : 0u) | (sh.c.err ? 2u : 0u);
-    if (lane == 0) { sh.xctl = ctl; sh.xctl_iter = iter; }      // (this rank's own record is taken from LDS when the records are collected)
-    if (__builtin_expect(cs.dbg_xfail_iter > 0 && iter >= cs.dbg_xfail_iter, 0)) return;      // (fault injection: the peers never see this record)
-    for (int g0 = 0; g0 < G; g0 += 64) {
-        const int g = g0 + lane;
-        if (g < G) {
-            const int w = g >> 1;
-            unsigned pay;
-            if (w < RW) {
-                const unsigned long long b = (unsigned long long)__double_as_longlong(sh.xrec[w]);
-                pay = (g & 1) ? (unsigned)b : (unsigned)(b >> 32);
-            } else pay = (g & 1) ? 0u : ctl;
-            const unsigned long long v = ((unsigned long long)tag << 32) | pay;
-            for (int q = 0; q < np; ++q) st_sys(ld_const(cs.outbox + q) + (size_t)(par * np + cs.rank) * G + g, v);
-        }
-    }
-}
-
-// the same wave, later: wait for the n_procs records of iteration `iter`, decide the swap, publish sh.xdone = iter.
-// Rows of 64 granules, row = (rank r, chunk k of its record); kXLoads rows in flight.
-template <int CAP>
-__device__ __forceinline__ void exchange_finish(CsRef cs_, StepSharedT<CAP> &sh, double *s_gath, int iter, int lane, bool publish = true)
-{
-    CsRef cs = rebase(cs_);
-    const int nc = cs.n_chains, RW = 4 + 2 * nc, G = cs.xg, np = cs.n_procs, par = iter & 1;
-    const unsigned tag = (unsigned)iter;
-    const unsigned long long *in = cs.inbox + (size_t)par * np * G;
-    unsigned *gu = reinterpret_cast<unsigned *>(s_gath);
-    const int chunks = (G + 63) >> 6, rows = np * chunks;
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();       // 100 MHz
-    unsigned anyctl = 0;
-    bool dead = false;
-    // This rank's own record does not travel: it is read from LDS where exchange_post took it from (sh.xrec, sh.xctl) -- the round
-    // trip of the rank's own stores through fine-grained memory was on the path of every lock-step iteration (HTM_XOWN=0 restores it).
-    const bool own_lds = cs.xown != 0 && sh.xctl_iter == iter;
-    for (int row0 = 0; row0 < rows && !dead; row0 += kXLoads) {
-        unsigned long long v[kXLoads];
-        for (;;) {
-            bool ok = true;
-#pragma unroll
-            for (int j = 0; j < kXLoads; ++j) {
-                const int row = row0 + j, r = row / chunks, k = (row - r * chunks) * 64 + lane;
-                v[j] = (unsigned long long)tag << 32;
-                if (row < rows && k < G) {
-                    if (own_lds && r == cs.rank) {
-                        const int w = k >> 1;
-                        unsigned pay;
-                        if (w < RW) {
-                            const unsigned long long b = (unsigned long long)__double_as_longlong(sh.xrec[w]);
-                            pay = (k & 1) ? (unsigned)b : (unsigned)(b >> 32);
-                        } else pay = (k & 1) ? 0u : sh.xctl;
-                        v[j] = ((unsigned long long)tag << 32) | pay;
-                    } else v[j] = ld_sys(in + (size_t)r * G + k);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < kXLoads; ++j) ok = ok && (unsigned)(v[j] >> 32) == tag;
-            if (__all(ok)) break;
-            if (__builtin_amdgcn_s_memrealtime() - t0 > cs.xwait_ticks) {       // 20 s: a peer is gone
-                if (lane == 0) sh.c.err = -10;
-                dead = true;
-                break;
-            }
-        }
-        if (dead) break;
-#pragma unroll
-        for (int j = 0; j < kXLoads; ++j) {
-            const int row = row0 + j, r = row / chunks, k = (row - r * chunks) * 64 + lane;
-            if (row < rows && k < G) {
-                const int w = k >> 1;
-                if (w < RW) gu[2 * (r * RW + w) + ((k & 1) ? 0 : 1)] = (unsigned)v[j];      // little-endian halves of the double
-                else if (!(k & 1)) anyctl |= (unsigned)v[j];
-            }
-        }
-    }
-    const bool stop_any = __ballot((anyctl & 1u) != 0) != 0ull, err_any = __ballot((anyctl & 2u) != 0) != 0ull;
-    if (lane == 0) {
-        if (!dead && sh.c.err == 0 && sh.c.stage == ST_WAIT_SWAP) {
-            apply_swap(cs, sh, s_gath);                         // iteration done; rank1 consumed its judge_swap draw
-            sh.base = (int)(sh.c.spos - sh.origin);
-        }
-        if (stop_any && sh.c.stop == 0) sh.c.stop = 3;          // everybody leaves after this iteration
-        if (err_any && sh.c.err == 0) sh.c.err = -11;           // a peer reported a failure
-        if (publish) __hip_atomic_store(&sh.xdone, iter, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
 }
 
 #ifdef HTM_STAMPS
@@ -1471,366 +1093,6 @@ __global__ __launch_bounds__(512) void k_step_wide(FwdDev f, ChainsDev cs, int m
 {
     const KArgLayout __attribute__((address_space(4))) &ka = *(const KArgLayout __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
     step_body<NCH, false, F32, -1, kMaxWideChains>(ka.f, ka.cs, mode, target_arg, gathered, ring_size, wmax, 0ull);
-}
-
-// Worker block of a k_mcmc launch: waits for work orders of its own launch and evaluates its event tile of
-// every model in the order (same arithmetic as k_full: wave <-> event, lane <-> station).  Block w, wave v
-// take events (w*8 + v) + k * 8 * W.  The immutable inputs of its first event (observation rows, station
-// coordinates) are loaded once per launch and stay in registers.  Hand-off in both directions by tagged
-// granules (data is the flag); chain state is read with agent-scope loads after the job word has been seen
-// (the master drained its stores before publishing it).  Leaves when the master has finished (PSync::quit)
-// or after a bounded wait.
-// NWV = waves per worker block (8: the master's block shape).  PIPE: the launch's master is the pipelined one (htm_pipe.hpp), whose
-// orders name a second left-out event and want the left-out events' sums reported on their own -- compiled only into those
-// launches: in the workers' event loop it costs the others 13 % at 10 000 x 128 x 16 fp64 (profiles/r04_h_worker_pipe_ab.txt).
-template <int NCH, bool F32, int NWV = 8, bool PIPE = false, int CAP = kMaxChains>
-__device__ __forceinline__ void worker_body(FwRef f_, CsRef cs_, unsigned long long launch, int w)
-{
-    CsRef cs = rebase(cs_);
-    FwRef f = rebase(f_);
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    double *s_red = reinterpret_cast<double *>(smem);          // [NWV <= 16]
-    unsigned *s_tag = reinterpret_cast<unsigned *>(smem + 128);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int W = cs.n_workers;
-    const int nc = cs.n_chains;
-    const int ev0 = w * NWV + wave;
-
-    constexpr int N = NCH > 0 ? NCH : 1;
-    StaRegs<N> st;
-    ObsRegs<N, F32> ob0;
-    if constexpr (NCH > 0) {
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int j = lane + 64 * c;
-            const bool valid = j < f.S;
-            st.sx[c] = valid ? f.sx[j] : 0.0; st.sy[c] = valid ? f.sy[j] : 0.0; st.sz[c] = valid ? f.sz[j] : 0.0;
-            st.tc[c] = 0.0; st.ac[c] = 0.0;
-        }
-        if (ev0 < f.E) load_obs_regs<NCH, F32>(ob0, f, ev0, lane);
-    }
-
-    int *s_chain = reinterpret_cast<int *>(smem + 136);
-    // wave 0: lane 8k + g holds granule g of chain (8 j + k)'s slot; lane 8k remembers the last tag served
-    constexpr int kGroups = (CAP + 7) / 8;
-    unsigned last_tag[kGroups];
-#pragma unroll
-    for (int j = 0; j < kGroups; ++j) last_tag[j] = 0;
-    // An order whose named commit does not show within kDeferTicks is put aside -- its tag stays in last_tag, so the polls
-    // skip it -- and becomes eligible again kDeferTicks later (if the slot still holds it): a wait that the master's
-    // signals should have ended (void_slot) must never keep the worker from the other chains' orders.
-    constexpr unsigned long long kDeferTicks = 2000ull;       // 20 us of the 100 MHz clock; legitimate waits are a few us
-    // (kept in LDS, wave 0 only: scalar registers are what this kernel is short of)
-    int *s_defer_chain = reinterpret_cast<int *>(smem + 192);
-    unsigned long long *s_defer_until = reinterpret_cast<unsigned long long *>(smem + 200);
-    if (threadIdx.x == 0) { *s_defer_chain = -1; *s_defer_until = 0ull; }
-    // [0] type | idx << 3, [1] x_new high, [2] x_new low, [3] committed element or ~0, [4] its value high, [5] low,
-    // [6] element (+1) whose value, as seen by this evaluation, is to be reported (two-ahead orders), 0 = none
-    unsigned *s_job = reinterpret_cast<unsigned *>(smem + 160);
-    const unsigned long long *slots = cs.slots + (size_t)(w % cs.slot_rep) * cs.slot_stride;
-    const int npoll = cs.npoll;
-    for (;;) {
-        if (wave == 0) {
-            unsigned tag = 0;
-            int chain = -1;
-            const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();          // 100 MHz
-            // one poll = the slots of all chains (one load per 8 chains) + the quit word; npoll polls in flight
-            constexpr int kPolls = 3;
-            unsigned long long x[kPolls][kGroups], qw[kPolls];
-            auto issue = [&](int b) __attribute__((always_inline)) {
-#pragma unroll
-                for (int j = 0; j < kGroups; ++j) {
-                    x[b][j] = 0ull;
-                    if (8 * j < nc && 8 * j + (lane >> 3) < nc) x[b][j] = ld_agent(slots + (size_t)(8 * j) * kGranPerSlot + lane);
-                }
-                qw[b] = lane == 63 ? ld_agent(&cs.ps->quit) : 0ull;
-            };
-            // returns 1: an order was taken (tag, chain, s_job set), -1: the master has quit, 0: nothing yet
-            auto check = [&](int b) __attribute__((always_inline)) -> int {
-#pragma unroll
-                for (int j = 0; j < kGroups; ++j) {
-                    if (8 * j >= nc) continue;
-                    const unsigned t = (unsigned)(x[b][j] >> 32), pay = (unsigned)x[b][j];
-                    const unsigned tq = (unsigned)__builtin_amdgcn_update_dpp(0, (int)t, 0x00, 0xF, 0xF, false);    // quad_perm [0,0,0,0]
-                    const unsigned t4 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)t, 0x114, 0xF, 0xF, false);   // row_shr:4
-                    bool ok = t == tq && t != 0u && 8 * j + (lane >> 3) < nc;
-                    if ((lane & 7) == 4) ok = ok && t == t4;                 // second quad agrees with the first
-                    if ((lane & 7) == 0) ok = ok && pay == (unsigned)launch && t != last_tag[j];
-                    unsigned long long m = __ballot(ok);
-                    m &= m >> 1; m &= m >> 2; m &= m >> 4; m &= 0x0101010101010101ull;
-                    if (m) {
-                        const int l0 = __ffsll((long long)m) - 1;           // lane of granule 0 of the chosen chain
-                        chain = 8 * j + (l0 >> 3);
-                        tag = (unsigned)__builtin_amdgcn_readlane((int)t, l0);
-                        if (lane == l0) last_tag[j] = tag;
-                        unsigned pv[7];
-#pragma unroll
-                        for (int q = 0; q < 7; ++q) pv[q] = (unsigned)__builtin_amdgcn_readlane((int)pay, l0 + 1 + q);
-                        if (lane == 0) {
-#pragma unroll
-                            for (int q = 0; q < 7; ++q) s_job[q] = pv[q];
-                        }
-                        return 1;
-                    }
-                }
-                const unsigned qlo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)qw[b], 63);
-                const unsigned qhi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(qw[b] >> 32), 63);
-                return ((((unsigned long long)qhi << 32) | qlo) > launch) ? -1 : 0;
-            };
-#pragma unroll
-            for (int b = 0; b < kPolls; ++b) if (b < npoll) issue(b);
-            auto rearm = [&](int dc) __attribute__((always_inline)) {       // the order put aside may be taken again
-#pragma unroll
-                for (int j = 0; j < kGroups; ++j)
-                    if (j == (dc >> 3) && lane == 8 * (dc & 7)) last_tag[j] = 0;
-                if (lane == 0) *s_defer_chain = -1;
-            };
-            for (bool spin = true; spin;) {
-                {
-                    const int dc = *s_defer_chain;
-                    if (__builtin_expect(dc >= 0, 0)) { if (__builtin_amdgcn_s_memrealtime() > *s_defer_until) rearm(dc); }
-                }
-#pragma unroll
-                for (int b = 0; b < kPolls; ++b) {
-                    if (b >= npoll) continue;
-#ifdef HTM_STAMPS
-                    if (cs.stamps && w == 0 && lane == 0) cs.stamps[27] += 1;      // polls of worker 0
-#endif
-                    int r = spin ? check(b) : 0;
-                    if (r == 1 && s_job[3] != 0xffffffffu) {
-                        // The order was sent ahead of the chain's latest commit: wait until that store is what memory returns
-                        // (the other waves read the chain's state only after this wave has seen it).  If the master takes the
-                        // order back meanwhile -- the chain repeated a pass and rewrote the element, so the value never shows --
-                        // it says so by rewriting the slot (void_slot, or a newer order): the order is dropped and the worker
-                        // keeps polling.  A wait that lasts longer than any commit takes to land puts the order ASIDE for a while
-                        // (kDeferTicks): it is neither dropped nor answered on the clock's say-so, the worker merely serves the other
-                        // chains' orders meanwhile and looks again later.  The further bounds are fail-stops (master gone, 30 s).
-                        const unsigned long long want = ((unsigned long long)s_job[4] << 32) | s_job[5];
-                        const unsigned long long tw0 = __builtin_amdgcn_s_memrealtime();
-                        for (unsigned spins = 0;; ++spins) {
-                            if ((unsigned long long)__double_as_longlong(ld_agent(cs.xall + s_job[3])) == want) break;
-                            const unsigned now_tag = (unsigned)(ld_agent(slots + (size_t)chain * kGranPerSlot) >> 32);
-                            if (now_tag != tag) {
-#ifdef HTM_STAMPS
-                                if (lane == 0 && w == 0 && cs.stamps) {
-                                    cs.stamps[112] += 1; cs.stamps[113] = chain; cs.stamps[114] = tag; cs.stamps[115] = s_job[3]; cs.stamps[116] = want;
-                                    cs.stamps[117] = (unsigned long long)__double_as_longlong(ld_agent(cs.xall + s_job[3])); cs.stamps[118] = s_job[0]; cs.stamps[119] = now_tag;
-                                }
-#endif
-                                r = 0; tag = 0; chain = -1;      // taken back: keep polling
-                                break;
-                            }
-                            if ((spins & 7u) == 7u && __builtin_amdgcn_s_memrealtime() - tw0 > kDeferTicks) {
-                                // not now: back to the polls, this order aside (it stays in last_tag until it is re-armed)
-                                if (w == 0 && lane == 0) cs.diag[24] += 1;          // (reported with error -8)
-                                { const int dc = *s_defer_chain; if (dc >= 0) rearm(dc); }
-                                if (lane == 0) { *s_defer_chain = chain; *s_defer_until = __builtin_amdgcn_s_memrealtime() + kDeferTicks; }
-                                r = 0; tag = 0; chain = -1;
-                                break;
-                            }
-                            if ((spins & 63u) == 63u) {          // fail-stops only
-                                if (w == 0 && lane == 0 && cs.diag[16] == 0 && __builtin_amdgcn_s_memrealtime() - t0 > 100000000ull) {
-                                    // a second in this wait: leave a note for the host's error message (once)
-                                    unsigned long long *dg = cs.diag;
-                                    dg[17] = chain; dg[18] = tag; dg[19] = s_job[3]; dg[20] = want;
-                                    dg[21] = (unsigned long long)__double_as_longlong(ld_agent(cs.xall + s_job[3])); dg[22] = s_job[0]; dg[23] = s_job[6];
-                                    dg[16] = 1;
-                                }
-                                if (ld_agent(&cs.ps->quit) > launch) { r = -1; tag = 0; chain = -1; break; }
-                                if (__builtin_amdgcn_s_memrealtime() - t0 > 3000000000ull) { r = -1; tag = 0; chain = -1; break; }
-                            }
-                            __builtin_amdgcn_s_sleep(1);
-                        }
-                    }
-                    if (r != 0) spin = false;
-                    if (spin) issue(b);
-                }
-                if (spin && __builtin_amdgcn_s_memrealtime() - t0 > 3000000000ull) spin = false;   // never spin forever (30 s)
-            }
-            if (lane == 0) { *s_tag = tag; *s_chain = chain; }
-        }
-        __syncthreads();
-        const unsigned tag = *s_tag;
-        const int m = *s_chain;
-        if (tag == 0) return;
-#ifdef HTM_STAMPS
-        const bool wstamp = cs.stamps && w == 0 && tid == 0;
-        if (wstamp) cs.stamps[21] += __builtin_amdgcn_s_memrealtime();
-#endif
-        {
-            // (bit 31 of the order word: an order of the pipelined master, htm_pipe.hpp -- no commit is named, and the word after
-            // it names a SECOND event the workers leave out)
-            const bool pipe_order = PIPE && (s_job[0] >> 31) != 0u;
-            const int type = (int)(s_job[0] & 7u), idx = (int)((s_job[0] & 0x7fffffffu) >> 3);
-            const double ov_val = __longlong_as_double((long long)(((unsigned long long)s_job[1] << 32) | s_job[2]));
-            // vs and qs of the evaluated model: chain state unless they are the proposal (same round of loads as
-            // the corrections and the event coordinates below)
-            const GroupOff go = group_offsets(cs);
-            const double beta_c = ld_agent(cs.xall + m), q_c = ld_agent(cs.xall + go.qs + m);
-            const double beta = type == 1 ? ov_val : beta_c, q = type == 3 ? ov_val : q_c;
-            // (once per order, not once per event: cls_forward.f90:118, :204 divide per station; event_misfit multiplies)
-            const double rbeta_j = 1.0 / beta, katt_j = (kPi * kFreq) / (q * beta);
-            int ov_kind = 0, ov_idx = -1, ov_evt = -1, ov_cmp = 0;
-            const int r_off = (int)s_job[6] - 1 - (go.hy + m * go.nh);
-            const int r_evt = s_job[6] ? r_off / 3 : -1;       // two-ahead orders: the event left to the chain's own wave
-            const int r_off2 = (int)s_job[4] - 1 - (go.hy + m * go.nh);
-            const int r_evt2 = (pipe_order && s_job[4]) ? r_off2 / 3 : -1;
-            // An order of the pipelined master: the wave that holds a left-out event evaluates it at BOTH candidate positions --
-            // where the state has it, and with the component that the hypocentre step in between proposes (its value comes in
-            // tagged granules beside the order) -- under this order's parameters, and reports the two sums on their own: the
-            // master adds the one that step's decision selects (htm_pipe.hpp).
-            unsigned long long lgv0 = 0, lgv1 = 0, lgv2 = 0, lgv3 = 0;
-            if (pipe_order && (r_evt >= 0 || r_evt2 >= 0)) {
-                const unsigned long long *lgi = cs.lo_gran + (size_t)m * 16;
-                lgv0 = ld_agent(lgi); lgv1 = ld_agent(lgi + 1); lgv2 = ld_agent(lgi + 2); lgv3 = ld_agent(lgi + 3);
-            }
-            auto leftout = [&](const auto &ob_, double x, double y, double z, int e, const auto &st_, double rb_, double ka_) __attribute__((always_inline)) {
-                if constexpr (NCH > 0) {
-                    const int k = (e == r_evt) ? 0 : 1;
-                    const int cmpk = k == 0 ? r_off - 3 * r_evt : r_off2 - 3 * r_evt2;
-                    unsigned long long *lg = cs.lo_gran + (size_t)m * 16;
-                    unsigned long long a = k == 0 ? lgv0 : lgv2, b = k == 0 ? lgv1 : lgv3;      // (requested with the order's state loads)
-                    for (unsigned spins = 0; spins < (1u << 22); ++spins) {
-                        if ((unsigned)(a >> 32) == tag && (unsigned)(b >> 32) == tag) break;
-                        __builtin_amdgcn_s_sleep(1);
-                        a = ld_agent(lg + 2 * k); b = ld_agent(lg + 2 * k + 1);
-                    }
-                    if ((unsigned)(a >> 32) != tag || (unsigned)(b >> 32) != tag) return;      // (never seen: the master's collector reports the unanswered order)
-                    const double xn = gran_f64(a, b);
-                    const double px[2] = {x, cmpk == 0 ? xn : x};
-                    const double py[2] = {y, cmpk == 1 ? xn : y};
-                    const double pz[2] = {z, cmpk == 2 ? xn : z};
-                    double o2[2];
-                    event_misfit<(NCH > 0 ? NCH : 1), 2, F32, true>(f, ob_, lane, st_, px, py, pz, rb_, ka_, o2);
-                    wave_sum<2>(o2);
-                    if (lane == 0) { st_gran_f64(lg + 8 + 4 * k, tag, o2[0]); st_gran_f64(lg + 8 + 4 * k + 2, tag, o2[1]); }
-                }
-            };
-            if (type == 2 || type == 4) { ov_kind = type; ov_idx = idx; }
-            else if (type >= 5) { ov_evt = idx / 3; ov_cmp = idx - 3 * ov_evt; }
-            const double *hyp = cs.xall + go.hy + (size_t)m * go.nh;
-            const double *tc = cs.xall + go.tc + (size_t)m * cs.S, *ac = cs.xall + go.ac + (size_t)m * cs.S;
-            double lane_acc = 0.0;
-            if constexpr (NCH > 0) {
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) {                 // chain state: agent-scope loads
-                    const int j = lane + 64 * c;
-                    const bool valid = j < f.S;
-                    st.tc[c] = valid ? ld_agent(tc + j) : 0.0;
-                    st.ac[c] = valid ? ld_agent(ac + j) : 0.0;
-                    if (valid && ov_idx == j) { if (ov_kind == 2) st.tc[c] = ov_val; if (ov_kind == 4) st.ac[c] = ov_val; }
-                }
-                if constexpr (!F32) {
-                    // Events ev0, ev0 + 8W, ...: the first one's observation rows are resident (ob0); every further event's
-                    // rows and coordinates are requested BEFORE the current event is evaluated (software pipeline, one
-                    // event of look-ahead).  fp64: an event's arithmetic covers the next one's loads, the deeper form below
-                    // measured -1 % at 1 000 and 10 000 events x 64 stations, and two stations per lane do not fit the 256
-                    // registers of a wave with three buffers.
-                    const bool full_rows64 = f.S == 64 * NCH && f.use_time != 0 && f.use_amp != 0;      // (loads without selects or branches)
-                    ObsRegs<NCH, F32> ob_cur = ob0, ob_nxt = ob0;
-                    double cx = 0.0, cy = 0.0, cz = 0.0, nx = 0.0, ny = 0.0, nz = 0.0;
-                    if (ev0 < f.E) { cx = ld_agent(hyp + 3 * ev0); cy = ld_agent(hyp + 3 * ev0 + 1); cz = ld_agent(hyp + 3 * ev0 + 2); }
-                    for (int ev = ev0; ev < f.E; ev += NWV * W) {
-                        const int evn = ev + NWV * W;
-                        if (evn < f.E) {
-                            if (full_rows64) load_obs_regs_nobranch<NCH, F32, HTM_NT_WORKERS != 0, HTM_VRPS_WORKERS != 0, true>(ob_nxt, f, evn, lane);
-                            else load_obs_regs<NCH, F32, HTM_NT_WORKERS != 0, HTM_VRPS_WORKERS != 0>(ob_nxt, f, evn, lane);
-                            nx = ld_agent(hyp + 3 * evn); ny = ld_agent(hyp + 3 * evn + 1); nz = ld_agent(hyp + 3 * evn + 2);
-                        }
-                        double ex = cx, ey = cy, ez = cz;      // (the proposed component of a first-iteration order: a rare branch)
-                        if (__builtin_expect(ev == ov_evt, 0)) { ex = ov_cmp == 0 ? ov_val : cx; ey = ov_cmp == 1 ? ov_val : cy; ez = ov_cmp == 2 ? ov_val : cz; }
-                        const double px[1] = {ex};
-                        const double py[1] = {ey};
-                        const double pz[1] = {ez};
-                        double out[1];
-                        if (__builtin_expect(pipe_order && (ev == r_evt || ev == r_evt2), 0)) leftout(ob_cur, cx, cy, cz, ev, st, rbeta_j, katt_j);
-                        else {
-                            event_misfit<NCH, 1, F32, true>(f, ob_cur, lane, st, px, py, pz, rbeta_j, katt_j, out);
-                            // two-ahead order: the event of the step in between is left to the chain's own wave (it may be mid-commit)
-                            lane_acc += (ev == r_evt) ? 0.0 : out[0];
-                        }
-                        ob_cur = ob_nxt; cx = nx; cy = ny; cz = nz;
-                    }
-                } else {
-                    // Events ev0, ev0 + 8W, ...: the first one's observation rows are resident (ob0).  Three register buffers in
-                    // rotation: the rows and coordinates of the event TWO places ahead are requested before the current event is
-                    // evaluated, with a fixed number of loads per request (load_obs_regs_nobranch), so that at E >> 8W two
-                    // events' loads fly under the arithmetic of a third: the fp32 forward's arithmetic is too short to cover an
-                    // event's loads (configs[4] shape: 837 -> 902 k steps/s).  The last <= 4 events of a wave take the plain path.
-                    const int s8 = NWV * W;
-                    ObsRegs<NCH, F32> b0 = ob0, b1 = ob0, b2 = ob0;
-                    double x0 = 0.0, y0 = 0.0, z0 = 0.0, x1 = 0.0, y1 = 0.0, z1 = 0.0, x2 = 0.0, y2 = 0.0, z2 = 0.0;
-                    // (every lane has a station in both chunks and both data types are used: the loads need no selects)
-                    const bool full_rows = (f.S & 63) == 0 && f.S == 64 * NCH && f.use_time != 0 && f.use_amp != 0;
-                    auto fetch = [&](ObsRegs<NCH, F32> &b, double &x, double &y, double &z, int e) __attribute__((always_inline)) {
-                        if (full_rows) load_obs_regs_nobranch<NCH, F32, HTM_NT_WORKERS != 0, HTM_VRPS_WORKERS != 0, true>(b, f, e, lane);
-                        else load_obs_regs_nobranch<NCH, F32, HTM_NT_WORKERS != 0, HTM_VRPS_WORKERS != 0>(b, f, e, lane);
-                        x = ld_agent(hyp + 3 * e); y = ld_agent(hyp + 3 * e + 1); z = ld_agent(hyp + 3 * e + 2);
-                    };
-                    auto eval = [&](const ObsRegs<NCH, F32> &b, double x, double y, double z, int e) __attribute__((always_inline)) {
-                        // (the proposed hypocentre component of an order of the first iteration: a rare branch, not three selects per event)
-                        double ex = x, ey = y, ez = z;
-                        if (__builtin_expect(e == ov_evt, 0)) { ex = ov_cmp == 0 ? ov_val : x; ey = ov_cmp == 1 ? ov_val : y; ez = ov_cmp == 2 ? ov_val : z; }
-                        const double px[1] = {ex};
-                        const double py[1] = {ey};
-                        const double pz[1] = {ez};
-                        double out[1];
-                        if (__builtin_expect(pipe_order && (e == r_evt || e == r_evt2), 0)) leftout(b, x, y, z, e, st, rbeta_j, katt_j);
-                        else {
-                            event_misfit<NCH, 1, F32, true>(f, b, lane, st, px, py, pz, rbeta_j, katt_j, out);
-                            // two-ahead order: the event of the step in between is left to the chain's own wave (it may be mid-commit)
-                            lane_acc += (e == r_evt) ? 0.0 : out[0];
-                        }
-                    };
-                    int ev = ev0;
-                    if (ev < f.E) {
-                        x0 = ld_agent(hyp + 3 * ev); y0 = ld_agent(hyp + 3 * ev + 1); z0 = ld_agent(hyp + 3 * ev + 2);
-                        if (ev + s8 < f.E) fetch(b1, x1, y1, z1, ev + s8);
-                    }
-                    while (ev + 4 * s8 < f.E) {            // b0 <- event ev, b1 <- ev + s8 on entry and again after the trip
-                        fetch(b2, x2, y2, z2, ev + 2 * s8); eval(b0, x0, y0, z0, ev);
-                        fetch(b0, x0, y0, z0, ev + 3 * s8); eval(b1, x1, y1, z1, ev + s8);
-                        fetch(b1, x1, y1, z1, ev + 4 * s8); eval(b2, x2, y2, z2, ev + 2 * s8);
-                        ev += 3 * s8;
-                    }
-                    if (ev < f.E) { if (ev + 2 * s8 < f.E) fetch(b2, x2, y2, z2, ev + 2 * s8); eval(b0, x0, y0, z0, ev); }
-                    if (ev + s8 < f.E) { if (ev + 3 * s8 < f.E) fetch(b0, x0, y0, z0, ev + 3 * s8); eval(b1, x1, y1, z1, ev + s8); }
-                    if (ev + 2 * s8 < f.E) eval(b2, x2, y2, z2, ev + 2 * s8);
-                    if (ev + 3 * s8 < f.E) eval(b0, x0, y0, z0, ev + 3 * s8);
-                }
-            } else {
-                // generic station count: corrections are read through plain loads after an agent acquire
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                for (int ev = ev0; ev < f.E; ev += NWV * W) {
-                    const bool ov = ev == ov_evt;
-                    const double hx = ld_agent(hyp + 3 * ev), hy = ld_agent(hyp + 3 * ev + 1), hz = ld_agent(hyp + 3 * ev + 2);
-                    const double px[1] = {(ov && ov_cmp == 0) ? ov_val : hx};
-                    const double py[1] = {(ov && ov_cmp == 1) ? ov_val : hy};
-                    const double pz[1] = {(ov && ov_cmp == 2) ? ov_val : hz};
-                    double out[1];
-                    event_misfit_generic<1>(f, ev, lane, f.sx, f.sy, f.sz, tc, ac, ov_kind, ov_idx, ov_val, px, py, pz,
-                                            beta, q, out);
-                    lane_acc += out[0];
-                }
-            }
-            const double tot = wave_sum1(lane_acc);
-#ifdef HTM_STAMPS
-            if (wstamp) cs.stamps[22] += __builtin_amdgcn_s_memrealtime();
-#endif
-            if (lane == 0) s_red[wave] = tot;
-            __syncthreads();
-#ifdef HTM_STAMPS
-            if (wstamp) cs.stamps[23] += __builtin_amdgcn_s_memrealtime();
-#endif
-            if (tid == 0) {
-                double tot8 = ((s_red[0] + s_red[1]) + (s_red[2] + s_red[3])) + ((s_red[4] + s_red[5]) + (s_red[6] + s_red[7]));
-                if constexpr (NWV == 12) tot8 = tot8 + ((s_red[8] + s_red[9]) + (s_red[10] + s_red[11]));
-                st_gran_f64(cs.pgran + ((size_t)m * cs.n_wg + w) * cs.pgran_stride, tag, tot8);
-            }
-            __syncthreads();
-        }
-    }
 }
 
 }  // namespace htm

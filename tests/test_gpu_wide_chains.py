@@ -1,5 +1,5 @@
 """GPU parity of 33..64 chains on a rank (HTM_MAX_CHAINS): the loop with workgroup barriers in its wide instantiations
-(k_mcmc_wide / k_step_wide, csrc/htm_step.hpp at kMaxWideChains).  Criteria as in tests/test_gpu_chains.py: the oracle step by
+(k_mcmc_wide, csrc/htm_mcmc.hpp, and k_step_wide, csrc/htm_step.hpp: step_body at kMaxWideChains).  Criteria as in tests/test_gpu_chains.py: the oracle step by
 step, bit-equality between launch shapes of the same job."""
 import ctypes as C
 import os
