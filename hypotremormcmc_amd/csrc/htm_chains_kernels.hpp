@@ -1,7 +1,7 @@
 // htm_chains_kernels.hpp -- the small non-template kernels around the chain loops: the producers of the random stream
 // (types and device helpers: htm_stream.hpp), the set-up of a launch with several master workgroups (htm_flow.hpp: MbShared and
 // its MW_* words are defined there) and the probe of the peer-mapped inboxes (htm_handoff.hpp).  A non-template kernel defined in a header gives every unit that includes it
-// a host stub and a copy of the device code of its own, so exactly ONE unit includes this file: htm_hip.hip.
+// a host stub and a copy of the device code of its own, so exactly ONE unit includes this file: htm_chains_run.hip.
 #pragma once
 #include "htm_flow.hpp"
 

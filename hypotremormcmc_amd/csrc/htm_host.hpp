@@ -3,8 +3,16 @@
 //
 //   htm_forward.hip        htm_forward_*, htm_device_*, the last-error string, the self-tests and htm_rng_jump; htm_forward_locate
 //                          (the location posteriors on a grid, kernels: htm_locate.hpp)
-//   htm_hip.hip            htm_chains_*, htm_comm_*: sets a chain set up and launches its loops; no k_mcmc is instantiated there
-//   htm_plan.hpp           the launch plan of a chain set: which loop each mode takes (loop_for) and the launch shape, worked out
+//   htm_chains_setup.hip   the chain sets' part of the C ABI, four units, none of which instantiates a k_mcmc.  Set-up: the plan
+//                          (htm_chains_plan, htm_chains_get_plan), htm_chains_create / _destroy / _share_gpu, the inbox of
+//                          the in-kernel exchange.  The only unit that takes sizes from the loops (htm_flow.hpp, htm_pipe.hpp,
+//                          htm_mcmc.hpp); emits no kernel
+//   htm_chains_run.hip     the kernel table's lookups, the launches, the random-stream producer, the run drivers, the
+//                          lock-step calls and the exchange's connection; the one unit with htm_chains_kernels.hpp
+//   htm_chains_state.hip   checkpoints and everything that reads a chain set: getters, records, step log, statistics
+//   htm_comm.hip           RCCL bound at run time: htm_comm_*, htm_chains_run_lockstep_comm.  These two see the types of
+//                          this header and nothing of the hand-off, the workers or the loops
+//   htm_plan.hpp          the launch plan of a chain set: which loop each mode takes (loop_for) and the launch shape, worked out
 //                          by plain functions without a device; kept in htm_chains::plan.  Ask for the plan of a shape with
 //                          htm_chains_plan (no GPU needed), for the plan of a chain set with htm_chains_get_plan
 //   htm_loop_*.hip         one unit per family of chain-master loops: nothing but its rows of the kernel table below
@@ -73,6 +81,15 @@ int dev_upload(std::vector<void *> &pool, T **p, const T *src, size_t n)
     int rc = dev_alloc(pool, p, n);
     if (rc) return rc;
     if (n) HIPCHK(hipMemcpy(*p, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return HTM_OK;
+}
+
+template <typename T>
+int dev_zeros(std::vector<void *> &pool, T **p, size_t n)
+{
+    int rc = dev_alloc(pool, p, n);
+    if (rc) return rc;
+    HIPCHK(hipMemset(*p, 0, n * sizeof(T)));
     return HTM_OK;
 }
 
@@ -162,9 +179,51 @@ int launch_full(htm_forward *h, const FullJob &jb, int gy);
 int full_batch_dev(htm_forward *h, int n_models, const double *d_hypo, const double *d_tc, const double *d_vs,
                    const double *d_ac, const double *d_qs, double *d_L);
 int ensure_obs_pack(htm_forward *h);
-// htm_hip.hip
+// htm_chains_run.hip
 int launch_mcmc(htm_chains *hc, int mode, int target, const double *gathered);
 int launch_step(htm_chains *hc, int mode, int target, const double *gathered);
+int no_kernel(const htm_chains *hc, const char *what, int mk);
+int stream_produce(htm_chains *hc, long long n);
+int bounded_stream_sync(htm_chains *hc, const char *what);
+// htm_chains_setup.hip
+int xchg_alloc(htm_chains *hc);
+
+// ---- a chain set's layouts, each written down once ----------------------------------------------------------------
+// The rank's parameter vector (ChainsDev::xall and the per-field arrays beside it): five groups in the order of the
+// proposal types, [vs | t_corr | qs | a_corr | hypo], group k holding n_chains rows of nx elements from `off` on.  (The
+// kernels work the same offsets out for themselves: group_offsets in htm_handoff.hpp, chain_pass in htm_step.hpp.)
+struct ParamLayout {
+    struct Group { size_t off, nx; } g[5];
+    size_t total;
+};
+inline ParamLayout param_layout(size_t n_chains, size_t S, size_t E)
+{
+    ParamLayout l{};
+    const size_t nx[5] = {1, S, 1, S, 3 * E};
+    for (int k = 0; k < 5; ++k) { l.g[k] = {l.total, nx[k]}; l.total += n_chains * nx[k]; }
+    return l;
+}
+
+// The hand-off regions: tagged words that the master, the workers and the peers leave for each other.  Set-up allocates
+// each zeroed (`words`); a checkpoint load zeroes them again, all but the last `kept` words (diag[24], [25] are counters
+// that survive a load).  The inbox exists once the exchange has been asked for (xchg_alloc, which sizes it).
+enum { kRegSlots, kRegLoGran, kRegPgran, kRegDiag, kRegInbox, kRegions };
+struct HandoffRegion { unsigned long long **p; size_t words, kept; };
+inline std::array<HandoffRegion, kRegions> handoff_regions(htm_chains *hc)
+{
+    ChainsDev &d = hc->dev;
+    return {{{&d.slots, (size_t)d.slot_rep * d.slot_stride, 0},
+             {&d.lo_gran, (size_t)d.n_chains * 16, 0},
+             {&d.pgran, (size_t)d.n_chains * 256 * d.pgran_stride, 0},      // (<= 256 workers whatever the launch shape)
+             {&d.diag, 32, 8},
+             {&hc->d_inbox, hc->inbox_bytes / sizeof(unsigned long long), 0}}};
+}
+
+inline void clear_host_records(htm_chains *hc)
+{
+    hc->lik_iter.clear(); hc->lik_chain.clear(); hc->lik_val.clear();
+    hc->smp_iter.clear(); hc->smp_chain.clear(); hc->smp_data.clear();
+}
 
 // ---- the kernel table ---------------------------------------------------------------------------------------------
 // Every instantiation of a chain-master kernel is written down once, as a row of the loop unit that compiles it
@@ -189,7 +248,7 @@ struct LoopRows { const LoopRow *rows; size_t n; };
 const LoopKernel *mcmc_kernel(int nch, bool fp32, int mk, bool wide);      // nullptr: not built
 const LoopKernel *step_kernel(int nch, bool fp32, bool wide);
 
-// one per loop unit, all searched by the two lookups above (htm_hip.hip)
+// one per loop unit, all searched by the two lookups above (htm_chains_run.hip)
 LoopRows loop_rows_free();         // MK 3, 8: the free-running master of a single rank, generic and specialised
 LoopRows loop_rows_lock();         // MK 4, 7: the free-running master in lock-step, and with several master workgroups
 LoopRows loop_rows_barrier();      // MK 0, 1, 2 and k_step: the loop with barriers

@@ -13,8 +13,12 @@
 
 namespace htm {
 
-// (the values of Mode, htm_device.hpp, that launch a chain-master loop; htm_hip.hip asserts that they agree)
+// (the values of Mode, htm_device.hpp, that launch a chain-master loop; htm_chains_setup.hip asserts that they agree)
 constexpr int kPlanModeRun = 0, kPlanModeAdvance = 1, kPlanModeLockrun = 4;
+
+// doubles in a rank's swap record: {the pair, its swap draw, the iteration | temperature and log-likelihood of every chain}
+// (the device headers write the same length out: RW in htm_handoff.hpp)
+constexpr size_t swap_words(int n_chains) { return 4 + 2 * (size_t)n_chains; }
 
 // ---- the environment switches of htm_chains_create, read once ------------------------------------------------------------------
 struct Knobs {
@@ -89,7 +93,7 @@ struct PlanJob {
     bool fp32 = false, use_time = true, use_amp = true;
 };
 
-// what the rules need from the device headers (filled in by htm_hip.hip, plan_sizes)
+// what the rules need from the device headers (filled in by htm_chains_setup.hip, plan_sizes)
 struct PlanSizes {
     size_t flow_shared = 0, wide_shared = 0, pipe_shared = 0;      // sizeof FlowShared, StepSharedT<kMaxWideChains>, PipeShared
     size_t pipe_ring_bytes = 0;                                    // pipe_ring_bytes(n_chains)
@@ -241,7 +245,7 @@ inline Plan plan_phase_a(const PlanJob &j, const Knobs &kn, const PlanSizes &sz)
                         p.mirror_n == (int)mir;      // (the mirror is part of every loop's LDS layout: one size for all)
     lp.pipe = usable && j.n_procs == 1 && kn.pipe;
     lp.pipe_lock = usable && kn.pipe_lock &&
-                   (size_t)j.n_procs * (4 + 2 * (size_t)nc) <= (size_t)sz.gath_stage;      // (MODE_LOCKRUN: any number of ranks)
+                   (size_t)j.n_procs * swap_words(nc) <= (size_t)sz.gath_stage;      // (MODE_LOCKRUN: any number of ranks)
     p.pipe_asked = lp.persist && (lp.pipe || lp.pipe_lock);
     return p;
 }

@@ -1,5 +1,5 @@
 // htm_steps_host.hpp -- the host idioms that the entry points of htm_steps.hip share, and htm_forward_locate (htm_forward.hip)
-// with them.  Internal: the handles of htm_forward.hip and htm_hip.hip keep their own pools (dev_alloc / dev_upload of htm_host.hpp).
+// with them.  Internal: the handles of htm_forward.hip and htm_chains_setup.hip keep their own pools (dev_alloc / dev_upload of htm_host.hpp).
 // StreamBuf is the workspace of a *_dev form, DevPool the device arrays of a host-pointer form; kMaxWorkItems, env_mib, Int<N>.
 #pragma once
 #include "htm_host.hpp"

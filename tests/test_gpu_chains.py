@@ -308,6 +308,54 @@ def test_checkpoint_resume_continues_the_run_and_checks_shapes():
         c[0].restore(blob[:64])
 
 
+def test_checkpoint_written_before_the_host_units_were_split_restores_field_by_field():
+    """tests/golden/ckpt_v2_2c_3s_2e.bin was written on an MI355X by the library as it was before htm_hip.hip became four units
+    (commit 8714a2b): ChainSet.checkpoint() after run(48) of the chain set this test builds -- 2 chains x 3 stations x 2 events,
+    the smallest shape at which every group of the parameter vector starts somewhere else and no group is as long as its
+    neighbour.  The blob is decoded here, by the layout CkptHeader documents
+    (csrc/htm_chains_state.hip) and the group order [vs | t_corr | qs | a_corr | hypo], not by the library: a restore must put
+    every field where the getters read it, write the same bytes back, and the chains must run on."""
+    import struct
+
+    from hypotremormcmc_amd import synth
+
+    nc, S, E = 2, 3, 2
+    with open(os.path.join(os.path.dirname(__file__), "golden", "ckpt_v2_2c_3s_2e.bin"), "rb") as f:
+        blob = f.read()
+    assert len(blob) == 456      # an 80-byte header, 32 doubles, 30 int32
+    head = struct.unpack("<2I6i4I2q2Q", blob[:80])
+    magic, version, h_nc, h_S, h_E, n_procs, rank, iter_done = head[:8]
+    rng, total = head[8:12], head[15]
+    assert (magic, version, h_nc, h_S, h_E, n_procs, rank) == (0x48544D43, 2, nc, S, E, 1, 0)
+    assert total == 2 * nc + 2 * nc * S + 3 * E * nc == 28 and iter_done >= 24
+    x = np.frombuffer(blob, "<f8", total + 2 * nc, 80)
+    cnt = np.frombuffer(blob, "<i4", 15 * nc, 80 + 8 * (total + 2 * nc))
+    group, off = {}, 0
+    for name, nx in (("vs", 1), ("t_corr", S), ("qs", 1), ("a_corr", S), ("hypo", 3 * E)):
+        group[name] = x[off:off + nc * nx].reshape(nc, nx)
+        off += nc * nx
+    temp, loglik = x[total:total + nc], x[total + nc:]
+    n_propose, n_accept = cnt[:7 * nc].reshape(nc, 7), cnt[7 * nc:14 * nc].reshape(nc, 7)
+    # (the counters count the steps of a chain at temperature 1, cls_mcmc.f90:186: they were really read)
+    assert n_propose.sum() == iter_done * np.count_nonzero(temp == 1.0) > 0
+
+    data = synth.make_synthetic(E, S, 7)
+    params = dict(synth.DEFAULT_PARAMS, n_procs=1, n_chains=nc, n_iter=100, n_burn=10, n_interval=5)
+    _, sets = _build_world(data, params)
+    cs = sets[0]
+    cs.restore(blob)
+    assert cs.iterations_done == iter_done and cs.rng_state() == tuple(rng)
+    for c in range(nc):
+        s = cs.state(c)
+        assert np.array_equal(s.hypo, group["hypo"][c]) and np.array_equal(s.t_corr, group["t_corr"][c])
+        assert np.array_equal(s.a_corr, group["a_corr"][c]) and s.vs == group["vs"][c, 0] and s.qs == group["qs"][c, 0]
+        assert s.temp == temp[c] and s.log_likelihood == loglik[c]
+        assert np.array_equal(s.n_propose, n_propose[c]) and np.array_equal(s.n_accept, n_accept[c])
+    assert cs.checkpoint() == blob
+    cs.run(5)
+    assert cs.iterations_done == iter_done + 5
+
+
 def test_c5_size_16_chains_against_oracle():
     """BASELINE configs[4] per-GPU shape in fp64: 10 000 events x 128 stations (2 stations per lane), 16 chains
     (two rounds of chain waves), every recorded log-likelihood and the RNG consumption against the oracle.

@@ -95,7 +95,7 @@ def test_two_master_workgroups_checkpoint_and_fp32(monkeypatch):
 
 def test_the_configuration_that_used_to_differ(monkeypatch):
     """100 x 64 x 16, depth steps of 20 (tools/mb_repro.py): a chain late from a full evaluation adopts an anchor up to three
-    iterations behind the wave that keeps its workgroup's stream window -- the window must still hold it (csrc/htm_hip.hip:
+    iterations behind the wave that keeps its workgroup's stream window -- the window must still hold it (csrc/htm_plan.hpp:
     mb_need).  With a 512-position ring one run in seven took ONE step of chain 2 from a wrong stream position (iterations
     5171, 5636, 6596, 7283, 8537, ...); every step of several runs against the oracle's step log."""
     from oracle import oracle
