@@ -77,19 +77,14 @@ int launch_full(htm_forward *h, const FullJob &jb, int gy)
 {
     dim3 grid(h->n_wg, gy), block(256);
     const size_t smem = 0;
-    if (h->dev.fp32 && (h->nch == 1 || h->nch == 2 || h->nch == 4)) {        // fp32 forward (htm_forward_set_precision)
+    if (h->dev.fp32) {        // fp32 forward: htm_forward_set_precision allows it for one or two stations per lane only
+        if (h->nch != 1 && h->nch != 2) return fail(HTM_ESTATE, "fp32 forward on a handle with %d stations", h->S);
         if (jb.desc) {
-            switch (h->nch) {
-            case 1: hipLaunchKernelGGL((k_full<1, false, true>), grid, block, smem, h->stream, h->dev, jb); break;
-            case 2: hipLaunchKernelGGL((k_full<2, false, true>), grid, block, smem, h->stream, h->dev, jb); break;
-            default: hipLaunchKernelGGL((k_full<4, false, true>), grid, block, smem, h->stream, h->dev, jb); break;
-            }
+            if (h->nch == 1) hipLaunchKernelGGL((k_full<1, false, true>), grid, block, smem, h->stream, h->dev, jb);
+            else hipLaunchKernelGGL((k_full<2, false, true>), grid, block, smem, h->stream, h->dev, jb);
         } else {
-            switch (h->nch) {
-            case 1: hipLaunchKernelGGL((k_full<1, true, true>), grid, block, smem, h->stream, h->dev, jb); break;
-            case 2: hipLaunchKernelGGL((k_full<2, true, true>), grid, block, smem, h->stream, h->dev, jb); break;
-            default: hipLaunchKernelGGL((k_full<4, true, true>), grid, block, smem, h->stream, h->dev, jb); break;
-            }
+            if (h->nch == 1) hipLaunchKernelGGL((k_full<1, true, true>), grid, block, smem, h->stream, h->dev, jb);
+            else hipLaunchKernelGGL((k_full<2, true, true>), grid, block, smem, h->stream, h->dev, jb);
         }
     } else if (jb.desc) {
         switch (h->nch) {

@@ -62,8 +62,11 @@ class Forward:
             pass
 
     def set_precision(self, precision: str):
-        """"fp32": single-precision forward model with fp64 sums and accept (BASELINE configs[4]; statistical
-        tolerance, no reference counterpart); "fp64": the reference's arithmetic.  Before creating chains."""
+        """"fp32": single-precision forward model with fp64 sums and accept (BASELINE configs[4]); "fp64": the reference's
+        arithmetic.  The reference has no such mode; the library's is pinned term by term against a numpy.longdouble
+        restatement of it (tests/fp32_restatement.py, tests/test_gpu_fp32_terms.py) and statistically against the fp64 run
+        (tests/test_gpu_fp32.py).  For n_sta <= 128: more stations raise HtmError and leave the handle in fp64.  Before
+        creating chains."""
         fp32 = str(precision).lower() in ("fp32", "f32", "single")
         check(self._lib.htm_forward_set_precision(self.handle, int(fp32)))
         self.forward_precision = "fp32" if fp32 else "fp64"

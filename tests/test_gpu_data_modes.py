@@ -246,6 +246,29 @@ def test_every_other_single_rank_loop(loop, mode, monkeypatch):
     _single_rank(monkeypatch, E, S, nc, mode, 3, 400 if nc > 8 else 500, env=env, loop=code, **kw)
 
 
+FP32_RAGGED = {      # (events x stations x chains, switches, asserted loop id): the fp32 instantiation of each loop at a ragged row
+    "generic master, 7 x 5": (7, 5, 3, {}, 3),                                          # k_mcmc<1, true, 3>, fewer events than waves
+    "generic master, 33 x 70": (33, 70, 5, {}, 3),                                      # k_mcmc<2, true, 3>, ragged second chunk
+    "generic master, 33 x 127": (33, 127, 4, {}, 3),                                    # ... one station short of full rows
+    "barrier loop": (33, 70, 5, {"HTM_FLOW": "0"}, 0),                                  # k_mcmc<2, true, 0>
+    "two-kernel path": (33, 70, 3, {"HTM_PERSIST": "0"}, -1),                           # k_step<2, true> + k_full<2, false, true>
+    "two master workgroups": (33, 70, 12, {"HTM_MB": "1"}, 7),                          # k_mcmc<2, true, 7>
+    "wide loop": (33, 70, 33, {}, 0),                                                   # k_mcmc_wide<2, true, 0>
+}
+
+
+@pytest.mark.parametrize("mode", ["M", "A"])
+@pytest.mark.parametrize("loop", list(FP32_RAGGED))
+def test_fp32_forward_through_every_loop_at_ragged_rows(loop, mode, monkeypatch):
+    """the fp32 forward met a ragged row in one loop only (the free-running master with one worker block, above); here in each
+    loop, with missing entries and with amplitudes only.  The criterion is the one of every chain test: decisions, counters, RNG
+    state and final states equal to the fp64 oracle, the records within T1 (RTOL_FP32) -- these are burn-in jobs with 6 km depth
+    steps, where the judged differences are large against the fp32 error (tests/test_gpu_wide_chains.py
+    test_wide_fp32_forward_checkpoint_and_decisions relies on the same)."""
+    E, S, nc, env, code = FP32_RAGGED[loop]
+    _single_rank(monkeypatch, E, S, nc, mode, 8, 400 if nc > 8 else 500, env=env, loop=code, fp32=True)
+
+
 @pytest.mark.parametrize("mode", ["A", "M"])
 def test_lockstep_ranks(mode, monkeypatch):
     """two ranks of four chains, one lock-step iteration per launch (k_mcmc<1, false, 1>), records exchanged by device copies"""

@@ -1,8 +1,9 @@
 """GPU: the fp32-forward / fp64-accept mode (BASELINE configs[4]: 10 000 events x 128 stations, fp32 forward with
 fp64 accept; htm_forward_set_precision).
 
-The reference is fp64 throughout (src/cls_forward.f90), so this mode has no bit-level oracle: its tolerance is
-STATISTICAL and stated here.  What is single precision: the synthetic travel time and amplitude of a
+The reference is fp64 throughout (src/cls_forward.f90), so this mode has no bit-level oracle.  Its arithmetic is pinned term by
+term against a numpy.longdouble restatement of the mode itself (T7 - T9 below, tests/fp32_restatement.py); what the mode costs a
+sampler is a STATISTICAL tolerance, stated here (T1 - T6).  What is single precision: the synthetic travel time and amplitude of a
 station-event pair (distance, sqrt, division, log; src/cls_forward.f90:115-118, :201-204) and the stored
 observations.  What stays fp64: coordinate differences, the weighted demean sums (:125-132), residuals, the misfit
 sum (:281-299), the Metropolis decision (src/cls_mcmc.f90:194-199) -- checked against the fp64 oracle:
@@ -23,6 +24,18 @@ sum (:281-299), the Metropolis decision (src/cls_mcmc.f90:194-199) -- checked ag
       the device's step-6 statistics (htm_quantiles).  The fp32 run differs from the fp64 run by no more than two fp64 runs
       with different seeds differ from each other (in units of each parameter's posterior width): rms <= 1.3 x + 0.05 -- both
       with the first run's seeds (common random numbers: the runs part only where a decision flips) and with the other seeds.
+  T7  term level (tests/test_gpu_fp32_terms.py): full, stacked and one-event values against the mode's definition in
+      numpy.longdouble on the inputs as the library stores them, |L - L_ref| <= ULPS32 * 2^-24 * D32 + 16 * 2^-53 * M, D32 the
+      first-order sensitivity of L to one rounding of every synthetic's terms, M the magnitudes of L's terms; ULPS32 = 4 measured on
+      the CPU from the documented arithmetic alone (tests/test_fp32_restatement.py), where coordinates rounded to float before the
+      difference, a sqrt 4 ulp high and a neighbour's correction exceed it -- T1 is relative to |L|, which is not what the error
+      scales with, and passes the first of them; pair probes put an event's weight on two stations so that L resolves single
+      synthetics;
+  T8  exact translation: coordinates on a 2^-16 km grid shifted by 2^12 and 2^20 km give the same bits, in fp32 and in fp64
+      (the coordinate differences stay fp64);
+  T9  ragged shapes: every n_sta <= 128 chunk shape x 1, 5, 37 events, 1001 x 64, 4099 x 70 and the single-type modes with missing
+      entries at T7 and T1, the refusal above 128 stations and the switch fp32 -> fp64 -> fp32 (same file); every chain loop with
+      the fp32 forward at ragged rows against the oracle's decisions (tests/test_gpu_data_modes.py).
 The measured values are written to gpurun_out/fp32_tolerances.txt."""
 import os
 
