@@ -86,6 +86,7 @@ __device__ __forceinline__ unsigned long long rl_u64(unsigned long long v, int l
 // barriers here, not waits for outstanding memory operations.
 __device__ __forceinline__ int lds_ld(const int *p) { const int v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); asm volatile("" ::: "memory"); return v; }
 __device__ __forceinline__ unsigned long long lds_ld(const unsigned long long *p) { const unsigned long long v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); asm volatile("" ::: "memory"); return v; }
+__device__ __forceinline__ double lds_ld(const double *p) { const double v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); asm volatile("" ::: "memory"); return v; }
 __device__ __forceinline__ void lds_st(int *p, int v) { asm volatile("" ::: "memory"); __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void lds_st(unsigned long long *p, unsigned long long v) { asm volatile("" ::: "memory"); __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
@@ -193,6 +194,21 @@ struct FlowTop {
     double L;
     double rbeta, katt;           // the chain's 1 / vs and pi f / (qs vs) (FlowShared)
     int n_lik, n_smp, avail;      // (the specialised master) what chain 0's wave decides the launch's end from: three more round trips there
+    int i0, iter_target;          // (the specialised master) FlowShared::i0 and the launch's target: the step's key, its look-ahead and its orders
+};
+
+// What the specialised master's step reads from LDS between its evaluation and its decision, requested in ONE batch with every
+// poll of its turn, in this order: the other chains' checks and the epoch (the turn); this chain's temperature of the iteration
+// before; the plan of that iteration's swap; with lanes as chains, every chain's committed key and its (T, 1/T, L) after that
+// iteration.  A wave's LDS operations execute in issue order and the last chain's wave stores the plan before its check, a
+// committing wave its record before `done`: a round whose checks let the turn pass holds the plan, and if its `done` of the
+// partner shows the partner's commit, the partner's record.  A round that does not pass is dropped with its poll.
+struct FlowTurn {
+    double T, rT;                 // T4 / rT4[ppar][c]
+    int i1, i2;                   // sw_i1 / sw_i2[ppar]
+    double r, logr;               // sw_r / sw_logr[ppar]
+    int dn;                       // done[lane & 7]
+    double Tl, rTl, Ll;           // T4 / rT4 / L4[ppar][lane & 7]
 };
 
 // What a job fixes, asked through a traits type: flow_step, flow_body and the helpers they call put every such question to
@@ -701,7 +717,9 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
     }
     const double r = ok ? r_ring : 0.0, logr = ok ? logr_ring : 0.0;
     const int cnt = dec_w - 1 + ok;                             // the judge draw happens only if prior_ok
-    const int key = (iter - sh.i0) * nc_ + c;
+    int key;
+    if constexpr (FX) key = (iter - tp.i0) * nc_ + c;      // (i0 came with the batch at the loop top: no wait here)
+    else key = (iter - sh.i0) * nc_ + c;
     // ---- the step has passed (or failed) its prior check: the later steps may go ahead on it
     if (c == nc_ - 1) {                                         // where this iteration's swap starts, and what it draws there
         const int E = p + cnt, k4 = iter & 3;
@@ -766,7 +784,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
             // next step, of its step after that, and the end of the iteration after next -- issued here, used behind the evaluation
             // (the hop tables reach kHops steps: with more chains than that -- several master workgroups -- the positions are looked
             // up at the top of the next step instead)
-            if (NW >= nc_ && W.rpos1 >= 0 && W.B2 >= 0 && c >= W.rc1 && iter + 1 <= sh.c.iter_target && (TR::mirror || rg.mir_n > 0)) {
+            if (NW >= nc_ && W.rpos1 >= 0 && W.B2 >= 0 && c >= W.rc1 && iter + 1 <= (FX ? tp.iter_target : sh.c.iter_target) && (TR::mirror || rg.mir_n > 0)) {
                 la = 1; la_epoch = W.epoch;
                 const int n1 = c - W.rc1;
                 // (one workgroup: a wave has one chain only with <= 8 = kHops chains, the tables reach in one entry)
@@ -916,12 +934,27 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
 
     // ---- the step's turn: every step before it in stream order has passed its check in this epoch (or lies before the
     // ---- epoch's anchor: checked earlier, final).  Lanes <-> chains.
+    [[maybe_unused]] FlowTurn tb;
     {
-        const int key_i = (iter - sh.i0) * nc_, key_m = key_i - nc_;
+        int key_i;
+        if constexpr (FX) key_i = key - c;
+        else key_i = (iter - sh.i0) * nc_;
+        const int key_m = key_i - nc_;
         const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
         for (unsigned spin = 0;; ++spin) {
             unsigned long long pv;
             int e;
+            if constexpr (FX) {
+                // (FlowTurn: one batch, one wait.  At most eight chains: lane & 7 stays inside every array, and a lane that is no
+                // chain reads words nobody looks at)
+                const int pp = (iter - 1) & 3, ln = lane & 7;
+                pv = lds_ld(&sh.prog[ln]);
+                e = lds_ld(&sh.epoch);
+                tb.T = lds_ld(&sh.T4[pp][c]); tb.rT = lds_ld(&sh.rT4[pp][c]);
+                tb.i1 = lds_ld(&sh.sw_i1[pp]); tb.i2 = lds_ld(&sh.sw_i2[pp]); tb.r = lds_ld(&sh.sw_r[pp]); tb.logr = lds_ld(&sh.sw_logr[pp]);
+                tb.dn = lds_ld(&sh.done[ln]);
+                tb.Tl = lds_ld(&sh.T4[pp][ln]); tb.rTl = lds_ld(&sh.rT4[pp][ln]); tb.Ll = lds_ld(&sh.L4[pp][ln]);
+            } else
             if constexpr (MB) {
                 // the chains of this workgroup: LDS, as with one workgroup; the others' and the shared words: the look at memory
                 // (the first round uses the one issued before the evaluation; a constant lag between the workgroups is all the
@@ -982,7 +1015,43 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
     // ---- the temperature of this iteration: the swap of the iteration before (cls_parallel.f90:121-136, :285-302), decided
     // ---- here by the waves of the two chains it concerns -- each evaluates the same expression on the same values
     const int par = iter & 3, ppar = (iter - 1) & 3;
-    double T = sh.T4[par][c], rT = sh.rT4[par][c];        // (first iteration of a launch: written by the prologue)
+    double T = 0.0, rT = 0.0;
+    if constexpr (!FX) { T = sh.T4[par][c]; rT = sh.rT4[par][c]; }        // (first iteration of a launch: written by the prologue)
+    if constexpr (FX) {
+        // the specialised master: everything from the batch of the round that let the turn pass (FlowTurn) -- no further wait
+        // unless the partner has not committed yet
+        const int key_p = key - c - nc_;      // key of chain 0's step of the iteration before
+        if (__builtin_expect(key_p > 0, 1)) {      // (iter - 1 > i0: not the first iteration of the launch)
+            T = tb.T; rT = tb.rT;
+            if (nc_ > 1) {
+                const int i1 = uni(tb.i1), i2 = uni(tb.i2);
+                if (c == i1 || c == i2) {
+                    const int o2 = c == i1 ? i2 : i1;
+                    const int want = key_p + o2;
+                    const double sr = tb.r, slr = tb.logr;
+                    double T1, T2, rT1, rT2, L1, L2;
+                    if (__builtin_expect(__builtin_amdgcn_readlane(tb.dn, o2) >= want, 1)) {
+                        // (the very LDS words the generic master reads, this chain's own among them: the bits cannot move)
+                        T1 = rl_f64(tb.Tl, i1); T2 = rl_f64(tb.Tl, i2); rT1 = rl_f64(tb.rTl, i1); rT2 = rl_f64(tb.rTl, i2);
+                        L1 = rl_f64(tb.Ll, i1); L2 = rl_f64(tb.Ll, i2);
+                    } else {
+                        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+                        for (unsigned spin = 0; lds_ld(&sh.done[o2]) < want; ++spin) {
+                            if ((spin & 15u) == 15u) {
+                                if (sh.c.err != 0) return kFlowAbort;
+                                if (__builtin_amdgcn_s_memrealtime() - t0 > 500000000ull) { if (lane == 0) sh.c.err = -12; return kFlowAbort; }
+                            }
+                            __builtin_amdgcn_s_sleep(1);
+                        }
+                        T1 = sh.T4[ppar][i1]; T2 = sh.T4[ppar][i2]; rT1 = sh.rT4[ppar][i1]; rT2 = sh.rT4[ppar][i2];
+                        L1 = sh.L4[ppar][i1]; L2 = sh.L4[ppar][i2];
+                    }
+                    const double del_s = (L2 - L1) * (rT1 - rT2);      // :292 (1/T formed once per temperature)
+                    if (sr >= kEps && slr <= del_s) { T = c == i1 ? T2 : T1; rT = c == i1 ? rT2 : rT1; }      // :131-136
+                }
+            }
+        } else { T = sh.T4[par][c]; rT = sh.rT4[par][c]; }      // (first iteration of a launch: written by the prologue; no swap)
+    } else
     if constexpr (LOCK) {
         // a lock-step rank (see flow_post_chain): the stop words of iteration iter - 2, the pair of iteration iter - 1, the bet on
         // judge_swap's draw; then -- only if this chain is one of the pair -- the partner's (T, L)
@@ -1296,7 +1365,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
             const int d2x = uni(d2v.x);
             may_order = (d1.x >= 1 && d1.x <= 4) || (HTM_ALLOW2 && NCH > 0 && d2x >= 1 && d2x <= 4);
         }
-        order_open = may_order && sh.ob_pos[c] == -1 && iter + 1 <= sh.c.iter_target;
+        order_open = may_order && sh.ob_pos[c] == -1 && iter + 1 <= (FX ? tp.iter_target : sh.c.iter_target);
     }
     else order_open = (TR::mirror || rg.mir_n > 0) && sh.ob_pos[c] == -1 && iter + 1 <= sh.c.iter_target;
     if (order_open) {
@@ -1308,7 +1377,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
             job1 = d1.x >= 1 && d1.x <= 4;
             mode = job1 ? 1 : 0; pj = p1; jt = d1.x; ji = d1.y;
             const int d2x = uni(d2v.x);
-            if (HTM_ALLOW2 && NCH > 0 && !job1 && iter + 2 <= sh.c.iter_target && d2x >= 1 && d2x <= 4) { mode = 2; pj = la_p2; jt = d2x; ji = uni(d2v.y); }
+            if (HTM_ALLOW2 && NCH > 0 && !job1 && iter + 2 <= (FX ? tp.iter_target : sh.c.iter_target) && d2x >= 1 && d2x <= 4) { mode = 2; pj = la_p2; jt = d2x; ji = uni(d2v.y); }
         } else {
             // this chain's next step is its step of the next iteration (this wave's other chains of this iteration come first)
             p1 = (W.rpos1 >= 0 && c >= W.rc1) ? hop_ahead(rg, W.rpos1, c - W.rc1) : -1;
@@ -1317,7 +1386,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
             d1.x = d1r.x; d1.y = d1r.y; d1.z = d1r.z;
             job1 = w1 && d1.x >= 1 && d1.x <= 4;
             mode = job1 ? 1 : 0; pj = p1; jt = d1.x; ji = d1.y;
-            if (HTM_ALLOW2 && NCH > 0 && w1 && !job1 && iter + 2 <= sh.c.iter_target && W.B2 >= 0) {
+            if (HTM_ALLOW2 && NCH > 0 && w1 && !job1 && iter + 2 <= (FX ? tp.iter_target : sh.c.iter_target) && W.B2 >= 0) {
                 const int p2 = hop_ahead(rg, W.B2, c);
                 if (p2 < lim) {
                     const i32x4 d2 = reinterpret_cast<const i32x4 *>(rg.dec)[p2 & M];
@@ -1530,6 +1599,7 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
             tp.L = sh.L[c];
             tp.rbeta = sh.rbeta[c]; tp.katt = sh.katt[c];
             if constexpr (flow_fixed_v<TR>) { tp.n_lik = lds_ld(&sh.c.n_lik); tp.n_smp = lds_ld(&sh.c.n_smp); tp.avail = lds_ld(&sh.avail); }
+            if constexpr (flow_fixed_v<TR>) { tp.i0 = lds_ld(&sh.i0); tp.iter_target = lds_ld(&sh.c.iter_target); }      // (launch constants: no wait of their own in the step)
             asm volatile("" ::: "memory");
         }
         {

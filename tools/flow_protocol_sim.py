@@ -98,8 +98,13 @@ class Shared:
     pass
 
 
-def wave(sh, st, w, NW, nc, i0, target, rnd, trace):
-    """one wave of the master: chains w, w + NW, ...; a generator that yields between shared-memory accesses"""
+def wave(sh, st, w, NW, nc, i0, target, rnd, trace, batched=False):
+    """one wave of the master: chains w, w + NW, ...; a generator that yields between shared-memory accesses.
+    batched: the specialised master's order of reads (csrc/htm_flow.hpp FlowTurn) -- with EVERY poll of the turn, behind the
+    checks and the epoch, in this order: the chain's own temperature of the iteration before, the plan of that iteration's swap,
+    every chain's committed key, every chain's record (T, L).  The plan is used only if that same round lets the turn pass, the
+    partner's record only if that same round's committed key of the partner shows its commit; otherwise the wave falls into the
+    spin on the partner's key and reads the record behind it, as the generic master does."""
     key = lambda i, c: (i - i0) * nc + c
     nextB = lambda pos, n: st.next_from(pos, n)[1]
     my_epoch, my_akey = 0, 0             # the epoch this wave predicts in, and that epoch's anchor key
@@ -167,6 +172,17 @@ def wave(sh, st, w, NW, nc, i0, target, rnd, trace):
         while True:
             pr = list(sh.prog); yield
             e = sh.epoch; yield
+            if batched:
+                q = (i - 1) & 3
+                b_T = sh.T4[q][c]; yield
+                b_E = sh.Eof[q]; yield
+                if batched == "records first":       # (a WRONG order, for the model's own check: the record read ahead of the key that validates it)
+                    b_T4 = list(sh.T4[q]); yield
+                    b_L4 = list(sh.L4[q]); yield
+                b_done = list(sh.done); yield
+                if batched != "records first":
+                    b_T4 = list(sh.T4[q]); yield
+                    b_L4 = list(sh.L4[q]); yield
             if e != my_epoch:
                 a_key, a_pos = sh.anchor[e & 1]; yield
                 e2 = sh.epoch; yield
@@ -206,18 +222,30 @@ def wave(sh, st, w, NW, nc, i0, target, rnd, trace):
         if restart:
             continue
         # ---- the swap of the iteration before, if this chain was in its pair
-        T_now = sh.T4[(i - 1) & 3][c] if i - 1 > i0 else sh.T4[i & 3][c]
+        if batched:
+            T_now = b_T if i - 1 > i0 else sh.T4[i & 3][c]      # (the first iteration of a launch: its own short branch)
+        else:
+            T_now = sh.T4[(i - 1) & 3][c] if i - 1 > i0 else sh.T4[i & 3][c]
         if i - 1 > i0 and nc > 1:
-            E_prev = sh.Eof[(i - 1) & 3]; yield      # written by the last chain's wave before it published its check
+            if batched:
+                E_prev = b_E                         # taken at the instant of the poll that let the turn pass
+            else:
+                E_prev = sh.Eof[(i - 1) & 3]; yield      # written by the last chain's wave before it published its check
             i1, i2, d = st.sw(E_prev)
             if c in (i1, i2):
                 o = i2 if c == i1 else i1
-                while True:
-                    dn = sh.done[o]; yield
-                    if dn >= key(i - 1, o):
-                        break
-                L1, L2 = sh.L4[(i - 1) & 3][i1], sh.L4[(i - 1) & 3][i2]; yield
-                T1, T2 = sh.T4[(i - 1) & 3][i1], sh.T4[(i - 1) & 3][i2]; yield
+                if batched and b_done[o] >= key(i - 1, o):
+                    # the partner's record as read behind that round's look at its committed key
+                    L1, L2, T1, T2 = b_L4[i1], b_L4[i2], b_T4[i1], b_T4[i2]
+                    sh.batch_hits += 1
+                else:
+                    while True:
+                        dn = sh.done[o]; yield
+                        if dn >= key(i - 1, o):
+                            break
+                    L1, L2 = sh.L4[(i - 1) & 3][i1], sh.L4[(i - 1) & 3][i2]; yield
+                    T1, T2 = sh.T4[(i - 1) & 3][i1], sh.T4[(i - 1) & 3][i2]; yield
+                    sh.batch_misses += 1
                 if swap_outcome(st, E_prev, L1, L2, T1, T2):
                     T_now = T2 if c == i1 else T1
         sh.T4[i & 3][c] = T_now; yield
@@ -251,9 +279,11 @@ def wave(sh, st, w, NW, nc, i0, target, rnd, trace):
     return
 
 
-def run_case(seed, verbose=False):
+def run_case(seed, verbose=False, batched=False, stats=None):
+    """batched: the specialised master's batch of reads at the turn (wave); it runs one chain per wave, so at most eight chains.
+    stats: a dict that collects how often the pair's path took the partner's record from the batch and how often from the spin"""
     rnd = random.Random(seed)
-    nc = rnd.choice([1, 2, 3, 5, 8, 8, 11, 16, 19])
+    nc = rnd.choice([1, 2, 3, 4, 5, 8, 8, 8] if batched else [1, 2, 3, 5, 8, 8, 11, 16, 19])
     NW = 8
     n_iter = rnd.randint(3, 40)
     p_rej = rnd.choice([0.0, 0.02, 0.2, 0.6, 1.0])
@@ -277,8 +307,9 @@ def run_case(seed, verbose=False):
         sh.T4[(i0 + 1) & 3][c] = T0[c]
     sh.last_iter, sh.stop_at = n_iter, stop_at
     sh.Eof = [0, 0, 0, 0]
+    sh.batch_hits = sh.batch_misses = 0
     trace = {}
-    gens = [wave(sh, st, w, NW, nc, i0, n_iter, rnd, trace) for w in range(NW)]
+    gens = [wave(sh, st, w, NW, nc, i0, n_iter, rnd, trace, batched) for w in range(NW)]
     alive = list(range(NW))
     steps = 0
     bias = rnd.choice([None, None, rnd.randrange(NW)])        # one wave that is scheduled rarely (a straggler)
@@ -303,7 +334,11 @@ def run_case(seed, verbose=False):
             T[i1], T[i2] = T[i2], T[i1]
         p_end += d
     ok = (sh.x == xs and sh.L == Ls and T == Ts and p_end == ps and trace == tr_s)
-    if verbose or not ok:
+    if stats is not None:
+        stats["hits"] = stats.get("hits", 0) + sh.batch_hits
+        stats["misses"] = stats.get("misses", 0) + sh.batch_misses
+        stats["epochs"] = stats.get("epochs", 0) + sh.epoch
+    if verbose or (not ok and batched != "records first"):
         print("seed %d: nc %d, %d iterations (stop at %s), p_rej %.2f, epochs %d: %s" %
               (seed, nc, n_iter, stop_at, p_rej, sh.epoch, "equal" if ok else "MISMATCH"))
         if not ok:
@@ -729,6 +764,14 @@ if __name__ == "__main__":
             bad += 1
             break
     print("%d cases: %s" % (n, "all equal to the serial loop" if not bad else "FAILED"))
+    if not bad:
+        st_b = {}
+        for s in range(1, n + 1):
+            if not run_case(s, batched=True, stats=st_b):
+                bad += 1
+                break
+        print("%d cases with the turn's batch of reads (partner's record from the batch %d times, from the spin %d times): %s" %
+              (n, st_b.get("hits", 0), st_b.get("misses", 0), "all equal to the serial loop" if not bad else "FAILED"))
     if not bad:
         for s in range(1, n + 1):
             if not run_case_lock(s):
