@@ -373,6 +373,9 @@ struct orc_job {
     int          slog_cap, slog_n;
     int32_t     *slog_i;
     double      *slog_d;
+    /* swap log */
+    int          wlog_cap, wlog_n;
+    int32_t     *wlog;
 };
 
 static const double EPS = 2.220446049250313e-16; /* epsilon(1.d0) */
@@ -495,6 +498,7 @@ void orc_job_destroy(orc_job *job)
     orc_forward_destroy(job->fwd);
     free(job->scratch_hypo);
     free(job->slog_i); free(job->slog_d);
+    free(job->wlog);
     free(job);
 }
 
@@ -603,6 +607,16 @@ static void chain_step(orc_job *job, int r, int jc, int i)
     if (c->temp < 1.0 + EPS && (i % job->p.n_interval) == 1) record(job, rk, c, i);
 }
 
+/* swap log: observes what select_pair did; takes no draw and changes no state the run reads */
+static void log_swap(orc_job *job, int iter, int i1, int i2, int n_draws)
+{
+    if (job->wlog_n < job->wlog_cap) {
+        int32_t *w = job->wlog + 5 * (size_t)job->wlog_n;
+        w[0] = iter; w[1] = i1; w[2] = i2; w[3] = n_draws; w[4] = i1 / job->p.n_chains;
+        job->wlog_n++;
+    }
+}
+
 /* src/cls_parallel.f90:285-302 */
 static int judge_swap(double temp1, double temp2, double l1, double l2, orc_rng *rng)
 {
@@ -623,11 +637,13 @@ static void swap_temperature(orc_job *job)
     if (n_proc * n_chain < 2) return;
     orc_rng *rng0 = &job->ranks[0].rng;
     int i1 = (int)(orc_rand_u(rng0) * n_proc * n_chain);
-    int i2;
+    int i2, n_draws = 1;
     for (;;) {
         i2 = (int)(orc_rand_u(rng0) * n_proc * n_chain);
+        ++n_draws;
         if (i1 != i2) break;
     }
+    log_swap(job, job->i_done, i1, i2, n_draws);
     int rank1 = i1 / n_chain, rank2 = i2 / n_chain;
     int chain1 = i1 % n_chain, chain2 = i2 % n_chain; /* 0-based */
     orc_chain *c1 = &job->ranks[rank1].chains[chain1];
@@ -663,11 +679,13 @@ void orc_job_rank_begin(orc_job *job, int rank, double *rec)
     rec[3] = (double)i;
     if (n_proc * n_chain > 1) {
         if (rank == 0) { /* select_pair, src/cls_parallel.f90:226-230 */
-            int i1 = (int)(orc_rand_u(&rk->rng) * n_proc * n_chain), i2;
+            int i1 = (int)(orc_rand_u(&rk->rng) * n_proc * n_chain), i2, n_draws = 1;
             for (;;) {
                 i2 = (int)(orc_rand_u(&rk->rng) * n_proc * n_chain);
+                ++n_draws;
                 if (i1 != i2) break;
             }
+            log_swap(job, i, i1, i2, n_draws);
             rec[0] = (double)i1;
             rec[1] = (double)i2;
         }
@@ -786,6 +804,21 @@ void orc_job_get_steplog(const orc_job *job, int32_t *irows, double *drows)
 {
     memcpy(irows, job->slog_i, 8 * (size_t)job->slog_n * sizeof(int32_t));
     memcpy(drows, job->slog_d, 4 * (size_t)job->slog_n * sizeof(double));
+}
+
+void orc_job_enable_swaplog(orc_job *job, int cap)
+{
+    free(job->wlog);
+    job->wlog_cap = cap;
+    job->wlog_n = 0;
+    job->wlog = cap ? (int32_t *)malloc(5 * (size_t)cap * sizeof(int32_t)) : NULL;
+}
+
+int orc_job_swaplog_n(const orc_job *job) { return job->wlog_n; }
+
+void orc_job_get_swaplog(const orc_job *job, int32_t *rows)
+{
+    memcpy(rows, job->wlog, 5 * (size_t)job->wlog_n * sizeof(int32_t));
 }
 
 /* ====================================================================================================

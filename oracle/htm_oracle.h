@@ -111,6 +111,12 @@ void     orc_job_get_rng(const orc_job *job, int rank, uint32_t state[4]);
 void     orc_job_enable_steplog(orc_job *job, int cap);
 int      orc_job_steplog_n(const orc_job *job);
 void     orc_job_get_steplog(const orc_job *job, int32_t *irows /* n x 8 */, double *drows /* n x 4 */);
+/* per-iteration swap trace (optional): rows of {iter, i1, i2, draws select_pair took (src/cls_parallel.f90:226-230: one for
+ * i1, one per try at i2), rank whose stream gives judge_swap's number (:294) = i1 / n_chains}.  Logging takes no draw.
+ * cap = max rows kept (0 disables). */
+void     orc_job_enable_swaplog(orc_job *job, int cap);
+int      orc_job_swaplog_n(const orc_job *job);
+void     orc_job_get_swaplog(const orc_job *job, int32_t *rows /* n x 5 */);
 
 /* step 4 (hypo_tremor_select): regressions of one window set, out[n_win][6] = {vs, b, t0, a0, cc_t, cc_a}
  * (src/cls_selector.f90:75-132, src/mod_regress.f90) */

@@ -88,6 +88,9 @@ def lib():
     L.orc_job_enable_steplog.argtypes = [vp, C.c_int]
     L.orc_job_steplog_n.argtypes = [vp]
     L.orc_job_get_steplog.argtypes = [vp, ip, dp]
+    L.orc_job_enable_swaplog.argtypes = [vp, C.c_int]
+    L.orc_job_swaplog_n.argtypes = [vp]
+    L.orc_job_get_swaplog.argtypes = [vp, ip]
     # the FFT stand-in the compiled reference's steps 2 and 3 link instead of FFTW (ref_dft.c)
     for n in ("fftw_plan_dft_r2c_1d", "fftw_plan_dft_c2r_1d"):
         getattr(L, n).argtypes = [C.c_int, vp, vp, C.c_int]
@@ -321,6 +324,17 @@ class Job:
             lib().orc_job_get_steplog(self.h, ir.ctypes.data_as(C.POINTER(C.c_int32)),
                                       dr.ctypes.data_as(C.POINTER(C.c_double)))
         return ir, dr
+
+    def enable_swaplog(self, cap: int):
+        lib().orc_job_enable_swaplog(self.h, int(cap))
+
+    def swaplog(self):
+        """one row per iteration: iter, i1, i2, draws select_pair took, rank that drew the judge number"""
+        n = lib().orc_job_swaplog_n(self.h)
+        rows = np.empty((n, 5), np.int32)
+        if n:
+            lib().orc_job_get_swaplog(self.h, rows.ctypes.data_as(C.POINTER(C.c_int32)))
+        return rows
 
 
 def select_regress(sta_x, sta_y, sta_z, z_guess, t, t_err, a, a_err):
