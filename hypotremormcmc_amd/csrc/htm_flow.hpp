@@ -69,6 +69,12 @@ struct FlowShared : StepShared {
     // type | event << 3 of the chain's PREVIOUS step (0: none yet; kept across launches in ChainsDev::prev_mid): if it was a
     // hypocentre step, a full evaluation leaves its event to the chain's own wave -- whenever the order went out (flow_step)
     int pv_mid[kMaxChains];
+#ifdef HTM_STAMPS
+    // diagnostic build: per wave, ticks between two steps -- [0] a step's return -> the batch of the loop top issued (the roll-over and
+    // the batch's instructions), [1] -> all of the batch returned (its wait), [2] -> the step's entry (the checks), [3] the stamps' own
+    // bookkeeping at a step's end
+    unsigned long long stamp_bt[8][4];
+#endif
 };
 
 // a wave-uniform value that reached a vector register (read from LDS) back in a scalar one
@@ -169,8 +175,15 @@ struct FlowWave {                 // a wave's predictions (wave-uniform)
 // partial-update steps (0 front: loads issued, 1 proposal + check published, 2 evaluation, 3 turn, 4 swap + decision + commit,
 // 5 records + orders), 6 ticks of its full-evaluation steps, 7 / 8 the two counts, 9 ticks between steps (loop top), 10 wait part of 6
 #define FSTAMP(k) do { if (lane == 0 && cs.stamps) { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); st_acc[k] += n_ - t_last; t_last = n_; } } while (0)
+// the stretch between two steps (flow_body), split three ways: FlowShared::stamp_bt.  The sums are kept in registers of lane 0 and
+// stored once, at the launch's end: no bookkeeping of their own inside the stretch.  What a step's end adds to its wave's sums in LDS
+// (flow_step, behind FSTAMP(5)) is timed and reported as stamp_bt[..][3]: tools/flow_stamps.py subtracts it from `between`.
+#define BSTAMP(k) do { if (lane == 0 && cs.stamps) { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); bt_acc[k] += n_ - bt_last; bt_last = n_; } } while (0)
+#define BSTAMP_FROM_HERE() do { if (lane == 0 && cs.stamps) bt_last = __builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define FSTAMP(k) do { } while (0)
+#define BSTAMP(k) do { } while (0)
+#define BSTAMP_FROM_HERE() do { } while (0)
 #endif
 
 // What a wave with ONE chain knows about its next step before the step begins: looked up from the stream window while the
@@ -873,6 +886,20 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
             // an order sent ahead (one or two steps) may have been answered already: its granules are requested now, under the
             // evaluation of the wave's own event
             const bool early = pre;
+            // (the specialised master: a full evaluation looks ahead as a partial update does -- the same three hop-table entries here, in
+            // front of its own event's evaluation and its polls of the workers' granules, what the stream holds at those positions behind
+            // the first of them -- so that the step behind it starts `known` and the wave's B2 comes from FlowNext::b3.  One chain per wave,
+            // one workgroup: the tables reach in one entry.  Still a prediction, valid in its epoch and inside the window; nothing this
+            // step commits, or orders for itself, depends on it)
+            if constexpr (FX) {
+                if (NW >= nc_ && W.rpos1 >= 0 && W.B2 >= 0 && c >= W.rc1 && iter + 1 <= tp.iter_target) {
+                    la = 1; la_epoch = W.epoch;
+                    const int n1 = c - W.rc1;
+                    if (n1 > 0) hA = rg.hop[(W.rpos1 & M) * kHops + n1 - 1];
+                    if (c > 0) hB = rg.hop[(W.B2 & M) * kHops + c - 1];
+                    hE = rg.hop[(W.B2 & M) * kHops + nc_ - 1];
+                }
+            }
             if (early) issue(0);
             // The event of the chain's previous step, if that was a hypocentre step: the workers LEFT IT OUT (an order sent two
             // steps ahead was evaluated while that step may or may not have committed), this wave adds its misfit -- at the
@@ -895,11 +922,25 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
             }
             bool have = false;
             if (early) have = complete(0);
+            if constexpr (FX) {
+                if (!have) issue(0);      // (the first poll's loads: their round trip covers the look-ahead's second round)
+                if (la) {
+                    la_p1 = W.rpos1 + uni(hA); la_p2 = W.B2 + uni(hB); la_E2 = W.B2 + uni(hE);
+                    const int lim = uni(sh.fill) - 16;
+                    if (la_p1 < lim && la_p2 < lim && la_E2 + 16 < lim) {
+                        la = 2;
+                        d1v = reinterpret_cast<const i32x4 *>(rg.dec)[la_p1 & M];
+                        d2v = reinterpret_cast<const i32x4 *>(rg.dec)[la_p2 & M];
+                        swv = reinterpret_cast<const i32x4 *>(rg.sw)[la_E2 & M];
+                        la_g = rg.pg[la_p1 & M]; la_r = rg.pr[la_p1 & M]; la_logr = rg.plogr[la_p1 & M];
+                    }
+                }
+            }
 #ifdef HTM_STAMPS
             const unsigned long long tw0_ = __builtin_amdgcn_s_memtime();
 #endif
             if (!have) {
-                issue(0);
+                if constexpr (!FX) issue(0);
                 for (;;) {
                     issue(1);
                     if (complete(0)) { which = 0; break; }
@@ -1447,6 +1488,8 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
         unsigned long long *a = sh.stamp_acc + 12 * (wave & 7);
         if (need_full) { a[6] += t_last - t_step0; a[8] += 1; a[10] += t_wait; }
         else { for (int k = 0; k < 6; ++k) a[k] += st_acc[k]; a[9] += st_acc[6]; a[7] += 1; }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        sh.stamp_bt[wave & 7][3] += __builtin_amdgcn_s_memtime() - t_last;      // (this sum's own update falls behind the stamp: a few ticks)
     }
 #endif
     return p + cnt;
@@ -1498,6 +1541,7 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
     for (int k = tid; k < 7 * nc; k += blockDim.x) { sh.np[k] = 0; sh.na[k] = 0; }
 #ifdef HTM_STAMPS
     for (int k = tid; k < 96; k += blockDim.x) sh.stamp_acc[k] = 0ull;
+    for (int k = tid; k < 32; k += blockDim.x) sh.stamp_bt[k >> 2][k & 3] = 0ull;
 #endif
     for (int k = tid; k < rg.mir_n; k += blockDim.x) { rg.mx[k] = cs.xall[k]; if (rg.mir_steps) rg.mstep[k] = cs.stall[k]; }
     if constexpr (LOCK) {      // where the peers' inboxes are mapped (flow_post_chain / flow_post_header)
@@ -1581,6 +1625,7 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
     mw.epoch = 0; mw.last_iter = sh.c.iter_target; mw.err = 0; mw.n_lik = sh.c.n_lik; mw.n_smp = sh.c.n_smp; mw.pv = 0ull;
 #ifdef HTM_STAMPS
     const unsigned long long t_loop0 = __builtin_amdgcn_s_memtime();
+    unsigned long long bt_last = t_loop0, bt_acc[3] = {0, 0, 0};
 #endif
     while (alive) {
         // ---- top of a step: the epoch its position is predicted in
@@ -1602,6 +1647,11 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
             if constexpr (flow_fixed_v<TR>) { tp.i0 = lds_ld(&sh.i0); tp.iter_target = lds_ld(&sh.c.iter_target); }      // (launch constants: no wait of their own in the step)
             asm volatile("" ::: "memory");
         }
+#ifdef HTM_STAMPS
+        BSTAMP(0);      // (the loop's end, and whatever ran since the step returned)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        BSTAMP(1);
+#endif
         {
             const int e = tp.epoch;
             if (__builtin_expect(e != W.epoch, 0)) {
@@ -1685,8 +1735,10 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
         }
         // (several master workgroups: a wave has one chain -- "wave" c of as many waves as there are chains)
         if constexpr (MB) MB_HIST(mw, (known ? 4 : 0) | (W.epoch & 3));
+        BSTAMP(2);
         const int r = flow_step<NCH, F32, LOCK, MB, TR>(f, cs, sh, rg, W, nx, g_mb, mw, s_gath, wmax, s_sx, s_sy, s_sz, c, p, iter, lane, MB ? c : wave,
                                               MB ? 64 : NW, launch, wave == 0, look, back, rec_phase == 1, tp, fs, own);
+        BSTAMP_FROM_HERE();
         if (r == kFlowRestart) continue;      // (nothing was committed: the wave's copies of its chain's corrections stand)
         if (r == kFlowAbort || r == kFlowStop) break;
         // ---- this wave's next step
@@ -1710,12 +1762,18 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
         }
     }
 #ifdef HTM_STAMPS
-    if (lane == 0 && cs.stamps && wave < 8) sh.stamp_acc[12 * wave + 11] += __builtin_amdgcn_s_memtime() - t_loop0;
+    if (lane == 0 && cs.stamps && wave < 8) {
+        sh.stamp_acc[12 * wave + 11] += __builtin_amdgcn_s_memtime() - t_loop0;
+        for (int k = 0; k < 3; ++k) sh.stamp_bt[wave][k] += bt_acc[k];
+    }
 #endif
     __syncthreads();
 #ifdef HTM_STAMPS
-    if (cs.stamps)
+    if (cs.stamps) {
         for (int k = tid; k < 96; k += blockDim.x) if (sh.stamp_acc[k]) atomicAdd(&cs.stamps[32 + k], sh.stamp_acc[k]);      // (the workers' own stamps sit at 20..28)
+        // (behind the 128 words of htm_chains_read_stamps, where the pipelined master keeps its trace: htm_chains_read_trace reads them)
+        for (int k = tid; k < 32; k += blockDim.x) if (sh.stamp_bt[k >> 2][k & 3]) atomicAdd(&cs.stamps[128 + k], sh.stamp_bt[k >> 2][k & 3]);
+    }
 #endif
     // ---- every step up to last_iter is committed: the swap of the last iteration, counters, the launch's end state
     if constexpr (LOCK) {

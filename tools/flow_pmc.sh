@@ -1,15 +1,20 @@
 # Run ON THE GPU BOX (through gpurun): instruction counters of the free-running master alone (tools/flow_pmc.py), three
 # counter passes (counters in their own runs, --kernel-trace only), summary to gpurun_out/<tag>_flow_pmc.txt.
 #   bash tools/flow_pmc.sh r03_z
+# HTM_LIB=<library> in the environment counts another build (hypotremormcmc_amd/_lib.py reads it when tools/flow_pmc.py imports the
+# package); a build of an older header needs HTM_LIB_OLDER_BUILD=1 with it, as tools/ab.sh sets it: the `before` halves of
+# profiles/*_flow_pmc.txt are taken that way.
+# Every pass runs under a time limit of its own, and a pass that fails ends the script: nothing more is started on the GPU.
+set -e
 cd /tmp && export TMPDIR=/tmp
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out
 T=${1:-flow}
 mkdir -p $OUT
 N=20000
-rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM --kernel-trace -d $OUT/pmc_${T}_1 -o p --output-format csv -- python3 $ROOT/tools/flow_pmc.py $N > $OUT/pmc_${T}_1.log 2>&1
-rocprofv3 --pmc SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_BRANCH SQ_WAVE_CYCLES --kernel-trace -d $OUT/pmc_${T}_2 -o p --output-format csv -- python3 $ROOT/tools/flow_pmc.py $N > $OUT/pmc_${T}_2.log 2>&1
-rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_WAIT_INST_ANY SQ_BUSY_CYCLES --kernel-trace -d $OUT/pmc_${T}_3 -o p --output-format csv -- python3 $ROOT/tools/flow_pmc.py $N > $OUT/pmc_${T}_3.log 2>&1
+timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM --kernel-trace -d $OUT/pmc_${T}_1 -o p --output-format csv -- python3 $ROOT/tools/flow_pmc.py $N > $OUT/pmc_${T}_1.log 2>&1
+timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_BRANCH SQ_WAVE_CYCLES --kernel-trace -d $OUT/pmc_${T}_2 -o p --output-format csv -- python3 $ROOT/tools/flow_pmc.py $N > $OUT/pmc_${T}_2.log 2>&1
+timeout -k 10 300 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_WAIT_INST_ANY SQ_BUSY_CYCLES --kernel-trace -d $OUT/pmc_${T}_3 -o p --output-format csv -- python3 $ROOT/tools/flow_pmc.py $N > $OUT/pmc_${T}_3.log 2>&1
 python3 - $OUT $T $N <<'PY'
 import csv, glob, os, sys
 out, tag, n = sys.argv[1], sys.argv[2], int(sys.argv[3])

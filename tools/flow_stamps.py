@@ -33,12 +33,19 @@ lib.htm_chains_read_stamps.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
 a = (C.c_uint64 * 128)()
 lib.htm_chains_read_stamps(cs.handle, a)
 base = list(a)
+# the split of `between` (FlowShared::stamp_bt): 8 waves x 4 sums behind the 128 words, read as 16 pairs
+lib.htm_chains_read_trace.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
+t = (C.c_uint64 * 32)()
+lib.htm_chains_read_trace(cs.handle, t, 16)
+base_bt = list(t)
 n = 20000 if E_ <= 1000 else 2000
 t0 = time.perf_counter()
 _run(n)
 print("wall us/iteration %.3f (stamps build)" % (1e6 * (time.perf_counter() - t0) / n))
 lib.htm_chains_read_stamps(cs.handle, a)
 d = [a[k] - base[k] for k in range(128)]
+lib.htm_chains_read_trace(cs.handle, t, 16)
+bt = [t[k] - base_bt[k] for k in range(32)]
 names = ["front: loads issued", "proposal, check published", "evaluation (2 positions)", "turn", "swap + decision + commit", "records + orders"]
 print("ticks per step, by wave (partial-update steps); full-evaluation steps: total ticks per step (of which waiting for the workers)")
 print("%-4s %8s " % ("wave", "steps") + " ".join("%9s" % s[:9] for s in names) + " %9s %9s | %7s %9s %9s | %9s %9s" % ("lock-step", "sum", "jobs", "ticks", "wait", "loop/iter", "between"))
@@ -57,3 +64,19 @@ jobs_all = sum(d[32 + 12 * w + 8] for w in range(min(8, nc)))
 if jobs_all:
     print("worker block 0 per order: evaluation of its events %.2f us, block sum + store %.2f us  (%d orders)" %
           ((d[22] - d[21]) / jobs_all / 100.0, (d[23] - d[22]) / jobs_all / 100.0, jobs_all))
+
+# `between` split (all steps of the wave, partial or full): `roll-over` from a step's return to the last read of the loop top's batch
+# issued (the roll-over and the batch's own instructions), `top batch` from there until all of the batch has returned (its wait),
+# `checks` from there to the step's entry.  These three sums are kept in registers (no bookkeeping inside the
+# stretch); `stamps` is what the stamps build itself adds behind a step's last stamp (its sums in LDS), timed, and `net` = between
+# - stamps.  `other` = net - the three: the call and return, the step's first stamp, the stamps' own reads of the clock.
+print("between two steps, ticks per step, by wave")
+print("%-4s %9s %9s %9s %9s | %9s %9s %9s" % ("wave", "roll-over", "top batch", "checks", "other", "stamps", "between", "net"))
+for w in range(min(8, nc)):
+    b = d[32 + 12 * w:32 + 12 * w + 12]
+    steps = max(1, b[7] + b[8])
+    inside = sum(b[:6]) + b[6] + b[9]
+    between = (b[11] - inside) / steps
+    q = [bt[4 * w + k] / steps for k in range(4)]
+    net = between - q[3]
+    print("%-4d %9.0f %9.0f %9.0f %9.0f | %9.0f %9.0f %9.0f" % (w, q[0], q[1], q[2], net - q[0] - q[1] - q[2], q[3], between, net))
