@@ -523,11 +523,14 @@ int htm_forward_time_full_batch_dev(htm_forward *h, int n_models, const double *
 // made here, on the host.  n_draws = 0: htm_forward_locate, one structure (t_corr, a_corr [S]; *vs, *qs) and k_locate;
 // n_draws >= 1: htm_forward_locate_marginal, t_corr, a_corr [n_draws][S], vs, qs [n_draws] and k_locate_marginal; with log_z
 // htm_forward_locate_draw_evidence instead (loc, marg, vol NULL): k_locate_draw_evidence, k_locate_draw_combine, log_z [E][n_draws]
-// and summary [E][4] or NULL.
-static int locate_run(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr, const double *qs,
-                      const double *grid9, const double *prior5, double *loc, double *marg, double *vol, double *log_z = nullptr,
-                      double *summary = nullptr)
+// and summary [E][4] or NULL.  F32: the single-precision forward of htm_forward_locate_set_precision -- the kernels' F32
+// instantiations, and the draws' table in floats.
+extern "C++" {      // (a template, among the C entry points)
+template <bool F32>
+static int locate_run_as(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr, const double *qs,
+                         const double *grid9, const double *prior5, double *loc, double *marg, double *vol, double *log_z, double *summary)
 {
+    typedef LocPairT<loc_real<F32>> Pair;
     const bool draws = n_draws > 0, evid = log_z != nullptr;
     LocGrid g{};
     if (int rc = map_grid_parse(grid9, &g)) return rc;
@@ -556,7 +559,7 @@ static int locate_run(htm_forward *h, int n_draws, const double *t_corr, const d
     const double per_event = sizeof(double) * (evid ? (double)n_tiles * Kpad * 2.0 + K + 4.0 + nm
                                                     : (double)n_tiles * g.stride + (vol ? (double)cells : 0.0) + 2.0 * nm + 16.0) +
                              sizeof(LocSta) * (double)S + sizeof(LocEv);
-    const double table = draws ? sizeof(LocPair) * ((double)S + 1.0) * Kpad + sizeof(double) * (2.0 * S + 2.0) * K : 0.0;
+    const double table = draws ? sizeof(Pair) * ((double)S + 1.0) * Kpad + sizeof(double) * (2.0 * S + 2.0) * K : 0.0;
     if (draws && table + per_event > mb * 1048576.0)
         return fail(HTM_EINVAL, "HTM_LOCATE_MB = %g: the table of %d draws (%.0f bytes) and one event (%.0f bytes) do not fit", mb, K, table, per_event);
     long nb = std::min<long>(E, 65535L);
@@ -583,21 +586,22 @@ static int locate_run(htm_forward *h, int n_draws, const double *t_corr, const d
 
     LocJob jb{};
     jb.sta = d_sta; jb.ev = d_ev; jb.prior = d_prior; jb.part = d_part; jb.vol = d_vol; jb.S = S;
-    LocDraws dr{};
+    LocDraws<loc_real<F32>> dr{};
     if (!draws) {
         HIPCHK(hipMemcpy(h->d_tc, t_corr, (size_t)S * sizeof(double), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(h->d_ac, a_corr, (size_t)S * sizeof(double), hipMemcpyHostToDevice));
         jb.rbeta = 1.0 / *vs; jb.katt = (kPi * kFreq) / (*qs * *vs);          // as event_misfit forms them
+        jb.rbeta32 = (float)jb.rbeta; jb.katt32 = (float)jb.katt;
     } else {
         // (the station records' tc and ac are not read on this path: k_locate_pack fills them from whatever the handle holds)
         std::vector<double> rk(2 * (size_t)K);
         for (int k = 0; k < K; ++k) { rk[k] = 1.0 / vs[k]; rk[(size_t)K + k] = (kPi * kFreq) / (qs[k] * vs[k]); }
         double *d_dtc = nullptr, *d_dac = nullptr, *d_rk = nullptr;
-        LocPair *d_corr = nullptr, *d_vq = nullptr;
+        Pair *d_corr = nullptr, *d_vq = nullptr;
         if ((rc = pool.upload(&d_dtc, t_corr, (size_t)K * S)) || (rc = pool.upload(&d_dac, a_corr, (size_t)K * S)) || (rc = pool.upload(&d_rk, rk.data(), rk.size())) ||
             (rc = pool.alloc(&d_corr, (size_t)S * Kpad)) || (rc = pool.alloc(&d_vq, (size_t)Kpad)))
             return rc;
-        hipLaunchKernelGGL(k_locate_pack_draws, dim3((unsigned)((((long)S + 1) * Kpad + 255) / 256)), dim3(256), 0, h->stream, S, K, Kpad, d_dtc, d_dac, d_rk,
+        hipLaunchKernelGGL(k_locate_pack_draws<loc_real<F32>>, dim3((unsigned)((((long)S + 1) * Kpad + 255) / 256)), dim3(256), 0, h->stream, S, K, Kpad, d_dtc, d_dac, d_rk,
                            d_rk + K, d_corr, d_vq);
         dr.vq = d_vq; dr.corr = d_corr; dr.K = K; dr.Kpad = Kpad;
     }
@@ -629,9 +633,9 @@ static int locate_run(htm_forward *h, int n_draws, const double *t_corr, const d
         const dim3 grid((unsigned)n_tiles, (unsigned)m), block(kLocThreads);
         with_mode(mode, [&](auto M) {
             constexpr int MODE = decltype(M)::value;
-            if (!draws) hipLaunchKernelGGL(k_locate<MODE>, grid, block, 0, h->stream, g, jb);
-            else if (evid) hipLaunchKernelGGL(k_locate_draw_evidence<MODE>, grid, block, 0, h->stream, g, jb, dr);
-            else hipLaunchKernelGGL(k_locate_marginal<MODE>, grid, block, 0, h->stream, g, jb, dr);
+            if (!draws) hipLaunchKernelGGL((k_locate<MODE, F32>), grid, block, 0, h->stream, g, jb);
+            else if (evid) hipLaunchKernelGGL((k_locate_draw_evidence<MODE, F32>), grid, block, 0, h->stream, g, jb, dr);
+            else hipLaunchKernelGGL((k_locate_marginal<MODE, F32>), grid, block, 0, h->stream, g, jb, dr);
         });
         if (evid)
             hipLaunchKernelGGL(k_locate_draw_combine, dim3((unsigned)m), dim3(256), 0, h->stream, (int)n_tiles, K, Kpad, d_part, log_cell, d_logz, d_sum);
@@ -648,6 +652,24 @@ static int locate_run(htm_forward *h, int n_draws, const double *t_corr, const d
         if (marg && (rc = pool.download(marg + (size_t)e0 * nm, d_marg, (size_t)m * nm, "the marginals'"))) return rc;
         if (vol && (rc = pool.download(vol + (size_t)e0 * cells, d_vol, (size_t)m * cells, "the volume's"))) return rc;
     }
+    return HTM_OK;
+}
+}  // extern "C++"
+
+static int locate_run(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr, const double *qs,
+                      const double *grid9, const double *prior5, double *loc, double *marg, double *vol, double *log_z = nullptr,
+                      double *summary = nullptr)
+{
+    return h->loc_fp32 ? locate_run_as<true>(h, n_draws, t_corr, vs, a_corr, qs, grid9, prior5, loc, marg, vol, log_z, summary)
+                       : locate_run_as<false>(h, n_draws, t_corr, vs, a_corr, qs, grid9, prior5, loc, marg, vol, log_z, summary);
+}
+
+// The arithmetic of the three locate entry points on this handle (include/htm_hip.h); step 5's switch is htm_forward_set_precision
+int htm_forward_locate_set_precision(htm_forward *h, int forward_fp32)
+{
+    if (!h) return fail(HTM_EINVAL, "NULL handle");
+    if (forward_fp32 != 0 && forward_fp32 != 1) return fail(HTM_EINVAL, "forward_fp32 = %d: need 0 (fp64) or 1 (fp32)", forward_fp32);
+    h->loc_fp32 = forward_fp32 != 0;
     return HTM_OK;
 }
 

@@ -126,6 +126,8 @@ struct htm_forward {
     // [E] every event's own share of dev.const_sum, per data type: sum_j (log_2pi_half + log stdv(j, event)) in station order
     // (htm_forward_locate: an event's term of the log-likelihood)
     double *d_lconst_t = nullptr, *d_lconst_a = nullptr;
+    // htm_forward_locate_set_precision: the three locate entry points evaluate the synthetics in fp32 (dev.fp32 is step 5's)
+    bool loc_fp32 = false;
 };
 
 struct htm_chains {

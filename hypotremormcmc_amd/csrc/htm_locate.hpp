@@ -25,6 +25,12 @@
 // No floating-point atomics anywhere: the bits do not depend on timing.  The volume of log posteriors is written only when it
 // is asked for.
 //
+// Every one of the three evaluation kernels exists twice: F32 = false, all arithmetic fp64, and F32 = true, the single-precision
+// forward of htm_forward_locate_set_precision (the rule: loc_station).  The float copies of the structure are
+// made ONCE, where the records are packed: the station's corrections in LocSta's last slot (k_locate_pack), 1 / vs and
+// pi f / (qs vs) in LocJob (the host), the draws' table as pairs of floats in the place of the pairs of doubles
+// (k_locate_pack_draws<float>).  The kernels convert nothing that is uniform.
+//
 // Partial record of a tile (doubles): [0] the tile's maximum lp (-inf: no included cell; k_locate_combine overwrites it with
 // the tile's scale), [1] its first cell's linear index (-1: none), [2] that cell's log-likelihood term, [3] the tile's weight
 // sum, then mx[nx] (weight per ix over the tile's rows), S[rows_per_tile] (weight per row), T[rows_per_tile] (weight times x
@@ -58,11 +64,24 @@ constexpr int kLocmCells = HTM_LOCM_CELLS;
 constexpr int kLocMaxDraws = 4096;      // draws per call (include/htm_hip.h)
 static_assert(kLocDraws >= 1 && kLocMaxDraws % kLocDraws == 0, "whole blocks of draws");
 static_assert(kLocmCells >= 1 && kLocPerThread % kLocmCells == 0, "whole chunks");
+// the same two choices for the F32 instantiations, whose register budget is another (measured: DESIGN.md 3.13)
+#ifndef HTM_LOC_CHUNK32
+#define HTM_LOC_CHUNK32 4
+#endif
+#ifndef HTM_LOCM_CELLS32
+#define HTM_LOCM_CELLS32 HTM_LOCM_CELLS
+#endif
+constexpr int kLocChunk32 = HTM_LOC_CHUNK32;
+constexpr int kLocmCells32 = HTM_LOCM_CELLS32;
+static_assert(kLocChunk32 >= 1 && kLocPerThread % kLocChunk32 == 0 && kLocmCells32 >= 1 && kLocPerThread % kLocmCells32 == 0, "whole chunks");
 
-// what the evaluation reads of one station for one event; 80 bytes, read with scalar loads
+// what the evaluation reads of one station for one event; 80 bytes, read with scalar loads.  tc32, ac32: tc and ac rounded to
+// float, for the single-precision forward
 struct __attribute__((aligned(16))) LocSta {
-    double sx, sy, sz, tc, ac, tob, tpr, aob, apr, pad;
+    double sx, sy, sz, tc, ac, tob, tpr, aob, apr;
+    float tc32, ac32;
 };
+static_assert(sizeof(LocSta) == 80, "nine doubles and two floats: the record kept its size");
 // per event: 1 / sum of precisions (time, amplitude) and sum_j (log_2pi_half + log stdv_j) (time, amplitude)
 struct __attribute__((aligned(16))) LocEv {
     double rpst, rpsa, ct, ca;
@@ -83,6 +102,7 @@ struct LocJob {
     double *vol;            // [nb][nz][ny][nx] or nullptr
     int S;
     double rbeta, katt;     // 1 / vs, pi f / (qs vs)
+    float rbeta32, katt32;  // the same, rounded to float
 };
 
 // a record at a wave-uniform address through the constant address space: scalar loads, as ld_const (the doubles travel in pairs)
@@ -91,8 +111,15 @@ __device__ __forceinline__ LocSta loc_ld_sta(const LocSta *p)
 {
     typedef const loc_f64x2 __attribute__((address_space(4))) *CP;
     const CP q = (CP)(unsigned long long)p;
-    const loc_f64x2 a = q[0], b = q[1], c = q[2], d = q[3], e = q[4];
-    return LocSta{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1], e[0], e[1]};
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    typedef const double __attribute__((address_space(4))) *CD;
+    typedef const f32x2 __attribute__((address_space(4))) *CF;
+    const loc_f64x2 a = q[0], b = q[1], c = q[2], d = q[3];
+    // (the last pair is a double and two floats, loaded as what they are: with the floats bit-cast out of a fifth pair's second
+    // double, the compiler narrowed the load to the FIRST double's low word -- offset 0x40, not 0x48, in the assembly)
+    const double apr = ((CD)q)[8];
+    const f32x2 c32 = ((CF)q)[9];
+    return LocSta{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1], apr, c32[0], c32[1]};
 }
 __device__ __forceinline__ LocEv loc_ld_ev(const LocEv *p)
 {
@@ -113,7 +140,8 @@ __global__ __launch_bounds__(256) void k_locate_pack(FwdDev f, int e0, int nb, c
     const size_t k = (size_t)(e0 + b) * f.S + j;
     LocSta r;
     r.sx = f.sx[j]; r.sy = f.sy[j]; r.sz = f.sz[j]; r.tc = tc[j]; r.ac = ac[j];
-    r.tob = f.t_obs[k]; r.tpr = f.t_prec[k]; r.aob = f.a_obs[k]; r.apr = f.a_prec[k]; r.pad = 0.0;
+    r.tob = f.t_obs[k]; r.tpr = f.t_prec[k]; r.aob = f.a_obs[k]; r.apr = f.a_prec[k];
+    r.tc32 = (float)r.tc; r.ac32 = (float)r.ac;
     sta[i] = r;
     if (j == 0) ev[b] = LocEv{f.rpsum_t[e0 + b], f.rpsum_a[e0 + b], lct[e0 + b], lca[e0 + b]};
 }
@@ -243,17 +271,21 @@ __device__ __forceinline__ void loc_tile_reduce(const LocGrid &g, const LocJob &
     }
 }
 
-struct __attribute__((aligned(16))) LocPair {
-    double a, b;
+// a pair of T: doubles, or the floats of the single-precision forward
+template <class T>
+struct __attribute__((aligned(2 * sizeof(T)))) LocPairT {
+    T a, b;
 };
-// D pairs at a wave-uniform, 16-byte aligned address through the constant address space: scalar loads
-template <int D>
-__device__ __forceinline__ void loc_ld_pairs(const LocPair *p, double (&a)[D], double (&b)[D])
+typedef LocPairT<double> LocPair;
+// D pairs at a wave-uniform address, aligned to the pair, through the constant address space: scalar loads
+template <class T, int D>
+__device__ __forceinline__ void loc_ld_pairs(const LocPairT<T> *p, T (&a)[D], T (&b)[D])
 {
-    typedef const loc_f64x2 __attribute__((address_space(4))) *CP;
+    typedef T vec2 __attribute__((ext_vector_type(2)));
+    typedef const vec2 __attribute__((address_space(4))) *CP;
     const CP q = (CP)(unsigned long long)p;
 #pragma unroll
-    for (int i = 0; i < D; ++i) { const loc_f64x2 v = q[i]; a[i] = v[0]; b[i] = v[1]; }
+    for (int i = 0; i < D; ++i) { const vec2 v = q[i]; a[i] = v[0]; b[i] = v[1]; }
 }
 
 // Cell c of a tile of ncell cells whose first x-row is iy0: its centre's x and y and its log prior in x and y from the event's
@@ -284,27 +316,49 @@ struct LocSums {
 // The station st at the cell (x, y, zc) under D structures (1 / vs, pi f / (qs vs), the station's corrections tc, ac), into the
 // sums: the distance and its logarithm once, then per structure the residuals (synthetic minus observation: cls_forward.f90:
 // 115-118, :201-204 as event_misfit) and their shifted sums.  first: station 0, which gives the shifts by the same operations
-// (its u is r - r, not a constant).  MODE: 1 travel times only, 2 amplitudes only, 3 both
-template <int MODE, int D>
-__device__ __forceinline__ void loc_station(const LocSta &st, const double (&tc)[D], const double (&ac)[D], bool first, double x, double y, double zc,
-                                            const double (&rbeta)[D], const double (&katt)[D], LocSums<D> &sm)
+// (its u is r - r, not a constant).  MODE: 1 travel times only, 2 amplitudes only, 3 both.
+//
+// F32, the single-precision forward (event_misfit<.., F32>'s rule at a cell centre; T is float, and the structure comes as its
+// float copies): the three coordinate differences are formed in fp64 and rounded to float; d = v_sqrt_f32(fma(dz, dz, fma(dy,
+// dy, dx dx))) and log2 d = v_log_f32(d), once per (cell, station); per structure the travel time fma(d, 1 / vs, -tc) and the
+// amplitude fma(-d, pi f / (qs vs), -fma(log2 d, ln 2, ac)) in float -- ln d is folded into the structure's own fma, as
+// event_misfit has it, and is never formed by itself --; each synthetic is promoted to double BEFORE the observation is
+// subtracted.  Observations, precisions, shifts and sums are fp64 in both forms: everything from `rt` and `ra` on is one text.
+template <bool F32>
+using loc_real = std::conditional_t<F32, float, double>;
+
+template <int MODE, int D, bool F32>
+__device__ __forceinline__ void loc_station(const LocSta &st, const loc_real<F32> (&tc)[D], const loc_real<F32> (&ac)[D], bool first, double x, double y,
+                                            double zc, const loc_real<F32> (&rbeta)[D], const loc_real<F32> (&katt)[D], LocSums<D> &sm)
 {
+    typedef loc_real<F32> T;
     constexpr bool UT = (MODE & 1) != 0, UA = (MODE & 2) != 0;
-    const double dx = x - st.sx, dy = y - st.sy, dz = zc - st.sz;
-    const double d = htm_sqrt(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)));
-    double nld = 0.0;
-    if constexpr (UA) nld = -htm_log(d);
+    // the distance; and for the amplitudes -ln d (fp64) or log2 d (F32)
+    T d, lg = 0;
+    if constexpr (F32) {
+        const float dx = (float)(x - st.sx), dy = (float)(y - st.sy), dz = (float)(zc - st.sz);
+        d = __builtin_amdgcn_sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)));
+        if constexpr (UA) lg = __builtin_amdgcn_logf(d);
+    } else {
+        const double dx = x - st.sx, dy = y - st.sy, dz = zc - st.sz;
+        d = htm_sqrt(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)));
+        if constexpr (UA) lg = -htm_log(d);
+    }
 #pragma unroll
     for (int q = 0; q < D; ++q) {
         if constexpr (UT) {
-            const double rt = __builtin_fma(d, rbeta[q], -tc[q]) - st.tob;
+            double rt;
+            if constexpr (F32) rt = (double)__builtin_fmaf(d, rbeta[q], -tc[q]) - st.tob;
+            else rt = __builtin_fma(d, rbeta[q], -tc[q]) - st.tob;
             if (first) sm.r0t[q] = rt;
             const double u = rt - sm.r0t[q], pu = st.tpr * u;
             sm.t1[q] += pu;
             sm.t2[q] = __builtin_fma(pu, u, sm.t2[q]);
         }
         if constexpr (UA) {
-            const double ra = (__builtin_fma(-d, katt[q], nld) - ac[q]) - st.aob;
+            double ra;
+            if constexpr (F32) ra = (double)__builtin_fmaf(-d, katt[q], -__builtin_fmaf(lg, 0.69314718055994531f, ac[q])) - st.aob;
+            else ra = (__builtin_fma(-d, katt[q], lg) - ac[q]) - st.aob;
             if (first) sm.r0a[q] = ra;
             const double u = ra - sm.r0a[q], pu = st.apr * u;
             sm.a1[q] += pu;
@@ -323,9 +377,11 @@ __device__ __forceinline__ double loc_term(const LocSums<D> &sm, const LocEv &ev
     return e;
 }
 
-template <int MODE>
+template <int MODE, bool F32>
 __global__ __launch_bounds__(256) void k_locate(LocGrid g, LocJob jb)
 {
+    typedef loc_real<F32> T;
+    constexpr int CHUNK = F32 ? kLocChunk32 : kLocChunk;
     __shared__ double s_w[kLocTile];
     const int t = threadIdx.x;
     const LocTile tl = loc_tile(g, jb);
@@ -334,33 +390,37 @@ __global__ __launch_bounds__(256) void k_locate(LocGrid g, LocJob jb)
     const LocSta *sta = jb.sta + (size_t)tl.b * jb.S;
     const LocEv ev = loc_ld_ev(jb.ev + tl.b);
     const double *prior = tl.prior;
-    const double rbeta[1] = {jb.rbeta}, katt[1] = {jb.katt};
+    T rbeta[1], katt[1];
+    if constexpr (F32) { rbeta[0] = jb.rbeta32; katt[0] = jb.katt32; }
+    else { rbeta[0] = jb.rbeta; katt[0] = jb.katt; }
 
     double lp[kLocPerThread];
     LocBest best{-__builtin_inf(), 0.0, INT_MAX};
 #pragma unroll
-    for (int ch = 0; ch < kLocPerThread / kLocChunk; ++ch) {
-        double x[kLocChunk], y[kLocChunk], pxy[kLocChunk];
-        LocSums<1> sm[kLocChunk];
-        if (ch * kLocChunk * kLocThreads >= ncell) {      // (block-uniform: no cell of this chunk exists)
+    for (int ch = 0; ch < kLocPerThread / CHUNK; ++ch) {
+        double x[CHUNK], y[CHUNK], pxy[CHUNK];
+        LocSums<1> sm[CHUNK];
+        if (ch * CHUNK * kLocThreads >= ncell) {      // (block-uniform: no cell of this chunk exists)
 #pragma unroll
-            for (int k = 0; k < kLocChunk; ++k) lp[ch * kLocChunk + k] = __builtin_nan("");
+            for (int k = 0; k < CHUNK; ++k) lp[ch * CHUNK + k] = __builtin_nan("");
             continue;
         }
 #pragma unroll
-        for (int k = 0; k < kLocChunk; ++k) {
-            loc_cell_xy(g, iy0, ncell, prior, t + kLocThreads * (ch * kLocChunk + k), x[k], y[k], pxy[k]);
+        for (int k = 0; k < CHUNK; ++k) {
+            loc_cell_xy(g, iy0, ncell, prior, t + kLocThreads * (ch * CHUNK + k), x[k], y[k], pxy[k]);
             sm[k].clear();
         }
         for (int j = 0; j < jb.S; ++j) {
             const LocSta st = loc_ld_sta(sta + j);
-            const double tc[1] = {st.tc}, ac[1] = {st.ac};
+            T tc[1], ac[1];
+            if constexpr (F32) { tc[0] = st.tc32; ac[0] = st.ac32; }
+            else { tc[0] = st.tc; ac[0] = st.ac; }
 #pragma unroll
-            for (int k = 0; k < kLocChunk; ++k) loc_station<MODE>(st, tc, ac, j == 0, x[k], y[k], zc, rbeta, katt, sm[k]);
+            for (int k = 0; k < CHUNK; ++k) loc_station<MODE, 1, F32>(st, tc, ac, j == 0, x[k], y[k], zc, rbeta, katt, sm[k]);
         }
 #pragma unroll
-        for (int k = 0; k < kLocChunk; ++k)
-            lp[ch * kLocChunk + k] = loc_cell_done(g, jb, tl, t + kLocThreads * (ch * kLocChunk + k), loc_term<MODE>(sm[k], ev, 0), pxy[k], best);
+        for (int k = 0; k < CHUNK; ++k)
+            lp[ch * CHUNK + k] = loc_cell_done(g, jb, tl, t + kLocThreads * (ch * CHUNK + k), loc_term<MODE>(sm[k], ev, 0), pxy[k], best);
     }
     loc_tile_reduce(g, jb, tl, best, s_w, [&](int k) { return lp[k]; });
 }
@@ -378,26 +438,29 @@ __global__ __launch_bounds__(256) void k_locate(LocGrid g, LocJob jb)
 //                        draws the station loop runs once.  Across the blocks a cell keeps (m, s), s = sum_k exp(l_k - m);
 //                        the cells' log posteriors go to the LDS array that holds the weights afterwards (a thread's own
 //                        words), so the loop over a thread's cells is a loop, not sixteen copies of the code.
+template <class T>          // double, or float: the table of the single-precision forward, every entry rounded to float
 struct LocDraws {
-    const LocPair *vq;      // [Kpad] {1 / vs, pi f / (qs vs)}
-    const LocPair *corr;    // [S][Kpad] {t_corr, a_corr}
-    int K, Kpad;            // draws; padded to a multiple of kLocDraws
+    const LocPairT<T> *vq;      // [Kpad] {1 / vs, pi f / (qs vs)}
+    const LocPairT<T> *corr;    // [S][Kpad] {t_corr, a_corr}
+    int K, Kpad;                // draws; padded to a multiple of kLocDraws
 };
 
+template <class T>
 __global__ __launch_bounds__(256) void k_locate_pack_draws(int S, int K, int Kpad, const double *tc, const double *ac, const double *rbeta,
-                                                           const double *katt, LocPair *corr, LocPair *vq)
+                                                           const double *katt, LocPairT<T> *corr, LocPairT<T> *vq)
 {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long)(S + 1) * Kpad) return;
     const int j = (int)(i / Kpad), k = min((int)(i - (long)j * Kpad), K - 1);
-    if (j == S) vq[i - (long)S * Kpad] = LocPair{rbeta[k], katt[k]};
-    else corr[i] = LocPair{tc[(size_t)k * S + j], ac[(size_t)k * S + j]};
+    if (j == S) vq[i - (long)S * Kpad] = LocPairT<T>{(T)rbeta[k], (T)katt[k]};
+    else corr[i] = LocPairT<T>{(T)tc[(size_t)k * S + j], (T)ac[(size_t)k * S + j]};
 }
 
-template <int MODE>
-__global__ __launch_bounds__(256) void k_locate_marginal(LocGrid g, LocJob jb, LocDraws dr)
+template <int MODE, bool F32>
+__global__ __launch_bounds__(256) void k_locate_marginal(LocGrid g, LocJob jb, LocDraws<loc_real<F32>> dr)
 {
-    constexpr int C = kLocmCells, D = kLocDraws;
+    typedef loc_real<F32> T;
+    constexpr int C = F32 ? kLocmCells32 : kLocmCells, D = kLocDraws;
     __shared__ double s_w[kLocTile];
     const int t = threadIdx.x;
     const LocTile tl = loc_tile(g, jb);
@@ -420,7 +483,7 @@ __global__ __launch_bounds__(256) void k_locate_marginal(LocGrid g, LocJob jb, L
         }
 #pragma unroll 1
         for (int k0 = 0; k0 < dr.K; k0 += D) {                  // (uniform) a block of draws
-            double rbeta[D], katt[D];
+            T rbeta[D], katt[D];
             loc_ld_pairs(dr.vq + k0, rbeta, katt);
             LocSums<D> sm[C];
 #pragma unroll
@@ -429,10 +492,10 @@ __global__ __launch_bounds__(256) void k_locate_marginal(LocGrid g, LocJob jb, L
             // over the others carries no selection per draw
             auto station = [&](int j, bool first) {
                 const LocSta st = loc_ld_sta(sta + j);
-                double tc[D], ac[D];
+                T tc[D], ac[D];
                 loc_ld_pairs(dr.corr + (size_t)j * dr.Kpad + k0, tc, ac);
 #pragma unroll
-                for (int k = 0; k < C; ++k) loc_station<MODE>(st, tc, ac, first, x[k], y[k], zc, rbeta, katt, sm[k]);
+                for (int k = 0; k < C; ++k) loc_station<MODE, D, F32>(st, tc, ac, first, x[k], y[k], zc, rbeta, katt, sm[k]);
             };
             station(0, true);
             for (int j = 1; j < jb.S; ++j) station(j, false);
@@ -499,9 +562,10 @@ __device__ __forceinline__ void loc_ms_merge(double &m, double &s, double mo, do
     m = hi; s = __builtin_fma(s_lo, e, s_hi);
 }
 
-template <int MODE>
-__global__ __launch_bounds__(256) void k_locate_draw_evidence(LocGrid g, LocJob jb, LocDraws dr)
+template <int MODE, bool F32>
+__global__ __launch_bounds__(256) void k_locate_draw_evidence(LocGrid g, LocJob jb, LocDraws<loc_real<F32>> dr)
 {
+    typedef loc_real<F32> T;
     constexpr int D = kLoceDraws;
     __shared__ double s_m[4][D], s_s[4][D];
     const int t = threadIdx.x, lane = t & 63;
@@ -516,7 +580,8 @@ __global__ __launch_bounds__(256) void k_locate_draw_evidence(LocGrid g, LocJob 
 
 #pragma unroll 1
     for (int k0 = 0; k0 < dr.K; k0 += D) {                      // (uniform) a block of draws
-        double rbeta[D], katt[D], m[D], s[D];
+        T rbeta[D], katt[D];
+        double m[D], s[D];
         loc_ld_pairs(dr.vq + k0, rbeta, katt);
 #pragma unroll
         for (int q = 0; q < D; ++q) { m[q] = -__builtin_inf(); s[q] = 0.0; }
@@ -529,9 +594,9 @@ __global__ __launch_bounds__(256) void k_locate_draw_evidence(LocGrid g, LocJob 
             sm.clear();
             auto station = [&](int j, bool first) {             // (as in k_locate_marginal)
                 const LocSta st = loc_ld_sta(sta + j);
-                double tc[D], ac[D];
+                T tc[D], ac[D];
                 loc_ld_pairs(dr.corr + (size_t)j * dr.Kpad + k0, tc, ac);
-                loc_station<MODE>(st, tc, ac, first, x, y, zc, rbeta, katt, sm);
+                loc_station<MODE, D, F32>(st, tc, ac, first, x, y, zc, rbeta, katt, sm);
             };
             station(0, true);
             for (int j = 1; j < jb.S; ++j) station(j, false);

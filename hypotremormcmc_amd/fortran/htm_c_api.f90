@@ -22,6 +22,7 @@ module htm_c_api
   public :: htm_forward_locate
   public :: htm_forward_locate_marginal
   public :: htm_forward_locate_draw_evidence
+  public :: htm_forward_locate_set_precision
   public :: htm_chains_checkpoint_size, htm_chains_checkpoint_save, htm_chains_checkpoint_load
 
   integer(c_size_t), parameter :: HTM_XCHG_HANDLE_BYTES = 64_c_size_t, HTM_COMM_ID_BYTES = 128_c_size_t
@@ -400,6 +401,14 @@ module htm_c_api
        type(c_ptr), value :: summary
        integer(c_int) :: rc
      end function htm_forward_locate_draw_evidence
+     !> the arithmetic of the three locate entry points on this handle (include/htm_hip.h): forward_fp32 = 1 forms the synthetics in
+     !> single precision, 0 (a new handle's setting) in double precision; independent of step 5's precision
+     function htm_forward_locate_set_precision(handle, forward_fp32) bind(C, name="htm_forward_locate_set_precision") result(rc)
+       import :: c_int, c_ptr
+       type(c_ptr), value :: handle
+       integer(c_int), value :: forward_fp32
+       integer(c_int) :: rc
+     end function htm_forward_locate_set_precision
      !> step-4 regressions (include/htm_hip.h): t, t_err, a, a_err (n_sta, n_win); out (6, n_win) = vs, b, t0, a0, cc_t, cc_a
      function htm_select_regress(device, n_sta, n_win, sta_x, sta_y, sta_z, z_guess, t, t_err, a, a_err, out) &
           & bind(C, name="htm_select_regress") result(rc)

@@ -47,6 +47,7 @@ class Forward:
         self.handle = h
         self.device = device
         self.forward_precision = "fp64"
+        self.locate_precision = "fp64"
         if str(forward_precision).lower() in ("fp32", "f32", "single"):
             self.set_precision("fp32")
 
@@ -70,6 +71,18 @@ class Forward:
         fp32 = str(precision).lower() in ("fp32", "f32", "single")
         check(self._lib.htm_forward_set_precision(self.handle, int(fp32)))
         self.forward_precision = "fp32" if fp32 else "fp64"
+
+    def set_locate_precision(self, precision: str):
+        """The arithmetic of `locate.locate`, `locate_marginal` and `draw_evidence` on this object, and of nothing else: "fp32"
+        forms the synthetic travel time and amplitude of a (cell, station) in single precision and keeps observations, sums
+        and everything behind a cell's term fp64 (pinned by tests/locate_fp32_restatement.py); "fp64", a new
+        object's setting, is the arithmetic they have without it, bit for bit.  Independent of `set_precision`, which is step
+        5's; any number of stations.  Remembered in `locate_precision`."""
+        p = str(precision).lower()
+        if p not in ("fp32", "fp64"):
+            raise ValueError(f"locate precision {precision!r}: need 'fp32' or 'fp64'")
+        check(self._lib.htm_forward_locate_set_precision(self.handle, int(p == "fp32")))
+        self.locate_precision = p
 
     def obs_pack_bytes(self) -> int:
         """Bytes of the packed per-event observation records (the specialised chain master's; 0: none were built)."""

@@ -4,6 +4,7 @@ grid -- no MCMC, any number of windows (kernels in hypotremorm
 
     python -m hypotremormcmc_amd.locate <parameter file> --cell DX [DY DZ] [--bounds x0 x1 y0 y1 z0 z1] [--structure DIR]
                                         [--windows FILE] [--flat-prior] [--volume-of WIN] [--draws K [--draw-weights]]
+                                        [--precision fp64|fp32]
 
 run in the data directory (station file, opt_data.NNNNNN.dat).  --structure DIR holds `uniform_structure.stat` and
 `station_corrections.stat` of the calibration run (default: the parameter file's directory); --windows FILE lists the window
@@ -32,10 +33,17 @@ largest weight, the stacked record number of the draw that has it, the mixture's
 line per draw: its record number, vs, qs, and its joint weight over all windows -- the windows are independent given the
 structure, so the log weights add: which draws of the calibration posterior the located windows prefer), and adds one line to
 the summary.  Without --draw-weights nothing is written or printed that was not before.
+
+--precision fp32 evaluates everything that the invocation evaluates with the single-precision forward: the
+synthetic travel time and amplitude of a (cell, station) in fp32, the observations, every sum and everything behind a cell's
+term in fp64.  File names and layouts are unchanged; the summary gains one line that names the precision.  The default is
+fp64, and without the option nothing is written or printed that was not before.  The parameter file's `forward_precision` and
+HTM_FORWARD_PRECISION are step 5's and do not switch this program.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import os
 import sys
 
@@ -55,13 +63,29 @@ BEST_HEADER = ("# window ID, best cell's centre x y z, log posterior there, log-
                "posterior mean x y z, 1: the best cell lies on a face of the box")
 
 
-def locate(fwd, t_corr, vs, a_corr, qs, grid, prior=None, marginals=True, volume=False):
+@contextlib.contextmanager
+def _precision(fwd, precision):
+    """`precision` None: the Forward's locate precision as it is; "fp32" or "fp64": that one inside the block, and the
+    previous setting back after it"""
+    if precision is None:
+        yield
+        return
+    before = fwd.locate_precision
+    fwd.set_locate_precision(precision)
+    try:
+        yield
+    finally:
+        fwd.set_locate_precision(before)
+
+
+def locate(fwd, t_corr, vs, a_corr, qs, grid, prior=None, marginals=True, volume=False, precision=None):
     """The location posterior of every event of the Forward `fwd` on `grid` = x0, dx, nx, y0, dy, ny, z0, dz, nz under the fixed
     structure t_corr [n_sta], vs, a_corr [n_sta], qs; prior [n_events][5] = mu_x, mu_y, w_xy, z0, w_z or None (flat).  Returns
     a dict: index [E] (int64; the best cell's ix + nx (iy + ny iz), -1: every cell excluded), best [E][3] its centre, lp and
     ell [E] the log posterior and the log-likelihood term there, log_evidence [E], mean [E][3], cov [E][3][3], loc [E][16]
     the library's record, marg_x / marg_y / marg_z [E][n] (None without `marginals`), vol [E][nz][ny][nx] (None without
-    `volume`)."""
+    `volume`).  precision: None, the Forward's own setting (Forward.set_locate_precision; "fp64" unless it was changed), or
+    "fp32" / "fp64" for this call, the previous setting put back after it."""
     g, (nx, ny, nz) = _grid(grid)
     E, S = fwd.n_events, fwd.n_sta
     tc = np.ascontiguousarray(np.asarray(t_corr, dtype=np.float64).reshape(-1))
@@ -70,27 +94,30 @@ def locate(fwd, t_corr, vs, a_corr, qs, grid, prior=None, marginals=True, volume
         raise ValueError(f"t_corr and a_corr have {tc.size} and {ac.size} values: need one per station ({S})")
     pr = _prior_array(prior, E)
     loc, marg, vol = _outputs(E, nx, ny, nz, marginals, volume)
-    _lib.check(_lib.load().htm_forward_locate(fwd.handle, _lib.ptr(tc), float(vs), _lib.ptr(ac), float(qs), _lib.ptr(g), _lib.ptr(pr),
-                                              _lib.ptr(loc), _lib.ptr(marg), _lib.ptr(vol)))
+    with _precision(fwd, precision):
+        _lib.check(_lib.load().htm_forward_locate(fwd.handle, _lib.ptr(tc), float(vs), _lib.ptr(ac), float(qs), _lib.ptr(g), _lib.ptr(pr),
+                                                  _lib.ptr(loc), _lib.ptr(marg), _lib.ptr(vol)))
     return _result(loc, marg, vol, nx, ny)
 
 
-def locate_marginal(fwd, t_corr, vs, a_corr, qs, grid, prior=None, marginals=True, volume=False):
+def locate_marginal(fwd, t_corr, vs, a_corr, qs, grid, prior=None, marginals=True, volume=False, precision=None):
     """`locate` with the structure marginalised over K draws of it: t_corr [K][n_sta], vs [K], a_corr [K][n_sta], qs [K].  A
     cell's log-likelihood term is log((1 / K) sum_k exp(l_k)), l_k the term `locate` takes under draw k; one kernel evaluates
-    all draws (htm_forward_locate_marginal).  Returns the dict of `locate`; K = 1 gives its very bits."""
+    all draws (htm_forward_locate_marginal).  Returns the dict of `locate`; K = 1 gives its very bits, in
+    either precision (`precision`: as `locate`'s)."""
     g, (nx, ny, nz) = _grid(grid)
     E, S = fwd.n_events, fwd.n_sta
     K, tc, v, ac, q = _draws(t_corr, vs, a_corr, qs, S)
     pr = _prior_array(prior, E)
     loc, marg, vol = _outputs(E, nx, ny, nz, marginals, volume)
-    _lib.check(_lib.load().htm_forward_locate_marginal(fwd.handle, K, _lib.ptr(tc), _lib.ptr(v), _lib.ptr(ac), _lib.ptr(q), _lib.ptr(g),
-                                                       _lib.ptr(pr), _lib.ptr(loc), _lib.ptr(marg), _lib.ptr(vol)))
+    with _precision(fwd, precision):
+        _lib.check(_lib.load().htm_forward_locate_marginal(fwd.handle, K, _lib.ptr(tc), _lib.ptr(v), _lib.ptr(ac), _lib.ptr(q), _lib.ptr(g),
+                                                           _lib.ptr(pr), _lib.ptr(loc), _lib.ptr(marg), _lib.ptr(vol)))
     return _result(loc, marg, vol, nx, ny)
 
 
-def draw_evidence(fwd, t_corr, vs, a_corr, qs, grid, prior=None):
-    """The inputs of `locate_marginal`.  Returns a dict: log_z [E][K], the log evidence `locate` gives under draw k alone
+def draw_evidence(fwd, t_corr, vs, a_corr, qs, grid, prior=None, precision=None):
+    """The inputs of `locate_marginal`, `precision` included.  Returns a dict: log_z [E][K], the log evidence `locate` gives under draw k alone
     (-inf: no cell under that draw); with the normalised weights w_k = exp(log_z_k) / sum exp(log_z): n_eff [E] = 1 / sum_k
     w_k^2, w_max [E], k_max [E] (int64; the lowest index of the largest weight, -1 for a window without a cell, whose n_eff,
     w_max and log_evidence are NaN), log_evidence [E] = log((1 / K) sum_k exp(log_z_k)), `locate_marginal`'s
@@ -101,8 +128,9 @@ def draw_evidence(fwd, t_corr, vs, a_corr, qs, grid, prior=None):
     pr = _prior_array(prior, E)
     log_z = np.empty((E, K))
     summ = np.empty((E, 4))
-    _lib.check(_lib.load().htm_forward_locate_draw_evidence(fwd.handle, K, _lib.ptr(tc), _lib.ptr(v), _lib.ptr(ac), _lib.ptr(q), _lib.ptr(g),
-                                                            _lib.ptr(pr), _lib.ptr(log_z), _lib.ptr(summ)))
+    with _precision(fwd, precision):
+        _lib.check(_lib.load().htm_forward_locate_draw_evidence(fwd.handle, K, _lib.ptr(tc), _lib.ptr(v), _lib.ptr(ac), _lib.ptr(q), _lib.ptr(g),
+                                                                _lib.ptr(pr), _lib.ptr(log_z), _lib.ptr(summ)))
     return {"log_z": log_z, "n_eff": summ[:, 0].copy(), "w_max": summ[:, 1].copy(), "k_max": summ[:, 2].astype(np.int64),
             "log_evidence": summ[:, 3].copy()}
 
@@ -354,12 +382,13 @@ def draws_summary_text(ev, n_draws) -> str:
             f"{int((ev['w_max'] > 0.5).sum())} windows where one draw outweighs all the others (w_max > 0.5: their intervals are one structure's)\n")
 
 
-def summary_text(res, grid, n_draws=None) -> str:
+def summary_text(res, grid, n_draws=None, precision="fp64") -> str:
     n = len(res["index"])
     how = "" if n_draws is None else f", the structure marginalised over {n_draws} draws"
+    prec = "" if precision == "fp64" else f"forward precision: {precision} (the synthetics in single precision, every sum in fp64)\n"
     return (f"{n} windows located on {' x '.join(str(c) for c in grid_counts(grid))} cells{how}\n"
             f"{int(on_face(res['index'], grid).sum())} with the best cell on a face of the box (not resolved by this grid), "
-            f"{int((res['index'] < 0).sum())} without an included cell\n")
+            f"{int((res['index'] < 0).sum())} without an included cell\n" + prec)
 
 
 def main(argv=None):
@@ -374,6 +403,8 @@ def main(argv=None):
                     "in --structure DIR; writes hypo_grid_marginal.*")
     ap.add_argument("--draw-weights", action="store_true", help="with --draws: also write what every draw weighs per window and their "
                     "effective number (hypo_grid_marginal.draws.dat) and the draws' joint weights (hypo_grid_marginal.structure.dat)")
+    ap.add_argument("--precision", choices=("fp64", "fp32"), default="fp64", help="fp32: the synthetic travel times and amplitudes in single "
+                    "precision, every sum in fp64 (default fp64)")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
     if args.draws is not None and args.draws < 1:
         ap.error(f"--draws {args.draws}: need at least one draw")
@@ -397,6 +428,7 @@ def main(argv=None):
         fwd = Forward(par.n_stations, len(ids), par.sta_x, par.sta_y, par.sta_z, obs, use_amp=par.get_use_amp(), use_time=par.get_use_time(),
                       device=device)
         try:
+            fwd.set_locate_precision(args.precision)
             prior = None if args.flat_prior else step5_prior(par, obs)
             res = evaluate(fwd, t_corr, vs, a_corr, qs, grid, prior=prior, volume=volume)
             return (res, draw_evidence(fwd, t_corr, vs, a_corr, qs, grid, prior=prior)) if weights else res
@@ -415,7 +447,7 @@ def main(argv=None):
         one = run([args.volume_of], True)
         with open(os.path.join(work, stem + ".%d.vol.dat" % args.volume_of), "w") as fh:
             fh.write(volume_text(one["vol"][0], grid))
-    sys.stdout.write(summary_text(res, grid, args.draws))
+    sys.stdout.write(summary_text(res, grid, args.draws, args.precision))
     if ev is not None:
         with open(os.path.join(work, stem + ".draws.dat"), "w") as fh:
             fh.write(draws_text(win_id, ev, records))

@@ -136,7 +136,8 @@ int htm_forward_time_full_batch_dev(htm_forward *h, int n_models, const double *
 /* Location posteriors on a grid under a FIXED structure.  With t_corr, vs, a_corr, qs fixed the
  * log-likelihood of :268-303 is a sum of independent per-event terms; the term l of every event of the handle is taken at
  * every cell centre of grid9 (the map grid, above; and nx ny nz <= 2^31 - 1).  The handle's stations, observations, use_time / use_amp and missing-data
- * rule are used as they stand, always through its fp64 arrays (whatever htm_forward_set_precision says).  t_corr, a_corr
+ * rule are used as they stand, always through its fp64 arrays (whatever htm_forward_set_precision says; the fp32 evaluation of these entry points is
+ * htm_forward_locate_set_precision's, below).  t_corr, a_corr
  * [n_sta], host pointers.  prior5 [n_events][5] = {mu_x, mu_y, w_xy, z0, w_z} or NULL (flat prior): the log prior of a cell is
  * the sum of the normalised Gaussian log densities N(mu_x, w_xy), N(mu_y, w_xy) in x and y and of the normalised depth prior
  * of src/cls_model.f90:178-185, log(z - z0) - 2 log w_z - (z - z0)^2 / (2 w_z^2) for z > z0 and -inf otherwise.  The log
@@ -194,6 +195,28 @@ int htm_forward_locate_marginal(htm_forward *h, int n_draws, const double *t_cor
 int htm_forward_locate_draw_evidence(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr,
                                      const double *qs, const double *grid9, const double *prior5, double *log_z,
                                      double *summary);
+
+/* SINGLE-PRECISION FORWARD of the three entry points above: forward_fp32 = 1 makes htm_forward_locate,
+ * htm_forward_locate_marginal and htm_forward_locate_draw_evidence on this handle, and nothing else, form the synthetic travel
+ * time and amplitude of a (cell, station) in fp32; 0 (a new handle's setting) is the fp64 arithmetic, bit for bit in every
+ * output what a handle gives on which this was never called.  It is independent of htm_forward_set_precision, which governs
+ * step 5's kernels only and leaves these entry points alone; there is no limit on n_sta.  The rule (event_misfit's fp32 rule
+ * at a cell centre):
+ *   - the three coordinate differences, cell centre minus station, are formed in fp64 and then rounded to float;
+ *   - d = sqrt(fma(dz, dz, fma(dy, dy, dx dx))) in float, the hardware's v_sqrt_f32;
+ *   - log2 d by the hardware's v_log_f32, once per (cell, station) whatever the number of draws;
+ *   - per structure or draw, in float, from the float copies (round to nearest) of 1 / vs, pi f / (qs vs), t_corr and a_corr:
+ *     the travel time fma(d, 1 / vs, -t_corr) and the amplitude fma(-d, pi f / (qs vs), -fma(log2 d, (float)ln 2, a_corr)) --
+ *     ln d is folded into the draw's own fma and never formed by itself;
+ *   - each synthetic is promoted to double BEFORE the observation is subtracted.
+ * The observations and precisions (NOT rounded to float, unlike step 5's mode), the first station's shift, the shifted sums,
+ * a cell's term and everything behind it -- prior, best cell, weights, reduces, marginals, moments, evidences, the
+ * log-mean-exp over draws -- stay fp64.  Excluded cells keep their meaning (a centre on a station with amplitudes in use:
+ * log2 0 = -inf, the term NaN); one draw still gives htm_forward_locate's very bits; two calls give the same bits, whatever
+ * the batching.  A cell's term differs from the fp64 one by a few 2^-24 of sum_j precision_j |demeaned residual_j| scale_j,
+ * scale_j the magnitude of the terms of station j's synthetic (tests/locate_fp32_restatement.py states and pins the bound).
+ * NULL handle, or a value other than 0 or 1: HTM_EINVAL, and the setting stays as it was. */
+int htm_forward_locate_set_precision(htm_forward *h, int forward_fp32);
 
 /* ------------------------------------------------------------------------------------------------
  * Device-resident chains: `type mcmc` x n_chains inside `type parallel`

@@ -13,6 +13,7 @@ The yardstick is timed with HIP events on the handle's stream (htm_forward_time_
 mean of 20 calls) on a slice of the grid -- 64 positions are one call, and every call costs the same.
 
     python tools/bench_locate.py [--windows 1000] [--stations 64] [--big-windows 1000] [--reps 3] [--use both|time|amp]
+                                 [--precision fp64|fp32]   # the arithmetic of htm_forward_locate (the yardstick stays fp64)
                                  [--lib NAME=PATH ...]     # A/B: the same with other builds of the library (HTM_LIB)
     python tools/bench_locate.py --one         # the measurement in this process
     python tools/bench_locate.py --once        # one call on the large grid and nothing else, for a kernel trace
@@ -47,7 +48,7 @@ def measure(args):
         fwd.close()
         assert (res["index"] >= 0).all()
         t = float(np.median(times))
-        print(f"htm_forward_locate   {n:5d} windows x {S} stations, {name} cells: {t * 1e3:10.2f} ms per call "
+        print(f"htm_forward_locate{job.tag}   {n:5d} windows x {S} stations, {name} cells: {t * 1e3:10.2f} ms per call "
               f"(min {min(times) * 1e3:.2f}, max {max(times) * 1e3:.2f}) = {n * cells / t:.3e} (window, position)/s "
               f"= {n * cells * S / t:.3e} station terms/s", flush=True)
         return n * cells / t

@@ -12,6 +12,7 @@ the size that is timed.  Every K is a process of its own under its own `timeout`
 go to the screen and, appended, to --out (the job and the driver: tools/locate_bench_job.py).
 
     python tools/bench_locate_draws.py [--windows 1000] [--stations 64] [--reps 3] [--draws 8 64] [--use both|time|amp]
+                                       [--precision fp64|fp32]   # the arithmetic of all three
                                        [--lib NAME=PATH ...]     # A/B: the same with other builds of the library (HTM_LIB)
     python tools/bench_locate_draws.py --one K                   # one K in this process
     python tools/bench_locate_draws.py --once K                  # one call of the new entry point and nothing else, for a kernel trace
@@ -57,7 +58,7 @@ def one(args, K):
         assert np.isfinite(res).all()
         times[name], results[name] = ts, res
         t = float(np.median(ts))
-        print(f"{name:34s} K = {K:3d}, {E} windows x {S} stations, {bj.GRID_NAME} cells: {t * 1e3:10.2f} ms (min {min(ts) * 1e3:.2f}, max {max(ts) * 1e3:.2f}) "
+        print(f"{name + job.tag:34s} K = {K:3d}, {E} windows x {S} stations, {bj.GRID_NAME} cells: {t * 1e3:10.2f} ms (min {min(ts) * 1e3:.2f}, max {max(ts) * 1e3:.2f}) "
               f"= {E * cells * K / t:.3e} (window, position, draw)/s", flush=True)
     fwd.close()
     new, marg, old = (times[n] for n in names)

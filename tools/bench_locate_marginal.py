@@ -11,6 +11,7 @@ come back): the median, with the fastest and the slowest.  Every K is a process 
 that fails ends the run.  The lines go to the screen and, appended, to --out (the job and the driver: tools/locate_bench_job.py).
 
     python tools/bench_locate_marginal.py [--windows 1000] [--stations 64] [--reps 3] [--draws 1 8 64] [--use both|time|amp]
+                                          [--precision fp64|fp32]   # the arithmetic of both sides
                                           [--lib NAME=PATH ...]     # A/B: the same with other builds of the library (HTM_LIB)
     python tools/bench_locate_marginal.py --one K                   # one K in this process
     python tools/bench_locate_marginal.py --once K                  # one marginal call and nothing else, for a kernel trace
@@ -53,7 +54,7 @@ def one(args, K):
         assert (res["index"] >= 0).all()
         times[name] = ts
         t = float(np.median(ts))
-        print(f"{name:30s} K = {K:3d}, {E} windows x {S} stations, {bj.GRID_NAME} cells: {t * 1e3:10.2f} ms (min {min(ts) * 1e3:.2f}, max {max(ts) * 1e3:.2f}) "
+        print(f"{name + job.tag:30s} K = {K:3d}, {E} windows x {S} stations, {bj.GRID_NAME} cells: {t * 1e3:10.2f} ms (min {min(ts) * 1e3:.2f}, max {max(ts) * 1e3:.2f}) "
               f"= {E * cells * K / t:.3e} (window, position, draw)/s", flush=True)
     fwd.close()
     new, old = times["htm_forward_locate_marginal"], times[f"{K} x htm_forward_locate"]

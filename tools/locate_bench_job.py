@@ -26,6 +26,8 @@ class Job:
         from hypotremormcmc_amd import synth
 
         self.use = USE[args.use]
+        self.precision = args.precision              # of the three locate entry points (Forward.set_locate_precision)
+        self.tag = "" if args.precision == "fp64" else f" [{args.precision}]"
         E, S = self.E, self.S = args.windows, args.stations
         self.data = synth.make_synthetic(E, S, 3)
         self.prior = np.stack([np.zeros(E), np.zeros(E), np.full(E, 30.0), np.zeros(E), np.full(E, 10.0)], axis=1)
@@ -46,8 +48,10 @@ class Job:
         from hypotremormcmc_amd.forward import Forward, ObsArrays
 
         d = self.data
-        return Forward(self.S, n, d.sta_x, d.sta_y, d.sta_z, ObsArrays(d.t_obs[:n], d.t_stdv[:n], d.a_obs[:n], d.a_stdv[:n]),
-                       use_time=self.use[0], use_amp=self.use[1])
+        fwd = Forward(self.S, n, d.sta_x, d.sta_y, d.sta_z, ObsArrays(d.t_obs[:n], d.t_stdv[:n], d.a_obs[:n], d.a_stdv[:n]),
+                      use_time=self.use[0], use_amp=self.use[1])
+        fwd.set_locate_precision(self.precision)
+        return fwd
 
 
 def timed(f, reps):
@@ -68,6 +72,8 @@ def add_arguments(ap, draws=None):
     if draws:
         ap.add_argument("--draws", type=int, nargs="+", default=draws)
     ap.add_argument("--use", choices=list(USE), default="both", help="the data types the Forward uses (the kernels' MODE)")
+    ap.add_argument("--precision", choices=("fp64", "fp32"), default="fp64", help="the arithmetic of the locate entry points (DESIGN.md 3.13); "
+                    "fp32 is named in every line")
     ap.add_argument("--lib", action="append", default=[], metavar="NAME=PATH", help="also run with this build of the library")
 
 
@@ -78,6 +84,8 @@ def drive(script, args, steps, out=None):
     shared = ["--windows", str(args.windows), "--stations", str(args.stations), "--reps", str(args.reps)]
     if args.use != "both":
         shared += ["--use", args.use]
+    if args.precision != "fp64":
+        shared += ["--precision", args.precision]
     fh = open(out, "a") if out else None
 
     def say(text):
@@ -89,7 +97,8 @@ def drive(script, args, steps, out=None):
 
     try:
         for name, path in builds:
-            say(f"# {name}" + (f" ({path})" if path else "") + (f", --use {args.use}" if args.use != "both" else "") + "\n")
+            say(f"# {name}" + (f" ({path})" if path else "") + (f", --use {args.use}" if args.use != "both" else "")
+                + (f", --precision {args.precision}" if args.precision != "fp64" else "") + "\n")
             env = dict(os.environ)
             if path:
                 env["HTM_LIB"] = os.path.abspath(path)
