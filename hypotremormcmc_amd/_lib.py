@@ -86,6 +86,7 @@ SIGNATURES = {
     "htm_forward_locate_marginal": (C.c_int, [vp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, dp]),
     "htm_forward_locate_draw_evidence": (C.c_int, [vp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp]),
     "htm_forward_locate_set_precision": (C.c_int, [vp, C.c_int]),
+    "htm_forward_locate_stack": (C.c_int, [vp, C.c_int, dp, dp, dp, dp, dp, dp, ip, C.c_int, dp, dp, dp, dp, dp, dp, dp]),
     "htm_chains_create": (C.c_int, [vp, C.POINTER(ChainsInit), C.POINTER(vp)]),
     "htm_chains_destroy": (C.c_int, [vp]),
     "htm_chains_run": (C.c_int, [vp, C.c_int]),

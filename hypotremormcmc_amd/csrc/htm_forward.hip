@@ -525,10 +525,19 @@ int htm_forward_time_full_batch_dev(htm_forward *h, int n_models, const double *
 // htm_forward_locate_draw_evidence instead (loc, marg, vol NULL): k_locate_draw_evidence, k_locate_draw_combine, log_z [E][n_draws]
 // and summary [E][4] or NULL.  F32: the single-precision forward of htm_forward_locate_set_precision -- the kernels' F32
 // instantiations, and the draws' table in floats.
+// stk: htm_forward_locate_stack -- the batch volume is always on the device and is not downloaded; after a batch's
+// k_locate_combine k_locate_stack adds the batch's windows to the layers' stacks, after the last batch k_locate_stack_project
+// makes the three maps.  loc may then be NULL.
+struct LocStackOut {
+    const int *layer;       // [E] or NULL: every window in layer 0
+    int n_layer;
+    double *xy, *xz, *yz, *stack, *tally;      // host; stack may be NULL
+};
 extern "C++" {      // (a template, among the C entry points)
 template <bool F32>
 static int locate_run_as(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr, const double *qs,
-                         const double *grid9, const double *prior5, double *loc, double *marg, double *vol, double *log_z, double *summary)
+                         const double *grid9, const double *prior5, double *loc, double *marg, double *vol, double *log_z, double *summary,
+                         const LocStackOut *stk)
 {
     typedef LocPairT<loc_real<F32>> Pair;
     const bool draws = n_draws > 0, evid = log_z != nullptr;
@@ -557,15 +566,27 @@ static int locate_run_as(htm_forward *h, int n_draws, const double *t_corr, cons
     const int K = n_draws, Kpad = (K + kLocDraws - 1) / kLocDraws * kLocDraws;
     // (the draws' evidences: a pair per tile and draw of the padded table, log_z and the summary, the prior's tables)
     const double per_event = sizeof(double) * (evid ? (double)n_tiles * Kpad * 2.0 + K + 4.0 + nm
-                                                    : (double)n_tiles * g.stride + (vol ? (double)cells : 0.0) + 2.0 * nm + 16.0) +
+                                                    : (double)n_tiles * g.stride + (vol || stk ? (double)cells : 0.0) + 2.0 * nm + 16.0 + (stk ? 1.0 : 0.0)) +
                              sizeof(LocSta) * (double)S + sizeof(LocEv);
     const double table = draws ? sizeof(Pair) * ((double)S + 1.0) * Kpad + sizeof(double) * (2.0 * S + 2.0) * K : 0.0;
     if (draws && table + per_event > mb * 1048576.0)
         return fail(HTM_EINVAL, "HTM_LOCATE_MB = %g: the table of %d draws (%.0f bytes) and one event (%.0f bytes) do not fit", mb, K, table, per_event);
+    // the stack: every layer's volume, its three maps and its tally, and the windows' layers, once per call
+    const long map_cells = (long)n[0] * n[1] + (long)n[0] * n[2] + (long)n[1] * n[2];
+    double fixed = 0.0;
+    if (stk) {
+        const double n_out = (double)stk->n_layer * ((double)cells + (double)map_cells + 2.0);
+        if (n_out > (double)INT_MAX)
+            return fail(HTM_EINVAL, "%d layers of %ld + %ld cells and a tally: more than 2^31 - 1 doubles", stk->n_layer, cells, map_cells);
+        fixed = sizeof(double) * n_out + (stk->layer ? sizeof(int) * (double)E : 0.0);
+        if (fixed + table + per_event > mb * 1048576.0)
+            return fail(HTM_EINVAL, "HTM_LOCATE_MB = %g: the stack of %d layers (%.0f bytes)%s and one event (%.0f bytes) do not fit", mb, stk->n_layer, fixed,
+                        draws ? ", the table of the draws" : "", per_event);
+    }
     long nb = std::min<long>(E, 65535L);
     nb = std::min(nb, kMaxWorkItems / (n_tiles * kLocThreads));
     nb = std::min(nb, (kMaxWorkItems - 256) / S);
-    nb = std::min(nb, (long)std::min((mb * 1048576.0 - table) / per_event, 65535.0));
+    nb = std::min(nb, (long)std::min((mb * 1048576.0 - table - fixed) / per_event, 65535.0));
     nb = std::max(nb, 1L);
 
     HIPCHK(hipSetDevice(h->device));
@@ -582,7 +603,18 @@ static int locate_run_as(htm_forward *h, int n_draws, const double *t_corr, cons
                (rc = pool.alloc(&d_marg, (size_t)nb * nm)))
         return rc;
     if (prior5 && (rc = pool.alloc(&d_prior, (size_t)nb * nm))) return rc;
-    if (vol && (rc = pool.alloc(&d_vol, (size_t)nb * cells))) return rc;
+    if ((vol || stk) && (rc = pool.alloc(&d_vol, (size_t)nb * cells))) return rc;
+    double *d_w = nullptr, *d_stack = nullptr, *d_xy = nullptr, *d_xz = nullptr, *d_yz = nullptr, *d_tally = nullptr;
+    int *d_layer = nullptr;
+    const size_t nl = stk ? (size_t)stk->n_layer : 0;
+    if (stk) {
+        if ((rc = pool.alloc(&d_w, (size_t)nb)) || (rc = pool.alloc(&d_stack, nl * cells)) || (rc = pool.alloc(&d_xy, nl * n[0] * n[1])) ||
+            (rc = pool.alloc(&d_xz, nl * n[0] * n[2])) || (rc = pool.alloc(&d_yz, nl * n[1] * n[2])) || (rc = pool.alloc(&d_tally, nl * 2)))
+            return rc;
+        if (stk->layer && (rc = pool.upload(&d_layer, stk->layer, (size_t)E))) return rc;
+        HIPCHK(hipMemsetAsync(d_stack, 0, nl * cells * sizeof(double), h->stream));
+        HIPCHK(hipMemsetAsync(d_tally, 0, nl * 2 * sizeof(double), h->stream));
+    }
 
     LocJob jb{};
     jb.sta = d_sta; jb.ev = d_ev; jb.prior = d_prior; jb.part = d_part; jb.vol = d_vol; jb.S = S;
@@ -640,7 +672,10 @@ static int locate_run_as(htm_forward *h, int n_draws, const double *t_corr, cons
         if (evid)
             hipLaunchKernelGGL(k_locate_draw_combine, dim3((unsigned)m), dim3(256), 0, h->stream, (int)n_tiles, K, Kpad, d_part, log_cell, d_logz, d_sum);
         else
-            hipLaunchKernelGGL(k_locate_combine, dim3((unsigned)m), dim3(256), 0, h->stream, g, d_part, log_cell, d_loc, d_marg);
+            hipLaunchKernelGGL(k_locate_combine, dim3((unsigned)m), dim3(256), 0, h->stream, g, d_part, log_cell, d_loc, d_marg, d_w);
+        if (stk)
+            hipLaunchKernelGGL(k_locate_stack, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->stream, cells, (int)m, (int)e0, d_vol, d_loc, d_w, d_layer,
+                               stk->n_layer, d_stack, d_tally);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(h->stream));
         if (evid) {
@@ -648,9 +683,20 @@ static int locate_run_as(htm_forward *h, int n_draws, const double *t_corr, cons
             if (summary && (rc = pool.download(summary + (size_t)e0 * 4, d_sum, (size_t)m * 4, "the draws' summary's"))) return rc;
             continue;
         }
-        if ((rc = pool.download(loc + (size_t)e0 * 16, d_loc, (size_t)m * 16, "the locations'"))) return rc;
+        if (loc && (rc = pool.download(loc + (size_t)e0 * 16, d_loc, (size_t)m * 16, "the locations'"))) return rc;
         if (marg && (rc = pool.download(marg + (size_t)e0 * nm, d_marg, (size_t)m * nm, "the marginals'"))) return rc;
         if (vol && (rc = pool.download(vol + (size_t)e0 * cells, d_vol, (size_t)m * cells, "the volume's"))) return rc;
+    }
+    if (stk) {
+        const long most = std::max((long)nl * std::max((long)n[0] * n[1], (long)n[0] * n[2]), 64L * (long)nl * n[1] * n[2]);
+        const unsigned blocks = (unsigned)std::min((most + 255) / 256, 1L << 20);
+        hipLaunchKernelGGL(k_locate_stack_project, dim3(blocks), dim3(256), 0, h->stream, g, stk->n_layer, d_stack, d_xy, d_xz, d_yz);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if ((rc = pool.download(stk->xy, d_xy, nl * n[0] * n[1], "the xy map's")) || (rc = pool.download(stk->xz, d_xz, nl * n[0] * n[2], "the xz map's")) ||
+            (rc = pool.download(stk->yz, d_yz, nl * n[1] * n[2], "the yz map's")) || (rc = pool.download(stk->tally, d_tally, nl * 2, "the tally's")))
+            return rc;
+        if (stk->stack && (rc = pool.download(stk->stack, d_stack, nl * cells, "the stack's"))) return rc;
     }
     return HTM_OK;
 }
@@ -658,10 +704,10 @@ static int locate_run_as(htm_forward *h, int n_draws, const double *t_corr, cons
 
 static int locate_run(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr, const double *qs,
                       const double *grid9, const double *prior5, double *loc, double *marg, double *vol, double *log_z = nullptr,
-                      double *summary = nullptr)
+                      double *summary = nullptr, const LocStackOut *stk = nullptr)
 {
-    return h->loc_fp32 ? locate_run_as<true>(h, n_draws, t_corr, vs, a_corr, qs, grid9, prior5, loc, marg, vol, log_z, summary)
-                       : locate_run_as<false>(h, n_draws, t_corr, vs, a_corr, qs, grid9, prior5, loc, marg, vol, log_z, summary);
+    return h->loc_fp32 ? locate_run_as<true>(h, n_draws, t_corr, vs, a_corr, qs, grid9, prior5, loc, marg, vol, log_z, summary, stk)
+                       : locate_run_as<false>(h, n_draws, t_corr, vs, a_corr, qs, grid9, prior5, loc, marg, vol, log_z, summary, stk);
 }
 
 // The arithmetic of the three locate entry points on this handle (include/htm_hip.h); step 5's switch is htm_forward_set_precision
@@ -709,6 +755,26 @@ int htm_forward_locate_draw_evidence(htm_forward *h, int n_draws, const double *
     if (!t_corr || !vs || !a_corr || !qs || !grid9 || !log_z) return fail(HTM_EINVAL, "NULL argument");
     if (int rc = locate_draws_ok(n_draws, vs, qs)) return rc;
     return locate_run(h, n_draws, t_corr, vs, a_corr, qs, grid9, prior5, nullptr, nullptr, nullptr, log_z, summary);
+}
+
+// The stacked density of the windows' posteriors (include/htm_hip.h): n_draws = 0 htm_forward_locate's
+// structure (*vs, *qs), n_draws >= 1 htm_forward_locate_marginal's
+int htm_forward_locate_stack(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr, const double *qs,
+                             const double *grid9, const double *prior5, const int *layer, int n_layer, double *loc, double *marg, double *xy,
+                             double *xz, double *yz, double *stack, double *tally)
+{
+    if (!h) return fail(HTM_EINVAL, "NULL handle");
+    if (!t_corr || !vs || !a_corr || !qs || !grid9) return fail(HTM_EINVAL, "NULL argument");
+    if (n_draws == 0) {
+        if (!std::isfinite(*vs) || !std::isfinite(*qs) || !(*vs > 0.0) || !(*qs > 0.0))
+            return fail(HTM_EINVAL, "vs = %g, qs = %g: need finite values > 0", *vs, *qs);
+    } else if (int rc = locate_draws_ok(n_draws, vs, qs))
+        return rc;
+    if (n_layer < 1) return fail(HTM_EINVAL, "n_layer = %d: need at least 1", n_layer);
+    if (!layer && n_layer != 1) return fail(HTM_EINVAL, "n_layer = %d without a layer per window", n_layer);
+    if (!xy || !xz || !yz || !tally) return fail(HTM_EINVAL, "NULL output: xy, xz, yz and tally are required");
+    const LocStackOut stk{layer, n_layer, xy, xz, yz, stack, tally};
+    return locate_run(h, n_draws, t_corr, vs, a_corr, qs, grid9, prior5, loc, marg, nullptr, nullptr, nullptr, &stk);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -22,8 +22,10 @@
 //                     (loc_cell_done, loc_tile_reduce), and k_locate_combine serves both.
 //   k_locate_draw_evidence<MODE>, k_locate_draw_combine    htm_forward_locate_draw_evidence: every draw's log evidence per event
 //                     and what the draws weigh, described where they stand, below k_locate_marginal
+//   k_locate_stack, k_locate_stack_project    htm_forward_locate_stack: the windows' posteriors, one unit of mass each, summed per
+//                     layer from the batch's volume, and the three projections; described where they stand, at the end
 // No floating-point atomics anywhere: the bits do not depend on timing.  The volume of log posteriors is written only when it
-// is asked for.
+// is asked for, or stacked.
 //
 // Every one of the three evaluation kernels exists twice: F32 = false, all arithmetic fp64, and F32 = true, the single-precision
 // forward of htm_forward_locate_set_precision (the rule: loc_station).  The float copies of the structure are
@@ -686,7 +688,8 @@ __global__ __launch_bounds__(256) void k_locate_draw_combine(int n_tiles, int K,
 
 // One workgroup of 256 threads per event of the batch.  loc [nb][16], marg [nb][nx + ny + nz] (always there: the moments are
 // taken from the marginals).
-__global__ __launch_bounds__(256) void k_locate_combine(LocGrid g, double *part, double log_cell, double *loc, double *marg)
+// wsum [nb] or nullptr: the event's weight sum W (0 for an event without an included cell), for k_locate_stack.
+__global__ __launch_bounds__(256) void k_locate_combine(LocGrid g, double *part, double log_cell, double *loc, double *marg, double *wsum)
 {
     __shared__ double s_red4[4];
     __shared__ double s_blp[4], s_bell[4], s_bidx[4];
@@ -711,6 +714,7 @@ __global__ __launch_bounds__(256) void k_locate_combine(LocGrid g, double *part,
 #pragma unroll
     for (int w = 1; w < 4; ++w) better(s_blp[w], s_bell[w], s_bidx[w]);
     if (bidx < 0.0) {       // (block-uniform) no included cell
+        if (t == 0 && wsum) wsum[b] = 0.0;
         if (t < 16) L[t] = t == 0 ? -1.0 : nan;
         for (int i = t; i < nm; i += 256) M[i] = nan;
         return;
@@ -776,6 +780,113 @@ __global__ __launch_bounds__(256) void k_locate_combine(LocGrid g, double *part,
         L[4] = blp; L[5] = bell; L[6] = (blp + htm_log(W)) + log_cell;
         L[7] = mean[0]; L[8] = mean[1]; L[9] = mean[2];
         L[10] = var[0]; L[11] = cxy; L[12] = cxz; L[13] = var[1]; L[14] = cyz; L[15] = var[2];
+        if (wsum) wsum[b] = W;
+    }
+}
+
+// ---- the stacked density of the windows' posteriors (the rule: include/htm_hip.h) ------------------------
+// A window e of layer L with an included cell puts the mass exp(lp_e(c) - lp_best,e) * (1 / W_e) into cell c of stack[L]: one
+// unit of mass per window.  The batch's log posteriors are read from the volume that k_locate / k_locate_marginal wrote, lp_best
+// from the batch's loc records, W from k_locate_combine's wsum.
+//
+//   k_locate_stack          after a batch's k_locate_combine.  A thread owns a CELL, the batch's windows are the serial loop in
+//                           event order: for a fixed window consecutive threads read consecutive lp.  What is uniform per window
+//                           -- its layer, whether it takes part, lp_best, W -- comes through scalar loads.  kLocStkAhead
+//                           windows' lp are requested before the first of them is added: the loads are independent, only the
+//                           adds are ordered.  The thread keeps the running total of the current layer in a register; when the
+//                           layer changes, and at the end, it writes it to stack[L][c], which only it owns, and on entering a
+//                           layer it reads that layer's total first: a cell's total goes through memory unchanged from batch to
+//                           batch, so its additions are the same however the windows are batched.  Thread 0 of block 0 counts
+//                           the windows: tally[L][0] those that add their unit, tally[L][1] those without an included cell.
+//   k_locate_stack_project  after the last batch: xy (sum over iz), xz (over iy), yz (over ix) of the finished stack.  xy and xz:
+//                           a thread per map cell, the summed axis in ascending order, neighbouring threads neighbouring ix;
+//                           yz: a wave per map cell, its x-row lane-strided in ascending ix, then the wave sums' fixed tree.
+//                           Grid-stride loops: every map cell has one owner and an order that depends on the grid alone.
+// No floating-point atomics.  All index arithmetic is in size_t or long: batch x cells passes 2^31.
+constexpr int kLocStkAhead = 8;         // windows whose lp are in flight ahead of the accumulate
+
+// one value at a wave-uniform address through the constant address space: a scalar load
+template <class T>
+__device__ __forceinline__ T loc_ld_uniform(const T *p)
+{
+    typedef const T __attribute__((address_space(4))) *CP;
+    return *(CP)(unsigned long long)p;
+}
+
+// vol [nb][cells], loc [nb][16], wsum [nb]: the batch's; layer [n_events] or nullptr (every window in layer 0), e0 the batch's
+// first event; stack [n_layer][cells], tally [n_layer][2]
+__global__ __launch_bounds__(256) void k_locate_stack(long cells, int nb, int e0, const double *vol, const double *loc, const double *wsum,
+                                                      const int *layer, int n_layer, double *stack, double *tally)
+{
+    const long c = (long)blockIdx.x * 256 + threadIdx.x;
+    const bool live = c < cells;
+    const size_t cc = live ? (size_t)c : 0;      // (a thread beyond the grid reads cell 0 and writes nothing)
+    // the window's layer, or -1: it takes no part (uniform)
+    auto layer_of = [&](int b) {
+        const int L = layer ? loc_ld_uniform(layer + e0 + b) : 0;
+        return L >= 0 && L < n_layer ? L : -1;
+    };
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (int b = 0; b < nb; ++b) {
+            const int L = layer_of(b);
+            if (L >= 0) tally[2 * (size_t)L + (loc[16 * (size_t)b] < 0.0 ? 1 : 0)] += 1.0;
+        }
+    int cur = -1;
+    double acc = 0.0;
+    for (int b0 = 0; b0 < nb; b0 += kLocStkAhead) {
+        // the requests of the block's windows, unconditional so that they are counted: beyond the batch's end the last window
+        // is read again and dropped
+        double v[kLocStkAhead], idx[kLocStkAhead], best[kLocStkAhead], w[kLocStkAhead];
+        int lay[kLocStkAhead];
+#pragma unroll
+        for (int q = 0; q < kLocStkAhead; ++q) {
+            const int b = min(b0 + q, nb - 1);
+            v[q] = vol[(size_t)b * (size_t)cells + cc];
+            lay[q] = layer_of(b);
+            idx[q] = loc_ld_uniform(loc + 16 * (size_t)b); best[q] = loc_ld_uniform(loc + 16 * (size_t)b + 4); w[q] = loc_ld_uniform(wsum + b);
+        }
+#pragma unroll
+        for (int q = 0; q < kLocStkAhead; ++q) {
+            if (b0 + q >= nb) break;                                     // (uniform)
+            const int L = lay[q];
+            if (L < 0 || idx[q] < 0.0) continue;                         // (uniform) it takes no part, or has no included cell
+            if (L != cur) {
+                if (cur >= 0 && live) stack[(size_t)cur * (size_t)cells + cc] = acc;
+                cur = L;
+                acc = live ? stack[(size_t)L * (size_t)cells + cc] : 0.0;
+            }
+            const double rw = 1.0 / w[q];                                // (uniform: once per window)
+            acc += loc_included(v[q]) ? exp(v[q] - best[q]) * rw : 0.0;
+        }
+    }
+    if (cur >= 0 && live) stack[(size_t)cur * (size_t)cells + cc] = acc;
+}
+
+__global__ __launch_bounds__(256) void k_locate_stack_project(LocGrid g, int n_layer, const double *stack, double *xy, double *xz, double *yz)
+{
+    const size_t nx = g.nx, ny = g.ny, nz = g.nz, cells = nx * ny * nz, nl = n_layer;
+    const size_t n_thr = (size_t)gridDim.x * 256, t0 = (size_t)blockIdx.x * 256 + threadIdx.x;
+    for (size_t i = t0; i < nl * ny * nx; i += n_thr) {                  // xy [layer][iy][ix]: iz ascending
+        const size_t L = i / (nx * ny);
+        const double *p = stack + L * cells + (i - L * nx * ny);
+        double a = 0.0;
+        for (size_t iz = 0; iz < nz; ++iz) a += p[iz * nx * ny];
+        xy[i] = a;
+    }
+    for (size_t i = t0; i < nl * nz * nx; i += n_thr) {                  // xz [layer][iz][ix]: iy ascending
+        const size_t L = i / (nx * nz), r = i - L * nx * nz, iz = r / nx;
+        const double *p = stack + L * cells + iz * nx * ny + (r - iz * nx);
+        double a = 0.0;
+        for (size_t iy = 0; iy < ny; ++iy) a += p[iy * nx];
+        xz[i] = a;
+    }
+    const size_t lane = threadIdx.x & 63;
+    for (size_t i = t0 >> 6; i < nl * nz * ny; i += n_thr >> 6) {        // yz [layer][iz][iy] (wave-uniform): the x-row i of the stack
+        const double *p = stack + i * nx;
+        double a = 0.0;
+        for (size_t ix = lane; ix < nx; ix += 64) a += p[ix];
+        a = wave_sum1(a);
+        if (lane == 0) yz[i] = a;
     }
 }
 

@@ -84,6 +84,13 @@ class Forward:
         check(self._lib.htm_forward_locate_set_precision(self.handle, int(p == "fp32")))
         self.locate_precision = p
 
+    def locate_stack(self, n_draws, t_corr, vs, a_corr, qs, grid9, prior5, layer, n_layer, loc, marg, xy, xz, yz, stack, tally):
+        """htm_forward_locate_stack on this object (include/htm_hip.h): contiguous float64 arrays as the
+        library takes them, `layer` int32 or None, None for an output that is not asked for.  `locate.stack` prepares them."""
+        check(self._lib.htm_forward_locate_stack(self.handle, int(n_draws), ptr(t_corr), ptr(vs), ptr(a_corr), ptr(qs), ptr(grid9), ptr(prior5),
+                                                 None if layer is None else layer.ctypes.data_as(_lib.ip), int(n_layer), ptr(loc), ptr(marg),
+                                                 ptr(xy), ptr(xz), ptr(yz), ptr(stack), ptr(tally)))
+
     def obs_pack_bytes(self) -> int:
         """Bytes of the packed per-event observation records (the specialised chain master's; 0: none were built)."""
         n = C.c_int64(0)

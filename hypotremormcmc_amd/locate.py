@@ -5,6 +5,7 @@ grid -- no MCMC, any number of windows (kernels in hypotremorm
     python -m hypotremormcmc_amd.locate <parameter file> --cell DX [DY DZ] [--bounds x0 x1 y0 y1 z0 z1] [--structure DIR]
                                         [--windows FILE] [--flat-prior] [--volume-of WIN] [--draws K [--draw-weights]]
                                         [--precision fp64|fp32]
+                                        [--stack [--time-bins N] [--stack-volume] [--stack-resolved] [--level 0.68 0.95]]
 
 run in the data directory (station file, opt_data.NNNNNN.dat).  --structure DIR holds `uniform_structure.stat` and
 `station_corrections.stat` of the calibration run (default: the parameter file's directory); --windows FILE lists the window
@@ -39,6 +40,17 @@ synthetic travel time and amplitude of a (cell, station) in fp32, the observatio
 term in fp64.  File names and layouts are unchanged; the summary gains one line that names the precision.  The default is
 fp64, and without the option nothing is written or printed that was not before.  The parameter file's `forward_precision` and
 HTM_FORWARD_PRECISION are step 5's and do not switch this program.
+
+--stack also makes the map product of `density` for the located windows: every window's grid posterior,
+normalised to one unit of mass, summed per time layer on the device (`stack`, htm_forward_locate_stack), in the same
+evaluation that `<stem>.stat` and `<stem>.best.dat` are written from (<stem>: hypo_grid, or hypo_grid_marginal with --draws;
+either --precision).  It writes `<stem>.density.xy.dat`, `.xz.dat`, `.yz.dat` and with --stack-volume `.vol.dat`: one line per
+cell in the order and formats of tremor_density.*.dat -- layer, indices, centre, the expected number of windows in the cell and
+the smallest --level whose highest-density region of the layer holds the cell -- without a sample count, for there are no
+samples.  --time-bins N gives the layers (density.time_layers).  --stack-resolved leaves out every window whose best cell lies
+on a face of the box (a first evaluation finds them; the summary says how many).  One summary line per layer: windows
+stacked, windows without an included cell, and the share of the layer's mass on the faces of the box.  The other options of
+this paragraph without --stack are argument errors.
 """
 from __future__ import annotations
 
@@ -50,6 +62,7 @@ import sys
 import numpy as np
 
 from . import _lib
+from .density import AXES, MAPS, time_layers
 from .forward import Forward
 from .grid import add_grid_arguments, centres, grid9, grid_counts, grid_from_args
 from .obs_data import ObsData
@@ -133,6 +146,46 @@ def draw_evidence(fwd, t_corr, vs, a_corr, qs, grid, prior=None, precision=None)
                                                                 _lib.ptr(pr), _lib.ptr(log_z), _lib.ptr(summ)))
     return {"log_z": log_z, "n_eff": summ[:, 0].copy(), "w_max": summ[:, 1].copy(), "k_max": summ[:, 2].astype(np.int64),
             "log_evidence": summ[:, 3].copy()}
+
+
+def stack(fwd, t_corr, vs, a_corr, qs, grid, prior=None, layer=None, n_layer=1, volume=False, precision=None):
+    """The stacked density of the windows' posteriors on `grid` (htm_forward_locate_stack): every window of
+    layer L = layer[e] in 0 .. n_layer - 1 that has an included cell adds exp(lp - lp_best) / W, one unit of mass, to the
+    layer's stack, in event order, on the device; no per-window volume comes back.  The inputs of `locate`, or, with t_corr
+    [K][n_sta] and vs [K] (a 2-D t_corr or a 1-D vs), of `locate_marginal`.  layer [E] ints or None (n_layer must be 1: every
+    window in layer 0); a window whose layer is outside 0 .. n_layer - 1 takes no part.  Returns the dict of `locate` (its
+    very bits; vol None) plus xy [n_layer][ny][nx], xz [n_layer][nz][nx], yz [n_layer][nz][ny], tally [n_layer][2] = windows
+    stacked, windows without an included cell, and stack [n_layer][nz][ny][nx] (None without `volume`)."""
+    g, (nx, ny, nz) = _grid(grid)
+    E, S = fwd.n_events, fwd.n_sta
+    if np.ndim(vs) >= 1 or np.ndim(t_corr) == 2:
+        K, tc, v, ac, q = _draws(t_corr, vs, a_corr, qs, S)
+    else:
+        K, v, q = 0, np.array([float(vs)]), np.array([float(qs)])
+        tc = np.ascontiguousarray(np.asarray(t_corr, dtype=np.float64).reshape(-1))
+        ac = np.ascontiguousarray(np.asarray(a_corr, dtype=np.float64).reshape(-1))
+        if tc.size != S or ac.size != S:
+            raise ValueError(f"t_corr and a_corr have {tc.size} and {ac.size} values: need one per station ({S})")
+    n_layer = int(n_layer)
+    if n_layer < 1:
+        raise ValueError(f"n_layer = {n_layer}: need at least 1")
+    lay = None
+    if layer is None:
+        if n_layer != 1:
+            raise ValueError(f"n_layer = {n_layer} without a layer per window")
+    else:
+        lay = np.ascontiguousarray(layer, dtype=np.int32)
+        if lay.shape != (E,):
+            raise ValueError(f"layer is {lay.shape}: need one per window ({E})")
+    if n_layer * (nx * ny * nz + nx * ny + nx * nz + ny * nz + 2) > INT_MAX:
+        raise ValueError(f"{n_layer} layers of {nx} x {ny} x {nz} cells, their maps and tallies: more than 2^31 - 1 values")
+    pr = _prior_array(prior, E)
+    loc, marg, _ = _outputs(E, nx, ny, nz, True, False)
+    out = {"xy": np.empty((n_layer, ny, nx)), "xz": np.empty((n_layer, nz, nx)), "yz": np.empty((n_layer, nz, ny)),
+           "stack": np.empty((n_layer, nz, ny, nx)) if volume else None, "tally": np.empty((n_layer, 2))}
+    with _precision(fwd, precision):
+        fwd.locate_stack(K, tc, v, ac, q, g, pr, lay, n_layer, loc, marg, out["xy"], out["xz"], out["yz"], out["stack"], out["tally"])
+    return dict(_result(loc, marg, None, nx, ny), **out)
 
 
 def draw_weights(log_z):
@@ -382,6 +435,84 @@ def draws_summary_text(ev, n_draws) -> str:
             f"{int((ev['w_max'] > 0.5).sum())} windows where one draw outweighs all the others (w_max > 0.5: their intervals are one structure's)\n")
 
 
+# ---- the stacked density's files (--stack) ----------------------------------------------------------------------------------
+def hpd_levels_mass(mass, levels):
+    """`density.hpd_levels` for non-negative floats: per cell of one layer's map the smallest of `levels` whose highest-density
+    region holds the cell, 0 where none does.  The region of a level is the smallest set of cells, taken in descending mass,
+    whose mass reaches that share of the map's sum; cells of equal mass enter together, so the region is unique.  Empty cells
+    are in no region.  On integer-valued input it gives what density.hpd_levels gives."""
+    m = np.asarray(mass, dtype=np.float64)
+    levels = sorted(float(v) for v in levels)
+    if any(not 0.0 < v <= 1.0 for v in levels):
+        raise ValueError(f"levels {levels}: need 0 < level <= 1")
+    if not np.all(m >= 0.0):
+        raise ValueError("masses must be non-negative numbers")
+    out = np.zeros(m.shape)
+    vals, inv, mult = np.unique(m.reshape(-1), return_inverse=True, return_counts=True)
+    order = np.argsort(vals)[::-1]                                    # the distinct masses, descending
+    group = vals[order] * mult[order]
+    total = float(group.sum())
+    if total == 0.0 or not levels:
+        return out
+    before = np.concatenate([[0.0], np.cumsum(group)[:-1]])           # mass of the groups that entered earlier
+    lev_of = np.zeros(len(vals))
+    for rank, k in enumerate(order):
+        if vals[k] == 0.0:
+            continue
+        for v in levels:                                             # the group enters the region of every level not yet reached
+            if before[rank] < v * total:
+                lev_of[k] = v
+                break
+    return lev_of[inv.reshape(-1)].reshape(m.shape)
+
+
+STACK_HEADERS = {nm: "# layer, cell " + " ".join("i" + "xyz"[a] for a in AXES[nm]) + ", centre " + " ".join("xyz"[a] for a in AXES[nm])
+                     + ", expected windows (the stacked grid posteriors' mass; there are no samples, so no sample count), "
+                     "smallest level whose region holds the cell (0: none)" for nm in MAPS}
+
+
+def stack_map_text(name, mass, grid, levels) -> str:
+    """the text of <stem>.density.<name>.dat from mass [n_layer][...] of map `name` ("xy", "xz", "yz", "vol"; slowest axis
+    first, as `stack` returns it): tremor_density.<name>.dat's order and formats without the sample count"""
+    g = grid9(grid)
+    m = np.asarray(mass, dtype=np.float64)
+    axes = AXES[name]
+    cen = [centres(g, a) for a in axes]
+    lines = [STACK_HEADERS[name]]
+    for L in range(m.shape[0]):
+        lev = hpd_levels_mass(m[L], levels)
+        for idx in np.ndindex(*m.shape[1:]):
+            cell = idx[::-1]                                         # fastest axis first
+            lines.append("%5d" % L + "".join("%6d" % i for i in cell) + "".join("%14.6f" % v[i] for v, i in zip(cen, cell))
+                         + "%14.6e%8.4f" % (m[L][idx], lev[idx]))
+    return "\n".join(lines) + "\n"
+
+
+def resolved_layer(layer, index, grid):
+    """`layer` with -1 (takes no part) for every window whose best cell `index` lies on a face of the box (on_face): the grid
+    does not resolve it"""
+    return np.where(on_face(index, grid), -1, np.asarray(layer, dtype=np.int32)).astype(np.int32)
+
+
+def face_share(stack_vol):
+    """per layer of stack [n_layer][nz][ny][nx] the share of its mass in the cells on a face of the box (NaN: an empty layer)"""
+    s = np.asarray(stack_vol, dtype=np.float64)
+    inner = s[:, 1:-1, 1:-1, 1:-1].sum(axis=(1, 2, 3))
+    total = s.sum(axis=(1, 2, 3))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(total > 0.0, (total - inner) / total, np.nan)
+
+
+def stack_summary_text(tally, share, n_unresolved=None) -> str:
+    """one line per layer: windows stacked, windows without an included cell, the share of the layer's mass on the faces of the
+    box; with --stack-resolved a first line says how many windows were left out"""
+    lines = [] if n_unresolved is None else [f"{n_unresolved} windows left out of the stack: their best cell lies on a face of the box"]
+    for L, ((n_in, n_none), sh) in enumerate(zip(np.asarray(tally).tolist(), share)):
+        on = "NaN" if np.isnan(sh) else "%.2f %%" % (100.0 * sh)
+        lines.append(f"layer {L}: {int(n_in)} windows stacked, {int(n_none)} without an included cell, {on} of the mass on the faces of the box")
+    return "\n".join(lines) + "\n"
+
+
 def summary_text(res, grid, n_draws=None, precision="fp64") -> str:
     n = len(res["index"])
     how = "" if n_draws is None else f", the structure marginalised over {n_draws} draws"
@@ -405,11 +536,29 @@ def main(argv=None):
                     "effective number (hypo_grid_marginal.draws.dat) and the draws' joint weights (hypo_grid_marginal.structure.dat)")
     ap.add_argument("--precision", choices=("fp64", "fp32"), default="fp64", help="fp32: the synthetic travel times and amplitudes in single "
                     "precision, every sum in fp64 (default fp64)")
+    ap.add_argument("--stack", action="store_true", help="also stack the windows' posteriors on the device into density maps: writes "
+                    "<stem>.density.xy.dat, .xz.dat and .yz.dat")
+    ap.add_argument("--time-bins", type=int, metavar="N", help="with --stack: layers of equal spans of window ids (default 1)")
+    ap.add_argument("--stack-volume", action="store_true", help="with --stack: also the 3-D stack, <stem>.density.vol.dat")
+    ap.add_argument("--stack-resolved", action="store_true", help="with --stack: leave out the windows whose best cell lies on a face of the box "
+                    "(a first evaluation finds them)")
+    ap.add_argument("--level", type=float, nargs="+", metavar="P", help="with --stack: shares of a layer's mass for the regions (default 0.68 0.95)")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
     if args.draws is not None and args.draws < 1:
         ap.error(f"--draws {args.draws}: need at least one draw")
     if args.draw_weights and args.draws is None:
         ap.error("--draw-weights needs --draws K: the weights are those of the K draws")
+    if not args.stack:
+        for given, name in ((args.time_bins is not None, "--time-bins"), (args.stack_volume, "--stack-volume"),
+                            (args.stack_resolved, "--stack-resolved"), (args.level is not None, "--level")):
+            if given:
+                ap.error(f"{name} needs --stack: it is an option of the stacked density")
+    n_bins = 1 if args.time_bins is None else args.time_bins
+    levels = [0.68, 0.95] if args.level is None else args.level
+    if n_bins < 1:
+        ap.error("--time-bins must be at least 1")
+    if any(not 0.0 < v <= 1.0 for v in levels):
+        ap.error("--level must lie in (0, 1]")
     r5 = Step5Run.open(args.parameter_file, windows=args.windows)
     par, work, device, win_id = r5.par, r5.work, r5.device, r5.win_id
     grid = grid_from_args(ap, args, par)
@@ -423,19 +572,32 @@ def main(argv=None):
     if not win_id:
         raise SystemExit("ERROR: no window to locate")
 
-    def run(ids, volume, weights=False):
+    n_unresolved = None
+
+    def run(ids, volume, weights=False, stacked=False):
+        nonlocal n_unresolved
         obs = ObsData(ids, par.n_stations, par.sta_x, par.sta_y, directory=work)
         fwd = Forward(par.n_stations, len(ids), par.sta_x, par.sta_y, par.sta_z, obs, use_amp=par.get_use_amp(), use_time=par.get_use_time(),
                       device=device)
         try:
             fwd.set_locate_precision(args.precision)
             prior = None if args.flat_prior else step5_prior(par, obs)
-            res = evaluate(fwd, t_corr, vs, a_corr, qs, grid, prior=prior, volume=volume)
+            if stacked:
+                # one evaluation gives the maps and what the .stat and .best.dat files are written from; --stack-resolved needs
+                # the best cells before it, from an evaluation of their own
+                layer = time_layers(ids, n_bins)
+                if args.stack_resolved:
+                    first = evaluate(fwd, t_corr, vs, a_corr, qs, grid, prior=prior, marginals=False)
+                    layer = resolved_layer(layer, first["index"], grid)
+                    n_unresolved = int((layer < 0).sum())
+                res = stack(fwd, t_corr, vs, a_corr, qs, grid, prior=prior, layer=layer, n_layer=n_bins, volume=True)
+            else:
+                res = evaluate(fwd, t_corr, vs, a_corr, qs, grid, prior=prior, volume=volume)
             return (res, draw_evidence(fwd, t_corr, vs, a_corr, qs, grid, prior=prior)) if weights else res
         finally:
             fwd.close()
 
-    res, ev = run(win_id, False, True) if args.draw_weights else (run(win_id, False), None)
+    res, ev = run(win_id, False, True, args.stack) if args.draw_weights else (run(win_id, False, stacked=args.stack), None)
     marg = np.concatenate([res["marg_x"], res["marg_y"], res["marg_z"]], axis=1)
     with open(os.path.join(work, stem + ".stat"), "w") as fh:
         fh.write(stat_text(win_id, marginal_quantiles(marg, grid)))
@@ -448,6 +610,12 @@ def main(argv=None):
         with open(os.path.join(work, stem + ".%d.vol.dat" % args.volume_of), "w") as fh:
             fh.write(volume_text(one["vol"][0], grid))
     sys.stdout.write(summary_text(res, grid, args.draws, args.precision))
+    if args.stack:
+        for nm in MAPS:
+            if nm != "vol" or args.stack_volume:
+                with open(os.path.join(work, stem + ".density.%s.dat" % nm), "w") as fh:
+                    fh.write(stack_map_text(nm, res["stack" if nm == "vol" else nm], grid, levels))
+        sys.stdout.write(stack_summary_text(res["tally"], face_share(res["stack"]), n_unresolved))
     if ev is not None:
         with open(os.path.join(work, stem + ".draws.dat"), "w") as fh:
             fh.write(draws_text(win_id, ev, records))

@@ -218,6 +218,42 @@ int htm_forward_locate_draw_evidence(htm_forward *h, int n_draws, const double *
  * NULL handle, or a value other than 0 or 1: HTM_EINVAL, and the setting stays as it was. */
 int htm_forward_locate_set_precision(htm_forward *h, int forward_fp32);
 
+/* STACKED DENSITY of the windows' grid posteriors: what htm_hypo_density is for the samples of step 5, for
+ * windows that were located on the grid -- formed on the device, batch after batch; nothing of size n_events x cells crosses
+ * to the host.  n_draws = 0: the fixed structure of htm_forward_locate (vs and qs point to one value each, t_corr, a_corr
+ * [n_sta]); n_draws >= 1: the inputs of htm_forward_locate_marginal.  layer [n_events] gives every window its layer, or NULL
+ * with n_layer == 1 (every window in layer 0).  THE RULE:
+ *   - a window e whose layer L_e lies in 0 .. n_layer - 1 and that has an included cell puts the mass
+ *     m_e(c) = exp(lp_e(c) - lp_best,e) * (1 / W_e) into cell c: the subtraction first (it is exact for the cells that matter),
+ *     then the exponential, then the product with the reciprocal, which is formed once per window.  lp_e(c) and lp_best,e are
+ *     the very numbers that the entry points above return in vol and loc[4]; W_e = sum_c exp(lp_e(c) - lp_best,e) is the
+ *     weight sum as they form it for the marginals (good to 1e-12 relative), kept from that reduce, not recomputed from loc[6];
+ *   - excluded cells (lp NaN or -inf) get nothing;
+ *   - a window whose layer is outside 0 .. n_layer - 1 takes no part and is in nobody's tally, as in htm_hypo_density;
+ *   - a window without an included cell (loc[0] = -1) is counted in tally[L][1] and adds nothing; every other window of the
+ *     layer is counted in tally[L][0] and adds one unit of mass;
+ *   - stack[L][c] is the sum of m_e(c) over the layer's windows in ascending event order, sequentially, starting from 0;
+ *   - xy [n_layer][ny][nx] is the sum of the finished stack over iz, xz [n_layer][nz][nx] over iy, yz [n_layer][nz][ny] over
+ *     ix, each in an order that depends on the grid alone.
+ * stack [n_layer][nz][ny][nx] or NULL; tally [n_layer][2], doubles with integral values; xy, xz, yz and tally are required.
+ * loc [n_events][16] and marg [n_events][nx + ny + nz] may be NULL; where given they are bit for bit what htm_forward_locate /
+ * htm_forward_locate_marginal return.  A stacked cell is good to (2e-12 + n 2^-53) relative of the rule applied to vol and
+ * loc[4], n the layer's windows; a layer's stack and each of its maps sum to tally[L][0] to (2e-12 + cells 2^-53) relative.
+ * htm_forward_locate_set_precision applies: it changes lp, and the stack consumes lp.
+ * No floating-point atomics: two calls give the same bits, and the bits do not depend on HTM_LOCATE_MB -- a cell's running
+ * total goes through memory unchanged from one batch to the next.  The workspace: per event of a batch
+ *   8 (n_tiles stride + cells + 1 + 2 (nx + ny + nz) + 16) + 80 n_sta + 32 bytes
+ * (rows = max(1, min(ny, 256, 4096 / nx)) x-rows per tile, n_tiles = nz ceil(ny / rows), stride = 4 + nx + 2 rows), and once
+ * per call 8 n_layer (cells + nx ny + nx nz + ny nz + 2) bytes, 4 n_events for the layers where they are given, and the draws'
+ * table as for htm_forward_locate_marginal.
+ * Refused with HTM_EINVAL and a message before any device call, the outputs untouched: whatever those two entry points refuse;
+ * n_layer < 1; layer == NULL with n_layer != 1; a NULL xy, xz, yz or tally; n_layer (cells + nx ny + nx nz + ny nz + 2) above
+ * 2^31 - 1; the once-per-call part and one event not fitting under HTM_LOCATE_MB (the message names the variable).
+ * Synchronous. */
+int htm_forward_locate_stack(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr,
+                             const double *qs, const double *grid9, const double *prior5, const int *layer, int n_layer,
+                             double *loc, double *marg, double *xy, double *xz, double *yz, double *stack, double *tally);
+
 /* ------------------------------------------------------------------------------------------------
  * Device-resident chains: `type mcmc` x n_chains inside `type parallel`
  *                          reference: src/cls_mcmc.f90, src/cls_parallel.f90, src/hypo_tremor_mcmc.f90
