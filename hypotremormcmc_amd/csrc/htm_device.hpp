@@ -121,6 +121,49 @@ __device__ __forceinline__ void wave_sum_transposed(double (&v)[N])
     for (int k = 0; k < N; ++k) v[k] = __hiloint2double(__builtin_amdgcn_readlane(hi, k), __builtin_amdgcn_readlane(lo, k));
 }
 
+// The lane's classes of wave_sum_transposed as 0 / 1 VALUES in two vector registers, formed once per launch by a kernel whose loop
+// has no scalar registers left for loop-invariant lane masks (the specialised chain master: LoopRegs below): each use is one
+// v_cmp against the register where the form above rebuilds shift, xor, and, compare from the lane id at every call.
+struct SumRegs {
+    int b0, b1;      // (lane ^ lane >> 2) & 1, (lane >> 1 ^ lane >> 2) & 1
+};
+__device__ __forceinline__ SumRegs sum_regs()
+{
+    const unsigned lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    SumRegs m;
+    m.b0 = (int)((lane ^ (lane >> 2)) & 1u); m.b1 = (int)(((lane >> 1) ^ (lane >> 2)) & 1u);
+    asm volatile("" : "+v"(m.b0), "+v"(m.b1));      // (kept as values, not re-derived from the lane id)
+    return m;
+}
+// the same selects and the same additions in the same order as wave_sum_transposed(v): the same bits
+template <int N>
+__device__ __forceinline__ void wave_sum_transposed(double (&v)[N], const SumRegs &m)
+{
+    static_assert(N == 2 || N == 4, "two or four values");
+    const bool b0 = m.b0 != 0;
+    double x;
+    {
+        const double keep = b0 ? v[1] : v[0], send = b0 ? v[0] : v[1];
+        x = keep + dpp_mov_f64<0xB1, 0xF>(send);                       // quad_perm [1,0,3,2]
+    }
+    if constexpr (N == 4) {
+        const bool b1 = m.b1 != 0;
+        const double keep2 = b0 ? v[3] : v[2], send2 = b0 ? v[2] : v[3];
+        const double y = keep2 + dpp_mov_f64<0xB1, 0xF>(send2);
+        const double keep = b1 ? y : x, send = b1 ? x : y;
+        x = keep + dpp_mov_f64<0x4E, 0xF>(send);                       // quad_perm [2,3,0,1]
+    } else {
+        x += dpp_mov_f64<0x4E, 0xF>(x);
+    }
+    x += dpp_mov_f64<0x141, 0xF>(x);                                   // row_half_mirror
+    x += dpp_mov_f64<0x140, 0xF>(x);                                   // row_mirror
+    x = swap16_sum(x);
+    x = swap32_sum(x);
+    const int lo = __double2loint(x), hi = __double2hiint(x);
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = __hiloint2double(__builtin_amdgcn_readlane(hi, k), __builtin_amdgcn_readlane(lo, k));
+}
+
 // N independent sums, interleaved step by step so that the DPP latencies overlap.
 // Must be called with all 64 lanes active; inactive stations contribute 0.
 template <int N>
@@ -156,6 +199,14 @@ __device__ __forceinline__ void wave_sum(double (&v)[N])
     for (int k = 0; k < N; ++k) v[k] += dpp_mov_f64<0x143, 0xC>(v[k]);  // row_bcast:31 -> rows 2,3
 #pragma unroll
     for (int k = 0; k < N; ++k) v[k] = readlane63_f64(v[k]);
+}
+
+// (two or four sums with the lane classes in registers: the transposed form whenever wave_sum(v) takes it)
+template <int N>
+__device__ __forceinline__ void wave_sum(double (&v)[N], const SumRegs &m)
+{
+    if constexpr (HTM_TSUM != 0 && HTM_MFMA_SUM == 0 && (N == 2 || N == 4)) wave_sum_transposed<N>(v, m);
+    else wave_sum<N>(v);
 }
 
 __device__ __forceinline__ double wave_sum1(double a)
@@ -202,6 +253,58 @@ __device__ __forceinline__ double htm_log(double x)
     const double y = __builtin_fma(k, 0x1.62e42fee00000p-1, -(b - f));
     return x == 0.0 ? -__builtin_inf() : y;
 }
+
+// The ten constants of htm_log -- the seven coefficients, ln2_lo, ln2_hi and the threshold sqrt(1/2) -- in VECTOR registers for a
+// launch.  An fp64 literal costs the instruction that uses it nothing when it sits in a register already, and an s_mov_b32 pair in
+// front of it when it does not: a kernel with scalar registers to spare keeps the twenty halves there across its loop, the specialised
+// chain master has none (106 of 106 in use) and rebuilt them at every call -- 18 moves per partial-update step -- while 85 of its
+// 256 vector registers stood empty.  The opaque move keeps the compiler from seeing the values again and folding them back.
+struct LogRegs {
+    double p6, p5, p4, p3, p2, p1, p0, ln2_lo, ln2_hi, rt_half;
+};
+__device__ __forceinline__ LogRegs log_regs()
+{
+    LogRegs k = {0x1.2b5900de53b32p-3, 0x1.39fe51a7c18f9p-3, 0x1.7462b51cb66b1p-3, 0x1.c71c62e3f11e6p-3, 0x1.2492492df281ap-2,
+                 0x1.99999999952d7p-2, 0x1.5555555555558p-1, 0x1.a39ef35793c76p-33, 0x1.62e42fee00000p-1, 0.70710678118654752};
+    asm volatile("" : "+v"(k.p6), "+v"(k.p5), "+v"(k.p4), "+v"(k.p3), "+v"(k.p2), "+v"(k.p1), "+v"(k.p0), "+v"(k.ln2_lo), "+v"(k.ln2_hi),
+                 "+v"(k.rt_half));
+    return k;
+}
+// htm_log(x) with its constants read from those registers: the same operations on the same operands in the same order, the same bits
+// for every argument (tests/test_gpu_loop_constants.py)
+__device__ __forceinline__ double htm_log(double x, const LogRegs &c)
+{
+    const double m0 = __builtin_amdgcn_frexp_mant(x);                 // [0.5, 1)
+    const int lo = m0 < c.rt_half ? 1 : 0;
+    const double f = __builtin_fma(m0, lo ? 2.0 : 1.0, -1.0);         // m - 1, exact
+    const double k = (double)(__builtin_amdgcn_frexp_exp(x) - lo);
+    const double D = f + 2.0;
+    double r = __builtin_amdgcn_rcp(D);
+    r = __builtin_fma(__builtin_fma(-D, r, 1.0), r, r);
+    double s = f * r;
+    s = __builtin_fma(__builtin_fma(-s, D, f), r, s);
+    const double z = s * s;
+    double p = __builtin_fma(z, c.p6, c.p5);
+    p = __builtin_fma(z, p, c.p4);
+    p = __builtin_fma(z, p, c.p3);
+    p = __builtin_fma(z, p, c.p2);
+    p = __builtin_fma(z, p, c.p1);
+    p = __builtin_fma(z, p, c.p0);
+    const double hf = 0.5 * f;
+    const double a = __builtin_fma(f, hf, z * p);                     // f^2/2 + R
+    const double t = __builtin_fma(s, a, k * c.ln2_lo);               // + e * ln2_lo
+    const double b = __builtin_fma(f, hf, -t);
+    const double y = __builtin_fma(k, c.ln2_hi, -(b - f));
+    return x == 0.0 ? -__builtin_inf() : y;
+}
+
+// What the specialised chain master keeps in vector registers for a launch and hands to the evaluation (htm_flow.hpp flow_body forms
+// it, flow_step passes it on); NoLoopRegs, the default of every other caller, stands for "nothing": the literal forms above.
+struct LoopRegs {
+    LogRegs lg;
+    SumRegs sm;
+};
+struct NoLoopRegs {};
 
 // Square root of the squared distance (cls_forward.f90:115-117, :201-203), fp64: the device library's iteration
 // (v_rsq_f64 seed, one coupled Goldschmidt step, two residual corrections) without its rescaling of arguments below
@@ -439,12 +542,17 @@ __device__ __forceinline__ void load_obs_pack(ObsRegs<NCH, F32> &ob, const void 
 // per commit of vs or qs): two fp64 divisions, ~28 instructions, that the compiler does not move out of a loop over events.
 // FULL: every lane has a station in every chunk and both data types are used (the caller has checked, as for
 // load_obs_regs_nobranch<.., FULL>): no `valid` selects, no branches on use_time / use_amp.  Same arithmetic, same order.
-template <int NCH, int NPOS, bool F32 = false, bool PRE = false, bool FULL = false, class FW>
+// `lr`: the LoopRegs of a caller that keeps them (the specialised chain master) -- the logarithm's constants and the sum's lane
+// classes come from its registers; same operations, same bits.  (A pointer that defaults to null, not a reference to a
+// default-constructed nothing: the temporary alone made the register allocator number the F32 barrier loops' registers differently.)
+template <int NCH, int NPOS, bool F32 = false, bool PRE = false, bool FULL = false, class FW, class LR = NoLoopRegs>
 __device__ __forceinline__ void event_misfit(const FW &f, const ObsRegs<NCH, F32> &ob, int lane,
                                              const StaRegs<NCH> &st, const double (&px)[NPOS],
                                              const double (&py)[NPOS], const double (&pz)[NPOS], double beta,
-                                             double q, double (&out)[NPOS])
+                                             double q, double (&out)[NPOS], const LR *lr = nullptr)
 {
+    constexpr bool kRegs = std::is_same<LR, LoopRegs>::value;
+    static_assert(kRegs || std::is_same<LR, NoLoopRegs>::value, "LoopRegs or nothing");
     // Strength reduction (round 2): the reference divides per station -- d / beta, d * pi * freq / (q * beta)
     // (cls_forward.f90:118, :204) -- and per event mean (:131, :217).  beta, q and the precision sums are the same for all
     // stations of a call, so the divisions are done ONCE (two here, the sums' reciprocals on the host) and the per-station
@@ -502,13 +610,17 @@ __device__ __forceinline__ void event_misfit(const FW &f, const ObsRegs<NCH, F32
                 red[2 * p] = __builtin_fma(tpr[c], ts[p][c] - tob[c], red[2 * p]);
             }
             if (FULL || f.use_amp) {
-                as[p][c] = __builtin_fma(-d, katt, -htm_log(d)) - st.ac[c];
+                double lg;
+                if constexpr (kRegs) lg = htm_log(d, lr->lg);
+                else lg = htm_log(d);
+                as[p][c] = __builtin_fma(-d, katt, -lg) - st.ac[c];
                 red[2 * p + 1] = __builtin_fma(apr[c], as[p][c] - aob[c], red[2 * p + 1]);
             }
         }
     }
     }
-    wave_sum<2 * NPOS>(red);
+    if constexpr (kRegs) wave_sum<2 * NPOS>(red, lr->sm);
+    else wave_sum<2 * NPOS>(red);
     const double rpst = ob.rpst, rpsa = ob.rpsa;
 #pragma unroll
     for (int p = 0; p < NPOS; ++p) {

@@ -79,6 +79,11 @@ struct FlowShared : StepShared {
 
 // a wave-uniform value that reached a vector register (read from LDS) back in a scalar one
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// the same for a double whose lanes all hold one value: a scalar register pair (two v_readfirstlane)
+__device__ __forceinline__ double uni_f64(double v)
+{
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
 // lane l of a 64-bit word, as a wave-uniform value
 __device__ __forceinline__ unsigned long long rl_u64(unsigned long long v, int l)
 {
@@ -584,7 +589,7 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
                                          MbShared *g_mb, MbWave &mw, double *s_gath, int wmax,
                                          const double *s_sx, const double *s_sy, const double *s_sz, int c, int p, int iter,
                                          int lane, int wave, int NW, unsigned long long launch, bool ext, int look, int back,
-                                         bool rec_now, const FlowTop &tp, const FlowSta &fs, FlowOwn &own)
+                                         bool rec_now, const FlowTop &tp, const FlowSta &fs, FlowOwn &own, const LoopRegs &lr)
 {
     CsRef cs = rebase(cs_);
     FwRef f = rebase(f_);
@@ -726,6 +731,11 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
     int ok = 1;
     if (ptype == 1) {                                           // :178-187
         if (x_new <= mu) { lpr = (double)-1.0e+30f; ok = 0; }
+        else if constexpr (FX) {
+            // (the logarithm's constants from the launch's registers: LoopRegs.  They count as lane-dependent, so the ratio is read
+            // back as the wave-uniform value it is -- the decision behind it stays a scalar branch)
+            lpr = uni_f64(lpr + htm_log(x_new - mu, lr.lg) - htm_log(x_old - mu, lr.lg));
+        }
         else lpr = lpr + htm_log(x_new - mu) - htm_log(x_old - mu);       // (:184-185; htm_device.hpp: < 0.75 ulp, a third of the library routine's instructions)
     }
     const double r = ok ? r_ring : 0.0, logr = ok ? logr_ring : 0.0;
@@ -789,9 +799,13 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
     if (__builtin_expect(ok != 0, 1)) {
         if (__builtin_expect(partial, 1)) {
             const int cmp = idx - 3 * ev;        // 0 x, 1 y, 2 z of event ev (selects: see htm_step.hpp)
-            const double px[2] = {hx, cmp == 0 ? x_new : hx};
-            const double py[2] = {hy, cmp == 1 ? x_new : hy};
-            const double pz[2] = {hz, cmp == 2 ? x_new : hz};
+            // (the specialised master: x_new is wave-uniform and so are the three old coordinates -- read into a scalar pair, the new
+            // position is three scalar selects and the coordinate differences take their scalar operand directly; copies, no bit moves)
+            double xs = x_new;
+            if constexpr (FX) xs = uni_f64(x_new);
+            const double px[2] = {hx, cmp == 0 ? xs : hx};
+            const double py[2] = {hy, cmp == 1 ? xs : hy};
+            const double pz[2] = {hz, cmp == 2 ? xs : hz};
             double out[2];
             // look-ahead, first round trip (a wave with one chain): the hop-table entries that give the start of this chain's
             // next step, of its step after that, and the end of the iteration after next -- issued here, used behind the evaluation
@@ -820,7 +834,8 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
                     la = (la_p1 >= 0 && la_p2 >= 0 && la_E2 >= 0) ? 3 : 0;
                 }
             }
-            if constexpr (NCH > 0) event_misfit<NCH, 2, F32, true, TR::full_rows>(f, ob, lane, st, px, py, pz, tp.rbeta, tp.katt, out);
+            if constexpr (FX) event_misfit<NCH, 2, F32, true, true>(f, ob, lane, st, px, py, pz, tp.rbeta, tp.katt, out, &lr);
+            else if constexpr (NCH > 0) event_misfit<NCH, 2, F32, true, TR::full_rows>(f, ob, lane, st, px, py, pz, tp.rbeta, tp.katt, out);
             else event_misfit_generic<2>(f, ev, lane, s_sx, s_sy, s_sz, tc, ac, 0, -1, 0.0, px, py, pz, beta, q, out);
             L_new = L_cur + wave_sum1(out[0] - out[1]);
             // look-ahead, second round trip: what the stream holds at those positions -- used after the commit
@@ -916,7 +931,8 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
                     }
                     const double pxd[1] = {d_ex}, pyd[1] = {d_ey}, pzd[1] = {d_ez};
                     double outd[1];
-                    event_misfit<NCH, 1, F32, false, TR::full_rows>(f, ob, lane, st, pxd, pyd, pzd, type == 1 ? x_new : beta, type == 3 ? x_new : q, outd);
+                    if constexpr (FX) event_misfit<NCH, 1, F32, false, true>(f, ob, lane, st, pxd, pyd, pzd, type == 1 ? x_new : beta, type == 3 ? x_new : q, outd, &lr);
+                    else event_misfit<NCH, 1, F32, false, TR::full_rows>(f, ob, lane, st, pxd, pyd, pzd, type == 1 ? x_new : beta, type == 3 ? x_new : q, outd);
                     own_lane = outd[0];
                 }
             }
@@ -1602,6 +1618,10 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
         fs.d_hyp = lane - 1; fs.m_qs = lane == 5 ? -1 : 0;
         asm volatile("" : "+v"(fs.m_el), "+v"(fs.m_hyp), "+v"(fs.m_sc), "+v"(fs.d_hyp), "+v"(fs.m_qs));      // (kept as values, not re-derived from compares)
     }
+    // the logarithm's ten constants and the transposed sum's two lane classes, in vector registers for the launch (htm_device.hpp
+    // LoopRegs: 22 registers the loop's scalar file has no room for; the evaluations and the Rayleigh prior ratio read them)
+    LoopRegs lr = {{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, {0, 0}};
+    if constexpr (flow_fixed_v<TR>) { lr.lg = log_regs(); lr.sm = sum_regs(); }
     // (one station per lane: 6 registers of 256, the kernel has no vector spills and no scratch; two stations per lane keep the LDS reads)
     if constexpr (flow_fixed_v<TR> && NCH == 1) { fs.x = s_sx[lane]; fs.y = s_sy[lane]; fs.z = s_sz[lane]; }
     FlowNext nx;
@@ -1737,7 +1757,7 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
         if constexpr (MB) MB_HIST(mw, (known ? 4 : 0) | (W.epoch & 3));
         BSTAMP(2);
         const int r = flow_step<NCH, F32, LOCK, MB, TR>(f, cs, sh, rg, W, nx, g_mb, mw, s_gath, wmax, s_sx, s_sy, s_sz, c, p, iter, lane, MB ? c : wave,
-                                              MB ? 64 : NW, launch, wave == 0, look, back, rec_phase == 1, tp, fs, own);
+                                              MB ? 64 : NW, launch, wave == 0, look, back, rec_phase == 1, tp, fs, own, lr);
         BSTAMP_FROM_HERE();
         if (r == kFlowRestart) continue;      // (nothing was committed: the wave's copies of its chain's corrections stand)
         if (r == kFlowAbort || r == kFlowStop) break;

@@ -73,6 +73,26 @@ __global__ void k_mathtest(int which, const double *x, double *y, int n)
         }
         return;
     }
+    if (which == 7) {            // htm_log with its constants in registers (LogRegs), against mode 0 bit for bit
+        const LogRegs lg = log_regs();
+        if (i < n) y[i] = htm_log(x[i], lg);
+        return;
+    }
+    if (which == 8 || which == 9) {     // the transposed sum with the lane classes in registers (SumRegs): four values at once (8), two
+        const SumRegs sm = sum_regs();  // pairs (9); against mode 6.  x = four blocks of n / 4 values, n / 4 a multiple of 64: whole waves
+        const int q = n / 4;
+        if (i < q) {
+            double v[4] = {x[i], x[q + i], x[2 * q + i], x[3 * q + i]};
+            if (which == 8) wave_sum_transposed<4>(v, sm);
+            else {
+                double a[2] = {v[0], v[1]}, b[2] = {v[2], v[3]};
+                wave_sum_transposed<2>(a, sm); wave_sum_transposed<2>(b, sm);
+                v[0] = a[0]; v[1] = a[1]; v[2] = b[0]; v[3] = b[1];
+            }
+            for (int k = 0; k < 4; ++k) y[k * q + i] = v[k];
+        }
+        return;
+    }
     if (i < n) y[i] = which == 0 ? htm_log(x[i]) : which == 1 ? htm_sqrt(x[i]) : which == 2 ? sqrt(x[i]) : log(x[i]);   // 3: the device library's log (Rayleigh prior ratio, htm_step.hpp)
 }
 

@@ -664,7 +664,10 @@ int htm_selftest(int device);
  * bound of the logarithm: < 1 ulp).  The wave-level sums of the likelihood (cls_forward.f90:125-132, :210-217, :281-299) have
  * their own modes: 4 = every lane's sum of its wave's 64 values on the matrix pipe (n a multiple of 64), 5 / 6 = x is four blocks
  * of n / 4 values, a wave's four sums taken at once (5) or one by one (6) -- a test compares the associations bit for bit
- * (n a multiple of 256).  Synchronous. */
+ * (n a multiple of 256).  The forms the specialised chain master runs with loop constants in vector registers: 7 = the logarithm
+ * of mode 0 with its ten constants read from registers (must equal mode 0 bit for bit), 8 / 9 = the sums of mode 5 with the lane
+ * classes read from two registers, four values at once (8) or as two pairs (9) (must equal mode 6; n a multiple of 256).
+ * Synchronous. */
 int htm_selftest_math(int device, int which, const double *x, double *y, int n);
 
 /* mod_random's generator (reference src/mod_random.f90:60-74) is linear over GF(2): the state after n draws is
