@@ -137,6 +137,7 @@ SIGNATURES = {
     "htm_chains_handoff_stats": (C.c_int, [vp, C.POINTER(C.c_int64)]),
     "htm_chains_master_stats": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "htm_chains_fixed_master": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "htm_chains_sized_master": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "htm_chains_plan": (C.c_int, [C.POINTER(PlanJob), C.POINTER(PlanDevice), C.POINTER(LaunchPlan)]),
     "htm_chains_get_plan": (C.c_int, [vp, C.POINTER(LaunchPlan), C.POINTER(PlanDevice)]),
     "htm_chains_last_run_stats": (C.c_int, [vp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

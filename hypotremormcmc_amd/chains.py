@@ -298,6 +298,13 @@ class ChainSet:
         check(self._lib.htm_chains_fixed_master(self.handle, C.byref(on), None))
         return bool(on.value)
 
+    def sized_master(self):
+        """(n_chains, ring) that the latest single-rank launch held as compile-time constants -- the specialised master's sized
+        instantiation; (0, 0) if it was no sized launch"""
+        nc = C.c_int(); ring = C.c_int()
+        check(self._lib.htm_chains_sized_master(self.handle, C.byref(nc), C.byref(ring)))
+        return nc.value, ring.value
+
     @property
     def n_worker_blocks(self) -> int:
         on = C.c_int(); n = C.c_int()

@@ -16,19 +16,24 @@ namespace htm {
 // ---- the kernel table's two lookups (htm_host.hpp): the rows of every loop unit -------------------------------------------
 // Three or more stations per lane run the instantiation for any station count (<0, ..>), as they always have; the fp32
 // forward and the masters of htm_flow.hpp / htm_pipe.hpp other than MK 3 and 4 exist for one or two stations per lane only.
-static const LoopKernel *find_row(bool step, bool wide, int nch, bool fp32, int mk)
+// (sized: a row that holds the chain count and / or the ring size as literals -- LoopRow::nc, ::ring, 0: any -- for a launch with
+// `nc` chains on a ring of `ring`; the rows of before hold neither)
+static const LoopRow *find_row(bool step, bool wide, int nch, bool fp32, int mk, bool sized = false, int nc = 0, int ring = 0)
 {
     const int n = (nch == 1 || nch == 2) ? nch : 0;
     const LoopRows units[] = {loop_rows_free(), loop_rows_lock(), loop_rows_barrier(), loop_rows_wide(), loop_rows_pipe()};
     for (const LoopRows &u : units)
         for (size_t k = 0; k < u.n; ++k) {
             const LoopRow &r = u.rows[k];
-            if (r.step == step && r.wide == wide && r.nch == n && r.fp32 == fp32 && r.mk == mk) return &r.k;
+            if (r.step == step && r.wide == wide && r.nch == n && r.fp32 == fp32 && r.mk == mk && sized == (r.nc != 0 || r.ring != 0) &&
+                (r.nc == 0 || r.nc == nc) && (r.ring == 0 || r.ring == ring)) return &r;
         }
     return nullptr;
 }
-const LoopKernel *mcmc_kernel(int nch, bool fp32, int mk, bool wide) { return find_row(false, wide, nch, fp32, mk); }
-const LoopKernel *step_kernel(int nch, bool fp32, bool wide) { return find_row(true, wide, nch, fp32, 0); }
+static const LoopKernel *kernel_of(const LoopRow *r) { return r ? &r->k : nullptr; }
+const LoopKernel *mcmc_kernel(int nch, bool fp32, int mk, bool wide) { return kernel_of(find_row(false, wide, nch, fp32, mk)); }
+const LoopKernel *step_kernel(int nch, bool fp32, bool wide) { return kernel_of(find_row(true, wide, nch, fp32, 0)); }
+const LoopRow *sized_kernel(int nch, bool fp32, int mk, int nc, int ring) { return find_row(false, false, nch, fp32, mk, true, nc, ring); }
 
 int no_kernel(const htm_chains *hc, const char *what, int mk)
 {
@@ -51,10 +56,24 @@ int launch_mcmc(htm_chains *hc, int mode, int target, const double *gathered)
     if (mk == 8 && !h->dev.obs_pack) return fail(HTM_EINVAL, "the specialised chain master needs the forward's packed records");
     const LoopKernel *k = mcmc_kernel(h->nch, h->dev.fp32 != 0, mk, lp.wide);
     if (!k) return no_kernel(hc, "k_mcmc", mk);
+    // Loop 8 with this launch's chain count and ring as literals (k_mcmc_sized), where a row holds exactly these and the mirror is the
+    // full one with its step sizes (what loop 8 is planned with: checked here against the values the kernel is handed).  Any other
+    // launch runs k_mcmc<.., 8> as planned -- the plan does not know the sized kernels.  HTM_SIZED=0: never.
+    int sized_nc = 0, sized_ring = 0;
+    if (mk == 8 && hc->sized && hc->dev.mirror_steps != 0 &&
+        hc->dev.mirror_n == 2 * hc->dev.n_chains + 2 * hc->dev.n_chains * hc->dev.S && hc->dev.S == 64 * h->nch) {
+        if (const LoopRow *rs = sized_kernel(h->nch, h->dev.fp32 != 0, mk, hc->dev.n_chains, lp.ring_size)) {
+            k = &rs->k; sized_nc = rs->nc; sized_ring = rs->ring;
+        }
+    }
+    // (a sized kernel holds what it is handed as literals: the launch's values must be exactly those, and its 512 threads)
+    if ((sized_nc && hc->dev.n_chains != sized_nc) || (sized_ring && l.ring_size != sized_ring) || ((sized_nc || sized_ring) && k->threads != 512))
+        return fail(HTM_EINVAL, "the sized chain master for %d chains and a ring of %d does not fit this launch (%d chains, ring %d, %d threads)",
+                    sized_nc, sized_ring, hc->dev.n_chains, l.ring_size, k->threads);
     // (the specialised master's chain wave keeps its chain's correction pair in registers, htm_flow.hpp FlowOwn: a wave per chain)
     if (mk == 8 && hc->dev.n_chains > std::min(k->threads / 64, 8))
         return fail(HTM_EINVAL, "the specialised chain master runs one chain per wave: %d chains, %d threads", hc->dev.n_chains, k->threads);
-    if (mode == MODE_RUN) hc->last_fixed = mk == 8;
+    if (mode == MODE_RUN) { hc->last_fixed = mk == 8; hc->last_sized_nc = sized_nc; hc->last_sized_ring = sized_ring; }
     if (mk == 5 || mk == 6) { l.smem = lp.pipe_smem; l.ring_size = lp.pipe_ring; }      // (its own LDS layout and stream window)
     // several master workgroups: what their chains share lives in memory (MbShared), set up by a one-wave kernel first
     if (mk == 7) hipLaunchKernelGGL(k_mb_init, dim3(1), dim3(64), 0, h->stream, hc->dev, target);
@@ -241,6 +260,8 @@ static int ctrl_error(const htm_chains *hc)
         return fail(HTM_ESTATE, "several master workgroups: a wait for %s gave up after 5 s (after iteration %d)",
                     hc->h_ctrl.err == -17 ? "the swap record of the iteration before" : hc->h_ctrl.err == -18 ? "the swap partner's record"
                     : hc->h_ctrl.err == -19 ? "the anchor the wave had just written" : "the last iteration's records at the end of the launch", hc->h_ctrl.iter_done);
+    case -22: return fail(HTM_ESTATE, "a sized chain master (k_mcmc_sized) was launched with another chain count, ring size or mirror than it is built for "
+                          "(%d chains, ring %d, mirror %d)", hc->dev.n_chains, hc->plan.ring_size, hc->dev.mirror_n);
     default: return fail(HTM_ESTATE, "device error flag %d", hc->h_ctrl.err);
     }
 }

@@ -339,6 +339,7 @@ int htm_chains_create(htm_forward *h, const htm_chains_init *init, htm_chains **
     htm_chains *hc = guard.hc;
     hc->fwd = h;
     hc->plan = a.loop;
+    hc->sized = kn.sized;
     hc->cap = a.stream_cap;
     ChainsDev &d = hc->dev;
     d.n_chains = nc; d.n_procs = init->n_procs; d.rank = init->rank; d.S = h->S; d.E = h->E;

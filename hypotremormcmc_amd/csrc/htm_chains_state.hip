@@ -278,6 +278,14 @@ int htm_chains_fixed_master(htm_chains *hc, int *on, int *worker_blocks)
     return HTM_OK;
 }
 
+// the chain count and the ring size the latest single-rank launch held as literals (k_mcmc_sized); 0, 0: it was no sized launch
+int htm_chains_sized_master(htm_chains *hc, int *n_chains, int *ring)
+{
+    if (!hc || !n_chains || !ring) return fail(HTM_EINVAL, "NULL argument");
+    *n_chains = hc->last_sized_nc; *ring = hc->last_sized_ring;      // (set by launch_mcmc with last_fixed)
+    return HTM_OK;
+}
+
 int htm_chains_master_stats(htm_chains *hc, int *single_rank_loop, int *lockstep_loop, int64_t *flushes)
 {
     if (!hc) return fail(HTM_EINVAL, "NULL argument");

@@ -240,12 +240,32 @@ struct FlowGeneric {
     static constexpr bool full_rows = false;   // S == 64 * NCH && use_time && use_amp
     static constexpr bool one_rank = false;    // n_procs == 1 (and no lock-step protocol)
     static constexpr bool mirror = false;      // mirror_n == 2 nc + 2 nc S (all parameters but the hypocentres) && mirror_steps
+    static constexpr int n_chains = 0;         // the rank's chains, 0: read at run time (ChainsDev::n_chains)
+    static constexpr int ring = 0;             // positions of the LDS stream window, 0: read at run time (the kernel's ring_size)
 };
 struct FlowFixed {
     static constexpr bool full_rows = true, one_rank = true, mirror = true;
+    static constexpr int n_chains = 0, ring = 0;
 };
+// FlowFixed's answers, and the two sizes a job fixes as well: the chain count, with everything derived from it (the groups'
+// offsets in the parameter vector, the mirror's length, the steps' keys, the window's look-ahead), and the ring, whose ten arrays
+// then sit at literal LDS addresses under a literal mask -- scalars the loop no longer keeps.  The host takes a sized kernel only
+// for a launch with exactly these values (launch_mcmc), and flow_body checks them once more (kErrSized).
+template <int NC, int RING>
+struct FlowSized : FlowFixed {
+    static_assert(NC >= 0 && NC <= 8 && (RING == 0 || (RING >= 256 && (RING & (RING - 1)) == 0)), "a wave per chain; the ring is a power of two");
+    static constexpr int n_chains = NC, ring = RING;
+};
+// a size the traits may know: their literal, else the run-time value
+template <class TR> __device__ __forceinline__ constexpr int flow_nc(int run_time) { return TR::n_chains > 0 ? TR::n_chains : run_time; }
+template <class TR> __device__ __forceinline__ constexpr int flow_ring(int run_time) { return TR::ring > 0 ? TR::ring : run_time; }
+// A sized master with a wave per chain (the chain count a literal, eight chain waves): ONE test at the loop top for everything
+// rare between two steps, `known` handed to the step instead of compared again, no roll-over of the wave's chain.  (With the
+// scalars that the sizes freed this pays; the same change on run-time sizes added spills and lost: DESIGN.md 10.)
+template <class TR> constexpr bool flow_hot_v = TR::n_chains > 0;
+constexpr int kErrSized = -22;    // Ctrl::err: a sized master was launched with another chain count, ring or mirror (never expected)
 
-// every answer fixed: the specialised master (k_mcmc<.., 8>)
+// every answer fixed: the specialised master (k_mcmc<.., 8>, sized or not)
 template <class TR> constexpr bool flow_fixed_v = TR::full_rows && TR::one_rank && TR::mirror;
 
 // the lane's station coordinates, kept in registers for the launch by the specialised master with one station per lane
@@ -584,12 +604,14 @@ __device__ __forceinline__ void flow_lock_finish(CsRef cs_, FlowShared &sh, int 
 // counterpart of chain_pass).  All 64 lanes execute with identical (uniform) values; lane <-> station only inside
 // event_misfit.  `ext`: this wave keeps the LDS window of the stream ahead (chain 0's wave, one round of <= 64 positions
 // per step, in flight under the step's own loads).  Returns the stream position after the step, kFlowRestart or kFlowAbort.
+// (`known`: the step's start and proposal are FlowNext's, as flow_body has just decided from the very words this function
+// compares -- a sized master takes its word for it, flow_hot_v)
 template <int NCH, bool F32, bool LOCK, bool MB = false, class TR = FlowGeneric>
 __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, const Ring &rg, FlowWave &W, FlowNext &nx,
                                          MbShared *g_mb, MbWave &mw, double *s_gath, int wmax,
                                          const double *s_sx, const double *s_sy, const double *s_sz, int c, int p, int iter,
                                          int lane, int wave, int NW, unsigned long long launch, bool ext, int look, int back,
-                                         bool rec_now, const FlowTop &tp, const FlowSta &fs, FlowOwn &own, const LoopRegs &lr)
+                                         bool rec_now, const FlowTop &tp, const FlowSta &fs, FlowOwn &own, const LoopRegs &lr, bool known)
 {
     CsRef cs = rebase(cs_);
     FwRef f = rebase(f_);
@@ -609,7 +631,8 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
         const int fl = sh.fill;
         // (this step is chain c's: the iteration's base lies 4 c .. 6 c positions back; the other waves may still read `back`
         // positions behind it, and want `look` positions ahead of it)
-        fill_to = min(min(p - 4 * c + look, sh.avail), p - 6 * c - back + M + 1);
+        // (a sized master: `avail`, a constant of the launch, came with the batch at the loop top)
+        fill_to = min(min(p - 4 * c + look, flow_hot_v<TR> ? tp.avail : sh.avail), p - 6 * c - back + M + 1);
         // (several master workgroups: the wave has ONE step per iteration for all the draws of the rank's chains -- two rounds)
         if (fill_to > fl + (MB ? 128 : 64)) fill_to = fl + (MB ? 128 : 64);
         if (fill_to > fl) pf_load(pf, cs, sh, fl + lane, fill_to);
@@ -621,17 +644,19 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
     constexpr bool FX = flow_fixed_v<TR>;
     constexpr bool OWN_ROW = flow_own_row_v<TR, NCH>;      // the lane's two corrections in registers (FlowOwn)
     constexpr int LS = NCH == 2 ? 7 : 6;        // (full rows: log2 of the row length)
-    int nc_ = cs.n_chains, nh = 3 * cs.E, psame_ = cs.prior_same;
+    constexpr bool NCK = TR::n_chains > 0;      // the chain count is a literal: no scalar load, no register
+    int nc_ = flow_nc<TR>(cs.n_chains), nh = 3 * cs.E, psame_ = cs.prior_same;
     const int S_ = TR::full_rows ? 64 * NCH : cs.S;
     const void *pack_ = nullptr;
     if constexpr (FX) pack_ = f.obs_pack;
     // (the specialised master: everything the step takes from the kernel arguments in ONE batch of scalar loads -- one wait)
-    if constexpr (FX) asm volatile("" : "+s"(xall_), "+s"(prior_), "+s"(pack_), "+s"(nc_), "+s"(nh), "+s"(psame_));
+    if constexpr (FX && NCK) asm volatile("" : "+s"(xall_), "+s"(prior_), "+s"(pack_), "+s"(nh), "+s"(psame_));
+    else if constexpr (FX) asm volatile("" : "+s"(xall_), "+s"(prior_), "+s"(pack_), "+s"(nc_), "+s"(nh), "+s"(psame_));
     else asm volatile("" : "+s"(xall_), "+s"(prior_));
     // the decoded proposal (htm_stream.hpp), its Gaussian and its judge draw: looked up during the step before (FlowNext), or here
     int type, idx, evt, dec_w;
     double g, r_ring, logr_ring;
-    if (nx.p == p && nx.it == iter && nx.c == c && nx.epoch == W.epoch) {
+    if (flow_hot_v<TR> ? known : (nx.p == p && nx.it == iter && nx.c == c && nx.epoch == W.epoch)) {
         type = nx.type; idx = nx.idx; evt = nx.evt; dec_w = nx.dec_w; g = nx.g; r_ring = nx.r; logr_ring = nx.logr;
     } else {
         const i32x4 dec = reinterpret_cast<const i32x4 *>(rg.dec)[p & M];
@@ -1515,13 +1540,18 @@ __device__ __forceinline__ int flow_step(FwRef f_, CsRef cs_, FlowShared &sh, co
 // (MB: one of several master workgroups of the launch -- block b runs chains 8 b .. 8 b + 7; returns true in the workgroup that
 // finishes last, which has written the launch's end state and releases the workers)
 template <int NCH, bool F32, bool LOCK = false, bool MB = false, class TR = FlowGeneric>
-__device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, int ring_size, int wmax, unsigned long long launch)
+__device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, int ring_arg, int wmax, unsigned long long launch)
 {
     CsRef cs = rebase(cs_);
     FwRef f = rebase(f_);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     FlowShared &sh = *reinterpret_cast<FlowShared *>(smem);
     char *carve = smem + ((sizeof(FlowShared) + 15) & ~size_t(15));
+    // (the sizes the traits know are literals from here on: the ring's arrays, the carve behind them and the mirror at fixed LDS
+    // addresses, everything counted in chains a constant)
+    const int ring_size = flow_ring<TR>(ring_arg);
+    constexpr bool SZ = TR::n_chains > 0 || TR::ring > 0;      // a sized master (FlowSized)
+    const int S_carve = (SZ && TR::full_rows) ? 64 * NCH : f.S;
     Ring rg;
     rg.mask = ring_size - 1;
     rg.U = reinterpret_cast<double *>(carve);          carve += sizeof(double) * ring_size;
@@ -1533,27 +1563,37 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
     rg.sw = reinterpret_cast<int4 *>(carve);           carve += sizeof(int4) * ring_size;
     rg.hop = reinterpret_cast<int *>(carve);           carve += sizeof(int) * kHops * ring_size;
     double *s_sx = reinterpret_cast<double *>(carve);
-    double *s_sy = s_sx + f.S;
-    double *s_sz = s_sy + f.S;
-    double *s_gath = s_sz + f.S;
-    rg.mir_n = cs.mirror_n;
+    double *s_sy = s_sx + S_carve;
+    double *s_sz = s_sy + S_carve;
+    double *s_gath = s_sz + S_carve;
+    // (fixed traits: the full mirror with its step sizes, htm_plan.hpp flow_fixed -- a function of the chain count where that is known)
+    rg.mir_n = (TR::mirror && TR::full_rows && TR::n_chains > 0) ? 2 * TR::n_chains + 2 * TR::n_chains * 64 * NCH : cs.mirror_n;
     rg.mx = s_gath + kGathStage;
     rg.mstep = rg.mx + rg.mir_n;
-    rg.mir_steps = cs.mirror_steps != 0;
+    rg.mir_steps = (TR::mirror && TR::n_chains > 0) ? true : cs.mirror_steps != 0;
     rg.lock = LOCK ? 1 : 0;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int NW = min((int)(blockDim.x >> 6), 8);      // chain waves
-    const int nc = cs.n_chains;
+    const int NW = TR::n_chains > 0 ? 8 : min((int)(blockDim.x >> 6), 8);      // chain waves (a sized master: 512 threads, checked below)
+    const int nc = flow_nc<TR>(cs.n_chains);
     static_assert(!TR::one_rank || (!LOCK && !MB), "fixed answers: the single-rank free-running master of one workgroup");
+    if constexpr (SZ) {
+        // a sized master launched with other sizes than its literals (launch_mcmc refuses such a launch: never expected).  Kernel
+        // arguments and the block size: uniform.  Nothing of the LDS layout has been touched; the launch ends with the named failure
+        if (cs.n_chains != nc || ring_arg != ring_size || cs.mirror_n != rg.mir_n || (cs.mirror_steps != 0) != rg.mir_steps ||
+            blockDim.x != 512u) {
+            if (tid == 0) cs.ctrl->err = kErrSized;
+            return true;
+        }
+    }
     {
         const int vz0 = opaque_zero();
         constexpr int kCtrlWords = (int)(sizeof(Ctrl) / sizeof(int));
         if (tid < kCtrlWords) reinterpret_cast<int *>(&sh.c)[tid] = reinterpret_cast<const int *>(cs.ctrl)[tid + vz0];
         if (tid == kCtrlWords) sh.hop_end = cs.stream.hop_end[vz0];
     }
-    for (int j = tid; j < f.S; j += blockDim.x) { s_sx[j] = f.sx[j]; s_sy[j] = f.sy[j]; s_sz[j] = f.sz[j]; }
+    for (int j = tid; j < S_carve; j += blockDim.x) { s_sx[j] = f.sx[j]; s_sy[j] = f.sy[j]; s_sz[j] = f.sz[j]; }
     for (int k = tid; k < 7 * nc; k += blockDim.x) { sh.np[k] = 0; sh.na[k] = 0; }
 #ifdef HTM_STAMPS
     for (int k = tid; k < 96; k += blockDim.x) sh.stamp_acc[k] = 0ull;
@@ -1672,6 +1712,17 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         BSTAMP(1);
 #endif
+        // (a sized master: ONE test for everything rare between here and the step -- a new epoch, the launch's end or a failure, a
+        // prediction of the wave's that the window did not cover, a start that the step before did not look up.  Formed from the very
+        // words the checks below compare, with the batch just read; `hot` = none of them: every check below is skipped and the step
+        // starts at FlowNext's position.  Else the checks run as they always did, in their order.  The other loops: never hot.)
+        bool hot = false;
+        if constexpr (flow_hot_v<TR>) {
+            const int ne = (uni(tp.epoch) ^ W.epoch) | (nx.epoch ^ W.epoch) | (nx.it ^ iter) | (nx.c ^ c) | uni(tp.err);      // != 0: one of them differs
+            const int ng = W.rpos1 | W.B2 | nx.p | (uni(tp.last_iter) - iter);                                            // < 0: one of them is
+            hot = (ne | (ng >> 31)) == 0;
+        }
+        if (!flow_hot_v<TR> || !hot) {
         {
             const int e = tp.epoch;
             if (__builtin_expect(e != W.epoch, 0)) {
@@ -1690,8 +1741,12 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
             if (W.rpos1 < 0) { W.rpos1 = flow_next_base<MB, TR::one_rank>(cs, sh, rg, W.rpos, nc - W.rc, sh.fill); W.rc1 = 0; }
             if (W.B2 < 0 && W.rpos1 >= 0) W.B2 = flow_next_base<MB, TR::one_rank>(cs, sh, rg, W.rpos1, nc - W.rc1, sh.fill);
         }
-        // where the step starts: known from the step before (FlowNext), or from the hop table now
-        const bool known = nx.p >= 0 && nx.it == iter && nx.c == c && nx.epoch == W.epoch;
+        }
+        // where the step starts: known from the step before (FlowNext: a hot step's always is), or from the hop table now
+        bool known_;
+        if constexpr (flow_hot_v<TR>) known_ = hot || (nx.p >= 0 && nx.it == iter && nx.c == c && nx.epoch == W.epoch);
+        else known_ = nx.p >= 0 && nx.it == iter && nx.c == c && nx.epoch == W.epoch;
+        const bool known = known_;
         // (more than kHops steps from the reference position take chained table entries: every entry read must lie inside the
         // window -- a position past it holds another iteration's numbers, and nothing downstream would notice)
         auto hops_in_window = [&](int pos, int n) __attribute__((always_inline)) {
@@ -1757,7 +1812,7 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
         if constexpr (MB) MB_HIST(mw, (known ? 4 : 0) | (W.epoch & 3));
         BSTAMP(2);
         const int r = flow_step<NCH, F32, LOCK, MB, TR>(f, cs, sh, rg, W, nx, g_mb, mw, s_gath, wmax, s_sx, s_sy, s_sz, c, p, iter, lane, MB ? c : wave,
-                                              MB ? 64 : NW, launch, wave == 0, look, back, rec_phase == 1, tp, fs, own, lr);
+                                              MB ? 64 : NW, launch, wave == 0, look, back, rec_phase == 1, tp, fs, own, lr, known);
         BSTAMP_FROM_HERE();
         if (r == kFlowRestart) continue;      // (nothing was committed: the wave's copies of its chain's corrections stand)
         if (r == kFlowAbort || r == kFlowStop) break;
@@ -1765,9 +1820,10 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
 #ifdef HTM_MB_DIAG
         mw.hist = 0u;
 #endif
-        c += MB ? nc : NW;
-        if (c >= nc) {
-            c = MB ? 8 * mb_b + wave : wave;
+        // (a sized master: a wave per chain -- every step is the wave's last of its iteration, and its chain stays)
+        if constexpr (!flow_hot_v<TR>) c += MB ? nc : NW;
+        if (flow_hot_v<TR> || c >= nc) {
+            if constexpr (!flow_hot_v<TR>) c = MB ? 8 * mb_b + wave : wave;
             iter += 1;
             rec_phase = rec_phase + 1 == n_int ? 0 : rec_phase + 1;
             if (W.rpos1 < 0) {    // (the window did not cover the prediction when it was made: it does now)
@@ -1777,8 +1833,13 @@ __device__ __forceinline__ bool flow_body(FwRef f_, CsRef cs_, int target_arg, i
             W.rc = W.rc1; W.rpos = W.rpos1;
             W.rc1 = 0; W.rpos1 = W.B2 >= 0 ? W.B2 : flow_next_base<MB, TR::one_rank>(cs, sh, rg, W.rpos, nc - W.rc, sh.fill);
             // (the base of the iteration after next: looked up during the step, or from the tables now)
+            if constexpr (flow_hot_v<TR>) {      // (the same five conditions as one test)
+                if ((((nx.p | nx.b3 | W.rpos1) >> 31) | (nx.epoch ^ W.epoch) | (nx.it ^ iter)) == 0) W.B2 = nx.b3;
+                else W.B2 = flow_next_base<MB, TR::one_rank>(cs, sh, rg, W.rpos1, nc, sh.fill);
+            } else {
             if (nx.p >= 0 && nx.epoch == W.epoch && nx.it == iter && nx.b3 >= 0 && W.rpos1 >= 0) W.B2 = nx.b3;
             else W.B2 = flow_next_base<MB, TR::one_rank>(cs, sh, rg, W.rpos1, nc, sh.fill);
+            }
         }
     }
 #ifdef HTM_STAMPS

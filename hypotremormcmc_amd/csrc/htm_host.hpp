@@ -157,7 +157,9 @@ struct htm_chains {
     const double *pending_gathered = nullptr;  // lock-step: records whose swap the next k_step applies
     double *d_gath_host = nullptr, *h_gath_pinned = nullptr;   // staging buffers of htm_chains_step_end_host
     unsigned long long launch_seq = 0;         // k_mcmc launches of this chain set so far (the kernels' launch index)
-    bool last_fixed = false;                   // the latest MODE_RUN launch was the specialised instantiation (k_mcmc<.., 8>)
+    bool last_fixed = false;                   // the latest MODE_RUN launch was the specialised instantiation (k_mcmc<.., 8>, sized or not)
+    int last_sized_nc = 0, last_sized_ring = 0;      // ... the sized one (k_mcmc_sized) with these literals; 0, 0: not
+    bool sized = true;                         // HTM_SIZED=0 at htm_chains_create: never the sized instantiation (A/B runs, tests)
     bool ctrl_fresh = false;                   // h_ctrl is the device's control block as of an idle stream (no launch since it was read)
     htm::ChainsDev dev_np{};                   // view for the non-persistent kernels (partial sums per k_full tile)
     uint32_t init_state[4] = {0, 0, 0, 0};     // mod_random state at stream position 0
@@ -244,14 +246,16 @@ struct LoopLaunch {
     unsigned long long seq;      // the chain set's count of k_mcmc launches (k_step takes none)
 };
 struct LoopKernel { const void *fn; int threads; int (*launch)(const LoopLaunch &); };      // threads 0: the caller chooses (k_step)
-struct LoopRow { bool step, wide; int nch; bool fp32; int mk; LoopKernel k; };
+// (nc, ring: the chain count and the ring size a sized instantiation holds as literals -- 0: any, read at run time)
+struct LoopRow { bool step, wide; int nch; bool fp32; int mk; int nc, ring; LoopKernel k; };
 struct LoopRows { const LoopRow *rows; size_t n; };
 
 const LoopKernel *mcmc_kernel(int nch, bool fp32, int mk, bool wide);      // nullptr: not built
+const LoopRow *sized_kernel(int nch, bool fp32, int mk, int nc, int ring);  // loop mk's row whose literals are these (0 in a row: any); nullptr: none
 const LoopKernel *step_kernel(int nch, bool fp32, bool wide);
 
 // one per loop unit, all searched by the two lookups above (htm_chains_run.hip)
-LoopRows loop_rows_free();         // MK 3, 8: the free-running master of a single rank, generic and specialised
+LoopRows loop_rows_free();         // MK 3, 8: the free-running master of a single rank, generic, specialised and sized
 LoopRows loop_rows_lock();         // MK 4, 7: the free-running master in lock-step, and with several master workgroups
 LoopRows loop_rows_barrier();      // MK 0, 1, 2 and k_step: the loop with barriers
 LoopRows loop_rows_wide();         // k_mcmc_wide, k_step_wide: the loop with barriers for up to kMaxWideChains chains

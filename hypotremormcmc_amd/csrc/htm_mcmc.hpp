@@ -1,4 +1,4 @@
-// htm_mcmc.hpp -- k_mcmc, k_mcmc_wide: the kernel of every persistent launch of the main loop -- the chain master's workgroup(s) in
+// htm_mcmc.hpp -- k_mcmc, k_mcmc_sized, k_mcmc_wide: the kernel of every persistent launch of the main loop -- the chain master's workgroup(s) in
 // front, the full-evaluation workers (htm_worker.hpp) behind them.  MK names the master's loop.  No loop is defined or included
 // here: the three bodies are only declared, and a unit defines the one it instantiates by including that loop's header
 // (htm_step.hpp, htm_flow.hpp or htm_pipe.hpp) next to this one (htm_loop_*.hip).
@@ -10,6 +10,7 @@ namespace htm {
 
 // the loops (their default template arguments stay with their definitions: k_mcmc names every argument)
 struct FlowGeneric; struct FlowFixed;
+template <int NC, int RING> struct FlowSized;
 template <int NCH, bool PERSIST, bool F32, int MK, int CAP>
 __device__ __forceinline__ void step_body(FwRef f_, CsRef cs_, int mode, int target_arg, const double *gathered, int ring_size, int wmax, unsigned long long launch);
 template <int NCH, bool F32, bool LOCK, bool MB, class TR>
@@ -51,6 +52,24 @@ __global__ __launch_bounds__((mcmc_threads<NCH, MK>())) void k_mcmc(FwdDev f, Ch
         if (threadIdx.x == 0) st_agent(&ka.cs.ps->quit, launch + 1ull);
     } else {
         worker_body<NCH, F32, mcmc_threads<NCH, MK>() / 64, (MK == 5 || MK == 6)>(ka.f, ka.cs, launch, (int)blockIdx.x - n_mb);
+    }
+}
+
+// k_mcmc<.., 8> with the chain count and the stream window's ring as literals too (htm_flow.hpp FlowSized): the same arguments,
+// the same 512 threads, the same workers.  launch_mcmc takes it for a launch of loop 8 whose run-time values are exactly these
+// (the kernel table's rows carry them: LoopRow::nc, ::ring); the master checks them once more before it touches anything.
+template <int NCH, bool F32, int NC, int RING>
+__global__ __launch_bounds__(512) void k_mcmc_sized(FwdDev f, ChainsDev cs, int mode, int target_arg,
+                                                     const double *gathered, int ring_size, int wmax,
+                                                     unsigned long long launch)
+{
+    const KArgLayout __attribute__((address_space(4))) &ka = *(const KArgLayout __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+    if (blockIdx.x == 0) {
+        flow_body<NCH, F32, false, false, FlowSized<NC, RING>>(ka.f, ka.cs, target_arg, ring_size, wmax, launch);
+        __syncthreads();
+        if (threadIdx.x == 0) st_agent(&ka.cs.ps->quit, launch + 1ull);
+    } else {
+        worker_body<NCH, F32, 8, false>(ka.f, ka.cs, launch, (int)blockIdx.x - 1);
     }
 }
 

@@ -38,6 +38,7 @@ struct Knobs {
     bool ring_slack = true;        // HTM_RING_SLACK=0 keeps the old ring sizes of up to eight chains (A/B only)
     bool flow = true;              // HTM_FLOW=0 keeps the loop with barriers (step_body)
     bool fast = true;              // HTM_FAST=0 forces the free-running master's generic instantiation (A/B runs, tests)
+    bool sized = true;             // HTM_SIZED=0: loop 8 never takes its sized instantiation (k_mcmc_sized; A/B runs, tests).  No part of the plan
     bool flow_lock = true;         // HTM_FLOW_LOCK=0
     bool pipe = false, pipe_lock = false;    // HTM_PIPE=1 / HTM_PIPE_LOCK=1 (opt-in)
 };
@@ -81,6 +82,7 @@ inline Knobs read_knobs()
     k.ring_slack = !starts("HTM_RING_SLACK", '0');
     k.flow = !starts("HTM_FLOW", '0');
     k.fast = !starts("HTM_FAST", '0');
+    k.sized = !starts("HTM_SIZED", '0');
     k.flow_lock = !starts("HTM_FLOW_LOCK", '0');
     k.pipe = starts("HTM_PIPE", '1');
     k.pipe_lock = starts("HTM_PIPE_LOCK", '1');

@@ -424,6 +424,13 @@ int htm_chains_master_stats(htm_chains *hc, int *single_rank_loop, int *lockstep
  * *worker_blocks (may be NULL) = the worker blocks of a launch.  No reference counterpart (diagnostics). */
 int htm_chains_fixed_master(htm_chains *hc, int *on, int *worker_blocks);
 
+/* *n_chains, *ring = the chain count and the ring size (positions of the stream window in LDS) that the latest single-rank launch
+ * held as compile-time constants: the specialised master's sized instantiation (8 chains on a ring of 512: DESIGN.md 3.0), for
+ * which htm_chains_fixed_master reports 1 as well.  0, 0: the launch was no sized one, or nothing was launched yet.  HTM_SIZED=0
+ * in the environment at htm_chains_create keeps the sized instantiation out (A/B runs, tests).  No reference counterpart
+ * (diagnostics). */
+int htm_chains_sized_master(htm_chains *hc, int *n_chains, int *ring);
+
 /* The launch plan of a chain set: which chain-master loop each mode runs and the shape it is launched with.  htm_chains_create
  * works it out from the job, the environment (the HTM_* switches) and a few facts it asks the device; htm_chains_plan runs the
  * same rules on facts the caller supplies and needs no device, so the plan of any shape can be asked on a machine without a GPU.
