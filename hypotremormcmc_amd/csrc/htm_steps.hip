@@ -25,20 +25,29 @@
 
 using namespace htm;
 
-extern "C" {
-
-int htm_quantiles_dev(int device, const double *d_samples, long n_mod, long n_par, long ld, const int ranks_1based[3],
-                      double *d_out, void *hip_stream)
+namespace {
+// what both forms of the select refuse before any device call
+int select_check(const void *samples, const void *out, long n_mod, long n_par, long ld, const int *ranks_1based)
 {
-    if (!d_samples || !d_out || !ranks_1based) return fail(HTM_EINVAL, "NULL argument");
+    if (!samples || !out || !ranks_1based) return fail(HTM_EINVAL, "NULL argument");
     if (n_mod < 1 || n_par < 1 || ld < n_par) return fail(HTM_EINVAL, "bad shape (n_mod %ld, n_par %ld, ld %ld)", n_mod, n_par, ld);
     // the select kernels count rows in int (LDS counters, the slab histogram's atomics) and take int ranks
     if (n_mod > INT_MAX) return fail(HTM_EINVAL, "n_mod %ld exceeds %d rows per column", n_mod, INT_MAX);
     for (int r = 0; r < 3; ++r)
         if (ranks_1based[r] < 1 || ranks_1based[r] > n_mod)
             return fail(HTM_EINVAL, "rank %d outside 1..%ld (the reference would index outside its sorted column)", ranks_1based[r], n_mod);
-    int rc = use_device(device);
+    return HTM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int htm_quantiles_dev(int device, const double *d_samples, long n_mod, long n_par, long ld, const int ranks_1based[3],
+                      double *d_out, void *hip_stream)
+{
+    int rc = select_check(d_samples, d_out, n_mod, n_par, ld, ranks_1based);
     if (rc) return rc;
+    if ((rc = use_device(device))) return rc;
     const dim3 grid((unsigned)((n_par + 63) / 64)), block(64 * kSelRG);
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const char *force = getenv("HTM_SELECT_SLABS");
@@ -81,11 +90,9 @@ int htm_quantiles_dev(int device, const double *d_samples, long n_mod, long n_pa
 
 int htm_quantiles(int device, const double *samples, long n_mod, long n_par, const int ranks_1based[3], double *out)
 {
-    if (!samples || !out) return fail(HTM_EINVAL, "NULL argument");
-    if (n_mod < 1 || n_par < 1) return fail(HTM_EINVAL, "bad shape");
-    if (n_mod > INT_MAX) return fail(HTM_EINVAL, "n_mod %ld exceeds %d rows per column", n_mod, INT_MAX);
-    int rc = use_device(device);
+    int rc = select_check(samples, out, n_mod, n_par, n_par, ranks_1based);      // the ranks too: not after the upload
     if (rc) return rc;
+    if ((rc = use_device(device))) return rc;
     DevPool pool;
     double *d_x = nullptr, *d_o = nullptr;
     if ((rc = pool.upload(&d_x, samples, (size_t)n_mod * n_par)) || (rc = pool.alloc(&d_o, (size_t)n_par * 3))) return rc;

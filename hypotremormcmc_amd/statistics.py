@@ -69,7 +69,8 @@ def sample_matrix(samples, what, *, n_seq=1, max_lag=1, name="samples", layout="
 
 
 def quantiles(samples: np.ndarray, n_mod: int | None = None, device: int = 0) -> np.ndarray:
-    """[n_par][3] = (il-th, im-th, iu-th smallest) of every column of samples [n_rows][n_par], on the GPU."""
+    """[n_par][3] = (il-th, im-th, iu-th smallest) of every column of samples [n_rows][n_par], on the GPU.  NaN and inf are
+    ordered, not refused: -NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN, NaNs among themselves by payload."""
     x, n_rows = sample_matrix(samples, "htm_quantiles selects over", n_seq=None, finite=False)
     il, im, iu = ranks(n_rows if n_mod is None else n_mod)
     for what, v in (("n_mod", n_mod or 0), ("rank", max(il, im, iu))):

@@ -474,7 +474,9 @@ int htm_chains_profile(htm_chains *hc, int n_iter, double *step_us, int *step_la
  * the elements il = int(0.025*n_mod), im = int(0.5*n_mod), iu = int(0.975*n_mod) (1-based, single-
  * precision products) of the sorted column.  htm_quantiles returns exactly those elements without sorting:
  * samples [n_mod][n_par] row-major (one recorded model per row), ranks_1based[3] = {il, im, iu} or any other
- * three ranks in 1..n_mod, out [n_par][3]; n_mod <= INT_MAX, else HTM_EINVAL before any device call.  Host
+ * three ranks in 1..n_mod (any order, repeats allowed), out [n_par][3]; n_mod <= INT_MAX, else HTM_EINVAL before any device
+ * call, as for a rank outside 1..n_mod.  A column is ordered as a total order on the bits of its doubles: -NaN < -inf < ... <
+ * -0.0 < +0.0 < ... < +inf < +NaN, NaNs among themselves by payload; the element returned keeps its bits.  Host
  * pointers; synchronous.  The _dev form takes device
  * pointers (ld = row stride in doubles) and is asynchronous on `hip_stream` (NULL = the null stream). */
 int htm_quantiles(int device, const double *samples, long n_mod, long n_par, const int ranks_1based[3],
