@@ -60,6 +60,19 @@ class LaunchPlan(C.Structure):
     _fields_ = [(n, C.c_int64) for n in SCALARS] + [("loop", (C.c_int64 * 2) * 3), ("loop_built", (C.c_int64 * 2) * 3)]
 
 
+class LocateRequest(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_sta", "n_events", "job", "n_draws", "volume", "prior", "n_layer", "layer", "forward_fp32")]
+
+
+class LocatePlan(C.Structure):
+    INTS = ("rows", "tpl", "stride", "cells", "n_tiles", "n_marg", "map_cells", "n_draws", "n_draws_padded")
+    PER_EVENT = ("sta", "ev", "part", "logz", "sum", "loc", "marg", "prior", "vol", "w")      # len_*: elements per event of a batch
+    PER_CALL = ("dtc", "dac", "rk", "corr", "vq", "stack", "xy", "xz", "yz", "tally", "layer")      # len_*: elements once per call
+    BYTES = ("per_event_bytes", "table_bytes", "fixed_bytes")
+    _fields_ = ([(n, C.c_int64) for n in INTS] + [("len_" + n, C.c_int64) for n in PER_EVENT + PER_CALL] + [(n, C.c_double) for n in BYTES] +
+                [("nb_limit", C.c_int64 * 4), ("nb", C.c_int64)])
+
+
 # every symbol include/htm_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "htm_last_error": (C.c_char_p, []),
@@ -87,6 +100,7 @@ SIGNATURES = {
     "htm_forward_locate_draw_evidence": (C.c_int, [vp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp]),
     "htm_forward_locate_set_precision": (C.c_int, [vp, C.c_int]),
     "htm_forward_locate_stack": (C.c_int, [vp, C.c_int, dp, dp, dp, dp, dp, dp, ip, C.c_int, dp, dp, dp, dp, dp, dp, dp]),
+    "htm_forward_locate_plan": (C.c_int, [C.POINTER(LocateRequest), dp, C.POINTER(LocatePlan)]),
     "htm_chains_create": (C.c_int, [vp, C.POINTER(ChainsInit), C.POINTER(vp)]),
     "htm_chains_destroy": (C.c_int, [vp]),
     "htm_chains_run": (C.c_int, [vp, C.c_int]),

@@ -1,9 +1,7 @@
 // htm_forward.hip -- the C ABI (include/htm_hip.h) of the forward model over the kernels in htm_kernels.hpp: htm_forward_*,
-// htm_device_*, the library's one last-error string, htm_rng_jump and the self-tests; htm_forward_locate over the kernels in
-// htm_locate.hpp.  What the units share: htm_host.hpp.
-#include "htm_steps_host.hpp"
+// htm_device_*, the library's one last-error string, htm_rng_jump and the self-tests.  What the units share: htm_host.hpp.
+#include "htm_host.hpp"
 #include "htm_forward_kernels.hpp"
-#include "htm_locate.hpp"
 
 #include <cmath>
 #include <cstdarg>
@@ -173,18 +171,6 @@ int ensure_obs_pack(htm_forward *h)
     }
     h->dev.obs_pack = slot;
     return HTM_OK;
-}
-
-// f(std::integral_constant<int, MODE>()) for the run-time mode 0 .. 3 (1: travel times, 2: amplitudes): a kernel family's instantiation
-template <class F>
-static void with_mode(int mode, F f)
-{
-    switch (mode) {
-    case 0: f(std::integral_constant<int, 0>()); break;
-    case 1: f(std::integral_constant<int, 1>()); break;
-    case 2: f(std::integral_constant<int, 2>()); break;
-    default: f(std::integral_constant<int, 3>()); break;
-    }
 }
 
 }  // namespace htm
@@ -515,266 +501,6 @@ int htm_forward_time_full_batch_dev(htm_forward *h, int n_models, const double *
     HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
     *avg_us = 1000.0 * ms / reps;
     return HTM_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// The location posterior of every event of the handle on a grid, under a fixed structure or marginalised over draws of it
-// (include/htm_hip.h; kernels and the partial records: htm_locate.hpp).  The prior is separable: its three tables per event are
-// made here, on the host.  n_draws = 0: htm_forward_locate, one structure (t_corr, a_corr [S]; *vs, *qs) and k_locate;
-// n_draws >= 1: htm_forward_locate_marginal, t_corr, a_corr [n_draws][S], vs, qs [n_draws] and k_locate_marginal; with log_z
-// htm_forward_locate_draw_evidence instead (loc, marg, vol NULL): k_locate_draw_evidence, k_locate_draw_combine, log_z [E][n_draws]
-// and summary [E][4] or NULL.  F32: the single-precision forward of htm_forward_locate_set_precision -- the kernels' F32
-// instantiations, and the draws' table in floats.
-// stk: htm_forward_locate_stack -- the batch volume is always on the device and is not downloaded; after a batch's
-// k_locate_combine k_locate_stack adds the batch's windows to the layers' stacks, after the last batch k_locate_stack_project
-// makes the three maps.  loc may then be NULL.
-struct LocStackOut {
-    const int *layer;       // [E] or NULL: every window in layer 0
-    int n_layer;
-    double *xy, *xz, *yz, *stack, *tally;      // host; stack may be NULL
-};
-extern "C++" {      // (a template, among the C entry points)
-template <bool F32>
-static int locate_run_as(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr, const double *qs,
-                         const double *grid9, const double *prior5, double *loc, double *marg, double *vol, double *log_z, double *summary,
-                         const LocStackOut *stk)
-{
-    typedef LocPairT<loc_real<F32>> Pair;
-    const bool draws = n_draws > 0, evid = log_z != nullptr;
-    LocGrid g{};
-    if (int rc = map_grid_parse(grid9, &g)) return rc;
-    const int n[3] = {g.nx, g.ny, g.nz};
-    const long cells = (long)n[0] * n[1] * n[2];
-    if (cells > (long)INT_MAX) return fail(HTM_EINVAL, "%d x %d x %d cells: more than 2^31 - 1", n[0], n[1], n[2]);
-    const int E = h->E, S = h->S;
-    if (prior5)
-        for (int i = 0; i < E; ++i)
-            if (!(prior5[5 * i + 2] > 0.0) || !(prior5[5 * i + 4] > 0.0))
-                return fail(HTM_EINVAL, "event %d: prior widths w_xy = %g, w_z = %g: need values > 0", i, prior5[5 * i + 2], prior5[5 * i + 4]);
-    double mb;
-    int rc = env_mib("HTM_LOCATE_MB", 1024.0, &mb);
-    if (rc) return rc;
-    // tiles: whole x-rows of one z-layer, at most kLocRows of them and kLocTile cells
-    g.rows = std::max(1, std::min(std::min(n[1], kLocRows), kLocTile / n[0]));
-    g.tpl = (n[1] + g.rows - 1) / g.rows;
-    g.stride = kLocHead + n[0] + 2 * g.rows;
-    const long n_tiles = (long)n[2] * g.tpl;
-    // (a tile that is not a layer's last holds more than 2048 cells or 256 rows of at most 16: at most 2^31 / 256 + 4096 tiles, 2^31 work-items per event)
-    // events per batch: a launch's grid (y <= 65535, 2^32 - 1 work-items) and the workspace under HTM_LOCATE_MB MiB
-    const long nm = (long)n[0] + n[1] + n[2];
-    // the draws' table and the draws as they come (the pack kernel's input) are part of the workspace, once per call
-    const int K = n_draws, Kpad = (K + kLocDraws - 1) / kLocDraws * kLocDraws;
-    // (the draws' evidences: a pair per tile and draw of the padded table, log_z and the summary, the prior's tables)
-    const double per_event = sizeof(double) * (evid ? (double)n_tiles * Kpad * 2.0 + K + 4.0 + nm
-                                                    : (double)n_tiles * g.stride + (vol || stk ? (double)cells : 0.0) + 2.0 * nm + 16.0 + (stk ? 1.0 : 0.0)) +
-                             sizeof(LocSta) * (double)S + sizeof(LocEv);
-    const double table = draws ? sizeof(Pair) * ((double)S + 1.0) * Kpad + sizeof(double) * (2.0 * S + 2.0) * K : 0.0;
-    if (draws && table + per_event > mb * 1048576.0)
-        return fail(HTM_EINVAL, "HTM_LOCATE_MB = %g: the table of %d draws (%.0f bytes) and one event (%.0f bytes) do not fit", mb, K, table, per_event);
-    // the stack: every layer's volume, its three maps and its tally, and the windows' layers, once per call
-    const long map_cells = (long)n[0] * n[1] + (long)n[0] * n[2] + (long)n[1] * n[2];
-    double fixed = 0.0;
-    if (stk) {
-        const double n_out = (double)stk->n_layer * ((double)cells + (double)map_cells + 2.0);
-        if (n_out > (double)INT_MAX)
-            return fail(HTM_EINVAL, "%d layers of %ld + %ld cells and a tally: more than 2^31 - 1 doubles", stk->n_layer, cells, map_cells);
-        fixed = sizeof(double) * n_out + (stk->layer ? sizeof(int) * (double)E : 0.0);
-        if (fixed + table + per_event > mb * 1048576.0)
-            return fail(HTM_EINVAL, "HTM_LOCATE_MB = %g: the stack of %d layers (%.0f bytes)%s and one event (%.0f bytes) do not fit", mb, stk->n_layer, fixed,
-                        draws ? ", the table of the draws" : "", per_event);
-    }
-    long nb = std::min<long>(E, 65535L);
-    nb = std::min(nb, kMaxWorkItems / (n_tiles * kLocThreads));
-    nb = std::min(nb, (kMaxWorkItems - 256) / S);
-    nb = std::min(nb, (long)std::min((mb * 1048576.0 - table - fixed) / per_event, 65535.0));
-    nb = std::max(nb, 1L);
-
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    DevPool pool;
-    LocSta *d_sta = nullptr;
-    LocEv *d_ev = nullptr;
-    double *d_prior = nullptr, *d_part = nullptr, *d_vol = nullptr, *d_loc = nullptr, *d_marg = nullptr, *d_logz = nullptr, *d_sum = nullptr;
-    if ((rc = pool.alloc(&d_sta, (size_t)nb * S)) || (rc = pool.alloc(&d_ev, (size_t)nb))) return rc;
-    if (evid) {
-        if ((rc = pool.alloc(&d_part, (size_t)nb * n_tiles * Kpad * 2)) || (rc = pool.alloc(&d_logz, (size_t)nb * K)) || (rc = pool.alloc(&d_sum, (size_t)nb * 4)))
-            return rc;
-    } else if ((rc = pool.alloc(&d_part, (size_t)nb * n_tiles * g.stride)) || (rc = pool.alloc(&d_loc, (size_t)nb * 16)) ||
-               (rc = pool.alloc(&d_marg, (size_t)nb * nm)))
-        return rc;
-    if (prior5 && (rc = pool.alloc(&d_prior, (size_t)nb * nm))) return rc;
-    if ((vol || stk) && (rc = pool.alloc(&d_vol, (size_t)nb * cells))) return rc;
-    double *d_w = nullptr, *d_stack = nullptr, *d_xy = nullptr, *d_xz = nullptr, *d_yz = nullptr, *d_tally = nullptr;
-    int *d_layer = nullptr;
-    const size_t nl = stk ? (size_t)stk->n_layer : 0;
-    if (stk) {
-        if ((rc = pool.alloc(&d_w, (size_t)nb)) || (rc = pool.alloc(&d_stack, nl * cells)) || (rc = pool.alloc(&d_xy, nl * n[0] * n[1])) ||
-            (rc = pool.alloc(&d_xz, nl * n[0] * n[2])) || (rc = pool.alloc(&d_yz, nl * n[1] * n[2])) || (rc = pool.alloc(&d_tally, nl * 2)))
-            return rc;
-        if (stk->layer && (rc = pool.upload(&d_layer, stk->layer, (size_t)E))) return rc;
-        HIPCHK(hipMemsetAsync(d_stack, 0, nl * cells * sizeof(double), h->stream));
-        HIPCHK(hipMemsetAsync(d_tally, 0, nl * 2 * sizeof(double), h->stream));
-    }
-
-    LocJob jb{};
-    jb.sta = d_sta; jb.ev = d_ev; jb.prior = d_prior; jb.part = d_part; jb.vol = d_vol; jb.S = S;
-    LocDraws<loc_real<F32>> dr{};
-    if (!draws) {
-        HIPCHK(hipMemcpy(h->d_tc, t_corr, (size_t)S * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_ac, a_corr, (size_t)S * sizeof(double), hipMemcpyHostToDevice));
-        jb.rbeta = 1.0 / *vs; jb.katt = (kPi * kFreq) / (*qs * *vs);          // as event_misfit forms them
-        jb.rbeta32 = (float)jb.rbeta; jb.katt32 = (float)jb.katt;
-    } else {
-        // (the station records' tc and ac are not read on this path: k_locate_pack fills them from whatever the handle holds)
-        std::vector<double> rk(2 * (size_t)K);
-        for (int k = 0; k < K; ++k) { rk[k] = 1.0 / vs[k]; rk[(size_t)K + k] = (kPi * kFreq) / (qs[k] * vs[k]); }
-        double *d_dtc = nullptr, *d_dac = nullptr, *d_rk = nullptr;
-        Pair *d_corr = nullptr, *d_vq = nullptr;
-        if ((rc = pool.upload(&d_dtc, t_corr, (size_t)K * S)) || (rc = pool.upload(&d_dac, a_corr, (size_t)K * S)) || (rc = pool.upload(&d_rk, rk.data(), rk.size())) ||
-            (rc = pool.alloc(&d_corr, (size_t)S * Kpad)) || (rc = pool.alloc(&d_vq, (size_t)Kpad)))
-            return rc;
-        hipLaunchKernelGGL(k_locate_pack_draws<loc_real<F32>>, dim3((unsigned)((((long)S + 1) * Kpad + 255) / 256)), dim3(256), 0, h->stream, S, K, Kpad, d_dtc, d_dac, d_rk,
-                           d_rk + K, d_corr, d_vq);
-        dr.vq = d_vq; dr.corr = d_corr; dr.K = K; dr.Kpad = Kpad;
-    }
-    const double log_cell = std::log(g.dx * g.dy * g.dz);
-    const double log_2pi_half = 0.5 * std::log(2.0 * std::acos(-1.0));
-    const int mode = (h->dev.use_time ? 1 : 0) | (h->dev.use_amp ? 2 : 0);
-    std::vector<double> tab;
-    for (long e0 = 0; e0 < E; e0 += nb) {
-        const long m = std::min(nb, (long)E - e0);
-        if (prior5) {
-            // log densities per ix, iy (normalised Gaussians) and iz (the depth prior of cls_model.f90:178-185, normalised;
-            // -inf at and below z0)
-            tab.resize((size_t)m * nm);
-            for (long b = 0; b < m; ++b) {
-                const double *p = prior5 + 5 * (e0 + b);
-                double *q = tab.data() + (size_t)b * nm;
-                const double lw = std::log(p[2]), lwz = std::log(p[4]);
-                for (int i = 0; i < n[0]; ++i) { const double d = map_centre(g.x0, g.dx, i) - p[0]; q[i] = (-log_2pi_half - lw) - d * d / (2.0 * p[2] * p[2]); }
-                for (int i = 0; i < n[1]; ++i) { const double d = map_centre(g.y0, g.dy, i) - p[1]; q[n[0] + i] = (-log_2pi_half - lw) - d * d / (2.0 * p[2] * p[2]); }
-                for (int i = 0; i < n[2]; ++i) {
-                    const double d = map_centre(g.z0, g.dz, i) - p[3];
-                    q[n[0] + n[1] + i] = d > 0.0 ? (std::log(d) - 2.0 * lwz) - d * d / (2.0 * p[4] * p[4]) : -INFINITY;
-                }
-            }
-            HIPCHK(hipMemcpy(d_prior, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-        hipLaunchKernelGGL(k_locate_pack, dim3((unsigned)((m * S + 255) / 256)), dim3(256), 0, h->stream, h->dev, (int)e0, (int)m, h->d_tc, h->d_ac,
-                           h->d_lconst_t, h->d_lconst_a, d_sta, d_ev);
-        const dim3 grid((unsigned)n_tiles, (unsigned)m), block(kLocThreads);
-        with_mode(mode, [&](auto M) {
-            constexpr int MODE = decltype(M)::value;
-            if (!draws) hipLaunchKernelGGL((k_locate<MODE, F32>), grid, block, 0, h->stream, g, jb);
-            else if (evid) hipLaunchKernelGGL((k_locate_draw_evidence<MODE, F32>), grid, block, 0, h->stream, g, jb, dr);
-            else hipLaunchKernelGGL((k_locate_marginal<MODE, F32>), grid, block, 0, h->stream, g, jb, dr);
-        });
-        if (evid)
-            hipLaunchKernelGGL(k_locate_draw_combine, dim3((unsigned)m), dim3(256), 0, h->stream, (int)n_tiles, K, Kpad, d_part, log_cell, d_logz, d_sum);
-        else
-            hipLaunchKernelGGL(k_locate_combine, dim3((unsigned)m), dim3(256), 0, h->stream, g, d_part, log_cell, d_loc, d_marg, d_w);
-        if (stk)
-            hipLaunchKernelGGL(k_locate_stack, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->stream, cells, (int)m, (int)e0, d_vol, d_loc, d_w, d_layer,
-                               stk->n_layer, d_stack, d_tally);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (evid) {
-            if ((rc = pool.download(log_z + (size_t)e0 * K, d_logz, (size_t)m * K, "the draws' evidences'"))) return rc;
-            if (summary && (rc = pool.download(summary + (size_t)e0 * 4, d_sum, (size_t)m * 4, "the draws' summary's"))) return rc;
-            continue;
-        }
-        if (loc && (rc = pool.download(loc + (size_t)e0 * 16, d_loc, (size_t)m * 16, "the locations'"))) return rc;
-        if (marg && (rc = pool.download(marg + (size_t)e0 * nm, d_marg, (size_t)m * nm, "the marginals'"))) return rc;
-        if (vol && (rc = pool.download(vol + (size_t)e0 * cells, d_vol, (size_t)m * cells, "the volume's"))) return rc;
-    }
-    if (stk) {
-        const long most = std::max((long)nl * std::max((long)n[0] * n[1], (long)n[0] * n[2]), 64L * (long)nl * n[1] * n[2]);
-        const unsigned blocks = (unsigned)std::min((most + 255) / 256, 1L << 20);
-        hipLaunchKernelGGL(k_locate_stack_project, dim3(blocks), dim3(256), 0, h->stream, g, stk->n_layer, d_stack, d_xy, d_xz, d_yz);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if ((rc = pool.download(stk->xy, d_xy, nl * n[0] * n[1], "the xy map's")) || (rc = pool.download(stk->xz, d_xz, nl * n[0] * n[2], "the xz map's")) ||
-            (rc = pool.download(stk->yz, d_yz, nl * n[1] * n[2], "the yz map's")) || (rc = pool.download(stk->tally, d_tally, nl * 2, "the tally's")))
-            return rc;
-        if (stk->stack && (rc = pool.download(stk->stack, d_stack, nl * cells, "the stack's"))) return rc;
-    }
-    return HTM_OK;
-}
-}  // extern "C++"
-
-static int locate_run(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr, const double *qs,
-                      const double *grid9, const double *prior5, double *loc, double *marg, double *vol, double *log_z = nullptr,
-                      double *summary = nullptr, const LocStackOut *stk = nullptr)
-{
-    return h->loc_fp32 ? locate_run_as<true>(h, n_draws, t_corr, vs, a_corr, qs, grid9, prior5, loc, marg, vol, log_z, summary, stk)
-                       : locate_run_as<false>(h, n_draws, t_corr, vs, a_corr, qs, grid9, prior5, loc, marg, vol, log_z, summary, stk);
-}
-
-// The arithmetic of the three locate entry points on this handle (include/htm_hip.h); step 5's switch is htm_forward_set_precision
-int htm_forward_locate_set_precision(htm_forward *h, int forward_fp32)
-{
-    if (!h) return fail(HTM_EINVAL, "NULL handle");
-    if (forward_fp32 != 0 && forward_fp32 != 1) return fail(HTM_EINVAL, "forward_fp32 = %d: need 0 (fp64) or 1 (fp32)", forward_fp32);
-    h->loc_fp32 = forward_fp32 != 0;
-    return HTM_OK;
-}
-
-int htm_forward_locate(htm_forward *h, const double *t_corr, double vs, const double *a_corr, double qs, const double *grid9,
-                       const double *prior5, double *loc, double *marg, double *vol)
-{
-    if (!h) return fail(HTM_EINVAL, "NULL handle");
-    if (!t_corr || !a_corr || !grid9 || !loc) return fail(HTM_EINVAL, "NULL argument");
-    if (!std::isfinite(vs) || !std::isfinite(qs) || !(vs > 0.0) || !(qs > 0.0))
-        return fail(HTM_EINVAL, "vs = %g, qs = %g: need finite values > 0", vs, qs);
-    return locate_run(h, 0, t_corr, &vs, a_corr, &qs, grid9, prior5, loc, marg, vol);
-}
-
-// what both entry points over draws ask of them
-static int locate_draws_ok(int n_draws, const double *vs, const double *qs)
-{
-    if (n_draws < 1 || n_draws > kLocMaxDraws) return fail(HTM_EINVAL, "n_draws = %d: need 1..%d", n_draws, kLocMaxDraws);
-    for (int k = 0; k < n_draws; ++k)
-        if (!std::isfinite(vs[k]) || !std::isfinite(qs[k]) || !(vs[k] > 0.0) || !(qs[k] > 0.0))
-            return fail(HTM_EINVAL, "draw %d: vs = %g, qs = %g: need finite values > 0", k, vs[k], qs[k]);
-    return HTM_OK;
-}
-
-int htm_forward_locate_marginal(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr, const double *qs,
-                                const double *grid9, const double *prior5, double *loc, double *marg, double *vol)
-{
-    if (!h) return fail(HTM_EINVAL, "NULL handle");
-    if (!t_corr || !vs || !a_corr || !qs || !grid9 || !loc) return fail(HTM_EINVAL, "NULL argument");
-    if (int rc = locate_draws_ok(n_draws, vs, qs)) return rc;
-    return locate_run(h, n_draws, t_corr, vs, a_corr, qs, grid9, prior5, loc, marg, vol);
-}
-
-int htm_forward_locate_draw_evidence(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr, const double *qs,
-                                     const double *grid9, const double *prior5, double *log_z, double *summary)
-{
-    if (!h) return fail(HTM_EINVAL, "NULL handle");
-    if (!t_corr || !vs || !a_corr || !qs || !grid9 || !log_z) return fail(HTM_EINVAL, "NULL argument");
-    if (int rc = locate_draws_ok(n_draws, vs, qs)) return rc;
-    return locate_run(h, n_draws, t_corr, vs, a_corr, qs, grid9, prior5, nullptr, nullptr, nullptr, log_z, summary);
-}
-
-// The stacked density of the windows' posteriors (include/htm_hip.h): n_draws = 0 htm_forward_locate's
-// structure (*vs, *qs), n_draws >= 1 htm_forward_locate_marginal's
-int htm_forward_locate_stack(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr, const double *qs,
-                             const double *grid9, const double *prior5, const int *layer, int n_layer, double *loc, double *marg, double *xy,
-                             double *xz, double *yz, double *stack, double *tally)
-{
-    if (!h) return fail(HTM_EINVAL, "NULL handle");
-    if (!t_corr || !vs || !a_corr || !qs || !grid9) return fail(HTM_EINVAL, "NULL argument");
-    if (n_draws == 0) {
-        if (!std::isfinite(*vs) || !std::isfinite(*qs) || !(*vs > 0.0) || !(*qs > 0.0))
-            return fail(HTM_EINVAL, "vs = %g, qs = %g: need finite values > 0", *vs, *qs);
-    } else if (int rc = locate_draws_ok(n_draws, vs, qs))
-        return rc;
-    if (n_layer < 1) return fail(HTM_EINVAL, "n_layer = %d: need at least 1", n_layer);
-    if (!layer && n_layer != 1) return fail(HTM_EINVAL, "n_layer = %d without a layer per window", n_layer);
-    if (!xy || !xz || !yz || !tally) return fail(HTM_EINVAL, "NULL output: xy, xz, yz and tally are required");
-    const LocStackOut stk{layer, n_layer, xy, xz, yz, stack, tally};
-    return locate_run(h, n_draws, t_corr, vs, a_corr, qs, grid9, prior5, loc, marg, nullptr, nullptr, nullptr, &stk);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -1,10 +1,17 @@
 // htm_grid.hpp -- the map grid of the analysis programs, stated once: the box that htm_hypo_density bins samples on
 // (htm_density.hpp) and that htm_forward_locate tabulates posteriors on (htm_locate.hpp).  For host and device code; no call
-// into the HIP runtime.  The caller's form is grid9 = {x0, dx, nx, y0, dy, ny, z0, dz, nz} in doubles (include/htm_hip.h).
+// into the HIP runtime, and nothing of HIP included: a plain C++ compiler reads it too (htm_locate_plan.hpp).  The caller's form is
+// grid9 = {x0, dx, nx, y0, dy, ny, z0, dz, nz} in doubles (include/htm_hip.h).
 #pragma once
 #include <cmath>
 
-#include "htm_host.hpp"      // fail
+#include "htm_limits.hpp"      // fail
+
+#ifdef __HIPCC__
+#define HTM_GRID_FN __host__ __device__ __forceinline__
+#else
+#define HTM_GRID_FN inline
+#endif
 
 #pragma GCC visibility push(hidden)
 
@@ -20,7 +27,7 @@ struct MapGrid {
 };
 
 // the centre of cell i: one multiplication, then one addition (the library is built with -ffp-contract=off)
-__host__ __device__ __forceinline__ double map_centre(double v0, double dv, int i)
+HTM_GRID_FN double map_centre(double v0, double dv, int i)
 {
     const double t = ((double)i + 0.5) * dv;
     return v0 + t;

@@ -1,8 +1,12 @@
 // htm_host.hpp -- what the host translation units of libhtm_hip.so share.  Internal: not installed, not part of the ABI
 // (include/htm_hip.h is).
 //
-//   htm_forward.hip        htm_forward_*, htm_device_*, the last-error string, the self-tests and htm_rng_jump; htm_forward_locate
-//                          (the location posteriors on a grid, kernels: htm_locate.hpp)
+//   htm_forward.hip        htm_forward_* of step 5, htm_device_*, the last-error string, the self-tests and htm_rng_jump
+//   htm_locate.hip         htm_forward_locate* (the location posteriors on a grid, their marginal over draws, the draws' evidences,
+//                          the stacked density) on a forward handle; the one unit with the kernels of htm_locate.hpp
+//   htm_locate_plan.hpp    the batch plan of a locate call: the grid's tiles, every device array's length, the bytes under
+//                          HTM_LOCATE_MB and the events per batch, worked out by plain functions without a device and without
+//                          HIP.  Ask for the plan of a shape with htm_forward_locate_plan (no GPU needed)
 //   htm_chains_setup.hip   the chain sets' part of the C ABI, four units, none of which instantiates a k_mcmc.  Set-up: the plan
 //                          (htm_chains_plan, htm_chains_get_plan), htm_chains_create / _destroy / _share_gpu, the inbox of
 //                          the in-kernel exchange.  The only unit that takes sizes from the loops (htm_flow.hpp, htm_pipe.hpp,
@@ -24,9 +28,9 @@
 //                          htm_flow.hpp).  tests/test_loop_unit_headers.py holds every unit to the headers of its loop
 //   htm_steps.hip          steps 1-4, 6, the convergence diagnostics and the location error ellipsoids (htm_hypo_ellipsoid*);
 //                          touches neither htm_forward nor htm_chains
-//   htm_steps_host.hpp     the host idioms of htm_steps.hip, and of htm_forward_locate in htm_forward.hip: StreamBuf, a
-//                          stream-ordered workspace that hands out typed pieces; DevPool, the device arrays of a host-pointer
-//                          form (alloc, upload, download); kMaxWorkItems, the limit of one launch; env_mib, an HTM_x_MB switch
+//   htm_steps_host.hpp     the host idioms of htm_steps.hip and htm_locate.hip: StreamBuf, a stream-ordered workspace that
+//                          hands out typed pieces; DevPool, the device arrays of a host-pointer form (alloc, upload, download)
+//   htm_limits.hpp         kMaxWorkItems, the limit of one launch; env_mib, an HTM_x_MB switch.  Without HIP, for the plans
 //
 // Host code is plain C++17 + the HIP runtime: no torch, no third-party dependency.  There is no CPU fallback on purpose:
 // every entry point needs a usable HIP device and fails with HTM_ENODEVICE otherwise.

@@ -1,5 +1,5 @@
 // htm_locate.hpp -- every window's location posterior on a grid under a FIXED structure (vs, qs, station corrections): the
-// kernels of htm_forward_locate (htm_forward.hip; rule, choices and measurements: DESIGN.md §3.10).  With the global parameters
+// kernels of htm_forward_locate (htm_locate.hip; rule, choices and measurements: DESIGN.md §3.10).  With the global parameters
 // fixed the log-likelihood is a sum of independent per-event terms (each event is demeaned on its own: cls_forward.f90:113-133,
 // :199-218, :268-303), so an event's term is a function of its position alone and is tabulated at the cell centres (htm_grid.hpp).
 //
@@ -42,29 +42,20 @@
 #include <type_traits>
 
 #include "htm_device.hpp"
-#include "htm_grid.hpp"
+#include "htm_locate_plan.hpp"      // the tile's constants, LocSta, LocEv, LocPairT, LocGrid: shared with the host's plan, defined there
 
 namespace htm {
 
-constexpr int kLocThreads = 256;
-constexpr int kLocPerThread = 16;       // cells of a tile per thread
-constexpr int kLocChunk = 4;            // of them evaluated side by side
-constexpr int kLocTile = kLocThreads * kLocPerThread;
-constexpr int kLocRows = 256;           // x-rows per tile at the most
-constexpr int kLocHead = 4;
-static_assert(kLocTile >= kMapMaxCells, "a tile holds at least one whole x-row");
+// (the kernels' argument, as this compiler lays it out)
+static_assert(sizeof(LocGrid) == 72, "rows, tpl and stride follow nz directly, in MapGrid's tail padding (htm_grid.hpp)");
+
+constexpr int kLocChunk = 4;            // cells of a thread evaluated side by side
 static_assert(kLocPerThread % kLocChunk == 0, "whole chunks");
-// k_locate_marginal: draws per block and cells of a thread side by side (the choice and its alternatives: DESIGN.md 3.11)
-#ifndef HTM_LOCM_DRAWS
-#define HTM_LOCM_DRAWS 8
-#endif
+// k_locate_marginal: cells of a thread side by side (the choice and its alternatives: DESIGN.md 3.11)
 #ifndef HTM_LOCM_CELLS
 #define HTM_LOCM_CELLS 1
 #endif
-constexpr int kLocDraws = HTM_LOCM_DRAWS;
 constexpr int kLocmCells = HTM_LOCM_CELLS;
-constexpr int kLocMaxDraws = 4096;      // draws per call (include/htm_hip.h)
-static_assert(kLocDraws >= 1 && kLocMaxDraws % kLocDraws == 0, "whole blocks of draws");
 static_assert(kLocmCells >= 1 && kLocPerThread % kLocmCells == 0, "whole chunks");
 // the same two choices for the F32 instantiations, whose register budget is another (measured: DESIGN.md 3.13)
 #ifndef HTM_LOC_CHUNK32
@@ -76,25 +67,6 @@ static_assert(kLocmCells >= 1 && kLocPerThread % kLocmCells == 0, "whole chunks"
 constexpr int kLocChunk32 = HTM_LOC_CHUNK32;
 constexpr int kLocmCells32 = HTM_LOCM_CELLS32;
 static_assert(kLocChunk32 >= 1 && kLocPerThread % kLocChunk32 == 0 && kLocmCells32 >= 1 && kLocPerThread % kLocmCells32 == 0, "whole chunks");
-
-// what the evaluation reads of one station for one event; 80 bytes, read with scalar loads.  tc32, ac32: tc and ac rounded to
-// float, for the single-precision forward
-struct __attribute__((aligned(16))) LocSta {
-    double sx, sy, sz, tc, ac, tob, tpr, aob, apr;
-    float tc32, ac32;
-};
-static_assert(sizeof(LocSta) == 80, "nine doubles and two floats: the record kept its size");
-// per event: 1 / sum of precisions (time, amplitude) and sum_j (log_2pi_half + log stdv_j) (time, amplitude)
-struct __attribute__((aligned(16))) LocEv {
-    double rpst, rpsa, ct, ca;
-};
-
-struct LocGrid : MapGrid {
-    int rows;        // x-rows per tile
-    int tpl;         // tiles per z-layer
-    int stride;      // doubles per partial record
-};
-static_assert(sizeof(LocGrid) == 72, "rows, tpl and stride follow nz directly, in MapGrid's tail padding (htm_grid.hpp)");
 
 struct LocJob {
     const LocSta *sta;      // [nb][S]
@@ -273,13 +245,7 @@ __device__ __forceinline__ void loc_tile_reduce(const LocGrid &g, const LocJob &
     }
 }
 
-// a pair of T: doubles, or the floats of the single-precision forward
-template <class T>
-struct __attribute__((aligned(2 * sizeof(T)))) LocPairT {
-    T a, b;
-};
-typedef LocPairT<double> LocPair;
-// D pairs at a wave-uniform address, aligned to the pair, through the constant address space: scalar loads
+// D pairs (LocPairT: htm_locate_plan.hpp) at a wave-uniform address, aligned to the pair, through the constant address space: scalar loads
 template <class T, int D>
 __device__ __forceinline__ void loc_ld_pairs(const LocPairT<T> *p, T (&a)[D], T (&b)[D])
 {

@@ -1,8 +1,10 @@
-// htm_steps_host.hpp -- the host idioms that the entry points of htm_steps.hip share, and htm_forward_locate (htm_forward.hip)
+// htm_steps_host.hpp -- the host idioms that the entry points of htm_steps.hip share, and the locate entry points (htm_locate.hip)
 // with them.  Internal: the handles of htm_forward.hip and htm_chains_setup.hip keep their own pools (dev_alloc / dev_upload of htm_host.hpp).
-// StreamBuf is the workspace of a *_dev form, DevPool the device arrays of a host-pointer form; kMaxWorkItems, env_mib, Int<N>.
+// StreamBuf is the workspace of a *_dev form, DevPool the device arrays of a host-pointer form; Int<N>; kMaxWorkItems and env_mib
+// come with htm_limits.hpp.
 #pragma once
 #include "htm_host.hpp"
+#include "htm_limits.hpp"
 
 #include <type_traits>
 
@@ -10,23 +12,9 @@
 
 namespace htm {
 
-// the dispatch packet holds a launch's grid in work-items as a uint32_t (hsa_kernel_dispatch_packet_t::grid_size_x)
-constexpr long kMaxWorkItems = 0xffffffffL;
-
 // a template argument chosen at run time: switch (r) { case 2: launch(Int<2>()); ... } with one generic lambda `launch`
 template <int N>
 using Int = std::integral_constant<int, N>;
-
-// HTM_x_MB: a positive number of MiB, `dflt` when the switch is not set
-inline int env_mib(const char *name, double dflt, double *mb)
-{
-    *mb = dflt;
-    if (const char *e = getenv(name)) {
-        *mb = atof(e);
-        if (!(*mb > 0.0)) return fail(HTM_EINVAL, "%s = %s: a positive number of MiB", name, e);
-    }
-    return HTM_OK;
-}
 
 // Workspace on a stream: one block, handed out in typed pieces.  alloc(st, carve) runs `carve`, a function of the buffer that
 // take()s every array, twice: once to add the lengths up, once on the block (at least a byte; hipMallocAsync, or hipMalloc where

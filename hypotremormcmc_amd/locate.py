@@ -188,6 +188,35 @@ def stack(fwd, t_corr, vs, a_corr, qs, grid, prior=None, layer=None, n_layer=1, 
     return dict(_result(loc, marg, None, nx, ny), **out)
 
 
+JOBS = {"fixed": 0, "marginal": 1, "draw_evidence": 2}      # HTM_LOCATE_FIXED .. of include/htm_hip.h
+
+
+def plan(n_sta, n_events, grid, job="fixed", n_draws=0, volume=False, prior=False, n_layer=0, layer=False, precision="fp64"):
+    """The workspace and the batches of a call of that shape under the HTM_LOCATE_MB of the environment, without a Forward and
+    without a GPU (htm_forward_locate_plan, which states the formula): job "fixed" (`locate`), "marginal" (`locate_marginal`) or
+    "draw_evidence" with n_draws; volume and prior: whether the call has them; n_layer >= 1: `stack`, with a layer per window
+    or not.  Returns a dict: rows, tpl, stride, cells, n_tiles, n_marg, map_cells, n_draws, n_draws_padded; per_event and
+    per_call, the elements of every device array by name; per_event_bytes, table_bytes, fixed_bytes; nb_limit [4] and nb, the
+    events per batch.  A shape that the call would refuse raises HtmError with the call's message."""
+    if job not in JOBS:
+        raise ValueError(f"job {job!r}: need one of {sorted(JOBS)}")
+    if precision not in ("fp32", "fp64"):
+        raise ValueError(f"locate precision {precision!r}: need 'fp32' or 'fp64'")
+    rq = _lib.LocateRequest(int(n_sta), int(n_events), JOBS[job], int(n_draws), int(bool(volume)), int(bool(prior)), int(n_layer),
+                            int(bool(layer)), int(precision == "fp32"))
+    g = np.ascontiguousarray(grid, dtype=np.float64).reshape(-1)
+    if g.size != 9:
+        raise ValueError(f"grid has {g.size} values: need x0, dx, nx, y0, dy, ny, z0, dz, nz")
+    p = _lib.LocatePlan()
+    _lib.check(_lib.load().htm_forward_locate_plan(rq, _lib.ptr(g), p))
+    d = {n: int(getattr(p, n)) for n in _lib.LocatePlan.INTS + ("nb",)}
+    d.update({n: float(getattr(p, n)) for n in _lib.LocatePlan.BYTES})
+    d["per_event"] = {n: int(getattr(p, "len_" + n)) for n in _lib.LocatePlan.PER_EVENT}
+    d["per_call"] = {n: int(getattr(p, "len_" + n)) for n in _lib.LocatePlan.PER_CALL}
+    d["nb_limit"] = [int(v) for v in p.nb_limit]
+    return d
+
+
 def draw_weights(log_z):
     """log_z [E][K] (or one row) -> the normalised weights of the draws per window, exp(log_z - max) over their sum; NaN for a
     window without a cell (every log_z -inf)"""

@@ -153,7 +153,8 @@ int htm_forward_time_full_batch_dev(htm_forward *h, int n_models, const double *
  * NULL handle or output, vs or qs not finite or <= 0, a bad grid, w_xy or w_z <= 0: HTM_EINVAL before any device call.
  * Synchronous.  Every sum has a fixed order: two calls give the same bits.  The events go to the device in batches so that no
  * launch passes 2^32 - 1 work-items and the workspace, the device copy of vol included, stays under HTM_LOCATE_MB MiB
- * (environment, default 1024; one event at the least); the result does not depend on it. */
+ * (environment, default 1024; one event at the least; what is counted: htm_forward_locate_plan, below); the result does not
+ * depend on it. */
 int htm_forward_locate(htm_forward *h, const double *t_corr, double vs, const double *a_corr, double qs,
                        const double *grid9, const double *prior5, double *loc, double *marg, double *vol);
 
@@ -168,7 +169,7 @@ int htm_forward_locate(htm_forward *h, const double *t_corr, double vs, const do
  * absolute terms among its draws.
  * Refused with HTM_EINVAL before any device call: whatever htm_forward_locate refuses; n_draws outside 1..4096; a vs[k] or
  * qs[k] that is not finite or <= 0 (the message names the draw).  The table of the draws is part of the workspace under
- * HTM_LOCATE_MB: when it and one event do not fit, HTM_EINVAL names the variable.  Synchronous; every sum has a fixed order,
+ * HTM_LOCATE_MB (htm_forward_locate_plan): when it and one event do not fit, HTM_EINVAL names the variable.  Synchronous; every sum has a fixed order,
  * the draws are taken in their order: two calls give the same bits, and the bits do not depend on the batching. */
 int htm_forward_locate_marginal(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr,
                                 const double *qs, const double *grid9, const double *prior5, double *loc, double *marg,
@@ -188,9 +189,8 @@ int htm_forward_locate_marginal(htm_forward *h, int n_draws, const double *t_cor
  * 0.5: one draw outweighs all the others together) says that the marginalised intervals of that window are one structure's:
  * n_draws was too small for it.
  * Refused with HTM_EINVAL before any device call: whatever htm_forward_locate_marginal refuses, with its messages, and a NULL
- * log_z.  The workspace of an event is n_tiles * Kpad * 2 + n_draws + 4 doubles (Kpad: n_draws padded to whole blocks of 8)
- * next to its prior tables and station records; it and the draws' table stay under HTM_LOCATE_MB as there, and when the table
- * and one event do not fit, HTM_EINVAL names the variable.  Synchronous; every sum has a fixed order and there are no
+ * log_z.  The workspace of an event and the draws' table stay under HTM_LOCATE_MB as there (htm_forward_locate_plan), and when
+ * the table and one event do not fit, HTM_EINVAL names the variable.  Synchronous; every sum has a fixed order and there are no
  * floating-point atomics: two calls give the same bits, and the bits do not depend on the batching. */
 int htm_forward_locate_draw_evidence(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr,
                                      const double *qs, const double *grid9, const double *prior5, double *log_z,
@@ -241,11 +241,8 @@ int htm_forward_locate_set_precision(htm_forward *h, int forward_fp32);
  * loc[4], n the layer's windows; a layer's stack and each of its maps sum to tally[L][0] to (2e-12 + cells 2^-53) relative.
  * htm_forward_locate_set_precision applies: it changes lp, and the stack consumes lp.
  * No floating-point atomics: two calls give the same bits, and the bits do not depend on HTM_LOCATE_MB -- a cell's running
- * total goes through memory unchanged from one batch to the next.  The workspace: per event of a batch
- *   8 (n_tiles stride + cells + 1 + 2 (nx + ny + nz) + 16) + 80 n_sta + 32 bytes
- * (rows = max(1, min(ny, 256, 4096 / nx)) x-rows per tile, n_tiles = nz ceil(ny / rows), stride = 4 + nx + 2 rows), and once
- * per call 8 n_layer (cells + nx ny + nx nz + ny nz + 2) bytes, 4 n_events for the layers where they are given, and the draws'
- * table as for htm_forward_locate_marginal.
+ * total goes through memory unchanged from one batch to the next.  The workspace per event of a batch holds the event's volume,
+ * and the stacks, their maps, their tallies and the windows' layers are counted once per call (htm_forward_locate_plan).
  * Refused with HTM_EINVAL and a message before any device call, the outputs untouched: whatever those two entry points refuse;
  * n_layer < 1; layer == NULL with n_layer != 1; a NULL xy, xz, yz or tally; n_layer (cells + nx ny + nx nz + ny nz + 2) above
  * 2^31 - 1; the once-per-call part and one event not fitting under HTM_LOCATE_MB (the message names the variable).
@@ -253,6 +250,51 @@ int htm_forward_locate_set_precision(htm_forward *h, int forward_fp32);
 int htm_forward_locate_stack(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr,
                              const double *qs, const double *grid9, const double *prior5, const int *layer, int n_layer,
                              double *loc, double *marg, double *xy, double *xz, double *yz, double *stack, double *tally);
+
+/* THE WORKSPACE AND THE BATCHES of the four entry points above, worked out without a handle and without a device: what a call
+ * of that shape would allocate and how many events it would send at a time, or the refusal it would meet, with the same code
+ * and text.  HTM_LOCATE_MB is read from the environment as a call reads it.  The request names what a call says through its
+ * arguments: `job` 0 htm_forward_locate, 1 htm_forward_locate_marginal, 2 htm_forward_locate_draw_evidence (n_draws 0 for
+ * job 0, 1..4096 otherwise); `volume`: vol is asked for; `prior`: prior5 is given; n_layer >= 1: htm_forward_locate_stack
+ * (jobs 0 and 1; 0: no stack) with `layer` given or not; forward_fp32: htm_forward_locate_set_precision's setting.
+ * THE FORMULA, stated here once.  With cells = nx ny nz, n_marg = nx + ny + nz, rows = max(1, min(ny, 256, 4096 / nx)) x-rows
+ * per tile, tpl = ceil(ny / rows) tiles per z-layer, n_tiles = nz tpl, stride = 4 + nx + 2 rows doubles per tile, Kpad = n_draws
+ * padded to whole blocks of 8:
+ *   per event of a batch, bytes:
+ *     jobs 0, 1   8 (n_tiles stride + 16 + 2 n_marg + [cells: with vol, or stacked] + [1: stacked]) + 80 n_sta + 32
+ *     job 2       8 (n_tiles Kpad 2 + n_draws + 4 + n_marg) + 80 n_sta + 32
+ *     (the prior's n_marg is counted with a flat prior too, where nothing is allocated for it);
+ *   the draws' table, once per call (jobs 1, 2):  P (n_sta + 1) Kpad + 8 (2 n_sta + 2) n_draws, a pair P = 16 bytes, 8 with
+ *     forward_fp32;
+ *   the stack, once per call:  8 n_layer (cells + nx ny + nx nz + ny nz + 2) + 4 n_events where `layer` is given.
+ * nb, the events of a batch, is the smallest of n_events and nb_limit[0..3]: 65535 (a launch's grid), (2^32 - 1) / (256
+ * n_tiles) and (2^32 - 257) / n_sta (the work-items of a launch), and floor((HTM_LOCATE_MB 2^20 - table - stack) / per event),
+ * itself at most 65535; and 1 at the least.  len_*: the elements of every device array, per event of a batch (sta .. w) and
+ * once per call (dtc .. layer); 0: the call has no such array.
+ * HTM_EINVAL, in this order: a NULL argument or a request that no entry point makes; a bad grid; more than 2^31 - 1 cells;
+ * HTM_LOCATE_MB not positive; the draws' table and one event above it; n_layer (cells + nx ny + nx nz + ny nz + 2) above
+ * 2^31 - 1; the stack, the table and one event above HTM_LOCATE_MB.  (A call checks the prior's widths after the cells.) */
+#define HTM_LOCATE_FIXED          0
+#define HTM_LOCATE_MARGINAL       1
+#define HTM_LOCATE_DRAW_EVIDENCE  2
+typedef struct htm_locate_request {
+    int32_t n_sta, n_events;
+    int32_t job, n_draws;
+    int32_t volume, prior;
+    int32_t n_layer, layer;
+    int32_t forward_fp32;
+} htm_locate_request;
+typedef struct htm_locate_plan {
+    int64_t rows, tpl, stride;
+    int64_t cells, n_tiles, n_marg, map_cells;        /* map_cells = nx ny + nx nz + ny nz */
+    int64_t n_draws, n_draws_padded;
+    int64_t len_sta, len_ev, len_part, len_logz, len_sum, len_loc, len_marg, len_prior, len_vol, len_w;
+    int64_t len_dtc, len_dac, len_rk, len_corr, len_vq, len_stack, len_xy, len_xz, len_yz, len_tally, len_layer;
+    double per_event_bytes, table_bytes, fixed_bytes;
+    int64_t nb_limit[4];
+    int64_t nb;
+} htm_locate_plan;
+int htm_forward_locate_plan(const htm_locate_request *request, const double *grid9, htm_locate_plan *plan);
 
 /* ------------------------------------------------------------------------------------------------
  * Device-resident chains: `type mcmc` x n_chains inside `type parallel`

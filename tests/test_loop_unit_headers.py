@@ -1,5 +1,6 @@
 """CPU: every chain-master loop unit (csrc/htm_loop_*.hip) includes the headers of the ONE loop it builds and nothing of the
-others; k_mcmc's header (htm_mcmc.hpp) includes no loop; the forward unit includes none either; of the chain sets' four host
+others; k_mcmc's header (htm_mcmc.hpp) includes no loop; the forward unit and the locate unit include none either, and only the
+locate unit sees the locate kernels; of the chain sets' four host
 units only the set-up and the run unit see a loop header, each the ones it takes something from.  Read from the compiler's own
 dependency list (hipcc -MM: preprocessing only), so an include that comes in through another header counts."""
 import os
@@ -65,7 +66,7 @@ def test_loop_unit_includes_only_its_own_loop(unit):
 
 def test_the_chain_set_host_units_are_the_ones_listed():
     units = {f[:-4] for f in os.listdir(CSRC) if f.endswith(".hip")}
-    assert units == set(ALLOWED) | set(CHAIN_UNITS) | {"htm_forward", "htm_steps"}
+    assert units == set(ALLOWED) | set(CHAIN_UNITS) | {"htm_forward", "htm_locate", "htm_steps"}
 
 
 @pytest.mark.parametrize("unit", sorted(CHAIN_UNITS))
@@ -95,7 +96,23 @@ def test_the_chain_kernels_header_is_included_by_one_unit():
 
 
 def test_forward_unit_includes_no_loop():
-    assert not (_project_headers("htm_forward.hip") & LOOP_HEADERS)
+    got = _project_headers("htm_forward.hip")
+    assert not (got & LOOP_HEADERS)
+    assert not (got & {"htm_locate.hpp", "htm_locate_plan.hpp", "htm_steps_host.hpp"}), "locate has a unit of its own"
+
+
+def test_locate_unit_includes_no_loop_and_is_the_one_with_the_locate_kernels():
+    got = _project_headers("htm_locate.hip")
+    assert {"htm_locate.hpp", "htm_locate_plan.hpp", "htm_host.hpp"} <= got      # (the closure was really read)
+    assert not (got & (LOOP_HEADERS | SHARED_BY_LOOPS | {"htm_chains_kernels.hpp", "htm_forward_kernels.hpp"}))
+    users = [f for f in sorted(os.listdir(CSRC)) if f.endswith(".hip") and "htm_locate.hpp" in _project_headers(f)]
+    assert users == ["htm_locate.hip"]
+
+
+def test_the_locate_plan_includes_nothing_of_hip():
+    """a plain C++ compiler reads it: of the project's headers it sees the map grid and the limits only"""
+    got = _project_headers("htm_locate_plan.hpp", as_hip=True)
+    assert got | {"htm_locate_plan.hpp"} == {"htm_locate_plan.hpp", "htm_grid.hpp", "htm_limits.hpp"}
 
 
 def test_mcmc_header_includes_no_loop():
