@@ -61,7 +61,7 @@ class LaunchPlan(C.Structure):
 
 
 class LocateRequest(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("n_sta", "n_events", "job", "n_draws", "volume", "prior", "n_layer", "layer", "forward_fp32")]
+    _fields_ = [(n, C.c_int32) for n in ("n_sta", "n_events", "job", "n_draws", "volume", "prior", "n_layer", "layer", "forward_fp32", "residuals")]
 
 
 class LocatePlan(C.Structure):
@@ -69,8 +69,9 @@ class LocatePlan(C.Structure):
     PER_EVENT = ("sta", "ev", "part", "logz", "sum", "loc", "marg", "prior", "vol", "w")      # len_*: elements per event of a batch
     PER_CALL = ("dtc", "dac", "rk", "corr", "vq", "stack", "xy", "xz", "yz", "tally", "layer")      # len_*: elements once per call
     BYTES = ("per_event_bytes", "table_bytes", "fixed_bytes")
+    RESIDUALS = ("rbase", "rpart", "res", "fit")      # len_*: elements per event of a batch, of a request with residuals
     _fields_ = ([(n, C.c_int64) for n in INTS] + [("len_" + n, C.c_int64) for n in PER_EVENT + PER_CALL] + [(n, C.c_double) for n in BYTES] +
-                [("nb_limit", C.c_int64 * 4), ("nb", C.c_int64)])
+                [("nb_limit", C.c_int64 * 4), ("nb", C.c_int64)] + [("len_" + n, C.c_int64) for n in RESIDUALS])
 
 
 # every symbol include/htm_hip.h declares: name -> (restype, argtypes)
@@ -96,6 +97,7 @@ SIGNATURES = {
     "htm_forward_sync": (C.c_int, [vp]),
     "htm_forward_time_full_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, dp]),
     "htm_forward_locate": (C.c_int, [vp, dp, C.c_double, dp, C.c_double, dp, dp, dp, dp, dp]),
+    "htm_forward_locate_residuals": (C.c_int, [vp, dp, C.c_double, dp, C.c_double, dp, dp, dp, dp, dp, dp]),
     "htm_forward_locate_marginal": (C.c_int, [vp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, dp]),
     "htm_forward_locate_draw_evidence": (C.c_int, [vp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp]),
     "htm_forward_locate_set_precision": (C.c_int, [vp, C.c_int]),

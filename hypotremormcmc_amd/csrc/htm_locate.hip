@@ -1,5 +1,6 @@
 // htm_locate.hip -- the locate part of the C ABI (include/htm_hip.h): the location posterior of every event of a forward handle
-// on a grid, under a fixed structure or marginalised over draws of it, the draws' evidences and the stacked density, over the
+// on a grid, under a fixed structure or marginalised over draws of it, the draws' evidences, the stacked density and the stations'
+// residuals, over the
 // kernels of htm_locate.hpp -- the one unit that includes them.  What a call allocates and how it is batched is the plan of
 // htm_locate_plan.hpp, which htm_forward_locate_plan gives out without a device; this unit runs it.  The handle itself
 // (htm_forward, with d_lconst_t, d_lconst_a and loc_fp32 for these entry points) is htm_forward.hip's.
@@ -22,6 +23,7 @@ struct LocCall {
     double *loc, *marg, *vol;                     // kLocFixed, kLocMarginal
     double *log_z, *summary;                      // kLocEvidence
     double *xy, *xz, *yz, *stack, *tally;         // rq.n_layer > 0; stack may be NULL
+    double *res, *fit;                            // rq.residuals
 };
 
 // the device arrays of a call, each as long as the plan says (LocLengths; per event ones times the batch); nullptr: none
@@ -32,6 +34,7 @@ struct LocWork {
     double *prior = nullptr, *part = nullptr, *vol = nullptr, *loc = nullptr, *marg = nullptr, *logz = nullptr, *sum = nullptr, *w = nullptr;
     double *stack = nullptr, *xy = nullptr, *xz = nullptr, *yz = nullptr, *tally = nullptr;
     int *layer = nullptr;
+    double *rbase = nullptr, *rpart = nullptr, *res = nullptr, *fit = nullptr;
 
     template <class T>
     int take(T **p, size_t n) { return n ? pool.alloc(p, n) : HTM_OK; }
@@ -100,7 +103,8 @@ struct LocRun {
         if ((rc = w.take(&w.sta, nb * n.sta)) || (rc = w.take(&w.ev, nb * n.ev)) || (rc = w.take(&w.part, nb * n.part)) || (rc = w.take(&w.logz, nb * n.logz)) ||
             (rc = w.take(&w.sum, nb * n.sum)) || (rc = w.take(&w.loc, nb * n.loc)) || (rc = w.take(&w.marg, nb * n.marg)) || (rc = w.take(&w.prior, nb * n.prior)) ||
             (rc = w.take(&w.vol, nb * n.vol)) || (rc = w.take(&w.w, nb * n.w)) || (rc = w.take(&w.stack, n.stack)) || (rc = w.take(&w.xy, n.xy)) ||
-            (rc = w.take(&w.xz, n.xz)) || (rc = w.take(&w.yz, n.yz)) || (rc = w.take(&w.tally, n.tally)))
+            (rc = w.take(&w.xz, n.xz)) || (rc = w.take(&w.yz, n.yz)) || (rc = w.take(&w.tally, n.tally)) || (rc = w.take(&w.rbase, nb * n.rbase)) ||
+            (rc = w.take(&w.rpart, nb * n.rpart)) || (rc = w.take(&w.res, nb * n.res)) || (rc = w.take(&w.fit, nb * n.fit)))
             return rc;
         if (n.layer && (rc = w.pool.upload(&w.layer, c.layer, n.layer))) return rc;
         if (n.stack) {
@@ -168,6 +172,16 @@ struct LocRun {
         if (c.rq.n_layer)
             hipLaunchKernelGGL(k_locate_stack, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->stream, cells, (int)m, (int)e0, w.vol, w.loc, w.w, w.layer,
                                c.rq.n_layer, w.stack, w.tally);
+        if (c.rq.residuals) {
+            // the residual pass reads the batch's volume, loc records and weight sums where k_locate and k_locate_combine left them
+            const LocRes rs{w.loc, w.w, w.rbase, w.rpart, w.res, w.fit, cells, (int)pl.n_rblk};
+            with_mode(mode, [&](auto M) {
+                constexpr int MODE = decltype(M)::value;
+                hipLaunchKernelGGL((k_locate_res_best<MODE, F32>), dim3((unsigned)m), dim3(64), 0, h->stream, g, jb, rs);
+                hipLaunchKernelGGL((k_locate_residuals<MODE, F32>), dim3((unsigned)pl.n_rblk, (unsigned)m), block, 0, h->stream, g, jb, rs);
+            });
+            hipLaunchKernelGGL(k_locate_res_combine, dim3((unsigned)m), dim3(256), 0, h->stream, rs, S, mode & 1, (mode >> 1) & 1);
+        }
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(h->stream));
         if (job == kLocEvidence) {
@@ -178,6 +192,10 @@ struct LocRun {
         if (c.loc && (rc = w.pool.download(c.loc + (size_t)e0 * 16, w.loc, (size_t)m * 16, "the locations'"))) return rc;
         if (c.marg && (rc = w.pool.download(c.marg + (size_t)e0 * nm, w.marg, (size_t)m * nm, "the marginals'"))) return rc;
         if (c.vol && (rc = w.pool.download(c.vol + (size_t)e0 * cells, w.vol, (size_t)m * cells, "the volume's"))) return rc;
+        if (c.rq.residuals) {
+            if ((rc = w.pool.download(c.res + (size_t)e0 * 4 * S, w.res, (size_t)m * 4 * S, "the residuals'"))) return rc;
+            if ((rc = w.pool.download(c.fit + (size_t)e0 * 10, w.fit, (size_t)m * 10, "the fit's"))) return rc;
+        }
         return HTM_OK;
     }
 
@@ -274,7 +292,9 @@ int htm_forward_locate_plan(const htm_locate_request *request, const double *gri
     if (!r.layer && r.n_layer > 1) return fail(HTM_EINVAL, "n_layer = %d without a layer per window", r.n_layer);
     if (r.layer && r.n_layer == 0) return fail(HTM_EINVAL, "a layer per window without a stack (n_layer = 0)");
     if (r.job == kLocEvidence && (r.volume || r.n_layer)) return fail(HTM_EINVAL, "the draws' evidences come without a volume and without a stack");
-    const LocRequest rq{r.n_sta, r.n_events, r.job, r.n_draws, r.volume != 0, r.prior != 0, r.n_layer, r.layer != 0, r.forward_fp32 != 0};
+    if (r.residuals && (r.job != kLocFixed || r.volume || r.n_layer))
+        return fail(HTM_EINVAL, "the residuals come under a fixed structure, without a volume and without a stack");
+    const LocRequest rq{r.n_sta, r.n_events, r.job, r.n_draws, r.volume != 0, r.prior != 0, r.n_layer, r.layer != 0, r.forward_fp32 != 0, r.residuals != 0};
     LocPlan p;
     if (int rc = locate_tiles(grid9, &p)) return rc;
     double mb;
@@ -288,10 +308,11 @@ int htm_forward_locate_plan(const htm_locate_request *request, const double *gri
 #define LEN(a) plan->len_##a = (int64_t)n.a;
     LEN(sta) LEN(ev) LEN(part) LEN(logz) LEN(sum) LEN(loc) LEN(marg) LEN(prior) LEN(vol) LEN(w)
     LEN(dtc) LEN(dac) LEN(rk) LEN(corr) LEN(vq) LEN(stack) LEN(xy) LEN(xz) LEN(yz) LEN(tally) LEN(layer)
-#undef LEN
     plan->per_event_bytes = p.per_event; plan->table_bytes = p.table; plan->fixed_bytes = p.fixed;
     for (int i = 0; i < kLocLimits; ++i) plan->nb_limit[i] = p.limit[i];
     plan->nb = p.nb;
+    LEN(rbase) LEN(rpart) LEN(res) LEN(fit)
+#undef LEN
     return HTM_OK;
 }
 
@@ -305,6 +326,24 @@ int htm_forward_locate(htm_forward *h, const double *t_corr, double vs, const do
     c.t_corr = t_corr; c.vs = &vs; c.a_corr = a_corr; c.qs = &qs;
     c.grid9 = grid9; c.prior5 = prior5; c.rq.prior = prior5 != nullptr;
     c.loc = loc; c.marg = marg; c.vol = vol; c.rq.volume = vol != nullptr;
+    return locate_run(h, c);
+}
+
+// The stations' residuals, the source terms and the fit of every window (include/htm_hip.h): htm_forward_locate's
+// call with the residual pass behind every batch's combine.  The batch volume is kept on the device and is not downloaded; loc and
+// marg may be NULL
+int htm_forward_locate_residuals(htm_forward *h, const double *t_corr, double vs, const double *a_corr, double qs, const double *grid9,
+                                 const double *prior5, double *loc, double *marg, double *res, double *fit)
+{
+    if (!h) return fail(HTM_EINVAL, "NULL handle");
+    if (!t_corr || !a_corr || !grid9) return fail(HTM_EINVAL, "NULL argument");
+    if (int rc = locate_structure_ok(vs, qs)) return rc;
+    if (!res || !fit) return fail(HTM_EINVAL, "NULL output: res and fit are required");
+    LocCall c = locate_call(h, kLocFixed, 0);
+    c.t_corr = t_corr; c.vs = &vs; c.a_corr = a_corr; c.qs = &qs;
+    c.grid9 = grid9; c.prior5 = prior5; c.rq.prior = prior5 != nullptr;
+    c.loc = loc; c.marg = marg;
+    c.res = res; c.fit = fit; c.rq.residuals = true;
     return locate_run(h, c);
 }
 

@@ -23,9 +23,12 @@
 //   k_locate_draw_evidence<MODE>, k_locate_draw_combine    htm_forward_locate_draw_evidence: every draw's log evidence per event
 //                     and what the draws weigh, described where they stand, below k_locate_marginal
 //   k_locate_stack, k_locate_stack_project    htm_forward_locate_stack: the windows' posteriors, one unit of mass each, summed per
-//                     layer from the batch's volume, and the three projections; described where they stand, at the end
+//                     layer from the batch's volume, and the three projections; described where they stand, below k_locate_combine
+//   k_locate_res_best, k_locate_residuals<MODE>, k_locate_res_combine    htm_forward_locate_residuals: every station's residual, the
+//                     offsets that the demeaning takes away and chi2, at the best cell and as means over the window's posterior,
+//                     from the batch's volume; described where they stand, at the end
 // No floating-point atomics anywhere: the bits do not depend on timing.  The volume of log posteriors is written only when it
-// is asked for, or stacked.
+// is asked for, stacked, or read by the residual pass.
 //
 // Every one of the three evaluation kernels exists twice: F32 = false, all arithmetic fp64, and F32 = true, the single-precision
 // forward of htm_forward_locate_set_precision (the rule: loc_station).  The float copies of the structure are
@@ -287,6 +290,8 @@ struct LocSums {
 // (its u is r - r, not a constant).  MODE: 1 travel times only, 2 amplitudes only, 3 both.
 //
 // F32, the single-precision forward (event_misfit<.., F32>'s rule at a cell centre; T is float, and the structure comes as its
+// (loc_res_station and LocResCell, at the end of this file, restate this body's residuals and sums operation for operation for the
+// residual pass: an edit here is an edit there.)
 // float copies): the three coordinate differences are formed in fp64 and rounded to float; d = v_sqrt_f32(fma(dz, dz, fma(dy,
 // dy, dx dx))) and log2 d = v_log_f32(d), once per (cell, station); per structure the travel time fma(d, 1 / vs, -tc) and the
 // amplitude fma(-d, pi f / (qs vs), -fma(log2 d, ln 2, ac)) in float -- ln d is folded into the structure's own fma, as
@@ -853,6 +858,251 @@ __global__ __launch_bounds__(256) void k_locate_stack_project(LocGrid g, int n_l
         for (size_t ix = lane; ix < nx; ix += 64) a += p[ix];
         a = wave_sum1(a);
         if (lane == 0) yz[i] = a;
+    }
+}
+
+// ---- the stations' residuals, the source terms and the fit of every window (the rule: include/htm_hip.h) --
+// What the forward model demeans away and what is left of a station after it, at the best cell and as means over the window's
+// posterior: with r_j(c) station j's residual (synthetic minus observation) at cell c and p_j its precision, the offset
+// m(c) = sum_j p_j r_j(c) / sum_j p_j, the residual rho_j(c) = m(c) - r_j(c) and chi2(c) = sum_j p_j rho_j(c)^2; the weights
+// w(c) = exp(lp(c) - lp_best) of the included cells, W their sum.  A posterior mean is taken about the best cell, mean(q) =
+// q(best) + sum_c w(c) (q(c) - q(best)) / W, so everything a cell adds is a DIFFERENCE from the best cell's value, which the best
+// cell itself and a posterior of one cell give as exact zeros.  The batch's log posteriors are read from the volume that k_locate
+// wrote, lp_best and the best index from its loc records, W from k_locate_combine's wsum: after a batch's k_locate_combine.
+//
+//   k_locate_res_best     one wave per event, the stations in their order (uniform: scalar loads, every lane the same numbers):
+//                         r_j(best) per station and data type, then m(best) and chi2(best) from the shifted sums, by the very
+//                         operations that k_locate_residuals applies to a cell (loc_res_station, loc_res_cell)
+//   k_locate_residuals    grid = (blocks of kLocResBlock cells, events of the batch); cells by linear index, a thread owns the
+//                         cells t, t + 256, ... of its block, kLocResCells side by side.  ONE station loop per cell (uniform,
+//                         the outer loop): per station the lanes' sum_k w (r_j - r_j(best)) goes through the wave sums' fixed
+//                         tree and lane 0 puts it into LDS; after kLocResSta stations, and at the end, the four waves' values
+//                         are added in wave order and written to the block's partial record -- a barrier per kLocResSta
+//                         stations, none per station.  When the loop ends the cell's m and chi2 fall out of the shifted sums;
+//                         the event's own sums (kLocResEv) close the record.  An excluded cell, and a thread beyond the grid's
+//                         end (which reads cell 0), contribute by SELECTION, never by 0 * value: their residuals may be NaN or
+//                         infinite.
+//   k_locate_res_combine  one workgroup per event: a thread per station adds the partial records in ascending block order; res
+//                         and fit.  An event without an included cell, and a data type that is not in use, give NaN.
+// No floating-point atomics; no cap on n_sta.  All index arithmetic is in size_t or long.
+struct LocRes {
+    const double *loc, *wsum;       // [nb][16], [nb]: k_locate_combine's
+    double *base;                   // [nb][2 S + kLocResBase]
+    double *part;                   // [nb][n_blk][2 S + kLocResEv]
+    double *res, *fit;              // [nb][S][4], [nb][10]
+    long cells;
+    int n_blk;
+};
+
+// loc_station's residuals of station st at the cell (x, y, z) under one structure, by the same operations: rt, ra (what MODE
+// leaves out stays 0)
+template <int MODE, bool F32>
+__device__ __forceinline__ void loc_res_station(const LocSta &st, const LocJob &jb, double x, double y, double z, double &rt, double &ra)
+{
+    constexpr bool UT = (MODE & 1) != 0, UA = (MODE & 2) != 0;
+    rt = 0.0; ra = 0.0;
+    if constexpr (F32) {
+        const float dx = (float)(x - st.sx), dy = (float)(y - st.sy), dz = (float)(z - st.sz);
+        const float d = __builtin_amdgcn_sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)));
+        if constexpr (UT) rt = (double)__builtin_fmaf(d, jb.rbeta32, -st.tc32) - st.tob;
+        if constexpr (UA) {
+            const float lg = __builtin_amdgcn_logf(d);
+            ra = (double)__builtin_fmaf(-d, jb.katt32, -__builtin_fmaf(lg, 0.69314718055994531f, st.ac32)) - st.aob;
+        }
+    } else {
+        const double dx = x - st.sx, dy = y - st.sy, dz = z - st.sz;
+        const double d = htm_sqrt(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)));
+        if constexpr (UT) rt = __builtin_fma(d, jb.rbeta, -st.tc) - st.tob;
+        if constexpr (UA) { const double lg = -htm_log(d); ra = (__builtin_fma(-d, jb.katt, lg) - st.ac) - st.aob; }
+    }
+}
+
+// a cell's shifted sums, as loc_station keeps them (LocSums<1>), and what falls out of them: m = r_0 + t1 / sum p,
+// chi2 = t2 - t1^2 / sum p
+struct LocResCell {
+    double r0t, r0a, t1, t2, a1, a2;
+    __device__ __forceinline__ void clear() { r0t = r0a = t1 = t2 = a1 = a2 = 0.0; }
+    template <int MODE>
+    __device__ __forceinline__ void add(const LocSta &st, bool first, double rt, double ra)
+    {
+        if constexpr ((MODE & 1) != 0) {
+            if (first) r0t = rt;
+            const double u = rt - r0t, pu = st.tpr * u;
+            t1 += pu; t2 = __builtin_fma(pu, u, t2);
+        }
+        if constexpr ((MODE & 2) != 0) {
+            if (first) r0a = ra;
+            const double u = ra - r0a, pu = st.apr * u;
+            a1 += pu; a2 = __builtin_fma(pu, u, a2);
+        }
+    }
+    __device__ __forceinline__ double mt(const LocEv &ev) const { return r0t + t1 * ev.rpst; }
+    __device__ __forceinline__ double ma(const LocEv &ev) const { return r0a + a1 * ev.rpsa; }
+    __device__ __forceinline__ double chi2t(const LocEv &ev) const { return t2 - (t1 * t1) * ev.rpst; }
+    __device__ __forceinline__ double chi2a(const LocEv &ev) const { return a2 - (a1 * a1) * ev.rpsa; }
+};
+
+// the centre of the cell of linear index c
+__device__ __forceinline__ void loc_res_centre(const LocGrid &g, long c, double &x, double &y, double &z)
+{
+    const long nxy = (long)g.nx * g.ny;
+    const int iz = (int)(c / nxy), iy = (int)((c - (long)iz * nxy) / g.nx), ix = (int)(c - (long)iz * nxy - (long)iy * g.nx);
+    x = map_centre(g.x0, g.dx, ix); y = map_centre(g.y0, g.dy, iy); z = map_centre(g.z0, g.dz, iz);
+}
+
+template <int MODE, bool F32>
+__global__ __launch_bounds__(64) void k_locate_res_best(LocGrid g, LocJob jb, LocRes rs)
+{
+    const int b = blockIdx.x, S = jb.S;
+    const double idx = loc_ld_uniform(rs.loc + 16 * (size_t)b);
+    if (idx < 0.0) return;                                  // (uniform) no included cell: k_locate_res_combine writes the NaN
+    const LocSta *sta = jb.sta + (size_t)b * S;
+    const LocEv ev = loc_ld_ev(jb.ev + b);
+    double *base = rs.base + (size_t)b * (2 * (size_t)S + kLocResBase);
+    double x, y, z;
+    loc_res_centre(g, (long)idx, x, y, z);
+    LocResCell sm;
+    sm.clear();
+    for (int j = 0; j < S; ++j) {
+        const LocSta st = loc_ld_sta(sta + j);
+        double rt, ra;
+        loc_res_station<MODE, F32>(st, jb, x, y, z, rt, ra);
+        sm.add<MODE>(st, j == 0, rt, ra);
+        if (threadIdx.x == 0) { base[2 * (size_t)j] = rt; base[2 * (size_t)j + 1] = ra; }
+    }
+    if (threadIdx.x == 0) {
+        double *q = base + 2 * (size_t)S;
+        q[0] = sm.mt(ev); q[1] = sm.chi2t(ev); q[2] = sm.ma(ev); q[3] = sm.chi2a(ev);
+    }
+}
+
+template <int MODE, bool F32>
+__global__ __launch_bounds__(256) void k_locate_residuals(LocGrid g, LocJob jb, LocRes rs)
+{
+    constexpr bool UT = (MODE & 1) != 0, UA = (MODE & 2) != 0;
+    constexpr int C = kLocResCells;
+    __shared__ double s_sta[4][kLocResSta][2];
+    __shared__ double s_ev[4][kLocResEv];
+    const int t = threadIdx.x, lane = t & 63, b = blockIdx.y, S = jb.S;
+    const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
+    const double idx = loc_ld_uniform(rs.loc + 16 * (size_t)b);
+    if (idx < 0.0) return;                                  // (uniform) no included cell: nothing of this event's records is read
+    const double lp_best = loc_ld_uniform(rs.loc + 16 * (size_t)b + 4);
+    const LocSta *sta = jb.sta + (size_t)b * S;
+    const LocEv ev = loc_ld_ev(jb.ev + b);
+    const size_t reclen = 2 * (size_t)S + kLocResEv;
+    const double *base = rs.base + (size_t)b * (2 * (size_t)S + kLocResBase);
+    double *rec = rs.part + ((size_t)b * rs.n_blk + blockIdx.x) * reclen;
+    const double *vol = jb.vol + (size_t)b * (size_t)rs.cells;
+
+    double x[C], y[C], z[C], w[C];
+    bool inc[C];
+    LocResCell sm[C];
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+        const long c = (long)blockIdx.x * kLocResBlock + kLocThreads * k + t;
+        const bool live = c < rs.cells;
+        const long cc = live ? c : 0;                       // (a thread beyond the end reads cell 0 and adds nothing)
+        const double v = vol[(size_t)cc];
+        inc[k] = live && loc_included(v);
+        w[k] = inc[k] ? exp(v - lp_best) : 0.0;
+        loc_res_centre(g, cc, x[k], y[k], z[k]);
+        sm[k].clear();
+    }
+    for (int j0 = 0; j0 < S; j0 += kLocResSta) {            // (uniform) a block of stations
+        const int nj = min(kLocResSta, S - j0);
+        for (int jj = 0; jj < nj; ++jj) {
+            const int j = j0 + jj;
+            const LocSta st = loc_ld_sta(sta + j);
+            const loc_f64x2 rb = *(const loc_f64x2 __attribute__((address_space(4))) *)(unsigned long long)(base + 2 * (size_t)j);
+            double v[2] = {0.0, 0.0};
+#pragma unroll
+            for (int k = 0; k < C; ++k) {
+                double rt, ra;
+                loc_res_station<MODE, F32>(st, jb, x[k], y[k], z[k], rt, ra);
+                sm[k].add<MODE>(st, j == 0, rt, ra);
+                if constexpr (UT) v[0] += inc[k] ? w[k] * (rt - rb[0]) : 0.0;
+                if constexpr (UA) v[1] += inc[k] ? w[k] * (ra - rb[1]) : 0.0;
+            }
+            wave_sum<2>(v);
+            if (lane == 0) { s_sta[wv][jj][0] = v[0]; s_sta[wv][jj][1] = v[1]; }
+        }
+        __syncthreads();
+        if (t < 2 * nj) {
+            const int jj = t >> 1, d = t & 1;
+            rec[2 * (size_t)j0 + t] = (s_sta[0][jj][d] + s_sta[1][jj][d]) + (s_sta[2][jj][d] + s_sta[3][jj][d]);
+        }
+        __syncthreads();                                    // (read before the next block of stations overwrites it)
+    }
+    // the cells' offsets and chi2 against the best cell's, and the event's sums
+    const double *q = base + 2 * (size_t)S;
+    const double mtb = loc_ld_uniform(q), ctb = loc_ld_uniform(q + 1), mab = loc_ld_uniform(q + 2), cab = loc_ld_uniform(q + 3);
+    double e[kLocResEv];
+#pragma unroll
+    for (int i = 0; i < kLocResEv; ++i) e[i] = 0.0;
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+        if constexpr (UT) {
+            const double u = sm[k].mt(ev) - mtb, wu = w[k] * u;
+            e[0] += inc[k] ? wu : 0.0; e[1] += inc[k] ? wu * u : 0.0; e[2] += inc[k] ? w[k] * (sm[k].chi2t(ev) - ctb) : 0.0;
+        }
+        if constexpr (UA) {
+            const double u = sm[k].ma(ev) - mab, wu = w[k] * u;
+            e[3] += inc[k] ? wu : 0.0; e[4] += inc[k] ? wu * u : 0.0; e[5] += inc[k] ? w[k] * (sm[k].chi2a(ev) - cab) : 0.0;
+        }
+    }
+    wave_sum<kLocResEv>(e);
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < kLocResEv; ++i) s_ev[wv][i] = e[i];
+    }
+    __syncthreads();
+    if (t < kLocResEv) rec[2 * (size_t)S + t] = (s_ev[0][t] + s_ev[1][t]) + (s_ev[2][t] + s_ev[3][t]);
+}
+
+// use_t, use_a: the data types of the handle
+__global__ __launch_bounds__(256) void k_locate_res_combine(LocRes rs, int S, int use_t, int use_a)
+{
+    __shared__ double s_ev[kLocResEv];
+    const int t = threadIdx.x, b = blockIdx.x;
+    const double nan = __builtin_nan("");
+    double *R = rs.res + (size_t)b * 4 * (size_t)S, *F = rs.fit + (size_t)b * 10;
+    if (rs.loc[16 * (size_t)b] < 0.0) {                     // (block-uniform) no included cell
+        for (size_t i = t; i < 4 * (size_t)S; i += 256) R[i] = nan;
+        if (t < 10) F[t] = nan;
+        return;
+    }
+    const size_t reclen = 2 * (size_t)S + kLocResEv;
+    const double *P = rs.part + (size_t)b * rs.n_blk * reclen;
+    const double *base = rs.base + (size_t)b * (2 * (size_t)S + kLocResBase), *q = base + 2 * (size_t)S;
+    const double W = rs.wsum[b];
+    if (t < kLocResEv) {
+        double a = 0.0;
+        for (int i = 0; i < rs.n_blk; ++i) a += P[(size_t)i * reclen + 2 * (size_t)S + t];
+        s_ev[t] = a;
+    }
+    __syncthreads();
+    const int use[2] = {use_t, use_a};
+    for (int j = t; j < S; j += 256)
+        for (int d = 0; d < 2; ++d) {
+            double best = nan, mean = nan;
+            if (use[d]) {
+                double a = 0.0;
+                for (int i = 0; i < rs.n_blk; ++i) a += P[(size_t)i * reclen + 2 * (size_t)j + d];
+                best = q[2 * d] - base[2 * (size_t)j + d];
+                mean = best + (s_ev[3 * d] - a) / W;
+            }
+            R[4 * (size_t)j + 2 * d] = best; R[4 * (size_t)j + 2 * d + 1] = mean;
+        }
+    if (t < 2) {
+        const int d = t;
+        double f[5] = {nan, nan, nan, nan, nan};
+        if (use[d]) {
+            const double m1 = s_ev[3 * d] / W, var = s_ev[3 * d + 1] / W - m1 * m1;
+            f[0] = q[2 * d]; f[1] = q[2 * d] + m1; f[2] = var > 0.0 ? htm_sqrt(var) : 0.0;      // (floored at 0)
+            f[3] = q[2 * d + 1]; f[4] = q[2 * d + 1] + s_ev[3 * d + 2] / W;
+        }
+        for (int i = 0; i < 5; ++i) F[5 * d + i] = f[i];
     }
 }
 

@@ -28,6 +28,13 @@ static_assert(kLocTile >= kMapMaxCells, "a tile holds at least one whole x-row")
 constexpr int kLocDraws = HTM_LOCM_DRAWS;
 constexpr int kLocMaxDraws = 4096;      // draws per call (include/htm_hip.h)
 static_assert(kLocDraws >= 1 && kLocMaxDraws % kLocDraws == 0, "whole blocks of draws");
+// k_locate_residuals: cells of a thread side by side, the cells of a workgroup (one partial record each), the stations whose
+// sums cross the four waves together, and the event's own sums at a record's end
+constexpr int kLocResCells = 4;
+constexpr int kLocResBlock = kLocThreads * kLocResCells;
+constexpr int kLocResSta = 64;
+constexpr int kLocResEv = 6;            // per data type: sum w u, sum w u^2 (u = m - m(best)), sum w (chi2 - chi2(best))
+constexpr int kLocResBase = 4;          // per data type: m(best), chi2(best), behind the stations' residuals at the best cell
 
 // what the evaluation reads of one station for one event; 80 bytes, read with scalar loads.  tc32, ac32: tc and ac rounded to
 // float, for the single-precision forward
@@ -64,6 +71,7 @@ struct LocRequest {
     int n_layer;        // layers of the stack; 0: no stack
     bool layer;         // the stack has a layer per window
     bool fp32;          // the single-precision forward: the draws' table holds pairs of floats
+    bool residuals;     // htm_forward_locate_residuals: the stations' residuals and the fit (kLocFixed only, without a stack)
 };
 
 // ---- what the run needs -------------------------------------------------------------------------------------------
@@ -81,11 +89,16 @@ struct LocLengths {
     size_t corr, vq;                 // the draws' table, pairs
     size_t stack, xy, xz, yz, tally;
     size_t layer;                    // ints
+    // per event of a batch, of a call with residuals
+    size_t rbase;                    // the stations' residuals at the best cell, {t, a} each, then m and chi2 there
+    size_t rpart;                    // the partial records of the residual pass: per block of cells [n_sta][2] and the event's sums
+    size_t res, fit;
 };
 enum { kLocByEvents, kLocByTiles, kLocByPack, kLocByBudget, kLocLimits };
 struct LocPlan {
     LocGrid g;
     long cells, n_tiles, nm, map_cells;      // nm: the marginals' length nx + ny + nz; map_cells: nx ny + nx nz + ny nz
+    long n_rblk;                             // blocks of kLocResBlock cells: the residual pass's workgroups per event
     int K, Kpad;                             // draws; padded to whole blocks of kLocDraws
     LocLengths len;
     double per_event, table, fixed;          // bytes: per event of a batch; the draws' table and its input; the stack's part
@@ -109,6 +122,7 @@ inline int locate_tiles(const double *grid9, LocPlan *p)
     p->n_tiles = (long)g.nz * g.tpl;
     p->nm = (long)g.nx + g.ny + g.nz;
     p->map_cells = (long)g.nx * g.ny + (long)g.nx * g.nz + (long)g.ny * g.nz;
+    p->n_rblk = (p->cells + kLocResBlock - 1) / kLocResBlock;
     return HTM_OK;
 }
 
@@ -129,13 +143,18 @@ inline int locate_budget(const LocRequest &rq, double mb, LocPlan *p)
     if (evid) { n.part = n_tiles * Kpad * 2; n.logz = (size_t)K; n.sum = 4; }
     else { n.part = n_tiles * g.stride; n.loc = 16; n.marg = nm; }
     if (rq.prior) n.prior = nm;
-    if (rq.volume || stk) n.vol = cells;
-    if (stk) n.w = 1;
+    if (rq.volume || stk || rq.residuals) n.vol = cells;
+    if (stk || rq.residuals) n.w = 1;
+    if (rq.residuals) {
+        n.rbase = 2 * S + kLocResBase; n.rpart = (size_t)p->n_rblk * (2 * S + kLocResEv);
+        n.res = 4 * S; n.fit = 10;
+    }
     if (draws) { n.dtc = n.dac = (size_t)K * S; n.rk = 2 * (size_t)K; n.corr = S * Kpad; n.vq = (size_t)Kpad; }
 
     // (the prior's tables are counted whether or not the call has a prior: a flat-prior call is planned as if it allocated them.
     // Every other term is an array of the call: the stack's + 1 of include/htm_hip.h is w, which a stacked call allocates)
-    p->per_event = sizeof(double) * (double)(n.part + n.logz + n.sum + n.loc + n.marg + nm + n.vol + n.w) + sizeof(LocSta) * (double)n.sta +
+    p->per_event = sizeof(double) * (double)(n.part + n.logz + n.sum + n.loc + n.marg + nm + n.vol + n.w + n.rbase + n.rpart + n.res + n.fit) +
+                   sizeof(LocSta) * (double)n.sta +
                    sizeof(LocEv) * (double)n.ev;
     // the draws' table and the draws as they come are part of the workspace, once per call
     const size_t pair = rq.fp32 ? sizeof(LocPairT<float>) : sizeof(LocPairT<double>);
@@ -159,6 +178,8 @@ inline int locate_budget(const LocRequest &rq, double mb, LocPlan *p)
     // events per batch; one at the least, whatever the budget (only a call with a table or a stack is refused for it)
     p->limit[kLocByEvents] = 65535L;                                                  // a launch's grid: y <= 65535
     p->limit[kLocByTiles] = kMaxWorkItems / (p->n_tiles * kLocThreads);               // the evaluation: (tiles, events) blocks of kLocThreads
+    if (rq.residuals)                                                                 // the residual pass: (blocks of cells, events), whichever are more
+        p->limit[kLocByTiles] = kMaxWorkItems / (std::max(p->n_tiles, p->n_rblk) * kLocThreads);
     p->limit[kLocByPack] = (kMaxWorkItems - 256) / rq.n_sta;                          // k_locate_pack: a thread per (event, station), whole blocks of 256
     p->limit[kLocByBudget] = (long)std::min((mb * 1048576.0 - p->table - p->fixed) / p->per_event, 65535.0);      // the workspace under mb MiB
     p->nb = (long)rq.n_events;

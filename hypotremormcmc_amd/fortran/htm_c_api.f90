@@ -20,6 +20,7 @@ module htm_c_api
   public :: htm_hypo_ellipsoid, htm_hypo_ellipsoid_dev
   public :: htm_hypo_density, htm_hypo_density_dev
   public :: htm_forward_locate
+  public :: htm_forward_locate_residuals
   public :: htm_forward_locate_marginal
   public :: htm_forward_locate_draw_evidence
   public :: htm_forward_locate_set_precision
@@ -373,6 +374,21 @@ module htm_c_api
        type(c_ptr), value :: marg, vol
        integer(c_int) :: rc
      end function htm_forward_locate
+     !> the stations' residuals, the source terms and the fit of every window under the fixed structure (include/htm_hip.h): the
+     !> inputs of htm_forward_locate; loc (16, n_events) and marg or c_null_ptr; res (4, n_sta, n_events) = rho_t at the best cell
+     !> and its posterior mean, the same of rho_a; fit (10, n_events) = per data type the offset at the best cell, its posterior
+     !> mean and standard deviation, chi2 at the best cell and its posterior mean
+     function htm_forward_locate_residuals(handle, t_corr, vs, a_corr, qs, grid9, prior5, loc, marg, res, fit) &
+          & bind(C, name="htm_forward_locate_residuals") result(rc)
+       import :: c_int, c_double, c_ptr
+       type(c_ptr), value :: handle
+       real(c_double), intent(in) :: t_corr(*), a_corr(*)
+       real(c_double), value :: vs, qs
+       real(c_double), intent(in) :: grid9(9)
+       type(c_ptr), value :: prior5, loc, marg
+       real(c_double), intent(out) :: res(*), fit(*)
+       integer(c_int) :: rc
+     end function htm_forward_locate_residuals
      !> the same with the structure marginalised over n_draws draws (include/htm_hip.h): t_corr, a_corr (n_sta, n_draws);
      !> vs, qs (n_draws); the outputs as htm_forward_locate's
      function htm_forward_locate_marginal(handle, n_draws, t_corr, vs, a_corr, qs, grid9, prior5, loc, marg, vol) &

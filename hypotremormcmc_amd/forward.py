@@ -91,6 +91,12 @@ class Forward:
                                                  None if layer is None else layer.ctypes.data_as(_lib.ip), int(n_layer), ptr(loc), ptr(marg),
                                                  ptr(xy), ptr(xz), ptr(yz), ptr(stack), ptr(tally)))
 
+    def locate_residuals(self, t_corr, vs, a_corr, qs, grid9, prior5, loc, marg, res, fit):
+        """htm_forward_locate_residuals on this object (include/htm_hip.h): contiguous float64 arrays as the
+        library takes them, None for loc or marg that is not asked for.  `locate.residuals` prepares them."""
+        check(self._lib.htm_forward_locate_residuals(self.handle, ptr(t_corr), float(vs), ptr(a_corr), float(qs), ptr(grid9), ptr(prior5), ptr(loc),
+                                                     ptr(marg), ptr(res), ptr(fit)))
+
     def obs_pack_bytes(self) -> int:
         """Bytes of the packed per-event observation records (the specialised chain master's; 0: none were built)."""
         n = C.c_int64(0)

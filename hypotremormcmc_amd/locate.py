@@ -6,6 +6,7 @@ grid -- no MCMC, any number of windows (kernels in hypotremorm
                                         [--windows FILE] [--flat-prior] [--volume-of WIN] [--draws K [--draw-weights]]
                                         [--precision fp64|fp32]
                                         [--stack [--time-bins N] [--stack-volume] [--stack-resolved] [--level 0.68 0.95]]
+                                        [--residuals]
 
 run in the data directory (station file, opt_data.NNNNNN.dat).  --structure DIR holds `uniform_structure.stat` and
 `station_corrections.stat` of the calibration run (default: the parameter file's directory); --windows FILE lists the window
@@ -51,6 +52,16 @@ samples.  --time-bins N gives the layers (density.time_layers).  --stack-resolve
 on a face of the box (a first evaluation finds them; the summary says how many).  One summary line per layer: windows
 stacked, windows without an included cell, and the share of the layer's mass on the faces of the box.  The other options of
 this paragraph without --stack are argument errors.
+
+--residuals says how well every window fits where it lies (`residuals`, htm_forward_locate_residuals): per
+station the residual that the demeaning leaves (observation minus demeaned synthetic) at the best cell and as a mean over the
+window's posterior, and per window the two offsets that the demeaning takes away -- the precision-weighted mean time residual,
+an origin-time shift, and the mean amplitude residual, minus the log source amplitude -- with their posterior spread, and chi2.
+It writes `hypo_grid.residuals.dat` (one line per window and station), `hypo_grid.fit.dat` (one line per window) and
+`hypo_grid.stations.dat` (one line per station over all windows: does the calibration run's correction hold for these
+windows?), and one summary line that names the station with the largest mean residual.  Without --stack the one evaluation
+serves `hypo_grid.stat` and `hypo_grid.best.dat` too; with --stack it is a second one.  It takes a fixed structure: with
+--draws it is an argument error.  Without --residuals nothing is written or printed that was not before.
 """
 from __future__ import annotations
 
@@ -72,6 +83,14 @@ from .statistics import HYPO_HEADER, INT_MAX
 DRAWS_HEADER = ("# window ID, effective number of the draws n_eff, n_eff / K, largest weight, record number of the draw that has it, "
                 "log evidence of the mixture, 1: that weight is above 0.5 (the intervals are one structure's)")
 STRUCTURE_HEADER = "# record number of the draw, vs, qs, joint log weight over all windows relative to the best draw, normalised joint weight"
+RESIDUALS_HEADER = ("# window ID, station, 1: the station's data are missing for the window, then per data type in use (time, amplitude): "
+                    "residual (observation minus demeaned synthetic) at the best cell, its posterior mean, the best cell's over the standard deviation")
+FIT_HEADER = ("# window ID, stations with data, then per data type in use (time, amplitude): offset (weighted mean of synthetic minus observation) "
+              "at the best cell, its posterior mean and standard deviation, chi2 at the best cell, its posterior mean; "
+              "with amplitudes last: log source amplitude (minus the mean amplitude offset)")
+STATIONS_HEADER = ("# station, windows with data, then per data type in use (time, amplitude): precision-weighted mean over those windows of the "
+                   "posterior-mean residual, its standard error, its weighted rms, largest |best-cell residual / standard deviation| and its window ID")
+FIT_NAMES = tuple(f"{q}_{d}{s}" for d in "ta" for q, s in (("m", "_best"), ("m", "_mean"), ("m", "_sd"), ("chi2", "_best"), ("chi2", "_mean")))
 BEST_HEADER = ("# window ID, best cell's centre x y z, log posterior there, log-likelihood term there, log evidence, "
                "posterior mean x y z, 1: the best cell lies on a face of the box")
 
@@ -188,14 +207,40 @@ def stack(fwd, t_corr, vs, a_corr, qs, grid, prior=None, layer=None, n_layer=1, 
     return dict(_result(loc, marg, None, nx, ny), **out)
 
 
+def residuals(fwd, t_corr, vs, a_corr, qs, grid, prior=None, precision=None):
+    """The stations' residuals, the source terms and the fit of every window where `locate` puts it
+    (htm_forward_locate_residuals): the inputs of `locate`.  Returns the dict of `locate` (its very bits; vol
+    None) plus res_t_best, res_t_mean, res_a_best, res_a_mean [E][S] -- station j's residual rho = offset - (synthetic -
+    observation) at the best cell and its mean over the window's posterior, per data type -- and fit [E][10] = per data type,
+    time first, the offset m at the best cell, its posterior mean and standard deviation, chi2 at the best cell and its
+    posterior mean, with a view per column under FIT_NAMES (m_t_best, m_t_mean, m_t_sd, chi2_t_best, chi2_t_mean, m_a_best,
+    ...).  A data type that the Forward does not use is NaN, a window without an included cell NaN throughout."""
+    g, (nx, ny, nz) = _grid(grid)
+    E, S = fwd.n_events, fwd.n_sta
+    tc = np.ascontiguousarray(np.asarray(t_corr, dtype=np.float64).reshape(-1))
+    ac = np.ascontiguousarray(np.asarray(a_corr, dtype=np.float64).reshape(-1))
+    if tc.size != S or ac.size != S:
+        raise ValueError(f"t_corr and a_corr have {tc.size} and {ac.size} values: need one per station ({S})")
+    pr = _prior_array(prior, E)
+    loc, marg, _ = _outputs(E, nx, ny, nz, True, False)
+    res, fit = np.empty((E, S, 4)), np.empty((E, 10))
+    with _precision(fwd, precision):
+        fwd.locate_residuals(tc, vs, ac, qs, g, pr, loc, marg, res, fit)
+    out = dict(_result(loc, marg, None, nx, ny), res=res, fit=fit, res_t_best=res[:, :, 0], res_t_mean=res[:, :, 1], res_a_best=res[:, :, 2],
+               res_a_mean=res[:, :, 3])
+    out.update({nm: fit[:, k] for k, nm in enumerate(FIT_NAMES)})
+    return out
+
+
 JOBS = {"fixed": 0, "marginal": 1, "draw_evidence": 2}      # HTM_LOCATE_FIXED .. of include/htm_hip.h
 
 
-def plan(n_sta, n_events, grid, job="fixed", n_draws=0, volume=False, prior=False, n_layer=0, layer=False, precision="fp64"):
+def plan(n_sta, n_events, grid, job="fixed", n_draws=0, volume=False, prior=False, n_layer=0, layer=False, precision="fp64", residuals=False):
     """The workspace and the batches of a call of that shape under the HTM_LOCATE_MB of the environment, without a Forward and
     without a GPU (htm_forward_locate_plan, which states the formula): job "fixed" (`locate`), "marginal" (`locate_marginal`) or
     "draw_evidence" with n_draws; volume and prior: whether the call has them; n_layer >= 1: `stack`, with a layer per window
-    or not.  Returns a dict: rows, tpl, stride, cells, n_tiles, n_marg, map_cells, n_draws, n_draws_padded; per_event and
+    or not; residuals: `residuals` (job "fixed", no volume, no stack), whose dict alone has per_event's rbase, rpart, res and fit.
+    Returns a dict: rows, tpl, stride, cells, n_tiles, n_marg, map_cells, n_draws, n_draws_padded; per_event and
     per_call, the elements of every device array by name; per_event_bytes, table_bytes, fixed_bytes; nb_limit [4] and nb, the
     events per batch.  A shape that the call would refuse raises HtmError with the call's message."""
     if job not in JOBS:
@@ -203,7 +248,7 @@ def plan(n_sta, n_events, grid, job="fixed", n_draws=0, volume=False, prior=Fals
     if precision not in ("fp32", "fp64"):
         raise ValueError(f"locate precision {precision!r}: need 'fp32' or 'fp64'")
     rq = _lib.LocateRequest(int(n_sta), int(n_events), JOBS[job], int(n_draws), int(bool(volume)), int(bool(prior)), int(n_layer),
-                            int(bool(layer)), int(precision == "fp32"))
+                            int(bool(layer)), int(precision == "fp32"), int(bool(residuals)))
     g = np.ascontiguousarray(grid, dtype=np.float64).reshape(-1)
     if g.size != 9:
         raise ValueError(f"grid has {g.size} values: need x0, dx, nx, y0, dy, ny, z0, dz, nz")
@@ -213,6 +258,8 @@ def plan(n_sta, n_events, grid, job="fixed", n_draws=0, volume=False, prior=Fals
     d.update({n: float(getattr(p, n)) for n in _lib.LocatePlan.BYTES})
     d["per_event"] = {n: int(getattr(p, "len_" + n)) for n in _lib.LocatePlan.PER_EVENT}
     d["per_call"] = {n: int(getattr(p, "len_" + n)) for n in _lib.LocatePlan.PER_CALL}
+    if residuals:
+        d["per_event"].update({n: int(getattr(p, "len_" + n)) for n in _lib.LocatePlan.RESIDUALS})
     d["nb_limit"] = [int(v) for v in p.nb_limit]
     return d
 
@@ -422,6 +469,98 @@ def best_text(win_id, res, grid) -> str:
     return "\n".join(lines) + "\n"
 
 
+# ---- the residuals' files (--residuals) --------------------------------------------------------------------------------------
+MISSING_STDV = 1.0e-16      # the reference's missing-data rule (cls_forward.f90:76-92): keyed on t_stdv alone
+
+
+def _types(use):
+    """(column of res, column of fit, index of the standard deviations) per data type in use"""
+    return [(2 * d, 5 * d, d) for d in range(2) if use[d]]
+
+
+def residuals_text(win_id, names, res, t_stdv, a_stdv, use=(True, True)) -> str:
+    """the text of hypo_grid.residuals.dat from `residuals`' res [E][S][4]: one line per (window, station); a missing station's
+    columns, and a window's without a cell, are NaN"""
+    sd = (np.asarray(t_stdv, dtype=np.float64), np.asarray(a_stdv, dtype=np.float64))
+    lines = [RESIDUALS_HEADER]
+    for e, w in enumerate(win_id):
+        for j, nm in enumerate(names):
+            miss = bool(sd[0][e, j] <= MISSING_STDV)
+            line = "%9d %-12s%3d" % (w, str(nm).strip()[:12], int(miss))
+            for r, _, d in _types(use):
+                best, mean = (np.nan, np.nan) if miss else (res[e, j, r], res[e, j, r + 1])
+                line += field(best, 15) + field(mean, 15) + field(np.nan if miss else best / sd[d][e, j], 13, 4)
+            lines.append(line)
+    return "\n".join(lines) + "\n"
+
+
+def fit_text(win_id, fit, t_stdv, use=(True, True)) -> str:
+    """the text of hypo_grid.fit.dat from `residuals`' fit [E][10]: one line per window"""
+    n_data = (np.asarray(t_stdv, dtype=np.float64) > MISSING_STDV).sum(axis=1)
+    lines = [FIT_HEADER]
+    for e, w in enumerate(win_id):
+        line = "%9d%6d" % (w, n_data[e])
+        for _, f, _ in _types(use):
+            line += "".join(field(fit[e, f + k], 15) for k in range(5))
+        if use[1]:
+            line += field(-fit[e, 6], 15)
+        lines.append(line)
+    return "\n".join(lines) + "\n"
+
+
+def station_statistics(win_id, res, t_stdv, a_stdv, use=(True, True)):
+    """per station over the windows that have its data and a cell, from `residuals`' res [E][S][4]: n [S], and per data type d
+    (0 time, 1 amplitude; NaN where not in use, or no such window) mean [2][S] the precision-weighted mean of the posterior-mean
+    residual, se [2][S] its standard error 1 / sqrt(sum p), rms [2][S] the weighted rms, zmax [2][S] the largest |best-cell
+    residual / standard deviation| and zwin [2][S] its window id (-1: none)"""
+    res = np.asarray(res, dtype=np.float64)
+    E, S = res.shape[:2]
+    sd = (np.asarray(t_stdv, dtype=np.float64), np.asarray(a_stdv, dtype=np.float64))
+    ok = (sd[0] > MISSING_STDV) & ~np.isnan(res).all(axis=2)
+    out = {"n": ok.sum(axis=0), "mean": np.full((2, S), np.nan), "se": np.full((2, S), np.nan), "rms": np.full((2, S), np.nan),
+           "zmax": np.full((2, S), np.nan), "zwin": np.full((2, S), -1, dtype=np.int64)}
+    ids = np.asarray(win_id, dtype=np.int64)
+    for r, _, d in _types(use):
+        for j in range(S):
+            k = np.nonzero(ok[:, j])[0]
+            if k.size == 0:
+                continue
+            p = 1.0 / sd[d][k, j] ** 2
+            out["mean"][d, j] = (p * res[k, j, r + 1]).sum() / p.sum()
+            out["se"][d, j] = 1.0 / np.sqrt(p.sum())
+            out["rms"][d, j] = np.sqrt((p * res[k, j, r + 1] ** 2).sum() / p.sum())
+            z = np.abs(res[k, j, r] / sd[d][k, j])
+            out["zmax"][d, j], out["zwin"][d, j] = z.max(), ids[k[int(np.argmax(z))]]
+    return out
+
+
+def stations_text(win_id, names, res, t_stdv, a_stdv, use=(True, True)) -> str:
+    """the text of hypo_grid.stations.dat (station_statistics): one line per station"""
+    st = station_statistics(win_id, res, t_stdv, a_stdv, use)
+    lines = [STATIONS_HEADER]
+    for j, nm in enumerate(names):
+        line = "%-12s%6d" % (str(nm).strip()[:12], st["n"][j])
+        for _, _, d in _types(use):
+            line += field(st["mean"][d, j], 15) + field(st["se"][d, j], 15) + field(st["rms"][d, j], 15) + field(st["zmax"][d, j], 13, 4) + "%9d" % st["zwin"][d, j]
+        lines.append(line)
+    return "\n".join(lines) + "\n"
+
+
+def stations_summary_text(win_id, names, res, t_stdv, a_stdv, use=(True, True)) -> str:
+    """the summary's line about the stations: per data type in use the station with the largest absolute mean residual"""
+    st = station_statistics(win_id, res, t_stdv, a_stdv, use)
+    parts = []
+    for _, _, d in _types(use):
+        m = np.abs(st["mean"][d])
+        if np.isnan(m).all():
+            parts.append(f"{('time', 'amplitude')[d]}: no station has a window with data and a cell")
+            continue
+        j = int(np.nanargmax(m))
+        parts.append(f"{('time', 'amplitude')[d]}: station {str(names[j]).strip()} {st['mean'][d, j]:.6f} ({st['mean'][d, j] / st['se'][d, j]:.2f} standard errors, "
+                     f"{int(st['n'][j])} windows)")
+    return "largest mean residual of a station over the located windows -- " + "; ".join(parts) + "\n"
+
+
 def volume_text(vol, grid) -> str:
     """the text of hypo_grid.WIN.vol.dat from one window's vol [nz][ny][nx]: linear index, cell centre, log posterior"""
     nx, ny, nz = grid_counts(grid)
@@ -572,7 +711,11 @@ def main(argv=None):
     ap.add_argument("--stack-resolved", action="store_true", help="with --stack: leave out the windows whose best cell lies on a face of the box "
                     "(a first evaluation finds them)")
     ap.add_argument("--level", type=float, nargs="+", metavar="P", help="with --stack: shares of a layer's mass for the regions (default 0.68 0.95)")
+    ap.add_argument("--residuals", action="store_true", help="also write every station's residual per window, the windows' source terms and fit, "
+                    "and the stations' mean residuals: hypo_grid.residuals.dat, .fit.dat and .stations.dat (a fixed structure: not with --draws)")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    if args.residuals and args.draws is not None:
+        ap.error("--residuals takes a fixed structure: the residuals under draws of the structure are not computed (leave out --draws)")
     if args.draws is not None and args.draws < 1:
         ap.error(f"--draws {args.draws}: need at least one draw")
     if args.draw_weights and args.draws is None:
@@ -602,9 +745,10 @@ def main(argv=None):
         raise SystemExit("ERROR: no window to locate")
 
     n_unresolved = None
+    resid = None      # with --residuals: its result and the windows' standard deviations
 
-    def run(ids, volume, weights=False, stacked=False):
-        nonlocal n_unresolved
+    def run(ids, volume, weights=False, stacked=False, with_residuals=False):
+        nonlocal n_unresolved, resid
         obs = ObsData(ids, par.n_stations, par.sta_x, par.sta_y, directory=work)
         fwd = Forward(par.n_stations, len(ids), par.sta_x, par.sta_y, par.sta_z, obs, use_amp=par.get_use_amp(), use_time=par.get_use_time(),
                       device=device)
@@ -620,13 +764,18 @@ def main(argv=None):
                     layer = resolved_layer(layer, first["index"], grid)
                     n_unresolved = int((layer < 0).sum())
                 res = stack(fwd, t_corr, vs, a_corr, qs, grid, prior=prior, layer=layer, n_layer=n_bins, volume=True)
+                if with_residuals:      # a second evaluation: the stack's call keeps no residuals
+                    resid = (residuals(fwd, t_corr, vs, a_corr, qs, grid, prior=prior), obs.t_stdv, obs.a_stdv)
+            elif with_residuals:        # the one evaluation serves .stat and .best.dat too
+                res = residuals(fwd, t_corr, vs, a_corr, qs, grid, prior=prior)
+                resid = (res, obs.t_stdv, obs.a_stdv)
             else:
                 res = evaluate(fwd, t_corr, vs, a_corr, qs, grid, prior=prior, volume=volume)
             return (res, draw_evidence(fwd, t_corr, vs, a_corr, qs, grid, prior=prior)) if weights else res
         finally:
             fwd.close()
 
-    res, ev = run(win_id, False, True, args.stack) if args.draw_weights else (run(win_id, False, stacked=args.stack), None)
+    res, ev = run(win_id, False, True, args.stack) if args.draw_weights else (run(win_id, False, stacked=args.stack, with_residuals=args.residuals), None)
     marg = np.concatenate([res["marg_x"], res["marg_y"], res["marg_z"]], axis=1)
     with open(os.path.join(work, stem + ".stat"), "w") as fh:
         fh.write(stat_text(win_id, marginal_quantiles(marg, grid)))
@@ -645,6 +794,15 @@ def main(argv=None):
                 with open(os.path.join(work, stem + ".density.%s.dat" % nm), "w") as fh:
                     fh.write(stack_map_text(nm, res["stack" if nm == "vol" else nm], grid, levels))
         sys.stdout.write(stack_summary_text(res["tally"], face_share(res["stack"]), n_unresolved))
+    if resid is not None:
+        rr, t_stdv, a_stdv = resid
+        use = (bool(par.get_use_time()), bool(par.get_use_amp()))
+        for name, text in (("residuals", residuals_text(win_id, par.stations, rr["res"], t_stdv, a_stdv, use)),
+                           ("fit", fit_text(win_id, rr["fit"], t_stdv, use)),
+                           ("stations", stations_text(win_id, par.stations, rr["res"], t_stdv, a_stdv, use))):
+            with open(os.path.join(work, stem + "." + name + ".dat"), "w") as fh:
+                fh.write(text)
+        sys.stdout.write(stations_summary_text(win_id, par.stations, rr["res"], t_stdv, a_stdv, use))
     if ev is not None:
         with open(os.path.join(work, stem + ".draws.dat"), "w") as fh:
             fh.write(draws_text(win_id, ev, records))

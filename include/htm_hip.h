@@ -251,12 +251,48 @@ int htm_forward_locate_stack(htm_forward *h, int n_draws, const double *t_corr, 
                              const double *qs, const double *grid9, const double *prior5, const int *layer, int n_layer,
                              double *loc, double *marg, double *xy, double *xz, double *yz, double *stack, double *tally);
 
-/* THE WORKSPACE AND THE BATCHES of the four entry points above, worked out without a handle and without a device: what a call
+/* PER-STATION RESIDUALS, SOURCE TERMS AND FIT of every window under the fixed structure of htm_forward_locate:
+ * how well a window fits where it was located, which stations disagree, and the two numbers that the forward model demeans away.
+ * The arguments up to marg are htm_forward_locate's.  THE RULE, for event e, a data type d that the handle uses (t: travel
+ * times, a: amplitudes), station j and cell c:
+ *   - r_dj(c) is the synthetic minus the observation (src/cls_forward.f90:115-118, :201-204), p_dj the handle's precision (the
+ *     missing-data rule as it stands: precision 1);
+ *   - the OFFSET m_d(c) = sum_j p_dj r_dj(c) / sum_j p_dj, the reference's t_mean / a_mean (:125-132, :210-217): the
+ *     precision-weighted mean time residual is an origin-time shift, and -m_a is the log source amplitude;
+ *   - the RESIDUAL rho_dj(c) = m_d(c) - r_dj(c): the observation minus the demeaned synthetic, with the sign of :284 and :295;
+ *   - chi2_d(c) = sum_j p_dj rho_dj(c)^2, formed in one pass from the shifted sums (u = r - r_0, r_0 the first station's):
+ *     m = r_0 + (sum p u) / sum p, chi2 = sum p u^2 - (sum p u)^2 / sum p;
+ *   - the posterior is the one the same call returns: the weights w(c) = exp(lp(c) - lp_best) on the included cells and 0 on the
+ *     others, W their sum as the marginals' reduce forms it, the best cell loc[0];
+ *   - a posterior mean is taken ABOUT THE BEST CELL, as the mean position is: mean(q) = q(best) + (sum_c w(c) (q(c) - q(best)))
+ *     / W, so a posterior that sits in one cell gives q(best) exactly; the offset's variance from u = m(c) - m(best) as
+ *     sum w u^2 / W - (sum w u / W)^2, floored at 0 before the square root;
+ *   - an excluded cell contributes by selection, never by 0 * value: its residual may be NaN or infinite.
+ * res [n_events][n_sta][4] = {rho_t(best), mean(rho_t), rho_a(best), mean(rho_a)} per station.
+ * fit [n_events][10], per data type, time first: {m(best), mean(m), sd(m), chi2(best), mean(chi2)}; loc[5] equals
+ *   -0.5 (chi2_t(best) + chi2_a(best)) - (the constants of :283-286 and :294-297) to htm_forward_locate's bound on a term.
+ * A data type that the handle does not use gives NaN; an event without an included cell gives NaN throughout.  res, the two m
+ * entries and the chi2 entries are good to 1e-12 of the sum of the absolute values of their terms; the variance to 1e-12 of itself
+ * plus 8 epsilon Xbar sd, Xbar the posterior mean of |synthetic| + |observation| and their p-weighted means.
+ * loc [n_events][16] and marg may be NULL; where given they are bit for bit what htm_forward_locate returns for the same
+ * arguments and precision setting.  htm_forward_locate_set_precision applies: with fp32 set the posterior and the synthetics
+ * inside the residuals come from the same single-precision forward; observations, precisions, offsets, sums and everything
+ * behind them stay fp64.  A per-station posterior spread is not given: it needs m(c) while station j is in hand, a second
+ * evaluation of every distance.  Draws of the structure are not taken.
+ * Refused with HTM_EINVAL before any device call: whatever htm_forward_locate refuses, with its messages (a NULL loc is not
+ * refused), and a NULL res or fit.  Synchronous.  Every sum has a fixed order and there are no floating-point atomics: two calls
+ * give the same bits, and the bits do not depend on HTM_LOCATE_MB.  The workspace per event of a batch holds the event's volume
+ * (htm_forward_locate_plan). */
+int htm_forward_locate_residuals(htm_forward *h, const double *t_corr, double vs, const double *a_corr, double qs,
+                                 const double *grid9, const double *prior5, double *loc, double *marg, double *res, double *fit);
+
+/* THE WORKSPACE AND THE BATCHES of the five entry points above, worked out without a handle and without a device: what a call
  * of that shape would allocate and how many events it would send at a time, or the refusal it would meet, with the same code
  * and text.  HTM_LOCATE_MB is read from the environment as a call reads it.  The request names what a call says through its
  * arguments: `job` 0 htm_forward_locate, 1 htm_forward_locate_marginal, 2 htm_forward_locate_draw_evidence (n_draws 0 for
  * job 0, 1..4096 otherwise); `volume`: vol is asked for; `prior`: prior5 is given; n_layer >= 1: htm_forward_locate_stack
- * (jobs 0 and 1; 0: no stack) with `layer` given or not; forward_fp32: htm_forward_locate_set_precision's setting.
+ * (jobs 0 and 1; 0: no stack) with `layer` given or not; forward_fp32: htm_forward_locate_set_precision's setting;
+ * `residuals`: htm_forward_locate_residuals (job 0, without `volume` and without a stack).
  * THE FORMULA, stated here once.  With cells = nx ny nz, n_marg = nx + ny + nz, rows = max(1, min(ny, 256, 4096 / nx)) x-rows
  * per tile, tpl = ceil(ny / rows) tiles per z-layer, n_tiles = nz tpl, stride = 4 + nx + 2 rows doubles per tile, Kpad = n_draws
  * padded to whole blocks of 8:
@@ -264,13 +300,16 @@ int htm_forward_locate_stack(htm_forward *h, int n_draws, const double *t_corr, 
  *     jobs 0, 1   8 (n_tiles stride + 16 + 2 n_marg + [cells: with vol, or stacked] + [1: stacked]) + 80 n_sta + 32
  *     job 2       8 (n_tiles Kpad 2 + n_draws + 4 + n_marg) + 80 n_sta + 32
  *     (the prior's n_marg is counted with a flat prior too, where nothing is allocated for it);
+ *     with `residuals`, on top of job 0's:  8 (cells + 1 + (2 n_sta + 4) + n_rblk (2 n_sta + 6) + 4 n_sta + 10) -- the kept
+ *     volume, the weight sum w, the residuals and sums at the best cell, the partial records of n_rblk = ceil(cells / 1024) blocks
+ *     of cells, res and fit;
  *   the draws' table, once per call (jobs 1, 2):  P (n_sta + 1) Kpad + 8 (2 n_sta + 2) n_draws, a pair P = 16 bytes, 8 with
  *     forward_fp32;
  *   the stack, once per call:  8 n_layer (cells + nx ny + nx nz + ny nz + 2) + 4 n_events where `layer` is given.
  * nb, the events of a batch, is the smallest of n_events and nb_limit[0..3]: 65535 (a launch's grid), (2^32 - 1) / (256
- * n_tiles) and (2^32 - 257) / n_sta (the work-items of a launch), and floor((HTM_LOCATE_MB 2^20 - table - stack) / per event),
+ * n_tiles) -- with `residuals` (2^32 - 1) / (256 max(n_tiles, n_rblk)) -- and (2^32 - 257) / n_sta (the work-items of a launch), and floor((HTM_LOCATE_MB 2^20 - table - stack) / per event),
  * itself at most 65535; and 1 at the least.  len_*: the elements of every device array, per event of a batch (sta .. w) and
- * once per call (dtc .. layer); 0: the call has no such array.
+ * once per call (dtc .. layer), and the residuals' per event of a batch (rbase .. fit); 0: the call has no such array.
  * HTM_EINVAL, in this order: a NULL argument or a request that no entry point makes; a bad grid; more than 2^31 - 1 cells;
  * HTM_LOCATE_MB not positive; the draws' table and one event above it; n_layer (cells + nx ny + nx nz + ny nz + 2) above
  * 2^31 - 1; the stack, the table and one event above HTM_LOCATE_MB.  (A call checks the prior's widths after the cells.) */
@@ -283,6 +322,7 @@ typedef struct htm_locate_request {
     int32_t volume, prior;
     int32_t n_layer, layer;
     int32_t forward_fp32;
+    int32_t residuals;                                /* htm_forward_locate_residuals (job 0, no volume, no stack) */
 } htm_locate_request;
 typedef struct htm_locate_plan {
     int64_t rows, tpl, stride;
@@ -293,6 +333,7 @@ typedef struct htm_locate_plan {
     double per_event_bytes, table_bytes, fixed_bytes;
     int64_t nb_limit[4];
     int64_t nb;
+    int64_t len_rbase, len_rpart, len_res, len_fit;   /* per event of a batch, of a request with `residuals`; 0 otherwise */
 } htm_locate_plan;
 int htm_forward_locate_plan(const htm_locate_request *request, const double *grid9, htm_locate_plan *plan);
 
