@@ -10,8 +10,8 @@
 //                     workgroup reads it with uniform SCALAR loads (ld_const), and one record of constants per event
 //   k_locate<MODE>    grid = (tiles, events of the batch).  A tile is up to kLocRows whole x-rows of ONE z-layer, at most
 //                     kLocTile cells; a thread owns the cells t, t + 256, ... of it, kLocChunk at a time (independent
-//                     dependency chains).  The demeaned misfit comes in one pass from the shifted identity (loc_station,
-//                     loc_term: the station arithmetic of all three kernel families, stated once).
+//                     dependency chains).  The demeaned misfit comes in one pass from the shifted identity (loc_distance,
+//                     loc_residuals, LocSums: the station rule of every kernel that evaluates a cell, stated once).
 //                     The lanes keep their cells' log posteriors in registers, the workgroup finds the tile's maximum and
 //                     its first cell, puts the weights exp(lp - max) in LDS and sums them there in a fixed order: per x-row
 //                     (a wave per row, the fixed-tree wave sum) and per ix over the rows.  One partial record per tile.
@@ -26,7 +26,8 @@
 //                     layer from the batch's volume, and the three projections; described where they stand, below k_locate_combine
 //   k_locate_res_best, k_locate_residuals<MODE>, k_locate_res_combine    htm_forward_locate_residuals: every station's residual, the
 //                     offsets that the demeaning takes away and chi2, at the best cell and as means over the window's posterior,
-//                     from the batch's volume; described where they stand, at the end
+//                     from the batch's volume; described where they stand, at the end.  They share k_locate's station rule
+//                     (loc_station_res) and the sums' offset and chi2 (LocSums<1>); the reductions are their own
 // No floating-point atomics anywhere: the bits do not depend on timing.  The volume of log posteriors is written only when it
 // is asked for, stacked, or read by the residual pass.
 //
@@ -139,14 +140,17 @@ __device__ __forceinline__ void loc_best_wave(LocBest &a)
     for (int off = 32; off; off >>= 1) loc_better(a, __shfl_xor(a.lp, off), __shfl_xor(a.ell, off), __shfl_xor(a.idx, off));
 }
 
-// sum over the block's 256 threads in a fixed order: the wave sums' tree, then (w0 + w1) + (w2 + w3); every thread gets it
+// the four waves' values, `stride` apart in LDS, in a fixed order: (w0 + w1) + (w2 + w3)
+__device__ __forceinline__ double loc_sum4(const double *s, int stride = 1) { return (s[0] + s[stride]) + (s[2 * stride] + s[3 * stride]); }
+
+// sum over the block's 256 threads in a fixed order: the wave sums' tree, then loc_sum4; every thread gets it
 __device__ __forceinline__ double loc_block_sum(double v, double *s_red4)
 {
     const double w = wave_sum1(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) s_red4[threadIdx.x >> 6] = w;
     __syncthreads();
-    return (s_red4[0] + s_red4[1]) + (s_red4[2] + s_red4[3]);
+    return loc_sum4(s_red4);
 }
 
 // what a workgroup knows of its tile and event
@@ -270,10 +274,15 @@ __device__ __forceinline__ void loc_cell_xy(const LocGrid &g, int iy0, int ncell
     pxy = prior ? prior[ix] + prior[g.nx + iy0 + r] : 0.0;
 }
 
-// ---- the station body of k_locate, k_locate_marginal and k_locate_draw_evidence ------------------------------------------
+// ---- the station rule of all five kernels that evaluate the forward model at a cell ---------------------------------------
+// k_locate, k_locate_marginal, k_locate_draw_evidence (loc_station) and the residual pass, k_locate_res_best and
+// k_locate_residuals (loc_station_res), are built from the same three statements: loc_distance, loc_residuals, LocSums::add.
+//
 // The demeaned misfit of a cell comes in one pass from the shifted identity sum p (r - m)^2 = sum p u^2 - (sum p u)^2 / sum p,
-// u = r - r_0 (r_0: the first station's residual).  Per data type and per structure (D of them side by side: one for k_locate,
-// a block of draws for the other two): the shifts and the running sums
+// u = r - r_0 (r_0: the first station's residual).  Per data type and per structure (D of them side by side: one for k_locate
+// and the residual pass, a block of draws for the other two): the shifts and the running sums, and what falls out of them when
+// the stations are through: the offset m = r_0 + s1 / sum p that the demeaning takes away, and chi2 = s2 - s1^2 / sum p
+// (1 / sum p per data type: LocEv's rpst, rpsa)
 template <int D>
 struct LocSums {
     double r0t[D], r0a[D], t1[D], t2[D], a1[D], a2[D];
@@ -282,62 +291,93 @@ struct LocSums {
 #pragma unroll
         for (int q = 0; q < D; ++q) t1[q] = t2[q] = a1[q] = a2[q] = r0t[q] = r0a[q] = 0.0;
     }
+    // a station's residual r of precision p into one data type's sums.  first: station 0, which gives the shift by the same
+    // operations (its u is r - r, not a constant)
+    __device__ __forceinline__ static void add(bool first, double r, double p, double &r0, double &s1, double &s2)
+    {
+        if (first) r0 = r;
+        const double u = r - r0, pu = p * u;
+        s1 += pu;
+        s2 = __builtin_fma(pu, u, s2);
+    }
+    __device__ __forceinline__ double mt(const LocEv &ev, int q = 0) const { return r0t[q] + t1[q] * ev.rpst; }
+    __device__ __forceinline__ double ma(const LocEv &ev, int q = 0) const { return r0a[q] + a1[q] * ev.rpsa; }
+    __device__ __forceinline__ double chi2t(const LocEv &ev, int q = 0) const { return t2[q] - (t1[q] * t1[q]) * ev.rpst; }
+    __device__ __forceinline__ double chi2a(const LocEv &ev, int q = 0) const { return a2[q] - (a1[q] * a1[q]) * ev.rpsa; }
 };
 
-// The station st at the cell (x, y, zc) under D structures (1 / vs, pi f / (qs vs), the station's corrections tc, ac), into the
-// sums: the distance and its logarithm once, then per structure the residuals (synthetic minus observation: cls_forward.f90:
-// 115-118, :201-204 as event_misfit) and their shifted sums.  first: station 0, which gives the shifts by the same operations
-// (its u is r - r, not a constant).  MODE: 1 travel times only, 2 amplitudes only, 3 both.
-//
-// F32, the single-precision forward (event_misfit<.., F32>'s rule at a cell centre; T is float, and the structure comes as its
-// (loc_res_station and LocResCell, at the end of this file, restate this body's residuals and sums operation for operation for the
-// residual pass: an edit here is an edit there.)
-// float copies): the three coordinate differences are formed in fp64 and rounded to float; d = v_sqrt_f32(fma(dz, dz, fma(dy,
-// dy, dx dx))) and log2 d = v_log_f32(d), once per (cell, station); per structure the travel time fma(d, 1 / vs, -tc) and the
-// amplitude fma(-d, pi f / (qs vs), -fma(log2 d, ln 2, ac)) in float -- ln d is folded into the structure's own fma, as
-// event_misfit has it, and is never formed by itself --; each synthetic is promoted to double BEFORE the observation is
-// subtracted.  Observations, precisions, shifts and sums are fp64 in both forms: everything from `rt` and `ra` on is one text.
+// F32 = false: all arithmetic fp64.  F32 = true, the single-precision forward (event_misfit<.., F32>'s rule at a cell centre; T is
+// float, and the structure comes as its float copies): the three coordinate differences are formed in fp64 and rounded to float;
+// d = v_sqrt_f32(fma(dz, dz, fma(dy, dy, dx dx))) and log2 d = v_log_f32(d), once per (cell, station); per structure the travel
+// time fma(d, 1 / vs, -tc) and the amplitude fma(-d, pi f / (qs vs), -fma(log2 d, ln 2, ac)) in float -- ln d is folded into the
+// structure's own fma, as event_misfit has it, and is never formed by itself --; each synthetic is promoted to double BEFORE the
+// observation is subtracted.  Observations, precisions, shifts and sums are fp64 in both forms: everything from `rt` and `ra` on
+// is one text.
 template <bool F32>
 using loc_real = std::conditional_t<F32, float, double>;
 
+// the distance d of the cell (x, y, z) from the station; and, where amplitudes are in use (UA), lg = -ln d (fp64) or log2 d (F32)
+template <bool UA, bool F32>
+__device__ __forceinline__ void loc_distance(const LocSta &st, double x, double y, double z, loc_real<F32> &d, loc_real<F32> &lg)
+{
+    lg = 0;
+    if constexpr (F32) {
+        const float dx = (float)(x - st.sx), dy = (float)(y - st.sy), dz = (float)(z - st.sz);
+        d = __builtin_amdgcn_sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)));
+        if constexpr (UA) lg = __builtin_amdgcn_logf(d);
+    } else {
+        const double dx = x - st.sx, dy = y - st.sy, dz = z - st.sz;
+        d = htm_sqrt(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)));
+        if constexpr (UA) lg = -htm_log(d);
+    }
+}
+
+// The station's residuals (synthetic minus observation: cls_forward.f90:115-118, :201-204 as event_misfit) at the distance d
+// under ONE structure -- 1 / vs, pi f / (qs vs), the station's corrections tc, ac --, each into structure q's sums as it is
+// formed: the time sums are added before the amplitude residual is formed.  rt, ra: the residuals themselves (what MODE
+// leaves out stays 0).  MODE: 1 travel times only, 2 amplitudes only, 3 both.
+template <int MODE, bool F32, int D>
+__device__ __forceinline__ void loc_residuals(const LocSta &st, bool first, loc_real<F32> d, loc_real<F32> lg, loc_real<F32> rbeta, loc_real<F32> katt,
+                                              loc_real<F32> tc, loc_real<F32> ac, LocSums<D> &sm, int q, double &rt, double &ra)
+{
+    rt = 0.0; ra = 0.0;
+    if constexpr ((MODE & 1) != 0) {
+        if constexpr (F32) rt = (double)__builtin_fmaf(d, rbeta, -tc) - st.tob;
+        else rt = __builtin_fma(d, rbeta, -tc) - st.tob;
+        sm.add(first, rt, st.tpr, sm.r0t[q], sm.t1[q], sm.t2[q]);
+    }
+    if constexpr ((MODE & 2) != 0) {
+        if constexpr (F32) ra = (double)__builtin_fmaf(-d, katt, -__builtin_fmaf(lg, 0.69314718055994531f, ac)) - st.aob;
+        else ra = (__builtin_fma(-d, katt, lg) - ac) - st.aob;
+        sm.add(first, ra, st.apr, sm.r0a[q], sm.a1[q], sm.a2[q]);
+    }
+}
+
+// The station st at the cell (x, y, zc) under D structures, into the sums: the distance and its logarithm once, then every
+// structure's residuals
 template <int MODE, int D, bool F32>
 __device__ __forceinline__ void loc_station(const LocSta &st, const loc_real<F32> (&tc)[D], const loc_real<F32> (&ac)[D], bool first, double x, double y,
                                             double zc, const loc_real<F32> (&rbeta)[D], const loc_real<F32> (&katt)[D], LocSums<D> &sm)
 {
-    typedef loc_real<F32> T;
-    constexpr bool UT = (MODE & 1) != 0, UA = (MODE & 2) != 0;
-    // the distance; and for the amplitudes -ln d (fp64) or log2 d (F32)
-    T d, lg = 0;
-    if constexpr (F32) {
-        const float dx = (float)(x - st.sx), dy = (float)(y - st.sy), dz = (float)(zc - st.sz);
-        d = __builtin_amdgcn_sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)));
-        if constexpr (UA) lg = __builtin_amdgcn_logf(d);
-    } else {
-        const double dx = x - st.sx, dy = y - st.sy, dz = zc - st.sz;
-        d = htm_sqrt(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)));
-        if constexpr (UA) lg = -htm_log(d);
-    }
+    loc_real<F32> d, lg;
+    loc_distance<(MODE & 2) != 0, F32>(st, x, y, zc, d, lg);
 #pragma unroll
     for (int q = 0; q < D; ++q) {
-        if constexpr (UT) {
-            double rt;
-            if constexpr (F32) rt = (double)__builtin_fmaf(d, rbeta[q], -tc[q]) - st.tob;
-            else rt = __builtin_fma(d, rbeta[q], -tc[q]) - st.tob;
-            if (first) sm.r0t[q] = rt;
-            const double u = rt - sm.r0t[q], pu = st.tpr * u;
-            sm.t1[q] += pu;
-            sm.t2[q] = __builtin_fma(pu, u, sm.t2[q]);
-        }
-        if constexpr (UA) {
-            double ra;
-            if constexpr (F32) ra = (double)__builtin_fmaf(-d, katt[q], -__builtin_fmaf(lg, 0.69314718055994531f, ac[q])) - st.aob;
-            else ra = (__builtin_fma(-d, katt[q], lg) - ac[q]) - st.aob;
-            if (first) sm.r0a[q] = ra;
-            const double u = ra - sm.r0a[q], pu = st.apr * u;
-            sm.a1[q] += pu;
-            sm.a2[q] = __builtin_fma(pu, u, sm.a2[q]);
-        }
+        double rt, ra;
+        loc_residuals<MODE, F32>(st, first, d, lg, rbeta[q], katt[q], tc[q], ac[q], sm, q, rt, ra);
     }
+}
+
+// The same under the job's one structure as LocJob and the station's record hold it, for the residual pass, which wants the
+// residuals themselves too
+template <int MODE, bool F32>
+__device__ __forceinline__ void loc_station_res(const LocSta &st, const LocJob &jb, bool first, double x, double y, double z, LocSums<1> &sm,
+                                                double &rt, double &ra)
+{
+    loc_real<F32> d, lg;
+    loc_distance<(MODE & 2) != 0, F32>(st, x, y, z, d, lg);
+    if constexpr (F32) loc_residuals<MODE, F32>(st, first, d, lg, jb.rbeta32, jb.katt32, st.tc32, st.ac32, sm, 0, rt, ra);
+    else loc_residuals<MODE, F32>(st, first, d, lg, jb.rbeta, jb.katt, st.tc, st.ac, sm, 0, rt, ra);
 }
 
 // the cell's log-likelihood term under structure q from the finished sums
@@ -345,8 +385,8 @@ template <int MODE, int D>
 __device__ __forceinline__ double loc_term(const LocSums<D> &sm, const LocEv &ev, int q)
 {
     double e = 0.0;
-    if constexpr ((MODE & 1) != 0) e -= 0.5 * (sm.t2[q] - (sm.t1[q] * sm.t1[q]) * ev.rpst) + ev.ct;
-    if constexpr ((MODE & 2) != 0) e -= 0.5 * (sm.a2[q] - (sm.a1[q] * sm.a1[q]) * ev.rpsa) + ev.ca;
+    if constexpr ((MODE & 1) != 0) e -= 0.5 * sm.chi2t(ev, q) + ev.ct;
+    if constexpr ((MODE & 2) != 0) e -= 0.5 * sm.chi2a(ev, q) + ev.ca;
     return e;
 }
 
@@ -872,7 +912,7 @@ __global__ __launch_bounds__(256) void k_locate_stack_project(LocGrid g, int n_l
 //
 //   k_locate_res_best     one wave per event, the stations in their order (uniform: scalar loads, every lane the same numbers):
 //                         r_j(best) per station and data type, then m(best) and chi2(best) from the shifted sums, by the very
-//                         operations that k_locate_residuals applies to a cell (loc_res_station, loc_res_cell)
+//                         operations that k_locate_residuals applies to a cell (loc_station_res: k_locate's station rule)
 //   k_locate_residuals    grid = (blocks of kLocResBlock cells, events of the batch); cells by linear index, a thread owns the
 //                         cells t, t + 256, ... of its block, kLocResCells side by side.  ONE station loop per cell (uniform,
 //                         the outer loop): per station the lanes' sum_k w (r_j - r_j(best)) goes through the wave sums' fixed
@@ -894,54 +934,6 @@ struct LocRes {
     int n_blk;
 };
 
-// loc_station's residuals of station st at the cell (x, y, z) under one structure, by the same operations: rt, ra (what MODE
-// leaves out stays 0)
-template <int MODE, bool F32>
-__device__ __forceinline__ void loc_res_station(const LocSta &st, const LocJob &jb, double x, double y, double z, double &rt, double &ra)
-{
-    constexpr bool UT = (MODE & 1) != 0, UA = (MODE & 2) != 0;
-    rt = 0.0; ra = 0.0;
-    if constexpr (F32) {
-        const float dx = (float)(x - st.sx), dy = (float)(y - st.sy), dz = (float)(z - st.sz);
-        const float d = __builtin_amdgcn_sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)));
-        if constexpr (UT) rt = (double)__builtin_fmaf(d, jb.rbeta32, -st.tc32) - st.tob;
-        if constexpr (UA) {
-            const float lg = __builtin_amdgcn_logf(d);
-            ra = (double)__builtin_fmaf(-d, jb.katt32, -__builtin_fmaf(lg, 0.69314718055994531f, st.ac32)) - st.aob;
-        }
-    } else {
-        const double dx = x - st.sx, dy = y - st.sy, dz = z - st.sz;
-        const double d = htm_sqrt(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)));
-        if constexpr (UT) rt = __builtin_fma(d, jb.rbeta, -st.tc) - st.tob;
-        if constexpr (UA) { const double lg = -htm_log(d); ra = (__builtin_fma(-d, jb.katt, lg) - st.ac) - st.aob; }
-    }
-}
-
-// a cell's shifted sums, as loc_station keeps them (LocSums<1>), and what falls out of them: m = r_0 + t1 / sum p,
-// chi2 = t2 - t1^2 / sum p
-struct LocResCell {
-    double r0t, r0a, t1, t2, a1, a2;
-    __device__ __forceinline__ void clear() { r0t = r0a = t1 = t2 = a1 = a2 = 0.0; }
-    template <int MODE>
-    __device__ __forceinline__ void add(const LocSta &st, bool first, double rt, double ra)
-    {
-        if constexpr ((MODE & 1) != 0) {
-            if (first) r0t = rt;
-            const double u = rt - r0t, pu = st.tpr * u;
-            t1 += pu; t2 = __builtin_fma(pu, u, t2);
-        }
-        if constexpr ((MODE & 2) != 0) {
-            if (first) r0a = ra;
-            const double u = ra - r0a, pu = st.apr * u;
-            a1 += pu; a2 = __builtin_fma(pu, u, a2);
-        }
-    }
-    __device__ __forceinline__ double mt(const LocEv &ev) const { return r0t + t1 * ev.rpst; }
-    __device__ __forceinline__ double ma(const LocEv &ev) const { return r0a + a1 * ev.rpsa; }
-    __device__ __forceinline__ double chi2t(const LocEv &ev) const { return t2 - (t1 * t1) * ev.rpst; }
-    __device__ __forceinline__ double chi2a(const LocEv &ev) const { return a2 - (a1 * a1) * ev.rpsa; }
-};
-
 // the centre of the cell of linear index c
 __device__ __forceinline__ void loc_res_centre(const LocGrid &g, long c, double &x, double &y, double &z)
 {
@@ -961,13 +953,12 @@ __global__ __launch_bounds__(64) void k_locate_res_best(LocGrid g, LocJob jb, Lo
     double *base = rs.base + (size_t)b * (2 * (size_t)S + kLocResBase);
     double x, y, z;
     loc_res_centre(g, (long)idx, x, y, z);
-    LocResCell sm;
+    LocSums<1> sm;
     sm.clear();
     for (int j = 0; j < S; ++j) {
         const LocSta st = loc_ld_sta(sta + j);
         double rt, ra;
-        loc_res_station<MODE, F32>(st, jb, x, y, z, rt, ra);
-        sm.add<MODE>(st, j == 0, rt, ra);
+        loc_station_res<MODE, F32>(st, jb, j == 0, x, y, z, sm, rt, ra);
         if (threadIdx.x == 0) { base[2 * (size_t)j] = rt; base[2 * (size_t)j + 1] = ra; }
     }
     if (threadIdx.x == 0) {
@@ -997,7 +988,7 @@ __global__ __launch_bounds__(256) void k_locate_residuals(LocGrid g, LocJob jb, 
 
     double x[C], y[C], z[C], w[C];
     bool inc[C];
-    LocResCell sm[C];
+    LocSums<1> sm[C];
 #pragma unroll
     for (int k = 0; k < C; ++k) {
         const long c = (long)blockIdx.x * kLocResBlock + kLocThreads * k + t;
@@ -1019,8 +1010,7 @@ __global__ __launch_bounds__(256) void k_locate_residuals(LocGrid g, LocJob jb, 
 #pragma unroll
             for (int k = 0; k < C; ++k) {
                 double rt, ra;
-                loc_res_station<MODE, F32>(st, jb, x[k], y[k], z[k], rt, ra);
-                sm[k].add<MODE>(st, j == 0, rt, ra);
+                loc_station_res<MODE, F32>(st, jb, j == 0, x[k], y[k], z[k], sm[k], rt, ra);
                 if constexpr (UT) v[0] += inc[k] ? w[k] * (rt - rb[0]) : 0.0;
                 if constexpr (UA) v[1] += inc[k] ? w[k] * (ra - rb[1]) : 0.0;
             }
@@ -1030,7 +1020,7 @@ __global__ __launch_bounds__(256) void k_locate_residuals(LocGrid g, LocJob jb, 
         __syncthreads();
         if (t < 2 * nj) {
             const int jj = t >> 1, d = t & 1;
-            rec[2 * (size_t)j0 + t] = (s_sta[0][jj][d] + s_sta[1][jj][d]) + (s_sta[2][jj][d] + s_sta[3][jj][d]);
+            rec[2 * (size_t)j0 + t] = loc_sum4(&s_sta[0][jj][d], 2 * kLocResSta);
         }
         __syncthreads();                                    // (read before the next block of stations overwrites it)
     }
@@ -1057,7 +1047,7 @@ __global__ __launch_bounds__(256) void k_locate_residuals(LocGrid g, LocJob jb, 
         for (int i = 0; i < kLocResEv; ++i) s_ev[wv][i] = e[i];
     }
     __syncthreads();
-    if (t < kLocResEv) rec[2 * (size_t)S + t] = (s_ev[0][t] + s_ev[1][t]) + (s_ev[2][t] + s_ev[3][t]);
+    if (t < kLocResEv) rec[2 * (size_t)S + t] = loc_sum4(&s_ev[0][t], kLocResEv);
 }
 
 // use_t, use_a: the data types of the handle

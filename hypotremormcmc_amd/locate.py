@@ -95,19 +95,68 @@ BEST_HEADER = ("# window ID, best cell's centre x y z, log posterior there, log-
                "posterior mean x y z, 1: the best cell lies on a face of the box")
 
 
-@contextlib.contextmanager
-def _precision(fwd, precision):
-    """`precision` None: the Forward's locate precision as it is; "fp32" or "fp64": that one inside the block, and the
-    previous setting back after it"""
-    if precision is None:
-        yield
-        return
-    before = fwd.locate_precision
-    fwd.set_locate_precision(precision)
-    try:
-        yield
-    finally:
-        fwd.set_locate_precision(before)
+def _corrections(t_corr, vs, a_corr, qs, S, draws):
+    """K and t_corr, vs, a_corr, qs as the library takes them.  A fixed structure (K = 0): one t_corr and a_corr per station and
+    the scalars vs, qs as arrays of one; draws: K of vs and qs, K x S of the corrections"""
+    tc, ac = (np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1)) for a in (t_corr, a_corr))
+    if not draws:
+        if tc.size != S or ac.size != S:
+            raise ValueError(f"t_corr and a_corr have {tc.size} and {ac.size} values: need one per station ({S})")
+        return 0, tc, np.array([float(vs)]), ac, np.array([float(qs)])
+    v, q = (np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1)) for a in (vs, qs))
+    K = v.size
+    if q.size != K or tc.size != K * S or ac.size != K * S:
+        raise ValueError(f"{K} draws of vs: need as many of qs (got {q.size}) and one t_corr and a_corr per draw and station "
+                         f"({K} x {S}; got {tc.size} and {ac.size} values)")
+    return K, tc, v, ac, q
+
+
+class _Call:
+    """One call's inputs as the library takes them, checked, and the outputs every call has: the grid `g` and its counts nx, ny,
+    nz (at most 2^31 - 1 cells), the structure K, tc, vs, ac, qs (_corrections), the prior [E][5] or None, loc [E][16], marg
+    [E][nx + ny + nz] and vol [E][nz][ny][nx] (None where not asked for)"""
+
+    def __init__(self, fwd, t_corr, vs, a_corr, qs, grid, prior, draws, marginals=True, volume=False):
+        self.fwd, E = fwd, fwd.n_events
+        self.g = grid9(grid)
+        self.nx, self.ny, self.nz = nx, ny, nz = grid_counts(self.g)
+        if nx * ny * nz > INT_MAX:
+            raise ValueError(f"{nx} x {ny} x {nz} cells: more than 2^31 - 1")
+        self.K, self.tc, self.vs, self.ac, self.qs = _corrections(t_corr, vs, a_corr, qs, fwd.n_sta, draws)
+        self.prior = None if prior is None else np.ascontiguousarray(prior, dtype=np.float64)
+        if prior is not None and self.prior.shape != (E, 5):
+            raise ValueError(f"prior is {self.prior.shape}: need mu_x, mu_y, w_xy, z0, w_z of every event ({E})")
+        self.loc = np.empty((E, 16))
+        self.marg = np.empty((E, nx + ny + nz)) if marginals else None
+        self.vol = np.empty((E, nz, ny, nx)) if volume else None
+
+    def run(self, entry, precision, *outputs, scalars=False):
+        """the library's `entry` on the Forward: the structure (`scalars`: vs and qs by value and no K, as the entry points of a
+        fixed structure take it), the grid, the prior, then `outputs` (float64 arrays or None by their pointers, anything else as
+        it is).  precision: None, the Forward's locate precision as it is; "fp32" or "fp64": that one for this call, and the
+        previous setting back after it"""
+        p = _lib.ptr
+        head = (p(self.tc), float(self.vs[0]), p(self.ac), float(self.qs[0])) if scalars else (self.K, p(self.tc), p(self.vs), p(self.ac), p(self.qs))
+        tail = [p(a) if a is None or isinstance(a, np.ndarray) else a for a in outputs]
+        if precision is not None:
+            before = self.fwd.locate_precision
+            self.fwd.set_locate_precision(precision)
+        try:
+            _lib.check(getattr(_lib.load(), entry)(self.fwd.handle, *head, p(self.g), p(self.prior), *tail))
+        finally:
+            if precision is not None:
+                self.fwd.set_locate_precision(before)
+
+    def result(self):
+        """the dict of `locate` from the library's arrays"""
+        loc, marg, nx, ny = self.loc, self.marg, self.nx, self.ny
+        cov = np.empty((loc.shape[0], 3, 3))
+        for (i, j), k in zip(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2)), range(10, 16)):
+            cov[:, i, j] = cov[:, j, i] = loc[:, k]
+        return {"index": loc[:, 0].astype(np.int64), "best": loc[:, 1:4].copy(), "lp": loc[:, 4].copy(), "ell": loc[:, 5].copy(),
+                "log_evidence": loc[:, 6].copy(), "mean": loc[:, 7:10].copy(), "cov": cov, "loc": loc,
+                "marg_x": None if marg is None else marg[:, :nx], "marg_y": None if marg is None else marg[:, nx:nx + ny],
+                "marg_z": None if marg is None else marg[:, nx + ny:], "vol": self.vol}
 
 
 def locate(fwd, t_corr, vs, a_corr, qs, grid, prior=None, marginals=True, volume=False, precision=None):
@@ -118,18 +167,9 @@ def locate(fwd, t_corr, vs, a_corr, qs, grid, prior=None, marginals=True, volume
     the library's record, marg_x / marg_y / marg_z [E][n] (None without `marginals`), vol [E][nz][ny][nx] (None without
     `volume`).  precision: None, the Forward's own setting (Forward.set_locate_precision; "fp64" unless it was changed), or
     "fp32" / "fp64" for this call, the previous setting put back after it."""
-    g, (nx, ny, nz) = _grid(grid)
-    E, S = fwd.n_events, fwd.n_sta
-    tc = np.ascontiguousarray(np.asarray(t_corr, dtype=np.float64).reshape(-1))
-    ac = np.ascontiguousarray(np.asarray(a_corr, dtype=np.float64).reshape(-1))
-    if tc.size != S or ac.size != S:
-        raise ValueError(f"t_corr and a_corr have {tc.size} and {ac.size} values: need one per station ({S})")
-    pr = _prior_array(prior, E)
-    loc, marg, vol = _outputs(E, nx, ny, nz, marginals, volume)
-    with _precision(fwd, precision):
-        _lib.check(_lib.load().htm_forward_locate(fwd.handle, _lib.ptr(tc), float(vs), _lib.ptr(ac), float(qs), _lib.ptr(g), _lib.ptr(pr),
-                                                  _lib.ptr(loc), _lib.ptr(marg), _lib.ptr(vol)))
-    return _result(loc, marg, vol, nx, ny)
+    c = _Call(fwd, t_corr, vs, a_corr, qs, grid, prior, False, marginals, volume)
+    c.run("htm_forward_locate", precision, c.loc, c.marg, c.vol, scalars=True)
+    return c.result()
 
 
 def locate_marginal(fwd, t_corr, vs, a_corr, qs, grid, prior=None, marginals=True, volume=False, precision=None):
@@ -137,15 +177,9 @@ def locate_marginal(fwd, t_corr, vs, a_corr, qs, grid, prior=None, marginals=Tru
     cell's log-likelihood term is log((1 / K) sum_k exp(l_k)), l_k the term `locate` takes under draw k; one kernel evaluates
     all draws (htm_forward_locate_marginal).  Returns the dict of `locate`; K = 1 gives its very bits, in
     either precision (`precision`: as `locate`'s)."""
-    g, (nx, ny, nz) = _grid(grid)
-    E, S = fwd.n_events, fwd.n_sta
-    K, tc, v, ac, q = _draws(t_corr, vs, a_corr, qs, S)
-    pr = _prior_array(prior, E)
-    loc, marg, vol = _outputs(E, nx, ny, nz, marginals, volume)
-    with _precision(fwd, precision):
-        _lib.check(_lib.load().htm_forward_locate_marginal(fwd.handle, K, _lib.ptr(tc), _lib.ptr(v), _lib.ptr(ac), _lib.ptr(q), _lib.ptr(g),
-                                                           _lib.ptr(pr), _lib.ptr(loc), _lib.ptr(marg), _lib.ptr(vol)))
-    return _result(loc, marg, vol, nx, ny)
+    c = _Call(fwd, t_corr, vs, a_corr, qs, grid, prior, True, marginals, volume)
+    c.run("htm_forward_locate_marginal", precision, c.loc, c.marg, c.vol)
+    return c.result()
 
 
 def draw_evidence(fwd, t_corr, vs, a_corr, qs, grid, prior=None, precision=None):
@@ -154,15 +188,9 @@ def draw_evidence(fwd, t_corr, vs, a_corr, qs, grid, prior=None, precision=None)
     w_k^2, w_max [E], k_max [E] (int64; the lowest index of the largest weight, -1 for a window without a cell, whose n_eff,
     w_max and log_evidence are NaN), log_evidence [E] = log((1 / K) sum_k exp(log_z_k)), `locate_marginal`'s
     (htm_forward_locate_draw_evidence)."""
-    g, (nx, ny, nz) = _grid(grid)
-    E, S = fwd.n_events, fwd.n_sta
-    K, tc, v, ac, q = _draws(t_corr, vs, a_corr, qs, S)
-    pr = _prior_array(prior, E)
-    log_z = np.empty((E, K))
-    summ = np.empty((E, 4))
-    with _precision(fwd, precision):
-        _lib.check(_lib.load().htm_forward_locate_draw_evidence(fwd.handle, K, _lib.ptr(tc), _lib.ptr(v), _lib.ptr(ac), _lib.ptr(q), _lib.ptr(g),
-                                                                _lib.ptr(pr), _lib.ptr(log_z), _lib.ptr(summ)))
+    c = _Call(fwd, t_corr, vs, a_corr, qs, grid, prior, True, marginals=False)
+    log_z, summ = np.empty((fwd.n_events, c.K)), np.empty((fwd.n_events, 4))
+    c.run("htm_forward_locate_draw_evidence", precision, log_z, summ)
     return {"log_z": log_z, "n_eff": summ[:, 0].copy(), "w_max": summ[:, 1].copy(), "k_max": summ[:, 2].astype(np.int64),
             "log_evidence": summ[:, 3].copy()}
 
@@ -175,16 +203,8 @@ def stack(fwd, t_corr, vs, a_corr, qs, grid, prior=None, layer=None, n_layer=1, 
     window in layer 0); a window whose layer is outside 0 .. n_layer - 1 takes no part.  Returns the dict of `locate` (its
     very bits; vol None) plus xy [n_layer][ny][nx], xz [n_layer][nz][nx], yz [n_layer][nz][ny], tally [n_layer][2] = windows
     stacked, windows without an included cell, and stack [n_layer][nz][ny][nx] (None without `volume`)."""
-    g, (nx, ny, nz) = _grid(grid)
-    E, S = fwd.n_events, fwd.n_sta
-    if np.ndim(vs) >= 1 or np.ndim(t_corr) == 2:
-        K, tc, v, ac, q = _draws(t_corr, vs, a_corr, qs, S)
-    else:
-        K, v, q = 0, np.array([float(vs)]), np.array([float(qs)])
-        tc = np.ascontiguousarray(np.asarray(t_corr, dtype=np.float64).reshape(-1))
-        ac = np.ascontiguousarray(np.asarray(a_corr, dtype=np.float64).reshape(-1))
-        if tc.size != S or ac.size != S:
-            raise ValueError(f"t_corr and a_corr have {tc.size} and {ac.size} values: need one per station ({S})")
+    c = _Call(fwd, t_corr, vs, a_corr, qs, grid, prior, np.ndim(vs) >= 1 or np.ndim(t_corr) == 2)
+    nx, ny, nz, E = c.nx, c.ny, c.nz, fwd.n_events
     n_layer = int(n_layer)
     if n_layer < 1:
         raise ValueError(f"n_layer = {n_layer}: need at least 1")
@@ -198,13 +218,11 @@ def stack(fwd, t_corr, vs, a_corr, qs, grid, prior=None, layer=None, n_layer=1, 
             raise ValueError(f"layer is {lay.shape}: need one per window ({E})")
     if n_layer * (nx * ny * nz + nx * ny + nx * nz + ny * nz + 2) > INT_MAX:
         raise ValueError(f"{n_layer} layers of {nx} x {ny} x {nz} cells, their maps and tallies: more than 2^31 - 1 values")
-    pr = _prior_array(prior, E)
-    loc, marg, _ = _outputs(E, nx, ny, nz, True, False)
     out = {"xy": np.empty((n_layer, ny, nx)), "xz": np.empty((n_layer, nz, nx)), "yz": np.empty((n_layer, nz, ny)),
            "stack": np.empty((n_layer, nz, ny, nx)) if volume else None, "tally": np.empty((n_layer, 2))}
-    with _precision(fwd, precision):
-        fwd.locate_stack(K, tc, v, ac, q, g, pr, lay, n_layer, loc, marg, out["xy"], out["xz"], out["yz"], out["stack"], out["tally"])
-    return dict(_result(loc, marg, None, nx, ny), **out)
+    c.run("htm_forward_locate_stack", precision, None if lay is None else lay.ctypes.data_as(_lib.ip), n_layer, c.loc, c.marg, out["xy"], out["xz"],
+          out["yz"], out["stack"], out["tally"])
+    return dict(c.result(), **out)
 
 
 def residuals(fwd, t_corr, vs, a_corr, qs, grid, prior=None, precision=None):
@@ -215,19 +233,10 @@ def residuals(fwd, t_corr, vs, a_corr, qs, grid, prior=None, precision=None):
     time first, the offset m at the best cell, its posterior mean and standard deviation, chi2 at the best cell and its
     posterior mean, with a view per column under FIT_NAMES (m_t_best, m_t_mean, m_t_sd, chi2_t_best, chi2_t_mean, m_a_best,
     ...).  A data type that the Forward does not use is NaN, a window without an included cell NaN throughout."""
-    g, (nx, ny, nz) = _grid(grid)
-    E, S = fwd.n_events, fwd.n_sta
-    tc = np.ascontiguousarray(np.asarray(t_corr, dtype=np.float64).reshape(-1))
-    ac = np.ascontiguousarray(np.asarray(a_corr, dtype=np.float64).reshape(-1))
-    if tc.size != S or ac.size != S:
-        raise ValueError(f"t_corr and a_corr have {tc.size} and {ac.size} values: need one per station ({S})")
-    pr = _prior_array(prior, E)
-    loc, marg, _ = _outputs(E, nx, ny, nz, True, False)
-    res, fit = np.empty((E, S, 4)), np.empty((E, 10))
-    with _precision(fwd, precision):
-        fwd.locate_residuals(tc, vs, ac, qs, g, pr, loc, marg, res, fit)
-    out = dict(_result(loc, marg, None, nx, ny), res=res, fit=fit, res_t_best=res[:, :, 0], res_t_mean=res[:, :, 1], res_a_best=res[:, :, 2],
-               res_a_mean=res[:, :, 3])
+    c = _Call(fwd, t_corr, vs, a_corr, qs, grid, prior, False)
+    res, fit = np.empty((fwd.n_events, fwd.n_sta, 4)), np.empty((fwd.n_events, 10))
+    c.run("htm_forward_locate_residuals", precision, c.loc, c.marg, res, fit, scalars=True)
+    out = dict(c.result(), res=res, fit=fit, res_t_best=res[:, :, 0], res_t_mean=res[:, :, 1], res_a_best=res[:, :, 2], res_a_mean=res[:, :, 3])
     out.update({nm: fit[:, k] for k, nm in enumerate(FIT_NAMES)})
     return out
 
@@ -285,53 +294,6 @@ def joint_draw_weights(log_z):
     log_w = tot - np.max(tot)
     w = np.exp(log_w)
     return log_w, w / w.sum()
-
-
-def _grid(grid):
-    """`grid` as the library takes it, and its cell counts (nx, ny, nz): at most 2^31 - 1 cells"""
-    g = grid9(grid)
-    nx, ny, nz = grid_counts(g)
-    if nx * ny * nz > INT_MAX:
-        raise ValueError(f"{nx} x {ny} x {nz} cells: more than 2^31 - 1")
-    return g, (nx, ny, nz)
-
-
-def _draws(t_corr, vs, a_corr, qs, S):
-    """K and the draws' arrays t_corr, vs, a_corr, qs as the library takes them: K of vs and qs, K x S of the corrections"""
-    v = np.ascontiguousarray(np.asarray(vs, dtype=np.float64).reshape(-1))
-    q = np.ascontiguousarray(np.asarray(qs, dtype=np.float64).reshape(-1))
-    K = v.size
-    tc = np.ascontiguousarray(np.asarray(t_corr, dtype=np.float64).reshape(-1))
-    ac = np.ascontiguousarray(np.asarray(a_corr, dtype=np.float64).reshape(-1))
-    if q.size != K or tc.size != K * S or ac.size != K * S:
-        raise ValueError(f"{K} draws of vs: need as many of qs (got {q.size}) and one t_corr and a_corr per draw and station "
-                         f"({K} x {S}; got {tc.size} and {ac.size} values)")
-    return K, tc, v, ac, q
-
-
-def _outputs(E, nx, ny, nz, marginals, volume):
-    """the arrays the library fills: loc, marg and vol (None where not asked for)"""
-    return np.empty((E, 16)), np.empty((E, nx + ny + nz)) if marginals else None, np.empty((E, nz, ny, nx)) if volume else None
-
-
-def _prior_array(prior, E):
-    if prior is None:
-        return None
-    pr = np.ascontiguousarray(prior, dtype=np.float64)
-    if pr.shape != (E, 5):
-        raise ValueError(f"prior is {pr.shape}: need mu_x, mu_y, w_xy, z0, w_z of every event ({E})")
-    return pr
-
-
-def _result(loc, marg, vol, nx, ny):
-    """the dict of `locate` from the library's arrays"""
-    cov = np.empty((loc.shape[0], 3, 3))
-    for (i, j), k in zip(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2)), range(10, 16)):
-        cov[:, i, j] = cov[:, j, i] = loc[:, k]
-    return {"index": loc[:, 0].astype(np.int64), "best": loc[:, 1:4].copy(), "lp": loc[:, 4].copy(), "ell": loc[:, 5].copy(),
-            "log_evidence": loc[:, 6].copy(), "mean": loc[:, 7:10].copy(), "cov": cov, "loc": loc,
-            "marg_x": None if marg is None else marg[:, :nx], "marg_y": None if marg is None else marg[:, nx:nx + ny],
-            "marg_z": None if marg is None else marg[:, nx + ny:], "vol": vol}
 
 
 def marginal_quantiles(marg, grid, levels=(0.025, 0.5, 0.975)):
@@ -690,6 +652,55 @@ def summary_text(res, grid, n_draws=None, precision="fp64") -> str:
             f"{int((res['index'] < 0).sum())} without an included cell\n" + prec)
 
 
+@contextlib.contextmanager
+def _forward(r5, args, ids):
+    """(obs, fwd, prior): the data of the windows `ids` of the run `r5`, a Forward on them at the invocation's precision, closed
+    at the end of the block, and their prior (None: --flat-prior)"""
+    par = r5.par
+    obs = ObsData(ids, par.n_stations, par.sta_x, par.sta_y, directory=r5.work)
+    fwd = Forward(par.n_stations, len(ids), par.sta_x, par.sta_y, par.sta_z, obs, use_amp=par.get_use_amp(), use_time=par.get_use_time(),
+                  device=r5.device)
+    try:
+        fwd.set_locate_precision(args.precision)
+        yield obs, fwd, None if args.flat_prior else step5_prior(par, obs)
+    finally:
+        fwd.close()
+
+
+def _evaluate(r5, args, ids, grid, evaluate, structure, n_bins):
+    """Everything the invocation computes of the windows `ids`, on one Forward; evaluate: `locate` or `locate_marginal`, structure:
+    t_corr, vs, a_corr, qs as it takes them.  Returns (res, ev, resid, n_unresolved): the result that .stat and .best.dat are
+    written from; draw_evidence's with --draw-weights; with --residuals (`residuals`' result, the windows' t_stdv, a_stdv); with
+    --stack-resolved the number of windows left out of the stack.  None for what was not asked for."""
+    ev = resid = n_unresolved = None
+    with _forward(r5, args, ids) as (obs, fwd, prior):
+        if args.stack:
+            # one evaluation gives the maps and what the .stat and .best.dat files are written from; --stack-resolved needs
+            # the best cells before it, from an evaluation of their own
+            layer = time_layers(ids, n_bins)
+            if args.stack_resolved:
+                first = evaluate(fwd, *structure, grid, prior=prior, marginals=False)
+                layer = resolved_layer(layer, first["index"], grid)
+                n_unresolved = int((layer < 0).sum())
+            res = stack(fwd, *structure, grid, prior=prior, layer=layer, n_layer=n_bins, volume=True)
+            if args.residuals:          # a second evaluation: the stack's call keeps no residuals
+                resid = (residuals(fwd, *structure, grid, prior=prior), obs.t_stdv, obs.a_stdv)
+        elif args.residuals:            # the one evaluation serves .stat and .best.dat too
+            res = residuals(fwd, *structure, grid, prior=prior)
+            resid = (res, obs.t_stdv, obs.a_stdv)
+        else:
+            res = evaluate(fwd, *structure, grid, prior=prior, volume=False)
+        if args.draw_weights:
+            ev = draw_evidence(fwd, *structure, grid, prior=prior)
+    return res, ev, resid, n_unresolved
+
+
+def _volume_of(r5, args, grid, evaluate, structure):
+    """the log posterior [nz][ny][nx] of the window --volume-of, from a Forward of that one window"""
+    with _forward(r5, args, [args.volume_of]) as (_, fwd, prior):
+        return evaluate(fwd, *structure, grid, prior=prior, volume=True)["vol"][0]
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m hypotremormcmc_amd.locate", description=__doc__.split("\n\n")[0])
     ap.add_argument("parameter_file")
@@ -732,7 +743,7 @@ def main(argv=None):
     if any(not 0.0 < v <= 1.0 for v in levels):
         ap.error("--level must lie in (0, 1]")
     r5 = Step5Run.open(args.parameter_file, windows=args.windows)
-    par, work, device, win_id = r5.par, r5.work, r5.device, r5.win_id
+    par, work, win_id = r5.par, r5.work, r5.win_id
     grid = grid_from_args(ap, args, par)
     structure = args.structure if args.structure else work
     if args.draws is None:
@@ -744,70 +755,34 @@ def main(argv=None):
     if not win_id:
         raise SystemExit("ERROR: no window to locate")
 
-    n_unresolved = None
-    resid = None      # with --residuals: its result and the windows' standard deviations
+    res, ev, resid, n_unresolved = _evaluate(r5, args, win_id, grid, evaluate, (t_corr, vs, a_corr, qs), n_bins)
 
-    def run(ids, volume, weights=False, stacked=False, with_residuals=False):
-        nonlocal n_unresolved, resid
-        obs = ObsData(ids, par.n_stations, par.sta_x, par.sta_y, directory=work)
-        fwd = Forward(par.n_stations, len(ids), par.sta_x, par.sta_y, par.sta_z, obs, use_amp=par.get_use_amp(), use_time=par.get_use_time(),
-                      device=device)
-        try:
-            fwd.set_locate_precision(args.precision)
-            prior = None if args.flat_prior else step5_prior(par, obs)
-            if stacked:
-                # one evaluation gives the maps and what the .stat and .best.dat files are written from; --stack-resolved needs
-                # the best cells before it, from an evaluation of their own
-                layer = time_layers(ids, n_bins)
-                if args.stack_resolved:
-                    first = evaluate(fwd, t_corr, vs, a_corr, qs, grid, prior=prior, marginals=False)
-                    layer = resolved_layer(layer, first["index"], grid)
-                    n_unresolved = int((layer < 0).sum())
-                res = stack(fwd, t_corr, vs, a_corr, qs, grid, prior=prior, layer=layer, n_layer=n_bins, volume=True)
-                if with_residuals:      # a second evaluation: the stack's call keeps no residuals
-                    resid = (residuals(fwd, t_corr, vs, a_corr, qs, grid, prior=prior), obs.t_stdv, obs.a_stdv)
-            elif with_residuals:        # the one evaluation serves .stat and .best.dat too
-                res = residuals(fwd, t_corr, vs, a_corr, qs, grid, prior=prior)
-                resid = (res, obs.t_stdv, obs.a_stdv)
-            else:
-                res = evaluate(fwd, t_corr, vs, a_corr, qs, grid, prior=prior, volume=volume)
-            return (res, draw_evidence(fwd, t_corr, vs, a_corr, qs, grid, prior=prior)) if weights else res
-        finally:
-            fwd.close()
+    def write(name, text):
+        with open(os.path.join(work, stem + name), "w") as fh:
+            fh.write(text)
 
-    res, ev = run(win_id, False, True, args.stack) if args.draw_weights else (run(win_id, False, stacked=args.stack, with_residuals=args.residuals), None)
-    marg = np.concatenate([res["marg_x"], res["marg_y"], res["marg_z"]], axis=1)
-    with open(os.path.join(work, stem + ".stat"), "w") as fh:
-        fh.write(stat_text(win_id, marginal_quantiles(marg, grid)))
-    with open(os.path.join(work, stem + ".best.dat"), "w") as fh:
-        fh.write(best_text(win_id, res, grid))
+    write(".stat", stat_text(win_id, marginal_quantiles(np.concatenate([res["marg_x"], res["marg_y"], res["marg_z"]], axis=1), grid)))
+    write(".best.dat", best_text(win_id, res, grid))
     if args.volume_of is not None:
         if args.volume_of not in win_id:
             raise SystemExit(f"ERROR: --volume-of {args.volume_of} is not among the windows")
-        one = run([args.volume_of], True)
-        with open(os.path.join(work, stem + ".%d.vol.dat" % args.volume_of), "w") as fh:
-            fh.write(volume_text(one["vol"][0], grid))
+        write(".%d.vol.dat" % args.volume_of, volume_text(_volume_of(r5, args, grid, evaluate, (t_corr, vs, a_corr, qs)), grid))
     sys.stdout.write(summary_text(res, grid, args.draws, args.precision))
     if args.stack:
         for nm in MAPS:
             if nm != "vol" or args.stack_volume:
-                with open(os.path.join(work, stem + ".density.%s.dat" % nm), "w") as fh:
-                    fh.write(stack_map_text(nm, res["stack" if nm == "vol" else nm], grid, levels))
+                write(".density.%s.dat" % nm, stack_map_text(nm, res["stack" if nm == "vol" else nm], grid, levels))
         sys.stdout.write(stack_summary_text(res["tally"], face_share(res["stack"]), n_unresolved))
     if resid is not None:
         rr, t_stdv, a_stdv = resid
         use = (bool(par.get_use_time()), bool(par.get_use_amp()))
-        for name, text in (("residuals", residuals_text(win_id, par.stations, rr["res"], t_stdv, a_stdv, use)),
-                           ("fit", fit_text(win_id, rr["fit"], t_stdv, use)),
-                           ("stations", stations_text(win_id, par.stations, rr["res"], t_stdv, a_stdv, use))):
-            with open(os.path.join(work, stem + "." + name + ".dat"), "w") as fh:
-                fh.write(text)
+        write(".residuals.dat", residuals_text(win_id, par.stations, rr["res"], t_stdv, a_stdv, use))
+        write(".fit.dat", fit_text(win_id, rr["fit"], t_stdv, use))
+        write(".stations.dat", stations_text(win_id, par.stations, rr["res"], t_stdv, a_stdv, use))
         sys.stdout.write(stations_summary_text(win_id, par.stations, rr["res"], t_stdv, a_stdv, use))
     if ev is not None:
-        with open(os.path.join(work, stem + ".draws.dat"), "w") as fh:
-            fh.write(draws_text(win_id, ev, records))
-        with open(os.path.join(work, stem + ".structure.dat"), "w") as fh:
-            fh.write(structure_text(records, vs, qs, ev["log_z"]))
+        write(".draws.dat", draws_text(win_id, ev, records))
+        write(".structure.dat", structure_text(records, vs, qs, ev["log_z"]))
         sys.stdout.write(draws_summary_text(ev, args.draws))
 
 
