@@ -61,7 +61,7 @@ class LaunchPlan(C.Structure):
 
 
 class LocateRequest(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("n_sta", "n_events", "job", "n_draws", "volume", "prior", "n_layer", "layer", "forward_fp32", "residuals")]
+    _fields_ = [(n, C.c_int32) for n in ("n_sta", "n_events", "job", "n_draws", "volume", "prior", "n_layer", "layer", "forward_fp32", "residuals", "boxes")]
 
 
 class LocatePlan(C.Structure):
@@ -70,8 +70,9 @@ class LocatePlan(C.Structure):
     PER_CALL = ("dtc", "dac", "rk", "corr", "vq", "stack", "xy", "xz", "yz", "tally", "layer")      # len_*: elements once per call
     BYTES = ("per_event_bytes", "table_bytes", "fixed_bytes")
     RESIDUALS = ("rbase", "rpart", "res", "fit")      # len_*: elements per event of a batch, of a request with residuals
+    BOXES = ("org",)                                  # len_*: elements per event of a batch, of a request with boxes
     _fields_ = ([(n, C.c_int64) for n in INTS] + [("len_" + n, C.c_int64) for n in PER_EVENT + PER_CALL] + [(n, C.c_double) for n in BYTES] +
-                [("nb_limit", C.c_int64 * 4), ("nb", C.c_int64)] + [("len_" + n, C.c_int64) for n in RESIDUALS])
+                [("nb_limit", C.c_int64 * 4), ("nb", C.c_int64)] + [("len_" + n, C.c_int64) for n in RESIDUALS + BOXES])
 
 
 # every symbol include/htm_hip.h declares: name -> (restype, argtypes)
@@ -102,6 +103,7 @@ SIGNATURES = {
     "htm_forward_locate_draw_evidence": (C.c_int, [vp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp]),
     "htm_forward_locate_set_precision": (C.c_int, [vp, C.c_int]),
     "htm_forward_locate_stack": (C.c_int, [vp, C.c_int, dp, dp, dp, dp, dp, dp, ip, C.c_int, dp, dp, dp, dp, dp, dp, dp]),
+    "htm_forward_locate_boxes": (C.c_int, [vp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp]),
     "htm_forward_locate_plan": (C.c_int, [C.POINTER(LocateRequest), dp, C.POINTER(LocatePlan)]),
     "htm_chains_create": (C.c_int, [vp, C.POINTER(ChainsInit), C.POINTER(vp)]),
     "htm_chains_destroy": (C.c_int, [vp]),

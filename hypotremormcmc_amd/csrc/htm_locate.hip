@@ -1,6 +1,6 @@
 // htm_locate.hip -- the locate part of the C ABI (include/htm_hip.h): the location posterior of every event of a forward handle
 // on a grid, under a fixed structure or marginalised over draws of it, the draws' evidences, the stacked density and the stations'
-// residuals, over the
+// residuals, and the same posterior on a box of its own per event, over the
 // kernels of htm_locate.hpp -- the one unit that includes them.  What a call allocates and how it is batched is the plan of
 // htm_locate_plan.hpp, which htm_forward_locate_plan gives out without a device; this unit runs it.  The handle itself
 // (htm_forward, with d_lconst_t, d_lconst_a and loc_fp32 for these entry points) is htm_forward.hip's.
@@ -19,6 +19,7 @@ struct LocCall {
     LocRequest rq;
     const double *t_corr, *vs, *a_corr, *qs;      // one structure (t_corr, a_corr [S]; *vs, *qs) or rq.n_draws of them ([n_draws][S]; [n_draws])
     const double *grid9, *prior5;
+    const double *origin3;                        // [E][3] where rq.boxes: every event's box origin
     const int *layer;                             // [E] where rq.layer
     double *loc, *marg, *vol;                     // kLocFixed, kLocMarginal
     double *log_z, *summary;                      // kLocEvidence
@@ -35,6 +36,7 @@ struct LocWork {
     double *stack = nullptr, *xy = nullptr, *xz = nullptr, *yz = nullptr, *tally = nullptr;
     int *layer = nullptr;
     double *rbase = nullptr, *rpart = nullptr, *res = nullptr, *fit = nullptr;
+    double *org = nullptr;
 
     template <class T>
     int take(T **p, size_t n) { return n ? pool.alloc(p, n) : HTM_OK; }
@@ -78,6 +80,7 @@ struct LocRun {
     LocJob jb{};
     LocDraws<loc_real<F32>> dr{};
     std::vector<double> tab;      // a batch's prior tables
+    std::vector<double> org;      // a batch's box origins, [m][4]
 
     LocRun(htm_forward *h_, const LocCall &c_) : h(h_), c(c_) {}
 
@@ -104,14 +107,14 @@ struct LocRun {
             (rc = w.take(&w.sum, nb * n.sum)) || (rc = w.take(&w.loc, nb * n.loc)) || (rc = w.take(&w.marg, nb * n.marg)) || (rc = w.take(&w.prior, nb * n.prior)) ||
             (rc = w.take(&w.vol, nb * n.vol)) || (rc = w.take(&w.w, nb * n.w)) || (rc = w.take(&w.stack, n.stack)) || (rc = w.take(&w.xy, n.xy)) ||
             (rc = w.take(&w.xz, n.xz)) || (rc = w.take(&w.yz, n.yz)) || (rc = w.take(&w.tally, n.tally)) || (rc = w.take(&w.rbase, nb * n.rbase)) ||
-            (rc = w.take(&w.rpart, nb * n.rpart)) || (rc = w.take(&w.res, nb * n.res)) || (rc = w.take(&w.fit, nb * n.fit)))
+            (rc = w.take(&w.rpart, nb * n.rpart)) || (rc = w.take(&w.res, nb * n.res)) || (rc = w.take(&w.fit, nb * n.fit)) || (rc = w.take(&w.org, nb * n.org)))
             return rc;
         if (n.layer && (rc = w.pool.upload(&w.layer, c.layer, n.layer))) return rc;
         if (n.stack) {
             HIPCHK(hipMemsetAsync(w.stack, 0, n.stack * sizeof(double), h->stream));
             HIPCHK(hipMemsetAsync(w.tally, 0, n.tally * sizeof(double), h->stream));
         }
-        jb.sta = w.sta; jb.ev = w.ev; jb.prior = w.prior; jb.part = w.part; jb.vol = w.vol; jb.S = c.rq.n_sta;
+        jb.sta = w.sta; jb.ev = w.ev; jb.prior = w.prior; jb.part = w.part; jb.vol = w.vol; jb.org = w.org; jb.S = c.rq.n_sta;
         return HTM_OK;
     }
 
@@ -142,7 +145,15 @@ struct LocRun {
         return HTM_OK;
     }
 
-    // events e0 .. e0 + m - 1: the prior's tables, pack, evaluate, combine, stack, download
+    // the grid of event e: the call's, with the event's own origin where the call has boxes (what loc_grid_of does on the device)
+    MapGrid grid_of(long e) const
+    {
+        MapGrid ge = pl.g;
+        if (c.rq.boxes) { ge.x0 = c.origin3[3 * e]; ge.y0 = c.origin3[3 * e + 1]; ge.z0 = c.origin3[3 * e + 2]; }
+        return ge;
+    }
+
+    // events e0 .. e0 + m - 1: the boxes' origins, the prior's tables, pack, evaluate, combine, stack, download
     int batch(long e0, long m)
     {
         const LocGrid &g = pl.g;
@@ -151,9 +162,15 @@ struct LocRun {
         const double log_cell = std::log(g.dx * g.dy * g.dz);
         const int mode = (h->dev.use_time ? 1 : 0) | (h->dev.use_amp ? 2 : 0);
         int rc;
+        if (c.rq.boxes) {       // (the origins travel with the batch: event e0 + b is row b)
+            org.assign((size_t)m * 4, 0.0);
+            for (long b = 0; b < m; ++b)
+                for (int a = 0; a < 3; ++a) org[(size_t)b * 4 + a] = c.origin3[3 * (e0 + b) + a];
+            HIPCHK(hipMemcpy(w.org, org.data(), org.size() * sizeof(double), hipMemcpyHostToDevice));
+        }
         if (c.rq.prior) {
             tab.resize((size_t)m * nm);
-            for (long b = 0; b < m; ++b) locate_prior_tables(c.prior5 + 5 * (e0 + b), g, tab.data() + (size_t)b * nm);
+            for (long b = 0; b < m; ++b) locate_prior_tables(c.prior5 + 5 * (e0 + b), grid_of(e0 + b), tab.data() + (size_t)b * nm);
             HIPCHK(hipMemcpy(w.prior, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
         }
         hipLaunchKernelGGL(k_locate_pack, dim3((unsigned)((m * S + 255) / 256)), dim3(256), 0, h->stream, h->dev, (int)e0, (int)m, h->d_tc, h->d_ac,
@@ -168,7 +185,7 @@ struct LocRun {
         if (job == kLocEvidence)
             hipLaunchKernelGGL(k_locate_draw_combine, dim3((unsigned)m), dim3(256), 0, h->stream, (int)n_tiles, K, Kpad, w.part, log_cell, w.logz, w.sum);
         else
-            hipLaunchKernelGGL(k_locate_combine, dim3((unsigned)m), dim3(256), 0, h->stream, g, w.part, log_cell, w.loc, w.marg, w.w);
+            hipLaunchKernelGGL(k_locate_combine, dim3((unsigned)m), dim3(256), 0, h->stream, g, w.part, log_cell, w.loc, w.marg, w.w, w.org);
         if (c.rq.n_layer)
             hipLaunchKernelGGL(k_locate_stack, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->stream, cells, (int)m, (int)e0, w.vol, w.loc, w.w, w.layer,
                                c.rq.n_layer, w.stack, w.tally);
@@ -294,7 +311,10 @@ int htm_forward_locate_plan(const htm_locate_request *request, const double *gri
     if (r.job == kLocEvidence && (r.volume || r.n_layer)) return fail(HTM_EINVAL, "the draws' evidences come without a volume and without a stack");
     if (r.residuals && (r.job != kLocFixed || r.volume || r.n_layer))
         return fail(HTM_EINVAL, "the residuals come under a fixed structure, without a volume and without a stack");
-    const LocRequest rq{r.n_sta, r.n_events, r.job, r.n_draws, r.volume != 0, r.prior != 0, r.n_layer, r.layer != 0, r.forward_fp32 != 0, r.residuals != 0};
+    if (r.boxes && (r.job == kLocEvidence || r.n_layer || r.residuals))
+        return fail(HTM_EINVAL, "a box per event comes under a fixed structure or its mixture over draws, without a stack and without residuals");
+    const LocRequest rq{r.n_sta, r.n_events, r.job, r.n_draws, r.volume != 0, r.prior != 0, r.n_layer, r.layer != 0, r.forward_fp32 != 0, r.residuals != 0,
+                        r.boxes != 0};
     LocPlan p;
     if (int rc = locate_tiles(grid9, &p)) return rc;
     double mb;
@@ -311,7 +331,7 @@ int htm_forward_locate_plan(const htm_locate_request *request, const double *gri
     plan->per_event_bytes = p.per_event; plan->table_bytes = p.table; plan->fixed_bytes = p.fixed;
     for (int i = 0; i < kLocLimits; ++i) plan->nb_limit[i] = p.limit[i];
     plan->nb = p.nb;
-    LEN(rbase) LEN(rpart) LEN(res) LEN(fit)
+    LEN(rbase) LEN(rpart) LEN(res) LEN(fit) LEN(org)
 #undef LEN
     return HTM_OK;
 }
@@ -370,6 +390,27 @@ int htm_forward_locate_draw_evidence(htm_forward *h, int n_draws, const double *
     c.t_corr = t_corr; c.vs = vs; c.a_corr = a_corr; c.qs = qs;
     c.grid9 = grid9; c.prior5 = prior5; c.rq.prior = prior5 != nullptr;
     c.log_z = log_z; c.summary = summary;
+    return locate_run(h, c);
+}
+
+// A box of its own per event (include/htm_hip.h): n_draws = 0 htm_forward_locate's structure (*vs, *qs), n_draws >= 1
+// htm_forward_locate_marginal's, event e on grid9's cells from origin3[e]
+int htm_forward_locate_boxes(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr, const double *qs,
+                             const double *grid9, const double *origin3, const double *prior5, double *loc, double *marg, double *vol)
+{
+    if (!h) return fail(HTM_EINVAL, "NULL handle");
+    if (!t_corr || !vs || !a_corr || !qs || !grid9 || !loc) return fail(HTM_EINVAL, "NULL argument");
+    if (int rc = n_draws == 0 ? locate_structure_ok(*vs, *qs) : locate_draws_ok(n_draws, vs, qs)) return rc;
+    if (!origin3) return fail(HTM_EINVAL, "NULL origin3: a box per event needs every event's origin");
+    for (int e = 0; e < h->E; ++e)
+        for (int a = 0; a < 3; ++a)
+            if (!std::isfinite(origin3[3 * (size_t)e + a]))
+                return fail(HTM_EINVAL, "event %d: box origin %c = %g: need a finite value", e, "xyz"[a], origin3[3 * (size_t)e + a]);
+    LocCall c = locate_call(h, n_draws == 0 ? kLocFixed : kLocMarginal, n_draws);
+    c.t_corr = t_corr; c.vs = vs; c.a_corr = a_corr; c.qs = qs;
+    c.grid9 = grid9; c.prior5 = prior5; c.rq.prior = prior5 != nullptr;
+    c.origin3 = origin3; c.rq.boxes = true;
+    c.loc = loc; c.marg = marg; c.vol = vol; c.rq.volume = vol != nullptr;
     return locate_run(h, c);
 }
 

@@ -31,6 +31,12 @@
 // No floating-point atomics anywhere: the bits do not depend on timing.  The volume of log posteriors is written only when it
 // is asked for, stacked, or read by the residual pass.
 //
+// A BOX PER EVENT (htm_forward_locate_boxes): k_locate, k_locate_marginal and k_locate_combine evaluate event b of
+// the batch on the launch's grid with the origin org[b] in the place of the grid's (loc_grid_of, called at their top; a null
+// `org` is the one grid for all).  Cell sizes, counts, tiles, the partial records and every reduction order stay the launch's:
+// nothing after "which grid is this event on" changes, so an event's bits are those of a launch on its own grid.  The other
+// kernels take no boxes.
+//
 // Every one of the three evaluation kernels exists twice: F32 = false, all arithmetic fp64, and F32 = true, the single-precision
 // forward of htm_forward_locate_set_precision (the rule: loc_station).  The float copies of the structure are
 // made ONCE, where the records are packed: the station's corrections in LocSta's last slot (k_locate_pack), 1 / vs and
@@ -78,6 +84,7 @@ struct LocJob {
     const double *prior;    // [nb][nx + ny + nz] log prior per ix, iy, iz, or nullptr: flat
     double *part;           // [nb][nz * tpl][stride]
     double *vol;            // [nb][nz][ny][nx] or nullptr
+    const double *org;      // [nb][4] every event's box origin x0, y0, z0 and one unused, or nullptr: the grid's (loc_grid_of)
     int S;
     double rbeta, katt;     // 1 / vs, pi f / (qs vs)
     float rbeta32, katt32;  // the same, rounded to float
@@ -105,6 +112,21 @@ __device__ __forceinline__ LocEv loc_ld_ev(const LocEv *p)
     const CP q = (CP)(unsigned long long)p;
     const loc_f64x2 a = q[0], b = q[1];
     return LocEv{a[0], a[1], b[0], b[1]};
+}
+
+// The grid of event b of the batch: the launch's, with the event's own origin where the call has a box per event (org [nb][4] =
+// x0, y0, z0 and one unused; nullptr: the launch's grid as it is).  b is block-uniform, so the two pairs come through scalar
+// loads, as loc_ld_ev's.  The host's copy writes the array before the launch and no kernel does.
+__device__ __forceinline__ LocGrid loc_grid_of(const LocGrid &g, const double *org, int b)
+{
+    LocGrid ge = g;
+    if (org) {      // (uniform)
+        typedef const loc_f64x2 __attribute__((address_space(4))) *CP;
+        const CP q = (CP)(unsigned long long)(org + 4 * (size_t)b);
+        const loc_f64x2 xy = q[0], z = q[1];
+        ge.x0 = xy[0]; ge.y0 = xy[1]; ge.z0 = z[0];
+    }
+    return ge;
 }
 
 __device__ __forceinline__ bool loc_included(double lp) { return lp == lp && lp != -__builtin_inf(); }
@@ -391,9 +413,10 @@ __device__ __forceinline__ double loc_term(const LocSums<D> &sm, const LocEv &ev
 }
 
 template <int MODE, bool F32>
-__global__ __launch_bounds__(256) void k_locate(LocGrid g, LocJob jb)
+__global__ __launch_bounds__(256) void k_locate(LocGrid launch, LocJob jb)
 {
     typedef loc_real<F32> T;
+    const LocGrid g = loc_grid_of(launch, jb.org, blockIdx.y);
     constexpr int CHUNK = F32 ? kLocChunk32 : kLocChunk;
     __shared__ double s_w[kLocTile];
     const int t = threadIdx.x;
@@ -470,9 +493,10 @@ __global__ __launch_bounds__(256) void k_locate_pack_draws(int S, int K, int Kpa
 }
 
 template <int MODE, bool F32>
-__global__ __launch_bounds__(256) void k_locate_marginal(LocGrid g, LocJob jb, LocDraws<loc_real<F32>> dr)
+__global__ __launch_bounds__(256) void k_locate_marginal(LocGrid launch, LocJob jb, LocDraws<loc_real<F32>> dr)
 {
     typedef loc_real<F32> T;
+    const LocGrid g = loc_grid_of(launch, jb.org, blockIdx.y);
     constexpr int C = F32 ? kLocmCells32 : kLocmCells, D = kLocDraws;
     __shared__ double s_w[kLocTile];
     const int t = threadIdx.x;
@@ -700,8 +724,11 @@ __global__ __launch_bounds__(256) void k_locate_draw_combine(int n_tiles, int K,
 // One workgroup of 256 threads per event of the batch.  loc [nb][16], marg [nb][nx + ny + nz] (always there: the moments are
 // taken from the marginals).
 // wsum [nb] or nullptr: the event's weight sum W (0 for an event without an included cell), for k_locate_stack.
-__global__ __launch_bounds__(256) void k_locate_combine(LocGrid g, double *part, double log_cell, double *loc, double *marg, double *wsum)
+// org [nb][4] or nullptr: the events' box origins, as LocJob's.
+__global__ __launch_bounds__(256) void k_locate_combine(LocGrid launch, double *part, double log_cell, double *loc, double *marg, double *wsum,
+                                                        const double *org)
 {
+    const LocGrid g = loc_grid_of(launch, org, blockIdx.x);
     __shared__ double s_red4[4];
     __shared__ double s_blp[4], s_bell[4], s_bidx[4];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6, b = blockIdx.x;

@@ -72,6 +72,7 @@ struct LocRequest {
     bool layer;         // the stack has a layer per window
     bool fp32;          // the single-precision forward: the draws' table holds pairs of floats
     bool residuals;     // htm_forward_locate_residuals: the stations' residuals and the fit (kLocFixed only, without a stack)
+    bool boxes;         // htm_forward_locate_boxes: a box origin per event (kLocFixed and kLocMarginal, without a stack or residuals)
 };
 
 // ---- what the run needs -------------------------------------------------------------------------------------------
@@ -84,6 +85,7 @@ struct LocLengths {
     size_t logz, sum;                // the draws' evidences and their summary
     size_t loc, marg, prior, vol;
     size_t w;                        // the event's weight sum, for the stack
+    size_t org;                      // the event's box origin x0, y0, z0 and one unused: two aligned pairs of doubles; boxes only
     // once per call
     size_t dtc, dac, rk;             // the draws as they come, and their 1 / vs and pi f / (qs vs): the pack kernel's input
     size_t corr, vq;                 // the draws' table, pairs
@@ -145,6 +147,7 @@ inline int locate_budget(const LocRequest &rq, double mb, LocPlan *p)
     if (rq.prior) n.prior = nm;
     if (rq.volume || stk || rq.residuals) n.vol = cells;
     if (stk || rq.residuals) n.w = 1;
+    if (rq.boxes) n.org = 4;
     if (rq.residuals) {
         n.rbase = 2 * S + kLocResBase; n.rpart = (size_t)p->n_rblk * (2 * S + kLocResEv);
         n.res = 4 * S; n.fit = 10;
@@ -152,8 +155,9 @@ inline int locate_budget(const LocRequest &rq, double mb, LocPlan *p)
     if (draws) { n.dtc = n.dac = (size_t)K * S; n.rk = 2 * (size_t)K; n.corr = S * Kpad; n.vq = (size_t)Kpad; }
 
     // (the prior's tables are counted whether or not the call has a prior: a flat-prior call is planned as if it allocated them.
-    // Every other term is an array of the call: the stack's + 1 of include/htm_hip.h is w, which a stacked call allocates)
-    p->per_event = sizeof(double) * (double)(n.part + n.logz + n.sum + n.loc + n.marg + nm + n.vol + n.w + n.rbase + n.rpart + n.res + n.fit) +
+    // Every other term is an array of the call: the stack's + 1 of include/htm_hip.h is w, which a stacked call allocates; with
+    // boxes, + 8 * 4 bytes: the event's origin)
+    p->per_event = sizeof(double) * (double)(n.part + n.logz + n.sum + n.loc + n.marg + nm + n.vol + n.w + n.org + n.rbase + n.rpart + n.res + n.fit) +
                    sizeof(LocSta) * (double)n.sta +
                    sizeof(LocEv) * (double)n.ev;
     // the draws' table and the draws as they come are part of the workspace, once per call

@@ -6,7 +6,7 @@ grid -- no MCMC, any number of windows (kernels in hypotremorm
                                         [--windows FILE] [--flat-prior] [--volume-of WIN] [--draws K [--draw-weights]]
                                         [--precision fp64|fp32]
                                         [--stack [--time-bins N] [--stack-volume] [--stack-resolved] [--level 0.68 0.95]]
-                                        [--residuals]
+                                        [--residuals] [--refine F [--refine-radius R]]
 
 run in the data directory (station file, opt_data.NNNNNN.dat).  --structure DIR holds `uniform_structure.stat` and
 `station_corrections.stat` of the calibration run (default: the parameter file's directory); --windows FILE lists the window
@@ -62,6 +62,23 @@ It writes `hypo_grid.residuals.dat` (one line per window and station), `hypo_gri
 windows?), and one summary line that names the station with the largest mean residual.  Without --stack the one evaluation
 serves `hypo_grid.stat` and `hypo_grid.best.dat` too; with --stack it is a second one.  It takes a fixed structure: with
 --draws it is an argument error.  Without --residuals nothing is written or printed that was not before.
+
+--refine F gives the resolution of a grid F times as fine where it matters, for a few thousand cells per window (DESIGN.md
+§3.16; `refine`, htm_forward_locate_boxes): after the evaluation that the invocation makes anyway, on the same Forward, every
+window is evaluated again on a box of its own about that evaluation's best cell -- 2 R + 1 coarse cells per axis (R:
+--refine-radius, default 2), snapped to the coarse cells' edges, shifted inwards where it would cross the outer box, in cells
+of 1 / F of the coarse size (refine_boxes) -- with the same structure or draws, prior and precision, in one launch per batch.
+It writes `<stem>.refined.stat` (hypo.stat's layout, from the fine marginals: the intervals are CONDITIONAL ON THE BOX, and
+the header says so) and `<stem>.refined.best.dat` (best.dat's columns on the fine grid, then the box's lower corner, a lower
+bound of the coarse posterior's mass inside the box from the coarse marginals (box_mass_bound), 1 when the best fine cell lies
+on a face of its box that is no face of the outer box -- the box is too small: raise the radius --, and 1 when it lies on a
+face of the outer box), and one more summary line: the box in coarse and in fine cells, the windows with a best cell on an
+inner face, and the windows whose mass bound is below 0.99.  A window without an included coarse cell is not refined: NaN.
+Why R = 2: on noise-free data with truths at fine cell centres (6 windows x 40 seeds, 10 x 10 x 5 coarse cells, F = 4) R = 1
+left 32 of 240 refined best cells off the truth -- in all 32 the best COARSE cell lay two or more cells from the truth; all 32
+were flagged on an inner face, and 7 exact windows were flagged too -- and R = 2 none, with no flag.  The products of --stack,
+--residuals, --draw-weights and --volume-of remain the coarse grid's.  --refine-radius without --refine is an argument error.
+Without --refine nothing is written or printed that was not before.
 """
 from __future__ import annotations
 
@@ -91,6 +108,12 @@ FIT_HEADER = ("# window ID, stations with data, then per data type in use (time,
 STATIONS_HEADER = ("# station, windows with data, then per data type in use (time, amplitude): precision-weighted mean over those windows of the "
                    "posterior-mean residual, its standard error, its weighted rms, largest |best-cell residual / standard deviation| and its window ID")
 FIT_NAMES = tuple(f"{q}_{d}{s}" for d in "ta" for q, s in (("m", "_best"), ("m", "_mean"), ("m", "_sd"), ("chi2", "_best"), ("chi2", "_mean")))
+REFINED_STAT_HEADER = ("# refined: every window on a box of its own about its best cell of the coarse grid; the intervals are conditional "
+                       "on that box (its lower corner and a bound of the coarse posterior's mass inside it: the .refined.best.dat file)")
+REFINED_BEST_TAIL = (" (here: of the window's own box, in fine cells), the box's lower corner x y z, lower bound of the coarse posterior's mass "
+                     "inside the box, 1: the best cell lies on a face of its box that is no face of the outer box (the box is too small), "
+                     "1: it lies on a face of the outer box")
+MASS_BOUND_LOW = 0.99       # the summary counts the windows whose box may hold less than this of the coarse posterior's mass
 BEST_HEADER = ("# window ID, best cell's centre x y z, log posterior there, log-likelihood term there, log evidence, "
                "posterior mean x y z, 1: the best cell lies on a face of the box")
 
@@ -109,6 +132,11 @@ def _corrections(t_corr, vs, a_corr, qs, S, draws):
         raise ValueError(f"{K} draws of vs: need as many of qs (got {q.size}) and one t_corr and a_corr per draw and station "
                          f"({K} x {S}; got {tc.size} and {ac.size} values)")
     return K, tc, v, ac, q
+
+
+def _has_draws(t_corr, vs):
+    """whether a structure is draws of it, a 1-D vs or a 2-D t_corr"""
+    return np.ndim(vs) >= 1 or np.ndim(t_corr) == 2
 
 
 class _Call:
@@ -130,11 +158,11 @@ class _Call:
         self.marg = np.empty((E, nx + ny + nz)) if marginals else None
         self.vol = np.empty((E, nz, ny, nx)) if volume else None
 
-    def run(self, entry, precision, *outputs, scalars=False):
+    def run(self, entry, precision, *outputs, scalars=False, origins=None):
         """the library's `entry` on the Forward: the structure (`scalars`: vs and qs by value and no K, as the entry points of a
-        fixed structure take it), the grid, the prior, then `outputs` (float64 arrays or None by their pointers, anything else as
-        it is).  precision: None, the Forward's locate precision as it is; "fp32" or "fp64": that one for this call, and the
-        previous setting back after it"""
+        fixed structure take it), the grid, `origins` behind it where the entry point takes a box per event, the prior, then
+        `outputs` (float64 arrays or None by their pointers, anything else as it is).  precision: None, the Forward's locate
+        precision as it is; "fp32" or "fp64": that one for this call, and the previous setting back after it"""
         p = _lib.ptr
         head = (p(self.tc), float(self.vs[0]), p(self.ac), float(self.qs[0])) if scalars else (self.K, p(self.tc), p(self.vs), p(self.ac), p(self.qs))
         tail = [p(a) if a is None or isinstance(a, np.ndarray) else a for a in outputs]
@@ -142,7 +170,8 @@ class _Call:
             before = self.fwd.locate_precision
             self.fwd.set_locate_precision(precision)
         try:
-            _lib.check(getattr(_lib.load(), entry)(self.fwd.handle, *head, p(self.g), p(self.prior), *tail))
+            boxes = [] if origins is None else [p(origins)]
+            _lib.check(getattr(_lib.load(), entry)(self.fwd.handle, *head, p(self.g), *boxes, p(self.prior), *tail))
         finally:
             if precision is not None:
                 self.fwd.set_locate_precision(before)
@@ -203,7 +232,7 @@ def stack(fwd, t_corr, vs, a_corr, qs, grid, prior=None, layer=None, n_layer=1, 
     window in layer 0); a window whose layer is outside 0 .. n_layer - 1 takes no part.  Returns the dict of `locate` (its
     very bits; vol None) plus xy [n_layer][ny][nx], xz [n_layer][nz][nx], yz [n_layer][nz][ny], tally [n_layer][2] = windows
     stacked, windows without an included cell, and stack [n_layer][nz][ny][nx] (None without `volume`)."""
-    c = _Call(fwd, t_corr, vs, a_corr, qs, grid, prior, np.ndim(vs) >= 1 or np.ndim(t_corr) == 2)
+    c = _Call(fwd, t_corr, vs, a_corr, qs, grid, prior, _has_draws(t_corr, vs))
     nx, ny, nz, E = c.nx, c.ny, c.nz, fwd.n_events
     n_layer = int(n_layer)
     if n_layer < 1:
@@ -241,14 +270,121 @@ def residuals(fwd, t_corr, vs, a_corr, qs, grid, prior=None, precision=None):
     return out
 
 
+def locate_boxes(fwd, t_corr, vs, a_corr, qs, grid, origins, prior=None, marginals=True, volume=False, precision=None):
+    """`locate` -- or, with t_corr [K][n_sta] and vs [K] (a 2-D t_corr or a 1-D vs), `locate_marginal` -- with a box of its own
+    per event (htm_forward_locate_boxes): origins [E][3], absolute; event e is evaluated on the grid
+    origins[e][0], dx, nx, origins[e][1], dy, ny, origins[e][2], dz, nz, the cell sizes and counts `grid`'s, whose own three
+    origins are checked and otherwise not read.  One launch serves the batch.  Row e of every result is bit for bit what
+    `locate` / `locate_marginal` returns in row e with that event's grid: `index` is the cell within the event's box, `best` and
+    `mean` are absolute coordinates.  Returns the dict of `locate` plus origin [E][3]."""
+    c = _Call(fwd, t_corr, vs, a_corr, qs, grid, prior, _has_draws(t_corr, vs), marginals, volume)
+    org = np.ascontiguousarray(origins, dtype=np.float64)
+    if org.shape != (fwd.n_events, 3):
+        raise ValueError(f"origins is {org.shape}: need x0, y0, z0 of every event ({fwd.n_events})")
+    c.run("htm_forward_locate_boxes", precision, c.loc, c.marg, c.vol, origins=org)
+    return dict(c.result(), origin=org)
+
+
+def _cell_ijk(index, counts):
+    """(ix, iy, iz) [E][3] of the linear indices ix + nx (iy + ny iz); a window without a cell (-1) gives cell 0"""
+    idx = np.asarray(index, dtype=np.int64).reshape(-1)
+    idx = np.where(idx < 0, 0, idx)
+    nx, ny, _ = counts
+    return np.stack([idx % nx, (idx // nx) % ny, idx // (nx * ny)], axis=1)
+
+
+def refine_boxes(index, grid, factor, radius):
+    """The refinement policy, stated once: every window's fine box about its best coarse cell `index` [E] of `grid`.  Per axis a
+    with n_a coarse cells of size dv_a from v0_a, b_a the best cell's index on it, R = radius, F = factor: the box is
+    w_a = min(2 R + 1, n_a) coarse cells wide and begins at the coarse cell i0_a = clamp(b_a - R, 0, n_a - w_a) -- snapped to
+    the coarse cells' edges, and where it would cross the outer box shifted inwards, not cut --, its origin is
+    v0_a + i0_a * dv_a (one multiplication, then one addition), its cells are dv_a / F wide and w_a F of them: every window has
+    the same fine counts, so one grid and one launch serve a batch.  A window without an included coarse cell (index -1) gets
+    i0 = 0 and is marked.  Returns a dict: fine_grid (grid9, the coarse grid's origins in the three slots that
+    `locate_boxes` does not read), origins [E][3], i0 [E][3] (int64), widths (w_x, w_y, w_z), none [E] (bool)."""
+    g, F, R = grid9(grid), int(factor), int(radius)
+    if F != factor or R != radius or F < 1 or R < 0:
+        raise ValueError(f"factor {factor}, radius {radius}: need integers, factor >= 1 and radius >= 0")
+    n = grid_counts(g)
+    none = np.asarray(index, dtype=np.int64).reshape(-1) < 0
+    b = _cell_ijk(index, n)
+    widths = tuple(min(2 * R + 1, n[a]) for a in range(3))
+    i0 = np.stack([np.clip(b[:, a] - R, 0, n[a] - widths[a]) for a in range(3)], axis=1)
+    i0[none] = 0
+    origins = np.stack([g[3 * a] + i0[:, a].astype(np.float64) * g[3 * a + 1] for a in range(3)], axis=1)
+    fine = np.array([v for a in range(3) for v in (g[3 * a], g[3 * a + 1] / F, float(widths[a] * F))])
+    return {"fine_grid": fine, "origins": origins, "i0": i0, "widths": widths, "none": none}
+
+
+def box_mass_bound(marg_x, marg_y, marg_z, i0, widths):
+    """[E]: a lower bound of the coarse posterior's mass inside every window's box, from what the coarse pass already returns.
+    With m_a the coarse axis marginal's mass in the box's cells i0_a .. i0_a + w_a - 1 on axis a, the mass outside the box is
+    at most sum_a (1 - m_a) (a cell outside it is outside on one axis at the least), so the mass inside is at least
+    max(0, 1 - sum_a (1 - m_a)).  NaN for a window whose marginals are NaN."""
+    i0 = np.asarray(i0, dtype=np.int64).reshape(-1, 3)
+    out = np.ones(i0.shape[0])
+    for a, m in enumerate((marg_x, marg_y, marg_z)):
+        m = np.asarray(m, dtype=np.float64).reshape(i0.shape[0], -1)
+        inside = np.array([m[e, i0[e, a]:i0[e, a] + widths[a]].sum() for e in range(i0.shape[0])])
+        out -= 1.0 - inside
+    return np.where(np.isnan(out), np.nan, np.maximum(out, 0.0))
+
+
+def box_faces(index, fine_grid, i0, widths, grid):
+    """(inner_face, outer_face) [E] of the best fine cells `index` within their boxes: whether the cell lies on a face of its
+    box that is not a face of the outer box `grid`, and whether it lies on a face of the outer box (False for index -1)"""
+    nf, n = grid_counts(fine_grid), grid_counts(grid)
+    i0 = np.asarray(i0, dtype=np.int64).reshape(-1, 3)
+    has = np.asarray(index, dtype=np.int64).reshape(-1) >= 0
+    f = _cell_ijk(index, nf)
+    inner, outer = np.zeros(has.size, dtype=bool), np.zeros(has.size, dtype=bool)
+    for a in range(3):
+        for on, at_outer in ((f[:, a] == 0, i0[:, a] == 0), (f[:, a] == nf[a] - 1, i0[:, a] + widths[a] == n[a])):
+            inner |= has & on & ~at_outer
+            outer |= has & on & at_outer
+    return inner, outer
+
+
+def refine(fwd, t_corr, vs, a_corr, qs, grid, factor, radius=2, prior=None, coarse=None, precision=None):
+    """Coarse to fine: the evaluation on `grid` (`locate`, or `locate_marginal` for draws as `locate_boxes`
+    tells them) unless its result is handed in as `coarse`, then `refine_boxes` about its best cells, then `locate_boxes` on
+    those boxes: cells of 1 / factor of the coarse size, 2 radius + 1 coarse cells per axis.  Returns the fine result
+    (`locate_boxes`' dict; `index` within the window's box) plus coarse_index [E], i0 [E][3] and widths, fine_grid, mass_bound
+    [E] (box_mass_bound; None when `coarse` has no marginals), inner_face [E] -- the best fine cell lies on a face of its box
+    that is not a face of the outer box: the box is too small, raise the radius -- and outer_face [E].  A window without an
+    included coarse cell comes back as a window without a cell (index -1, NaN): the coarse pass gave nothing to refine about.
+    The fine posterior is conditional on the box."""
+    if coarse is None:
+        coarse = (locate_marginal if _has_draws(t_corr, vs) else locate)(fwd, t_corr, vs, a_corr, qs, grid, prior=prior, precision=precision)
+    bx = refine_boxes(coarse["index"], grid, factor, radius)
+    res = locate_boxes(fwd, t_corr, vs, a_corr, qs, bx["fine_grid"], bx["origins"], prior=prior, precision=precision)
+    none = bx["none"]
+    if none.any():
+        res["index"] = np.where(none, -1, res["index"])
+        for key in ("best", "lp", "ell", "log_evidence", "mean", "cov", "marg_x", "marg_y", "marg_z", "vol"):
+            if res.get(key) is not None:
+                res[key][none] = np.nan
+        if res.get("loc") is not None:
+            res["loc"][none, 0], res["loc"][none, 1:] = -1.0, np.nan
+    inner, outer = box_faces(res["index"], bx["fine_grid"], bx["i0"], bx["widths"], grid)
+    mass = None if coarse.get("marg_x") is None else box_mass_bound(coarse["marg_x"], coarse["marg_y"], coarse["marg_z"], bx["i0"], bx["widths"])
+    if mass is not None:
+        mass = np.where(none, np.nan, mass)                # (nothing was refined: no box to speak of)
+    res.update(coarse_index=np.asarray(coarse["index"], dtype=np.int64).copy(), i0=bx["i0"], widths=bx["widths"], fine_grid=bx["fine_grid"],
+               mass_bound=mass, inner_face=inner, outer_face=outer)
+    return res
+
+
 JOBS = {"fixed": 0, "marginal": 1, "draw_evidence": 2}      # HTM_LOCATE_FIXED .. of include/htm_hip.h
 
 
-def plan(n_sta, n_events, grid, job="fixed", n_draws=0, volume=False, prior=False, n_layer=0, layer=False, precision="fp64", residuals=False):
+def plan(n_sta, n_events, grid, job="fixed", n_draws=0, volume=False, prior=False, n_layer=0, layer=False, precision="fp64", residuals=False,
+         boxes=False):
     """The workspace and the batches of a call of that shape under the HTM_LOCATE_MB of the environment, without a Forward and
     without a GPU (htm_forward_locate_plan, which states the formula): job "fixed" (`locate`), "marginal" (`locate_marginal`) or
     "draw_evidence" with n_draws; volume and prior: whether the call has them; n_layer >= 1: `stack`, with a layer per window
-    or not; residuals: `residuals` (job "fixed", no volume, no stack), whose dict alone has per_event's rbase, rpart, res and fit.
+    or not; residuals: `residuals` (job "fixed", no volume, no stack), whose dict alone has per_event's rbase, rpart, res and fit;
+    boxes: `locate_boxes` (jobs "fixed" and "marginal", no stack, no residuals), whose dict alone has per_event's org.
     Returns a dict: rows, tpl, stride, cells, n_tiles, n_marg, map_cells, n_draws, n_draws_padded; per_event and
     per_call, the elements of every device array by name; per_event_bytes, table_bytes, fixed_bytes; nb_limit [4] and nb, the
     events per batch.  A shape that the call would refuse raises HtmError with the call's message."""
@@ -257,7 +393,7 @@ def plan(n_sta, n_events, grid, job="fixed", n_draws=0, volume=False, prior=Fals
     if precision not in ("fp32", "fp64"):
         raise ValueError(f"locate precision {precision!r}: need 'fp32' or 'fp64'")
     rq = _lib.LocateRequest(int(n_sta), int(n_events), JOBS[job], int(n_draws), int(bool(volume)), int(bool(prior)), int(n_layer),
-                            int(bool(layer)), int(precision == "fp32"), int(bool(residuals)))
+                            int(bool(layer)), int(precision == "fp32"), int(bool(residuals)), int(bool(boxes)))
     g = np.ascontiguousarray(grid, dtype=np.float64).reshape(-1)
     if g.size != 9:
         raise ValueError(f"grid has {g.size} values: need x0, dx, nx, y0, dy, ny, z0, dz, nz")
@@ -269,6 +405,8 @@ def plan(n_sta, n_events, grid, job="fixed", n_draws=0, volume=False, prior=Fals
     d["per_call"] = {n: int(getattr(p, "len_" + n)) for n in _lib.LocatePlan.PER_CALL}
     if residuals:
         d["per_event"].update({n: int(getattr(p, "len_" + n)) for n in _lib.LocatePlan.RESIDUALS})
+    if boxes:
+        d["per_event"]["org"] = int(p.len_org)
     d["nb_limit"] = [int(v) for v in p.nb_limit]
     return d
 
@@ -296,16 +434,18 @@ def joint_draw_weights(log_z):
     return log_w, w / w.sum()
 
 
-def marginal_quantiles(marg, grid, levels=(0.025, 0.5, 0.975)):
+def marginal_quantiles(marg, grid, levels=(0.025, 0.5, 0.975), origin=None):
     """marg [E][nx + ny + nz] (or one row): the quantiles of the three axis marginals, [E][3][len(levels)].  On an axis the
     quantile q lies in the first cell k whose cumulative mass c_k reaches q, and linearly inside it:
-    v0 + dv (k + (q - c_{k-1}) / m_k).  A marginal of NaN gives NaN."""
+    v0 + dv (k + (q - c_{k-1}) / m_k).  A marginal of NaN gives NaN.  origin [E][3] (or one row): every event's own v0
+    (`locate_boxes`) in the place of the grid's."""
     g = grid9(grid)
     n = grid_counts(g)
     m = np.asarray(marg, dtype=np.float64)
     one = m.ndim == 1
     m = m.reshape(-1, sum(n))
     out = np.full((m.shape[0], 3, len(levels)), np.nan)
+    v0 = np.tile(g[0::3], (m.shape[0], 1)) if origin is None else np.asarray(origin, dtype=np.float64).reshape(m.shape[0], 3)
     off = 0
     for a in range(3):
         for e in range(m.shape[0]):
@@ -318,7 +458,7 @@ def marginal_quantiles(marg, grid, levels=(0.025, 0.5, 0.975)):
                 while k > 0 and ma[k] == 0.0:          # (rounding left the last cells' sum below q: the last cell with mass)
                     k -= 1
                 before = c[k - 1] if k > 0 else 0.0
-                out[e, a, j] = g[3 * a] + g[3 * a + 1] * (k + min((q - before) / ma[k], 1.0))
+                out[e, a, j] = v0[e, a] + g[3 * a + 1] * (k + min((q - before) / ma[k], 1.0))
         off += n[a]
     return out[0] if one else out
 
@@ -523,6 +663,35 @@ def stations_summary_text(win_id, names, res, t_stdv, a_stdv, use=(True, True)) 
     return "largest mean residual of a station over the located windows -- " + "; ".join(parts) + "\n"
 
 
+def refined_stat_text(win_id, fine) -> str:
+    """the text of <stem>.refined.stat from `refine`'s result: hypo.stat's layout from the fine marginals, every window's
+    quantiles from its own box's origin, behind a line that says what they are conditional on"""
+    marg = np.concatenate([fine["marg_x"], fine["marg_y"], fine["marg_z"]], axis=1)
+    return REFINED_STAT_HEADER + "\n" + stat_text(win_id, marginal_quantiles(marg, fine["fine_grid"], origin=fine["origin"]))
+
+
+def refined_best_text(win_id, fine) -> str:
+    """the text of <stem>.refined.best.dat from `refine`'s result: best.dat's columns on the fine grid (its flag: a face of the
+    window's own box), then the box's lower corner, mass_bound, inner_face, outer_face"""
+    lines = [BEST_HEADER + REFINED_BEST_TAIL]
+    for i, w in enumerate(win_id):
+        vals = list(fine["best"][i]) + [fine["lp"][i], fine["ell"][i], fine["log_evidence"][i]] + list(fine["mean"][i])
+        mass = np.nan if fine["mass_bound"] is None else fine["mass_bound"][i]
+        lines.append("%9d" % w + "".join(field(v, 15) for v in vals) + "%3d" % int(fine["inner_face"][i] or fine["outer_face"][i])
+                     + "".join(field(v, 15) for v in fine["origin"][i]) + field(mass, 13, 9) + "%3d%3d" % (int(fine["inner_face"][i]), int(fine["outer_face"][i])))
+    return "\n".join(lines) + "\n"
+
+
+def refined_summary_text(fine, factor, radius) -> str:
+    """the summary's line about the refinement"""
+    nf = grid_counts(fine["fine_grid"])
+    mass = fine["mass_bound"]
+    low = 0 if mass is None else int((mass < MASS_BOUND_LOW).sum())
+    return (f"refined by {factor} about the best cells (radius {radius}): boxes of {' x '.join(str(w) for w in fine['widths'])} coarse cells, "
+            f"{' x '.join(str(c) for c in nf)} fine cells; {int(np.sum(fine['inner_face']))} windows with the best fine cell on an inner face of their box "
+            f"(the box is too small: raise --refine-radius), {low} whose box is not known to hold {MASS_BOUND_LOW} of the coarse posterior's mass\n")
+
+
 def volume_text(vol, grid) -> str:
     """the text of hypo_grid.WIN.vol.dat from one window's vol [nz][ny][nx]: linear index, cell centre, log posterior"""
     nx, ny, nz = grid_counts(grid)
@@ -671,8 +840,9 @@ def _evaluate(r5, args, ids, grid, evaluate, structure, n_bins):
     """Everything the invocation computes of the windows `ids`, on one Forward; evaluate: `locate` or `locate_marginal`, structure:
     t_corr, vs, a_corr, qs as it takes them.  Returns (res, ev, resid, n_unresolved): the result that .stat and .best.dat are
     written from; draw_evidence's with --draw-weights; with --residuals (`residuals`' result, the windows' t_stdv, a_stdv); with
-    --stack-resolved the number of windows left out of the stack.  None for what was not asked for."""
-    ev = resid = n_unresolved = None
+    --stack-resolved the number of windows left out of the stack; with --refine `refine`'s result about the best cells of `res`,
+    the last call on the Forward.  None for what was not asked for."""
+    ev = resid = n_unresolved = fine = None
     with _forward(r5, args, ids) as (obs, fwd, prior):
         if args.stack:
             # one evaluation gives the maps and what the .stat and .best.dat files are written from; --stack-resolved needs
@@ -692,7 +862,9 @@ def _evaluate(r5, args, ids, grid, evaluate, structure, n_bins):
             res = evaluate(fwd, *structure, grid, prior=prior, volume=False)
         if args.draw_weights:
             ev = draw_evidence(fwd, *structure, grid, prior=prior)
-    return res, ev, resid, n_unresolved
+        if args.refine is not None:
+            fine = refine(fwd, *structure, grid, args.refine, args.refine_radius, prior=prior, coarse=res)
+    return res, ev, resid, n_unresolved, fine
 
 
 def _volume_of(r5, args, grid, evaluate, structure):
@@ -724,7 +896,18 @@ def main(argv=None):
     ap.add_argument("--level", type=float, nargs="+", metavar="P", help="with --stack: shares of a layer's mass for the regions (default 0.68 0.95)")
     ap.add_argument("--residuals", action="store_true", help="also write every station's residual per window, the windows' source terms and fit, "
                     "and the stations' mean residuals: hypo_grid.residuals.dat, .fit.dat and .stations.dat (a fixed structure: not with --draws)")
+    ap.add_argument("--refine", type=int, metavar="F", help="also evaluate every window on a box of its own about its best cell, in cells of 1 / F "
+                    "of the size (F >= 2): writes <stem>.refined.stat and <stem>.refined.best.dat")
+    ap.add_argument("--refine-radius", type=int, metavar="R", help="with --refine: the box reaches R cells to either side of the best cell (default 2)")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    if args.refine_radius is not None and args.refine is None:
+        ap.error("--refine-radius needs --refine F: it is the size of the refinement's boxes")
+    if args.refine is not None and args.refine < 2:
+        ap.error(f"--refine {args.refine}: need a factor of at least 2")
+    if args.refine_radius is not None and args.refine_radius < 0:
+        ap.error(f"--refine-radius {args.refine_radius}: need at least 0")
+    if args.refine_radius is None:
+        args.refine_radius = 2
     if args.residuals and args.draws is not None:
         ap.error("--residuals takes a fixed structure: the residuals under draws of the structure are not computed (leave out --draws)")
     if args.draws is not None and args.draws < 1:
@@ -755,7 +938,7 @@ def main(argv=None):
     if not win_id:
         raise SystemExit("ERROR: no window to locate")
 
-    res, ev, resid, n_unresolved = _evaluate(r5, args, win_id, grid, evaluate, (t_corr, vs, a_corr, qs), n_bins)
+    res, ev, resid, n_unresolved, fine = _evaluate(r5, args, win_id, grid, evaluate, (t_corr, vs, a_corr, qs), n_bins)
 
     def write(name, text):
         with open(os.path.join(work, stem + name), "w") as fh:
@@ -784,6 +967,10 @@ def main(argv=None):
         write(".draws.dat", draws_text(win_id, ev, records))
         write(".structure.dat", structure_text(records, vs, qs, ev["log_z"]))
         sys.stdout.write(draws_summary_text(ev, args.draws))
+    if fine is not None:
+        write(".refined.stat", refined_stat_text(win_id, fine))
+        write(".refined.best.dat", refined_best_text(win_id, fine))
+        sys.stdout.write(refined_summary_text(fine, args.refine, args.refine_radius))
 
 
 if __name__ == "__main__":

@@ -286,13 +286,33 @@ int htm_forward_locate_stack(htm_forward *h, int n_draws, const double *t_corr, 
 int htm_forward_locate_residuals(htm_forward *h, const double *t_corr, double vs, const double *a_corr, double qs,
                                  const double *grid9, const double *prior5, double *loc, double *marg, double *res, double *fit);
 
-/* THE WORKSPACE AND THE BATCHES of the five entry points above, worked out without a handle and without a device: what a call
+/* A BOX OF ITS OWN PER EVENT: htm_forward_locate (n_draws == 0: vs and qs point to one value each, t_corr,
+ * a_corr [n_sta]) or htm_forward_locate_marginal (1 <= n_draws <= 4096: their inputs) with every event on a grid of its own, in
+ * one launch per batch -- the fine pass of a coarse-to-fine refinement, whose boxes the caller chooses.  origin3 [n_events][3],
+ * host pointer, is ABSOLUTE: event e is evaluated on the grid {origin3[e][0], dx, nx, origin3[e][1], dy, ny, origin3[e][2], dz,
+ * nz}, the cell sizes and counts grid9's.  grid9's own three origins must pass the map grid's checks and are otherwise not read.
+ * THE RULE: for every event e, loc[e], marg[e] and vol[e] are bit for bit what htm_forward_locate (n_draws == 0) or
+ * htm_forward_locate_marginal returns in row e for the same handle, structure, precision setting and prior, with that event's
+ * grid as grid9.  So loc[e][0] is the cell's linear index WITHIN THE EVENT'S BOX, and loc[e][1..3] and [7..9] are absolute
+ * coordinates; the prior's tables are made per event on that event's grid; a posterior is conditional on the event's box.
+ * The origins travel with the batch: the result does not depend on HTM_LOCATE_MB, which counts 32 bytes more per event
+ * (htm_forward_locate_plan, `boxes`).  htm_forward_locate_set_precision applies.  The evidences of the draws, the stack and the
+ * residual pass take no boxes.
+ * Refused with HTM_EINVAL and a message before any device call: whatever those two entry points refuse, with their texts; a
+ * NULL origin3; an origin that is not finite (the message names the event and the axis).  Synchronous; every sum has a fixed
+ * order and there are no floating-point atomics: two calls give the same bits. */
+int htm_forward_locate_boxes(htm_forward *h, int n_draws, const double *t_corr, const double *vs, const double *a_corr,
+                             const double *qs, const double *grid9, const double *origin3, const double *prior5,
+                             double *loc, double *marg, double *vol);
+
+/* THE WORKSPACE AND THE BATCHES of the six entry points above, worked out without a handle and without a device: what a call
  * of that shape would allocate and how many events it would send at a time, or the refusal it would meet, with the same code
  * and text.  HTM_LOCATE_MB is read from the environment as a call reads it.  The request names what a call says through its
  * arguments: `job` 0 htm_forward_locate, 1 htm_forward_locate_marginal, 2 htm_forward_locate_draw_evidence (n_draws 0 for
  * job 0, 1..4096 otherwise); `volume`: vol is asked for; `prior`: prior5 is given; n_layer >= 1: htm_forward_locate_stack
  * (jobs 0 and 1; 0: no stack) with `layer` given or not; forward_fp32: htm_forward_locate_set_precision's setting;
- * `residuals`: htm_forward_locate_residuals (job 0, without `volume` and without a stack).
+ * `residuals`: htm_forward_locate_residuals (job 0, without `volume` and without a stack); `boxes`: htm_forward_locate_boxes
+ * (jobs 0 and 1 with or without `volume` and `prior`; without a stack and without `residuals`).
  * THE FORMULA, stated here once.  With cells = nx ny nz, n_marg = nx + ny + nz, rows = max(1, min(ny, 256, 4096 / nx)) x-rows
  * per tile, tpl = ceil(ny / rows) tiles per z-layer, n_tiles = nz tpl, stride = 4 + nx + 2 rows doubles per tile, Kpad = n_draws
  * padded to whole blocks of 8:
@@ -303,13 +323,15 @@ int htm_forward_locate_residuals(htm_forward *h, const double *t_corr, double vs
  *     with `residuals`, on top of job 0's:  8 (cells + 1 + (2 n_sta + 4) + n_rblk (2 n_sta + 6) + 4 n_sta + 10) -- the kept
  *     volume, the weight sum w, the residuals and sums at the best cell, the partial records of n_rblk = ceil(cells / 1024) blocks
  *     of cells, res and fit;
+ *     with `boxes`, on top of job 0's or 1's:  8 * 4 -- the event's box origin x0, y0, z0 and one unused, two aligned pairs;
  *   the draws' table, once per call (jobs 1, 2):  P (n_sta + 1) Kpad + 8 (2 n_sta + 2) n_draws, a pair P = 16 bytes, 8 with
  *     forward_fp32;
  *   the stack, once per call:  8 n_layer (cells + nx ny + nx nz + ny nz + 2) + 4 n_events where `layer` is given.
  * nb, the events of a batch, is the smallest of n_events and nb_limit[0..3]: 65535 (a launch's grid), (2^32 - 1) / (256
  * n_tiles) -- with `residuals` (2^32 - 1) / (256 max(n_tiles, n_rblk)) -- and (2^32 - 257) / n_sta (the work-items of a launch), and floor((HTM_LOCATE_MB 2^20 - table - stack) / per event),
  * itself at most 65535; and 1 at the least.  len_*: the elements of every device array, per event of a batch (sta .. w) and
- * once per call (dtc .. layer), and the residuals' per event of a batch (rbase .. fit); 0: the call has no such array.
+ * once per call (dtc .. layer), and the residuals' (rbase .. fit) and the boxes' (org) per event of a batch; 0: the call has no
+ * such array.
  * HTM_EINVAL, in this order: a NULL argument or a request that no entry point makes; a bad grid; more than 2^31 - 1 cells;
  * HTM_LOCATE_MB not positive; the draws' table and one event above it; n_layer (cells + nx ny + nx nz + ny nz + 2) above
  * 2^31 - 1; the stack, the table and one event above HTM_LOCATE_MB.  (A call checks the prior's widths after the cells.) */
@@ -323,6 +345,7 @@ typedef struct htm_locate_request {
     int32_t n_layer, layer;
     int32_t forward_fp32;
     int32_t residuals;                                /* htm_forward_locate_residuals (job 0, no volume, no stack) */
+    int32_t boxes;                                    /* htm_forward_locate_boxes (jobs 0 and 1, no stack, no residuals) */
 } htm_locate_request;
 typedef struct htm_locate_plan {
     int64_t rows, tpl, stride;
@@ -334,6 +357,7 @@ typedef struct htm_locate_plan {
     int64_t nb_limit[4];
     int64_t nb;
     int64_t len_rbase, len_rpart, len_res, len_fit;   /* per event of a batch, of a request with `residuals`; 0 otherwise */
+    int64_t len_org;                                  /* per event of a batch, of a request with `boxes`: 4; 0 otherwise */
 } htm_locate_plan;
 int htm_forward_locate_plan(const htm_locate_request *request, const double *grid9, htm_locate_plan *plan);
 
